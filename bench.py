@@ -84,8 +84,8 @@ def cpu_all_cores(batch, band, per_core, cores):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --mode hdp: 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; --mode hdp: 1)")
     ap.add_argument("--mode", choices=("posterior", "em", "hdp", "service"), default="posterior")
     ap.add_argument("--config", type=int, default=0,
                     help="BASELINE.json configs by number: 3 = --mode posterior (configs[2]), 4 = --mode em (configs[3]), "
@@ -126,6 +126,9 @@ def parse_args(argv=None):
                          "(4: 105 ms per iteration for 1024 C3 reads, 2: 110), 1 = one batch on the wave kernels (150)")
     ap.add_argument("--rehearse", action="store_true", help="no GPU: gloo ranks, host band geometry as the step")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-started workers")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode posterior: after the timed steps, write what the last one computed to DIR/<name>.npy "
+                         "(float64; every read's counts, the pairs and totals of a fixed seeded sample of reads)")
     args = ap.parse_args(argv)
     if args.config:
         args.mode = {3: "posterior", 4: "em", 5: "hdp"}.get(args.config) or sys.exit("--config takes 3, 4 or 5")
@@ -133,8 +136,18 @@ def parse_args(argv=None):
     if args.mode == "hdp":  # long reads: its own default sizes
         if "--reads" not in given:
             args.reads, args.events, args.kmers = 1024, 50000, 41500
-        if "--steps" not in given:
-            args.steps, args.warmup = 5, 1
+        if args.steps is None and args.warmup is None:
+            args.warmup = 1
+        if args.steps is None:
+            args.steps = 5
+    if args.steps is None:
+        args.steps = 20
+    if args.warmup is None:
+        args.warmup = 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.mode != "posterior" or args.rehearse):
+        ap.error("--dump-outputs writes the outputs of --mode posterior on the GPU")
     return args
 
 
@@ -156,6 +169,39 @@ def make_items(cp, bt):
         items[i] = (it["x_offset"], it["lX"], it["y_offset"], it["lY"], it["anchor_offset"],
                     it["n_anchors"], it["model"], 1, 1, 0)  # ragged ends, as vanillaAlign.c:203
     return items
+
+
+def dump_outputs(dirname, b, sample_reads=128, budget=64 * 10 ** 6 - 4096):
+    """What the caller of the timed path receives for the batch of the last timed step, as float64 .npy files under
+    dirname (every value is a double or an integer below 2**53, so nothing is rounded):
+      counts.npy        every read's [aligned pairs, totalProbability refreshes, in-band cells]
+      sample_reads.npy  a fixed seeded sample of the reads, ascending
+      pairs.npy         their aligned pairs, rows [read, floor(p * 1e7), x, y], in the order the library returns them
+      pairs_logp.npy    the (F+B)-total exponent of each pair
+      totals.npy        their totalProbability refreshes, rows [read, diagonal, value]
+    At most `budget` bytes in all: reads of the sample beyond it are left out of every file but counts.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    npairs, ntot, ncells = b.counts()
+    n = len(npairs)
+    sample = np.sort(np.random.default_rng(20240601).choice(n, size=min(n, sample_reads), replace=False))
+    left = budget - 3 * 8 * n
+    kept, pairs, logp, totals = [], [np.zeros((0, 4))], [np.zeros(0)], [np.zeros((0, 3))]
+    for i in sample:
+        need = 8 * (1 + 5 * int(npairs[i]) + 3 * int(ntot[i]))
+        if need > left:
+            break
+        left -= need
+        tri, lp = b.pairs(int(i), npairs[i])
+        xay, tot = b.totals(int(i), ntot[i])
+        kept.append(i)
+        pairs.append(np.column_stack([np.full(len(tri), i), tri]).astype(np.float64))
+        logp.append(lp.astype(np.float64))
+        totals.append(np.column_stack([np.full(len(xay), i), xay, tot]).astype(np.float64))
+    out = {"counts": np.stack([npairs, ntot, ncells], axis=1).astype(np.float64),
+           "sample_reads": np.array(kept, np.float64), "pairs": np.concatenate(pairs),
+           "pairs_logp": np.concatenate(logp), "totals": np.concatenate(totals)}
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def rehearse(args, rank, world):
@@ -356,6 +402,9 @@ def main(argv=None):
             dist.barrier()
             dist.destroy_process_group()
         return 0
+
+    if args.dump_outputs:  # before the single-batch measurement below closes or reruns any batch
+        dump_outputs(args.dump_outputs, bs[(args.steps - 1) % inflight])
 
     ms_per_step = 1e3 * elapsed / args.steps
     gcells = total_cells * args.steps / elapsed / 1e9

@@ -55,3 +55,65 @@ def test_command_line_contract():
     assert h.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--mode", "--inflight", "--single-steps"):
         assert flag in h.stdout
+
+
+def test_steps_and_warmup_are_what_the_command_line_says():
+    assert (bench.parse_args([]).steps, bench.parse_args([]).warmup) == (20, 3)
+    a = bench.parse_args(["--mode", "hdp"])
+    assert (a.steps, a.warmup) == (5, 1)
+    for argv in (["--mode", "hdp", "--steps=7", "--warmup=2"], ["--mode", "hdp", "--steps", "7", "--warmup", "2"],
+                 ["--steps", "7", "--warmup", "2"]):
+        a = bench.parse_args(argv)
+        assert (a.steps, a.warmup) == (7, 2), argv
+
+
+class _FakeBatch:
+    """the three result calls of binding.Batch that dump_outputs uses, on made-up per-read results"""
+
+    def __init__(self, n, pairs_per_read):
+        rng = np.random.default_rng(7)
+        self.np = np.full(n, pairs_per_read, np.int64)
+        self.nt = rng.integers(0, 5, n)
+        self.tri = [rng.integers(0, 10 ** 7, (pairs_per_read, 3)) for _ in range(n)]
+        self.lp = [rng.standard_normal(pairs_per_read) for _ in range(n)]
+        self.tot = [(rng.integers(0, 10 ** 4, k), rng.standard_normal(k)) for k in self.nt]
+
+    def counts(self):
+        return self.np, self.nt, 10 * self.np
+
+    def pairs(self, i, n):
+        assert n == self.np[i]
+        return self.tri[i], self.lp[i]
+
+    def totals(self, i, n):
+        assert n == self.nt[i]
+        return self.tot[i]
+
+
+def test_dump_outputs_writes_float64_arrays_of_a_fixed_sample(tmp_path):
+    fb = _FakeBatch(300, 40)
+    bench.dump_outputs(str(tmp_path / "a"), fb)
+    bench.dump_outputs(str(tmp_path / "b"), fb)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["counts.npy", "pairs.npy", "pairs_logp.npy", "sample_reads.npy", "totals.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    reads = np.load(tmp_path / "a" / "sample_reads.npy").astype(int)
+    assert len(reads) == 128 and np.all(np.diff(reads) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "counts.npy")[:, 0], fb.np)
+    pairs = np.load(tmp_path / "a" / "pairs.npy")
+    assert np.array_equal(pairs[:, 1:], np.concatenate([fb.tri[i] for i in reads]))
+    assert np.array_equal(pairs[:, 0], np.repeat(reads, 40))
+    assert np.array_equal(np.load(tmp_path / "a" / "pairs_logp.npy"), np.concatenate([fb.lp[i] for i in reads]))
+    totals = np.load(tmp_path / "a" / "totals.npy")
+    assert np.array_equal(totals[:, 2], np.concatenate([fb.tot[i][1] for i in reads]))
+
+
+def test_dump_outputs_stays_within_its_budget(tmp_path):
+    fb = _FakeBatch(50, 1000)
+    bench.dump_outputs(str(tmp_path), fb, budget=200000)
+    size = sum(os.path.getsize(tmp_path / n) for n in os.listdir(tmp_path))
+    reads = np.load(tmp_path / "sample_reads.npy").astype(int)
+    assert size <= 200000 + 4096 and 0 < len(reads) < 50
+    assert len(np.load(tmp_path / "pairs.npy")) == 1000 * len(reads)
