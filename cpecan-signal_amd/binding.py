@@ -445,7 +445,10 @@ class Batch:
         self.hdp = bool(hdp) and not self.dna
 
     def run(self, after=None):
-        """after: a Batch of another context -- this batch's kernels start when that one's last run has finished"""
+        """after: a Batch that has run (usually of another context): this batch's kernels are ordered behind its last
+        run on the device -- behind its last forward sweep if it runs on the wave kernels as one stream group, behind
+        the whole run otherwise.  Read `after`'s results through its own sync() or readback (counts, pairs, totals),
+        not because this batch has finished."""
         if after is None:
             _check(lib().cpecan_hip_batch_run(self.h))
         else:

@@ -5,6 +5,7 @@
  */
 #include "cpecan_asm.h"
 
+#include <algorithm>
 #include <mutex>
 
 namespace {
@@ -116,42 +117,42 @@ extern "C" __global__ void cpecan_k_asm_ctx_init(const DevItem *items, long long
 
 /* The mask table of one batch: one thread per diagonal. */
 extern "C" __global__ void cpecan_k_asm_masks(const DevItem *items, long long nItems, const int *bandTab, unsigned *maskTab) {
-    const long long idx = blockIdx.y;
-    if (idx >= nItems) return;
-    const DevItem it = items[idx];
-    const long long d = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (d > it.lX + it.lY) return;
-    const int lo = bandTab[2 * (it.diagBase + d)], hi = bandTab[2 * (it.diagBase + d) + 1];
-    unsigned long long m[ASM_L], g[ASM_L];
-    for (int j = 0; j < ASM_L; j++) m[j] = g[j] = 0ull;
-    for (int x = lo - 1; x <= hi + 1; x++) { /* (column -1: the last slot, parked while the band starts at column 0) */
-        const int s = (x + 64 * ASM_L) % (64 * ASM_L);
-        g[s % ASM_L] |= ((1ull << ASM_MASK_GROUP) - 1) << ((s / ASM_L) & ~(ASM_MASK_GROUP - 1)); /* whole 128-byte lines (every
-                                                                 access of a ring row is 16 bytes per lane): no partial writes */
-        if (x >= lo && x <= hi) m[s % ASM_L] |= 1ull << (s / ASM_L);
+    for (long long idx = blockIdx.y; idx < nItems; idx += gridDim.y) { /* grid.y is capped at 65535 */
+        const DevItem it = items[idx];
+        const long long d = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+        if (d > it.lX + it.lY) continue;
+        const int lo = bandTab[2 * (it.diagBase + d)], hi = bandTab[2 * (it.diagBase + d) + 1];
+        unsigned long long m[ASM_L], g[ASM_L];
+        for (int j = 0; j < ASM_L; j++) m[j] = g[j] = 0ull;
+        for (int x = lo - 1; x <= hi + 1; x++) { /* (column -1: the last slot, parked while the band starts at column 0) */
+            const int s = (x + 64 * ASM_L) % (64 * ASM_L);
+            g[s % ASM_L] |= ((1ull << ASM_MASK_GROUP) - 1) << ((s / ASM_L) & ~(ASM_MASK_GROUP - 1)); /* whole 128-byte lines (every
+                                                                     access of a ring row is 16 bytes per lane): no partial writes */
+            if (x >= lo && x <= hi) m[s % ASM_L] |= 1ull << (s / ASM_L);
+        }
+        unsigned *e = maskTab + (it.diagBase + d) * (ASM_MASK_BYTES / 4);
+        for (int j = 0; j < ASM_L; j++) {
+            e[2 * j] = (unsigned) m[j];
+            e[2 * j + 1] = (unsigned) (m[j] >> 32);
+            e[8 + 2 * j] = (unsigned) g[j];
+            e[9 + 2 * j] = (unsigned) (g[j] >> 32);
+        }
+        e[6] = (unsigned) lo;
+        e[7] = (unsigned) hi;
+        /* the last layer's 8-byte emissions: 16 lanes to a line */
+        unsigned long long h = 0ull;
+        for (int q = 0; q < 64; q += 16)
+            if (g[ASM_L - 1] & (0xFFFFull << q)) h |= 0xFFFFull << q;
+        e[14] = (unsigned) h;
+        e[15] = (unsigned) (h >> 32);
     }
-    unsigned *e = maskTab + (it.diagBase + d) * (ASM_MASK_BYTES / 4);
-    for (int j = 0; j < ASM_L; j++) {
-        e[2 * j] = (unsigned) m[j];
-        e[2 * j + 1] = (unsigned) (m[j] >> 32);
-        e[8 + 2 * j] = (unsigned) g[j];
-        e[9 + 2 * j] = (unsigned) (g[j] >> 32);
-    }
-    e[6] = (unsigned) lo;
-    e[7] = (unsigned) hi;
-    /* the last layer's 8-byte emissions: 16 lanes to a line */
-    unsigned long long h = 0ull;
-    for (int q = 0; q < 64; q += 16)
-        if (g[ASM_L - 1] & (0xFFFFull << q)) h |= 0xFFFFull << q;
-    e[14] = (unsigned) h;
-    e[15] = (unsigned) (h >> 32);
 }
 
-extern "C" int cpecan_asm_launch_masks(hipStream_t stream, const DevItem *items, long long nItems, long long maxDiags,
-                                       const int *bandTab, unsigned *maskTab) {
-    hipLaunchKernelGGL(cpecan_k_asm_masks, dim3((unsigned) ((maxDiags + 255) / 256), (unsigned) nItems), dim3(256), 0, stream, items,
-                       nItems, bandTab, maskTab);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+extern "C" hipError_t cpecan_asm_launch_masks(hipStream_t stream, const DevItem *items, long long nItems, long long maxDiags,
+                                              const int *bandTab, unsigned *maskTab) {
+    hipLaunchKernelGGL(cpecan_k_asm_masks, dim3((unsigned) ((maxDiags + 255) / 256), (unsigned) std::min(nItems, 65535LL)),
+                       dim3(256), 0, stream, items, nItems, bandTab, maskTab);
+    return hipGetLastError();
 }
 
 /* Ring row 0: cell (0, 0) as the forward kernel of cpecan_kernel_wave.hip leaves it. */
@@ -166,11 +167,11 @@ extern "C" __global__ void cpecan_k_asm_begin(const DevItem *items, long long nI
     r[ASM_OFF_FXY / 8] = r[ASM_OFF_FXY / 8 + 1] = it.raggedL ? 0.0 : CP_NEG_INF; /* Fx, Fy */
 }
 
-extern "C" int cpecan_asm_launch_ctx_init(hipStream_t stream, const DevItem *items, long long nItems, char *ctx,
-                                          long long ctxBytes, double *ring, long long ringDoubles, int ringD) {
+extern "C" hipError_t cpecan_asm_launch_ctx_init(hipStream_t stream, const DevItem *items, long long nItems, char *ctx,
+                                                 long long ctxBytes, double *ring, long long ringDoubles, int ringD) {
     hipLaunchKernelGGL(cpecan_k_asm_ctx_init, dim3((unsigned) nItems), dim3(64), 0, stream, items, nItems, ctx, ctxBytes,
                        ring, ringDoubles, ringD);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return hipGetLastError();
 }
 
 extern "C" int cpecan_asm_launch_begin(hipStream_t stream, const DevItem *items, long long nItems, double *ring,

@@ -556,6 +556,7 @@ struct cpecan_batch {
      * contexts */
     bool useAsm = false, asmBackward = false;
     int asmMaxWindows = 0;
+    std::string asmSetupError; /* why a batch planned for them does not run on them (a failed setup launch) */
     DevBuf<AsmPlanWin> planWin;
     DevBuf<AsmPlanCtl> planCtl;
     DevBuf<long long> planOff;
@@ -1632,13 +1633,19 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
             B_TRY(hipMemcpyAsync(b->planWin.p, hWin.p, hWin.n * sizeof(AsmPlanWin), hipMemcpyHostToDevice, c->prep));
             B_TRY(hipMemcpyAsync(b->planCtl.p, hCtl.p, (size_t) ctlTotal * sizeof(AsmPlanCtl), hipMemcpyHostToDevice, c->prep));
             B_TRY(hipMemcpyAsync(b->planOff.p, hPlanOff.data(), (size_t) nItems * sizeof(long long), hipMemcpyHostToDevice, c->prep));
-            if (cpecan_asm_launch_masks(c->prep, b->items.p, nItems, maxDiags, b->bandTab.p, b->asmMasks.p) != 0 ||
-                cpecan_asm_launch_ctx_init(c->prep, b->items.p, nItems, b->asmCtx.p, ASM_CTX_BYTES, b->Fstore.p, b->ringDoubles,
-                                           b->ringD) != 0) {
-                cpecan_hip_batch_destroy(b);
-                return fail(CPECAN_EHIP, "context kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-            }
+            hipError_t asmErr = cpecan_asm_launch_masks(c->prep, b->items.p, nItems, maxDiags, b->bandTab.p, b->asmMasks.p);
+            if (asmErr == hipSuccess)
+                asmErr = cpecan_asm_launch_ctx_init(c->prep, b->items.p, nItems, b->asmCtx.p, ASM_CTX_BYTES, b->Fstore.p,
+                                                    b->ringDoubles, b->ringD);
             B_TRY(hipStreamSynchronize(c->prep)); /* hWin ends here */
+            if (asmErr != hipSuccess) {
+                /* the compiled kernels need none of this: the batch runs on them (cpecan_hip_batch_assembly_sweeps
+                 * reports 0 and leaves the reason in last_error) */
+                b->asmSetupError = std::string("assembly sweeps not set up: ") + hipGetErrorString(asmErr);
+                if (getenv("CPECAN_ASM_TRACE")) fprintf(stderr, "[cpecan asm] %s\n", b->asmSetupError.c_str());
+            }
+        }
+        if (b->asmMaxWindows > 0 && b->asmSetupError.empty()) {
             if (b->ringD >= 3 * maxSpan + 8 || maxWindows <= 2) {
                 /* the post kernel of a window runs beside the next window's sweeps (batch_run): the sweep back of window
                  * w+1 fills one half of the scratch while the post kernel of window w reads the other */
@@ -2051,6 +2058,7 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
 int cpecan_hip_batch_assembly_sweeps(cpecan_batch *b, int32_t *sweeps) {
     if (!b || !sweeps) return fail(CPECAN_EINVAL, "bad argument");
     *sweeps = b->useAsm ? (b->asmBackward ? 2 : 1) : 0;
+    if (!b->asmSetupError.empty()) g_err = b->asmSetupError;
     return CPECAN_OK;
 }
 

@@ -1432,18 +1432,18 @@ extern "C" __global__ void cpecan_k_track(const DevItem *__restrict__ items, lon
                                           const long long *__restrict__ trackBase,
                                           const unsigned short *__restrict__ kidx,
                                           const double *__restrict__ models, double *track) {
-    const long long item = blockIdx.y;
-    if (item >= nItems) return;
-    const DevItem it = items[item];
-    const double *rows = models + (long long) it.model * CP_MODEL_STRIDE + CP_MODEL_HEADER;
-    const long long n = (it.lX + 1) * CP_ROW;
-    double *dst = track + trackBase[item] * CP_ROW;
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long) gridDim.x * blockDim.x) {
-        const long long x = i / CP_ROW;
-        const int j = (int) (i - x * CP_ROW);
-        const int k = x == 0 ? 4096 : (int) kidx[it.xOff + x - 1];
-        dst[i] = rows[(long long) k * CP_ROW + j];
+    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
+        const DevItem it = items[item];
+        const double *rows = models + (long long) it.model * CP_MODEL_STRIDE + CP_MODEL_HEADER;
+        const long long n = (it.lX + 1) * CP_ROW;
+        double *dst = track + trackBase[item] * CP_ROW;
+        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+             i += (long long) gridDim.x * blockDim.x) {
+            const long long x = i / CP_ROW;
+            const int j = (int) (i - x * CP_ROW);
+            const int k = x == 0 ? 4096 : (int) kidx[it.xOff + x - 1];
+            dst[i] = rows[(long long) k * CP_ROW + j];
+        }
     }
 }
 
@@ -1515,7 +1515,7 @@ extern "C" int cpecan_systolic_launch_track(hipStream_t stream, const DevItem *i
                                             void *states, int maxLX) {
     int bx = (int) ((((long long) maxLX + 1) * CP_ROW + 255) / 256);
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_track, dim3(bx, (unsigned) nItems), dim3(256), 0, stream, items,
+    hipLaunchKernelGGL(cpecan_k_track, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items,
                        nItems, trackBase, kidx, models, (double *) track);
     if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(SyState), stream) != hipSuccess) return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;

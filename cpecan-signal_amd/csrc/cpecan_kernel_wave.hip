@@ -2144,26 +2144,26 @@ extern "C" __global__ void cpecan_k_wv_track(const DevItem *__restrict__ items, 
                                              const long long *__restrict__ trackBase,
                                              const unsigned short *__restrict__ kidx,
                                              const double *__restrict__ models, double *track) {
-    const long long item = blockIdx.y;
-    if (item >= nItems) return;
-    const DevItem it = items[item];
-    const double *model = models + (long long) it.model * CP_MODEL_STRIDE;
-    const double *rows = model + CP_MODEL_HEADER;
-    const long long n = (it.lX + 1) * WV_ROW;
-    double *dst = track + trackBase[item] * WV_ROW;
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long) gridDim.x * blockDim.x) {
-        const long long x = i / WV_ROW;
-        const int jj = (int) (i - x * WV_ROW);
-        const int k = x == 0 ? 4096 : (int) kidx[it.xOff + x - 1];
-        const double *r = rows + (long long) k * CP_ROW;
-        double v;
-        if (jj < 16) v = r[jj];
-        else if (jj == 16) v = r[CP_GAPX] + model[T_GAP_OPEN_X];
-        else if (jj == 17) v = r[CP_GAPX] + model[T_GAP_EXTEND_X];
-        else if (jj == 18) v = r[CP_GAPX] + model[T_GAP_SWITCH_TO_X];
-        else v = r[CP_GAPX];
-        dst[i] = v;
+    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
+        const DevItem it = items[item];
+        const double *model = models + (long long) it.model * CP_MODEL_STRIDE;
+        const double *rows = model + CP_MODEL_HEADER;
+        const long long n = (it.lX + 1) * WV_ROW;
+        double *dst = track + trackBase[item] * WV_ROW;
+        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+             i += (long long) gridDim.x * blockDim.x) {
+            const long long x = i / WV_ROW;
+            const int jj = (int) (i - x * WV_ROW);
+            const int k = x == 0 ? 4096 : (int) kidx[it.xOff + x - 1];
+            const double *r = rows + (long long) k * CP_ROW;
+            double v;
+            if (jj < 16) v = r[jj];
+            else if (jj == 16) v = r[CP_GAPX] + model[T_GAP_OPEN_X];
+            else if (jj == 17) v = r[CP_GAPX] + model[T_GAP_EXTEND_X];
+            else if (jj == 18) v = r[CP_GAPX] + model[T_GAP_SWITCH_TO_X];
+            else v = r[CP_GAPX];
+            dst[i] = v;
+        }
     }
 }
 extern "C" int cpecan_wave_launch_track(hipStream_t stream, const DevItem *items, long long nItems,
@@ -2171,7 +2171,7 @@ extern "C" int cpecan_wave_launch_track(hipStream_t stream, const DevItem *items
                                         const unsigned short *kidx, const double *models, void *states, int maxLX) {
     int bx = (int) ((((long long) maxLX + 1) * WV_ROW + 255) / 256);
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_wv_track, dim3(bx, (unsigned) nItems), dim3(256), 0, stream, items, nItems,
+    hipLaunchKernelGGL(cpecan_k_wv_track, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items, nItems,
                        trackBase, kidx, models, (double *) track);
     if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(WvState), stream) != hipSuccess) return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -2221,40 +2221,40 @@ extern "C" __global__ void cpecan_k_wv_track_vanilla(const DevItem *__restrict__
                                                      const long long *__restrict__ trackBase,
                                                      const unsigned short *__restrict__ kidx,
                                                      const double *__restrict__ models, double *track) {
-    const long long item = blockIdx.y;
-    if (item >= nItems) return;
-    const DevItem it = items[item];
-    const double *hdr = models + (long long) it.model * CP_VMODEL_STRIDE;
-    const double *rows = hdr + CP_VHDR;
-    const long long n = (it.lX + 1) * WV_ROW;
-    double *dst = track + trackBase[item] * WV_ROW;
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long) gridDim.x * blockDim.x) {
-        const long long x = i / WV_ROW;
-        const int jj = (int) (i - x * WV_ROW);
-        const long long p = x > 2 ? x - 2 : 0;
-        const int kPrev = kidx[it.xOff + p], kCur = kidx[it.xOff + p + 1];
-        const double *r = rows + (long long) kCur * CP_VROW;
-        double v = 0.0;
-        if (jj < 16) {
-            const double *q = r + 6 * (jj >> 3);
-            switch (jj & 7) {
-            case 0: v = q[CP_V_MU]; break;
-            case 1: v = q[CP_V_SD]; break;
-            case 2: v = q[CP_V_SD] == 0.0 ? 0.0 : 1.0 / q[CP_V_SD]; break;
-            case 3: v = q[CP_V_K]; break;
-            case 4: v = q[CP_V_NMU]; break;
-            case 5: v = 1.0 / q[CP_V_NMU]; break;
-            case 6: v = q[CP_V_LAMBDA]; break;
-            default: v = q[CP_V_LLAMBDA] - 1.8378770664093453; break;
+    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
+        const DevItem it = items[item];
+        const double *hdr = models + (long long) it.model * CP_VMODEL_STRIDE;
+        const double *rows = hdr + CP_VHDR;
+        const long long n = (it.lX + 1) * WV_ROW;
+        double *dst = track + trackBase[item] * WV_ROW;
+        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+             i += (long long) gridDim.x * blockDim.x) {
+            const long long x = i / WV_ROW;
+            const int jj = (int) (i - x * WV_ROW);
+            const long long p = x > 2 ? x - 2 : 0;
+            const int kPrev = kidx[it.xOff + p], kCur = kidx[it.xOff + p + 1];
+            const double *r = rows + (long long) kCur * CP_VROW;
+            double v = 0.0;
+            if (jj < 16) {
+                const double *q = r + 6 * (jj >> 3);
+                switch (jj & 7) {
+                case 0: v = q[CP_V_MU]; break;
+                case 1: v = q[CP_V_SD]; break;
+                case 2: v = q[CP_V_SD] == 0.0 ? 0.0 : 1.0 / q[CP_V_SD]; break;
+                case 3: v = q[CP_V_K]; break;
+                case 4: v = q[CP_V_NMU]; break;
+                case 5: v = 1.0 / q[CP_V_NMU]; break;
+                case 6: v = q[CP_V_LAMBDA]; break;
+                default: v = q[CP_V_LLAMBDA] - 1.8378770664093453; break;
+                }
+            } else {
+                const double d = fabs(r[CP_V_MU] - rows[(long long) kPrev * CP_VROW + CP_V_MU]);
+                long long bin = (long long) (d / 0.5);
+                if (bin >= 30) bin = 29;
+                v = jj < 21 ? hdr[CP_VHDR_BINS + bin * 5 + (jj - 16)] : (double) bin; /* (entry 21: the bin itself, E-step) */
             }
-        } else {
-            const double d = fabs(r[CP_V_MU] - rows[(long long) kPrev * CP_VROW + CP_V_MU]);
-            long long bin = (long long) (d / 0.5);
-            if (bin >= 30) bin = 29;
-            v = jj < 21 ? hdr[CP_VHDR_BINS + bin * 5 + (jj - 16)] : (double) bin; /* (entry 21: the bin itself, E-step) */
+            dst[i] = v;
         }
-        dst[i] = v;
     }
 }
 extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const DevItem *items, long long nItems,
@@ -2263,7 +2263,7 @@ extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const DevIte
                                                 int maxLX) {
     int bx = (int) ((((long long) maxLX + 1) * WV_ROW + 255) / 256);
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_wv_track_vanilla, dim3(bx, (unsigned) nItems), dim3(256), 0, stream, items, nItems,
+    hipLaunchKernelGGL(cpecan_k_wv_track_vanilla, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items, nItems,
                        trackBase, kidx, models, (double *) track);
     if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(WvState), stream) != hipSuccess) return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -2279,26 +2279,26 @@ extern "C" __global__ void cpecan_k_wv_track_hdp(const DevItem *__restrict__ ite
                                                  const long long *__restrict__ trackBase,
                                                  const int *__restrict__ kid, const DevHdpModel *__restrict__ models,
                                                  double *track) {
-    const long long item = blockIdx.y;
-    if (item >= nItems) return;
-    const DevItem it = items[item];
-    const DevHdpModel &m = models[it.model];
-    const long long n = (it.lX + 1) * WV_ROW;
-    double *dst = track + trackBase[item] * WV_ROW;
-    const double px = -2.3025850929940455;
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long) gridDim.x * blockDim.x) {
-        const long long x = i / WV_ROW;
-        const int jj = (int) (i - x * WV_ROW);
-        double v = 0.0;
-        if (jj == 0) {
-            const int id = kid[it.xOff + (x > 0 ? x - 1 : 0)];
-            v = id < 0 ? -1.0 : (double) ((long long) m.kmerRow[id] * m.gridLength);
-        } else if (jj == 16) v = px + m.t[T_GAP_OPEN_X];
-        else if (jj == 17) v = px + m.t[T_GAP_EXTEND_X];
-        else if (jj == 18) v = px + m.t[T_GAP_SWITCH_TO_X];
-        else if (jj == 19) v = px;
-        dst[i] = v;
+    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
+        const DevItem it = items[item];
+        const DevHdpModel &m = models[it.model];
+        const long long n = (it.lX + 1) * WV_ROW;
+        double *dst = track + trackBase[item] * WV_ROW;
+        const double px = -2.3025850929940455;
+        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+             i += (long long) gridDim.x * blockDim.x) {
+            const long long x = i / WV_ROW;
+            const int jj = (int) (i - x * WV_ROW);
+            double v = 0.0;
+            if (jj == 0) {
+                const int id = kid[it.xOff + (x > 0 ? x - 1 : 0)];
+                v = id < 0 ? -1.0 : (double) ((long long) m.kmerRow[id] * m.gridLength);
+            } else if (jj == 16) v = px + m.t[T_GAP_OPEN_X];
+            else if (jj == 17) v = px + m.t[T_GAP_EXTEND_X];
+            else if (jj == 18) v = px + m.t[T_GAP_SWITCH_TO_X];
+            else if (jj == 19) v = px;
+            dst[i] = v;
+        }
     }
 }
 extern "C" int cpecan_wave_launch_track_hdp(hipStream_t stream, const DevItem *items, long long nItems,
@@ -2306,7 +2306,7 @@ extern "C" int cpecan_wave_launch_track_hdp(hipStream_t stream, const DevItem *i
                                             const void *models, void *states, int maxLX) {
     int bx = (int) ((((long long) maxLX + 1) * WV_ROW + 255) / 256);
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_wv_track_hdp, dim3(bx, (unsigned) nItems), dim3(256), 0, stream, items, nItems,
+    hipLaunchKernelGGL(cpecan_k_wv_track_hdp, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items, nItems,
                        trackBase, kid, (const DevHdpModel *) models, (double *) track);
     if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(WvState), stream) != hipSuccess) return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -262,8 +262,12 @@ int cpecan_hip_batch_create_hdp(cpecan_ctx *ctx, const cpecan_item *items, int64
                                 const cpecan_band_params *params, int32_t flags, cpecan_batch **out);
 
 int cpecan_hip_batch_run(cpecan_batch *batch);
-/* The same, but the batch's kernels start when the last run of `after` (a batch of another context on the same device;
- * NULL: no condition) has finished -- ordered on the device, no host round trip.  A stream of batches then keeps the
+/* The same, but ordered on the device behind the last run of `after` (a batch on the same device; NULL, the batch
+ * itself or a batch that has never run: no condition), with no host round trip.  What is ordered: if `after` runs on
+ * the wave-per-alignment kernels as one stream group, this batch's kernels start when `after`'s last forward sweep has
+ * finished (its sweeps back, decode and pair packing may still be running); otherwise when `after`'s whole run has
+ * finished.  Either way `after`'s results are read through `after`'s own cpecan_hip_batch_sync or readback
+ * (counts, pairs, totals), never on the strength of this batch having finished.  A stream of batches then keeps the
  * device busy with one pass at a time (the wave-per-alignment kernels fill the register files with one batch) while
  * the host fetches and finishes the previous batch's pairs and prepares the next one. */
 int cpecan_hip_batch_run_after(cpecan_batch *batch, cpecan_batch *after);
@@ -288,7 +292,8 @@ int cpecan_hip_batch_systolic_rows(cpecan_batch *batch, int32_t *rows);
 int cpecan_hip_batch_kernel_family(cpecan_batch *batch, int32_t *wave);
 /* *sweeps = 1 if the batch's sweeps run on the hand-scheduled assembly kernels (strawMan machine, posterior decode,
  * bands of 121..158 k-mers: the BASELINE configs[2] shape), 2 if both the forward and the backward sweep do, 0 if on
- * the compiled kernels.  CPECAN_ASM=0 in the environment keeps every batch on the compiled kernels. */
+ * the compiled kernels.  CPECAN_ASM=0 in the environment keeps every batch on the compiled kernels.  A batch planned for
+ * them whose setup launch failed runs on the compiled kernels: 0, and last_error says why. */
 int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
 /* Systolic path only: HIP-event time of the last run spent in the forward-window kernels and in
  * the backward-window kernels (each launched `launches_each` times, once per traceback window). */

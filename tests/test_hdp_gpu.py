@@ -15,7 +15,7 @@ import pytest
 
 import pyoracle as o
 import synth
-from harness import assert_same_pairs, band_params, cp, make_items, orc_params
+from harness import assert_same_pairs, band_params, cp, hdp_batch, make_items, orc_params
 
 pytestmark = pytest.mark.gpu
 
@@ -30,31 +30,6 @@ def ctx():
 @pytest.fixture(scope="module")
 def nhdp(golden_dir):
     return o.load_nhdp(os.path.join(golden_dir, "testTemplate.nhdp"))
-
-
-def hdp_batch(seed, n, lX, every, nhdp):
-    """reads whose event means are drawn around the mode of each k-mer's HDP density"""
-    rng = np.random.default_rng(seed)
-    model = o.HdpModel(nhdp)
-    xs, evs, ans, items = "", [], [], []
-    for _ in range(n):
-        x = "".join(rng.choice(list("ACGT"), lX + 5))
-        ev, anchors = [], []
-        for k in range(lX):
-            row = nhdp["kmer_row"][model.kmer_id(x[k:k + 6])]
-            mode = nhdp["grid"][int(np.argmax(nhdp["y"][row]))]
-            if rng.random() < 0.1:
-                continue                                   # skipped k-mer
-            if k % every == 0:
-                anchors.append((k, len(ev)))
-            for _ in range(1 + rng.geometric(0.6) - 1 if rng.random() < 0.5 else 1):
-                ev.append((mode + rng.normal(0, 1.0), abs(rng.normal(1.0, 0.2)) + 1e-3, 0.01))
-        items.append(dict(x_offset=len(xs), lX=lX, y_offset=sum(len(e) for e in evs), lY=len(ev),
-                          anchor_offset=sum(len(a) for a in ans), n_anchors=len(anchors), model=0))
-        xs += x
-        evs.append(np.array(ev))
-        ans.append(np.array(anchors, np.int64).reshape(-1, 2))
-    return dict(x_chars=xs, events=np.concatenate(evs), anchors=np.concatenate(ans), items=items), model
 
 
 @pytest.mark.parametrize("general", [False, True], ids=["wave", "general"])
