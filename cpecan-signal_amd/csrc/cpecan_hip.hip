@@ -154,6 +154,17 @@ SY_DECLARE(_r3)
 WV_DECLARE(_l2)
 WV_DECLARE(_l3)
 WV_DECLARE(_l4)
+/* the strawMan machine's E-step with the expectations summed inside the sweep back (cpecan_kernel_wave.hip) */
+#define WV_DECLARE_FX(sfx)                                                                                        \
+    extern "C" long long cpecan_wave_fx_scratch_bytes##sfx(int ringD);                                            \
+    extern "C" int cpecan_wave_launch_backward_fx##sfx(hipStream_t, const DevItem *, long long, DevParams,        \
+                                                       const void *, const double *, const long long *,           \
+                                                       const double *, double *, long long, int, void *,          \
+                                                       long long *, double *, char *, long long, double *,        \
+                                                       const unsigned short *, int, int);
+WV_DECLARE_FX(_l2)
+WV_DECLARE_FX(_l3)
+WV_DECLARE_FX(_l4)
 /* ... and the same sweeps for the HDP signal machine (-DWV_HDP, symbols _h2.._h4) */
 WV_DECLARE(_h2)
 WV_DECLARE(_h3)
@@ -224,6 +235,14 @@ static const SyBuild SY_BUILDS[4] = { SY_BUILD(1, _r1), SY_BUILD(2, _r2), SY_BUI
 static const SyBuild WV_BUILDS[4] = { WV_BUILD(2, _l2), WV_BUILD(2, _l2), WV_BUILD(3, _l3), WV_BUILD(4, _l4) };
 static const SyBuild HV_BUILDS[4] = { WV_BUILD(2, _h2), WV_BUILD(2, _h2), WV_BUILD(3, _h3), WV_BUILD(4, _h4) };
 static const SyBuild VV_BUILDS[4] = { WV_BUILD(2, _v2), WV_BUILD(2, _v2), WV_BUILD(3, _v3), WV_BUILD(3, _v3) };
+struct FxBuild { /* fused expectations: the extra scratch and the launch, per build of WV_BUILDS */
+    long long (*scratch_bytes)(int);
+    decltype(&cpecan_wave_launch_backward_fx_l2) launch_backward;
+};
+static const FxBuild FX_BUILDS[4] = { { cpecan_wave_fx_scratch_bytes_l2, cpecan_wave_launch_backward_fx_l2 },
+                                      { cpecan_wave_fx_scratch_bytes_l2, cpecan_wave_launch_backward_fx_l2 },
+                                      { cpecan_wave_fx_scratch_bytes_l3, cpecan_wave_launch_backward_fx_l3 },
+                                      { cpecan_wave_fx_scratch_bytes_l4, cpecan_wave_launch_backward_fx_l4 } };
 /* which family a batch runs on: the wave kernels unless CPECAN_KERNELS=systolic asks for the workgroup-per-alignment ones */
 static bool use_wave_kernels() {
     const char *k = getenv("CPECAN_KERNELS");
@@ -498,6 +517,8 @@ struct cpecan_batch {
     DevBuf<double> events;
     DevBuf<double> Fstore, Bstore, dbgB;
     DevBuf<double> Bring; /* systolic Baum-Welch: backward cells of one window per item */
+    const FxBuild *fx = nullptr; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0): expectations
+                                    summed inside the sweep back, no B ring, no expectation kernel */
     DevBuf<long long> pairs;
     DevBuf<double> pairLogp;
     DevBuf<long long> nPairs, totXay, nTot, nCells;
@@ -1438,6 +1459,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     b->P.scanDecode = (flags & CPECAN_FLAG_SCAN_DECODE) ? 1 : 0;
     b->P.logThrSlack = params->threshold > 0.0 ? log(params->threshold) - 1e-3 : -INFINITY;
     b->P.ldsWidth = 0; /* (set per launch by the kernels that use it) */
+    b->P.expectResweep = 0;
 
     /* the HDP and vanilla machines have wave-per-alignment kernels of their own, for the posterior decode and for
      * the E-step (the 5-state machine runs on the general kernel); CPECAN_FLAG_GENERAL_KERNEL keeps such a batch on
@@ -1599,11 +1621,20 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
         }
         B_TRY(hipStreamSynchronize(c->prep));
         lap("band table upload, streams");
-        if (mode == CPECAN_MODE_EXPECTATIONS)
+        /* the strawMan machine's E-step on the wave kernels sums its expectations inside the sweep back (same box,
+         * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 (read per
+         * batch) keeps the ring of backward cells and the expectation kernel */
+        const char *fxEnv = getenv("CPECAN_EXPECT_FUSED");
+        if (mode == CPECAN_MODE_EXPECTATIONS && !(fxEnv != nullptr && atoi(fxEnv) == 0) && b->sy >= WV_BUILDS &&
+            b->sy < WV_BUILDS + 4 && !dna && !sm4 && !vanilla && !hdp) {
+            b->fx = &FX_BUILDS[b->sy - WV_BUILDS];
+            b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr && atoi(getenv("CPECAN_EXPECT_RESWEEP")) == 1;
+        }
+        if (mode == CPECAN_MODE_EXPECTATIONS && !b->fx)
             B_TRY(b->Bring.alloc((size_t) nItems * (size_t) b->ringD * (size_t) b->sy->bring_row_doubles()));
         b->stateBytes = b->sy->wave ? cpecan_wave_state_bytes() : cpecan_systolic_state_bytes();
         B_TRY(b->syStates.alloc((size_t) nItems * (size_t) b->stateBytes));
-        b->scratchBytes = (b->sy->scratch_bytes(b->ringD) + 63) / 64 * 64;
+        b->scratchBytes = (b->sy->scratch_bytes(b->ringD) + (b->fx ? b->fx->scratch_bytes(b->ringD) : 0) + 63) / 64 * 64;
         B_TRY(b->syScratch.alloc((size_t) nItems * (size_t) b->scratchBytes));
         B_TRY(b->track.alloc((size_t) trackTotal * (size_t) b->trackRow));
         B_TRY(b->trackBase.alloc((size_t) nItems));
@@ -1976,7 +2007,13 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                                                             b->pairLogp.p, b->totXay.p, b->totVal.p, scratchW,
                                                             b->scratchBytes, w);
                     if (postAside) HIP_TRY(hipEventRecord(b->evPost[(size_t) w], sP));
-                } else if (rc == 0 && n > 0 && !fwdOnly)
+                } else if (rc == 0 && n > 0 && !fwdOnly && b->fx)
+                    rc = b->fx->launch_backward(sB, b->items.p + i0, n, b->P, b->bandTab.p, b->track.p,
+                                                b->trackBase.p + i0, models, b->Fstore.p + i0 * b->ringDoubles,
+                                                b->ringDoubles, b->ringD, b->syStates.p + i0 * b->stateBytes,
+                                                b->totXay.p, b->totVal.p, b->syScratch.p + i0 * b->scratchBytes,
+                                                b->scratchBytes, b->expect.p, b->kidx.p, w, withSwitch);
+                else if (rc == 0 && n > 0 && !fwdOnly)
                     rc = b->sy->launch_backward(sB, b->items.p + i0, n, b->P, b->bandTab.p, b->track.p,
                                                 b->trackBase.p + i0, models,
                                                 b->Fstore.p + i0 * b->ringDoubles, b->ringDoubles, b->ringD,
@@ -1985,7 +2022,7 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                                                 b->scratchBytes,
                                                 b->Bring.p ? b->Bring.p + i0 * (long long) b->ringD * bringRow : nullptr,
                                                 w, withSwitch);
-                if (rc == 0 && n > 0 && b->mode == CPECAN_MODE_EXPECTATIONS)
+                if (rc == 0 && n > 0 && b->mode == CPECAN_MODE_EXPECTATIONS && !b->fx)
                     rc = b->sy->launch_expect(sB, b->items.p + i0, n, b->P, b->bandTab.p, b->track.p,
                                               b->trackBase.p + i0, b->kidx.p, models,
                                               b->Fstore.p + i0 * b->ringDoubles, b->ringDoubles,
@@ -2052,6 +2089,12 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
     }
     if (b->kernel != CPECAN_KERNEL_SYSTOLIC) return fail(CPECAN_EINVAL, "not a register-resident batch");
     *wave = b->sy->wave ? 1 : 0;
+    return CPECAN_OK;
+}
+
+int cpecan_hip_batch_expectation_pass(cpecan_batch *b, int32_t *fused) {
+    if (!b || !fused) return fail(CPECAN_EINVAL, "bad argument");
+    *fused = b->fx != nullptr ? 1 : 0; /* (set only where the wave kernels run the batch) */
     return CPECAN_OK;
 }
 

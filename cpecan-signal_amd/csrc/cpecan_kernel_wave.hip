@@ -104,6 +104,8 @@
 #define WV_CAND_SLACK 0.25   /* candidates: cells within this (log units) below the posterior threshold */
 #define WV_CAND_PER_DIAG 4   /* candidate capacity, in records per ring diagonal and layer */
 #define WV_EXPECT_CHUNKS 8   /* workgroups that share one window's diagonals in the expectation pass */
+/* where the eight transition sums M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y go among the nine of a strawMan model (from * 3 + to) */
+#define WV_EXPECT_SLOTS { 0 * 3 + 1, 1 * 3 + 1, 2 * 3 + 1, 0 * 3 + 0, 1 * 3 + 0, 2 * 3 + 0, 0 * 3 + 2, 2 * 3 + 2 }
 #ifndef WV_BACKWARD_PRIO
 #define WV_BACKWARD_PRIO 2
 #endif
@@ -1004,6 +1006,36 @@ struct ItemOut {
     long long nPairs, nTot;
 };
 
+/* Fused Baum-Welch expectations (KIND_EXPECT_FUSED): per refresh segment of a window (the ten decoded diagonals that
+ * share one totalProbability), in the alignment's HBM scratch after what cpecan_wave_scratch_bytes counts:
+ *   tr  the eight transition sums, wave totals, [segment][8]
+ *   g   per slot two gap-X sums, [segment][A | B][slot]: B the sum of the slot's column at the segment's end, A that of
+ *       the column it held before, when the slot changed columns within the segment.  One change at most: a slot's
+ *       column steps by P >= 128 and a band edge moves by at most one column per diagonal, so a second change would
+ *       need the band to travel P columns within the segment's ten diagonals
+ *   c   their matrix columns (-1: none) */
+struct WvFx {
+    double *tr, *g;
+    int *c;
+};
+#define WV_FX_EST_BOUND 30.0 /* nats an exact total may lie from the estimate the fused sums were taken against */
+__host__ __device__ inline long long wv_scratch_base_bytes(int ringD) {
+    return 2ll * ringD * sizeof(int) + ((long long) ringD / 10 + 8) * (sizeof(WinTotal) + 7 * WV_P * sizeof(double))
+           + 4ll * ringD * sizeof(unsigned long long)
+           + (long long) WV_L * WV_CAND_PER_DIAG * ringD * (sizeof(int2) + sizeof(double));
+}
+__host__ __device__ inline long long wv_fx_bytes(int ringD) {
+    return ((long long) ringD / 10 + 8) * (8 * sizeof(double) + 2 * WV_P * (sizeof(double) + sizeof(int)));
+}
+__device__ inline WvFx wv_fx_at(char *sc, int ringD) {
+    const long long nW = (long long) ringD / 10 + 8;
+    WvFx f;
+    f.tr = (double *) (sc + wv_scratch_base_bytes(ringD));
+    f.g = f.tr + nW * 8;
+    f.c = (int *) (f.g + nW * 2 * WV_P);
+    return f;
+}
+
 #define WV_PXN 64 /* LDS ring of gap-X rows, by column */
 struct BwdShared {
     double coef[64];
@@ -1046,13 +1078,16 @@ __device__ __forceinline__ int rank_in_diagonal(const unsigned long long (&m)[WV
 #define WV_KIND_POSTERIOR 0 /* sweep, collect decode candidates */
 #define WV_KIND_REDO 1      /* sweep once more with the exact totals in hand, pairs leave in the loop */
 #define WV_KIND_EXPECT 2    /* sweep, park the backward cells for the expectation kernel */
+#define WV_KIND_EXPECT_FUSED 3 /* sweep, sum the expectation terms against the estimate, per refresh segment */
+#define WV_KIND_EXPECT_REDO 4  /* sweep once more, the same sums against the exact totals (WvFx) */
 template <bool SW, int KIND>
 __device__ void backward_window(const DevItem &it, const DevParams &P, const int2 *__restrict__ bandTab,
                                 const double *__restrict__ track, const double *__restrict__ model,
                                 double *ring, int ringD, const WvWindow &win, ItemOut &out, BwdShared &sh,
                                 WinTotal *wtot, double *vw, double *rf, int2 *candKx, double *candFb, double *bring,
-                                int &nTotOut, int &nCandOut) {
+                                int &nTotOut, int &nCandOut, const WvFx &fxo) {
     constexpr int L = WV_L;
+    constexpr bool FX = KIND == WV_KIND_EXPECT_FUSED || KIND == WV_KIND_EXPECT_REDO;
     const int lane = threadIdx.x & 63;
     const int D = (int) (it.lX + it.lY);
     const unsigned cf = lds_addr(sh.coef);
@@ -1176,10 +1211,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
         };
         struct Q {
             double f[L], pm[L], py[L];
+            double fx[L], fy[L]; /* (fused kinds only) */
         };
         auto fetch = [&](const int tau, Rec &r, Q &q) __attribute__((always_inline)) {
             unsigned ev = 0u;
-            if (tau > tracedBackTo && tau < dTop) {
+            if ((FX ? tau >= tracedBackTo : tau > tracedBackTo) && tau < dTop) {
                 /* band(tau) from band(tau + 1): the steps of diagonal tau + 1 */
                 const unsigned bi = (unsigned) (tau + 1) & 31u;
                 if (bi == 31u || fFirst) {
@@ -1202,7 +1238,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 }
             }
             r.ev = ev;
-            const bool live = tau > tracedBackTo;
+            const bool live = FX ? tau >= tracedBackTo : tau > tracedBackTo;
             const unsigned rowOff = (unsigned) ((long long) (tau & ringMask) * (WV_ROW_DOUBLES * 8));
 #pragma unroll
             for (int j = 0; j < L; j++) {
@@ -1216,6 +1252,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 q.f[j] = fp.x;
                 q.pm[j] = fp.y;
                 q.py[j] = *(const double *) ((const char *) ring + offB);
+                if (FX) { /* (Fx, Fy) of the same cell: the expectation terms */
+                    const d2 fxy = *(const d2 *) ((const char *) ring + offA + (WV_OFF_FX(0) - WV_OFF_FM(0)) * 8);
+                    q.fx[j] = fxy.x;
+                    q.fy[j] = fxy.y;
+                }
             }
         };
 
@@ -1229,13 +1270,108 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
         long long emitted = 0; /* KIND_REDO: pairs written by this window so far */
         double totCur = CP_NEG_INF;
 
+        /* Fused expectations (diagonalCalculation_Expectations :841-863, cell_signal_updateTransAndKmerSkipExpectations
+         * :426-443), eight terms exp(F.from + B.to + (eP + tP) - ref) per cell.  Step t holds the backward cells of t+1
+         * and fetched row t two diagonals ago: it takes the lower and upper blocks of t+1 and the middle block of t+2
+         * (its forward cells are row t too); the loop's tail takes what is left of to+2 and to+1 from row `to`.  ref is
+         * the forward kernel's estimate of the window's total (the post kernel rescales each segment once the exact
+         * totals are known), or the segment's exact total on the re-sweep. */
+        double ea[8], gA[L], py1[L]; /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
+        int cA[L];
+        int segAcc = 0;
+        double refAcc = totEst;
+        if (FX) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) ea[i] = 0.0;
+#pragma unroll
+            for (int j = 0; j < L; j++) {
+                gA[j] = 0.0;
+                cA[j] = -1;
+                py1[j] = CP_NEG_INF;
+                fxo.c[lane * L + j] = -1; /* segment 0 has no A record yet */
+            }
+            if (KIND == WV_KIND_EXPECT_REDO) refAcc = uni64_d(ld_agent(&wtot[0].total));
+        }
+        auto fx_flush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                double v = ea[i];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+                if (lane == 0) fxo.tr[segAcc * 8 + i] = v;
+                ea[i] = 0.0;
+            }
+#pragma unroll
+            for (int j = 0; j < L; j++) {
+                const int sl = lane * L + j;
+                fxo.g[(segAcc * 2 + 1) * WV_P + sl] = gA[j];
+                fxo.c[(segAcc * 2 + 1) * WV_P + sl] = cA[j];
+                fxo.c[(segAcc * 2 + 2) * WV_P + sl] = -1; /* the next segment's A records */
+                gA[j] = 0.0;
+            }
+            segAcc++;
+            if (KIND == WV_KIND_EXPECT_REDO) refAcc = uni64_d(ld_agent(&wtot[segAcc].total));
+        };
+        /* rF, rX, rY: this slot's forward cells of row u1 - 1; nMin, nMax: the band of u1 */
+        auto fx_terms = [&](const double (&rF)[L], const double (&rX)[L], const double (&rY)[L], const int u1,
+                            const int nMin, const int nMax) __attribute__((always_inline)) {
+            double sF[L], sX[L], sY[L]; /* ... and those of the slot below (k-mer x-1) */
+#pragma unroll
+            for (int j = 0; j < L; j++) {
+                sF[j] = j > 0 ? rF[j > 0 ? j - 1 : 0] : ror1(rF[L - 1]);
+                sX[j] = j > 0 ? rX[j > 0 ? j - 1 : 0] : ror1(rX[L - 1]);
+                sY[j] = j > 0 ? rY[j > 0 ? j - 1 : 0] : ror1(rY[L - 1]);
+            }
+            if (u1 + 1 <= tPost0) { /* middle block of u1+1: B.match and match emission of u1+1 are hB, hP */
+#pragma unroll
+                for (int j = 0; j < L; j++) {
+                    const double eP = hP[j];
+                    ea[3] += exp(sF[j] + hB[j] + (eP + T[T_MATCH_CONTINUE]) - refAcc);
+                    ea[4] += exp(sX[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_X]) - refAcc);
+                    ea[5] += exp(sY[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_Y]) - refAcc);
+                }
+                if ((tPost0 - (u1 + 1)) % 10 == 9) fx_flush(); /* u1+1 ends its segment */
+            }
+            if (u1 <= tPost0) { /* lower and upper blocks of u1 */
+                const int sMin = nMin % WV_P;
+#pragma unroll
+                for (int j = 0; j < L; j++) {
+                    const int sl = lane * L + j;
+                    const int x = nMin + (sl - sMin + (sl < sMin ? WV_P : 0));
+                    const double p0 = exp(sF[j] + Bx[j] + px[j].a.x - refAcc);
+                    const double p1 = exp(sX[j] + Bx[j] + px[j].a.y - refAcc);
+                    const double p2 = SW ? exp(sY[j] + Bx[j] + px[j].b.x - refAcc) : 0.0;
+                    ea[0] += p0;
+                    ea[1] += p1;
+                    if (SW) ea[2] += p2;
+                    if (x <= nMax && x != cA[j]) { /* the slot took another column within the segment */
+                        if (gA[j] != 0.0) {
+                            fxo.g[(segAcc * 2) * WV_P + sl] = gA[j];
+                            fxo.c[(segAcc * 2) * WV_P + sl] = cA[j];
+                        }
+                        gA[j] = 0.0;
+                        cA[j] = x;
+                    }
+                    gA[j] += p0;
+                    gA[j] += p1;
+                    if (SW) gA[j] += p2;
+                    ea[6] += exp(rF[j] + By[j] + (py1[j] + T[T_GAP_OPEN_Y]) - refAcc);
+                    ea[7] += exp(rY[j] + By[j] + (py1[j] + T[T_GAP_EXTEND_Y]) - refAcc);
+                }
+            }
+        };
+
         auto step = [&](const int t, Rec &r, Q &q) __attribute__((always_inline)) {
             /* this diagonal's forward values (their loads were issued WV_PREFETCH diagonals ago), then the fetch
              * that re-uses their registers */
-            double qF[L], qPm[L], qPy[L];
+            double qF[L], qPm[L], qPy[L], qFx[L], qFy[L];
             unsigned long long mt[L];
 #pragma unroll
             for (int j = 0; j < L; j++) { qF[j] = q.f[j]; qPm[j] = q.pm[j]; qPy[j] = q.py[j]; mt[j] = r.m[j]; }
+            if (FX) {
+#pragma unroll
+                for (int j = 0; j < L; j++) { qFx[j] = q.fx[j]; qFy[j] = q.fy[j]; }
+            }
             const unsigned ev = r.ev;
             fetch(t - WV_PREFETCH, r, q);
             if (t < dTop) {
@@ -1286,6 +1422,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 }
                 ladd_finish<L>(pb, bm);
                 if (SW) ladd_finish<L>(pa, by);
+                if constexpr (FX) fx_terms(qF, qFx, qFy, t + 1, nxmin, nxmax); /* (before the cells of t+1 and their k-mers move on) */
 #pragma unroll
                 for (int j = 0; j < L; j++) {
                     hB[j] = Bm[j]; hP[j] = pm1[j];
@@ -1326,7 +1463,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 Uy[j] = By[j] + (qPy[j] + T[T_GAP_EXTEND_Y]);
 #endif
             }
-            if (t <= tracedBackFrom) {
+            if (t <= tracedBackFrom && KIND != WV_KIND_EXPECT_REDO) {
                 double fb[L];
 #pragma unroll
                 for (int j = 0; j < L; j++) fb[j] = qF[j] + Bm[j];
@@ -1399,7 +1536,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                         }
                         emitted += total;
                     }
-                } else {
+                } else if (!FX) {
                     /* decode candidates: cells within WV_CAND_SLACK of the threshold against the estimate */
 #pragma unroll
                     for (int j = 0; j < L; j++) {
@@ -1419,6 +1556,10 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             }
 #pragma unroll
             for (int j = 0; j < L; j++) pm1[j] = qPm[j];
+            if (FX) {
+#pragma unroll
+                for (int j = 0; j < L; j++) py1[j] = qPy[j];
+            }
         };
 
         int t = dTop;
@@ -1442,10 +1583,17 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             step(t, r1, q1); t--;
         }
         if (KIND == WV_KIND_REDO) out.nPairs += emitted;
+        if constexpr (FX) if (tPost0 > tracedBackTo) {
+            /* the middle block of to+2 and the blocks of to+1 (its middle block would read forward[to-1], freed by then
+             * in the reference); row `to` is in the fetch buffer the last step did not refill */
+            if (((dTop - (tracedBackTo + 1)) & 1) == 0) fx_terms(q1.f, q1.fx, q1.fy, tracedBackTo + 1, bxmin, bxmax);
+            else fx_terms(q0.f, q0.fx, q0.fy, tracedBackTo + 1, bxmin, bxmax);
+            fx_flush();
+        }
     }
     nTotOut = nTotWin;
     nCandOut = nCand;
-    if (KIND == WV_KIND_REDO) return;
+    if (KIND == WV_KIND_REDO || KIND == WV_KIND_EXPECT_REDO) return;
 
     /* -------------------- phase T0: the per-cell terms of every refresh -------------------- */
     /* diagonalCalculationTotalProbability (:736-754): v = cell_dotProduct(forward[t], backward[t]) (:391-397) and
@@ -1558,6 +1706,54 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
     }
 }
 
+#if !defined(WV_VANILLA) && !defined(WV_HDP)
+/* A window's fused expectation sums into the model's expectations (layout of cpecan_k_wv_expect's): segment k's sums
+ * were taken against ref_k -- the estimate, or on the re-sweep (exact) the segment's total itself -- and scale by
+ * exp(ref_k - total_k).  Threads 0-7 the transitions, thread 8 the likelihood (the exact total once per decoded diagonal,
+ * :849), every thread the gap-X sums of slots tid, tid + nth, ..., into the bins of their columns' k-mers. */
+__device__ void fx_finish(const int tid, const int nth, const DevItem &it, const WvFx &fx, const WinTotal *wtot,
+                          const int nSeg, const int tPost0, const int to, const double est, const bool exact,
+                          double *expect, const unsigned short *__restrict__ kidx) {
+    double *dst = expect + (long long) it.model * (9 + 4096 + 1);
+    const unsigned short *kx = kidx + it.xOff;
+    const int slot[8] = WV_EXPECT_SLOTS;
+    if (tid < 8) {
+        double sum = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < nSeg; k++) sum += fx.tr[k * 8 + tid] * (exact ? 1.0 : exp(est - wtot[k].total));
+        atomicAdd(dst + slot[tid], sum);
+    } else if (tid == 8) {
+        double lik = 0.0;
+#pragma unroll 1
+        for (int u = tPost0; u > to; u--) lik += wtot[(tPost0 - u) / 10].total;
+        atomicAdd(dst + 9 + 4096, lik);
+    }
+#pragma unroll 1
+    for (int s = tid; s < WV_P; s += nth) {
+        int cur = -1;
+        double sum = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < nSeg; k++) {
+            const double f = exact ? 1.0 : exp(est - wtot[k].total);
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const int col = fx.c[(k * 2 + r) * WV_P + s];
+                const double v = fx.g[(k * 2 + r) * WV_P + s];
+                if (col > 0 && v != 0.0) {
+                    if (col != cur) {
+                        if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
+                        cur = col;
+                        sum = 0.0;
+                    }
+                    sum += f * v;
+                }
+            }
+        }
+        if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
+    }
+}
+#endif
+
 } // namespace
 
 /* One wave per alignment: forward sweep up to its next traceback point.  Two instantiations: a -inf
@@ -1612,7 +1808,10 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
     const int2 *__restrict__ bandTab, const double *__restrict__ track,
     const long long *__restrict__ trackBase, const double *__restrict__ models, double *Fring,
     long long ringDoubles, int ringD, WvState *states, long long *pairs, double *pairLogp,
-    char *scratch, long long scratchBytes, double *Bring, int window, BwdShared (&shs)[WV_WPB]) {
+    char *scratch, long long scratchBytes, double *Bring, int window, BwdShared (&shs)[WV_WPB],
+    double *expect = nullptr, const unsigned short *kidx = nullptr) {
+    constexpr bool FX = KIND == WV_KIND_EXPECT_FUSED || KIND == WV_KIND_EXPECT_REDO;
+    constexpr bool REDO = KIND == WV_KIND_REDO || KIND == WV_KIND_EXPECT_REDO;
     const long long idx = (long long) blockIdx.x * WV_WPB + uni(threadIdx.x >> 6);
     BwdShared &sh = shs[uni(threadIdx.x >> 6)];
     if (idx >= nItems) return;
@@ -1623,8 +1822,9 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
         win.valid = ld_agent(&w->valid); win.top = ld_agent(&w->top); win.from = ld_agent(&w->from);
         win.to = ld_agent(&w->to); win.atEnd = ld_agent(&w->atEnd); win.nCand = win.nRefresh = win.pad = 0;
         win.est = ld_agent(&w->est);
+        if (KIND == WV_KIND_EXPECT_REDO) win.nRefresh = ld_agent(&w->nRefresh);
     }
-    if (uni(win.valid) != (KIND == WV_KIND_REDO ? 2 : 1)) return;
+    if (uni(win.valid) != (REDO ? 2 : 1)) return;
     const DevItem it = uniform_item(items[idx]);
     init_coef(sh.coef);
     ItemOut out;
@@ -1645,13 +1845,27 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
     int2 *candKx = (int2 *) ((char *) msk + 4ll * ringD * sizeof(unsigned long long));
     double *candFb = (double *) ((char *) candKx + (long long) WV_L * WV_CAND_PER_DIAG * ringD * sizeof(int2));
     int nTot = 0, nCand = 0;
+    WvFx fxo{};
+    if (FX) fxo = wv_fx_at(sc, ringD);
     backward_window<SW, KIND>(it, P, bandTab + it.diagBase, track + trackBase[idx] * WV_ROW,
                               models + (long long) it.model * WV_MODEL_DOUBLES, Fring + idx * ringDoubles, ringD, win,
                               out, sh, wtot, vw, rf, candKx, candFb,
-                              Bring ? Bring + idx * ((long long) ringD * WV_L * 3 * 64) : nullptr, nTot, nCand);
+                              Bring ? Bring + idx * ((long long) ringD * WV_L * 3 * 64) : nullptr, nTot, nCand, fxo);
+#if !defined(WV_VANILLA) && !defined(WV_HDP)
+    if constexpr (KIND == WV_KIND_EXPECT_REDO) {
+        /* the sums were taken against the exact totals: they go to the model's expectations as they are (the
+         * fence: this wave's lanes read back what other lanes wrote) */
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        const int dTop = uni(win.top), from = uni(win.from);
+        fx_finish(threadIdx.x & 63, 64, it, fxo, wtot, uni(win.nRefresh), dTop < from ? dTop : from, uni(win.to),
+                  uni64_d(win.est), true, expect, kidx);
+    }
+#endif
     if ((threadIdx.x & 63) == 0) {
         WvWindow *w = &state->win[window & 3];
-        if (KIND == WV_KIND_REDO) {
+        if (KIND == WV_KIND_EXPECT_REDO) {
+            w->valid = 0;
+        } else if (KIND == WV_KIND_REDO) {
             state->nPairs = out.nPairs;
             w->valid = 0;
         } else {
@@ -1679,6 +1893,26 @@ WV_BACKWARD_KERNEL(cpecan_k_wv_backward_em, false, WV_KIND_EXPECT)
 #if !defined(WV_VANILLA) /* (no gap Y -> gap X transition in the vanilla machine) */
 WV_BACKWARD_KERNEL(cpecan_k_wv_backward_em_sw, true, WV_KIND_EXPECT)
 #endif
+#if !defined(WV_VANILLA) && !defined(WV_HDP)
+/* the strawMan machine's E-step: expectations summed inside the sweep back (no B ring, no expectation kernel), and the
+ * re-sweep of the windows whose sums the estimate could not carry (cpecan_k_wv_post) */
+#define WV_BACKWARD_FX_KERNEL(name, SW, KIND)                                                                     \
+    extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(name)(                                       \
+        const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTab,       \
+        const double *__restrict__ track, const long long *__restrict__ trackBase,                                \
+        const double *__restrict__ models, double *Fring, long long ringDoubles, int ringD, WvState *states,      \
+        char *scratch, long long scratchBytes, double *expect, const unsigned short *__restrict__ kidx,           \
+        int window) {                                                                                             \
+        __shared__ BwdShared sh[WV_WPB];                                                                          \
+        wv_backward_kernel<SW, KIND>(items, nItems, P, bandTab, track, trackBase, models, Fring, ringDoubles,     \
+                                     ringD, states, nullptr, nullptr, scratch, scratchBytes, nullptr, window, sh, \
+                                     expect, kidx);                                                               \
+    }
+WV_BACKWARD_FX_KERNEL(cpecan_k_wv_backward_fx, false, WV_KIND_EXPECT_FUSED)
+WV_BACKWARD_FX_KERNEL(cpecan_k_wv_backward_fx_sw, true, WV_KIND_EXPECT_FUSED)
+WV_BACKWARD_FX_KERNEL(cpecan_k_wv_resweep_fx, false, WV_KIND_EXPECT_REDO)
+WV_BACKWARD_FX_KERNEL(cpecan_k_wv_resweep_fx_sw, true, WV_KIND_EXPECT_REDO)
+#endif
 
 /*
  * What follows a sweep back, one 256-thread workgroup per alignment (none of it is a recurrence along the
@@ -1696,13 +1930,13 @@ struct PostShared {
     double coef[64];
     double vbuf[256];
     int part[4];
-    int scan, carry;
+    int scan, carry, fxRedo;
 };
 extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTabAll,
     const double *__restrict__ models, const double *Fring, long long ringDoubles, int ringD, WvState *states,
     long long *pairs, double *pairLogp, long long *totXay, double *totVal, char *scratch, long long scratchBytes,
-    int window, int formTerms) {
+    int window, int fused, double *expect, const unsigned short *__restrict__ kidx) {
     constexpr int L = WV_L;
     __shared__ PostShared sh;
     const long long idx = blockIdx.x;
@@ -1720,6 +1954,7 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     const int nPost = tPost0 - tracedBackTo;                         /* diagonals decoded      */
     const int candCap = WV_CAND_PER_DIAG * WV_L * ringD;
     if (tid == 0) sh.scan = (P.scanDecode != 0 || !(P.logThrSlack > CP_NEG_INF) || nCand > candCap) ? 1 : 0;
+    if (tid == 0) sh.fxRedo = P.expectResweep != 0 ? 1 : 0; /* (tests: every window down the re-sweep) */
     __syncthreads();
     const unsigned cf = lds_addr(sh.coef);
     const int2 *bandTab = bandTabAll + it.diagBase;
@@ -1734,7 +1969,7 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     const double *candFb = (const double *) ((const char *) candKx + (long long) WV_L * WV_CAND_PER_DIAG * ringD * sizeof(int2));
     long long nPairs0 = uni64(ld_agent(&state->nPairs)), nTot0 = uni64(ld_agent(&state->nTot));
 
-    (void) models; (void) Fring; (void) ringDoubles; (void) formTerms;
+    (void) models; (void) Fring; (void) ringDoubles; (void) kidx; (void) expect;
 
     /* ------------------------------ phase T: the totals ------------------------------ */
     /* (plain loads throughout: what this kernel reads was written by an earlier kernel, or by this workgroup
@@ -1774,6 +2009,7 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
             if (w.second) tot = ladd(acc, partner, cf);
             wtot[k >> 1].total = tot;
             if (!(fabs(tot - totEst) <= WV_CAND_SLACK)) sh.scan = 1; /* also catches NaN and infinities */
+            if (!(fabs(tot - totEst) <= WV_FX_EST_BOUND)) sh.fxRedo = 1;
             const long long o = nTot0 + (k >> 1);
             if (o < it.totCap) {
                 totXay[it.totBase + o] = w.t;
@@ -1783,6 +2019,20 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
         __syncthreads();
     }
     __syncthreads();
+#if !defined(WV_VANILLA) && !defined(WV_HDP)
+    if (P.mode != 0 && fused) {
+        /* fused expectations: the sweep's sums scale by exp(est - total) per segment; a window whose totals stray too
+         * far from the estimate (or an estimate that is not finite) is swept once more against the exact totals */
+        const bool redo = nPost > 0 && sh.fxRedo != 0;
+        if (nPost > 0 && !redo)
+            fx_finish(tid, 256, it, wv_fx_at(sc, ringD), wtot, nTotWin, tPost0, tracedBackTo, totEst, false, expect, kidx);
+        if (tid == 0) {
+            state->nTot = nTot0 + nTotWin;
+            wp->valid = redo ? 2 : 0;
+        }
+        return;
+    }
+#endif
     if (P.mode != 0 || nPost <= 0 || sh.scan != 0) {
         if (tid == 0) {
             state->nTot = nTot0 + nTotWin;
@@ -2117,7 +2367,7 @@ extern "C" __global__ __launch_bounds__(WV_P) void WV_SYM(cpecan_k_wv_expect)(
     /* block reduction of the per-thread sums, then one atomic per value */
     if (threadIdx.x < 16) sExp[threadIdx.x] = 0.0;
     __syncthreads();
-    const int slot[8] = { 0 * 3 + 1, 1 * 3 + 1, 2 * 3 + 1, 0 * 3 + 0, 1 * 3 + 0, 2 * 3 + 0, 0 * 3 + 2, 2 * 3 + 2 };
+    const int slot[8] = WV_EXPECT_SLOTS;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
         double v = acc[i];
@@ -2318,11 +2568,9 @@ extern "C" int WV_SYM(cpecan_wave_rows)(void) { return WV_L; }
 extern "C" int WV_SYM(cpecan_wave_ring_row_doubles)(void) { return WV_ROW_DOUBLES; }
 extern "C" int WV_SYM(cpecan_wave_bring_row_doubles)(void) { return WV_L * 3 * 64; }
 /* HBM scratch per alignment: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list] */
-extern "C" long long WV_SYM(cpecan_wave_scratch_bytes)(int ringD) {
-    return 2ll * ringD * sizeof(int) + ((long long) ringD / 10 + 8) * (sizeof(WinTotal) + 7 * WV_P * sizeof(double))
-           + 4ll * ringD * sizeof(unsigned long long)
-           + (long long) WV_L * WV_CAND_PER_DIAG * ringD * (sizeof(int2) + sizeof(double));
-}
+extern "C" long long WV_SYM(cpecan_wave_scratch_bytes)(int ringD) { return wv_scratch_base_bytes(ringD); }
+/* ... and after it, in batches with fused expectations, the segments' sums (WvFx) */
+extern "C" long long WV_SYM(cpecan_wave_fx_scratch_bytes)(int ringD) { return wv_fx_bytes(ringD); }
 extern "C" int WV_SYM(cpecan_wave_launch_forward)(hipStream_t stream, const DevItem *items, long long nItems,
                                                   DevParams P, const void *bandTab, const double *track,
                                                   const long long *trackBase, const double *events,
@@ -2351,7 +2599,8 @@ extern "C" int WV_SYM(cpecan_wave_launch_backward)(hipStream_t stream, const Dev
 #define WV_LAUNCH_POST                                                                                            \
     hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) nItems), dim3(256), 0, stream, items, nItems, P, \
                        (const int2 *) bandTab, models, (const double *) Fring, ringDoubles, ringD,                \
-                       (WvState *) states, pairs, pairLogp, totXay, totVal, scratch, scratchBytes, window, 0)
+                       (WvState *) states, pairs, pairLogp, totXay, totVal, scratch, scratchBytes, window, 0,        \
+                       (double *) nullptr, (const unsigned short *) nullptr)
     if (P.mode != 0) {
 #if defined(WV_VANILLA)
         if (withSwitch) return -1;
@@ -2386,10 +2635,39 @@ extern "C" int WV_SYM(cpecan_wave_launch_post_asm)(hipStream_t stream, const Dev
                                                    double *totVal, char *scratch, long long scratchBytes, int window) {
     hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) nItems), dim3(256), 0, stream, items, nItems, P,
                        (const int2 *) bandTab, models, (const double *) Fring, ringDoubles, ringD, (WvState *) states, pairs,
-                       pairLogp, totXay, totVal, scratch, scratchBytes, window, 0);
+                       pairLogp, totXay, totVal, scratch, scratchBytes, window, 0, (double *) nullptr,
+                       (const unsigned short *) nullptr);
     hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_resweep), dim3((unsigned) ((nItems + WV_WPB - 1) / WV_WPB)), dim3(64 * WV_WPB), 0, stream,
                        items, nItems, P, (const int2 *) bandTab, track, trackBase, models, Fring, ringDoubles, ringD,
                        (WvState *) states, pairs, pairLogp, scratch, scratchBytes, (double *) nullptr, window);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+#endif
+
+#if !defined(WV_VANILLA) && !defined(WV_HDP)
+/* the strawMan E-step of a window with fused expectations: the sweep back summing them, the totals and the sums into
+ * expect[] (cpecan_k_wv_post), then the re-sweep of the windows the estimate could not carry (it returns at once for
+ * the others).  All three index alignments by blockIdx.x. */
+extern "C" int WV_SYM(cpecan_wave_launch_backward_fx)(hipStream_t stream, const DevItem *items, long long nItems,
+                                                      DevParams P, const void *bandTab, const double *track,
+                                                      const long long *trackBase, const double *models, double *Fring,
+                                                      long long ringDoubles, int ringD, void *states, long long *totXay,
+                                                      double *totVal, char *scratch, long long scratchBytes,
+                                                      double *expect, const unsigned short *kidx, int window,
+                                                      int withSwitch) {
+#define WV_LAUNCH_FX(k)                                                                                           \
+    hipLaunchKernelGGL(WV_SYM(k), dim3((unsigned) ((nItems + WV_WPB - 1) / WV_WPB)), dim3(64 * WV_WPB), 0, stream, items, nItems, P, \
+                       (const int2 *) bandTab, track, trackBase, models, Fring, ringDoubles, ringD,               \
+                       (WvState *) states, scratch, scratchBytes, expect, kidx, window)
+    if (withSwitch) WV_LAUNCH_FX(cpecan_k_wv_backward_fx_sw);
+    else WV_LAUNCH_FX(cpecan_k_wv_backward_fx);
+    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) nItems), dim3(256), 0, stream, items, nItems, P,
+                       (const int2 *) bandTab, models, (const double *) Fring, ringDoubles, ringD, (WvState *) states,
+                       (long long *) nullptr, (double *) nullptr, totXay, totVal, scratch, scratchBytes, window, 1,
+                       expect, kidx);
+    if (withSwitch) WV_LAUNCH_FX(cpecan_k_wv_resweep_fx_sw);
+    else WV_LAUNCH_FX(cpecan_k_wv_resweep_fx);
+#undef WV_LAUNCH_FX
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #endif

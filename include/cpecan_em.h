@@ -9,6 +9,9 @@
  * and per-read scaled emission tables resident in HBM; an iteration rewrites the nine transitions and the 4096
  * k-mer gap probabilities in place, runs the E-step kernels, sums the per-read blocks on the device, combines the
  * ranks with ONE all-reduce of 4106 doubles over RCCL, and normalises on the host -- no files, no gather on a master.
+ * The E-step takes whichever path its batches take: on the wave kernels the sums taken inside the sweep back, on the
+ * workgroup kernels (or with CPECAN_EXPECT_FUSED=0) the ring of backward cells and the expectation kernel
+ * (cpecan_hip_batch_expectation_pass).
  */
 #ifndef CPECAN_EM_H_
 #define CPECAN_EM_H_

@@ -295,6 +295,10 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *batch, int32_t *wave);
  * the compiled kernels.  CPECAN_ASM=0 in the environment keeps every batch on the compiled kernels.  A batch planned for
  * them whose setup launch failed runs on the compiled kernels: 0, and last_error says why. */
 int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
+/* *fused = 1 if the batch's E-step sums its Baum-Welch expectations inside the sweep back of the wave kernels (the
+ * strawMan machine, not the workgroup kernels; CPECAN_EXPECT_FUSED=0 in the environment when the batch is created opts out):
+ * no ring of backward cells, no expectation kernel.  0 for the ring-of-backward-cells path and for posterior batches. */
+int cpecan_hip_batch_expectation_pass(cpecan_batch *batch, int32_t *fused);
 /* Systolic path only: HIP-event time of the last run spent in the forward-window kernels and in
  * the backward-window kernels (each launched `launches_each` times, once per traceback window). */
 int cpecan_hip_batch_stage_ms(cpecan_batch *batch, float *ms_forward, float *ms_backward,
