@@ -1628,7 +1628,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
         if (mode == CPECAN_MODE_EXPECTATIONS && !(fxEnv != nullptr && atoi(fxEnv) == 0) && b->sy >= WV_BUILDS &&
             b->sy < WV_BUILDS + 4 && !dna && !sm4 && !vanilla && !hdp) {
             b->fx = &FX_BUILDS[b->sy - WV_BUILDS];
-            b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr && atoi(getenv("CPECAN_EXPECT_RESWEEP")) == 1;
+            b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr ? atoi(getenv("CPECAN_EXPECT_RESWEEP")) : 0;
         }
         if (mode == CPECAN_MODE_EXPECTATIONS && !b->fx)
             B_TRY(b->Bring.alloc((size_t) nItems * (size_t) b->ringD * (size_t) b->sy->bring_row_doubles()));

@@ -1322,28 +1322,62 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 sX[j] = j > 0 ? rX[j > 0 ? j - 1 : 0] : ror1(rX[L - 1]);
                 sY[j] = j > 0 ? rY[j > 0 ? j - 1 : 0] : ror1(rY[L - 1]);
             }
+            /* (re-sweep only) a total of -inf or NaN: every term is NaN, as in the reference, and the terms must then
+             * be those the reference forms -- a cell of the band whose neighbour is in the band too, the gap Y -> gap X
+             * term included on the build without it (its transition is -inf) -- instead of one per slot */
             if (u1 + 1 <= tPost0) { /* middle block of u1+1: B.match and match emission of u1+1 are hB, hP */
+                const bool nf = KIND == WV_KIND_EXPECT_REDO && !(refAcc > CP_NEG_INF);
+                int cMin = 0, cMax = -1, qMin = 0, qMax = -1; /* bands of u1+1 (the cell) and u1-1 (its neighbour) */
+                if (nf) {
+                    band_load(bandTab, u1 + 1, cMin, cMax);
+                    band_load(bandTab, u1 - 1, qMin, qMax);
+                }
 #pragma unroll
                 for (int j = 0; j < L; j++) {
                     const double eP = hP[j];
-                    ea[3] += exp(sF[j] + hB[j] + (eP + T[T_MATCH_CONTINUE]) - refAcc);
-                    ea[4] += exp(sX[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_X]) - refAcc);
-                    ea[5] += exp(sY[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_Y]) - refAcc);
+                    double p3 = exp(sF[j] + hB[j] + (eP + T[T_MATCH_CONTINUE]) - refAcc);
+                    double p4 = exp(sX[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_X]) - refAcc);
+                    double p5 = exp(sY[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_Y]) - refAcc);
+                    if (nf) {
+                        const int sl = lane * L + j, s0 = cMin % WV_P;
+                        const int x = cMin + (sl - s0 + (sl < s0 ? WV_P : 0));
+                        const bool in = x <= cMax && x - 1 >= qMin && x - 1 <= qMax;
+                        p3 = in ? p3 : 0.0;
+                        p4 = in ? p4 : 0.0;
+                        p5 = in ? p5 : 0.0;
+                    }
+                    ea[3] += p3;
+                    ea[4] += p4;
+                    ea[5] += p5;
                 }
                 if ((tPost0 - (u1 + 1)) % 10 == 9) fx_flush(); /* u1+1 ends its segment */
             }
             if (u1 <= tPost0) { /* lower and upper blocks of u1 */
                 const int sMin = nMin % WV_P;
+                const bool nf = KIND == WV_KIND_EXPECT_REDO && !(refAcc > CP_NEG_INF);
+                int qMin = 0, qMax = -1; /* band of u1-1 */
+                if (nf) band_load(bandTab, u1 - 1, qMin, qMax);
 #pragma unroll
                 for (int j = 0; j < L; j++) {
                     const int sl = lane * L + j;
                     const int x = nMin + (sl - sMin + (sl < sMin ? WV_P : 0));
-                    const double p0 = exp(sF[j] + Bx[j] + px[j].a.x - refAcc);
-                    const double p1 = exp(sX[j] + Bx[j] + px[j].a.y - refAcc);
-                    const double p2 = SW ? exp(sY[j] + Bx[j] + px[j].b.x - refAcc) : 0.0;
+                    double p0 = exp(sF[j] + Bx[j] + px[j].a.x - refAcc);
+                    double p1 = exp(sX[j] + Bx[j] + px[j].a.y - refAcc);
+                    double p2 = SW ? exp(sY[j] + Bx[j] + px[j].b.x - refAcc) : 0.0;
+                    double p6 = exp(rF[j] + By[j] + (py1[j] + T[T_GAP_OPEN_Y]) - refAcc);
+                    double p7 = exp(rY[j] + By[j] + (py1[j] + T[T_GAP_EXTEND_Y]) - refAcc);
+                    if (nf) {
+                        const bool inL = x <= nMax && x - 1 >= qMin && x - 1 <= qMax; /* lower neighbour (x-1, y) */
+                        const bool inU = x <= nMax && x >= qMin && x <= qMax;         /* upper neighbour (x, y-1) */
+                        p0 = inL ? p0 : 0.0;
+                        p1 = inL ? p1 : 0.0;
+                        p2 = inL ? (SW ? p2 : exp(CP_NEG_INF - refAcc)) : 0.0;
+                        p6 = inU ? p6 : 0.0;
+                        p7 = inU ? p7 : 0.0;
+                    }
                     ea[0] += p0;
                     ea[1] += p1;
-                    if (SW) ea[2] += p2;
+                    if (SW || nf) ea[2] += p2;
                     if (x <= nMax && x != cA[j]) { /* the slot took another column within the segment */
                         if (gA[j] != 0.0) {
                             fxo.g[(segAcc * 2) * WV_P + sl] = gA[j];
@@ -1354,9 +1388,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     }
                     gA[j] += p0;
                     gA[j] += p1;
-                    if (SW) gA[j] += p2;
-                    ea[6] += exp(rF[j] + By[j] + (py1[j] + T[T_GAP_OPEN_Y]) - refAcc);
-                    ea[7] += exp(rY[j] + By[j] + (py1[j] + T[T_GAP_EXTEND_Y]) - refAcc);
+                    if (SW || nf) gA[j] += p2;
+                    ea[6] += p6;
+                    ea[7] += p7;
                 }
             }
         };
@@ -1954,7 +1988,8 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     const int nPost = tPost0 - tracedBackTo;                         /* diagonals decoded      */
     const int candCap = WV_CAND_PER_DIAG * WV_L * ringD;
     if (tid == 0) sh.scan = (P.scanDecode != 0 || !(P.logThrSlack > CP_NEG_INF) || nCand > candCap) ? 1 : 0;
-    if (tid == 0) sh.fxRedo = P.expectResweep != 0 ? 1 : 0; /* (tests: every window down the re-sweep) */
+    /* (tests: 1 every window down the re-sweep, 2 every other one -- the items and windows alternate) */
+    if (tid == 0) sh.fxRedo = P.expectResweep == 1 || (P.expectResweep == 2 && ((idx ^ window) & 1)) ? 1 : 0;
     __syncthreads();
     const unsigned cf = lds_addr(sh.coef);
     const int2 *bandTab = bandTabAll + it.diagBase;

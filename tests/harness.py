@@ -105,6 +105,26 @@ def with_gap_switch(t, p_switch):
     return tuple(float(v) for v in t)
 
 
+def with_gap_x(batch, gx):
+    """the batch with every model's gap-X table replaced (a trained set's); gx None: the batch as it is"""
+    if gx is None:
+        return batch
+    return dict(batch, models=[(m, gx, gy) for (m, _, gy) in batch["models"]])
+
+
+def trained_transitions(ctx):
+    """(transitions, gap_x) after one EM step from the nanopore defaults: em.m_step of one GPU E-step with the
+    reference's pseudocount of 1e-4 per read, a tiny finite gap Y -> gap X switch as trained models have"""
+    import dist_em
+    import synth
+    batch = synth.make_batch(47, 6, 150, 310, anchor_every=30)
+    got = dist_em.gpu_e_step(cp, ctx, batch, band_params(0.01, 100, 20, 40), list(range(6)), cp.NANOPORE_TRANSITIONS,
+                             batch["models"][0][1], pseudocount=1e-4)
+    t, gx = dist_em.m_step(got)
+    assert np.isfinite(t[7]) and t[7] < np.log(0.01)
+    return tuple(float(v) for v in t), gx
+
+
 def hdp_batch(seed, n, lX, every, nhdp):
     """reads for the HDP machine whose event means are drawn around the mode of each k-mer's HDP density.
     Returns (batch, the oracle's HdpModel with its default transitions)."""

@@ -16,11 +16,10 @@ import os
 import numpy as np
 import pytest
 
-import dist_em
 import pyoracle as o
 import synth
 from harness import (assert_same_posterior, band_params, batch_results, cp, hdp_batch, make_items, run_gpu,
-                     run_oracle_hdp_item, run_oracle_item, with_gap_switch)
+                     run_oracle_hdp_item, run_oracle_item, trained_transitions, with_gap_switch, with_gap_x)
 
 STRONG = with_gap_switch(cp.NANOPORE_TRANSITIONS, 0.1)
 
@@ -35,12 +34,9 @@ def ctx():
 @pytest.fixture(scope="module")
 def trained(ctx):
     """(transitions, gap_x) after one EM step from the nanopore defaults"""
-    batch = synth.make_batch(47, 6, 150, 310, anchor_every=30)
-    got = dist_em.gpu_e_step(cp, ctx, batch, band_params(0.01, 100, 20, 40), list(range(6)), cp.NANOPORE_TRANSITIONS,
-                             batch["models"][0][1], pseudocount=1e-4)
-    t, gx = dist_em.m_step(got)
+    t, gx = trained_transitions(ctx)
     assert np.isfinite(t[7]) and t[7] < np.log(0.01)  # a tiny switch, as trained models have
-    return tuple(float(v) for v in t), gx
+    return t, gx
 
 
 @pytest.fixture(params=["strong", "trained"])
@@ -50,13 +46,6 @@ def tset(request):
         return "strong", STRONG, None
     t, gx = request.getfixturevalue("trained")
     return "trained", t, gx
-
-
-def with_gap_x(batch, gx):
-    """the batch with every model's gap-X table replaced (the trained set's)"""
-    if gx is None:
-        return batch
-    return dict(batch, models=[(m, gx, gy) for (m, _, gy) in batch["models"]])
 
 
 _ORACLE = {}
