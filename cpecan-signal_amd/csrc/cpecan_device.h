@@ -96,6 +96,26 @@ struct DevParams {
                           items on both paths and one item alternates between them; 0 (and any other value) none forced */
 };
 
+/* the arguments of the five general kernels (cpecan_general.h), one launch for all of them: each machine reads the
+ * inputs it has and the host passes null for the others */
+struct DevGeneralArgs {
+    const DevItem *items;
+    const int *bandL, *bandR;
+    const long long *cellPrefix;
+    const void *x;        /* per X position: k-mer index (unsigned short), HDP k-mer id (int) or nucleotide (char) */
+    const void *y;        /* events (3 doubles each) or nucleotides (char, 5-state) */
+    const double *yAux;   /* per event: log(noise) (vanilla) */
+    const void *models;   /* the machine's model blocks (DevHdpModel for HDP) */
+    double *F, *B;        /* forward-cell store, backward workspace */
+    long long *pairs;
+    double *pairLogp;
+    long long *nPairs, *totXay;
+    double *totVal;
+    long long *nTot;
+    double *dbgB;         /* backward-cell dump (strawMan, P.debug) */
+    double *expect;       /* Baum-Welch sums (expectation mode) */
+};
+
 /* lookup(): impl/pairwiseAligner.c:238-249 -- four cubics, float literals */
 __device__ __forceinline__ double cp_lookup(double x) {
     if (x <= 1.00f)

@@ -29,27 +29,11 @@
 #include <thread>
 #include <vector>
 
-extern "C" __global__ void cpecan_k_general(const DevItem *, DevParams, const int *, const int *,
-                                            const long long *, const unsigned short *,
-                                            const double *, const double *, double *, double *,
-                                            long long *, double *, long long *, long long *,
-                                            double *, long long *, double *, double *);
-extern "C" __global__ void cpecan_k_general5(const DevItem *, DevParams, const int *, const int *,
-                                             const long long *, const char *, const char *, const double *,
-                                             double *, double *, long long *, double *, long long *,
-                                             long long *, double *, long long *, double *, double *);
-extern "C" __global__ void cpecan_k_generalv(const DevItem *, DevParams, const int *, const int *,
-                                             const long long *, const unsigned short *, const double *,
-                                             const double *, const double *, double *, double *,
-                                             long long *, double *, long long *, long long *, double *,
-                                             long long *, double *);
-extern "C" __global__ void cpecan_k_general4(const DevItem *, DevParams, const int *, const int *, const long long *,
-                                             const unsigned short *, const double *, const double *, double *, double *,
-                                             long long *, double *, long long *, long long *, double *, long long *);
-extern "C" __global__ void cpecan_k_generalh(const DevItem *, DevParams, const int *, const int *,
-                                             const long long *, const int *, const double *,
-                                             const DevHdpModel *, double *, double *, long long *, double *,
-                                             long long *, long long *, double *, long long *, double *);
+extern "C" __global__ void cpecan_k_general(DevGeneralArgs, DevParams);
+extern "C" __global__ void cpecan_k_general4(DevGeneralArgs, DevParams);
+extern "C" __global__ void cpecan_k_general5(DevGeneralArgs, DevParams);
+extern "C" __global__ void cpecan_k_generalv(DevGeneralArgs, DevParams);
+extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
 #define W5_DECLARE(L)                                                                                             \
     extern "C" __global__ void cpecan_k_wave5_l##L(const DevItem *, DevParams, const int *, const int *,          \
                                                    const long long *, const char *, const char *, const double *, \
@@ -1826,53 +1810,41 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                            b->Fstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
                            em ? b->expect.p : nullptr);
         HIP_TRY(hipGetLastError());
-    } else if (b->dna) {
-        /* the forward sweep's two previous diagonals live in LDS where the widest band fits (3 diagonals of 5 states:
-         * 120 bytes per cell of width); CPECAN_GENERAL_LDS=0 keeps them in HBM (timing, tests) */
-        static const bool ldsOff = getenv("CPECAN_GENERAL_LDS") != nullptr && atoi(getenv("CPECAN_GENERAL_LDS")) == 0;
-        DevParams P5 = b->P;
-        P5.ldsWidth = (!ldsOff && b->maxWidth <= 248) ? b->maxWidth : 0;
-        hipLaunchKernelGGL(cpecan_k_general5, dim3((unsigned) b->nItems), dim3(256), (size_t) P5.ldsWidth * 120, c->stream,
-                           (const DevItem *) b->items.p, P5, (const int *) b->bandL.p,
-                           (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
-                           (const char *) b->chars.p, (const char *) b->charsY.p,
-                           (const double *) c->models5.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
-                           b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
-                           (double *) nullptr, b->mode == CPECAN_MODE_EXPECTATIONS ? b->expect.p : nullptr);
-        HIP_TRY(hipGetLastError());
-    } else if (b->hdp && b->kernel == CPECAN_KERNEL_GENERAL) {
-        hipLaunchKernelGGL(cpecan_k_generalh, dim3((unsigned) b->nItems), dim3(256), 0, c->stream,
-                           (const DevItem *) b->items.p, b->P, (const int *) b->bandL.p,
-                           (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
-                           (const int *) b->kid.p, (const double *) b->events.p,
-                           (const DevHdpModel *) c->modelsH.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
-                           b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
-                           b->mode == CPECAN_MODE_EXPECTATIONS ? b->expect.p : nullptr);
-        HIP_TRY(hipGetLastError());
-    } else if (b->sm4) {
-        hipLaunchKernelGGL(cpecan_k_general4, dim3((unsigned) b->nItems), dim3(256), 0, c->stream,
-                           (const DevItem *) b->items.p, b->P, (const int *) b->bandL.p, (const int *) b->bandR.p,
-                           (const long long *) b->cellPrefix.p, (const unsigned short *) b->kidx.p,
-                           (const double *) b->events.p, (const double *) c->models4.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
-                           b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p);
-        HIP_TRY(hipGetLastError());
-    } else if (b->vanilla && b->kernel == CPECAN_KERNEL_GENERAL) {
-        hipLaunchKernelGGL(cpecan_k_generalv, dim3((unsigned) b->nItems), dim3(256), 0, c->stream,
-                           (const DevItem *) b->items.p, b->P, (const int *) b->bandL.p,
-                           (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
-                           (const unsigned short *) b->kidx.p, (const double *) b->events.p,
-                           (const double *) b->logNoise.p, (const double *) c->modelsV.p, b->Fstore.p,
-                           b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p,
-                           b->nTot.p, b->mode == CPECAN_MODE_EXPECTATIONS ? b->expect.p : nullptr);
-        HIP_TRY(hipGetLastError());
-    } else if (b->kernel == CPECAN_KERNEL_GENERAL) {
-        hipLaunchKernelGGL(cpecan_k_general, dim3((unsigned) b->nItems), dim3(256), 0, c->stream,
-                           (const DevItem *) b->items.p, b->P, (const int *) b->bandL.p,
-                           (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
-                           (const unsigned short *) b->kidx.p, (const double *) b->events.p,
-                           (const double *) c->models.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
-                           b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
-                           b->dbgB.p, b->mode == CPECAN_MODE_EXPECTATIONS ? b->expect.p : nullptr);
+    } else if (b->dna || b->sm4 || b->kernel == CPECAN_KERNEL_GENERAL) {
+        /* the general kernels (cpecan_general.h): one per machine, one parameter list */
+        const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
+        DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
+                             (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p, nullptr, c->models.p,
+                             b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p,
+                             b->nTot.p, nullptr, em ? b->expect.p : nullptr };
+        DevParams P = b->P;
+        size_t lds = 0;
+        auto kernel = cpecan_k_general;
+        if (b->dna) {
+            /* the forward sweep's two previous diagonals live in LDS where the widest band fits (3 diagonals of 5
+             * states: 120 bytes per cell of width); CPECAN_GENERAL_LDS=0 keeps them in HBM (timing, tests) */
+            static const bool ldsOff = getenv("CPECAN_GENERAL_LDS") != nullptr && atoi(getenv("CPECAN_GENERAL_LDS")) == 0;
+            P.ldsWidth = (!ldsOff && b->maxWidth <= 248) ? b->maxWidth : 0;
+            lds = (size_t) P.ldsWidth * 120;
+            kernel = cpecan_k_general5;
+            a.x = b->chars.p;
+            a.y = b->charsY.p;
+            a.models = c->models5.p;
+        } else if (b->hdp && b->kernel == CPECAN_KERNEL_GENERAL) {
+            kernel = cpecan_k_generalh;
+            a.x = b->kid.p;
+            a.models = c->modelsH.p;
+        } else if (b->sm4) {
+            kernel = cpecan_k_general4;
+            a.models = c->models4.p;
+        } else if (b->vanilla && b->kernel == CPECAN_KERNEL_GENERAL) {
+            kernel = cpecan_k_generalv;
+            a.yAux = (const double *) b->logNoise.p;
+            a.models = c->modelsV.p;
+        } else {
+            a.dbgB = b->dbgB.p;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned) b->nItems), dim3(256), lds, c->stream, a, P);
         HIP_TRY(hipGetLastError());
     } else {
         /* one pass: the per-item track of emission constants (a function of the inputs, rebuilt every run inside the

@@ -68,6 +68,34 @@ def test_wave_kernels_fit_two_waves_per_simd(tmp_path, cells, hdp):
         assert int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1)) <= 192
 
 
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+@pytest.mark.parametrize("name,vgpr_cap,lds_cap", [("general", 168, 136), ("general4", 128, 8), ("general5", 128, 3464),
+                                                   ("generalv", 128, 1992), ("generalh", 168, 136)])
+def test_general_kernels_keep_their_occupancy(tmp_path, name, vgpr_cap, lds_cap):
+    """The five general kernels share one driver (cpecan_general.h) and differ in their machine: each keeps the waves
+    per SIMD it had as a kernel of its own (168 registers: three, 128: four), nothing in scratch, and no more static LDS
+    than its own E-step needs (the 5-state LDS diagonals are dynamic and come on top)."""
+    src = os.path.join(ROOT, "cpecan-signal_amd", "csrc", "cpecan_kernel_%s.hip" % name)
+    out = str(tmp_path / "g.s")
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                           "-fno-fast-math", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", out, src],
+                          stderr=subprocess.DEVNULL)
+    text = open(out).read()
+    kernel = "cpecan_k_" + name
+    meta = next(m for m in text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")
+                if ".name:           %s\n" % kernel in m)
+    vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
+    spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
+    lds = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1))
+    scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
+    body = text[text.index("\n" + kernel + ":"):]
+    body = body[:body.index("s_endpgm")]
+    assert vgpr <= vgpr_cap, "%s uses %d VGPRs (at most %d)" % (kernel, vgpr, vgpr_cap)
+    assert lds <= lds_cap, "%s takes %d bytes of static LDS (at most %d)" % (kernel, lds, lds_cap)
+    assert spill == 0 and scratch == 0 and "scratch_" not in body, "%s spills to scratch" % kernel
+
+
 def test_wave5_pair_kernels_fit_two_waves_per_simd(tmp_path):
     """The 5-state machine's two-waves-per-alignment kernels exist to put a forward and a backward wave on every SIMD
     of a small batch: each wave is allocated the registers of its own sweep only (256 at most: two waves per SIMD,
