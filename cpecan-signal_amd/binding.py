@@ -53,6 +53,7 @@ EXPORTS = [
     "cpecan_hip_models5_create", "cpecan_hip_batch_create_dna",
     "cpecan_hip_modelsv_create", "cpecan_hip_batch_create_vanilla", "cpecan_hip_models4_create", "cpecan_hip_batch_create_sm4",
     "cpecan_hip_modelsh_create", "cpecan_hip_batch_create_hdp",
+    "cpecan_hip_modelse_create", "cpecan_hip_batch_create_echelon",
 ]
 
 
@@ -81,6 +82,11 @@ class VanillaModelDesc(C.Structure):
     _fields_ = [("m_to_y_not_x", C.c_double), ("e_to_e", C.c_double), ("end_match_prob", C.c_double),
                 ("end_from_x_prob", C.c_double), ("end_from_y_prob", C.c_double),
                 ("match_probs", C.c_void_p), ("skip_probs", C.c_void_p), ("gap_y_probs", C.c_void_p)]
+
+
+class EchelonModelDesc(C.Structure):
+    _fields_ = [("end_match_prob", C.c_double), ("end_from_x_prob", C.c_double), ("match_probs", C.c_void_p),
+                ("skip_probs", C.c_void_p), ("gap_y_probs", C.c_void_p)]
 
 
 class HdpModelDesc(C.Structure):
@@ -160,6 +166,10 @@ def lib():
             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
             C.c_void_p, C.c_int64, C.POINTER(BandParams), C.c_int32, C.POINTER(C.c_void_p)]
         L.cpecan_hip_models4_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.cpecan_hip_modelse_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.cpecan_hip_batch_create_echelon.argtypes = [
+            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+            C.c_void_p, C.c_int64, C.POINTER(BandParams), C.c_int32, C.POINTER(C.c_void_p)]
         L.cpecan_hip_batch_create_sm4.argtypes = [
             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
             C.c_void_p, C.c_int64, C.POINTER(BandParams), C.c_int32, C.POINTER(C.c_void_p)]
@@ -363,6 +373,26 @@ class Context:
         _check(lib().cpecan_hip_models4_create(self.h, C.cast(descs, C.c_void_p), n, _ptr(ids)))
         return ids
 
+    def modelse_create(self, models):
+        """models: list of (end values[2] = end_match, end_from_x; match[20481], skip[60], gap_y[20481]) -> ids
+        (echelon signal machine, getStateMachineEchelon)"""
+        n = len(models)
+        descs = (EchelonModelDesc * n)()
+        keep = []
+        for i, (ends, match, skip, gy) in enumerate(models):
+            match = np.ascontiguousarray(match, dtype=np.float64)
+            skip = np.ascontiguousarray(skip, dtype=np.float64)
+            gy = np.ascontiguousarray(gy, dtype=np.float64)
+            assert match.size == MODEL_TABLE_LEN and gy.size == MODEL_TABLE_LEN and skip.size == 60 and len(ends) == 2
+            keep += [match, skip, gy]
+            descs[i].end_match_prob, descs[i].end_from_x_prob = float(ends[0]), float(ends[1])
+            descs[i].match_probs = match.ctypes.data
+            descs[i].skip_probs = skip.ctypes.data
+            descs[i].gap_y_probs = gy.ctypes.data
+        ids = np.zeros(n, np.int32)
+        _check(lib().cpecan_hip_modelse_create(self.h, C.cast(descs, C.c_void_p), n, _ptr(ids)))
+        return ids
+
     def modelsh_create(self, models):
         """models: list of (transitions[9], alphabet str, grid[G], y[rows, G], slope[rows, G],
         kmer_row[alphabet_size ** 6] int32) -> ids (HDP signal machine)"""
@@ -404,8 +434,9 @@ class Batch:
     """cpecan_batch: items is a numpy array of ITEM_DTYPE."""
 
     def __init__(self, ctx, items, x_chars, events, anchors, params, mode=MODE_POSTERIOR,
-                 kernel=KERNEL_AUTO, flags=0, y_chars=None, vanilla=False, hdp=False, sm4=False):
-        """events: double[n][3] for a signal batch (vanilla: with a modelsv_create model); y_chars
+                 kernel=KERNEL_AUTO, flags=0, y_chars=None, vanilla=False, hdp=False, sm4=False, echelon=False):
+        """events: double[n][3] for a signal batch (vanilla: with a modelsv_create model; echelon: with a
+        modelse_create model, an item's `reserved` = characters of its sequence past lX+5, 0..30); y_chars
         (str/bytes) instead for a DNA batch."""
         self.ctx = ctx
         items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
@@ -422,6 +453,11 @@ class Batch:
             _check(lib().cpecan_hip_batch_create_hdp(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
                                                      _ptr(ev), ev.size // 3, _ptr(an), an.shape[0],
                                                      C.byref(params), flags, C.byref(h)))
+        elif echelon:
+            ev = np.ascontiguousarray(events, dtype=np.float64).reshape(-1)
+            _check(lib().cpecan_hip_batch_create_echelon(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
+                                                         _ptr(ev), ev.size // 3, _ptr(an), an.shape[0],
+                                                         C.byref(params), flags, C.byref(h)))
         elif sm4:
             ev = np.ascontiguousarray(events, dtype=np.float64).reshape(-1)
             _check(lib().cpecan_hip_batch_create_sm4(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
@@ -443,6 +479,7 @@ class Batch:
         self.dna = y_chars is not None
         self.vanilla = bool(vanilla) and not self.dna
         self.hdp = bool(hdp) and not self.dna
+        self.echelon = bool(echelon) and not self.dna
 
     def run(self, after=None):
         """after: a Batch that has run (usually of another context): this batch's kernels are ordered behind its last
@@ -478,6 +515,8 @@ class Batch:
         _check(lib().cpecan_hip_batch_info(self.h, C.byref(k), C.byref(w), C.byref(m)))
         out = dict(kernel={1: "general", 2: "systolic"}.get(k.value, str(k.value)), workgroups=w.value,
                    max_band_width=m.value)
+        if self.echelon:
+            out["machine"] = "echelon"
         if self.dna:
             f = C.c_int32()
             _check(lib().cpecan_hip_batch_kernel_family(self.h, C.byref(f)))

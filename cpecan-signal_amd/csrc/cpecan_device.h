@@ -54,6 +54,10 @@
 #define CP_V_LAMBDA 4
 #define CP_V_LLAMBDA 5
 #define CP_VMODEL_STRIDE (CP_VHDR + 4097 * CP_VROW)
+/* echelon signal model block: the vanilla layout, its bins [log beta, log alpha, log(1-beta), log(1-alpha), 0], then
+ * log(n) for n = 0..5 (host libm) */
+#define CP_EMODEL_LOGN CP_VMODEL_STRIDE
+#define CP_EMODEL_STRIDE (CP_VMODEL_STRIDE + 8)
 #define CP_MODEL_HEADER 16 /* doubles in front of the rows: the 9 transitions */
 #define CP_MODEL_STRIDE (CP_MODEL_HEADER + 4097 * CP_ROW)
 
@@ -96,7 +100,7 @@ struct DevParams {
                           items on both paths and one item alternates between them; 0 (and any other value) none forced */
 };
 
-/* the arguments of the five general kernels (cpecan_general.h), one launch for all of them: each machine reads the
+/* the arguments of the general kernels (cpecan_general.h), one launch for all of them: each machine reads the
  * inputs it has and the host passes null for the others */
 struct DevGeneralArgs {
     const DevItem *items;
@@ -114,6 +118,13 @@ struct DevGeneralArgs {
     long long *nTot;
     double *dbgB;         /* backward-cell dump (strawMan, P.debug) */
     double *expect;       /* Baum-Welch sums (expectation mode) */
+};
+
+/* what the echelon kernel reads beside DevGeneralArgs (cpecan_kernel_generale.hip) */
+struct DevEchelonArgs {
+    const char *xChars;    /* per X position: the character (the look-ahead of multipleKmerMatchProb) */
+    const long long *xEnd; /* per item: X characters from x_offset on that belong to its sequence */
+    const double *yDur;    /* per event: the duration log-probabilities of 0..5 k-mers, host libm */
 };
 
 /* lookup(): impl/pairwiseAligner.c:238-249 -- four cubics, float literals */

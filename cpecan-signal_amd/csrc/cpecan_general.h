@@ -1,6 +1,6 @@
 /*
- * cpecan_general.h -- banded forward / backward / posterior DP for bands of ANY width: the driver of the five general
- * kernels, one per state machine (cpecan_kernel_general{,4,5,v,h}.hip).
+ * cpecan_general.h -- banded forward / backward / posterior DP for bands of ANY width: the driver of the six general
+ * kernels, one per state machine (cpecan_kernel_general{,4,5,v,h,e}.hip).
  *
  * One 256-thread workgroup per work item (= one getPosteriorProbsWithBanding call,
  * impl/pairwiseAligner.c:870-1006).  Threads stride over the cells of the current anti-diagonal;
@@ -21,6 +21,9 @@
  *   start_vector(raggedL, e[S]) / end_vector(raggedEnd, e[S])   the start and end state vectors;
  *   forward_cell(d, xmy, o[S]) / backward_cell(d, dTop, xmy, o[S]) its recurrences;
  *   match_into(middle, x, y)   the match state's mass reaching cell (x, y) from the forward cell (x-1, y-1);
+ *   kMultiMatch                whether states matchState..5 are all match states (the echelon machine), and then
+ *   step_into(middle, x, y, o[S])  every state's mass reaching cell (x, y) from (x-1, y-1) in place of match_into,
+ *                              and the decode emits s pairs per state s (diagonalCalculationMultiPosteriorMatchProbs);
  *   kDump                      whether it writes its backward cells to dbgB under P.debug;
  *   kExpect                    whether it has a Baum-Welch E-step, and then
  *   expect_diagonal(...)       what the E-step does with one posterior diagonal, and
@@ -38,6 +41,7 @@ struct GeneralCells {
     static constexpr int S = S_;
     static constexpr bool kExpect = false; /* has a Baum-Welch E-step */
     static constexpr bool kDump = false;   /* dumps its backward cells into dbgB under P.debug */
+    static constexpr bool kMultiMatch = false; /* states 1..5 are match states of s k-mers each (echelon) */
     const int *L, *R;
     const long long *pre; /* cell prefix per diagonal */
     double *F;            /* forward cells of this item */
@@ -64,6 +68,64 @@ struct GeneralCells {
     /* a second copy of forward diagonal d that the machine's forward sweep reads (none by default) */
     __device__ __forceinline__ double *lds_diagonal(long long) const { return nullptr; }
 };
+
+/* diagonalCalculationMultiPosteriorMatchProbs (impl/pairwiseAligner.c:797-839), by wave 0: per cell x-y ascending,
+ * every state s = 1..5 whose posterior reaches the threshold emits s pairs (x+n-1, y-1), n = 0..s-1, with the same
+ * posterior; a lane's pairs go to the slots after those of the lanes before it (a wave prefix sum of the counts) */
+template <int S>
+__device__ __forceinline__ void general_multi_decode(const DevGeneralArgs &a, const DevParams &P, const DevItem &it,
+                                                     long long d2, int l2, int w2, const double *fdd, const double *bdd,
+                                                     double total, long long &myPairs) {
+    const int lane = threadIdx.x & 63;
+    for (int base = 0; base < w2; base += 64) {
+        const int cc = base + lane;
+        double e[6];
+        int cnt = 0;
+        long long x = 0, y = 0;
+#pragma unroll
+        for (int s = 1; s < 6; s++) e[s] = CP_NEG_INF;
+        unsigned hits = 0;
+        if (cc < w2) {
+            const int xmy = l2 + 2 * cc;
+            x = (d2 + xmy) / 2;
+            y = (d2 - xmy) / 2;
+            if (x > 0 && y > 0) {
+#pragma unroll
+                for (int s = 1; s < 6; s++) {
+                    e[s] = (fdd[cc * S + s] + bdd[cc * S + s]) - total;
+                    if (exp(e[s]) >= P.threshold) {
+                        hits |= 1u << s;
+                        cnt += s;
+                    }
+                }
+            }
+        }
+        int incl = cnt; /* inclusive prefix sum of the counts over the wave */
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(incl, off);
+            if (lane >= off) incl += t;
+        }
+        const int all = __shfl(incl, 63);
+        long long idx = myPairs + (incl - cnt);
+        for (int s = 1; s < 6; s++) {
+            if (!((hits >> s) & 1u)) continue;
+            double p = exp(e[s]);
+            if (p > 1.0) p = 1.0;
+            const long long score = (long long) floor(p * 10000000.0);
+            for (int n = 0; n < s; n++, idx++) {
+                if (idx < it.pairCap) {
+                    long long *o = a.pairs + (it.pairBase + idx) * 3;
+                    o[0] = score;
+                    o[1] = x + n - 1;
+                    o[2] = y - 1;
+                    a.pairLogp[it.pairBase + idx] = e[s];
+                }
+            }
+        }
+        myPairs += all;
+    }
+}
 
 /* one work item (blockIdx.x) through machine m */
 template <class M>
@@ -176,11 +238,21 @@ __device__ __forceinline__ void general_pass(M &m, const DevGeneralArgs &a, cons
                             if (valid) {
                                 const int xmy = l3 + 2 * cc;
                                 const double *mid = m.fcell(d2 - 1, xmy);
-                                double mm = CP_NEG_INF;
-                                if (mid) mm = m.match_into(mid, (d2 + 1 + xmy) / 2, (d2 + 1 - xmy) / 2);
-                                v = mm + b3[cc * S];
+                                if constexpr (M::kMultiMatch) {
+                                    double st[S];
 #pragma unroll
-                                for (int s = 1; s < S; s++) v = cp_logAdd(v, CP_NEG_INF + b3[cc * S + s]);
+                                    for (int s = 0; s < S; s++) st[s] = CP_NEG_INF;
+                                    if (mid) m.step_into(mid, (d2 + 1 + xmy) / 2, (d2 + 1 - xmy) / 2, st);
+                                    v = st[0] + b3[cc * S];
+#pragma unroll
+                                    for (int s = 1; s < S; s++) v = cp_logAdd(v, st[s] + b3[cc * S + s]);
+                                } else {
+                                    double mm = CP_NEG_INF;
+                                    if (mid) mm = m.match_into(mid, (d2 + 1 + xmy) / 2, (d2 + 1 - xmy) / 2);
+                                    v = mm + b3[cc * S];
+#pragma unroll
+                                    for (int s = 1; s < S; s++) v = cp_logAdd(v, CP_NEG_INF + b3[cc * S + s]);
+                                }
                             }
                             acc2 = cp_wave_seq_fold(acc2, v, valid);
                         }
@@ -215,6 +287,11 @@ __device__ __forceinline__ void general_pass(M &m, const DevGeneralArgs &a, cons
                     __syncthreads();
                     continue;
                 }
+            }
+            if constexpr (M::kMultiMatch) {
+                if (wave == 0) general_multi_decode<S>(a, P, it, d2, l2, w2, fdd, bdd, total, myPairs);
+                __syncthreads();
+                continue;
             }
             if (wave == 0) {
                 /* diagonalCalculationPosteriorMatchProbs :756-795, ordered emission by wave 0 */

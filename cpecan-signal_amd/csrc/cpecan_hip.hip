@@ -31,6 +31,7 @@
 
 extern "C" __global__ void cpecan_k_general(DevGeneralArgs, DevParams);
 extern "C" __global__ void cpecan_k_general4(DevGeneralArgs, DevParams);
+extern "C" __global__ void cpecan_k_generale(DevGeneralArgs, DevParams, DevEchelonArgs);
 extern "C" __global__ void cpecan_k_general5(DevGeneralArgs, DevParams);
 extern "C" __global__ void cpecan_k_generalv(DevGeneralArgs, DevParams);
 extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
@@ -481,6 +482,9 @@ struct cpecan_ctx {
     int nModels4 = 0;
     std::vector<double> hostModelsV;
     int nModelsV = 0;
+    DevBuf<double> modelsE; /* echelon signal models, nModelsE * CP_EMODEL_STRIDE */
+    std::vector<double> hostModelsE;
+    int nModelsE = 0;
 };
 
 struct cpecan_batch {
@@ -494,8 +498,10 @@ struct cpecan_batch {
     DevBuf<long long> cellPrefix;
     DevBuf<char> chars, charsY; /* charsY: DNA batches (5-state machine) */
     bool dna = false;
-    bool vanilla = false, hdp = false, sm4 = false;
-    DevBuf<double> logNoise; /* vanilla batches: log(event noise), host libm */
+    bool vanilla = false, hdp = false, sm4 = false, echelon = false;
+    DevBuf<double> logNoise; /* vanilla and echelon batches: log(event noise), host libm */
+    DevBuf<double> duration; /* echelon batches: per event the duration terms of 0..5 k-mers, host libm */
+    DevBuf<long long> xEnd;  /* echelon batches: per item the X characters that belong to its sequence */
     DevBuf<int> kid;         /* HDP batches: k-mer id over the model's alphabet per X position */
     DevBuf<unsigned short> kidx;
     DevBuf<double> events;
@@ -971,6 +977,14 @@ int cpecan_hip_selftest_division(cpecan_ctx *c, int64_t n, uint64_t seed, int64_
     return CPECAN_OK;
 }
 
+/* emissions_signal_getDurationProb -> poissonPosteriorProb (impl/stateMachine.c:345-370, :551-554): the log
+ * posterior of n k-mers given the event's duration (its third value), with the host libm's log */
+static double echelon_duration(const double *event, int n) {
+    static const double logFactorial[6] = { 0.0, 0.0, 0.69314718056, 1.79175946923, 3.17805383035, 4.78749174278 };
+    const double lambda = event[2] / 0.00332005312085;
+    return (n + 1) * 0.1397619423751586 + n * log(lambda) - logFactorial[n] - 2 * lambda;
+}
+
 /* Device block of one vanilla model.  Every log() the reference takes per cell
  * (stateMachine3Vanilla_cellCalculate :1391-1407, logGaussPdf :338, logInvGaussPdf :328) depends on the
  * skip bin or the k-mer only: taken here once, with the host libm the reference would call. */
@@ -1044,6 +1058,52 @@ int cpecan_hip_modelsv_create(cpecan_ctx *c, const cpecan_vanilla_model *models,
     if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpy(c->modelsV.p, c->hostModelsV.data(), c->hostModelsV.size() * sizeof(double),
                       hipMemcpyHostToDevice));
+    return CPECAN_OK;
+}
+
+/* Device block of one echelon model: the vanilla layout (rows, end values) with the machine's own per-bin logs
+ * (stateMachineEchelon_cellCalculate :1418-1425: log beta, log alpha, log(1 - beta), log(1 - alpha)) and log(n) of
+ * emissions_signal_multipleKmerMatchProb (:548), all taken with the host libm. */
+static void derive_echelon(const cpecan_echelon_model *m, double *dst) {
+    cpecan_vanilla_model v = {};
+    v.end_match_prob = m->end_match_prob;
+    v.end_from_x_prob = m->end_from_x_prob;
+    v.match_probs = m->match_probs;
+    v.skip_probs = m->skip_probs;
+    v.gap_y_probs = m->gap_y_probs;
+    derive_vanilla(&v, dst);
+    for (int i = 0; i < CP_VHDR; i++) dst[i] = 0.0;
+    dst[CP_VHDR_END_M] = m->end_match_prob;
+    dst[CP_VHDR_END_X] = m->end_from_x_prob;
+    for (int bin = 0; bin < 30; bin++) {
+        const double a_mx = m->skip_probs[bin], a_mh = 1 - a_mx;
+        const double a_xx = m->skip_probs[bin + 30], a_xh = 1 - a_xx;
+        double *b = dst + CP_VHDR_BINS + bin * 5;
+        b[0] = log(a_mx);
+        b[1] = log(a_xx);
+        b[2] = log(a_mh);
+        b[3] = log(a_xh);
+        b[4] = 0.0;
+    }
+    for (int n = 0; n < 8; n++) dst[CP_EMODEL_LOGN + n] = n >= 1 && n <= 5 ? log((double) n) : 0.0;
+}
+
+int cpecan_hip_modelse_create(cpecan_ctx *c, const cpecan_echelon_model *models, int32_t n, int32_t *ids) {
+    if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
+    for (int i = 0; i < n; i++)
+        if (!models[i].match_probs || !models[i].skip_probs || !models[i].gap_y_probs)
+            return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t old = c->hostModelsE.size();
+    c->hostModelsE.resize(old + (size_t) n * CP_EMODEL_STRIDE);
+    for (int i = 0; i < n; i++) {
+        derive_echelon(&models[i], c->hostModelsE.data() + old + (size_t) i * CP_EMODEL_STRIDE);
+        ids[i] = c->nModelsE + i;
+    }
+    if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream)); /* (the old table goes back to the allocator's cache) */
+    HIP_TRY(c->modelsE.alloc(c->hostModelsE.size()));
+    HIP_TRY(hipMemcpy(c->modelsE.p, c->hostModelsE.data(), c->hostModelsE.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->nModelsE += n;
     return CPECAN_OK;
 }
 
@@ -1165,6 +1225,9 @@ int cpecan_hip_models_clear(cpecan_ctx *c) {
     c->models4.release();
     c->hostModels4.clear();
     c->nModels4 = 0;
+    c->modelsE.release();
+    c->hostModelsE.clear();
+    c->nModelsE = 0;
     for (auto *t : c->hdpTables) delete t;
     c->hdpTables.clear();
     c->hostModelsH.clear();
@@ -1218,9 +1281,12 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
                              const char *xChars, int64_t nX, const double *events, const char *yChars,
                              int64_t nEvents, const int64_t *anchors, int64_t nAnchorPairs,
                              const cpecan_band_params *params, int32_t mode, int32_t kernel,
-                             int32_t flags, cpecan_batch **out, bool vanilla = false, bool hdp = false, bool sm4 = false) {
+                             int32_t flags, cpecan_batch **out, bool vanilla = false, bool hdp = false, bool sm4 = false,
+                             bool echelon = false) {
     if (sm4 && (mode != CPECAN_MODE_POSTERIOR || (flags & CPECAN_FLAG_DEBUG_DUMP)))
         return fail(CPECAN_EINVAL, "4-state batches: posterior decode only, no cell dumps");
+    if (echelon && (mode != CPECAN_MODE_POSTERIOR || (flags & CPECAN_FLAG_DEBUG_DUMP)))
+        return fail(CPECAN_EINVAL, "echelon batches: posterior decode only, no cell dumps");
     const bool dna = yChars != nullptr;
     if (hdp && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "HDP batches: no cell dumps");
     if (hdp && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
@@ -1228,7 +1294,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     if (vanilla && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "vanilla batches: no cell dumps");
     if (vanilla && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
         return fail(CPECAN_EINVAL, "expectations run over the banded matrix only");
-    const int S = dna ? 5 : sm4 ? 4 : 3; /* states per cell */
+    const int S = dna ? 5 : echelon ? 7 : sm4 ? 4 : 3; /* states per cell */
     if (!c || !items || nItems <= 0 || !xChars || (!events && !yChars) || !params || !out)
         return fail(CPECAN_EINVAL, "bad argument");
     if (dna && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "DNA batches: no cell dumps");
@@ -1266,7 +1332,11 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
             s.anchor_offset < 0 || s.x_offset + s.lX + (!dna && s.lX > 0 ? 5 : 0) > nX ||
             s.y_offset + s.lY > nEvents || s.anchor_offset + s.n_anchors > nAnchorPairs)
             return fail(CPECAN_EINVAL, "item %lld points outside the supplied buffers", (long long) i);
+        if (echelon && (s.reserved < 0 || s.reserved > 30 || (s.lX > 0 && s.x_offset + s.lX + 5 + s.reserved > nX)))
+            return fail(CPECAN_EINVAL, "item %lld: its look-ahead (reserved = %d) points outside the supplied characters",
+                        (long long) i, s.reserved);
         if (s.model_id < 0 || s.model_id >= (dna ? c->nModels5 : vanilla ? c->nModelsV : sm4 ? c->nModels4
+                                                      : echelon ? c->nModelsE
                                                       : hdp ? (int) c->hostModelsH.size() : c->nModels))
             return fail(CPECAN_EINVAL, "item %lld: unknown model id %d", (long long) i, s.model_id);
         if (s.lX + s.lY >= (1ll << 30)) return fail(CPECAN_EINVAL, "item %lld too long", (long long) i);
@@ -1287,7 +1357,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
      * item's intervals stays in its cache. */
     PinnedBuf<int> hTab;
     /* the assembly sweeps' plan (build_asm_plan), for the batches that can run on them */
-    const bool wantPlan = !dna && !vanilla && !hdp && !sm4 && !unbanded && mode == CPECAN_MODE_POSTERIOR &&
+    const bool wantPlan = !dna && !vanilla && !hdp && !sm4 && !echelon && !unbanded && mode == CPECAN_MODE_POSTERIOR &&
                           kernel != CPECAN_KERNEL_GENERAL && use_wave_kernels() && !(flags & CPECAN_FLAG_WORKGROUP_KERNELS) &&
                           !(flags & CPECAN_FLAG_DEBUG_DUMP);
     std::vector<std::vector<AsmPlanWin>> planWins(wantPlan ? (size_t) nItems : 0);
@@ -1388,7 +1458,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
         return CPECAN_OK;
     };
     /* (what the kernel choice below will come to, as far as it is known before the bands are) */
-    const bool surelyGeneral = dna || sm4 || kernel == CPECAN_KERNEL_GENERAL || unbanded || (flags & CPECAN_FLAG_DEBUG_DUMP) ||
+    const bool surelyGeneral = dna || sm4 || echelon || kernel == CPECAN_KERNEL_GENERAL || unbanded || (flags & CPECAN_FLAG_DEBUG_DUMP) ||
                                ((hdp || vanilla) && (flags & CPECAN_FLAG_GENERAL_KERNEL));
     HIP_TRY(hTab.alloc((size_t) diagTotal * 2 + 2));
     {
@@ -1410,7 +1480,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
         /* the HDP machine scores with linear densities (quirk Q6): its posteriors are flat and far more
          * cells pass the threshold (2887 pairs for a ~800-event read in the reference's own test); a batch whose
          * counts outgrow this first guess is re-run with the counted sizes (ensure_counts) */
-        d.pairCap = (hdp ? 16 : 4) * (s.lX + s.lY) + 64;
+        d.pairCap = (hdp || echelon ? 16 : 4) * (s.lX + s.lY) + 64; /* (echelon: up to 15 pairs a cell) */
         pairTotal += d.pairCap;
         d.totBase = totTotal;
         d.totCap = (nDiag + 9) / 10 + nDiag / std::max<long long>(1, params->minDiagsBetweenTraceBack -
@@ -1429,8 +1499,8 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     b->nItems = nItems;
     b->mode = mode;
     b->flags = flags;
-    b->compactPairs = maxLXY < 65536;
-    b->nModels = dna ? c->nModels5 : vanilla ? c->nModelsV : sm4 ? c->nModels4 : hdp ? (int) c->hostModelsH.size() : c->nModels;
+    b->compactPairs = maxLXY + (echelon ? 4 : 0) < 65536; /* (an echelon pair's x reaches lX + 3) */
+    b->nModels = dna ? c->nModels5 : vanilla ? c->nModelsV : sm4 ? c->nModels4 : echelon ? c->nModelsE : hdp ? (int) c->hostModelsH.size() : c->nModels;
     b->expectLen = dna ? CPECAN_EXPECTATION5_LEN : vanilla ? CPECAN_EXPECTATIONV_LEN
                    : hdp ? CPECAN_EXPECTATIONH_LEN : CPECAN_EXPECTATION_LEN;
     b->P.threshold = params->threshold;
@@ -1449,7 +1519,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
      * the E-step (the 5-state machine runs on the general kernel); CPECAN_FLAG_GENERAL_KERNEL keeps such a batch on
      * the general kernel */
     const bool machineWave = (hdp || vanilla) && !(flags & CPECAN_FLAG_GENERAL_KERNEL);
-    int useKernel = dna || sm4 || ((hdp || vanilla) && !machineWave) ? CPECAN_KERNEL_GENERAL
+    int useKernel = dna || sm4 || echelon || ((hdp || vanilla) && !machineWave) ? CPECAN_KERNEL_GENERAL
                     : hdp || vanilla ? CPECAN_KERNEL_AUTO : kernel;
     /* the builds of the register-resident kernels this batch would run on, and the widest band they take */
     const SyBuild *fam = hdp ? HV_BUILDS : vanilla ? VV_BUILDS
@@ -1459,6 +1529,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     b->vanilla = vanilla;
     b->hdp = hdp;
     b->sm4 = sm4;
+    b->echelon = echelon;
     if (useKernel == CPECAN_KERNEL_AUTO)
         useKernel = (globalMaxWidth <= famMaxWidth && systolicOk && !b->P.debug && !unbanded)
                         ? CPECAN_KERNEL_SYSTOLIC : CPECAN_KERNEL_GENERAL;
@@ -1498,7 +1569,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
         B_TRY(hipMemcpyAsync(b->charsY.p, yChars, (size_t) nEvents, hipMemcpyHostToDevice, c->prep));
     } else {
         B_TRY(b->events.alloc((size_t) 3 * nEvents + 8));
-        if (vanilla) {
+        if (vanilla || echelon) {
             /* the batch's own copy of the events carries log(noise) (host libm, :325) in place of the duration, which
              * nothing on the device reads: the wave kernels stage events from this one array */
             std::vector<double, NoInit<double>> ev3((size_t) 3 * nEvents);
@@ -1511,7 +1582,19 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
             B_TRY(hipStreamSynchronize(c->prep)); /* ev3 ends here */
         } else
             B_TRY(hipMemcpyAsync(b->events.p, events, (size_t) 3 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
-        if (vanilla) { /* emissions_signal_logInvGaussPdf takes log(eventNoise) per cell (:325) */
+        if (echelon) { /* emissions_signal_getDurationProb (:551-554) of 0..5 k-mers per event */
+            std::vector<double> du((size_t) 6 * nEvents + 6);
+            for (int64_t i = 0; i < nEvents; i++)
+                for (int k = 0; k < 6; k++) du[(size_t) (6 * i + k)] = echelon_duration(events + 3 * i, k);
+            B_TRY(b->duration.alloc((size_t) 6 * nEvents + 8));
+            B_TRY(hipMemcpyAsync(b->duration.p, du.data(), (size_t) 6 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
+            std::vector<long long> xe((size_t) nItems);
+            for (int64_t i = 0; i < nItems; i++) xe[(size_t) i] = items[i].lX > 0 ? items[i].lX + 5 + items[i].reserved : 0;
+            B_TRY(b->xEnd.alloc((size_t) nItems));
+            B_TRY(hipMemcpyAsync(b->xEnd.p, xe.data(), (size_t) nItems * sizeof(long long), hipMemcpyHostToDevice, c->prep));
+            B_TRY(hipStreamSynchronize(c->prep)); /* du and xe end here */
+        }
+        if (vanilla || echelon) { /* emissions_signal_logInvGaussPdf takes log(eventNoise) per cell (:325) */
             std::vector<double> ln((size_t) nEvents + 1);
             for (int64_t i = 0; i < nEvents; i++) ln[(size_t) i] = log(events[3 * i + 1]);
             B_TRY(b->logNoise.alloc((size_t) nEvents + 8));
@@ -1763,6 +1846,17 @@ int cpecan_hip_batch_create_sm4(cpecan_ctx *c, const cpecan_item *items, int64_t
                              CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out, false, false, true);
 }
 
+int cpecan_hip_batch_create_echelon(cpecan_ctx *c, const cpecan_item *items, int64_t nItems, const char *xChars,
+                                    int64_t nX, const double *events, int64_t nEvents, const int64_t *anchors,
+                                    int64_t nAnchorPairs, const cpecan_band_params *params, int32_t flags,
+                                    cpecan_batch **out) {
+    if (flags & CPECAN_FLAG_EXPECTATIONS)
+        return fail(CPECAN_EINVAL, "echelon batches: posterior decode only (the reference has no expectations for this machine)");
+    if (!events) return fail(CPECAN_EINVAL, "bad argument");
+    return batch_create_impl(c, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
+                             CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out, false, false, false, true);
+}
+
 int cpecan_hip_batch_run(cpecan_batch *b) { return cpecan_hip_batch_run_after(b, nullptr); }
 
 int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
@@ -1809,6 +1903,15 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                            (const char *) b->chars.p, (const char *) b->charsY.p, (const double *) c->models5.p,
                            b->Fstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
                            em ? b->expect.p : nullptr);
+        HIP_TRY(hipGetLastError());
+    } else if (b->echelon) {
+        /* the echelon machine on the general driver (cpecan_kernel_generale.hip) */
+        DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
+                             (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p,
+                             (const double *) b->logNoise.p, c->modelsE.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
+                             b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p, nullptr, nullptr };
+        DevEchelonArgs e = { (const char *) b->chars.p, (const long long *) b->xEnd.p, (const double *) b->duration.p };
+        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, c->stream, a, b->P, e);
         HIP_TRY(hipGetLastError());
     } else if (b->dna || b->sm4 || b->kernel == CPECAN_KERNEL_GENERAL) {
         /* the general kernels (cpecan_general.h): one per machine, one parameter list */

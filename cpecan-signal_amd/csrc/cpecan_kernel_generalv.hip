@@ -7,13 +7,13 @@
  * logInvGaussPdf :322-331), X elements read as sequence_getKmer2 does (impl/pairwiseAligner.c:320-325).
  *
  * On the general driver (cpecan_general.h): any band width, posterior decode and Baum-Welch
- * expectations.
+ * expectations.  The inputs and the emission are shared with the echelon kernel (cpecan_general_twodists.h).
  *
  * Every log() the reference takes per cell is a function of the skip bin, the k-mer or the event
  * alone, so the host takes them once with its libm (cpecan_hip.hip: derive_vanilla); the device
  * adds them in the reference's order.
  */
-#include "cpecan_general.h"
+#include "cpecan_general_twodists.h"
 
 namespace {
 
@@ -25,58 +25,13 @@ __device__ __forceinline__ double match_fromv(const double *middle, double eP, c
     return m;
 }
 
-struct Vanilla : GeneralCells<3> {
+struct Vanilla : TwoDistCells<3> {
     static constexpr bool kExpect = true;
-    const unsigned short *kidx; /* k-mer index per X character position (4096 = not a k-mer) */
-    const double *ev;           /* events, 3 doubles each */
-    const double *lnoise;       /* log(event noise), host libm */
-    const double *hdr;          /* model header: scalars and per-bin log transition probabilities */
-    const double *rows;         /* CP_VROW doubles per k-mer */
     double (*sExp)[CP_EXPECTV_LEN + 1]; /* the E-step's sums in LDS, one copy per wave */
 
     __device__ Vanilla(const DevGeneralArgs &a, const DevItem &it, double (*sExp_)[CP_EXPECTV_LEN + 1])
-        : GeneralCells<3>(a, it), sExp(sExp_) {
-        kidx = (const unsigned short *) a.x + it.xOff;
-        ev = (const double *) a.y + 3 * it.yOff;
-        lnoise = a.yAux + it.yOff;
-        hdr = (const double *) a.models + (long long) it.model * CP_VMODEL_STRIDE;
-        rows = hdr + CP_VHDR;
-    }
+        : TwoDistCells<3>(a, it, CP_VMODEL_STRIDE), sExp(sExp_) {}
 
-    /* the two k-mers sequence_getKmer2 exposes for sequence index ix: a pointer to character
-     * max(ix-1, 0); the skip bin looks at the k-mers at +0 and +1, the emission at the one at +1
-     * (so sequence index 0 is scored with k-mer 1, as in the reference) */
-    __device__ __forceinline__ void kmers_of(long long ix, int &kPrev, int &kCur) const {
-        const long long p = ix > 0 ? ix - 1 : 0;
-        kPrev = kidx[p];
-        kCur = kidx[p + 1];
-    }
-    /* per-bin log transition probabilities: [bin][log a_mx, log a_xx, log a_mm, log a_xm, log a_my] */
-    __device__ __forceinline__ const double *bin_logs(int kPrev, int kCur) const {
-        const double d = fabs(rows[(long long) kCur * CP_VROW + CP_V_MU] - rows[(long long) kPrev * CP_VROW + CP_V_MU]);
-        long long bin = (long long) (d / 0.5);
-        if (bin >= 30) bin = 29;
-        return hdr + CP_VHDR_BINS + bin * 5;
-    }
-    /* emissions_signal_getEventMatchProbWithTwoDists on table `o` (0: match table, 6: extra-event table) */
-    __device__ __forceinline__ double emit2(int k, long long iy, int o) const {
-        const double *r = rows + (long long) k * CP_VROW + o;
-        double mean, noise, lnz;
-        if (iy >= 0) {
-            mean = ev[3 * iy];
-            noise = ev[3 * iy + 1];
-            lnz = lnoise[iy];
-        } else { /* NULLEVENT {-inf, 0} (:261): log(0) = -inf */
-            mean = CP_NEG_INF;
-            noise = 0.0;
-            lnz = CP_NEG_INF;
-        }
-        const double level = cp_logGauss(mean, r[CP_V_MU], r[CP_V_SD], r[CP_V_K]);
-        const double a = (noise - r[CP_V_NMU]) / r[CP_V_NMU];
-        const double l_twoPi = 1.8378770664093453;
-        const double nz = (r[CP_V_LLAMBDA] - l_twoPi - 3 * lnz - r[CP_V_LAMBDA] * a * a / noise) / 2;
-        return level + nz;
-    }
     __device__ __forceinline__ double match_into(const double *middle, long long x, long long y) const {
         int kPrev, kCur;
         kmers_of(x - 1, kPrev, kCur);

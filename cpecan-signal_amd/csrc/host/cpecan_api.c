@@ -583,6 +583,24 @@ StateMachine *getSignalStateMachine3Vanilla(const char *modelFile) {
     }
     return (StateMachine *) s;
 }
+StateMachine *getStateMachineEchelon(const char *modelFile) { /* impl/stateMachine.c:1773-1784 */
+    StateMachine *sM = stateMachineEchelon_construct(echelon, NUM_OF_KMERS, emissions_signal_initEmissionsToZero,
+                                                     emissions_signal_getDurationProb,
+                                                     emissions_signal_getBetaOrAlphaSkipProb,
+                                                     emissions_signal_multipleKmerMatchProb,
+                                                     emissions_signal_getEventMatchProbWithTwoDists, NULL);
+    if (modelFile) { /* emissions_signal_loadPoreModel :242-320: the skip bins serve as beta and alpha, as for vanilla */
+        const int64_t tableLen = 1 + NUM_OF_KMERS * MODEL_PARAMS;
+        FILE *f = fopen(modelFile, "r");
+        if (!f) die("cpecan: cannot open pore model %s", modelFile);
+        if (!read_doubles(f, sM->EMISSION_MATCH_PROBS, tableLen) || !read_doubles(f, sM->EMISSION_GAP_X_PROBS, 30) ||
+            !read_doubles(f, sM->EMISSION_GAP_Y_PROBS, tableLen))
+            die("This stateMachine is not correct for signal model (%s)", modelFile);
+        fclose(f);
+        for (int i = 0; i < 30; i++) sM->EMISSION_GAP_X_PROBS[i + 30] = sM->EMISSION_GAP_X_PROBS[i];
+    }
+    return sM;
+}
 void stateMachine3Vanilla_setStrandTransitionsToDefaults(StateMachine *sM, Strand strand) {
     StateMachine3Vanilla *s = (StateMachine3Vanilla *) sM;
     s->TRANSITION_M_TO_Y_NOT_X = strand == template ? 0.17f : 0.14f;
@@ -780,7 +798,7 @@ static cpecan_ctx *context(void) {
 /* returns 1 for the DNA-against-DNA combination (5-state machine, sequence_getBase on both sides),
  * 2 for k-mers against events under the vanilla machine (sequence_getKmer2), 3 under the HDP machine
  * (sequence_getKmer3), 4 under the 4-state signal machine and 0 under the 3-state strawMan machine (both
- * sequence_getKmer); anything else is not on the GPU path */
+ * sequence_getKmer), 5 under the echelon machine (sequence_getKmer2); anything else is not on the GPU path */
 static int check_known_combination(StateMachine *sM, Sequence *sX, Sequence *sY) {
     if (!cpecan_sm_functions_known(sM))
         die("cpecan: this StateMachine carries a cellCalculate or emission function of the caller's own; the GPU path "
@@ -802,13 +820,18 @@ static int check_known_combination(StateMachine *sM, Sequence *sX, Sequence *sY)
             die("cpecan: the vanilla machine needs sequence_getKmer2 / sequence_getEvent element getters");
         return 2;
     }
+    if (sM->type == echelon && sM->stateNumber == 7) {
+        if (sX->get != sequence_getKmer2 || sY->get != sequence_getEvent)
+            die("cpecan: the echelon machine needs sequence_getKmer2 / sequence_getEvent element getters");
+        return 5;
+    }
     if (sM->type == fourState && sM->stateNumber == 4) {
         if (sX->get != sequence_getKmer || sY->get != sequence_getEvent)
             die("cpecan: the 4-state machine needs sequence_getKmer / sequence_getEvent element getters");
         return 4;
     }
     if (sM->type != threeState || sM->stateNumber != 3)
-        die("cpecan: only the threeState (strawMan), fourState, vanilla and HDP signal StateMachines and the fiveState "
+        die("cpecan: only the threeState (strawMan), fourState, vanilla, echelon and HDP signal StateMachines and the fiveState "
             "symbol StateMachine run on the GPU path (type %d)", sM->type);
     if (sX->get != sequence_getKmer || sY->get != sequence_getEvent)
         die("cpecan: the GPU path needs sequence_getKmer / sequence_getEvent element getters");
@@ -827,8 +850,11 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
     cpecan_ctx *ctx = context();
     int64_t nX = 0, nY = 0, nA = 0, nItems = 0, capItems = 0;
     const int kind = n > 0 ? check_known_combination(sMs[0], sXs[0], sYs[0]) : 0;
-    const int dna = kind == 1, van = kind == 2, hdp = kind == 3, sm4 = kind == 4;
+    const int dna = kind == 1, van = kind == 2, hdp = kind == 3, sm4 = kind == 4, ech = kind == 5;
     if (sm4 && mode != 0) die("cpecan: the 4-state machine has no expectations (the reference has no Hmm for it)");
+    if (ech && (mode != 0 || unbanded == 2))
+        die("cpecan: the echelon machine has posterior decode only, through getAlignedPairsUsingAnchors, "
+            "getAlignedPairsWithoutBanding or getAlignedPairsUsingAnchorsBatch (the reference has no expectations for it)");
     const int64_t xPad = dna ? 0 : KMER_LENGTH - 1; /* a k-mer sequence of lX elements spans lX + 5 chars */
     for (int64_t i = 0; i < n; i++) {
         if (check_known_combination(sMs[i], sXs[i], sYs[i]) != kind)
@@ -941,12 +967,31 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
         }
         modelOf[i] = found;
     }
+    cpecan_echelon_model *modelsE = malloc(sizeof(cpecan_echelon_model) * (size_t) (ech ? n : 1));
+    for (int64_t i = 0; ech && i < n; i++) { /* one model per distinct StateMachineEchelon */
+        int32_t found = -1;
+        for (int32_t k = 0; k < nModels && found < 0; k++)
+            if (owner5[k] == sMs[i]) found = k;
+        if (found < 0) {
+            const StateMachineEchelon *se = (const StateMachineEchelon *) sMs[i];
+            cpecan_echelon_model *m = &modelsE[nModels];
+            m->end_match_prob = se->DEFAULT_END_MATCH_PROB;
+            m->end_from_x_prob = se->DEFAULT_END_FROM_X_PROB;
+            m->match_probs = sMs[i]->EMISSION_MATCH_PROBS;
+            m->skip_probs = sMs[i]->EMISSION_GAP_X_PROBS;
+            m->gap_y_probs = sMs[i]->EMISSION_GAP_Y_PROBS;
+            owner5[nModels] = sMs[i];
+            found = nModels++;
+        }
+        modelOf[i] = found;
+    }
     int32_t *ids = malloc(sizeof(int32_t) * (size_t) nModels);
     CHECK(cpecan_hip_models_clear(ctx));
     if (dna) CHECK(cpecan_hip_models5_create(ctx, models5, nModels, ids));
     else if (van) CHECK(cpecan_hip_modelsv_create(ctx, modelsV, nModels, 0, ids));
     else if (hdp) CHECK(cpecan_hip_modelsh_create(ctx, modelsH, nModels, ids));
     else if (sm4) CHECK(cpecan_hip_models4_create(ctx, models4, nModels, ids));
+    else if (ech) CHECK(cpecan_hip_modelse_create(ctx, modelsE, nModels, ids));
     else CHECK(cpecan_hip_models_create(ctx, models, nModels, 0, ids));
 
     int64_t xo = 0, yo = 0, ao = 0;
@@ -992,6 +1037,9 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
             it->model_id = ids[modelOf[i]];
             it->ragged_left = raggedL || r > 0;
             it->ragged_right = raggedR || r < nSp - 1;
+            /* the echelon look-ahead of a sub-alignment reads on into the rest of the read (the reference slices the
+             * sequence by offsetting its pointer, :1400) */
+            if (ech) it->reserved = (int32_t) (lX - x2 < 30 ? lX - x2 : 30);
             origin[nItems].read = i; origin[nItems].x1 = x1; origin[nItems].y1 = y1;
             nItems++;
         }
@@ -1015,6 +1063,9 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
             CHECK(cpecan_hip_batch_create_hdp(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
                                               (unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0) |
                                                   (mode ? CPECAN_FLAG_EXPECTATIONS : 0), &batch));
+        else if (ech)
+            CHECK(cpecan_hip_batch_create_echelon(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
+                                                  unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0, &batch));
         else if (sm4)
             CHECK(cpecan_hip_batch_create_sm4(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
                                               unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0, &batch));
@@ -1043,16 +1094,25 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
                             stList_append(lists[i], stIntTuple_construct3(tri[3 * q], tri[3 * q + 1], tri[3 * q + 2]));
                     } else if (unbanded) {
                         /* getAlignedPairsWithoutBanding walks the diagonals upwards (:1560): groups of
-                         * equal x+y in reverse group order, order inside a group kept */
+                         * equal x+y in reverse group order, order inside a group kept.  An echelon cell (x, y)
+                         * emits runs (x-1, y-1), (x, y-1), ... of one state each: a run begins where y changes
+                         * or x does not step on by one, and its first pair names the cell's diagonal. */
+                        int64_t *dg = malloc(sizeof(int64_t) * (size_t) (np[k] + 1));
+                        for (int64_t q = 0; q < np[k]; q++) {
+                            const int64_t x = tri[3 * q + 1], y = tri[3 * q + 2];
+                            const bool runGoesOn = ech && q > 0 && y == tri[3 * (q - 1) + 2] && x == tri[3 * (q - 1) + 1] + 1;
+                            dg[q] = runGoesOn ? dg[q - 1] : x + y;
+                        }
                         int64_t e = np[k];
                         while (e > 0) {
                             int64_t s = e - 1;
-                            const int64_t d = tri[3 * s + 1] + tri[3 * s + 2];
-                            while (s > 0 && tri[3 * (s - 1) + 1] + tri[3 * (s - 1) + 2] == d) s--;
+                            const int64_t d = dg[s];
+                            while (s > 0 && dg[s - 1] == d) s--;
                             for (int64_t q = s; q < e; q++)
                                 stList_append(lists[i], stIntTuple_construct3(tri[3 * q], tri[3 * q + 1], tri[3 * q + 2]));
                             e = s;
                         }
+                        free(dg);
                     } else {
                         /* shift back to the read's coordinates, then tail first (stList_pop, :1451-1453) */
                         for (int64_t q = np[k] - 1; q >= 0; q--)
@@ -1139,13 +1199,24 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
     }
     free(chars); free(events); free(anchors); free(items); free(origin); free(firstItem);
     free(models); free(modelOf); free(ids); free(models5); free(owner5); free(ychars); free(modelsV); free(modelsH); free(models4);
+    free(modelsE);
+}
+
+/* the decode the GPU path has for the machine: diagonalCalculationMultiPosteriorMatchProbs for the echelon machine (the
+ * reference's vanillaAlign.c:236-238), diagonalCalculationPosteriorMatchProbs for the others */
+static void check_decode(StateMachine *sM, DiagonalPosteriorProbFn fn) {
+    if (sM->type == echelon) {
+        if (fn != diagonalCalculationMultiPosteriorMatchProbs)
+            die("cpecan: the GPU path decodes the echelon machine with diagonalCalculationMultiPosteriorMatchProbs only");
+    } else if (fn != diagonalCalculationPosteriorMatchProbs)
+        die("cpecan: the GPU path implements diagonalCalculationPosteriorMatchProbs only "
+            "(diagonalCalculationMultiPosteriorMatchProbs for the echelon machine)");
 }
 
 stList *getAlignedPairsUsingAnchors(StateMachine *sM, Sequence *SsX, Sequence *SsY, stList *anchorPairs,
                                     PairwiseAlignmentParameters *p, DiagonalPosteriorProbFn fn,
                                     bool raggedL, bool raggedR) {
-    if (fn != diagonalCalculationPosteriorMatchProbs)
-        die("cpecan: the GPU path implements diagonalCalculationPosteriorMatchProbs only");
+    check_decode(sM, fn);
     stList *out = NULL;
     run_reads(1, &sM, &SsX, &SsY, &anchorPairs, p, raggedL, raggedR, 0, 0, &out, NULL);
     return out;
@@ -1184,8 +1255,7 @@ stList *getAlignedPairsWithoutBanding(StateMachine *sM, void *cX, void *cY, int6
                                       PairwiseAlignmentParameters *p, void *(*getXFcn)(void *, int64_t),
                                       void *(*getYFcn)(void *, int64_t), DiagonalPosteriorProbFn fn,
                                       bool raggedL, bool raggedR) {
-    if (fn != diagonalCalculationPosteriorMatchProbs)
-        die("cpecan: the GPU path implements diagonalCalculationPosteriorMatchProbs only");
+    check_decode(sM, fn);
     Sequence *sX = sequence_construct(lX, cX, getXFcn), *sY = sequence_construct(lY, cY, getYFcn);
     stList *out = NULL, *none = NULL;
     run_reads(1, &sM, &sX, &sY, &none, p, raggedL, raggedR, 0, 1, &out, NULL);
@@ -1920,13 +1990,16 @@ void writePosteriorProbs(char *posteriorProbsFile, char *readFile, double *match
         const double mean = events[y * NB_EVENT_PARAMS], noise = events[y * NB_EVENT_PARAMS + 1],
                      duration = events[y * NB_EVENT_PARAMS + 2];
         char kmer[KMER_LENGTH + 1], refKmer[KMER_LENGTH + 1];
-        memcpy(kmer, target + x, KMER_LENGTH);
+        /* (an echelon pair's x reaches past the last k-mer: what lies beyond the target reads as the pad 'n', and a
+         * k-mer that is not one has level and noise means 0, as model_entry has) */
+        for (int k = 0; k < KMER_LENGTH; k++) kmer[k] = x + k < refLength ? target[x + k] : 'n';
         kmer[KMER_LENGTH] = 0;
         for (int k = 0; k < KMER_LENGTH; k++)
             refKmer[k] = sameSense ? kmer[k] : complement_base(kmer[KMER_LENGTH - 1 - k]);
         refKmer[KMER_LENGTH] = 0;
         const int64_t ki = emissions_discrete_getKmerIndex(kmer);
-        const double levelMean = matchModel[1 + ki * MODEL_PARAMS], noiseMean = matchModel[1 + ki * MODEL_PARAMS + 2];
+        const double levelMean = ki > NUM_OF_KMERS ? 0.0 : matchModel[1 + ki * MODEL_PARAMS];
+        const double noiseMean = ki > NUM_OF_KMERS ? 0.0 : matchModel[1 + ki * MODEL_PARAMS + 2];
         fprintf(fh, "%s\t%lld\t%s\t%s\t%s\t%lld\t%f\t%f\t%f\t%s\t%f\t%f\t%f\t%f\t%f\n", contig,
                 (long long) xAdj, refKmer, readFile, strandLabel, (long long) y, mean, noise, duration, kmer,
                 levelMean, noiseMean, p, (mean - shift) / scale, (levelMean - shift) / scale);

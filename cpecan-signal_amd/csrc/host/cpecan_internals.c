@@ -15,6 +15,7 @@
  * with the reference's arithmetic (same logAdd, same order of transitions).
  */
 #include <assert.h>
+#include <ctype.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -111,6 +112,18 @@ double emissions_signal_getDurationProb(void *event, int64_t n) {
     if (n < 0 || n > 5) die("emissions_signal_getDurationProb: n = %lld (at most 5)", (long long) n);
     const double lambda = ((double *) event)[2] / 0.00332005312085;
     return (n + 1) * 0.1397619423751586 + n * log(lambda) - logFactorial[n] - 2 * lambda;
+}
+/* the echelon machine's match emission of n k-mers from the getKmer2 pointer `kmers` (:530-549): the sum starts at 0.0,
+ * not at log zero, and the one look-ahead is whether the character 6n places on is upper case (past the sequence that
+ * is the pad of sequence_padSequence) */
+double emissions_signal_multipleKmerMatchProb(const double *eventModel, void *kmers, void *event, int64_t n) {
+    double p = 0.0;
+    for (int64_t i = 0; i < n; i++) {
+        const char lastBase = *((char *) kmers + KMER_LENGTH * n);
+        if (!isupper((unsigned char) lastBase)) return LOG_ZERO;
+        p = logAdd(p, emissions_signal_getEventMatchProbWithTwoDists(eventModel, (char *) kmers + i, event));
+    }
+    return p - log(n);
 }
 /* the skip probability of the bin the two k-mers' level difference falls in -- NOT in log space (:429-471) */
 double emissions_signal_getKmerSkipProb(StateMachine *sM, void *kmers) {
@@ -425,6 +438,82 @@ static void vanilla_cell(StateMachine *sM, double *current, double *lower, doubl
         walk(a, 2, upper, current, s->getScaledMatchProbFcn(sM->EMISSION_GAP_Y_PROBS, cX, cY), doTransition, extraArgs);
     }
 }
+/* stateMachineEchelon_cellCalculate :1411-1455: match0..match5 (an event over 0..5 k-mers) and gapX; the order of the
+ * calls is the reference's */
+enum { echelonGapX = 6 };
+static void echelon_cell(StateMachine *sM, double *current, double *lower, double *middle, double *upper, void *cX,
+                         void *cY, DoTransitionFn doTransition, void *extraArgs) {
+    StateMachineEchelon *s = (StateMachineEchelon *) sM;
+    const double a_mx = s->getKmerSkipProb(sM, cX, 0), la_mx = log(a_mx);
+    const double a_mh = 1 - a_mx, la_mh = log(a_mh);
+    const double a_xx = s->getKmerSkipProb(sM, cX, 1), la_xx = log(a_xx);
+    const double a_xh = 1 - a_xx, la_xh = log(a_xh);
+    if (lower) {
+        for (int64_t n = 1; n < 6; n++) doTransition(lower, current, n, echelonGapX, 0, la_mx, extraArgs);
+        doTransition(lower, current, echelonGapX, echelonGapX, 0, la_xx, extraArgs);
+    }
+    if (middle) {
+        for (int64_t n = 1; n < 6; n++)
+            for (int64_t from = 0; from < 6; from++)
+                doTransition(middle, current, from, n, s->getMatchProbFcn(sM->EMISSION_MATCH_PROBS, cX, cY, n),
+                             (la_mh + s->getDurationProb(cY, n)), extraArgs);
+        for (int64_t n = 1; n < 6; n++)
+            doTransition(middle, current, echelonGapX, n, s->getMatchProbFcn(sM->EMISSION_MATCH_PROBS, cX, cY, n),
+                         (la_xh + s->getDurationProb(cY, n)), extraArgs);
+    }
+    if (upper) /* only the match states reach match0, the extra-event state */
+        for (int64_t n = 1; n < 6; n++)
+            doTransition(upper, current, n, 0, s->getScaledMatchProbFcn(sM->EMISSION_GAP_Y_PROBS, cX, cY),
+                         (la_mh + s->getDurationProb(cY, 0)), extraArgs);
+}
+static double echelon_start(StateMachine *sM, int64_t state) { /* :1237-1241: match1 */
+    state_check(sM, state);
+    return state == 1 ? 0 : LOG_ZERO;
+}
+static double echelon_ragged_start(StateMachine *sM, int64_t state) { /* :1243-1246 */
+    state_check(sM, state);
+    return state == echelonGapX ? 0 : LOG_ZERO;
+}
+static double echelon_end(StateMachine *sM, int64_t state) { /* :1248-1262, the ragged end as well (:1630) */
+    const StateMachineEchelon *s = (StateMachineEchelon *) sM;
+    state_check(sM, state);
+    return state == echelonGapX ? s->DEFAULT_END_FROM_X_PROB : s->DEFAULT_END_MATCH_PROB;
+}
+static void cpecan_echelon_set_functions(StateMachineEchelon *s) {
+    s->model.startStateProb = echelon_start;
+    s->model.raggedStartStateProb = echelon_ragged_start;
+    s->model.endStateProb = echelon_end;
+    s->model.raggedEndStateProb = echelon_end;
+    s->model.cellCalculate = echelon_cell;
+}
+/* stateMachineEchelon_construct :1602-1640; the end values are the reference's, which it marks as not being logs */
+StateMachine *stateMachineEchelon_construct(StateMachineType type, int64_t parameterSetSize,
+                                            void (*setEmissionsToDefaults)(StateMachine *sM, int64_t nbSkipParams),
+                                            double (*durationProbFcn)(void *event, int64_t n),
+                                            double (*skipProbFcn)(StateMachine *sM, void *kmerList, bool),
+                                            double (*matchProbFcn)(const double *, void *, void *, int64_t n),
+                                            double (*scaledMatchProbFcn)(const double *, void *, void *),
+                                            void (*cellCalcUpdateExpFcn)(double *, double *, int64_t, int64_t, double,
+                                                                         double, void *)) {
+    if (type != echelon) die("Tried to create a echelon state machine with the wrong type?");
+    StateMachineEchelon *s = calloc(1, sizeof *s);
+    s->DEFAULT_END_MATCH_PROB = 0.79015888282447311;
+    s->DEFAULT_END_FROM_X_PROB = 0.19652425498269727;
+    s->BACKGROUND_EVENT_PROB = -3.0;
+    s->model.type = type;
+    s->model.parameterSetSize = parameterSetSize;
+    s->model.stateNumber = 7;
+    s->model.matchState = 1;
+    cpecan_echelon_set_functions(s);
+    s->model.cellCalculateUpdateExpectations = cellCalcUpdateExpFcn;
+    s->getKmerSkipProb = skipProbFcn;
+    s->getDurationProb = durationProbFcn;
+    s->getMatchProbFcn = matchProbFcn;
+    s->getScaledMatchProbFcn = scaledMatchProbFcn;
+    setEmissionsToDefaults((StateMachine *) s, 60);
+    return (StateMachine *) s;
+}
+
 /* stateMachine5_cellCalculate :836-867 */
 static void sm5_cell(StateMachine *sM, double *current, double *lower, double *middle, double *upper, void *cX,
                      void *cY, DoTransitionFn doTransition, void *extraArgs) {
@@ -504,6 +593,13 @@ int cpecan_sm_functions_known(StateMachine *sM) {
     if (cell == (const void *) sm3hdp_cell) {
         const StateMachine3_HDP *s = (StateMachine3_HDP *) sM;
         return s->getYGapProbFcn == get_nanopore_kmer_density && s->getMatchProbFcn == get_nanopore_kmer_density;
+    }
+    if (cell == (const void *) echelon_cell) {
+        const StateMachineEchelon *s = (StateMachineEchelon *) sM;
+        return s->getKmerSkipProb == emissions_signal_getBetaOrAlphaSkipProb &&
+               s->getDurationProb == emissions_signal_getDurationProb &&
+               s->getMatchProbFcn == emissions_signal_multipleKmerMatchProb &&
+               s->getScaledMatchProbFcn == emissions_signal_getEventMatchProbWithTwoDists;
     }
     if (cell == (const void *) vanilla_cell) {
         const StateMachine3Vanilla *s = (StateMachine3Vanilla *) sM;
@@ -813,7 +909,8 @@ void diagonalCalculationPosteriorMatchProbs(StateMachine *sM, int64_t xay, DpMat
     }
 }
 /* the echelon machine's decode (:797-839): states matchState .. 5 of a cell, state s standing for s k-mers.  Host
- * only, like every function of this block; the echelon machine itself is not built (the reference marks it broken). */
+ * only, like every function of this block; passed to the aligner entry points it names the decode of the echelon
+ * kernel (cpecan_k_generale). */
 void diagonalCalculationMultiPosteriorMatchProbs(StateMachine *sM, int64_t xay, DpMatrix *forwardDpMatrix,
                                                  DpMatrix *backwardDpMatrix, Sequence *sX, Sequence *sY,
                                                  double totalProbability, PairwiseAlignmentParameters *p,

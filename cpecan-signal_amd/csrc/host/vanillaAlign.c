@@ -7,8 +7,10 @@
  * alignments run on the GPU side by side.
  *
  * Not carried over: --buildHDP / --alignments (training and re-sampling HDPs is outside this path; the option is
- * refused with a message), the echelon machine (the reference marks it as not working, impl/stateMachine.c:1617), and
- * expectations under the fourState machine (hmmContinuous_getEmptyHmm has no container for it in the reference either).
+ * refused with a message), and expectations or HMM files under the fourState and echelon machines (the reference has no
+ * container for them either; its loadHmmRoutine refuses echelon, vanillaAlign.c:157).  The echelon machine aligns as the
+ * reference's performSignalAlignmentP does: the target padded (sequence_padSequence, :197-199) and decoded with
+ * diagonalCalculationMultiPosteriorMatchProbs (:236-238).
  *
  * The guide alignment comes through sonLib's cigarRead in the reference.  sonLib is not part of this build, so
  * the line format is read here directly: "cigar: <query> <qStart> <qEnd> <+|-> <target> <tStart> <tEnd> <+|-> <score>
@@ -180,6 +182,11 @@ static StateMachine *build_state_machine(const char *modelFile, NanoporeReadAdju
         stateMachine3Vanilla_setStrandTransitionsToDefaults(sM, strand);
         return sM;
     }
+    if (type == echelon) { /* vanillaAlign.c:127-130 */
+        StateMachine *sM = getStateMachineEchelon(modelFile);
+        emissions_signal_scaleModel(sM, npp.scale, npp.shift, npp.var, npp.scale_sd, npp.var_sd);
+        return sM;
+    }
     if (type == threeState || type == fourState) { /* vanillaAlign.c:104-140 */
         StateMachine *sM = type == fourState ? getStateMachine4(modelFile) : getStrawManStateMachine3(modelFile);
         emissions_signal_scaleModel(sM, npp.scale, npp.shift, npp.var, npp.scale_sd, npp.var_sd);
@@ -195,7 +202,7 @@ static stList *remapped_anchor_pairs(stList *unmapped, int64_t *eventMap, int64_
     return filtered;
 }
 static void *(*target_getter(StateMachineType type))(void *, int64_t) {
-    return type == vanilla ? sequence_getKmer2 : type == threeStateHdp ? sequence_getKmer3 : sequence_getKmer;
+    return type == vanilla || type == echelon ? sequence_getKmer2 : type == threeStateHdp ? sequence_getKmer3 : sequence_getKmer;
 }
 
 /* ---- one strand: what one OpenMP section of the reference does ----------------------------------------------- */
@@ -257,12 +264,15 @@ static void *strand_alignment(void *arg) { /* performSignalAlignment + writePost
     fprintf(stderr, "vanillaAlign - doing banded alignment\n");
     stList *anchors = remapped_anchor_pairs(j->anchorPairs, j->eventMap, j->mapOffset);
     Sequence *sX = sequence_construct2(lX, j->target, target_getter(j->type), sequence_sliceNucleotideSequence2);
+    if (j->type == echelon) sequence_padSequence(sX);
     j->alignedPairs = getAlignedPairsUsingAnchors(sM, sX, j->eventSequence, anchors, j->p,
-                                                  diagonalCalculationPosteriorMatchProbs, 1, 1);
+                                                  j->type == echelon ? diagonalCalculationMultiPosteriorMatchProbs
+                                                                     : diagonalCalculationPosteriorMatchProbs, 1, 1);
     double total = 0.0; /* scoreByPosteriorProbabilityIgnoringGaps */
     for (int64_t i = 0; i < stList_length(j->alignedPairs); i++) total += (double) stIntTuple_get(stList_get(j->alignedPairs, i), 0);
     j->posteriorScore = 100.0 * total / ((double) stList_length(j->alignedPairs) * PAIR_ALIGNMENT_PROB_1);
     stList_sort(j->alignedPairs, sortByXPlusYCoordinate2);
+    if (j->type == echelon) free(sX->elements); /* (the padded copy) */
     sequence_sequenceDestroy(sX);
     stList_destruct(anchors);
     j->sM = sM;
@@ -434,7 +444,7 @@ int main(int argc, char *argv[]) {
         case 's': sMtype = threeState; break;
         case 'd': sMtype = threeStateHdp; break;
         case 'f': sMtype = fourState; break;
-        case 'e': die("vanillaAlign - the echelon machine is not on the GPU path");
+        case 'e': sMtype = echelon; break;
         case 'U': case 'a': case 'p':
             die("vanillaAlign - building and re-sampling HDPs is outside this path (run the reference's --buildHDP)");
         case 'M': substitute = optarg; break;
@@ -460,6 +470,10 @@ int main(int argc, char *argv[]) {
             return 1;
         }
     }
+    if (sMtype == echelon && (templateExpectationsFile || complementExpectationsFile))
+        die("vanillaAlign - the echelon machine has no expectations (the reference has no expectation function for it)");
+    if (sMtype == echelon && (templateHmmFile || complementHmmFile))
+        die("vanillaAlign - LoadSignalHmm : unupported stateMachineType (no HMM files for the echelon machine)");
     if (npReadDir) { /* additive: a directory of reads as one GPU batch */
         if (!targetFile || !outDir) die("vanillaAlign - ERROR: --npReadDir needs --reference and --outDir");
         if (templateExpectationsFile || complementExpectationsFile)
@@ -482,7 +496,7 @@ int main(int argc, char *argv[]) {
     if (!npReadFile || !targetFile) die("vanillaAlign - ERROR: --npRead and --reference are required");
     if (!readLabel) readLabel = npReadFile;
     fprintf(stderr, "vanillaAlign - using %s model\n",
-            sMtype == threeState ? "strawMan" : sMtype == vanilla ? "vanilla" : sMtype == fourState ? "fourState" : "strawMan-HDP");
+            sMtype == threeState ? "strawMan" : sMtype == vanilla ? "vanilla" : sMtype == fourState ? "fourState" : sMtype == echelon ? "echelon" : "strawMan-HDP");
     if ((templateHdp != NULL) != (complementHdp != NULL)) die("Need to have template and complement HDPs");
     NanoporeHDP *nHdpT = templateHdp ? deserialize_nhdp(templateHdp) : NULL;
     NanoporeHDP *nHdpC = complementHdp ? deserialize_nhdp(complementHdp) : NULL;
@@ -518,6 +532,7 @@ int main(int argc, char *argv[]) {
     const bool expectations = templateExpectationsFile && complementExpectationsFile;
     if (expectations && sMtype == fourState)
         die("vanillaAlign - the fourState machine has no expectations (the reference has no Hmm container for it)");
+
     StrandJob jobs[2] = {
         { template, sMtype, templateModelFile, templateHmmFile, templateExpectationsFile, posteriorProbsFile, readLabel, nHdpT,
           npRead->templateParams, tEventSequence, npRead->templateEvents, npRead->templateEventMap, pA->start2,

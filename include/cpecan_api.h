@@ -211,6 +211,34 @@ typedef struct _StateMachine3vanilla {
     double (*getScaledMatchProbFcn)(const double *scaledEventModel, void *kmer, void *event);
     double (*getMatchProbFcn)(const double *eventModel, void *kmer, void *event);
 } StateMachine3Vanilla;
+/* echelon signal machine (inc/stateMachine.h:233-246; data members): match0..match5 for an event over 0..5 k-mers and a
+ * k-mer skip state gapX (6), stateMachineEchelon_cellCalculate impl/stateMachine.c:1411-1455.  The end values are the
+ * reference's, used as log values as it does (:1617).  Posterior decode on the GPU (cpecan_k_generale) with
+ * diagonalCalculationMultiPosteriorMatchProbs; the reference has no expectation function or Hmm for it. */
+typedef struct _StateMachineEchelon {
+    StateMachine model;
+    double BACKGROUND_EVENT_PROB;
+    double DEFAULT_END_MATCH_PROB;
+    double DEFAULT_END_FROM_X_PROB;
+    double (*getKmerSkipProb)(StateMachine *sM, void *kmerList, bool getAlpha);
+    double (*getDurationProb)(void *event, int64_t n);
+    double (*getMatchProbFcn)(const double *eventModel, void *kmers, void *event, int64_t n);
+    double (*getScaledMatchProbFcn)(const double *scaledEventModel, void *kmer, void *event);
+} StateMachineEchelon;
+/* getStateMachineEchelon (impl/stateMachine.c:1773): the vanilla machine's 3-line .model file (match table, 30 skip
+ * bins stored as beta and alpha, extra-event table) */
+StateMachine *getStateMachineEchelon(const char *modelFile);
+StateMachine *stateMachineEchelon_construct(StateMachineType type, int64_t parameterSetSize,
+                                            void (*setEmissionsToDefaults)(StateMachine *sM, int64_t nbSkipParams),
+                                            double (*durationProbFcn)(void *event, int64_t n),
+                                            double (*skipProbFcn)(StateMachine *sM, void *kmerList, bool),
+                                            double (*matchProbFcn)(const double *, void *, void *, int64_t n),
+                                            double (*scaledMatchProbFcn)(const double *, void *, void *),
+                                            void (*cellCalcUpdateExpFcn)(double *fromCells, double *toCells,
+                                                                         int64_t from, int64_t to, double eP,
+                                                                         double tP, void *extraArgs));
+double emissions_signal_multipleKmerMatchProb(const double *eventModel, void *kmers, void *event, int64_t n); /* :530-549 */
+
 /* getSignalStateMachine3Vanilla (impl/stateMachine.c:1761): tables from a 3-line .model file, the 30
  * skip bins of its second line stored as beta and alpha (:284-297) */
 StateMachine *getSignalStateMachine3Vanilla(const char *modelFile);
@@ -784,6 +812,8 @@ _Static_assert(offsetof(StateMachine5, getXGapProbFcn) == 240 && sizeof(StateMac
 _Static_assert(offsetof(StateMachine3_HDP, hdpModel) == 184 && sizeof(StateMachine3_HDP) == 208, "StateMachine3_HDP layout");
 _Static_assert(offsetof(StateMachine3Vanilla, getKmerSkipProb) == 144 && sizeof(StateMachine3Vanilla) == 168,
                "StateMachine3Vanilla layout");
+_Static_assert(offsetof(StateMachineEchelon, getKmerSkipProb) == 128 && sizeof(StateMachineEchelon) == 160,
+               "StateMachineEchelon layout");
 _Static_assert(sizeof(struct _hmm) == 96 && offsetof(HmmDiscrete, transitions) == 96, "Hmm layout");
 _Static_assert(offsetof(ContinuousPairHmm, individualKmerGapProbs) == 104, "ContinuousPairHmm layout");
 _Static_assert(offsetof(VanillaHmm, getKmerSkipBin) == 120 && offsetof(HdpHmm, nhdp) == 144, "VanillaHmm / HdpHmm layout");

@@ -130,6 +130,19 @@ typedef struct {
 int cpecan_hip_modelsv_create(cpecan_ctx *ctx, const cpecan_vanilla_model *models, int32_t n,
                               int32_t threads, int32_t *ids);
 
+/* The echelon signal machine: getStateMachineEchelon() (impl/stateMachine.c:1773) after emissions_signal_scaleModel().
+ * Fields as in struct _StateMachineEchelon (inc/stateMachine.h:233-246): the two end values (used as log values, as the
+ * reference does), the match and extra-event tables in the reference's layout and the 60 skip-bin values of
+ * EMISSION_GAP_X_PROBS (beta[30] | alpha[30]).  X elements are read as sequence_getKmer2 does; k-mers must be
+ * ACGT-only.  Ids live in their own space (used by cpecan_hip_batch_create_echelon only). */
+typedef struct {
+    double end_match_prob, end_from_x_prob;
+    const double *match_probs; /* [CPECAN_MODEL_TABLE_LEN] */
+    const double *skip_probs;  /* [60]                     */
+    const double *gap_y_probs; /* [CPECAN_MODEL_TABLE_LEN] */
+} cpecan_echelon_model;
+int cpecan_hip_modelse_create(cpecan_ctx *ctx, const cpecan_echelon_model *models, int32_t n, int32_t *ids);
+
 /* The 3-state HDP signal machine: getHdpStateMachine3(NanoporeHDP *) (impl/stateMachine.c:1738) over a
  * finalized NanoporeHDP (deserialize_nhdp impl/nanopore_hdp.c:845).  transitions as cpecan_sm3_model; the
  * HDP as densities need it (dir_proc_density impl/hdp.c:2577-2601): the alphabet (sorted, as the k-mer ids
@@ -251,6 +264,19 @@ int cpecan_hip_batch_create_sm4(cpecan_ctx *ctx, const cpecan_item *items, int64
                                 const char *x_chars, int64_t n_x, const double *events, int64_t n_events,
                                 const int64_t *anchors, int64_t n_anchor_pairs,
                                 const cpecan_band_params *params, int32_t flags, cpecan_batch **out);
+
+/* k-mers against events with an echelon model (getAlignedPairsUsingAnchors / getAlignedPairsWithoutBanding with the
+ * StateMachine of getStateMachineEchelon and diagonalCalculationMultiPosteriorMatchProbs, sequence_getKmer2 /
+ * sequence_getEvent): same buffers as cpecan_hip_batch_create, model_id is a cpecan_hip_modelse_create id.  General
+ * kernel, posterior decode; flags: UNBANDED.  A cell emits s pairs (x+n-1, y-1), n < s, for every state s = 1..5 whose
+ * posterior reaches the threshold (impl/pairwiseAligner.c:797-839), so pairs repeat and x may reach lX+3.  The
+ * machine looks up to 30 characters past an item's lX+5 (emissions_signal_multipleKmerMatchProb): an item's
+ * `reserved` holds how many characters after those belong to its sequence (0..30; a sub-alignment of a longer read
+ * sees the rest of the read), and every character past them reads as the pad 'n' of sequence_padSequence. */
+int cpecan_hip_batch_create_echelon(cpecan_ctx *ctx, const cpecan_item *items, int64_t n_items,
+                                    const char *x_chars, int64_t n_x, const double *events, int64_t n_events,
+                                    const int64_t *anchors, int64_t n_anchor_pairs,
+                                    const cpecan_band_params *params, int32_t flags, cpecan_batch **out);
 
 /* k-mers against events with an HDP model (getAlignedPairsUsingAnchors with a StateMachine3_HDP,
  * sequence_getKmer3 / sequence_getEvent): same buffers as cpecan_hip_batch_create (x characters over the
