@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- banded pair-HMM forward/backward/posterior throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mode posterior|em]
+    python bench.py --gpus N --steps K --warmup W [--mode posterior|em] [--full]
+
+A plain run does what its headline figure needs: it sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given and prints its JSON line.  --full adds what takes runs of its own: the CPU baselines
+(cpu_baseline; --cpu-reads) and, in --mode posterior, the first reads checked against the oracle after the run
+(parity_check; --check) and one batch timed alone on each kernel family (roofline.single_batch; --single-steps).
 
 N > 1 without a rendezvous in the environment: this process starts its own N workers (one per GPU, through
 `python -m torch.distributed.run` on 127.0.0.1), before it touches a GPU itself, and passes their output on.  The
@@ -15,8 +20,8 @@ own 1024 reads).  Consecutive steps are pipelined (--inflight 2): step s+1 works
 streams of its own and is issued before step s is waited for, the way queued batches overlap in service; while the
 GPU works on one batch the host finishes the other's pairs (exp, threshold, floor with libm -- what makes the
 integer posteriors the reference's, bit for bit).  The timed region covers exactly K complete steps, pairs included.
-After it, rank 0 times ONE batch alone (--single-steps, each step waited for before the next is issued) on the
-wave-per-alignment kernels: roofline.frac_single_batch.
+With --full, after it, rank 0 times ONE batch alone (--single-steps, each step waited for before the next is issued)
+on each kernel family: roofline.frac_single_batch.
 
 --mode em.  BASELINE.json configs[3]: a step is one Baum-Welch iteration -- E-step of this rank's reads on the GPU
 (expectations summed on the device), ONE all-reduce of the [9 transitions | 4096 k-mer gaps | likelihood] vector
@@ -26,7 +31,7 @@ value      = in-band cells (each counted once) of all ranks / max-over-ranks wal
 roofline   = algorithmic bytes (48 B per cell: one fp64 write + one re-read of 3 states) /
              average duration of a pass, against the 8 TB/s HBM peak; dominant_kernel from HIP events on the
              library's own streams
-cpu_baseline = the CPU oracle (a port of the reference's algorithm; the reference itself cannot be built here:
+cpu_baseline = (--full) the CPU oracle (a port of the reference's algorithm; the reference itself cannot be built:
              sonLib is absent) timed on rank 0 over the first reads of the same batch: on all host cores of the job
              (a pool of forked workers, started before the process touches the GPU) and on one thread.
 
@@ -100,17 +105,20 @@ def parse_args(argv=None):
     ap.add_argument("--family", choices=("auto", "wave", "workgroup"), default="auto",
                     help="register-resident kernels of the timed region: wave-per-alignment or workgroup-per-"
                          "alignment; auto = workgroup when batches are pipelined (--inflight 2), wave otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baselines, the oracle check after the "
+                         "run and the single-batch measurement (--cpu-reads, --check, --single-steps)")
     ap.add_argument("--cpu-reads", type=int, default=60,
-                    help="reads timed on the CPU oracle, ~0.3 s each on one core (0: skip)")
+                    help="--full: reads timed on the CPU oracle, ~0.3 s each on one core (0: skip)")
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="worker processes of the all-core CPU baseline (0: the host cores this job may use, at most 16)")
-    ap.add_argument("--check", type=int, default=2, help="reads compared with the oracle after the run")
+    ap.add_argument("--check", type=int, default=2, help="--full: reads compared with the oracle after the run")
     ap.add_argument("--inflight", type=int, default=2,
                     help="batches in flight: step s+1 (another batch, its own streams) is issued before step s is "
                          "waited for, as a server with queued batches would; every step is still one pass over "
                          "one batch and all K steps complete inside the timed region")
     ap.add_argument("--single-steps", type=int, default=12,
-                    help="steps of the single-batch measurement after the timed region (rank 0, N=1; 0: skip)")
+                    help="--full: steps of the single-batch measurement after the timed region (rank 0, N=1; 0: skip)")
     ap.add_argument("--no-finalise", action="store_true",
                     help="leave the pairs as (x, y, exponent) in HBM inside the timed region instead of finishing "
                          "them on the host (GPU pass alone)")
@@ -148,6 +156,8 @@ def parse_args(argv=None):
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dump_outputs and (args.mode != "posterior" or args.rehearse):
         ap.error("--dump-outputs writes the outputs of --mode posterior on the GPU")
+    if not args.full:  # a plain run: the timed steps and what they computed, nothing else
+        args.cpu_reads = args.check = args.single_steps = 0
     return args
 
 

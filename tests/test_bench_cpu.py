@@ -53,8 +53,20 @@ def test_gpus_2_starts_its_own_two_ranks():
 def test_command_line_contract():
     h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
     assert h.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--inflight", "--single-steps"):
+    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--inflight", "--single-steps", "--full"):
         assert flag in h.stdout
+
+
+def test_only_full_runs_what_the_headline_does_not_need():
+    """a plain run: no CPU baseline, no oracle check, no single-batch measurement, whatever their sizes say; --full
+    runs them at the sizes given"""
+    for argv in ([], ["--mode", "em"], ["--cpu-reads", "5", "--check", "3", "--single-steps", "4"]):
+        a = bench.parse_args(argv)
+        assert not a.full and (a.cpu_reads, a.check, a.single_steps) == (0, 0, 0), argv
+    a = bench.parse_args(["--full"])
+    assert (a.cpu_reads, a.check, a.single_steps) == (60, 2, 12)
+    a = bench.parse_args(["--full", "--cpu-reads", "5", "--check", "0", "--single-steps", "4"])
+    assert (a.cpu_reads, a.check, a.single_steps) == (5, 0, 4)
 
 
 def test_steps_and_warmup_are_what_the_command_line_says():

@@ -1,4 +1,4 @@
-"""Summarise gpurun_out/<tag>_* (written by tools/profile_round.sh) into profiles/<tag>_*.
+"""Summarise $PROFILE_OUT/<tag>_* (default profile_out/; written by tools/profile_round.sh) into profiles/<tag>_*.
 
   profiles/<tag>_rocprofv3_kernel_stats.csv   rocprofv3 --kernel-trace --stats table, as is
   profiles/<tag>_rocprofv3_pmc_summary.json   per-kernel counter sums, bytes per pass, calibration; one section per
@@ -14,7 +14,7 @@ import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-go = os.path.join(root, "gpurun_out")
+go = os.environ.get("PROFILE_OUT") or os.path.join(root, "profile_out")
 PASSES = 3  # bench.py --steps 2 --warmup 1
 
 
