@@ -447,6 +447,56 @@ struct StreamFence {
     }
 };
 
+/* The three streams a chain of batches runs on: forward (track, begin, the forward sweeps), back (the sweeps back) and
+ * post (decode and re-sweep of a window, then the run's join, counts, packing and end event).  Every context has one;
+ * a run behind a wave batch of one stream group (cpecan_hip_batch_run_after) is issued on the lanes that batch ran on,
+ * so that a chain needs three hardware queues however many batches and contexts take part, and the order on each lane
+ * orders the chain.  The forward lane is the context's first stream; back and post come with the context's first
+ * wave batch of one group (the runtime deals its few hardware queues out in the order streams are made: a context
+ * whose batches never use them -- the workgroup kernels of the E-step contexts -- leaves the queues to the others).
+ * Held by reference: by its context, and by every batch whose last run went on it (until the batch runs again or is
+ * destroyed). */
+struct LaneSet {
+    int device = 0;
+    hipStream_t fwd = nullptr, back = nullptr, post = nullptr;
+    std::mutex mu; /* held for the whole enqueue of one run: runs from two host threads do not interleave */
+    std::atomic<int> refs{ 1 };
+};
+
+static void lanes_release(LaneSet *L) {
+    if (!L || --L->refs > 0) return;
+    (void) hipSetDevice(L->device);
+    for (hipStream_t s : { L->fwd, L->back, L->post })
+        if (s) {
+            (void) hipStreamSynchronize(s);
+            (void) hipStreamDestroy(s);
+        }
+    delete L;
+}
+
+static hipError_t lanes_create(int device, LaneSet **out) {
+    *out = nullptr;
+    LaneSet *L = new (std::nothrow) LaneSet();
+    if (!L) return hipErrorOutOfMemory;
+    L->device = device;
+    const hipError_t e = hipStreamCreateWithFlags(&L->fwd, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        lanes_release(L);
+        return e;
+    }
+    *out = L;
+    return hipSuccess;
+}
+
+/* the back and post lanes, made when a batch that runs on them is created */
+static hipError_t lanes_sweeps(LaneSet *L) {
+    std::lock_guard<std::mutex> hold(L->mu);
+    hipError_t e = hipSuccess;
+    for (hipStream_t *s : { &L->back, &L->post })
+        if (e == hipSuccess && !*s) e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+    return e;
+}
+
 } // namespace
 
 #define CP_WAVE5_PAIRED_BELOW 1536 /* alignments: below this (fewer than 1.5 per SIMD) the 5-state machine runs on two waves
@@ -454,7 +504,9 @@ struct StreamFence {
 struct cpecan_ctx {
     int device = 0;
     long long modelEpoch = 0; /* counts cpecan_hip_models_clear calls */
-    hipStream_t stream = nullptr;
+    LaneSet *lanes = nullptr;
+    hipStream_t stream = nullptr; /* lanes->fwd */
+    std::vector<cpecan_batch *> batches; /* its live batches (under g_batchesMu): ctx_fence waits for their runs */
     /* input preparation (uploads, table assembly, k-mer indices) goes through a stream of the highest priority: it
      * gets a hardware queue of its own and its copies and small kernels are not held up behind the sweeps of the
      * batches that are running while the next one is prepared; every call that uses it waits for it before it returns */
@@ -533,10 +585,14 @@ struct cpecan_batch {
      * its own, so that the tail of one group's kernel overlaps the other groups' kernels (a launch
      * lasts as long as its slowest workgroup).  evStage: per group, one event after every kernel. */
     int nGroups = 1;
+    /* (a wave batch of one group runs on lane sets instead: gStream empty, gStreamOwned false) */
     std::vector<hipStream_t> gStream, gStreamB; /* gStreamB: the wave kernels' backward sweeps (see batch_run) */
-    hipStream_t asmPost = nullptr;     /* assembly sweeps: the totals and the decode of a window, beside the next window's sweeps */
+    bool postAside = false;            /* assembly sweeps: the totals and the decode of a window on the post lane, beside
+                                          the next window's sweeps */
     std::vector<hipEvent_t> evPost;    /* ... done, per window */
     bool gStreamOwned = true;
+    LaneSet *runLanes = nullptr; /* the lanes of its last run (a reference) */
+    bool laneRun = false;        /* ... which went over their three streams: a follower is issued on them */
     long long modelEpoch = 0; /* the context's when the batch was created */
     int stateBytes = 0;
     std::vector<hipEvent_t> evStage, evJoin;
@@ -659,6 +715,31 @@ int cpecan_hip_device_count(int *count) {
     return CPECAN_OK;
 }
 
+} // extern "C"
+
+/* Every run of the context's batches is over, on whatever lanes it went (a lane also carries the runs of other
+ * contexts' batches, so no lane is waited for): what guards the model tables those runs read.  The context's prep
+ * stream is made to wait for the runs' end events under the list's lock (which only queues the waits), and the host
+ * waits for the prep stream after it: other threads' contexts are not held up for the length of a pass. */
+static std::mutex g_batchesMu; /* the contexts' batch lists */
+
+static hipError_t ctx_fence(cpecan_ctx *c) {
+    hipError_t r = hipSuccess;
+    {
+        std::lock_guard<std::mutex> g(g_batchesMu);
+        for (cpecan_batch *b : c->batches)
+            if (b->ran) {
+                hipError_t e = hipStreamWaitEvent(c->prep, b->ev2, 0);
+                if (e != hipSuccess) e = hipEventSynchronize(b->ev2); /* (the wait could not be queued: wait here) */
+                if (r == hipSuccess) r = e;
+            }
+    }
+    const hipError_t e = hipStreamSynchronize(c->prep);
+    return r != hipSuccess ? r : e;
+}
+
+extern "C" {
+
 int cpecan_hip_ctx_create(int device, cpecan_ctx **out) {
     if (!out) return fail(CPECAN_EINVAL, "ctx is NULL");
     *out = nullptr;
@@ -670,16 +751,18 @@ int cpecan_hip_ctx_create(int device, cpecan_ctx **out) {
     cpecan_ctx *c = new (std::nothrow) cpecan_ctx();
     if (!c) return fail(CPECAN_EINVAL, "out of host memory");
     c->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    /* the lanes first: a process gets few hardware queues (four by default) and the first streams made have one each */
+    hipError_t e = lanes_create(device, &c->lanes);
     if (e != hipSuccess) {
         delete c;
         return fail(CPECAN_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
     }
+    c->stream = c->lanes->fwd;
     int least = 0, greatest = 0;
     (void) hipDeviceGetStreamPriorityRange(&least, &greatest);
     e = hipStreamCreateWithPriority(&c->prep, hipStreamNonBlocking, greatest);
     if (e != hipSuccess) {
-        (void) hipStreamDestroy(c->stream);
+        lanes_release(c->lanes);
         delete c;
         return fail(CPECAN_EHIP, "hipStreamCreateWithPriority: %s", hipGetErrorString(e));
     }
@@ -690,11 +773,18 @@ int cpecan_hip_ctx_create(int device, cpecan_ctx **out) {
 int cpecan_hip_ctx_destroy(cpecan_ctx *c) {
     if (!c) return CPECAN_OK;
     (void) hipSetDevice(c->device);
-    /* the model tables go back to the allocator's cache below: nothing queued through this context may still read them
-     * (a batch of this context that is still running on streams of its own is the caller's to finish first) */
-    if (c->stream) (void) hipStreamSynchronize(c->stream);
+    /* the model tables go back to the allocator's cache below: no run of this context's batches may still read them,
+     * whichever lanes it went on.  The lanes themselves live on while a batch of another context holds them. */
+    (void) ctx_fence(c);
     if (c->prep) (void) hipStreamSynchronize(c->prep);
-    if (c->stream) (void) hipStreamDestroy(c->stream);
+    {
+        std::lock_guard<std::mutex> g(g_batchesMu);
+        for (cpecan_batch *b : c->batches) b->ctx = nullptr; /* (a batch may be destroyed after its context) */
+        c->batches.clear();
+    }
+    lanes_release(c->lanes);
+    c->lanes = nullptr;
+    c->stream = nullptr;
     if (c->prep) (void) hipStreamDestroy(c->prep);
     if (c->pinned) (void) hipHostFree(c->pinned);
     for (auto *t : c->hdpTables) delete t;
@@ -753,7 +843,7 @@ static void derive_rows(const cpecan_sm3_model *m, double *dst) {
  * device (no host mirror of the tables is kept).  *fresh receives the device address of the first new model. */
 static int grow_models(cpecan_ctx *c, int32_t n, double **fresh) {
     const size_t old = (size_t) c->nModels * CP_MODEL_STRIDE, total = old + (size_t) n * CP_MODEL_STRIDE;
-    if (c->stream) (void) hipStreamSynchronize(c->stream); /* (the old table goes back to the allocator's cache) */
+    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
     DevBuf<double> grown;
     hipError_t e = grown.alloc(total);
     if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
@@ -896,7 +986,7 @@ int cpecan_hip_models_create_scaled(cpecan_ctx *c, const cpecan_sm3_model *base,
     int rc = grow_models(c, n, &fresh);
     if (rc != CPECAN_OK) return rc;
     DevBuf<double> dBase, dScal, dPart;
-    StreamFence fence{ c->prep, c->stream };
+    StreamFence fence{ c->prep, nullptr };
     HIP_TRY(dBase.alloc(baseRows.size()));
     HIP_TRY(dScal.alloc((size_t) n * 5));
     HIP_TRY(dPart.alloc(part.n));
@@ -926,7 +1016,7 @@ int cpecan_hip_models_download(cpecan_ctx *c, int32_t id, double *out, int64_t c
     if (id < 0 || id >= c->nModels) return fail(CPECAN_EINVAL, "model id %d out of range (%d)", id, c->nModels);
     if (capacity < CP_MODEL_STRIDE) return fail(CPECAN_EINVAL, "capacity %lld < %d doubles", (long long) capacity, (int) CP_MODEL_STRIDE);
     HIP_TRY(hipSetDevice(c->device));
-    if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(ctx_fence(c));
     HIP_TRY(hipMemcpy(out, c->models.p + (size_t) id * CP_MODEL_STRIDE, CP_MODEL_STRIDE * sizeof(double), hipMemcpyDeviceToHost));
     return CPECAN_OK;
 }
@@ -950,14 +1040,17 @@ int cpecan_hip_models_set_transitions(cpecan_ctx *c, const double *transitions, 
     for (int i = 0; i < 9; i++) v[(size_t) i] = transitions[i];
     if (gapX) std::copy(gapX, gapX + CPECAN_NUM_KMERS, v.begin() + 9);
     for (double &t : c->switchToX) t = transitions[T_GAP_SWITCH_TO_X];
+    /* the tables are written in place: every run that reads them is over first (on whatever lanes it went); the
+     * update goes through the context's own prep stream, which no other context's run shares */
+    HIP_TRY(ctx_fence(c));
     DevBuf<double> dv;
-    StreamFence fence{ c->stream, nullptr };
+    StreamFence fence{ c->prep, nullptr };
     HIP_TRY(dv.alloc(v.size()));
-    HIP_TRY(hipMemcpyAsync(dv.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dv.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->prep));
     hipLaunchKernelGGL(cpecan_k_set_transitions, dim3((9 + CPECAN_NUM_KMERS + 255) / 256, (unsigned) std::min(c->nModels, 65535)),
-                       dim3(256), 0, c->stream, c->models.p, c->nModels, (const double *) dv.p, gapX ? 1 : 0);
+                       dim3(256), 0, c->prep, c->models.p, c->nModels, (const double *) dv.p, gapX ? 1 : 0);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream)); /* dv is released on return */
+    HIP_TRY(hipStreamSynchronize(c->prep)); /* dv is released on return */
     return CPECAN_OK;
 }
 
@@ -965,13 +1058,13 @@ int cpecan_hip_selftest_division(cpecan_ctx *c, int64_t n, uint64_t seed, int64_
     if (!c || n <= 0 || !mismatches) return fail(CPECAN_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<unsigned long long> bad;
-    StreamFence fence{ c->stream, nullptr };
+    StreamFence fence{ c->prep, nullptr };
     HIP_TRY(bad.alloc(1));
-    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), c->stream));
-    if (cpecan_systolic_divtest(c->stream, n, seed, bad.p) != 0)
+    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), c->prep));
+    if (cpecan_systolic_divtest(c->prep, n, seed, bad.p) != 0)
         return fail(CPECAN_EHIP, "division self-test launch failed");
     unsigned long long h = 0;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->prep));
     HIP_TRY(hipMemcpy(&h, bad.p, sizeof h, hipMemcpyDeviceToHost));
     *mismatches = (int64_t) h;
     return CPECAN_OK;
@@ -1053,7 +1146,7 @@ int cpecan_hip_modelsv_create(cpecan_ctx *c, const cpecan_vanilla_model *models,
     for (auto &t : pool) t.join();
     for (int i = 0; i < n; i++) ids[i] = c->nModelsV + i;
     c->nModelsV += n;
-    if (c->stream) (void) hipStreamSynchronize(c->stream); /* (the old table goes back to the allocator's cache) */
+    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
     hipError_t e = c->modelsV.alloc(c->hostModelsV.size());
     if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpy(c->modelsV.p, c->hostModelsV.data(), c->hostModelsV.size() * sizeof(double),
@@ -1100,7 +1193,7 @@ int cpecan_hip_modelse_create(cpecan_ctx *c, const cpecan_echelon_model *models,
         derive_echelon(&models[i], c->hostModelsE.data() + old + (size_t) i * CP_EMODEL_STRIDE);
         ids[i] = c->nModelsE + i;
     }
-    if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream)); /* (the old table goes back to the allocator's cache) */
+    HIP_TRY(ctx_fence(c)); /* (the old table goes back to the allocator's cache) */
     HIP_TRY(c->modelsE.alloc(c->hostModelsE.size()));
     HIP_TRY(hipMemcpy(c->modelsE.p, c->hostModelsE.data(), c->hostModelsE.size() * sizeof(double), hipMemcpyHostToDevice));
     c->nModelsE += n;
@@ -1151,7 +1244,7 @@ int cpecan_hip_modelsh_create(cpecan_ctx *c, const cpecan_hdp_model *models, int
         ids[i] = (int32_t) c->hostModelsH.size();
         c->hostModelsH.push_back(d);
     }
-    if (c->stream) (void) hipStreamSynchronize(c->stream);
+    (void) ctx_fence(c);
     HIP_TRY(c->modelsH.alloc(c->hostModelsH.size()));
     HIP_TRY(hipMemcpy(c->modelsH.p, c->hostModelsH.data(), c->hostModelsH.size() * sizeof(DevHdpModel),
                       hipMemcpyHostToDevice));
@@ -1172,7 +1265,7 @@ int cpecan_hip_models5_create(cpecan_ctx *c, const cpecan_sm5_model *models, int
         ids[i] = c->nModels5 + i;
     }
     c->nModels5 += n;
-    if (c->stream) (void) hipStreamSynchronize(c->stream); /* (the old table goes back to the allocator's cache) */
+    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
     hipError_t e = c->models5.alloc(c->hostModels5.size());
     if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpy(c->models5.p, c->hostModels5.data(), c->hostModels5.size() * sizeof(double),
@@ -1201,7 +1294,7 @@ int cpecan_hip_models4_create(cpecan_ctx *c, const cpecan_sm4_model *models, int
         for (int k = 0; k < 11; k++) dst[k] = models[i].transitions[k];
         ids[i] = c->nModels4 + i;
     }
-    if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream)); /* (the old table goes back to the allocator's cache) */
+    HIP_TRY(ctx_fence(c)); /* (the old table goes back to the allocator's cache) */
     HIP_TRY(c->models4.alloc(c->hostModels4.size()));
     HIP_TRY(hipMemcpy(c->models4.p, c->hostModels4.data(), c->hostModels4.size() * sizeof(double), hipMemcpyHostToDevice));
     c->nModels4 += n;
@@ -1211,7 +1304,7 @@ int cpecan_hip_models4_create(cpecan_ctx *c, const cpecan_sm4_model *models, int
 int cpecan_hip_models_clear(cpecan_ctx *c) {
     if (!c) return fail(CPECAN_EINVAL, "ctx is NULL");
     (void) hipSetDevice(c->device);
-    if (c->stream) (void) hipStreamSynchronize(c->stream); /* the tables go back to the allocator's cache: no reader may be left */
+    (void) ctx_fence(c); /* the tables go back to the allocator's cache: no reader may be left */
     c->modelEpoch++; /* batches created before this call hold ids into tables that are gone: batch_run refuses them */
     c->models.release();
     c->switchToX.clear();
@@ -1254,7 +1347,11 @@ int cpecan_hip_batch_destroy(cpecan_batch *b) {
     if (b->gStreamOwned)
         for (hipStream_t st : b->gStream) (void) hipStreamDestroy(st);
     for (hipStream_t st : b->gStreamB) (void) hipStreamDestroy(st);
-    if (b->asmPost) (void) hipStreamDestroy(b->asmPost);
+    lanes_release(b->runLanes);
+    {
+        std::lock_guard<std::mutex> g(g_batchesMu);
+        if (b->ctx) b->ctx->batches.erase(std::remove(b->ctx->batches.begin(), b->ctx->batches.end(), b), b->ctx->batches.end());
+    }
     for (hipEvent_t e : b->evPost) (void) hipEventDestroy(e);
     if (b->hPacked) pinned_cache().put(b->hPacked, b->hPackedBlock);
     if (b->hPost) pinned_cache().put(b->hPost, b->hPostBlock);
@@ -1494,6 +1591,10 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     cpecan_batch *b = new (std::nothrow) cpecan_batch();
     if (!b) return fail(CPECAN_EINVAL, "out of host memory");
     b->ctx = c;
+    {
+        std::lock_guard<std::mutex> g(g_batchesMu);
+        c->batches.push_back(b);
+    }
     b->device = c->device;
     b->modelEpoch = c->modelEpoch;
     b->nItems = nItems;
@@ -1533,14 +1634,17 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     if (useKernel == CPECAN_KERNEL_AUTO)
         useKernel = (globalMaxWidth <= famMaxWidth && systolicOk && !b->P.debug && !unbanded)
                         ? CPECAN_KERNEL_SYSTOLIC : CPECAN_KERNEL_GENERAL;
+    /* (refusals from here on go through cpecan_hip_batch_destroy: it takes the batch off the context's list) */
     if (useKernel == CPECAN_KERNEL_SYSTOLIC && (globalMaxWidth > famMaxWidth || !systolicOk)) {
-        delete b;
-        return fail(CPECAN_EINVAL, "band is %d cells wide (systolic kernel: at most %d, edges moving "
-                    "one k-mer per diagonal)", globalMaxWidth, famMaxWidth);
+        const int rc = fail(CPECAN_EINVAL, "band is %d cells wide (systolic kernel: at most %d, edges moving "
+                            "one k-mer per diagonal)", globalMaxWidth, famMaxWidth);
+        cpecan_hip_batch_destroy(b);
+        return rc;
     }
     if (useKernel == CPECAN_KERNEL_SYSTOLIC && b->P.debug) {
-        delete b;
-        return fail(CPECAN_EINVAL, "cell dumps are only available from the general kernel");
+        const int rc = fail(CPECAN_EINVAL, "cell dumps are only available from the general kernel");
+        cpecan_hip_batch_destroy(b);
+        return rc;
     }
     b->kernel = useKernel;
     b->maxWidth = globalMaxWidth;
@@ -1672,14 +1776,16 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
             b->nGroups = G;
             b->gStream.assign((size_t) G, nullptr);
             b->evJoin.assign((size_t) G, nullptr);
-            /* a wave batch of one group sweeps forward on the context's own stream: two streams per batch, so that
-             * two batches in flight stay within the four hardware queues a process gets */
+            /* a wave batch of one group runs on lane sets (batch_run): no streams of its own, so that a chain of
+             * batches stays within the four hardware queues a process gets */
             b->gStreamOwned = !(b->sy->wave && G == 1);
             if (b->gStreamOwned)
                 for (auto &st : b->gStream) B_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            else
-                b->gStream[0] = c->stream;
-            if (b->sy->wave) {
+            else {
+                b->gStream.clear();
+                B_TRY(lanes_sweeps(c->lanes));
+            }
+            if (b->sy->wave && b->gStreamOwned) {
                 b->gStreamB.assign((size_t) G, nullptr);
                 for (auto &st : b->gStreamB) B_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
             }
@@ -1748,7 +1854,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
                 /* the post kernel of a window runs beside the next window's sweeps (batch_run): the sweep back of window
                  * w+1 fills one half of the scratch while the post kernel of window w reads the other */
                 B_TRY(b->syScratch.alloc(2 * (size_t) nItems * (size_t) b->scratchBytes));
-                B_TRY(hipStreamCreateWithFlags(&b->asmPost, hipStreamNonBlocking));
+                b->postAside = true;
                 b->evPost.assign((size_t) b->asmMaxWindows, nullptr);
                 for (auto &e : b->evPost) B_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             }
@@ -1857,32 +1963,23 @@ int cpecan_hip_batch_create_echelon(cpecan_ctx *c, const cpecan_item *items, int
                              CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out, false, false, false, true);
 }
 
-int cpecan_hip_batch_run(cpecan_batch *b) { return cpecan_hip_batch_run_after(b, nullptr); }
+} // extern "C"
 
-int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
-    if (!b) return fail(CPECAN_EINVAL, "batch is NULL");
+/* One run of the batch, queued on the lane set L (its mutex held).  A wave batch of one stream group runs over the
+ * three lanes and ends on the post lane; every other batch runs on the forward lane (and streams of its own). */
+static int batch_enqueue(cpecan_batch *b, cpecan_batch *after, LaneSet *L) {
     cpecan_ctx *c = b->ctx;
-    if (b->modelEpoch != c->modelEpoch)
-        return fail(CPECAN_EINVAL, "cpecan_hip_models_clear was called on the context after this batch was created: "
-                    "its model ids are gone");
-    if (after && after->device != b->device) return fail(CPECAN_EINVAL, "the two batches live on different devices");
-    HIP_TRY(hipSetDevice(c->device));
-    if (after && after != b && after->ran) {
-        /* behind the other batch on the device.  A batch of the wave kernels in one stream group is followed as soon as
-         * its LAST FORWARD sweep is over: this batch's first forward sweep then shares the SIMDs with that batch's last
-         * sweep back, as the forward sweep of that batch's own next window would have, and the totals, decode, counts
-         * and packing of that batch run beside this one's first window. */
-        hipEvent_t done = after->ev2;
-        if (after->kernel == CPECAN_KERNEL_SYSTOLIC && after->sy && after->sy->wave && after->nGroups == 1 && after->nWindows > 0 &&
-            after->evStage.size() == (size_t) (4 * after->nWindows + 1))
-            done = after->evStage[(size_t) (1 + 4 * (after->nWindows - 1) + 1)];
-        HIP_TRY(hipStreamWaitEvent(c->stream, done, 0));
-    }
+    /* its own last run first, wherever it went (the ring, state and scratch are the batch's); then the batch it follows,
+     * unless stream order on the lanes already puts this run behind it */
+    if (b->ran) HIP_TRY(hipStreamWaitEvent(L->fwd, b->ev2, 0));
+    if (after && !(after->laneRun && after->runLanes == L)) HIP_TRY(hipStreamWaitEvent(L->fwd, after->ev2, 0));
+    hipStream_t sEnd = L->fwd; /* where the run ends: counts, packing, ev2 */
+    bool laneRun = false;
     b->countsValid = false;
-    HIP_TRY(hipEventRecord(b->ev0, c->stream));
+    HIP_TRY(hipEventRecord(b->ev0, L->fwd));
     if (b->mode == CPECAN_MODE_EXPECTATIONS)
-        HIP_TRY(hipMemsetAsync(b->expect.p, 0, b->expect.n * sizeof(double), c->stream));
-    HIP_TRY(hipEventRecord(b->ev1, c->stream));
+        HIP_TRY(hipMemsetAsync(b->expect.p, 0, b->expect.n * sizeof(double), L->fwd));
+    HIP_TRY(hipEventRecord(b->ev1, L->fwd));
     static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr; /* (tests, timing: the general kernel) */
     if (b->dna && !b->P.debug && !b->P.unbanded && b->maxWidth <= 192 && !wave5Off && !(b->flags & CPECAN_FLAG_GENERAL_KERNEL)) {
         /* the 5-state machine for bands a wave covers in one to three cells per lane: one wave per alignment, the
@@ -1898,7 +1995,7 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
             cpecan_k_wave5_l1, cpecan_k_wave5_l2, cpecan_k_wave5_l3, cpecan_k_wave5e_l1, cpecan_k_wave5e_l2, cpecan_k_wave5e_l3,
             cpecan_k_wave5p_l1, cpecan_k_wave5p_l2, cpecan_k_wave5p_l3, cpecan_k_wave5pe_l1, cpecan_k_wave5pe_l2, cpecan_k_wave5pe_l3 };
         auto kernel5 = kernels5[(size_t) ((paired ? 6 : 0) + (em ? 3 : 0) + l5)];
-        hipLaunchKernelGGL(kernel5, dim3((unsigned) b->nItems), dim3(paired ? 128 : 64), 0, c->stream, (const DevItem *) b->items.p, b->P,
+        hipLaunchKernelGGL(kernel5, dim3((unsigned) b->nItems), dim3(paired ? 128 : 64), 0, L->fwd, (const DevItem *) b->items.p, b->P,
                            (const int *) b->bandL.p, (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
                            (const char *) b->chars.p, (const char *) b->charsY.p, (const double *) c->models5.p,
                            b->Fstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
@@ -1911,7 +2008,7 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                              (const double *) b->logNoise.p, c->modelsE.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
                              b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p, nullptr, nullptr };
         DevEchelonArgs e = { (const char *) b->chars.p, (const long long *) b->xEnd.p, (const double *) b->duration.p };
-        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, c->stream, a, b->P, e);
+        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, L->fwd, a, b->P, e);
         HIP_TRY(hipGetLastError());
     } else if (b->dna || b->sm4 || b->kernel == CPECAN_KERNEL_GENERAL) {
         /* the general kernels (cpecan_general.h): one per machine, one parameter list */
@@ -1947,7 +2044,7 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
         } else {
             a.dbgB = b->dbgB.p;
         }
-        hipLaunchKernelGGL(kernel, dim3((unsigned) b->nItems), dim3(256), lds, c->stream, a, P);
+        hipLaunchKernelGGL(kernel, dim3((unsigned) b->nItems), dim3(256), lds, L->fwd, a, P);
         HIP_TRY(hipGetLastError());
     } else {
         /* one pass: the per-item track of emission constants (a function of the inputs, rebuilt every run inside the
@@ -1969,18 +2066,18 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
         /* the models as the sweeps read them: strawMan tables, or the HDP records of an HDP batch */
         const double *models = b->hdp ? (const double *) c->modelsH.p : b->vanilla ? c->modelsV.p : c->models.p;
         if (b->vanilla) { /* (no gap Y -> gap X transition in this machine) */
-            rc = cpecan_wave_launch_track_vanilla(c->stream, b->items.p, b->nItems, b->track.p, b->trackBase.p,
+            rc = cpecan_wave_launch_track_vanilla(L->fwd, b->items.p, b->nItems, b->track.p, b->trackBase.p,
                                                   b->kidx.p, c->modelsV.p, b->syStates.p, b->maxLX);
         } else if (b->hdp) {
             for (const DevHdpModel &m : c->hostModelsH)
                 if (m.t[T_GAP_SWITCH_TO_X] > -INFINITY) withSwitch = 1;
-            rc = cpecan_wave_launch_track_hdp(c->stream, b->items.p, b->nItems, b->track.p, b->trackBase.p, b->kid.p,
+            rc = cpecan_wave_launch_track_hdp(L->fwd, b->items.p, b->nItems, b->track.p, b->trackBase.p, b->kid.p,
                                               c->modelsH.p, b->syStates.p, b->maxLX);
         } else {
             for (int m = 0; m < c->nModels; m++)
                 if (c->switchToX[(size_t) m] > -INFINITY) withSwitch = 1;
             rc = (b->sy->wave ? cpecan_wave_launch_track : cpecan_systolic_launch_track)(
-                c->stream, b->items.p, b->nItems, b->track.p, b->trackBase.p, b->kidx.p, c->models.p, b->syStates.p,
+                L->fwd, b->items.p, b->nItems, b->track.p, b->trackBase.p, b->kidx.p, c->models.p, b->syStates.p,
                 b->maxLX);
         }
         /* the assembly sweeps (no model of the batch may let gap Y switch to gap X: they have no such term) */
@@ -1995,7 +2092,7 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
             asmArgs.ringD = b->ringD; asmArgs.maxWindows = b->asmMaxWindows; asmArgs.scratch = b->syScratch.p;
             asmArgs.scratchBytes = b->scratchBytes; asmArgs.logThrSlack = b->P.logThrSlack; asmArgs.modelStride = CP_MODEL_STRIDE;
             asmArgs.maskTab = b->asmMasks.p;
-            rc = cpecan_asm_launch_begin(c->stream, b->items.p, b->nItems, b->Fstore.p, b->ringDoubles);
+            rc = cpecan_asm_launch_begin(L->fwd, b->items.p, b->nItems, b->Fstore.p, b->ringDoubles);
             if (getenv("CPECAN_ASM_TRACE")) {
                 auto span = [](const char *what, const void *p, size_t bytes) {
                     fprintf(stderr, "[cpecan asm]   %-10s %p .. %p (%zu bytes)\n", what, p, (const char *) p + bytes, bytes);
@@ -2018,11 +2115,15 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                         b->asmMaxWindows, b->scratchBytes);
             }
         }
-        HIP_TRY(hipEventRecord(b->evFork, c->stream));
+        HIP_TRY(hipEventRecord(b->evFork, L->fwd));
+        laneRun = !b->gStreamOwned;
+        if (laneRun && (!L->back || !L->post)) return fail(CPECAN_EHIP, "lane set without its sweep lanes");
+        if (laneRun) sEnd = L->post;
         const long long per = (b->nItems + G - 1) / G;
         for (int gi = 0; gi < G && rc == 0; gi++) {
             const long long i0 = gi * per, n = std::min<long long>(per, b->nItems - i0);
-            hipStream_t sF = b->gStream[(size_t) gi], sB = b->sy->wave ? b->gStreamB[(size_t) gi] : sF;
+            hipStream_t sF = laneRun ? L->fwd : b->gStream[(size_t) gi];
+            hipStream_t sB = laneRun ? L->back : b->sy->wave ? b->gStreamB[(size_t) gi] : sF;
 #ifdef CPECAN_TIMING_BUILD
             if (getenv("CPECAN_TIMING_SERIAL")) sB = sF; /* timing study: every sweep alone on the chip */
 #endif
@@ -2039,7 +2140,7 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                  * state four window records); what does: the sweep back of w+2 (scratch), the forward sweep of w+3
                  * (ring rows, window record).  The forward sweep of w+2 still waits for the sweep back of w, which reads
                  * the context that sweep will overwrite when it ends. */
-                const bool postAside = asmRun && b->asmBackward && sB != sF && b->asmPost != nullptr;
+                const bool postAside = asmRun && b->asmBackward && sB != sF && b->postAside && laneRun;
                 char *scratchW = b->syScratch.p + (postAside ? (size_t) (w & 1) * (size_t) b->nItems * (size_t) b->scratchBytes : 0);
                 if (sB != sF && w >= 2) HIP_TRY(hipStreamWaitEvent(sF, ev[1 + 4 * (w - 2) + 3], 0));
                 if (postAside && w >= 3) HIP_TRY(hipStreamWaitEvent(sF, b->evPost[(size_t) w - 3], 0));
@@ -2066,7 +2167,7 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                     asmArgs.scratch = scratchW;
                     if (postAside && w >= 2) HIP_TRY(hipStreamWaitEvent(sB, b->evPost[(size_t) w - 2], 0));
                     rc = cpecan_asm_launch_backward(c->device, sB, &asmArgs);
-                    hipStream_t sP = postAside ? b->asmPost : sB;
+                    hipStream_t sP = postAside ? L->post : sB;
                     if (postAside) {
                         HIP_TRY(hipEventRecord(e4[3], sB));
                         HIP_TRY(hipStreamWaitEvent(sP, e4[3], 0));
@@ -2107,14 +2208,14 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                                               b->pairs.p, b->pairLogp.p);
                 if (!postAside) HIP_TRY(hipEventRecord(e4[3], sB));
             }
-            if (asmRun && b->asmBackward && sB != sF && b->asmPost != nullptr && b->nWindows > 0) /* the last post kernel follows all */
-                HIP_TRY(hipStreamWaitEvent(sB, b->evPost[(size_t) b->nWindows - 1], 0));
-            HIP_TRY(hipEventRecord(b->evJoin[(size_t) gi], sB)); /* the last sweep back follows every forward sweep */
-            HIP_TRY(hipStreamWaitEvent(c->stream, b->evJoin[(size_t) gi], 0));
+            /* the last sweep back follows every forward sweep; the run ends behind it on the post lane (after the last
+             * post kernel there), which leaves the forward lane to the next run's first forward sweep */
+            HIP_TRY(hipEventRecord(b->evJoin[(size_t) gi], sB));
+            HIP_TRY(hipStreamWaitEvent(sEnd, b->evJoin[(size_t) gi], 0));
         }
         if (rc == 0)
             rc = (b->sy->wave ? cpecan_wave_launch_counts : cpecan_systolic_launch_counts)(
-                c->stream, b->syStates.p, b->nItems, b->nPairs.p, b->nTot.p, b->nCells.p);
+                sEnd, b->syStates.p, b->nItems, b->nPairs.p, b->nTot.p, b->nCells.p);
         if (rc != 0) return fail(CPECAN_EHIP, "throughput kernel launch failed: %s",
                                  hipGetErrorString(hipGetLastError()));
     }
@@ -2133,19 +2234,61 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
         }
         if (b->packBase.n < (size_t) b->nItems + 1) HIP_TRY(b->packBase.alloc((size_t) b->nItems + 1));
         if (b->undecided.n == 0) HIP_TRY(b->undecided.alloc(1 + 2 * CP_UNDECIDED_CAP));
-        HIP_TRY(hipMemsetAsync(b->undecided.p, 0, sizeof(long long), c->stream));
-        hipLaunchKernelGGL(cpecan_k_pack_base, dim3(1), dim3(256), 0, c->stream, (const DevItem *) b->items.p,
+        HIP_TRY(hipMemsetAsync(b->undecided.p, 0, sizeof(long long), sEnd));
+        hipLaunchKernelGGL(cpecan_k_pack_base, dim3(1), dim3(256), 0, sEnd, (const DevItem *) b->items.p,
                            (const long long *) b->nPairs.p, (long long) b->nItems, b->packBase.p);
-        hipLaunchKernelGGL(cpecan_k_pack_pairs, dim3((unsigned) b->nItems), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(cpecan_k_pack_pairs, dim3((unsigned) b->nItems), dim3(256), 0, sEnd,
                            (const DevItem *) b->items.p, (const long long *) b->packBase.p, (const long long *) b->pairs.p,
                            (const double *) b->pairLogp.p, b->P.threshold, (long long) b->packed.n, b->packed.p,
                            b->packedPost.p, b->undecided.p, b->compactPairs ? 1 : 0);
         HIP_TRY(hipGetLastError());
         b->packedInRun = true;
     }
-    HIP_TRY(hipEventRecord(b->ev2, c->stream));
+    HIP_TRY(hipEventRecord(b->ev2, sEnd));
     b->ran = true;
+    b->laneRun = laneRun;
     return CPECAN_OK;
+}
+
+extern "C" {
+
+int cpecan_hip_batch_run(cpecan_batch *b) { return cpecan_hip_batch_run_after(b, nullptr); }
+
+int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
+    if (!b) return fail(CPECAN_EINVAL, "batch is NULL");
+    cpecan_ctx *c = b->ctx;
+    if (!c) return fail(CPECAN_EINVAL, "the batch's context has been destroyed");
+    if (b->modelEpoch != c->modelEpoch)
+        return fail(CPECAN_EINVAL, "cpecan_hip_models_clear was called on the context after this batch was created: "
+                    "its model ids are gone");
+    if (after && after->device != b->device) return fail(CPECAN_EINVAL, "the two batches live on different devices");
+    HIP_TRY(hipSetDevice(c->device));
+    if (after == b || (after && !after->ran)) after = nullptr;
+    /* behind a wave batch of one stream group, the whole run goes on the lanes that batch ran on: this batch's first
+     * forward sweep follows that batch's LAST FORWARD sweep on the forward lane and shares the SIMDs with its last
+     * sweep back, as the forward sweep of that batch's own next window would have; its sweeps back and post kernels
+     * queue behind that batch's on the other two lanes.  Otherwise on this context's lanes, behind the whole run of
+     * `after`. */
+    LaneSet *L = (after && after->laneRun && after->runLanes) ? after->runLanes : c->lanes;
+    std::lock_guard<std::mutex> hold(L->mu);
+    if (b->runLanes != L) {
+        L->refs++;
+        lanes_release(b->runLanes);
+        b->runLanes = L;
+    }
+    const int rc = batch_enqueue(b, after, L);
+    if (rc != CPECAN_OK) {
+        /* what was queued of the run is over before the error goes back (sync and destroy wait for its end event,
+         * which it never recorded) */
+        for (hipStream_t s : { L->fwd, L->back, L->post })
+            if (s) (void) hipStreamSynchronize(s);
+        if (b->gStreamOwned)
+            for (hipStream_t s : b->gStream) (void) hipStreamSynchronize(s);
+        for (hipStream_t s : b->gStreamB) (void) hipStreamSynchronize(s);
+        b->ran = false;
+        b->laneRun = false;
+    }
+    return rc;
 }
 
 int cpecan_hip_batch_systolic_rows(cpecan_batch *b, int32_t *rows) {
@@ -2217,7 +2360,8 @@ int cpecan_hip_batch_shader_clock_mhz(cpecan_batch *b, double *mhz) {
     *mhz = 0.0;
     if (!b->ran || b->kernel != CPECAN_KERNEL_SYSTOLIC || !b->sy->wave) return CPECAN_OK; /* not measured on this path */
     HIP_TRY(hipSetDevice(b->ctx->device));
-    if (cpecan_wave_shader_clock_mhz(b->ctx->stream, b->syStates.p, b->nItems, mhz) != 0)
+    HIP_TRY(hipEventSynchronize(b->ev2));
+    if (cpecan_wave_shader_clock_mhz(b->ctx->prep, b->syStates.p, b->nItems, mhz) != 0)
         return fail(CPECAN_EHIP, "reading the sweeps' clock counters failed");
     return CPECAN_OK;
 }
@@ -2232,8 +2376,9 @@ int cpecan_hip_batch_info(cpecan_batch *b, int32_t *kernel, int32_t *workgroups,
 
 int cpecan_hip_batch_sync(cpecan_batch *b) {
     if (!b) return fail(CPECAN_EINVAL, "batch is NULL");
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    HIP_TRY(hipSetDevice(b->device));
+    /* its own end event: the lanes it ran on may already carry the next batch's run */
+    if (b->ran) HIP_TRY(hipEventSynchronize(b->ev2));
     return CPECAN_OK;
 }
 
@@ -2336,10 +2481,13 @@ static int ensure_counts(cpecan_batch *b) {
     if (b->countsValid) return CPECAN_OK;
     HIP_TRY(hipSetDevice(b->ctx->device));
     Lap lap("ensure_counts");
+    /* readbacks wait for the run's end event and go through the context's prep stream: the lanes the run went on may
+     * carry the next batch's run already */
+    hipStream_t rs = b->ctx->prep;
     b->hNPairs.resize((size_t) b->nItems);
     b->hNTot.resize((size_t) b->nItems);
     for (int attempt = 0;; attempt++) {
-        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+        HIP_TRY(hipEventSynchronize(b->ev2));
         HIP_TRY(hipMemcpy(b->hNPairs.data(), b->nPairs.p, (size_t) b->nItems * sizeof(long long), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(b->hNTot.data(), b->nTot.p, (size_t) b->nItems * sizeof(long long), hipMemcpyDeviceToHost));
         bool over = false;
@@ -2374,11 +2522,11 @@ static int ensure_counts(cpecan_batch *b) {
             const long long n = b->hPairBase[(size_t) i + 1] - b->hPairBase[(size_t) i], o = b->hPairBase[(size_t) i];
             if (n == 0) continue;
             HIP_TRY(hipMemcpyAsync(b->hPairs.data() + o * 3, b->pairs.p + d.pairBase * 3, (size_t) n * 3 * sizeof(long long),
-                                   hipMemcpyDeviceToHost, b->ctx->stream));
+                                   hipMemcpyDeviceToHost, rs));
             HIP_TRY(hipMemcpyAsync(b->hLogp.data() + o, b->pairLogp.p + d.pairBase, (size_t) n * sizeof(double),
-                                   hipMemcpyDeviceToHost, b->ctx->stream));
+                                   hipMemcpyDeviceToHost, rs));
         }
-        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(rs));
         if (b->hdp && b->kernel == CPECAN_KERNEL_SYSTOLIC) {
             /* the HDP machine's event assignments from the wave kernels: appended by whichever thread got there, each
              * tagged with its traceback window (first field = from-state + 4 * window).  The reference walks windows
@@ -2440,21 +2588,21 @@ static int ensure_counts(cpecan_batch *b) {
             HIP_TRY(pinned_cache().get((void **) &b->hUndecided, (1 + 2 * CP_UNDECIDED_CAP) * sizeof(long long), &b->hUndecidedBlock));
         if (!packedAlready) {
         HIP_TRY(hipMemcpyAsync(b->packBase.p, b->hPairBase.data(), ((size_t) b->nItems + 1) * sizeof(long long),
-                               hipMemcpyHostToDevice, b->ctx->stream));
-        HIP_TRY(hipMemsetAsync(b->undecided.p, 0, sizeof(long long), b->ctx->stream));
-        hipLaunchKernelGGL(cpecan_k_pack_pairs, dim3((unsigned) b->nItems), dim3(256), 0, b->ctx->stream,
+                               hipMemcpyHostToDevice, rs));
+        HIP_TRY(hipMemsetAsync(b->undecided.p, 0, sizeof(long long), rs));
+        hipLaunchKernelGGL(cpecan_k_pack_pairs, dim3((unsigned) b->nItems), dim3(256), 0, rs,
                            (const DevItem *) b->items.p, (const long long *) b->packBase.p, (const long long *) b->pairs.p,
                            (const double *) b->pairLogp.p, b->P.threshold, (long long) b->packed.n, b->packed.p,
                            b->packedPost.p, b->undecided.p, b->compactPairs ? 1 : 0);
         HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemcpyAsync(b->hUndecided, b->undecided.p, (1 + 2 * CP_UNDECIDED_CAP) * sizeof(long long),
-                               hipMemcpyDeviceToHost, b->ctx->stream));
+                               hipMemcpyDeviceToHost, rs));
         HIP_TRY(hipMemcpyAsync(b->hPacked, b->packed.p, (size_t) all * (b->compactPairs ? sizeof(unsigned) : sizeof(PackedPair)),
-                               hipMemcpyDeviceToHost, b->ctx->stream));
+                               hipMemcpyDeviceToHost, rs));
         HIP_TRY(hipMemcpyAsync(b->hPost, b->packedPost.p, (size_t) all * sizeof(int), hipMemcpyDeviceToHost,
-                               b->ctx->stream));
-        HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+                               rs));
+        HIP_TRY(hipStreamSynchronize(rs));
     }
     /* The close calls: exp(), the threshold test and floor(p * 1e7) with the host's libm, the one the reference calls
      * (impl/pairwiseAligner.c:776-786), written back over the device's "undecided" verdict; and the number of pairs
@@ -2604,7 +2752,7 @@ int cpecan_hip_batch_expectations_device_ptr(cpecan_batch *b, void **devPtr, int
 int cpecan_hip_batch_fetch_expectations(cpecan_batch *b, int32_t modelId, double *out) {
     if (!b || !out || modelId < 0 || modelId >= b->nModels) return fail(CPECAN_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    if (b->ran) HIP_TRY(hipEventSynchronize(b->ev2));
     HIP_TRY(hipMemcpy(out, b->expect.p + (size_t) modelId * b->expectLen, (size_t) b->expectLen * sizeof(double),
                       hipMemcpyDeviceToHost));
     return CPECAN_OK;
@@ -2618,7 +2766,7 @@ int cpecan_hip_batch_debug_cells(cpecan_batch *b, int64_t item, double *forward,
     const DevItem &d = b->hItems[(size_t) item];
     if (nCells < d.nCells) return fail(CPECAN_EOVERFLOW, "need room for %lld cells", d.nCells);
     HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    if (b->ran) HIP_TRY(hipEventSynchronize(b->ev2));
     if (forward)
         HIP_TRY(hipMemcpy(forward, b->Fstore.p + d.cellBase * 3, (size_t) d.nCells * 3 * sizeof(double),
                           hipMemcpyDeviceToHost));

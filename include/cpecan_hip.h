@@ -289,13 +289,25 @@ int cpecan_hip_batch_create_hdp(cpecan_ctx *ctx, const cpecan_item *items, int64
 
 int cpecan_hip_batch_run(cpecan_batch *batch);
 /* The same, but ordered on the device behind the last run of `after` (a batch on the same device; NULL, the batch
- * itself or a batch that has never run: no condition), with no host round trip.  What is ordered: if `after` runs on
- * the wave-per-alignment kernels as one stream group, this batch's kernels start when `after`'s last forward sweep has
- * finished (its sweeps back, decode and pair packing may still be running); otherwise when `after`'s whole run has
- * finished.  Either way `after`'s results are read through `after`'s own cpecan_hip_batch_sync or readback
- * (counts, pairs, totals), never on the strength of this batch having finished.  A stream of batches then keeps the
- * device busy with one pass at a time (the wave-per-alignment kernels fill the register files with one batch) while
- * the host fetches and finishes the previous batch's pairs and prepares the next one. */
+ * itself or a batch that has never run: no condition), with no host round trip.
+ * Every run goes on a lane set: three streams (forward sweeps; sweeps back; post kernels, counts and pair packing).
+ * Each context has one; a run with no condition uses its own context's.
+ * What is ordered:
+ *  - `after` ran on the wave-per-alignment kernels as one stream group: this run is issued on the lane set `after`
+ *    ran on, behind it on each of the three streams.  Its first kernel starts when `after`'s last forward sweep has
+ *    finished; its sweeps back queue behind `after`'s sweeps back, its post kernels, counts and packing behind
+ *    `after`'s.  A chain of such batches uses the three streams of its first batch's lane set, whatever the number of
+ *    batches and contexts in it: it fits the runtime's default of four hardware queues.
+ *  - otherwise: this run starts, on its own context's lane set, when `after`'s whole run has finished.
+ *  - always: this run starts after the batch's own previous run has finished, wherever that one went.
+ * What is not ordered: nothing says that `after` has finished when this run has.  `after`'s results are read through
+ * `after`'s own cpecan_hip_batch_sync or readback (counts, pairs, totals), which wait for `after`'s run alone and not
+ * for the lanes it went on.  Runs of two host threads onto one lane set are queued whole, one after the other; a batch
+ * itself (and a context) is used by one thread at a time.  A run holds its lane set until the batch runs again or is
+ * destroyed, so `after`'s context may be destroyed while this run goes on.
+ * A stream of batches then keeps the device busy with one pass at a time (the wave-per-alignment kernels fill the
+ * register files with one batch) while the host fetches and finishes the previous batch's pairs and prepares the next
+ * one. */
 int cpecan_hip_batch_run_after(cpecan_batch *batch, cpecan_batch *after);
 int cpecan_hip_batch_sync(cpecan_batch *batch);
 /* HIP-event time of the last run's kernels, in ms (after sync). */
@@ -376,8 +388,11 @@ int cpecan_hip_selftest_division(cpecan_ctx *ctx, int64_t n, uint64_t seed, int6
  * process, or on the card, needs the memory. */
 int cpecan_hip_trim_cache(void);
 
-/* Stream of the context as an opaque pointer (a hipStream_t) for callers that need to order
- * their own work (e.g. an RCCL all-reduce of the expectations) after the batch kernels. */
+/* Stream of the context as an opaque pointer (a hipStream_t) for callers' own work (e.g. an RCCL all-reduce of the
+ * expectations): the forward stream of the context's lane set (cpecan_hip_batch_run_after).  A run of a wave batch
+ * of one stream group ends on the lane set's post stream, not on this one (other runs -- workgroup kernels, several
+ * stream groups, the general kernels -- do end on it), and the stream may carry other contexts' runs: work that needs
+ * a batch's results goes after cpecan_hip_batch_sync. */
 int cpecan_hip_ctx_stream(cpecan_ctx *ctx, void **stream);
 
 #ifdef __cplusplus
