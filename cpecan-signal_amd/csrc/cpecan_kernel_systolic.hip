@@ -667,7 +667,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
     const int tPost0 = dTop < tracedBackFrom ? dTop : tracedBackFrom; /* first decoded diagonal */
     const int nPost = tPost0 - tracedBackTo;                         /* diagonals decoded      */
     band_stage(bf, bandTab, D, dTop - (SY_BAND_RING - 1), dTop);
-    if (threadIdx.x == 0) sh.scan = 0;
+    /* threshold 0: every in-band cell is a pair, one of exponent -inf too (exp(-inf) = 0 >= 0, :776-786), and the
+     * candidates leave those out: the scan decodes the window, as in the wave kernels */
+    if (threadIdx.x == 0) sh.scan = P.logThrSlack > CP_NEG_INF ? 0 : 1;
     __syncthreads();
     /* Candidates for the posterior decode, collected by the sweep: a cell whose F.match + B.match
      * lies within SY_CAND_SLACK of the threshold, measured against an estimate of the window's

@@ -1,0 +1,347 @@
+"""Reads whose alignment path runs at a chosen place in the band: on its lower edge (the cell of least x on each
+diagonal, xmin), on its upper edge (xmax), a given number of cells inside or outside either, or across it.
+
+synth.make_read puts the anchors on the true path, so the band is centred on the path and its edge cells hold almost no
+mass: a kernel that gets an edge cell wrong leaves every total and pair unchanged.  Here the order is the other way
+round: the anchors come first (on a nominal path drawn like make_read's), the band follows from them (o.band), and only
+then is the read's own event-to-k-mer path drawn, one step at a time, to stay at the prescribed offset from the chosen
+edge; the events are emitted from that path as make_read emits them.  Posteriors of such reads are as sharp as those of
+make_read's, so the mass follows the path onto the edge.
+
+Coordinates are the band's: cell (x, y) has consumed x k-mers and y events, diagonal d = x + y, xmy = x - y, and
+diagonal d holds the cells L[d] <= xmy <= R[d] (steps of two).  A match step goes (x, y) -> (x + 1, y + 1) and emits
+event y from k-mer x; a gap-Y step (a stay) goes to (x, y + 1) and emits event y from k-mer x - 1; a gap-X step (a
+skipped k-mer) goes to (x + 1, y) and emits nothing.
+"""
+import numpy as np
+
+import pyoracle as o
+import synth
+
+# the widest band each build takes (k-mers): the workgroup family's waves, the wave family's cells per lane, the
+# assembly sweeps (three cells per lane, 121..158)
+WG1, WAVE_L2, ASM_MAX, WAVE_L3, WAVE_L4 = 56, 120, 158, 184, 248
+MAX_STAYS = 8
+HDP_SD = 1.0
+
+
+def nominal_counts(rng, lX, lY, skip=None):
+    """events per k-mer as make_read draws them (0 with p = .1, else 1 + geometric stays, forced to sum to lY).
+    skip = (a, S, dwell): k-mers a .. a + S - 1 emit nothing and k-mer a - 1 emits `dwell` events, the others at least
+    one each"""
+    stay = max(0.05, min(0.9, 1.0 - 0.9 * lX / max(lY, 1))) if lY > 0.9 * lX else 0.05
+    counts = np.where(rng.random(lX) < 0.10, 0, rng.geometric(1.0 - stay, lX))
+    fixed = np.zeros(lX, bool)
+    if skip is not None:
+        a, S, dwell = skip
+        counts[a:a + S] = 0
+        counts[a - 1] = dwell
+        fixed[a - 1:a + S] = True
+        free = ~fixed
+        counts[free] = np.maximum(counts[free], 1)
+    diff = int(lY - counts.sum())
+    while diff != 0:
+        if diff > 0:
+            pick = rng.choice(np.flatnonzero(~fixed), size=diff)
+            np.add.at(counts, pick, 1)
+        else:
+            nz = np.flatnonzero((counts > (1 if skip is not None else 0)) & ~fixed)
+            pick = rng.choice(nz, size=min(-diff, nz.size), replace=False)
+            counts[pick] -= 1
+        diff = int(lY - counts.sum())
+    return counts
+
+
+def anchors_of(counts, every, skip=None):
+    """every `every`-th k-mer that emitted, at its first event (make_read's rule without the jitter); none inside a
+    skipped stretch, so that one anchor pair spans it"""
+    lX = len(counts)
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    out = []
+    px = py = -1
+    for x0 in range(every // 2, lX, every):
+        x = x0
+        while x < lX and counts[x] == 0:
+            x += 1
+        if x >= lX:
+            break
+        if skip is not None and skip[0] - 1 < x0 < skip[0] + skip[1]:
+            continue
+        if x > px and first[x] > py:
+            out.append((x, int(first[x])))
+            px, py = x, int(first[x])
+    if skip is not None:  # the stretch's two ends: its dwell k-mer and the first k-mer after it
+        a, S, _ = skip
+        out = [p for p in out if not a - 1 <= p[0] <= a + S] + [(a - 1, int(first[a - 1])),
+                                                                              (a + S, int(first[a + S]))]
+        out.sort()
+    return np.array(out, np.int64).reshape(-1, 2)
+
+
+def widest(anchors, lX, lY, e):
+    L, R = o.band(anchors, lX, lY, e)
+    return int(((R - L) // 2 + 1).max())
+
+
+def target_of(L, R, place, offset, cross=None):
+    """the wanted xmy on every diagonal: `offset` cells inside the lower (place 'lower') or upper edge (negative: that
+    many cells outside it); cross = (d0, d1): lower edge up to d0, upper edge from d1, a straight line between"""
+    lo = L + 2 * offset
+    hi = R - 2 * offset
+    if place == "lower":
+        return lo
+    if place == "upper":
+        return hi
+    d0, d1 = cross
+    d = np.arange(len(L))
+    f = np.clip((d - d0) / max(d1 - d0, 1), 0.0, 1.0)
+    t = np.rint((1 - f) * lo + f * hi).astype(np.int64)
+    return t + ((t + d) & 1)  # xmy has the parity of its diagonal
+
+
+def walk(rng, lX, lY, target):
+    """the path from (0, 0) to (lX, lY) whose xmy stays as close to target[d] as the steps allow: a match step
+    wherever it is as close as a gap step, else the closer gap step.  The strawMan machine has no gap X <-> gap Y
+    switch, so a match step comes between a skip and a stay; no k-mer gets more than MAX_STAYS stays (where the edge
+    runs along one k-mer for longer, at the read's first k-mer say, the path leaves it for a while), and no stay comes
+    before the first k-mer (the model emits it from no k-mer).  Returns (the k-mer of every event (len lY), the path's
+    cells (x, y) in order, (0, 0) first)."""
+    x = y = run = 0
+    last = "M"
+    ev_kmer = []
+    cells = [(0, 0)]
+    while x < lX or y < lY:
+        opts = []
+        if x < lX and y < lY:
+            opts.append((abs(x - y - target[x + y + 2]), 0 if run < MAX_STAYS else -1, "M"))
+        if x < lX and (last != "Y" or y == lY):
+            opts.append((abs(x + 1 - y - target[x + y + 1]), 1 + rng.random(), "X"))
+        if y < lY and (x > 0 or x == lX) and (last != "X" or x == lX) and (run < MAX_STAYS or x == lX):
+            opts.append((abs(x - y - 1 - target[x + y + 1]), 1 + rng.random(), "Y"))
+        step = min(opts, key=lambda o: (o[0] if o[1] >= 0 else -1, o[1]))[2]
+        run = run + 1 if step == "Y" and last == "Y" else (1 if step == "Y" else 0)
+        last = step
+        if last == "M":
+            ev_kmer.append(x)
+            x += 1
+            y += 1
+        elif last == "X":
+            x += 1
+        else:
+            ev_kmer.append(x - 1)
+            y += 1
+        cells.append((x, y))
+    return np.array(ev_kmer, np.int64), np.array(cells, np.int64)
+
+
+def emit(rng, match, kidx, ev_kmer):
+    """events of a path, as make_read emits them (per-read affine rescaling of the pore model)"""
+    lY = len(ev_kmer)
+    scale, shift = rng.uniform(0.95, 1.05), rng.uniform(-5.0, 5.0)
+    var, scale_sd, var_sd = rng.uniform(0.9, 1.1), rng.uniform(0.9, 1.2), rng.uniform(0.9, 1.2)
+    scaled = synth.scale_model(match, scale, shift, var, scale_sd, var_sd)
+    t = scaled[1:].reshape(synth.NUM_KMERS, 5)[kidx[ev_kmer]]
+    events = np.zeros((lY, 3))
+    events[:, 0] = rng.normal(t[:, 0], t[:, 1])
+    events[:, 1] = np.maximum(np.abs(rng.normal(t[:, 2], t[:, 3])), 1e-3)
+    events[:, 2] = rng.exponential(0.01, lY)
+    return events, scaled, (scale, shift, var, scale_sd, var_sd)
+
+
+def plan(rng, lX, lY, every, width, skip=None, e=None):
+    """(anchors, expansion, nominal counts) of a read whose widest band is exactly `width` k-mers (the expansion is even: widths step
+    by two with it, so a nominal path of the wrong parity is drawn again); with e given, a read whose widest band at
+    that expansion is at most `width`"""
+    for k in range(64):
+        sk = None if skip is None else (skip[0], skip[1], skip[2] + k % 4)  # (the dwell sets the parity)
+        counts = nominal_counts(rng, lX, lY, sk)
+        an = anchors_of(counts, every, sk)
+        if e is not None:
+            if widest(an, lX, lY, e) <= width:
+                return an, e, counts
+            continue
+        e0 = 2 * max(1, (width - 2 * every) // 2)
+        ew = e0 + width - widest(an, lX, lY, e0)
+        if ew >= 0 and ew % 2 == 0 and widest(an, lX, lY, ew) == width:
+            return an, ew, counts
+    raise ValueError("no nominal path gives a band %d k-mers wide" % width)
+
+
+def emit_hdp(rng, seq_bytes, ev_kmer, hdp):
+    """events of a path for the HDP machine, as harness.hdp_batch draws them: around the mode of each k-mer's HDP
+    density.  hdp = (the nhdp dict of pyoracle.load_nhdp, the oracle's HdpModel)"""
+    nhdp, model = hdp
+    x = seq_bytes.decode()
+    mode = {}
+    events = np.zeros((len(ev_kmer), 3))
+    for j, k in enumerate(ev_kmer):
+        if k not in mode:
+            row = nhdp["kmer_row"][model.kmer_id(x[k:k + 6])]
+            mode[k] = nhdp["grid"][int(np.argmax(nhdp["y"][row]))]
+        events[j] = (mode[k] + rng.normal(0, HDP_SD), abs(rng.normal(1.0, 0.2)) + 1e-3, 0.01)
+    return events
+
+
+def edge_read(rng, match, lX, lY, e, place, offset=0, every=4, width=None, cross=None, skip=None, centred=False,
+              hdp=None):
+    """One strand whose path runs `offset` cells inside the `place` edge of its band ('lower', 'upper', or 'cross'
+    with cross = (d0, d1) as fractions of the diagonals).  With width set and e None, the expansion is chosen to make
+    the widest band exactly that many k-mers; with both set, the widest band at expansion e is at most `width`.
+    centred: the same sequence and anchors (so the same band), the events emitted from the nominal path the anchors
+    sit on instead: the mass down the middle of the band.  hdp: events for the HDP machine (emit_hdp).
+    Returns make_read's dict plus the expansion and the band."""
+    seq = rng.integers(0, 4, lX + 5).astype(np.uint8)
+    seq_bytes = bytes(np.frombuffer(b"ACGT", np.uint8)[seq])
+    kidx = synth.kmer_indices(seq_bytes)
+    if width is not None:
+        anchors, e, counts = plan(rng, lX, lY, every, width, skip, e)
+    else:
+        counts = nominal_counts(rng, lX, lY, skip)
+        anchors = anchors_of(counts, every, skip)
+    L, R = o.band(anchors, lX, lY, e)
+    if cross is not None:
+        cross = (int(cross[0] * (lX + lY)), int(cross[1] * (lX + lY)))
+    target = np.concatenate([target_of(L, R, place, offset, cross), [0, 0]])
+    ev_kmer, cells = walk(rng, lX, lY, target)
+    if centred:
+        ev_kmer, cells = np.repeat(np.arange(lX), counts), None
+    if hdp is not None:
+        return dict(seq=seq_bytes, events=emit_hdp(rng, seq_bytes, ev_kmer, hdp), anchors=anchors, ev_kmer=ev_kmer,
+                    cells=cells, e=e, L=L, R=R)
+    events, scaled, params = emit(rng, match, kidx, ev_kmer)
+    return dict(seq=seq_bytes, events=events, anchors=anchors, scaled_match=scaled, scale_params=params,
+                ev_kmer=ev_kmer, cells=cells, e=e, L=L, R=R)
+
+
+def edge_batch(seed, n, lX, lY, place, offset=0, every=4, e=40, width=None, cross=None, skip=None,
+               model_seed=synth.SEED0, centred=False, hdp=None):
+    """make_batch's layout (one scaled model per read) for n edge reads; every read gets the same expansion (the
+    first read's when width is set: its band is then exactly `width` wide, the others' at most that).  centred: the
+    same band, the mass in its middle (edge_read).  hdp: reads for the HDP machine, one model (id 0) shared, the
+    sequences as text (harness.hdp_batch's layout)"""
+    match, gap_x, gap_y = synth.synthetic_pore_model(model_seed)
+    xs, evs, ans, items, models = [], [], [], [], []
+    xo = yo = ao = 0
+    for r in range(n):
+        rng = np.random.default_rng(synth.SEED0 + seed * 1000 + r)
+        rd = edge_read(rng, match, lX, lY, None if width is not None and r == 0 else e, place, offset, every, width,
+                       cross, skip, centred, hdp)
+        if r == 0:
+            e = rd["e"]
+        xs.append(rd["seq"])
+        evs.append(rd["events"])
+        ans.append(rd["anchors"])
+        if hdp is None:
+            models.append((rd["scaled_match"], gap_x, gap_y))
+        items.append(dict(x_offset=xo, lX=lX, y_offset=yo, lY=lY, anchor_offset=ao, n_anchors=len(rd["anchors"]),
+                          model=0 if hdp is not None else r))
+        xo += lX + 5
+        yo += lY
+        ao += len(rd["anchors"])
+    if hdp is not None:
+        return dict(x_chars=b"".join(xs).decode(), events=np.concatenate(evs), anchors=np.concatenate(ans),
+                    items=items, e=e)
+    return dict(x_chars=b"".join(xs), events=np.concatenate(evs), anchors=np.concatenate(ans), items=items,
+                models=models, base_model=(match, gap_x, gap_y), e=e)
+
+
+def edge_mass(batch, i, bp, ragged=(0, 0), transitions=None):
+    """the oracle's cell dump of item i of a batch as per-diagonal arrays, a dict: dump (the oracle's), match[d] the
+    match posterior exp(F + B - total) of diagonal d's cells from xmin up (total: the window's, as the reference
+    refreshes it every ten decoded diagonals), gapx[d] the same of gap X, cell[d] the cells' posterior summed over the
+    states, xmin[d] the diagonal's least x, seg[d] the diagonal at which the total that covers d was refreshed"""
+    from harness import run_oracle_item
+    dump = run_oracle_item(batch, i, bp, ragged, transitions=transitions, dump=True)
+    txay = np.asarray(dump["totals_xay"])
+    tval = np.asarray(dump["totals"])
+    order = np.argsort(txay)
+    txay, tval = txay[order], tval[order]
+    F, B, L, R, off = dump["F"], dump["B"], dump["L"], dump["R"], dump["offsets"]
+    nd = len(L)
+    seg = np.searchsorted(txay, np.arange(nd))  # the refresh (of the total) that covers each diagonal
+    match, gapx, cell, xmin = [], [], [], []
+    for d in range(nd):
+        tot = tval[min(seg[d], len(tval) - 1)]
+        c = slice(off[d], off[d + 1])
+        p = np.exp(F[c] + B[c] - tot)
+        match.append(p[:, 0])
+        gapx.append(p[:, 1])
+        cell.append(p.sum(axis=1))
+        xmin.append((d + int(L[d])) // 2)
+    return dict(dump=dump, match=match, gapx=gapx, cell=cell, xmin=np.array(xmin),
+                seg=txay[np.minimum(seg, len(txay) - 1)])
+
+
+def edge_fraction(m, place, thr, reach=1, skip_ends=0, kind="match"):
+    """fraction of the diagonals d > 0 (less `skip_ends` at either end) whose cell on the `place` edge ('lower':
+    xmin, 'upper': xmax), or one within `reach` cells of it, has posterior >= thr: of the match state (kind 'match')
+    or of the cell, all states together ('cell')"""
+    nd = len(m[kind])
+    hit = n = 0
+    for d in range(1 + skip_ends, nd - skip_ends):
+        p = m[kind][d]
+        cells = p[:reach + 1] if place == "lower" else p[-(reach + 1):]
+        n += 1
+        hit += bool(cells.max() >= thr)
+    return hit / max(n, 1)
+
+
+def a_record_slots(m, cells_per_lane, floor=1e-3):
+    """the fused E-step's A-record condition on an oracle dump (edge_mass): refresh segments (the decoded diagonals
+    that share one total) in which one slot of the wave kernel (column x mod 64 * cells_per_lane) holds two columns
+    of the band, the higher one (the sweep back meets it first, and moves the slot on from it) with gap-X posterior
+    >= floor summed over the segment.  The issue that asked for this condition wants gap-X mass on both columns; the
+    kernel's store (cpecan_kernel_wave.hip, `x != cA[j]`) fires whenever the slot moves on from a column whose sum is
+    non-zero, whatever the new column holds, and a lost A record loses the higher column's sum only, so the lower
+    column has only to be in the band here.  Returns a list of (segment's top diagonal, slot, higher column, its gap-X
+    mass, lower column)."""
+    P = 64 * cells_per_lane
+    segs = {}
+    for d in range(1, len(m["gapx"])):
+        g = m["gapx"][d]
+        seg = segs.setdefault(int(m["seg"][d]), {})
+        for x, v in zip(m["xmin"][d] + np.arange(len(g)), g):
+            col = seg.setdefault(int(x) % P, {})
+            col[int(x)] = col.get(int(x), 0.0) + float(v)
+    out = []
+    for top, seg in sorted(segs.items()):
+        for slot, cols in seg.items():
+            if len(cols) > 1 and cols[max(cols)] >= floor:
+                out.append((top, slot, max(cols), cols[max(cols)], min(cols)))
+    return out
+
+
+# ---------------------------------------------- the case families ----------------------------------------------
+# name -> edge_batch arguments and what the coverage test asserts on the oracle (tests/test_band_edges_cpu.py):
+# `frac` of the decoded diagonals have posterior >= 0.01 (the cell's, all states) on the `place` edge or one cell
+# inside it; `width` the widest band; `arec` the cells per lane of the wave build whose A-record condition must occur
+FAMILY = dict(lX=200, lY=300, every=1, e=40, md=100, tb=40, ragged=(0, 0), offset=0, frac=0.25, width=None,
+              cross=None, skip=None, arec=None, seed=1)
+
+
+def _f(**kw):
+    return dict(FAMILY, **kw)
+
+
+FAMILIES = {
+    "lower": _f(place="lower", ragged=(1, 1), frac=0.25),
+    "lower1": _f(place="lower", offset=1, frac=0.25),
+    "upper": _f(place="upper", frac=0.5),
+    "upper1": _f(place="upper", offset=1, ragged=(1, 1), frac=0.5),
+    "lower-out": _f(place="lower", offset=-2, ragged=(1, 0), frac=0.02),
+    "upper-out": _f(place="upper", offset=-2, ragged=(0, 1), frac=0.05),
+    "cross": _f(place="cross", cross=(0.45, 0.5), md=60, tb=30, ragged=(1, 1), frac=0.05),
+}
+for _w in (56, 57, 120, 121, 158, 159, 184, 185, 248, 249):  # each build's widest band and one k-mer past it
+    FAMILIES["w%d" % _w] = _f(place="upper", lX=300, lY=450, width=_w, md=150, tb=40, ragged=(_w % 2, 1))
+FAMILIES["arec120"] = _f(place="upper", lX=300, lY=500, width=120, skip=(150, 30, 1), md=150, tb=40, ragged=(1, 1),
+                         arec=2)
+FAMILIES["arec184"] = _f(place="upper", lX=300, lY=500, width=184, skip=(150, 30, 1), md=150, tb=40, ragged=(1, 1),
+                         arec=3, seed=2)
+
+
+def family_batch(name, n=2, seed=None, centred=False, hdp=None):
+    f = FAMILIES[name]
+    return edge_batch(f["seed"] if seed is None else seed, n, f["lX"], f["lY"], f["place"], f["offset"],
+                      every=f["every"], e=f["e"], width=f["width"], cross=f["cross"], skip=f["skip"], centred=centred,
+                      hdp=hdp)
