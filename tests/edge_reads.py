@@ -345,3 +345,164 @@ def family_batch(name, n=2, seed=None, centred=False, hdp=None):
     return edge_batch(f["seed"] if seed is None else seed, n, f["lX"], f["lY"], f["place"], f["offset"],
                       every=f["every"], e=f["e"], width=f["width"], cross=f["cross"], skip=f["skip"], centred=centred,
                       hdp=hdp)
+
+
+# ------------------------------------------------ DNA (5-state) ------------------------------------------------
+# The same path-first construction for the 5-state symbol machine (DNA against DNA): x is lX bases (no pad), y the
+# bases the path emits.  A match step copies x's base into y (a substitution with probability DNA_SUB), a gap-Y step
+# inserts a random base, a gap-X step deletes x's base.  Bands are in cells of the (lX + 1) x (lY + 1) matrix.
+DNA_SUB = 0.02
+# the widest band of each 5-state build (cells): the wave5 kernels at one, two, three cells per lane; the general
+# kernel keeps its diagonals in LDS up to DNA_LDS, in HBM past it; its workgroup has 256 threads
+DNA_WAVE_L1, DNA_WAVE_L2, DNA_WAVE_L3, DNA_LDS, GENERAL_THREADS = 64, 128, 192, 248, 256
+
+
+def dna_y(rng, xb, cells):
+    """the bases a path (walk's cells, (0, 0) first) emits against x (0..3 codes)"""
+    y = []
+    for (x0, y0), (x1, y1) in zip(cells[:-1], cells[1:]):
+        if y1 == y0:
+            continue  # gap X: x's base deleted
+        if x1 == x0:
+            y.append(int(rng.integers(0, 4)))  # gap Y: an inserted base
+        elif rng.random() < DNA_SUB:
+            y.append(int((xb[x0] + rng.integers(1, 4)) % 4))
+        else:
+            y.append(int(xb[x0]))
+    return np.array(y, np.int64)
+
+
+def nominal_cells(counts):
+    """the nominal path of `counts` (nominal_counts) as cells: base x is matched to the first of its counts[x] y's and
+    the others inserted after it; counts[x] = 0 deletes it"""
+    x = y = 0
+    cells = [(0, 0)]
+    for c in counts:
+        if c == 0:
+            x += 1
+        else:
+            x, y = x + 1, y + 1
+        cells.append((x, y))
+        for _ in range(int(c) - 1):
+            y += 1
+            cells.append((x, y))
+    return np.array(cells, np.int64)
+
+
+def dna_read(rng, lX, lY, e, place, offset=0, every=4, width=None, cross=None, centred=False):
+    """one DNA pair (x, y) whose path runs as edge_read's does; centred: the same x and anchors (so the same band), y
+    emitted from the nominal path the anchors sit on.  Returns a dict: x, y (strings), anchors, cells (the path), e,
+    L, R"""
+    xb = rng.integers(0, 4, lX)
+    if width is not None:
+        anchors, e, counts = plan(rng, lX, lY, every, width, None, e)
+    else:
+        counts = nominal_counts(rng, lX, lY)
+        anchors = anchors_of(counts, every)
+    L, R = o.band(anchors, lX, lY, e)
+    if cross is not None:
+        cross = (int(cross[0] * (lX + lY)), int(cross[1] * (lX + lY)))
+    target = np.concatenate([target_of(L, R, place, offset, cross), [0, 0]])
+    _, cells = walk(rng, lX, lY, target)
+    if centred:
+        cells = nominal_cells(counts)
+    yb = dna_y(rng, xb, cells)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    return dict(x=bytes(acgt[xb]).decode(), y=bytes(acgt[yb]).decode(), anchors=anchors, cells=cells, e=e, L=L, R=R)
+
+
+DNA_FAMILY = dict(lX=300, lY=300, every=1, e=40, md=100, tb=40, ragged=(0, 0), offset=0, frac=0.25, width=None,
+                  cross=None, seed=1)
+
+
+def _d(**kw):
+    return dict(DNA_FAMILY, **kw)
+
+
+# name -> dna_batch arguments and what test_band_edges_cpu.py asserts on the oracle's dump (as FAMILIES)
+DNA_FAMILIES = {
+    "lower": _d(place="lower", ragged=(1, 1), frac=0.5),
+    "lower1": _d(place="lower", offset=1, frac=0.5),
+    "upper": _d(place="upper", frac=0.5),
+    "upper1": _d(place="upper", offset=1, ragged=(1, 1), frac=0.5),
+    "lower-out": _d(place="lower", offset=-2, ragged=(1, 0), frac=0.15),
+    "upper-out": _d(place="upper", offset=-2, ragged=(0, 1), frac=0.15),
+    "cross": _d(place="cross", cross=(0.45, 0.5), md=60, tb=30, ragged=(1, 1), frac=0.05),
+}
+for _w in (64, 65, 128, 129, 192, 193, 248, 249, 256, 257):  # each 5-state build's widest band and one cell past it
+    DNA_FAMILIES["w%d" % _w] = _d(place="upper", lX=380, lY=380, width=_w, md=150, tb=40, ragged=(_w % 2, 1),
+                                  frac=0.5)
+
+
+def dna_batch(name, n=2, seed=None, centred=False):
+    """n reads of DNA family `name` (every read at the first one's expansion) as test_dna5_gpu.run_case takes them:
+    dict(seqs=[(x, y, anchors)], e, reads)"""
+    f = DNA_FAMILIES[name]
+    seed = f["seed"] if seed is None else seed
+    e, seqs, reads = f["e"], [], []
+    for r in range(n):
+        rng = np.random.default_rng(synth.SEED0 + 500000 + seed * 1000 + r)
+        rd = dna_read(rng, f["lX"], f["lY"], None if f["width"] is not None and r == 0 else e, f["place"],
+                      f["offset"], f["every"], f["width"], f["cross"], centred)
+        e = rd["e"]
+        seqs.append((rd["x"], rd["y"], rd["anchors"]))
+        reads.append(rd)
+    return dict(seqs=seqs, e=e, reads=reads)
+
+
+def dna_edge_mass(x, y, anchors, bp, ragged=(0, 0)):
+    """edge_mass's per-diagonal cell posteriors (all five states) of one DNA pair on the oracle's dump"""
+    from harness import orc_params
+    dump = o.banded_dump(o.Sm5Model(), x, len(x), y, anchors, orc_params(bp, split=1 << 60), ragged[0], ragged[1])
+    return _cell_mass(dump)
+
+
+def _cell_mass(dump):
+    txay = np.asarray(dump["totals_xay"])
+    order = np.argsort(txay)
+    txay, tval = txay[order], np.asarray(dump["totals"])[order]
+    F, B, off = dump["F"], dump["B"], dump["offsets"]
+    seg = np.searchsorted(txay, np.arange(len(dump["L"])))
+    cell = [np.exp(F[off[d]:off[d + 1]] + B[off[d]:off[d + 1]] - tval[min(seg[d], len(tval) - 1)]).sum(axis=1)
+            for d in range(len(dump["L"]))]
+    return dict(dump=dump, cell=cell)
+
+
+# ------------------------------------ signal families for the other machines ------------------------------------
+# the general kernels' 256-thread chunking (cpecan_general.h) and their 64-lane waves: a band of exactly 256 (64)
+# k-mers and one past it, for the 4-state and echelon machines (make_batch's layout, as FAMILIES; kept apart so that the strawMan tests do not run them)
+WIDE_FAMILIES = {"w%d" % _w: _f(place="upper", lX=300, lY=450, width=_w, md=150, tb=40, ragged=(_w % 2, 1))
+                 for _w in (64, 65, 256, 257)}
+
+
+def signal_family(name):
+    return FAMILIES[name] if name in FAMILIES else WIDE_FAMILIES[name]
+
+
+def signal_batch(name, n=2, seed=None, centred=False):
+    """family_batch for a family of FAMILIES or WIDE_FAMILIES"""
+    f = signal_family(name)
+    return edge_batch(f["seed"] if seed is None else seed, n, f["lX"], f["lY"], f["place"], f["offset"],
+                      every=f["every"], e=f["e"], width=f["width"], cross=f["cross"], skip=f["skip"], centred=centred)
+
+
+def echelon_reads(batch, seed):
+    """a thin adapter for the echelon machine: a signal batch (signal_batch) as test_echelon_gpu.reads' reads, each
+    with its own machine (its scaled pore model, skip bins of its own) and event durations drawn as that test draws
+    them (the batch itself is left as it is).  The echelon machine does not follow the batch's path (its match
+    emission carries almost nothing of the event's level), so these reads give its kernel the batch's band widths, not
+    mass on the band's edge.  Returns [dict(seq, events, anchors, machine)]"""
+    import echelon_dp
+    _, _, gap_y = batch["base_model"]
+    out = []
+    for r, it in enumerate(batch["items"]):
+        rng = np.random.default_rng(synth.SEED0 + 700000 + seed * 1000 + r)
+        ev = batch["events"][it["y_offset"]: it["y_offset"] + it["lY"]].copy()
+        ev[:, 2] = rng.uniform(0.0008, 0.012, it["lY"])
+        skip = np.sort(rng.uniform(0.05, 0.4, 30))[::-1]
+        out.append(dict(seq=batch["x_chars"][it["x_offset"]: it["x_offset"] + it["lX"] + 5], events=ev,
+                        anchors=batch["anchors"][it["anchor_offset"]: it["anchor_offset"] + it["n_anchors"]],
+                        machine=echelon_dp.Machine(batch["models"][it["model"]][0], np.concatenate([skip, skip]),
+                                                   gap_y)))
+    return out
+

@@ -102,3 +102,106 @@ def test_edge_reads_far_above_the_fuzz_inputs(name):
     _, _, out = family_masses(name)
     new = np.mean([er.edge_fraction(m, "upper", 0.01, kind="cell") for _, m in out])
     assert new >= 0.5 and new > 10 * max(max(old), 0.01), (new, old)
+
+
+# the existing families and the HDP form, pinned before the generator gained the DNA and wide families
+FAMILY_DIGESTS = [("upper", "c194b2177262fed2"), ("w184", "52dcae084963502e"), ("arec120", "1b9af137ef8d3b93"),
+                  ("cross", "dc044a6c361142d1")]
+
+
+@pytest.mark.parametrize("name,digest", FAMILY_DIGESTS, ids=[n for n, _ in FAMILY_DIGESTS])
+def test_edge_family_unchanged(name, digest):
+    b = er.family_batch(name)
+    assert _digest(b["x_chars"], b["events"], b["anchors"], np.array([list(it.values()) for it in b["items"]]),
+                   *[m[0] for m in b["models"]]) == digest
+
+
+def test_edge_hdp_family_unchanged(golden_dir):
+    nhdp = o.load_nhdp(os.path.join(golden_dir, "testTemplate.nhdp"))
+    b = er.family_batch("w248", hdp=(nhdp, o.HdpModel(nhdp)))
+    assert _digest(b["x_chars"], b["events"], b["anchors"]) == "5933f77e595bd8c3" and b["e"] == 244
+
+
+def _edge_fractions(m, place):
+    places = ("lower", "upper") if place == "cross" else (place,)
+    return [er.edge_fraction(m, p, 0.01, kind="cell") for p in places]
+
+
+@pytest.mark.parametrize("name", list(er.DNA_FAMILIES))
+def test_dna_family_puts_mass_on_the_edge(name):
+    """the DNA families on the oracle's 5-state cell dump (posterior summed over the five states): the targeted edge
+    cell or the one next to it holds posterior >= 0.01 on at least the family's stated fraction of the decoded
+    diagonals (mean over the batch; both edges for 'cross'); the first read's widest band is the family's width, no
+    read's is wider"""
+    f = er.DNA_FAMILIES[name]
+    b = er.dna_batch(name)
+    bp = band_params(0.01, f["md"], f["tb"], b["e"])
+    widths = [er.widest(a, len(x), len(y), b["e"]) for x, y, a in b["seqs"]]
+    fr = np.mean([_edge_fractions(er.dna_edge_mass(x, y, a, bp, f["ragged"]), f["place"]) for x, y, a in b["seqs"]],
+                 axis=0)
+    assert np.all(fr >= f["frac"]), fr
+    if f["width"] is not None:
+        assert widths[0] == f["width"] and max(widths) == f["width"], widths
+    assert all(len(x) == f["lX"] for x, _, _ in b["seqs"])
+
+
+def test_dna_centred_batch_keeps_the_band():
+    """the stale-state cases' centred batch: the same x and anchors as the edge batch, its mass off the edge"""
+    b, c = er.dna_batch("w128"), er.dna_batch("w128", centred=True)
+    f = er.DNA_FAMILIES["w128"]
+    bp = band_params(0.01, f["md"], f["tb"], b["e"])
+    assert c["e"] == b["e"]
+    for (x, y, a), (cx, cy, ca) in zip(b["seqs"], c["seqs"]):
+        assert cx == x and np.array_equal(ca, a) and len(cy) == len(y)
+        edge = er.edge_fraction(er.dna_edge_mass(x, y, a, bp, f["ragged"]), "upper", 0.01, kind="cell")
+        mid = er.edge_fraction(er.dna_edge_mass(cx, cy, ca, bp, f["ragged"]), "upper", 0.01, kind="cell")
+        assert mid < 0.1 < edge, (mid, edge)
+
+
+# 4-state machine: (family, bar); the machine follows the strawMan path a little less closely
+SM4_FAMILIES = [("upper", 0.5), ("lower", 0.25), ("cross", 0.02), ("upper-out", 0.1), ("w256", 0.5), ("w257", 0.5)]
+
+
+@pytest.mark.parametrize("name,frac", SM4_FAMILIES, ids=[n for n, _ in SM4_FAMILIES])
+def test_sm4_family_puts_mass_on_the_edge(name, frac):
+    """as test_family_puts_mass_on_the_edge, on the oracle's 4-state cell dump (posterior summed over the four
+    states), for the families the 4-state GPU tests run"""
+    f = er.signal_family(name)
+    b = er.signal_batch(name)
+    bp = band_params(0.01, f["md"], f["tb"], b["e"])
+    p = harness.orc_params(bp, split=1 << 60)
+    fr, widths = [], []
+    for it in b["items"]:
+        m, _, gy = b["models"][it["model"]]
+        x = b["x_chars"][it["x_offset"]: it["x_offset"] + it["lX"] + 5]
+        ev = b["events"][it["y_offset"]: it["y_offset"] + it["lY"]]
+        an = b["anchors"][it["anchor_offset"]: it["anchor_offset"] + it["n_anchors"]]
+        widths.append(er.widest(an, it["lX"], it["lY"], b["e"]))
+        d = o.banded_dump(o.Sm4Model(m, gy), x, it["lX"], ev, an, p, f["ragged"][0], f["ragged"][1])
+        fr.append(_edge_fractions(er._cell_mass(d), f["place"]))
+    fr = np.mean(fr, axis=0)
+    assert np.all(fr >= frac), fr
+    if f["width"] is not None:
+        assert widths[0] == f["width"] and max(widths) == f["width"], widths
+
+
+# echelon machine: no edge families.  Its match emission carries almost nothing of the event's level (the sum of
+# emissions_signal_multipleKmerMatchProb starts at 0.0, not at log zero: log(1 + density) - log(n)), so its posterior
+# follows no path the reads are built on: at threshold 0.01 it spreads over 4-10 cells per event, a few cells inside
+# the upper edge on narrow bands and far from either edge on wide ones, whatever the path.  Its reads serve the
+# general kernel's widths only (64 and 256 k-mers and one past): every cell of those bands enters the totals.
+ECHELON_WIDTHS = ["w64", "w65", "w256", "w257"]
+
+
+@pytest.mark.parametrize("name", ECHELON_WIDTHS)
+def test_echelon_reads_have_the_family_width(name):
+    """edge_reads.echelon_reads keeps the batch's sequences, anchors and expansion: the first read's widest band is
+    the family's width, no read's is wider; the durations lie where test_echelon_gpu.reads draws them"""
+    f = er.signal_family(name)
+    b = er.signal_batch(name)
+    rds = er.echelon_reads(b, f["seed"])
+    widths = [er.widest(r["anchors"], len(r["seq"]) - 5, len(r["events"]), b["e"]) for r in rds]
+    for r in rds:
+        r["machine"].close()
+        assert np.all((r["events"][:, 2] >= 0.0008) & (r["events"][:, 2] < 0.012))
+    assert widths[0] == f["width"] and max(widths) == f["width"], widths
