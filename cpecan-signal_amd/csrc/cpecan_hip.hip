@@ -59,175 +59,29 @@ extern "C" __global__ void cpecan_k_hdp_kmer_id(const char *, long long, unsigne
                                                 unsigned long long, int, int *);
 extern "C" __global__ void cpecan_k_kmer_index(const char *, long long, unsigned short *);
 
-extern "C" int cpecan_systolic_max_width(void);
-extern "C" int cpecan_systolic_rows(void);
-extern "C" int cpecan_systolic_ring_row_doubles(void);
 extern "C" int cpecan_systolic_divtest(hipStream_t stream, long long n, unsigned long long seed,
                                        unsigned long long *bad);
-extern "C" int cpecan_systolic_state_bytes(void);
-extern "C" long long cpecan_systolic_scratch_bytes(int ringD);
-extern "C" int cpecan_systolic_launch_track(hipStream_t stream, const DevItem *items, long long nItems,
-                                            const double *track, const long long *trackBase,
-                                            const unsigned short *kidx, const double *models,
-                                            void *states, int maxLX);
-extern "C" int cpecan_systolic_launch_forward(hipStream_t stream, const DevItem *items, long long nItems,
-                                              DevParams P, const void *bandTab, const double *track,
-                                              const long long *trackBase, const double *events,
-                                              const double *models, double *Fring,
-                                              long long ringDoubles, int ringD, void *states);
-extern "C" int cpecan_systolic_launch_backward(hipStream_t stream, const DevItem *items, long long nItems,
-                                               DevParams P, const void *bandTab, const double *track,
-                                               const long long *trackBase, const double *models,
-                                               double *Fring, long long ringDoubles, int ringD,
-                                               void *states, long long *pairs, double *pairLogp,
-                                               long long *totXay, double *totVal, char *scratch,
-                                               long long scratchBytes, double *Bring, int window);
-extern "C" int cpecan_systolic_launch_expect(hipStream_t stream, const DevItem *items, long long nItems,
-                                             DevParams P, const void *bandTab, const double *track,
-                                             const long long *trackBase, const unsigned short *kidx,
-                                             const double *models, const double *Fring,
-                                             long long ringDoubles, const double *Bring, int ringD,
-                                             void *states, const char *scratch, long long scratchBytes,
-                                             double *expect, int window, long long *pairs, double *pairLogp);
-extern "C" int cpecan_systolic_bring_row_doubles(void);
-extern "C" int cpecan_systolic_launch_counts(hipStream_t stream, const void *states, long long nItems,
-                                             long long *nPairs, long long *nTot, long long *nCells);
-/* the same kernels built with fewer waves per workgroup (symbols suffixed _r1.._r3): bands up to 56, 120, 184
- * k-mers; the narrower the band, the more alignments are resident per CU */
-#define SY_DECLARE(sfx)                                                                                         \
-    extern "C" int cpecan_systolic_max_width##sfx(void);                                                          \
-    extern "C" int cpecan_systolic_ring_row_doubles##sfx(void);                                                   \
-    extern "C" int cpecan_systolic_bring_row_doubles##sfx(void);                                                  \
-    extern "C" long long cpecan_systolic_scratch_bytes##sfx(int ringD);                                           \
-    extern "C" int cpecan_systolic_launch_forward##sfx(hipStream_t, const DevItem *, long long, DevParams,        \
-                                                       const void *, const double *, const long long *,           \
-                                                       const double *, const double *, double *, long long, int, \
-                                                       void *);                                                   \
-    extern "C" int cpecan_systolic_launch_backward##sfx(hipStream_t, const DevItem *, long long, DevParams,       \
-                                                        const void *, const double *, const long long *,          \
-                                                        const double *, double *, long long, int, void *,         \
-                                                        long long *, double *, long long *, double *, char *,     \
-                                                        long long, double *, int);                                \
-    extern "C" int cpecan_systolic_launch_expect##sfx(hipStream_t, const DevItem *, long long, DevParams,         \
-                                                      const void *, const double *, const long long *,            \
-                                                      const unsigned short *, const double *, const double *,     \
-                                                      long long, const double *, int, void *, const char *,       \
-                                                      long long, double *, int, long long *, double *);
-SY_DECLARE(_r1)
-SY_DECLARE(_r2)
-SY_DECLARE(_r3)
-/* the wave-per-alignment kernels (cpecan_kernel_wave.hip), built for 1..4 cells per lane (symbols _l1.._l4) */
-#define WV_DECLARE(sfx)                                                                                         \
-    extern "C" int cpecan_wave_max_width##sfx(void);                                                              \
-    extern "C" int cpecan_wave_ring_row_doubles##sfx(void);                                                       \
-    extern "C" int cpecan_wave_bring_row_doubles##sfx(void);                                                      \
-    extern "C" long long cpecan_wave_scratch_bytes##sfx(int ringD);                                               \
-    extern "C" int cpecan_wave_launch_forward##sfx(hipStream_t, const DevItem *, long long, DevParams,            \
-                                                   const void *, const double *, const long long *,               \
-                                                   const double *, const double *, double *, long long, int,     \
-                                                   void *, int, int);                                             \
-    extern "C" int cpecan_wave_launch_backward##sfx(hipStream_t, const DevItem *, long long, DevParams,           \
-                                                    const void *, const double *, const long long *,              \
-                                                    const double *, double *, long long, int, void *,             \
-                                                    long long *, double *, long long *, double *, char *,         \
-                                                    long long, double *, int, int);                               \
-    extern "C" int cpecan_wave_launch_expect##sfx(hipStream_t, const DevItem *, long long, DevParams,             \
-                                                  const void *, const double *, const long long *,                \
-                                                  const unsigned short *, const double *, const double *,         \
-                                                  long long, const double *, int, void *, const char *,           \
-                                                  long long, double *, int, long long *, double *);
-WV_DECLARE(_l2)
-WV_DECLARE(_l3)
-WV_DECLARE(_l4)
-/* the strawMan machine's E-step with the expectations summed inside the sweep back (cpecan_kernel_wave.hip) */
-#define WV_DECLARE_FX(sfx)                                                                                        \
-    extern "C" long long cpecan_wave_fx_scratch_bytes##sfx(int ringD);                                            \
-    extern "C" int cpecan_wave_launch_backward_fx##sfx(hipStream_t, const DevItem *, long long, DevParams,        \
-                                                       const void *, const double *, const long long *,           \
-                                                       const double *, double *, long long, int, void *,          \
-                                                       long long *, double *, char *, long long, double *,        \
-                                                       const unsigned short *, int, int);
-WV_DECLARE_FX(_l2)
-WV_DECLARE_FX(_l3)
-WV_DECLARE_FX(_l4)
-/* ... and the same sweeps for the HDP signal machine (-DWV_HDP, symbols _h2.._h4) */
-WV_DECLARE(_h2)
-WV_DECLARE(_h3)
-WV_DECLARE(_h4)
-/* ... and for the vanilla signal machine (-DWV_VANILLA, symbols _v2, _v3; its four-cell build is built and linked,
- * cpecan_kernel_wave_v4.o, but not used: it does not fit the register file without spilling, and bands above 184
- * k-mers run on the general kernel) */
-WV_DECLARE(_v2)
-WV_DECLARE(_v3)
-extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const DevItem *items, long long nItems,
-                                                const double *track, const long long *trackBase,
-                                                const unsigned short *kidx, const double *models, void *states,
-                                                int maxLX);
-extern "C" int cpecan_wave_track_row_doubles_vanilla(void);
-extern "C" int cpecan_wave_launch_track_hdp(hipStream_t stream, const DevItem *items, long long nItems,
-                                            const double *track, const long long *trackBase, const int *kid,
-                                            const void *models, void *states, int maxLX);
-extern "C" int cpecan_wave_launch_track(hipStream_t stream, const DevItem *items, long long nItems,
-                                        const double *track, const long long *trackBase,
-                                        const unsigned short *kidx, const double *models, void *states, int maxLX);
-extern "C" int cpecan_wave_track_row_doubles(void);
-extern "C" int cpecan_wave_state_bytes(void);
 extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *states, long long nItems, double *mhz);
-extern "C" int cpecan_wave_launch_counts(hipStream_t stream, const void *states, long long nItems, long long *nPairs,
-                                         long long *nTot, long long *nCells);
 
-extern "C" int cpecan_wave_launch_post_asm_l3(hipStream_t stream, const DevItem *items, long long nItems, DevParams P,
-                                              const void *bandTab, const double *track, const long long *trackBase,
-                                              const double *models, double *Fring, long long ringDoubles, int ringD,
-                                              void *states, long long *pairs, double *pairLogp, long long *totXay,
-                                              double *totVal, char *scratch, long long scratchBytes, int window);
-
-struct SyBuild { /* one build of the throughput kernels */
-    int rows;  /* waves per workgroup (systolic) or cells per lane (wave) */
-    bool wave; /* one wave per alignment (cpecan_kernel_wave.hip) */
-    int (*max_width)(void);
-    int (*ring_row_doubles)(void);
-    int (*bring_row_doubles)(void);
-    long long (*scratch_bytes)(int);
-    int (*launch_forward)(hipStream_t, const DevItem *, long long, DevParams, const void *, const double *,
-                          const long long *, const double *, const double *, double *, long long, int, void *, int, int);
-    int (*launch_backward)(hipStream_t, const DevItem *, long long, DevParams, const void *, const double *,
-                           const long long *, const double *, double *, long long, int, void *, long long *, double *,
-                           long long *, double *, char *, long long, double *, int, int);
-    decltype(&cpecan_systolic_launch_expect) launch_expect;
-};
-#define SY_BUILD(r, sfx)                                                                                          \
-    { r, false, cpecan_systolic_max_width##sfx, cpecan_systolic_ring_row_doubles##sfx,                            \
-      cpecan_systolic_bring_row_doubles##sfx, cpecan_systolic_scratch_bytes##sfx,                                 \
-      [](hipStream_t st, const DevItem *it, long long n, DevParams P, const void *bt, const double *tr,           \
-         const long long *tb, const double *ev, const double *mo, double *F, long long rd, int D, void *S, int,   \
-         int) {                                                                                                   \
-          return cpecan_systolic_launch_forward##sfx(st, it, n, P, bt, tr, tb, ev, mo, F, rd, D, S);              \
-      },                                                                                                          \
-      [](hipStream_t st, const DevItem *it, long long n, DevParams P, const void *bt, const double *tr,           \
-         const long long *tb, const double *mo, double *F, long long rd, int D, void *S, long long *pa,           \
-         double *pl, long long *tx, double *tv, char *sc, long long sb, double *B, int w, int) {                  \
-          return cpecan_systolic_launch_backward##sfx(st, it, n, P, bt, tr, tb, mo, F, rd, D, S, pa, pl, tx, tv,  \
-                                                      sc, sb, B, w);                                              \
-      },                                                                                                          \
-      cpecan_systolic_launch_expect##sfx }
-#define WV_BUILD(r, sfx)                                                                                          \
-    { r, true, cpecan_wave_max_width##sfx, cpecan_wave_ring_row_doubles##sfx, cpecan_wave_bring_row_doubles##sfx, \
-      cpecan_wave_scratch_bytes##sfx, cpecan_wave_launch_forward##sfx, cpecan_wave_launch_backward##sfx,          \
-      cpecan_wave_launch_expect##sfx }
-static const SyBuild SY_BUILDS[4] = { SY_BUILD(1, _r1), SY_BUILD(2, _r2), SY_BUILD(3, _r3), SY_BUILD(4, ) };
-/* (a one-cell-per-lane build would only serve bands below 57 k-mers; the two-cell build takes those too) */
-static const SyBuild WV_BUILDS[4] = { WV_BUILD(2, _l2), WV_BUILD(2, _l2), WV_BUILD(3, _l3), WV_BUILD(4, _l4) };
-static const SyBuild HV_BUILDS[4] = { WV_BUILD(2, _h2), WV_BUILD(2, _h2), WV_BUILD(3, _h3), WV_BUILD(4, _h4) };
-static const SyBuild VV_BUILDS[4] = { WV_BUILD(2, _v2), WV_BUILD(2, _v2), WV_BUILD(3, _v3), WV_BUILD(3, _v3) };
-struct FxBuild { /* fused expectations: the extra scratch and the launch, per build of WV_BUILDS */
-    long long (*scratch_bytes)(int);
-    decltype(&cpecan_wave_launch_backward_fx_l2) launch_backward;
-};
-static const FxBuild FX_BUILDS[4] = { { cpecan_wave_fx_scratch_bytes_l2, cpecan_wave_launch_backward_fx_l2 },
-                                      { cpecan_wave_fx_scratch_bytes_l2, cpecan_wave_launch_backward_fx_l2 },
-                                      { cpecan_wave_fx_scratch_bytes_l3, cpecan_wave_launch_backward_fx_l3 },
-                                      { cpecan_wave_fx_scratch_bytes_l4, cpecan_wave_launch_backward_fx_l4 } };
+/* The builds of the throughput kernels (SweepBuild, cpecan_sweep.h), each defined next to its kernels: the workgroup
+ * family with 1..4 waves per workgroup (bands up to 56, 120, 184, 248 k-mers; the narrower the band, the more
+ * alignments are resident per CU); the wave family with 2..4 cells per lane for the strawMan (_l) and the HDP (_h)
+ * machine, 2 and 3 for the vanilla machine (_v: four cells per lane do not fit its register file without spilling, so
+ * that build does not exist and bands above 184 k-mers run on the general kernel).  A table is indexed by the rows a
+ * band of that width asks for, minus one; a one-cell-per-lane build would only serve bands below 57 k-mers, which the
+ * two-cell build takes too. */
+#define SWEEP_BUILD(name) extern "C" const SweepBuild name;
+SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
+SWEEP_BUILD(cpecan_systolic_build)
+SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(cpecan_wave_build_l4)
+SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
+SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
+typedef const SweepBuild *const SweepFamily[4];
+static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
+                                 &cpecan_systolic_build };
+static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
+static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
+static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
 /* which family a batch runs on: the wave kernels unless CPECAN_KERNELS=systolic asks for the workgroup-per-alignment ones */
 static bool use_wave_kernels() {
     const char *k = getenv("CPECAN_KERNELS");
@@ -559,8 +413,8 @@ struct cpecan_batch {
     DevBuf<double> events;
     DevBuf<double> Fstore, Bstore, dbgB;
     DevBuf<double> Bring; /* systolic Baum-Welch: backward cells of one window per item */
-    const FxBuild *fx = nullptr; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0): expectations
-                                    summed inside the sweep back, no B ring, no expectation kernel */
+    bool fused = false; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0): expectations summed
+                           inside the sweep back, no B ring, no expectation kernel */
     DevBuf<long long> pairs;
     DevBuf<double> pairLogp;
     DevBuf<long long> nPairs, totXay, nTot, nCells;
@@ -576,7 +430,7 @@ struct cpecan_batch {
     long long ringDoubles = 0;
     int ringD = 0, maxLX = 0;
     int nWorkers = 0, maxWidth = 0;
-    const SyBuild *sy = &SY_BUILDS[3]; /* systolic path: the build of the kernels the batch runs on */
+    const SweepBuild *sy = SY_BUILDS[3]; /* systolic path: the build of the kernels the batch runs on */
     int device = 0;                    /* the context's device, kept for the destructor */
     int nModels = 0;
     int expectLen = CPECAN_EXPECTATION_LEN; /* doubles per model in `expect` */
@@ -1623,9 +1477,9 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     int useKernel = dna || sm4 || echelon || ((hdp || vanilla) && !machineWave) ? CPECAN_KERNEL_GENERAL
                     : hdp || vanilla ? CPECAN_KERNEL_AUTO : kernel;
     /* the builds of the register-resident kernels this batch would run on, and the widest band they take */
-    const SyBuild *fam = hdp ? HV_BUILDS : vanilla ? VV_BUILDS
-                         : (use_wave_kernels() && !(flags & CPECAN_FLAG_WORKGROUP_KERNELS)) ? WV_BUILDS : SY_BUILDS;
-    const int famMaxWidth = fam[3].max_width();
+    const SweepFamily &fam = hdp ? HV_BUILDS : vanilla ? VV_BUILDS
+                             : (use_wave_kernels() && !(flags & CPECAN_FLAG_WORKGROUP_KERNELS)) ? WV_BUILDS : SY_BUILDS;
+    const int famMaxWidth = fam[3]->maxWidth;
     b->dna = dna;
     b->vanilla = vanilla;
     b->hdp = hdp;
@@ -1654,10 +1508,9 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
         const char *rows = getenv("CPECAN_SYSTOLIC_ROWS");
         int r = rows ? atoi(rows) : 1;
         r = r < 1 ? 1 : r > 4 ? 4 : r;
-        while (r < 4 && globalMaxWidth > fam[r - 1].max_width()) r++;
-        b->sy = &fam[r - 1];
-        b->trackRow = vanilla ? cpecan_wave_track_row_doubles_vanilla()
-                      : b->sy->wave ? cpecan_wave_track_row_doubles() : CP_ROW;
+        while (r < 4 && globalMaxWidth > fam[r - 1]->maxWidth) r++;
+        b->sy = fam[r - 1];
+        b->trackRow = b->sy->once->trackRowDoubles;
     }
     b->hItems = hItems;
 
@@ -1759,7 +1612,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
                                 : asmLikely && maxWindows > 2 && !(flags & CPECAN_FLAG_SMALL_FOOTPRINT) ? 3 : 2;
         while (b->ringD < (ringWindows > 1 ? ringWindows * maxSpan + 8 : maxSpan + 4)) b->ringD *= 2;
         /* the wave kernels keep one more row behind the ring: the -inf row lanes without a cell read */
-        b->ringDoubles = (long long) (b->ringD + (b->sy->wave ? 1 : 0)) * b->sy->ring_row_doubles();
+        b->ringDoubles = (long long) (b->ringD + (b->sy->wave ? 1 : 0)) * b->sy->ringRowDoubles;
         if (getenv("CPECAN_RING_PAD")) b->ringDoubles += atoll(getenv("CPECAN_RING_PAD"));
         b->maxLX = maxLX;
         B_TRY(b->Fstore.alloc((size_t) nItems * (size_t) b->ringDoubles));
@@ -1798,16 +1651,15 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
          * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 (read per
          * batch) keeps the ring of backward cells and the expectation kernel */
         const char *fxEnv = getenv("CPECAN_EXPECT_FUSED");
-        if (mode == CPECAN_MODE_EXPECTATIONS && !(fxEnv != nullptr && atoi(fxEnv) == 0) && b->sy >= WV_BUILDS &&
-            b->sy < WV_BUILDS + 4 && !dna && !sm4 && !vanilla && !hdp) {
-            b->fx = &FX_BUILDS[b->sy - WV_BUILDS];
+        if (mode == CPECAN_MODE_EXPECTATIONS && !(fxEnv != nullptr && atoi(fxEnv) == 0) && b->sy->backward_fx) {
+            b->fused = true;
             b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr ? atoi(getenv("CPECAN_EXPECT_RESWEEP")) : 0;
         }
-        if (mode == CPECAN_MODE_EXPECTATIONS && !b->fx)
-            B_TRY(b->Bring.alloc((size_t) nItems * (size_t) b->ringD * (size_t) b->sy->bring_row_doubles()));
-        b->stateBytes = b->sy->wave ? cpecan_wave_state_bytes() : cpecan_systolic_state_bytes();
+        if (mode == CPECAN_MODE_EXPECTATIONS && !b->fused)
+            B_TRY(b->Bring.alloc((size_t) nItems * (size_t) b->ringD * (size_t) b->sy->bringRowDoubles));
+        b->stateBytes = b->sy->once->stateBytes;
         B_TRY(b->syStates.alloc((size_t) nItems * (size_t) b->stateBytes));
-        b->scratchBytes = (b->sy->scratch_bytes(b->ringD) + (b->fx ? b->fx->scratch_bytes(b->ringD) : 0) + 63) / 64 * 64;
+        b->scratchBytes = (b->sy->scratch_bytes(b->ringD) + (b->fused ? b->sy->fx_scratch_bytes(b->ringD) : 0) + 63) / 64 * 64;
         B_TRY(b->syScratch.alloc((size_t) nItems * (size_t) b->scratchBytes));
         B_TRY(b->track.alloc((size_t) trackTotal * (size_t) b->trackRow));
         B_TRY(b->trackBase.alloc((size_t) nItems));
@@ -1819,7 +1671,7 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
          * per lane and fit their staging scheme (CPECAN_ASM=0: the compiled kernels, for tests and timing) */
         const bool asmOff = getenv("CPECAN_ASM") != nullptr && atoi(getenv("CPECAN_ASM")) == 0; /* (read per batch) */
         if (wantPlan && !asmOff && b->sy->wave && b->sy->rows == ASM_L && globalMaxWidth <= ASM_MAX_WIDTH && b->nGroups == 1 &&
-            b->stateBytes == (int) sizeof(WvState) && b->sy->ring_row_doubles() * 8 == ASM_ROW_BYTES /* (one ring format) */ &&
+            b->stateBytes == (int) sizeof(WvState) && b->sy->ringRowDoubles * 8 == ASM_ROW_BYTES /* (one ring format) */ &&
             cpecan_asm_load(c->device) == 0) {
             b->asmMaxWindows = std::max(maxWindows, 1);
             PinnedBuf<AsmPlanWin> hWin;
@@ -1965,10 +1817,224 @@ int cpecan_hip_batch_create_echelon(cpecan_ctx *c, const cpecan_item *items, int
 
 } // extern "C"
 
+/* The 5-state machine for bands a wave covers in one to three cells per lane: one wave per alignment, the recurrence in
+ * registers (cpecan_kernel_wave5.hip), posterior decode or expectations */
+static int enqueue_wave5(cpecan_batch *b, hipStream_t st) {
+    cpecan_ctx *c = b->ctx;
+    const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
+    /* a batch that leaves SIMDs with fewer than two waves runs the sweeps of an alignment on a pair of waves
+     * (forward and back overlapping); CPECAN_WAVE5_PAIRED=0/1 forces either form (tests, timing) */
+    const char *pairedEnv = getenv("CPECAN_WAVE5_PAIRED");
+    const int l5 = b->maxWidth <= 64 ? 0 : b->maxWidth <= 128 ? 1 : 2;
+    /* (the one-wave E-step at three cells per lane needs more registers than two waves of a SIMD can have) */
+    const bool paired = pairedEnv ? atoi(pairedEnv) != 0 : (b->nItems < CP_WAVE5_PAIRED_BELOW || (em && l5 == 2));
+    static const auto kernels5 = std::array<decltype(&cpecan_k_wave5_l1), 12>{
+        cpecan_k_wave5_l1, cpecan_k_wave5_l2, cpecan_k_wave5_l3, cpecan_k_wave5e_l1, cpecan_k_wave5e_l2, cpecan_k_wave5e_l3,
+        cpecan_k_wave5p_l1, cpecan_k_wave5p_l2, cpecan_k_wave5p_l3, cpecan_k_wave5pe_l1, cpecan_k_wave5pe_l2, cpecan_k_wave5pe_l3 };
+    auto kernel5 = kernels5[(size_t) ((paired ? 6 : 0) + (em ? 3 : 0) + l5)];
+    hipLaunchKernelGGL(kernel5, dim3((unsigned) b->nItems), dim3(paired ? 128 : 64), 0, st, (const DevItem *) b->items.p, b->P,
+                       (const int *) b->bandL.p, (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
+                       (const char *) b->chars.p, (const char *) b->charsY.p, (const double *) c->models5.p,
+                       b->Fstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
+                       em ? b->expect.p : nullptr);
+    HIP_TRY(hipGetLastError());
+    return CPECAN_OK;
+}
+
+/* The general kernels (cpecan_general.h): one per machine, one parameter list */
+static int enqueue_general(cpecan_batch *b, hipStream_t st) {
+    cpecan_ctx *c = b->ctx;
+    if (b->echelon) { /* (cpecan_kernel_generale.hip) */
+        DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
+                             (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p,
+                             (const double *) b->logNoise.p, c->modelsE.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
+                             b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p, nullptr, nullptr };
+        DevEchelonArgs e = { (const char *) b->chars.p, (const long long *) b->xEnd.p, (const double *) b->duration.p };
+        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, st, a, b->P, e);
+        HIP_TRY(hipGetLastError());
+        return CPECAN_OK;
+    }
+    const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
+    DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
+                         (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p, nullptr, c->models.p,
+                         b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p,
+                         b->nTot.p, nullptr, em ? b->expect.p : nullptr };
+    DevParams P = b->P;
+    size_t lds = 0;
+    auto kernel = cpecan_k_general;
+    if (b->dna) {
+        /* the forward sweep's two previous diagonals live in LDS where the widest band fits (3 diagonals of 5
+         * states: 120 bytes per cell of width); CPECAN_GENERAL_LDS=0 keeps them in HBM (timing, tests) */
+        static const bool ldsOff = getenv("CPECAN_GENERAL_LDS") != nullptr && atoi(getenv("CPECAN_GENERAL_LDS")) == 0;
+        P.ldsWidth = (!ldsOff && b->maxWidth <= 248) ? b->maxWidth : 0;
+        lds = (size_t) P.ldsWidth * 120;
+        kernel = cpecan_k_general5;
+        a.x = b->chars.p;
+        a.y = b->charsY.p;
+        a.models = c->models5.p;
+    } else if (b->hdp && b->kernel == CPECAN_KERNEL_GENERAL) {
+        kernel = cpecan_k_generalh;
+        a.x = b->kid.p;
+        a.models = c->modelsH.p;
+    } else if (b->sm4) {
+        kernel = cpecan_k_general4;
+        a.models = c->models4.p;
+    } else if (b->vanilla && b->kernel == CPECAN_KERNEL_GENERAL) {
+        kernel = cpecan_k_generalv;
+        a.yAux = (const double *) b->logNoise.p;
+        a.models = c->modelsV.p;
+    } else {
+        a.dbgB = b->dbgB.p;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned) b->nItems), dim3(256), lds, st, a, P);
+    HIP_TRY(hipGetLastError());
+    return CPECAN_OK;
+}
+
+/* The throughput kernels, one pass: the per-item track of emission constants (a function of the inputs, rebuilt every
+ * run inside the timed region), then for every traceback window the forward kernel and the backward kernel.  The wave
+ * kernels run the two on streams of their own: the sweep back of window w overlaps the forward sweep of window w+1 of the
+ * same alignments (each SIMD then holds a forward and a backward wave), and forward w+2, which re-uses window w's ring
+ * rows, waits for the sweep back of w.  Events around every kernel give per-kernel times and carry the dependencies.
+ * *sEnd: the stream the run ends on (the post lane where it went over the three lanes: *laneRun). */
+static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *laneRun) {
+    cpecan_ctx *c = b->ctx;
+    const SweepBuild *sy = b->sy;
+    const int G = b->nGroups, perGroup = 4 * b->nWindows + 1;
+    if (b->evStage.size() != (size_t) (G * perGroup)) {
+        for (hipEvent_t e : b->evStage) (void) hipEventDestroy(e);
+        b->evStage.assign((size_t) (G * perGroup), nullptr);
+        for (auto &e : b->evStage) HIP_TRY(hipEventCreate(&e));
+    }
+    SweepArgs all{};
+    all.items = b->items.p; all.nItems = b->nItems; all.P = b->P; all.bandTab = (const int2 *) b->bandTab.p;
+    all.track = b->track.p; all.trackBase = b->trackBase.p; all.maxLX = b->maxLX; all.events = b->events.p;
+    all.kidx = b->kidx.p; all.kid = b->kid.p; all.Fring = b->Fstore.p; all.ringDoubles = b->ringDoubles;
+    all.ringD = b->ringD; all.states = b->syStates.p; all.stateBytes = b->stateBytes; all.pairs = b->pairs.p;
+    all.pairLogp = b->pairLogp.p; all.totXay = b->totXay.p; all.totVal = b->totVal.p; all.scratch = b->syScratch.p;
+    all.scratchBytes = b->scratchBytes; all.Bring = b->Bring.p; all.bringRow = sy->bringRowDoubles;
+    all.expect = b->expect.p; all.nPairs = b->nPairs.p; all.nTot = b->nTot.p; all.nCells = b->nCells.p;
+    /* the models as the sweeps read them, and whether any of them lets gap Y switch to gap X (the nanopore default
+     * does not, stateMachine.c:1287: the kernels then run the build without that term; the vanilla machine has no such
+     * transition) */
+    all.models = sy->machine == SWEEP_HDP ? (const double *) c->modelsH.p : sy->machine == SWEEP_VANILLA ? c->modelsV.p : c->models.p;
+    if (sy->machine == SWEEP_HDP) {
+        for (const DevHdpModel &m : c->hostModelsH)
+            if (m.t[T_GAP_SWITCH_TO_X] > -INFINITY) all.withSwitch = 1;
+    } else if (sy->machine == SWEEP_STRAWMAN) {
+        for (int m = 0; m < c->nModels; m++)
+            if (c->switchToX[(size_t) m] > -INFINITY) all.withSwitch = 1;
+    }
+    int rc = sy->once->launch_track(L->fwd, all);
+    /* the assembly sweeps (no model of the batch may let gap Y switch to gap X: they have no such term) */
+    const bool asmRun = b->useAsm && !all.withSwitch && rc == 0;
+    AsmArgs asmArgs{};
+    if (asmRun) {
+        asmArgs.items = b->items.p; asmArgs.trackBase = b->trackBase.p; asmArgs.planWin = b->planWin.p;
+        asmArgs.planCtl = b->planCtl.p; asmArgs.planOff = b->planOff.p; asmArgs.events = b->events.p;
+        asmArgs.models = c->models.p; asmArgs.track = b->track.p; asmArgs.ring = b->Fstore.p;
+        asmArgs.ringDoubles = b->ringDoubles; asmArgs.states = b->syStates.p; asmArgs.ctx = b->asmCtx.p;
+        asmArgs.ctxBytes = ASM_CTX_BYTES; asmArgs.coef = cpecan_asm_coef(c->device); asmArgs.nItems = (int) b->nItems;
+        asmArgs.ringD = b->ringD; asmArgs.maxWindows = b->asmMaxWindows; asmArgs.scratch = b->syScratch.p;
+        asmArgs.scratchBytes = b->scratchBytes; asmArgs.logThrSlack = b->P.logThrSlack; asmArgs.modelStride = CP_MODEL_STRIDE;
+        asmArgs.maskTab = b->asmMasks.p;
+        rc = cpecan_asm_launch_begin(L->fwd, b->items.p, b->nItems, b->Fstore.p, b->ringDoubles);
+        if (getenv("CPECAN_ASM_TRACE")) {
+            auto span = [](const char *what, const void *p, size_t bytes) {
+                fprintf(stderr, "[cpecan asm]   %-10s %p .. %p (%zu bytes)\n", what, p, (const char *) p + bytes, bytes);
+            };
+            span("items", b->items.p, b->items.n * sizeof(DevItem));
+            span("trackBase", b->trackBase.p, b->trackBase.n * 8);
+            span("planWin", b->planWin.p, b->planWin.n * sizeof(AsmPlanWin));
+            span("planCtl", b->planCtl.p, b->planCtl.n * sizeof(AsmPlanCtl));
+            span("planOff", b->planOff.p, b->planOff.n * 8);
+            span("events", b->events.p, b->events.n * 8);
+            span("models", c->models.p, c->models.n * 8);
+            span("track", b->track.p, b->track.n * 8);
+            span("ring", b->Fstore.p, b->Fstore.n * 8);
+            span("states", b->syStates.p, b->syStates.n);
+            span("ctx", b->asmCtx.p, b->asmCtx.n);
+            span("scratch", b->syScratch.p, b->syScratch.n);
+            span("masks", b->asmMasks.p, b->asmMasks.n * 4);
+            span("coef", asmArgs.coef, 512);
+            fprintf(stderr, "[cpecan asm]   ringD %d ringDoubles %lld windows %d scratchBytes %lld\n", b->ringD, b->ringDoubles,
+                    b->asmMaxWindows, b->scratchBytes);
+        }
+    }
+    HIP_TRY(hipEventRecord(b->evFork, L->fwd));
+    *laneRun = !b->gStreamOwned;
+    if (*laneRun && (!L->back || !L->post)) return fail(CPECAN_EHIP, "lane set without its sweep lanes");
+    if (*laneRun) *sEnd = L->post;
+#ifdef CPECAN_TIMING_BUILD
+    static const bool fwdOnly = getenv("CPECAN_TIMING_FORWARD_ONLY") != nullptr; /* timing study: wrong results */
+    static const bool noPost = getenv("CPECAN_TIMING_NO_POST") != nullptr;       /* timing study: sweeps only */
+#else
+    const bool fwdOnly = false, noPost = false;
+#endif
+    const long long per = (b->nItems + G - 1) / G;
+    for (int gi = 0; gi < G && rc == 0; gi++) {
+        const long long i0 = gi * per, n = std::min<long long>(per, b->nItems - i0);
+        SweepArgs a = all.slice(i0, n);
+        hipStream_t sF = *laneRun ? L->fwd : b->gStream[(size_t) gi];
+        hipStream_t sB = *laneRun ? L->back : sy->wave ? b->gStreamB[(size_t) gi] : sF;
+#ifdef CPECAN_TIMING_BUILD
+        if (getenv("CPECAN_TIMING_SERIAL")) sB = sF; /* timing study: every sweep alone on the chip */
+#endif
+        hipEvent_t *ev = b->evStage.data() + (size_t) gi * perGroup;
+        HIP_TRY(hipStreamWaitEvent(sF, b->evFork, 0));
+        if (sB != sF) HIP_TRY(hipStreamWaitEvent(sB, b->evFork, 0));
+        HIP_TRY(hipEventRecord(ev[0], sF));
+        for (int w = 0; w < b->nWindows && rc == 0; w++) {
+            hipEvent_t *e4 = ev + 1 + 4 * w;
+            /* assembly sweeps: the window's totals and decode (and the re-sweep of what cannot be trusted) run on a
+             * stream of their own.  The sweep back of the next window does not wait for them (it fills the other
+             * half of the scratch), nor does the forward sweep of window w+2 (the ring holds three windows, the
+             * state four window records); what does: the sweep back of w+2 (scratch), the forward sweep of w+3
+             * (ring rows, window record).  The forward sweep of w+2 still waits for the sweep back of w, which reads
+             * the context that sweep will overwrite when it ends. */
+            const bool postAside = asmRun && b->asmBackward && sB != sF && b->postAside && *laneRun;
+            if (postAside) a.scratch = b->syScratch.p + (size_t) (w & 1) * (size_t) b->nItems * (size_t) b->scratchBytes;
+            if (sB != sF && w >= 2) HIP_TRY(hipStreamWaitEvent(sF, ev[1 + 4 * (w - 2) + 3], 0));
+            if (postAside && w >= 3) HIP_TRY(hipStreamWaitEvent(sF, b->evPost[(size_t) w - 3], 0));
+            HIP_TRY(hipEventRecord(e4[0], sF));
+            if (n > 0 && asmRun) {
+                asmArgs.window = w;
+                rc = cpecan_asm_launch_forward(c->device, sF, &asmArgs);
+            } else if (n > 0)
+                rc = sy->forward(sF, a, w);
+            HIP_TRY(hipEventRecord(e4[1], sF));
+            if (sB != sF) HIP_TRY(hipStreamWaitEvent(sB, e4[1], 0));
+            HIP_TRY(hipEventRecord(e4[2], sB));
+            if (rc == 0 && n > 0 && asmRun && b->asmBackward && !fwdOnly) {
+                asmArgs.window = w;
+                asmArgs.scratch = a.scratch;
+                if (postAside && w >= 2) HIP_TRY(hipStreamWaitEvent(sB, b->evPost[(size_t) w - 2], 0));
+                rc = cpecan_asm_launch_backward(c->device, sB, &asmArgs);
+                hipStream_t sP = postAside ? L->post : sB;
+                if (postAside) {
+                    HIP_TRY(hipEventRecord(e4[3], sB));
+                    HIP_TRY(hipStreamWaitEvent(sP, e4[3], 0));
+                }
+                if (rc == 0 && !noPost) rc = sy->post_asm(sP, a, w);
+                if (postAside) HIP_TRY(hipEventRecord(b->evPost[(size_t) w], sP));
+            } else if (rc == 0 && n > 0 && !fwdOnly)
+                rc = (b->fused ? sy->backward_fx : sy->backward)(sB, a, w);
+            if (rc == 0 && n > 0 && b->mode == CPECAN_MODE_EXPECTATIONS && !b->fused) rc = sy->expect(sB, a, w);
+            if (!postAside) HIP_TRY(hipEventRecord(e4[3], sB));
+        }
+        /* the last sweep back follows every forward sweep; the run ends behind it on the post lane (after the last
+         * post kernel there), which leaves the forward lane to the next run's first forward sweep */
+        HIP_TRY(hipEventRecord(b->evJoin[(size_t) gi], sB));
+        HIP_TRY(hipStreamWaitEvent(*sEnd, b->evJoin[(size_t) gi], 0));
+    }
+    if (rc == 0) rc = sy->once->launch_counts(*sEnd, all);
+    if (rc != 0) return fail(CPECAN_EHIP, "throughput kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return CPECAN_OK;
+}
+
 /* One run of the batch, queued on the lane set L (its mutex held).  A wave batch of one stream group runs over the
  * three lanes and ends on the post lane; every other batch runs on the forward lane (and streams of its own). */
 static int batch_enqueue(cpecan_batch *b, cpecan_batch *after, LaneSet *L) {
-    cpecan_ctx *c = b->ctx;
     /* its own last run first, wherever it went (the ring, state and scratch are the batch's); then the batch it follows,
      * unless stream order on the lanes already puts this run behind it */
     if (b->ran) HIP_TRY(hipStreamWaitEvent(L->fwd, b->ev2, 0));
@@ -1976,249 +2042,19 @@ static int batch_enqueue(cpecan_batch *b, cpecan_batch *after, LaneSet *L) {
     hipStream_t sEnd = L->fwd; /* where the run ends: counts, packing, ev2 */
     bool laneRun = false;
     b->countsValid = false;
+    int rc;
     HIP_TRY(hipEventRecord(b->ev0, L->fwd));
     if (b->mode == CPECAN_MODE_EXPECTATIONS)
         HIP_TRY(hipMemsetAsync(b->expect.p, 0, b->expect.n * sizeof(double), L->fwd));
     HIP_TRY(hipEventRecord(b->ev1, L->fwd));
     static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr; /* (tests, timing: the general kernel) */
-    if (b->dna && !b->P.debug && !b->P.unbanded && b->maxWidth <= 192 && !wave5Off && !(b->flags & CPECAN_FLAG_GENERAL_KERNEL)) {
-        /* the 5-state machine for bands a wave covers in one to three cells per lane: one wave per alignment, the
-         * recurrence in registers (cpecan_kernel_wave5.hip), posterior decode or expectations */
-        const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
-        /* a batch that leaves SIMDs with fewer than two waves runs the sweeps of an alignment on a pair of waves
-         * (forward and back overlapping); CPECAN_WAVE5_PAIRED=0/1 forces either form (tests, timing) */
-        const char *pairedEnv = getenv("CPECAN_WAVE5_PAIRED");
-        const int l5 = b->maxWidth <= 64 ? 0 : b->maxWidth <= 128 ? 1 : 2;
-        /* (the one-wave E-step at three cells per lane needs more registers than two waves of a SIMD can have) */
-        const bool paired = pairedEnv ? atoi(pairedEnv) != 0 : (b->nItems < CP_WAVE5_PAIRED_BELOW || (em && l5 == 2));
-        static const auto kernels5 = std::array<decltype(&cpecan_k_wave5_l1), 12>{
-            cpecan_k_wave5_l1, cpecan_k_wave5_l2, cpecan_k_wave5_l3, cpecan_k_wave5e_l1, cpecan_k_wave5e_l2, cpecan_k_wave5e_l3,
-            cpecan_k_wave5p_l1, cpecan_k_wave5p_l2, cpecan_k_wave5p_l3, cpecan_k_wave5pe_l1, cpecan_k_wave5pe_l2, cpecan_k_wave5pe_l3 };
-        auto kernel5 = kernels5[(size_t) ((paired ? 6 : 0) + (em ? 3 : 0) + l5)];
-        hipLaunchKernelGGL(kernel5, dim3((unsigned) b->nItems), dim3(paired ? 128 : 64), 0, L->fwd, (const DevItem *) b->items.p, b->P,
-                           (const int *) b->bandL.p, (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
-                           (const char *) b->chars.p, (const char *) b->charsY.p, (const double *) c->models5.p,
-                           b->Fstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
-                           em ? b->expect.p : nullptr);
-        HIP_TRY(hipGetLastError());
-    } else if (b->echelon) {
-        /* the echelon machine on the general driver (cpecan_kernel_generale.hip) */
-        DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
-                             (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p,
-                             (const double *) b->logNoise.p, c->modelsE.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
-                             b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p, nullptr, nullptr };
-        DevEchelonArgs e = { (const char *) b->chars.p, (const long long *) b->xEnd.p, (const double *) b->duration.p };
-        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, L->fwd, a, b->P, e);
-        HIP_TRY(hipGetLastError());
-    } else if (b->dna || b->sm4 || b->kernel == CPECAN_KERNEL_GENERAL) {
-        /* the general kernels (cpecan_general.h): one per machine, one parameter list */
-        const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
-        DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
-                             (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p, nullptr, c->models.p,
-                             b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p,
-                             b->nTot.p, nullptr, em ? b->expect.p : nullptr };
-        DevParams P = b->P;
-        size_t lds = 0;
-        auto kernel = cpecan_k_general;
-        if (b->dna) {
-            /* the forward sweep's two previous diagonals live in LDS where the widest band fits (3 diagonals of 5
-             * states: 120 bytes per cell of width); CPECAN_GENERAL_LDS=0 keeps them in HBM (timing, tests) */
-            static const bool ldsOff = getenv("CPECAN_GENERAL_LDS") != nullptr && atoi(getenv("CPECAN_GENERAL_LDS")) == 0;
-            P.ldsWidth = (!ldsOff && b->maxWidth <= 248) ? b->maxWidth : 0;
-            lds = (size_t) P.ldsWidth * 120;
-            kernel = cpecan_k_general5;
-            a.x = b->chars.p;
-            a.y = b->charsY.p;
-            a.models = c->models5.p;
-        } else if (b->hdp && b->kernel == CPECAN_KERNEL_GENERAL) {
-            kernel = cpecan_k_generalh;
-            a.x = b->kid.p;
-            a.models = c->modelsH.p;
-        } else if (b->sm4) {
-            kernel = cpecan_k_general4;
-            a.models = c->models4.p;
-        } else if (b->vanilla && b->kernel == CPECAN_KERNEL_GENERAL) {
-            kernel = cpecan_k_generalv;
-            a.yAux = (const double *) b->logNoise.p;
-            a.models = c->modelsV.p;
-        } else {
-            a.dbgB = b->dbgB.p;
-        }
-        hipLaunchKernelGGL(kernel, dim3((unsigned) b->nItems), dim3(256), lds, L->fwd, a, P);
-        HIP_TRY(hipGetLastError());
-    } else {
-        /* one pass: the per-item track of emission constants (a function of the inputs, rebuilt every run inside the
-         * timed region), then for every traceback window the forward kernel and the backward kernel.  The wave
-         * kernels run the two on streams of their own: the sweep back of window w overlaps the forward sweep of
-         * window w+1 of the same alignments (each SIMD then holds a forward and a backward wave), and forward w+2,
-         * which re-uses window w's ring rows, waits for the sweep back of w.  Events around every kernel give
-         * per-kernel times and carry the dependencies. */
-        const int G = b->nGroups, perGroup = 4 * b->nWindows + 1;
-        if (b->evStage.size() != (size_t) (G * perGroup)) {
-            for (hipEvent_t e : b->evStage) (void) hipEventDestroy(e);
-            b->evStage.assign((size_t) (G * perGroup), nullptr);
-            for (auto &e : b->evStage) HIP_TRY(hipEventCreate(&e));
-        }
-        /* does any model let gap Y switch to gap X?  (the nanopore default does not, stateMachine.c:1287: the
-         * kernels then run the build without that term) */
-        int withSwitch = 0;
-        int rc;
-        /* the models as the sweeps read them: strawMan tables, or the HDP records of an HDP batch */
-        const double *models = b->hdp ? (const double *) c->modelsH.p : b->vanilla ? c->modelsV.p : c->models.p;
-        if (b->vanilla) { /* (no gap Y -> gap X transition in this machine) */
-            rc = cpecan_wave_launch_track_vanilla(L->fwd, b->items.p, b->nItems, b->track.p, b->trackBase.p,
-                                                  b->kidx.p, c->modelsV.p, b->syStates.p, b->maxLX);
-        } else if (b->hdp) {
-            for (const DevHdpModel &m : c->hostModelsH)
-                if (m.t[T_GAP_SWITCH_TO_X] > -INFINITY) withSwitch = 1;
-            rc = cpecan_wave_launch_track_hdp(L->fwd, b->items.p, b->nItems, b->track.p, b->trackBase.p, b->kid.p,
-                                              c->modelsH.p, b->syStates.p, b->maxLX);
-        } else {
-            for (int m = 0; m < c->nModels; m++)
-                if (c->switchToX[(size_t) m] > -INFINITY) withSwitch = 1;
-            rc = (b->sy->wave ? cpecan_wave_launch_track : cpecan_systolic_launch_track)(
-                L->fwd, b->items.p, b->nItems, b->track.p, b->trackBase.p, b->kidx.p, c->models.p, b->syStates.p,
-                b->maxLX);
-        }
-        /* the assembly sweeps (no model of the batch may let gap Y switch to gap X: they have no such term) */
-        const bool asmRun = b->useAsm && !withSwitch && rc == 0;
-        AsmArgs asmArgs{};
-        if (asmRun) {
-            asmArgs.items = b->items.p; asmArgs.trackBase = b->trackBase.p; asmArgs.planWin = b->planWin.p;
-            asmArgs.planCtl = b->planCtl.p; asmArgs.planOff = b->planOff.p; asmArgs.events = b->events.p;
-            asmArgs.models = c->models.p; asmArgs.track = b->track.p; asmArgs.ring = b->Fstore.p;
-            asmArgs.ringDoubles = b->ringDoubles; asmArgs.states = b->syStates.p; asmArgs.ctx = b->asmCtx.p;
-            asmArgs.ctxBytes = ASM_CTX_BYTES; asmArgs.coef = cpecan_asm_coef(c->device); asmArgs.nItems = (int) b->nItems;
-            asmArgs.ringD = b->ringD; asmArgs.maxWindows = b->asmMaxWindows; asmArgs.scratch = b->syScratch.p;
-            asmArgs.scratchBytes = b->scratchBytes; asmArgs.logThrSlack = b->P.logThrSlack; asmArgs.modelStride = CP_MODEL_STRIDE;
-            asmArgs.maskTab = b->asmMasks.p;
-            rc = cpecan_asm_launch_begin(L->fwd, b->items.p, b->nItems, b->Fstore.p, b->ringDoubles);
-            if (getenv("CPECAN_ASM_TRACE")) {
-                auto span = [](const char *what, const void *p, size_t bytes) {
-                    fprintf(stderr, "[cpecan asm]   %-10s %p .. %p (%zu bytes)\n", what, p, (const char *) p + bytes, bytes);
-                };
-                span("items", b->items.p, b->items.n * sizeof(DevItem));
-                span("trackBase", b->trackBase.p, b->trackBase.n * 8);
-                span("planWin", b->planWin.p, b->planWin.n * sizeof(AsmPlanWin));
-                span("planCtl", b->planCtl.p, b->planCtl.n * sizeof(AsmPlanCtl));
-                span("planOff", b->planOff.p, b->planOff.n * 8);
-                span("events", b->events.p, b->events.n * 8);
-                span("models", c->models.p, c->models.n * 8);
-                span("track", b->track.p, b->track.n * 8);
-                span("ring", b->Fstore.p, b->Fstore.n * 8);
-                span("states", b->syStates.p, b->syStates.n);
-                span("ctx", b->asmCtx.p, b->asmCtx.n);
-                span("scratch", b->syScratch.p, b->syScratch.n);
-                span("masks", b->asmMasks.p, b->asmMasks.n * 4);
-                span("coef", asmArgs.coef, 512);
-                fprintf(stderr, "[cpecan asm]   ringD %d ringDoubles %lld windows %d scratchBytes %lld\n", b->ringD, b->ringDoubles,
-                        b->asmMaxWindows, b->scratchBytes);
-            }
-        }
-        HIP_TRY(hipEventRecord(b->evFork, L->fwd));
-        laneRun = !b->gStreamOwned;
-        if (laneRun && (!L->back || !L->post)) return fail(CPECAN_EHIP, "lane set without its sweep lanes");
-        if (laneRun) sEnd = L->post;
-        const long long per = (b->nItems + G - 1) / G;
-        for (int gi = 0; gi < G && rc == 0; gi++) {
-            const long long i0 = gi * per, n = std::min<long long>(per, b->nItems - i0);
-            hipStream_t sF = laneRun ? L->fwd : b->gStream[(size_t) gi];
-            hipStream_t sB = laneRun ? L->back : b->sy->wave ? b->gStreamB[(size_t) gi] : sF;
-#ifdef CPECAN_TIMING_BUILD
-            if (getenv("CPECAN_TIMING_SERIAL")) sB = sF; /* timing study: every sweep alone on the chip */
-#endif
-            hipEvent_t *ev = b->evStage.data() + (size_t) gi * perGroup;
-            HIP_TRY(hipStreamWaitEvent(sF, b->evFork, 0));
-            if (sB != sF) HIP_TRY(hipStreamWaitEvent(sB, b->evFork, 0));
-            HIP_TRY(hipEventRecord(ev[0], sF));
-            const long long bringRow = b->sy->bring_row_doubles();
-            for (int w = 0; w < b->nWindows && rc == 0; w++) {
-                hipEvent_t *e4 = ev + 1 + 4 * w;
-                /* assembly sweeps: the window's totals and decode (and the re-sweep of what cannot be trusted) run on a
-                 * stream of their own.  The sweep back of the next window does not wait for them (it fills the other
-                 * half of the scratch), nor does the forward sweep of window w+2 (the ring holds three windows, the
-                 * state four window records); what does: the sweep back of w+2 (scratch), the forward sweep of w+3
-                 * (ring rows, window record).  The forward sweep of w+2 still waits for the sweep back of w, which reads
-                 * the context that sweep will overwrite when it ends. */
-                const bool postAside = asmRun && b->asmBackward && sB != sF && b->postAside && laneRun;
-                char *scratchW = b->syScratch.p + (postAside ? (size_t) (w & 1) * (size_t) b->nItems * (size_t) b->scratchBytes : 0);
-                if (sB != sF && w >= 2) HIP_TRY(hipStreamWaitEvent(sF, ev[1 + 4 * (w - 2) + 3], 0));
-                if (postAside && w >= 3) HIP_TRY(hipStreamWaitEvent(sF, b->evPost[(size_t) w - 3], 0));
-                HIP_TRY(hipEventRecord(e4[0], sF));
-                /* the kernels index everything per alignment by blockIdx: shift the bases */
-                if (n > 0 && asmRun) {
-                    asmArgs.window = w;
-                    rc = cpecan_asm_launch_forward(c->device, sF, &asmArgs);
-                } else if (n > 0)
-                    rc = b->sy->launch_forward(sF, b->items.p + i0, n, b->P, b->bandTab.p, b->track.p,
-                                               b->trackBase.p + i0, b->events.p, models,
-                                               b->Fstore.p + i0 * b->ringDoubles, b->ringDoubles, b->ringD,
-                                               b->syStates.p + i0 * b->stateBytes, w, withSwitch);
-                HIP_TRY(hipEventRecord(e4[1], sF));
-                if (sB != sF) HIP_TRY(hipStreamWaitEvent(sB, e4[1], 0));
-                HIP_TRY(hipEventRecord(e4[2], sB));
-#ifdef CPECAN_TIMING_BUILD
-                static const bool fwdOnly = getenv("CPECAN_TIMING_FORWARD_ONLY") != nullptr; /* timing study: wrong results */
-#else
-                const bool fwdOnly = false;
-#endif
-                if (rc == 0 && n > 0 && asmRun && b->asmBackward && !fwdOnly) {
-                    asmArgs.window = w;
-                    asmArgs.scratch = scratchW;
-                    if (postAside && w >= 2) HIP_TRY(hipStreamWaitEvent(sB, b->evPost[(size_t) w - 2], 0));
-                    rc = cpecan_asm_launch_backward(c->device, sB, &asmArgs);
-                    hipStream_t sP = postAside ? L->post : sB;
-                    if (postAside) {
-                        HIP_TRY(hipEventRecord(e4[3], sB));
-                        HIP_TRY(hipStreamWaitEvent(sP, e4[3], 0));
-                    }
-#ifdef CPECAN_TIMING_BUILD
-                    static const bool noPost = getenv("CPECAN_TIMING_NO_POST") != nullptr; /* timing study: sweeps only */
-#else
-                    const bool noPost = false;
-#endif
-                    if (rc == 0 && !noPost)
-                        rc = cpecan_wave_launch_post_asm_l3(sP, b->items.p, n, b->P, b->bandTab.p, b->track.p, b->trackBase.p, models,
-                                                            b->Fstore.p, b->ringDoubles, b->ringD, b->syStates.p, b->pairs.p,
-                                                            b->pairLogp.p, b->totXay.p, b->totVal.p, scratchW,
-                                                            b->scratchBytes, w);
-                    if (postAside) HIP_TRY(hipEventRecord(b->evPost[(size_t) w], sP));
-                } else if (rc == 0 && n > 0 && !fwdOnly && b->fx)
-                    rc = b->fx->launch_backward(sB, b->items.p + i0, n, b->P, b->bandTab.p, b->track.p,
-                                                b->trackBase.p + i0, models, b->Fstore.p + i0 * b->ringDoubles,
-                                                b->ringDoubles, b->ringD, b->syStates.p + i0 * b->stateBytes,
-                                                b->totXay.p, b->totVal.p, b->syScratch.p + i0 * b->scratchBytes,
-                                                b->scratchBytes, b->expect.p, b->kidx.p, w, withSwitch);
-                else if (rc == 0 && n > 0 && !fwdOnly)
-                    rc = b->sy->launch_backward(sB, b->items.p + i0, n, b->P, b->bandTab.p, b->track.p,
-                                                b->trackBase.p + i0, models,
-                                                b->Fstore.p + i0 * b->ringDoubles, b->ringDoubles, b->ringD,
-                                                b->syStates.p + i0 * b->stateBytes, b->pairs.p, b->pairLogp.p,
-                                                b->totXay.p, b->totVal.p, b->syScratch.p + i0 * b->scratchBytes,
-                                                b->scratchBytes,
-                                                b->Bring.p ? b->Bring.p + i0 * (long long) b->ringD * bringRow : nullptr,
-                                                w, withSwitch);
-                if (rc == 0 && n > 0 && b->mode == CPECAN_MODE_EXPECTATIONS && !b->fx)
-                    rc = b->sy->launch_expect(sB, b->items.p + i0, n, b->P, b->bandTab.p, b->track.p,
-                                              b->trackBase.p + i0, b->kidx.p, models,
-                                              b->Fstore.p + i0 * b->ringDoubles, b->ringDoubles,
-                                              b->Bring.p + i0 * (long long) b->ringD * bringRow, b->ringD,
-                                              b->syStates.p + i0 * b->stateBytes,
-                                              b->syScratch.p + i0 * b->scratchBytes, b->scratchBytes, b->expect.p, w,
-                                              b->pairs.p, b->pairLogp.p);
-                if (!postAside) HIP_TRY(hipEventRecord(e4[3], sB));
-            }
-            /* the last sweep back follows every forward sweep; the run ends behind it on the post lane (after the last
-             * post kernel there), which leaves the forward lane to the next run's first forward sweep */
-            HIP_TRY(hipEventRecord(b->evJoin[(size_t) gi], sB));
-            HIP_TRY(hipStreamWaitEvent(sEnd, b->evJoin[(size_t) gi], 0));
-        }
-        if (rc == 0)
-            rc = (b->sy->wave ? cpecan_wave_launch_counts : cpecan_systolic_launch_counts)(
-                sEnd, b->syStates.p, b->nItems, b->nPairs.p, b->nTot.p, b->nCells.p);
-        if (rc != 0) return fail(CPECAN_EHIP, "throughput kernel launch failed: %s",
-                                 hipGetErrorString(hipGetLastError()));
-    }
+    if (b->dna && !b->P.debug && !b->P.unbanded && b->maxWidth <= 192 && !wave5Off && !(b->flags & CPECAN_FLAG_GENERAL_KERNEL))
+        rc = enqueue_wave5(b, L->fwd);
+    else if (b->echelon || b->dna || b->sm4 || b->kernel == CPECAN_KERNEL_GENERAL)
+        rc = enqueue_general(b, L->fwd);
+    else
+        rc = enqueue_sweeps(b, L, &sEnd, &laneRun);
+    if (rc != CPECAN_OK) return rc;
     /* posterior decode: the run ends with its candidates packed for the host (16-byte records + the device's verdict),
      * into a buffer sized by a guess the first time (about one candidate per diagonal) and by the last run's count
      * afterwards; ensure_counts packs again if the guess was short.  Done here, inside the pass, because a kernel
@@ -2312,7 +2148,7 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
 
 int cpecan_hip_batch_expectation_pass(cpecan_batch *b, int32_t *fused) {
     if (!b || !fused) return fail(CPECAN_EINVAL, "bad argument");
-    *fused = b->fx != nullptr ? 1 : 0; /* (set only where the wave kernels run the batch) */
+    *fused = b->fused ? 1 : 0; /* (set only where the wave kernels run the batch) */
     return CPECAN_OK;
 }
 

@@ -1493,84 +1493,58 @@ extern "C" int SY_SYM(cpecan_systolic_prof_fetch)(unsigned long long *dst) {
     return hipMemcpyToSymbol(HIP_SYMBOL(sy_prof), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
 }
 #endif
-extern "C" int SY_SYM(cpecan_systolic_max_width)(void) { return SY_P - 2 * SY_PREFETCH; }
-extern "C" int SY_SYM(cpecan_systolic_rows)(void) { return SY_R; }
-extern "C" int SY_SYM(cpecan_systolic_ring_row_doubles)(void) { return SY_R * SY_RING_VALUES * 64; }
-
-extern "C" int SY_SYM(cpecan_systolic_bring_row_doubles)(void) { return SY_R * 3 * 64; }
-#if SY_R == 4
-extern "C" int cpecan_systolic_state_bytes(void) { return (int) sizeof(SyState); }
-#endif
 /* HBM scratch per alignment: a hit count and an output offset per ring diagonal, and per refresh of the window one
  * WinTotal and the two rows of per-cell terms */
-extern "C" long long SY_SYM(cpecan_systolic_scratch_bytes)(int ringD) {
+static long long sy_scratch_bytes(int ringD) {
     return scratch_cand_offset(ringD)
            + (long long) SY_R * SY_CAND_PER_DIAG * ringD * (sizeof(int2) + sizeof(double));
 }
 
 /* Launchers of the four stages of one pass over a batch (the C-ABI layer sequences them:
  * track, then per window {forward, backward}, then counts). */
+static int sy_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 #if SY_R == 4
-extern "C" int cpecan_systolic_launch_track(hipStream_t stream, const DevItem *items, long long nItems,
-                                            const double *track, const long long *trackBase,
-                                            const unsigned short *kidx, const double *models,
-                                            void *states, int maxLX) {
-    int bx = (int) ((((long long) maxLX + 1) * CP_ROW + 255) / 256);
+static int sy_launch_track(hipStream_t stream, const SweepArgs &a) {
+    int bx = (int) ((((long long) a.maxLX + 1) * CP_ROW + 255) / 256);
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_track, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items,
-                       nItems, trackBase, kidx, models, (double *) track);
-    if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(SyState), stream) != hipSuccess) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    hipLaunchKernelGGL(cpecan_k_track, dim3(bx, (unsigned) std::min(a.nItems, 65535LL)), dim3(256), 0, stream, a.items,
+                       a.nItems, a.trackBase, a.kidx, a.models, a.track);
+    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(SyState), stream) != hipSuccess) return -1;
+    return sy_status();
+}
+static int sy_launch_counts(hipStream_t stream, const SweepArgs &a) {
+    hipLaunchKernelGGL(cpecan_k_sy_counts, dim3((unsigned) ((a.nItems + 255) / 256)), dim3(256), 0, stream,
+                       (const SyState *) a.states, a.nItems, a.nPairs, a.nTot, a.nCells);
+    return sy_status();
 }
 #endif
-extern "C" int SY_SYM(cpecan_systolic_launch_forward)(hipStream_t stream, const DevItem *items, long long nItems,
-                                              DevParams P, const void *bandTab, const double *track,
-                                              const long long *trackBase, const double *events,
-                                              const double *models, double *Fring,
-                                              long long ringDoubles, int ringD, void *states) {
-    hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_forward), dim3((unsigned) nItems), dim3(SY_P), 0, stream, items, nItems,
-                       P, (const int2 *) bandTab, track, trackBase, events, models, Fring, ringDoubles, ringD,
-                       (SyState *) states);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static int sy_launch_forward(hipStream_t stream, const SweepArgs &a, int) {
+    hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_forward), dim3((unsigned) a.nItems), dim3(SY_P), 0, stream, a.items, a.nItems,
+                       a.P, a.bandTab, a.track, a.trackBase, a.events, a.models, a.Fring, a.ringDoubles, a.ringD,
+                       (SyState *) a.states);
+    return sy_status();
 }
-extern "C" int SY_SYM(cpecan_systolic_launch_backward)(hipStream_t stream, const DevItem *items, long long nItems,
-                                               DevParams P, const void *bandTab, const double *track,
-                                               const long long *trackBase, const double *models,
-                                               double *Fring, long long ringDoubles, int ringD,
-                                               void *states, long long *pairs, double *pairLogp,
-                                               long long *totXay, double *totVal, char *scratch,
-                                               long long scratchBytes, double *Bring, int window) {
-    hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_backward), dim3((unsigned) nItems), dim3(SY_P), 0, stream, items, nItems,
-                       P, (const int2 *) bandTab, track, trackBase, models, Fring, ringDoubles, ringD,
-                       (SyState *) states, pairs, pairLogp, totXay, totVal, scratch, scratchBytes, Bring, window);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static int sy_launch_backward(hipStream_t stream, const SweepArgs &a, int window) {
+    hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_backward), dim3((unsigned) a.nItems), dim3(SY_P), 0, stream, a.items, a.nItems,
+                       a.P, a.bandTab, a.track, a.trackBase, a.models, a.Fring, a.ringDoubles, a.ringD,
+                       (SyState *) a.states, a.pairs, a.pairLogp, a.totXay, a.totVal, a.scratch, a.scratchBytes, a.Bring,
+                       window);
+    return sy_status();
 }
-extern "C" int SY_SYM(cpecan_systolic_launch_expect)(hipStream_t stream, const DevItem *items, long long nItems,
-                                             DevParams P, const void *bandTab, const double *track,
-                                             const long long *trackBase, const unsigned short *kidx,
-                                             const double *models, const double *Fring,
-                                             long long ringDoubles, const double *Bring, int ringD,
-                                             void *states, const char *scratch, long long scratchBytes,
-                                             double *expect, int window, long long *pairs, double *pairLogp) {
-    (void) pairs; (void) pairLogp; /* (the HDP machine's wave kernels append event assignments there) */
-    hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_expect), dim3((unsigned) nItems, SY_EXPECT_CHUNKS), dim3(SY_P), 0, stream,
-                       items, nItems, P, (const int2 *) bandTab, track, trackBase, kidx, models, Fring, ringDoubles,
-                       Bring, ringD, (SyState *) states, scratch, scratchBytes, expect, window);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) {
+    hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_expect), dim3((unsigned) a.nItems, SY_EXPECT_CHUNKS), dim3(SY_P), 0, stream,
+                       a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.kidx, a.models, a.Fring, a.ringDoubles,
+                       a.Bring, a.ringD, (SyState *) a.states, a.scratch, a.scratchBytes, a.expect, window);
+    return sy_status();
 }
-#if SY_R == 4
-extern "C" int cpecan_systolic_launch_counts(hipStream_t stream, const void *states, long long nItems,
-                                             long long *nPairs, long long *nTot, long long *nCells) {
-    hipLaunchKernelGGL(cpecan_k_sy_counts, dim3((unsigned) ((nItems + 255) / 256)), dim3(256), 0, stream,
-                       (const SyState *) states, nItems, nPairs, nTot, nCells);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-#endif
 
-extern "C" int SY_SYM(cpecan_systolic_occupancy)(int *workgroupsPerCU) {
-    int n = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, SY_SYM(cpecan_k_sy_backward), SY_P, 0);
-    if (e != hipSuccess) return -1;
-    *workgroupsPerCU = n;
-    return 0;
-}
+/* the records (host only: the device pass would emit them as constants, with pointers to host functions) */
+#ifndef __HIP_DEVICE_COMPILE__
+#if SY_R == 4
+const SweepMachine cpecan_systolic_machine = { (int) sizeof(SyState), CP_ROW, sy_launch_track, sy_launch_counts };
+#endif
+extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
+const SweepBuild SY_SYM(cpecan_systolic_build) = {
+    SY_R, false, SWEEP_STRAWMAN, &cpecan_systolic_machine, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, SY_R * 3 * 64,
+    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, sy_launch_expect, nullptr };
+#endif

@@ -45,7 +45,7 @@
  * log(0.1); symbols suffixed _h2.._h4 */
 /* -DWV_VANILLA: the 3-state vanilla signal machine (stateMachine3Vanilla_cellCalculate, impl/stateMachine.c:1368-1409):
  * transition probabilities per reference position (30 skip bins of the k-mer pair sequence_getKmer2 exposes), a
- * Gaussian level term plus an inverse-Gaussian noise term per emission; symbols suffixed _v2.._v4 */
+ * Gaussian level term plus an inverse-Gaussian noise term per emission; symbols suffixed _v2, _v3 (four cells per lane spill: not built) */
 #if defined(WV_VANILLA) && WV_L == 4
 #define WV_SYM(n) n##_v4
 #elif defined(WV_VANILLA) && WV_L == 3
@@ -66,6 +66,13 @@
 #define WV_SYM(n) n##_l2
 #else
 #define WV_SYM(n) n##_l1
+#endif
+/* what a machine needs once, not per build (track kernel, counts, its SweepMachine record), is compiled into its
+ * widest linked build: four cells per lane, three for the vanilla machine (whose four-cell build spills) */
+#if defined(WV_VANILLA)
+#define WV_WIDEST 3
+#else
+#define WV_WIDEST 4
 #endif
 #if defined(WV_VANILLA)
 #define WV_MODEL_DOUBLES ((long long) CP_VMODEL_STRIDE)
@@ -2420,7 +2427,19 @@ extern "C" __global__ __launch_bounds__(WV_P) void WV_SYM(cpecan_k_wv_expect)(
 
 #endif /* strawMan and HDP builds */
 
-#if WV_L == 4 && !defined(WV_HDP) && !defined(WV_VANILLA)
+#if WV_L == WV_WIDEST
+/* the track kernels' grid, and the states cleared behind them */
+static dim3 wv_track_grid(const SweepArgs &a) {
+    const long long bx = (((long long) a.maxLX + 1) * WV_ROW + 255) / 256;
+    return dim3((unsigned) std::min(bx, 64LL), (unsigned) std::min(a.nItems, 65535LL));
+}
+static int wv_clear_states(hipStream_t stream, const SweepArgs &a) {
+    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(WvState), stream) != hipSuccess) return -1;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+#endif
+
+#if WV_L == WV_WIDEST && !defined(WV_HDP) && !defined(WV_VANILLA)
 /* per-item track of emission constants, wave layout: column x (0..lX) = the 16 emission constants of the k-mer
  * that matrix column x scores (column 0 = the "not a k-mer" sentinel, sequence_getKmer index -1, :314-318),
  * its gap-X emission plus each of the three transitions into gap X (the eP + tP of cell_calculate*), and the
@@ -2451,18 +2470,11 @@ extern "C" __global__ void cpecan_k_wv_track(const DevItem *__restrict__ items, 
         }
     }
 }
-extern "C" int cpecan_wave_launch_track(hipStream_t stream, const DevItem *items, long long nItems,
-                                        const double *track, const long long *trackBase,
-                                        const unsigned short *kidx, const double *models, void *states, int maxLX) {
-    int bx = (int) ((((long long) maxLX + 1) * WV_ROW + 255) / 256);
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_wv_track, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items, nItems,
-                       trackBase, kidx, models, (double *) track);
-    if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(WvState), stream) != hipSuccess) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
+    hipLaunchKernelGGL(cpecan_k_wv_track, wv_track_grid(a), dim3(256), 0, stream, a.items, a.nItems, a.trackBase, a.kidx,
+                       a.models, a.track);
+    return wv_clear_states(stream, a);
 }
-extern "C" int cpecan_wave_track_row_doubles(void) { return WV_ROW; }
-extern "C" int cpecan_wave_state_bytes(void) { return (int) sizeof(WvState); }
 /* the shader clock the forward sweeps of the last run saw, in MHz (s_memtime ticks over 100 MHz s_memrealtime ticks,
  * summed over the first alignments of the batch); 0 when nothing ran */
 extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *states, long long nItems, double *mhz) {
@@ -2488,15 +2500,14 @@ extern "C" __global__ void cpecan_k_wv_counts(const WvState *states, long long n
     nTot[i] = states[i].nTot;
     nCells[i] = states[i].cells;
 }
-extern "C" int cpecan_wave_launch_counts(hipStream_t stream, const void *states, long long nItems, long long *nPairs,
-                                         long long *nTot, long long *nCells) {
-    hipLaunchKernelGGL(cpecan_k_wv_counts, dim3((unsigned) ((nItems + 255) / 256)), dim3(256), 0, stream,
-                       (const WvState *) states, nItems, nPairs, nTot, nCells);
+int cpecan_wave_launch_counts(hipStream_t stream, const SweepArgs &a) {
+    hipLaunchKernelGGL(cpecan_k_wv_counts, dim3((unsigned) ((a.nItems + 255) / 256)), dim3(256), 0, stream,
+                       (const WvState *) a.states, a.nItems, a.nPairs, a.nTot, a.nCells);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #endif
 
-#if WV_L == 4 && defined(WV_VANILLA)
+#if WV_L == WV_WIDEST && defined(WV_VANILLA)
 /* the vanilla machine's track: matrix column x scores the k-mer pair sequence_getKmer2 (impl/pairwiseAligner.c:320-325)
  * exposes for sequence index x - 1 -- a pointer to character max(x - 2, 0): the skip bin looks at the k-mers there
  * and one further, the emissions at the one further (columns 0, 1 and 2 all score k-mers 0 and 1, as in the
@@ -2542,21 +2553,14 @@ extern "C" __global__ void cpecan_k_wv_track_vanilla(const DevItem *__restrict__
         }
     }
 }
-extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const DevItem *items, long long nItems,
-                                                const double *track, const long long *trackBase,
-                                                const unsigned short *kidx, const double *models, void *states,
-                                                int maxLX) {
-    int bx = (int) ((((long long) maxLX + 1) * WV_ROW + 255) / 256);
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_wv_track_vanilla, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items, nItems,
-                       trackBase, kidx, models, (double *) track);
-    if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(WvState), stream) != hipSuccess) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
+    hipLaunchKernelGGL(cpecan_k_wv_track_vanilla, wv_track_grid(a), dim3(256), 0, stream, a.items, a.nItems, a.trackBase,
+                       a.kidx, a.models, a.track);
+    return wv_clear_states(stream, a);
 }
-extern "C" int cpecan_wave_track_row_doubles_vanilla(void) { return WV_ROW; }
 #endif
 
-#if WV_L == 4 && defined(WV_HDP)
+#if WV_L == WV_WIDEST && defined(WV_HDP)
 /* the HDP machine's track: column x (0..lX) = the offset (in doubles) of the table row of the k-mer that matrix
  * column x scores -- sequence_getKmer3 (:327-331): column 0 (index -1) reads the first k-mer, like column 1 -- and
  * the flat gap-X emission log(0.1) (stateMachine.c:1347) plus each of the three transitions into gap X */
@@ -2586,136 +2590,108 @@ extern "C" __global__ void cpecan_k_wv_track_hdp(const DevItem *__restrict__ ite
         }
     }
 }
-extern "C" int cpecan_wave_launch_track_hdp(hipStream_t stream, const DevItem *items, long long nItems,
-                                            const double *track, const long long *trackBase, const int *kid,
-                                            const void *models, void *states, int maxLX) {
-    int bx = (int) ((((long long) maxLX + 1) * WV_ROW + 255) / 256);
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_wv_track_hdp, dim3(bx, (unsigned) std::min(nItems, 65535LL)), dim3(256), 0, stream, items, nItems,
-                       trackBase, kid, (const DevHdpModel *) models, (double *) track);
-    if (hipMemsetAsync(states, 0, (size_t) nItems * sizeof(WvState), stream) != hipSuccess) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
+    hipLaunchKernelGGL(cpecan_k_wv_track_hdp, wv_track_grid(a), dim3(256), 0, stream, a.items, a.nItems, a.trackBase, a.kid,
+                       (const DevHdpModel *) a.models, a.track);
+    return wv_clear_states(stream, a);
 }
 #endif
 
-extern "C" int WV_SYM(cpecan_wave_max_width)(void) { return WV_P - 8; }
-extern "C" int WV_SYM(cpecan_wave_rows)(void) { return WV_L; }
-extern "C" int WV_SYM(cpecan_wave_ring_row_doubles)(void) { return WV_ROW_DOUBLES; }
-extern "C" int WV_SYM(cpecan_wave_bring_row_doubles)(void) { return WV_L * 3 * 64; }
-/* HBM scratch per alignment: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list] */
-extern "C" long long WV_SYM(cpecan_wave_scratch_bytes)(int ringD) { return wv_scratch_base_bytes(ringD); }
-/* ... and after it, in batches with fused expectations, the segments' sums (WvFx) */
-extern "C" long long WV_SYM(cpecan_wave_fx_scratch_bytes)(int ringD) { return wv_fx_bytes(ringD); }
-extern "C" int WV_SYM(cpecan_wave_launch_forward)(hipStream_t stream, const DevItem *items, long long nItems,
-                                                  DevParams P, const void *bandTab, const double *track,
-                                                  const long long *trackBase, const double *events,
-                                                  const double *models, double *Fring, long long ringDoubles,
-                                                  int ringD, void *states, int window, int withSwitch) {
-    if (withSwitch)
-        hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_forward_sw), dim3((unsigned) ((nItems + WV_WPB - 1) / WV_WPB)), dim3(64 * WV_WPB), 0, stream, items, nItems,
-                           P, (const int2 *) bandTab, track, trackBase, events, models, Fring, ringDoubles, ringD,
-                           (WvState *) states, window);
-    else
-        hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_forward), dim3((unsigned) ((nItems + WV_WPB - 1) / WV_WPB)), dim3(64 * WV_WPB), 0, stream, items, nItems, P,
-                           (const int2 *) bandTab, track, trackBase, events, models, Fring, ringDoubles, ringD,
-                           (WvState *) states, window);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+/* The launchers: each kernel signature is fed from the record in one place, so which kernel runs (_sw, _em, re-sweep)
+ * is a choice of function pointer */
+static dim3 wv_sweep_grid(const SweepArgs &a) { return dim3((unsigned) ((a.nItems + WV_WPB - 1) / WV_WPB)); }
+static int wv_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+static void wv_sweep_back(decltype(&WV_SYM(cpecan_k_wv_backward)) k, hipStream_t stream, const SweepArgs &a, int window) {
+    hipLaunchKernelGGL(k, wv_sweep_grid(a), dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track,
+                       a.trackBase, a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, a.pairs, a.pairLogp,
+                       a.scratch, a.scratchBytes, a.Bring, window);
 }
-extern "C" int WV_SYM(cpecan_wave_launch_backward)(hipStream_t stream, const DevItem *items, long long nItems,
-                                                   DevParams P, const void *bandTab, const double *track,
-                                                   const long long *trackBase, const double *models, double *Fring,
-                                                   long long ringDoubles, int ringD, void *states, long long *pairs,
-                                                   double *pairLogp, long long *totXay, double *totVal, char *scratch,
-                                                   long long scratchBytes, double *Bring, int window, int withSwitch) {
-#define WV_LAUNCH_B(k)                                                                                            \
-    hipLaunchKernelGGL(WV_SYM(k), dim3((unsigned) ((nItems + WV_WPB - 1) / WV_WPB)), dim3(64 * WV_WPB), 0, stream, items, nItems, P, \
-                       (const int2 *) bandTab, track, trackBase, models, Fring, ringDoubles, ringD,               \
-                       (WvState *) states, pairs, pairLogp, scratch, scratchBytes, Bring, window)
-#define WV_LAUNCH_POST                                                                                            \
-    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) nItems), dim3(256), 0, stream, items, nItems, P, \
-                       (const int2 *) bandTab, models, (const double *) Fring, ringDoubles, ringD,                \
-                       (WvState *) states, pairs, pairLogp, totXay, totVal, scratch, scratchBytes, window, 0,        \
-                       (double *) nullptr, (const unsigned short *) nullptr)
-    if (P.mode != 0) {
+/* the window's totals and decode -- or, fused, its totals and the sums into expect[] (no pairs) */
+static void wv_post(hipStream_t stream, const SweepArgs &a, int window, bool fused) {
+    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) a.nItems), dim3(256), 0, stream, a.items, a.nItems, a.P,
+                       a.bandTab, a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states,
+                       fused ? nullptr : a.pairs, fused ? nullptr : a.pairLogp, a.totXay, a.totVal, a.scratch,
+                       a.scratchBytes, window, fused ? 1 : 0, fused ? a.expect : nullptr, fused ? a.kidx : nullptr);
+}
+static int wv_launch_forward(hipStream_t stream, const SweepArgs &a, int window) {
+    hipLaunchKernelGGL(a.withSwitch ? WV_SYM(cpecan_k_wv_forward_sw) : WV_SYM(cpecan_k_wv_forward), wv_sweep_grid(a),
+                       dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.events,
+                       a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, window);
+    return wv_status();
+}
+/* the totals and the decode of a window swept back with decode candidates, then the kernel that sweeps once more the
+ * windows whose candidates could not be trusted (it returns at once for the others).  The same two follow the assembly
+ * sweep back of a window (cpecan_asm.h), which leaves the refreshes' terms and the candidates in scratch as the
+ * compiled sweep does */
+static int wv_launch_post(hipStream_t stream, const SweepArgs &a, int window) {
+    wv_post(stream, a, window, false);
+    wv_sweep_back(a.withSwitch ? WV_SYM(cpecan_k_wv_resweep_sw) : WV_SYM(cpecan_k_wv_resweep), stream, a, window);
+    return wv_status();
+}
+static int wv_launch_backward(hipStream_t stream, const SweepArgs &a, int window) {
+    if (a.P.mode != 0) {
 #if defined(WV_VANILLA)
-        if (withSwitch) return -1;
-        WV_LAUNCH_B(cpecan_k_wv_backward_em);
-        WV_LAUNCH_POST;
+        if (a.withSwitch) return -1;
+        wv_sweep_back(WV_SYM(cpecan_k_wv_backward_em), stream, a, window);
 #else
-        if (withSwitch) WV_LAUNCH_B(cpecan_k_wv_backward_em_sw);
-        else WV_LAUNCH_B(cpecan_k_wv_backward_em);
-        WV_LAUNCH_POST;
+        wv_sweep_back(a.withSwitch ? WV_SYM(cpecan_k_wv_backward_em_sw) : WV_SYM(cpecan_k_wv_backward_em), stream, a,
+                      window);
 #endif
-    } else {
-        /* the sweep with decode candidates, the window's totals and decode, then the kernel that sweeps once more
-         * the windows whose candidates could not be trusted (it returns at once for the others) */
-        if (withSwitch) WV_LAUNCH_B(cpecan_k_wv_backward_sw);
-        else WV_LAUNCH_B(cpecan_k_wv_backward);
-        WV_LAUNCH_POST;
-        if (withSwitch) WV_LAUNCH_B(cpecan_k_wv_resweep_sw);
-        else WV_LAUNCH_B(cpecan_k_wv_resweep);
+        wv_post(stream, a, window, false);
+        return wv_status();
     }
-#undef WV_LAUNCH_B
-#undef WV_LAUNCH_POST
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    wv_sweep_back(a.withSwitch ? WV_SYM(cpecan_k_wv_backward_sw) : WV_SYM(cpecan_k_wv_backward), stream, a, window);
+    return wv_launch_post(stream, a, window);
 }
-#if !defined(WV_VANILLA) && !defined(WV_HDP)
-/* what follows the assembly sweep back of a window (cpecan_asm.h), which leaves the refreshes' terms and the decode
- * candidates in scratch as the compiled sweep does: the totals, the decode; then the re-sweep kernel for the windows
- * whose candidates could not be trusted */
-extern "C" int WV_SYM(cpecan_wave_launch_post_asm)(hipStream_t stream, const DevItem *items, long long nItems, DevParams P,
-                                                   const void *bandTab, const double *track, const long long *trackBase,
-                                                   const double *models, double *Fring, long long ringDoubles, int ringD,
-                                                   void *states, long long *pairs, double *pairLogp, long long *totXay,
-                                                   double *totVal, char *scratch, long long scratchBytes, int window) {
-    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) nItems), dim3(256), 0, stream, items, nItems, P,
-                       (const int2 *) bandTab, models, (const double *) Fring, ringDoubles, ringD, (WvState *) states, pairs,
-                       pairLogp, totXay, totVal, scratch, scratchBytes, window, 0, (double *) nullptr,
-                       (const unsigned short *) nullptr);
-    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_resweep), dim3((unsigned) ((nItems + WV_WPB - 1) / WV_WPB)), dim3(64 * WV_WPB), 0, stream,
-                       items, nItems, P, (const int2 *) bandTab, track, trackBase, models, Fring, ringDoubles, ringD,
-                       (WvState *) states, pairs, pairLogp, scratch, scratchBytes, (double *) nullptr, window);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static int wv_launch_expect(hipStream_t stream, const SweepArgs &a, int window) {
+    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_expect), dim3((unsigned) a.nItems, WV_EXPECT_CHUNKS), dim3(WV_P), 0, stream,
+                       a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.kidx, a.models, a.Fring, a.ringDoubles,
+                       a.Bring, a.ringD, (WvState *) a.states, a.scratch, a.scratchBytes, a.expect, window, a.pairs,
+                       a.pairLogp);
+    return wv_status();
 }
-#endif
-
 #if !defined(WV_VANILLA) && !defined(WV_HDP)
 /* the strawMan E-step of a window with fused expectations: the sweep back summing them, the totals and the sums into
  * expect[] (cpecan_k_wv_post), then the re-sweep of the windows the estimate could not carry (it returns at once for
  * the others).  All three index alignments by blockIdx.x. */
-extern "C" int WV_SYM(cpecan_wave_launch_backward_fx)(hipStream_t stream, const DevItem *items, long long nItems,
-                                                      DevParams P, const void *bandTab, const double *track,
-                                                      const long long *trackBase, const double *models, double *Fring,
-                                                      long long ringDoubles, int ringD, void *states, long long *totXay,
-                                                      double *totVal, char *scratch, long long scratchBytes,
-                                                      double *expect, const unsigned short *kidx, int window,
-                                                      int withSwitch) {
-#define WV_LAUNCH_FX(k)                                                                                           \
-    hipLaunchKernelGGL(WV_SYM(k), dim3((unsigned) ((nItems + WV_WPB - 1) / WV_WPB)), dim3(64 * WV_WPB), 0, stream, items, nItems, P, \
-                       (const int2 *) bandTab, track, trackBase, models, Fring, ringDoubles, ringD,               \
-                       (WvState *) states, scratch, scratchBytes, expect, kidx, window)
-    if (withSwitch) WV_LAUNCH_FX(cpecan_k_wv_backward_fx_sw);
-    else WV_LAUNCH_FX(cpecan_k_wv_backward_fx);
-    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) nItems), dim3(256), 0, stream, items, nItems, P,
-                       (const int2 *) bandTab, models, (const double *) Fring, ringDoubles, ringD, (WvState *) states,
-                       (long long *) nullptr, (double *) nullptr, totXay, totVal, scratch, scratchBytes, window, 1,
-                       expect, kidx);
-    if (withSwitch) WV_LAUNCH_FX(cpecan_k_wv_resweep_fx_sw);
-    else WV_LAUNCH_FX(cpecan_k_wv_resweep_fx);
-#undef WV_LAUNCH_FX
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+static void wv_sweep_back_fx(decltype(&WV_SYM(cpecan_k_wv_backward_fx)) k, hipStream_t stream, const SweepArgs &a,
+                             int window) {
+    hipLaunchKernelGGL(k, wv_sweep_grid(a), dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track,
+                       a.trackBase, a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, a.scratch,
+                       a.scratchBytes, a.expect, a.kidx, window);
 }
+static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int window) {
+    wv_sweep_back_fx(a.withSwitch ? WV_SYM(cpecan_k_wv_backward_fx_sw) : WV_SYM(cpecan_k_wv_backward_fx), stream, a, window);
+    wv_post(stream, a, window, true);
+    wv_sweep_back_fx(a.withSwitch ? WV_SYM(cpecan_k_wv_resweep_fx_sw) : WV_SYM(cpecan_k_wv_resweep_fx), stream, a, window);
+    return wv_status();
+}
+#define WV_STRAWMAN_ONLY(f) f
+#else
+#define WV_STRAWMAN_ONLY(f) nullptr
 #endif
 
-extern "C" int WV_SYM(cpecan_wave_launch_expect)(hipStream_t stream, const DevItem *items, long long nItems,
-                                                 DevParams P, const void *bandTab, const double *track,
-                                                 const long long *trackBase, const unsigned short *kidx,
-                                                 const double *models, const double *Fring, long long ringDoubles,
-                                                 const double *Bring, int ringD, void *states, const char *scratch,
-                                                 long long scratchBytes, double *expect, int window, long long *pairs,
-                                                 double *pairLogp) {
-    hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_expect), dim3((unsigned) nItems, WV_EXPECT_CHUNKS), dim3(WV_P), 0, stream,
-                       items, nItems, P, (const int2 *) bandTab, track, trackBase, kidx, models, Fring, ringDoubles,
-                       Bring, ringD, (WvState *) states, scratch, scratchBytes, expect, window, pairs, pairLogp);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
+/* the records (host only: the device pass would emit them as constants, with pointers to host functions) */
+#ifndef __HIP_DEVICE_COMPILE__
+#if defined(WV_VANILLA)
+#define WV_MACHINE SWEEP_VANILLA
+#define WV_ONCE cpecan_wave_machine_vanilla
+#elif defined(WV_HDP)
+#define WV_MACHINE SWEEP_HDP
+#define WV_ONCE cpecan_wave_machine_hdp
+#else
+#define WV_MACHINE SWEEP_STRAWMAN
+#define WV_ONCE cpecan_wave_machine
+#endif
+#if WV_L == WV_WIDEST
+const SweepMachine WV_ONCE = { (int) sizeof(WvState), WV_ROW, wv_launch_track, cpecan_wave_launch_counts };
+#endif
+/* scratch: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list], and after it,
+ * in batches with fused expectations, the segments' sums (WvFx) */
+extern "C" const SweepBuild WV_SYM(cpecan_wave_build);
+const SweepBuild WV_SYM(cpecan_wave_build) = {
+    WV_L, true, WV_MACHINE, &WV_ONCE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
+    wv_scratch_base_bytes, WV_STRAWMAN_ONLY(wv_fx_bytes),
+    wv_launch_forward, wv_launch_backward, WV_STRAWMAN_ONLY(wv_launch_backward_fx), wv_launch_expect,
+    WV_STRAWMAN_ONLY(wv_launch_post) };
+#endif

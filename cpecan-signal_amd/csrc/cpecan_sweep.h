@@ -5,6 +5,8 @@
 #ifndef CPECAN_SWEEP_H_
 #define CPECAN_SWEEP_H_
 
+#include "cpecan_device.h"
+
 /* Per-alignment state handed between the forward-window and backward-window kernels. */
 struct SyState {
     int d;            /* last forward diagonal completed */
@@ -44,6 +46,87 @@ struct WvState {
 struct WinTotal {
     int t, xmin, xmax, nxmin, nxmax, second;
     double total;
+};
+
+/* What the stages of one pass over a batch read and write (host side only: the kernels keep their parameter lists, and
+ * each launcher unpacks the record into one of them).  The C-ABI layer fills it once per run; the window index is a
+ * launch argument of its own. */
+struct SweepArgs {
+    const DevItem *items;
+    long long nItems;
+    DevParams P;
+    const int2 *bandTab;
+    double *track; /* written by the track kernel, read by the sweeps */
+    const long long *trackBase;
+    int maxLX;
+    const double *events;
+    const unsigned short *kidx; /* per X position: k-mer index */
+    const int *kid;             /* ... HDP batches: k-mer id over the model's alphabet (the HDP track kernel) */
+    const double *models;       /* strawMan or vanilla tables, or the DevHdpModel records of an HDP batch */
+    double *Fring;
+    long long ringDoubles;
+    int ringD;
+    char *states;
+    int stateBytes;
+    long long *pairs;
+    double *pairLogp;
+    long long *totXay;
+    double *totVal;
+    char *scratch;
+    long long scratchBytes;
+    double *Bring; /* null unless the E-step keeps its backward cells */
+    int bringRow;  /* doubles per diagonal of it */
+    double *expect;
+    long long *nPairs, *nTot, *nCells; /* the counts kernel's */
+    int withSwitch; /* some model lets gap Y switch to gap X: the builds with that term */
+
+    /* the record of the stream group of n alignments from i0 on: the kernels index what is kept per alignment by
+     * blockIdx, so those bases shift; everything else is addressed through the item */
+    SweepArgs slice(long long i0, long long n) const {
+        SweepArgs a = *this;
+        a.items += i0;
+        a.nItems = n;
+        a.trackBase += i0;
+        a.Fring += i0 * ringDoubles;
+        a.states += i0 * stateBytes;
+        a.scratch += i0 * scratchBytes;
+        if (a.Bring) a.Bring += i0 * (long long) ringD * bringRow;
+        return a;
+    }
+};
+
+typedef int (*SweepLaunch)(hipStream_t stream, const SweepArgs &a, int window);
+
+/* the once-per-pass pieces of a machine on a kernel family: the track before the sweeps, the counts after them */
+struct SweepMachine {
+    int stateBytes;      /* per alignment: SyState or WvState */
+    int trackRowDoubles; /* per matrix column of the track */
+    int (*launch_track)(hipStream_t stream, const SweepArgs &a); /* (and the states cleared) */
+    int (*launch_counts)(hipStream_t stream, const SweepArgs &a);
+};
+extern "C" int cpecan_wave_launch_counts(hipStream_t stream, const SweepArgs &a); /* (one for the three wave machines) */
+extern "C" const SweepMachine cpecan_systolic_machine, cpecan_wave_machine, cpecan_wave_machine_hdp,
+    cpecan_wave_machine_vanilla;
+
+enum { SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA };
+
+/* One compiled build of the throughput kernels, defined next to them (cpecan_kernel_systolic.hip: cpecan_systolic_build
+ * and _r1.._r3; cpecan_kernel_wave.hip: cpecan_wave_build_l2.._l4, _h2.._h4, _v2, _v3) */
+struct SweepBuild {
+    int rows;    /* waves per workgroup (workgroup family) or cells per lane (wave family) */
+    bool wave;   /* one wave per alignment */
+    int machine; /* SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA */
+    const SweepMachine *once; /* ... and its once-per-pass pieces on this family */
+    int maxWidth;        /* widest band, in k-mers */
+    int ringRowDoubles;  /* per diagonal of the forward ring */
+    int bringRowDoubles; /* ... of the ring of backward cells */
+    long long (*scratch_bytes)(int ringD);    /* HBM scratch per alignment */
+    long long (*fx_scratch_bytes)(int ringD); /* ... and what fused expectations add behind it (null: none) */
+    SweepLaunch forward;
+    SweepLaunch backward;    /* the sweep back of a window and what follows it (totals, decode, re-sweep) */
+    SweepLaunch backward_fx; /* the E-step with the expectations summed inside the sweep back (null: none) */
+    SweepLaunch expect;      /* the E-step from the ring of backward cells */
+    SweepLaunch post_asm;    /* what follows the assembly sweep back of a window (null: no assembly sweeps) */
 };
 
 #endif

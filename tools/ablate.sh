@@ -13,11 +13,8 @@ for v in NONE "$@"; do
   flag=""; [ "$v" != NONE ] && flag="-DSY_ABLATE_$v"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
       -Wno-unused-function -I../include -Icsrc $flag -c csrc/cpecan_kernel_systolic.hip -o $out/systolic.o || { echo "$v build failed" | tee -a $out/result_systolic.txt; continue; }
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libcpecan_hip_abl.so csrc/cpecan_hip.o csrc/cpecan_asm.o \
-      csrc/cpecan_kernel_general.o csrc/cpecan_kernel_general5.o csrc/cpecan_kernel_generalv.o csrc/cpecan_kernel_generalh.o \
-      csrc/cpecan_kernel_general4.o $out/systolic.o csrc/cpecan_kernel_wave5.o \
-      csrc/cpecan_kernel_systolic_r1.o csrc/cpecan_kernel_systolic_r2.o csrc/cpecan_kernel_systolic_r3.o \
-      csrc/cpecan_kernel_wave_l2.o csrc/cpecan_kernel_wave_l3.o csrc/cpecan_kernel_wave_l4.o csrc/cpecan_kernel_wave_h2.o csrc/cpecan_kernel_wave_h3.o csrc/cpecan_kernel_wave_h4.o csrc/cpecan_kernel_wave_v2.o csrc/cpecan_kernel_wave_v3.o csrc/cpecan_kernel_wave_v4.o csrc/cpecan_geometry.o -lpthread
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libcpecan_hip_abl.so \
+      $(make -s print-objects | sed "s|csrc/cpecan_kernel_systolic.o|$out/systolic.o|") -lpthread
   r=$(cd $root && CPECAN_HIP_LIB=$out/libcpecan_hip_abl.so CPECAN_SYSTOLIC_GROUPS=1 timeout -k 10 120 python bench.py --steps 12 --warmup 3 --check 0 --cpu-reads 0 --inflight 1 --family workgroup --single-steps 0 2>/dev/null | python -c "
 import json,sys;j=json.loads(sys.stdin.read().strip().splitlines()[-1]);r=j['roofline'];print(j['ms_per_step'],r['backward_kernel']['avg_launch_ms'],r['forward_kernel']['avg_launch_ms'])")
   echo "$v $r" | tee -a $out/result_systolic.txt
