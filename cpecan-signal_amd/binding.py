@@ -51,7 +51,8 @@ EXPORTS = [
     "cpecan_hip_batch_destroy", "cpecan_hip_ctx_stream", "cpecan_hip_selftest_division", "cpecan_hip_batch_info", "cpecan_hip_batch_stage_ms",
     "cpecan_hip_batch_systolic_rows", "cpecan_hip_batch_kernel_family", "cpecan_hip_batch_assembly_sweeps", "cpecan_hip_batch_expectation_pass", "cpecan_hip_trim_cache", "cpecan_hip_models_set_transitions",
     "cpecan_hip_models5_create", "cpecan_hip_batch_create_dna",
-    "cpecan_hip_modelsv_create", "cpecan_hip_batch_create_vanilla", "cpecan_hip_models4_create", "cpecan_hip_batch_create_sm4",
+    "cpecan_hip_modelsv_create", "cpecan_hip_modelsv_create_scaled", "cpecan_hip_modelsv_download",
+    "cpecan_hip_modelsv_set_skip_probs", "cpecan_hip_batch_create_vanilla", "cpecan_hip_models4_create", "cpecan_hip_batch_create_sm4",
     "cpecan_hip_modelsh_create", "cpecan_hip_batch_create_hdp",
     "cpecan_hip_modelse_create", "cpecan_hip_batch_create_echelon",
 ]
@@ -161,6 +162,9 @@ def lib():
             C.POINTER(C.c_void_p)]
         L.cpecan_hip_models5_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.cpecan_hip_modelsv_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.cpecan_hip_modelsv_create_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.cpecan_hip_modelsv_download.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.cpecan_hip_modelsv_set_skip_probs.argtypes = [C.c_void_p, C.c_void_p]
         L.cpecan_hip_modelsh_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.cpecan_hip_batch_create_hdp.argtypes = [
             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -351,6 +355,38 @@ class Context:
         ids = np.zeros(n, np.int32)
         _check(lib().cpecan_hip_modelsv_create(self.h, C.cast(descs, C.c_void_p), n, threads, _ptr(ids)))
         return ids
+
+    def modelsv_create_scaled(self, base, scalings, threads=0):
+        """base: (scalars[5], match[20481], skip[60], gap_y[20481]) of one strand's unscaled vanilla model; scalings:
+        [n, 5] (scale, shift, var, scale_sd, var_sd) per read -> ids.  emissions_signal_scaleModel per read, the
+        blocks assembled on the device."""
+        scalars, match, skip, gy = base
+        match = np.ascontiguousarray(match, dtype=np.float64)
+        skip = np.ascontiguousarray(skip, dtype=np.float64)
+        gy = np.ascontiguousarray(gy, dtype=np.float64)
+        assert match.size == MODEL_TABLE_LEN and gy.size == MODEL_TABLE_LEN and skip.size == 60
+        sc = np.ascontiguousarray(scalings, dtype=np.float64).reshape(-1, 5)
+        desc = VanillaModelDesc()
+        (desc.m_to_y_not_x, desc.e_to_e, desc.end_match_prob, desc.end_from_x_prob,
+         desc.end_from_y_prob) = [float(v) for v in scalars]
+        desc.match_probs, desc.skip_probs, desc.gap_y_probs = match.ctypes.data, skip.ctypes.data, gy.ctypes.data
+        ids = np.zeros(len(sc), np.int32)
+        _check(lib().cpecan_hip_modelsv_create_scaled(self.h, C.byref(desc), _ptr(sc), len(sc), threads, _ptr(ids)))
+        return ids
+
+    def modelsv_download(self, model_id):
+        """the derived device block of one vanilla model (test aid)"""
+        n = C.c_int64(0)
+        _check(lib().cpecan_hip_modelsv_download(self.h, 0, None, 0, C.byref(n)))
+        out = np.zeros(n.value)
+        _check(lib().cpecan_hip_modelsv_download(self.h, int(model_id), _ptr(out), out.size, C.byref(n)))
+        return out
+
+    def modelsv_set_skip_probs(self, skip):
+        """the M-step's update of every vanilla model of the context, in place on the device: skip = beta[30] | alpha[30]"""
+        s = np.ascontiguousarray(skip, dtype=np.float64)
+        assert s.size == 60
+        _check(lib().cpecan_hip_modelsv_set_skip_probs(self.h, _ptr(s)))
 
     def models4_create(self, models):
         """models: list of (transitions[11] in the member order of _StateMachine4, match[20481], gap_x[4096],

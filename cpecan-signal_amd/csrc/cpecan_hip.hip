@@ -382,11 +382,12 @@ struct cpecan_ctx {
     std::vector<DevHdpModel> hostModelsH;
     DevBuf<DevHdpModel> modelsH;
     std::string hdpAlphabet;
-    DevBuf<double> modelsV; /* vanilla signal models, nModelsV * CP_VMODEL_STRIDE */
+    DevBuf<double> modelsV; /* vanilla signal models, nModelsV * CP_VMODEL_STRIDE (on the device only, as `models`) */
+    std::vector<double> mToYV; /* per vanilla model: its m_to_y_not_x (header entry 0), which log a_my and log a_mm of
+                                  the skip bins depend on (cpecan_hip_modelsv_set_skip_probs) */
     DevBuf<double> models4; /* 4-state signal models: strawMan tables whose header holds eleven transitions */
     std::vector<double> hostModels4;
     int nModels4 = 0;
-    std::vector<double> hostModelsV;
     int nModelsV = 0;
     DevBuf<double> modelsE; /* echelon signal models, nModelsE * CP_EMODEL_STRIDE */
     std::vector<double> hostModelsE;
@@ -711,6 +712,17 @@ static int grow_models(cpecan_ctx *c, int32_t n, double **fresh) {
     return CPECAN_OK;
 }
 
+/* the context's pinned staging slots (cpecan_hip_models_create, cpecan_hip_modelsv_create), at least `want` bytes */
+static int pinned_slots(cpecan_ctx *c, size_t want) {
+    if (c->pinnedBytes >= want) return CPECAN_OK;
+    if (c->pinned) (void) hipHostFree(c->pinned);
+    c->pinned = nullptr;
+    c->pinnedBytes = 0;
+    HIP_TRY(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
+    c->pinnedBytes = want;
+    return CPECAN_OK;
+}
+
 int cpecan_hip_models_create(cpecan_ctx *c, const cpecan_sm3_model *models, int32_t n,
                              int32_t threads, int32_t *ids) {
     if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
@@ -727,13 +739,8 @@ int cpecan_hip_models_create(cpecan_ctx *c, const cpecan_sm3_model *models, int3
     /* every host thread derives a model into one of its two pinned slots and sends it on its way; the slot is
      * written again once its copy has gone (no host copy of the whole table exists at any time) */
     const size_t slotBytes = CP_MODEL_STRIDE * sizeof(double), want = slotBytes * 2 * (size_t) nt;
-    if (c->pinnedBytes < want) {
-        if (c->pinned) (void) hipHostFree(c->pinned);
-        c->pinned = nullptr;
-        c->pinnedBytes = 0;
-        HIP_TRY(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-        c->pinnedBytes = want;
-    }
+    rc = pinned_slots(c, want);
+    if (rc != CPECAN_OK) return rc;
     std::vector<hipEvent_t> gone(2 * (size_t) nt, nullptr);
     for (auto &ev : gone) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     lap("device table, pinned slots");
@@ -935,6 +942,22 @@ static double echelon_duration(const double *event, int n) {
 /* Device block of one vanilla model.  Every log() the reference takes per cell
  * (stateMachine3Vanilla_cellCalculate :1391-1407, logGaussPdf :338, logInvGaussPdf :328) depends on the
  * skip bin or the k-mer only: taken here once, with the host libm the reference would call. */
+static void derive_vanilla_bins(double m_to_y_not_x, const double *skip_probs, double *bins /* 30 x 5 */) {
+    for (int bin = 0; bin < 30; bin++) {
+        const double a_mx = skip_probs[bin];
+        const double a_my = (1 - a_mx) * m_to_y_not_x;
+        const double a_mm = 1.0f - a_my - a_mx;
+        const double a_xx = skip_probs[bin + 30];
+        const double a_xm = 1.0f - a_xx;
+        double *b = bins + bin * 5;
+        b[0] = log(a_mx);
+        b[1] = log(a_xx);
+        b[2] = log(a_mm);
+        b[3] = log(a_xm);
+        b[4] = log(a_my);
+    }
+}
+
 static void derive_vanilla(const cpecan_vanilla_model *m, double *dst) {
     for (int i = 0; i < CP_VHDR; i++) dst[i] = 0.0;
     dst[0] = m->m_to_y_not_x;
@@ -945,19 +968,7 @@ static void derive_vanilla(const cpecan_vanilla_model *m, double *dst) {
     const double a_yy = m->e_to_e, a_ym = 1.0f - a_yy;
     dst[CP_VHDR_LOG_YY] = log(a_yy);
     dst[CP_VHDR_LOG_YM] = log(a_ym);
-    for (int bin = 0; bin < 30; bin++) {
-        const double a_mx = m->skip_probs[bin];
-        const double a_my = (1 - a_mx) * m->m_to_y_not_x;
-        const double a_mm = 1.0f - a_my - a_mx;
-        const double a_xx = m->skip_probs[bin + 30];
-        const double a_xm = 1.0f - a_xx;
-        double *b = dst + CP_VHDR_BINS + bin * 5;
-        b[0] = log(a_mx);
-        b[1] = log(a_xx);
-        b[2] = log(a_mm);
-        b[3] = log(a_xm);
-        b[4] = log(a_my);
-    }
+    derive_vanilla_bins(m->m_to_y_not_x, m->skip_probs, dst + CP_VHDR_BINS);
     const double c = -0.91893853320467267;
     double *rows = dst + CP_VHDR;
     for (int k = 0; k <= CPECAN_NUM_KMERS; k++) {
@@ -980,6 +991,25 @@ static void derive_vanilla(const cpecan_vanilla_model *m, double *dst) {
     }
 }
 
+/* Room for n more vanilla models at the end of the device table, as grow_models does for the strawMan table: a new
+ * block, the old rows copied across on the device (no host mirror of the tables is kept).  *fresh receives the device
+ * address of the first new model. */
+static int grow_models_v(cpecan_ctx *c, int32_t n, double **fresh) {
+    const size_t old = (size_t) c->nModelsV * CP_VMODEL_STRIDE, total = old + (size_t) n * CP_VMODEL_STRIDE;
+    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
+    DevBuf<double> grown;
+    hipError_t e = grown.alloc(total);
+    if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
+    {
+        StreamFence fence{ c->prep, nullptr };
+        /* on the stream the uploads that follow use, and over before the old block is released */
+        if (old) HIP_TRY(hipMemcpyAsync(grown.p, c->modelsV.p, old * sizeof(double), hipMemcpyDeviceToDevice, c->prep));
+    }
+    grown.swap(c->modelsV);
+    *fresh = c->modelsV.p + old;
+    return CPECAN_OK;
+}
+
 int cpecan_hip_modelsv_create(cpecan_ctx *c, const cpecan_vanilla_model *models, int32_t n, int32_t threads,
                               int32_t *ids) {
     if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
@@ -987,24 +1017,205 @@ int cpecan_hip_modelsv_create(cpecan_ctx *c, const cpecan_vanilla_model *models,
         if (!models[i].match_probs || !models[i].skip_probs || !models[i].gap_y_probs)
             return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
     HIP_TRY(hipSetDevice(c->device));
-    const size_t old = c->hostModelsV.size();
-    c->hostModelsV.resize(old + (size_t) n * CP_VMODEL_STRIDE);
+    Lap lap("modelsv_create");
+    int nt = threads > 0 ? threads : host_threads();
+    nt = std::max(1, std::min(nt, (int) n));
+    double *fresh = nullptr;
+    int rc = grow_models_v(c, n, &fresh);
+    if (rc != CPECAN_OK) return rc;
+    /* as cpecan_hip_models_create: every host thread derives models into one of its two pinned slots and sends the
+     * slot on its way; the slot is written again once its copy has gone.  A slot holds up to four neighbouring models:
+     * the copy engine's cost per copy is that of a block's transfer, so one copy per model would double the upload */
+    const int per = std::max(1, std::min(4, (int) n / (2 * nt)));
+    const size_t blockBytes = CP_VMODEL_STRIDE * sizeof(double), slotBytes = blockBytes * (size_t) per;
+    rc = pinned_slots(c, slotBytes * 2 * (size_t) nt);
+    if (rc != CPECAN_OK) return rc;
+    std::vector<hipEvent_t> gone(2 * (size_t) nt, nullptr);
+    for (auto &ev : gone) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    lap("device table, pinned slots");
+    std::atomic<int> bad{0};
+    std::vector<std::thread> pool;
+    for (int w = 0; w < nt; w++)
+        pool.emplace_back([&, w]() {
+            if (hipSetDevice(c->device) != hipSuccess) { bad = 1; return; }
+            int turn = 0;
+            for (int i = w * per; i < n; i += nt * per, turn++) {
+                const size_t slot = 2 * (size_t) w + (turn & 1);
+                double *dst = (double *) ((char *) c->pinned + slot * slotBytes);
+                const int m = std::min(per, (int) n - i); /* models of this slot */
+                if (turn >= 2 && hipEventSynchronize(gone[slot]) != hipSuccess) { bad = 1; return; }
+                for (int j = 0; j < m; j++) derive_vanilla(&models[i + j], dst + (size_t) j * CP_VMODEL_STRIDE);
+                if (hipMemcpyAsync(fresh + (size_t) i * CP_VMODEL_STRIDE, dst, blockBytes * (size_t) m, hipMemcpyHostToDevice, c->prep) != hipSuccess ||
+                    hipEventRecord(gone[slot], c->prep) != hipSuccess) { bad = 1; return; }
+            }
+        });
+    for (auto &t : pool) t.join();
+    hipError_t se = hipStreamSynchronize(c->prep);
+    for (auto &ev : gone) (void) hipEventDestroy(ev);
+    if (bad || se != hipSuccess) {
+        c->modelsV.release(); /* the table is in an unknown state: the context's vanilla models are gone */
+        c->mToYV.clear();
+        c->nModelsV = 0;
+        c->modelEpoch++;
+        return fail(CPECAN_EHIP, "model table upload failed: %s", hipGetErrorString(se != hipSuccess ? se : hipGetLastError()));
+    }
+    lap("derive blocks (threads) || upload");
+    for (int i = 0; i < n; i++) {
+        ids[i] = c->nModelsV + i;
+        c->mToYV.push_back(models[i].m_to_y_not_x);
+    }
+    c->nModelsV += n;
+    return CPECAN_OK;
+}
+
+/* Two neighbouring elements of one read's vanilla block from the base model's block, the read's scaling parameters
+ * (emissions_signal_scaleModel impl/stateMachine.c:631-651, which rewrites the match table only) and the two values
+ * per k-mer the host took with its libm (K and log lambda of the scaled match row): header, the extra-event half of
+ * every row and the "not a k-mer" row are the base's; every other entry is one IEEE multiply or add, rounded as on the
+ * host.  An element pair never straddles a row half (header, row and half are even), and a block starts on 16 bytes. */
+extern "C" __global__ void cpecan_k_scale_models_v(const double *base, const double *scalings /* n x 5 */,
+                                                   const double *hostPart /* n x 4096 x 2 */, int n, double *out) {
+    const long long e = 2 * ((long long) blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= CP_VMODEL_STRIDE) return;
+    const double2 b = *(const double2 *) (base + e);
+    const long long r = e - CP_VHDR;
+    const int k = r >= 0 ? (int) (r / CP_VROW) : -1, j = r >= 0 ? (int) (r % CP_VROW) : -1;
+    const bool plain = k < 0 || k >= CPECAN_NUM_KMERS || j >= 6;
+    for (int m = blockIdx.y; m < n; m += gridDim.y) {
+        double2 v = b;
+        if (!plain) {
+            const double *sc = scalings + 5 * (long long) m;
+            const double *h = hostPart + ((long long) m * CPECAN_NUM_KMERS + k) * 2;
+            if (j == CP_V_MU) { /* level mean, level sd */
+                v.x = __dadd_rn(__dmul_rn(b.x, sc[0]), sc[1]);
+                v.y = __dmul_rn(b.y, sc[2]);
+            } else if (j == CP_V_K) { /* K, noise mean */
+                v.x = h[0];
+                v.y = __dmul_rn(b.y, sc[3]);
+            } else { /* noise lambda and its log */
+                v.x = __dmul_rn(b.x, sc[4]);
+                v.y = h[1];
+            }
+        }
+        *(double2 *) (out + (long long) m * CP_VMODEL_STRIDE + e) = v;
+    }
+}
+
+int cpecan_hip_modelsv_create_scaled(cpecan_ctx *c, const cpecan_vanilla_model *base, const cpecan_read_scaling *scalings,
+                                     int32_t n, int32_t threads, int32_t *ids) {
+    if (!c || !base || !scalings || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
+    if (!base->match_probs || !base->skip_probs || !base->gap_y_probs) return fail(CPECAN_EINVAL, "the base model has a NULL table");
+    HIP_TRY(hipSetDevice(c->device));
+    Lap lap("modelsv_create_scaled");
+    static_assert(CP_VHDR % 2 == 0 && CP_VROW % 2 == 0 && CP_V_MU == 0 && CP_V_K == 2 && CP_V_LAMBDA == 4,
+                  "cpecan_k_scale_models_v writes a block as pairs of doubles");
+    std::vector<double> baseBlock(CP_VMODEL_STRIDE);
+    derive_vanilla(base, baseBlock.data());
+    PinnedBuf<double> part; /* (recycled pinned memory: no page faults, and the copy engine reads it directly) */
+    HIP_TRY(part.alloc((size_t) n * CPECAN_NUM_KMERS * 2));
     int nt = threads > 0 ? threads : host_threads();
     nt = std::max(1, std::min(nt, (int) n));
     std::vector<std::thread> pool;
     for (int w = 0; w < nt; w++)
         pool.emplace_back([&, w]() {
-            for (int i = w; i < n; i += nt)
-                derive_vanilla(&models[i], c->hostModelsV.data() + old + (size_t) i * CP_VMODEL_STRIDE);
+            const double lg = -0.91893853320467267;
+            for (int i = w; i < n; i += nt) {
+                const cpecan_read_scaling &s = scalings[i];
+                double *dst = part.p + (size_t) i * CPECAN_NUM_KMERS * 2;
+                for (int k = 0; k < CPECAN_NUM_KMERS; k++) { /* what derive_vanilla takes of the scaled match row */
+                    const double *a = base->match_probs + 1 + (size_t) k * CPECAN_MODEL_PARAMS;
+                    const double sd = a[1] * s.var, lambda = a[4] * s.var_sd;
+                    dst[2 * k] = sd == 0.0 ? -INFINITY : lg - log(sd);
+                    dst[2 * k + 1] = log(lambda);
+                }
+            }
         });
     for (auto &t : pool) t.join();
-    for (int i = 0; i < n; i++) ids[i] = c->nModelsV + i;
+    lap("host libm part (threads)");
+    double *fresh = nullptr;
+    int rc = grow_models_v(c, n, &fresh);
+    if (rc != CPECAN_OK) return rc;
+    DevBuf<double> dBase, dScal, dPart;
+    StreamFence fence{ c->prep, nullptr };
+    HIP_TRY(dBase.alloc(baseBlock.size()));
+    HIP_TRY(dScal.alloc((size_t) n * 5));
+    HIP_TRY(dPart.alloc(part.n));
+    lap("device table");
+    HIP_TRY(hipMemcpyAsync(dBase.p, baseBlock.data(), baseBlock.size() * sizeof(double), hipMemcpyHostToDevice, c->prep));
+    HIP_TRY(hipMemcpyAsync(dScal.p, scalings, (size_t) n * 5 * sizeof(double), hipMemcpyHostToDevice, c->prep));
+    HIP_TRY(hipMemcpyAsync(dPart.p, part.p, part.n * sizeof(double), hipMemcpyHostToDevice, c->prep));
+    hipLaunchKernelGGL(cpecan_k_scale_models_v, dim3((unsigned) ((CP_VMODEL_STRIDE / 2 + 255) / 256), (unsigned) std::min(n, 65535)),
+                       dim3(256), 0, c->prep, (const double *) dBase.p, (const double *) dScal.p, (const double *) dPart.p,
+                       (int) n, fresh);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->prep)); /* the staging blocks are released on return */
+    lap("upload + assemble");
+    for (int i = 0; i < n; i++) {
+        ids[i] = c->nModelsV + i;
+        c->mToYV.push_back(base->m_to_y_not_x);
+    }
     c->nModelsV += n;
-    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
-    hipError_t e = c->modelsV.alloc(c->hostModelsV.size());
-    if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
-    HIP_TRY(hipMemcpy(c->modelsV.p, c->hostModelsV.data(), c->hostModelsV.size() * sizeof(double),
-                      hipMemcpyHostToDevice));
+    return CPECAN_OK;
+}
+
+int cpecan_hip_modelsv_download(cpecan_ctx *c, int32_t id, double *out, int64_t capacity, int64_t *nDoubles) {
+    if (!c || !nDoubles) return fail(CPECAN_EINVAL, "bad argument");
+    *nDoubles = CP_VMODEL_STRIDE;
+    if (!out) return CPECAN_OK;
+    if (id < 0 || id >= c->nModelsV) return fail(CPECAN_EINVAL, "vanilla model id %d out of range (%d)", id, c->nModelsV);
+    if (capacity < CP_VMODEL_STRIDE) return fail(CPECAN_EINVAL, "capacity %lld < %d doubles", (long long) capacity, (int) CP_VMODEL_STRIDE);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(ctx_fence(c));
+    HIP_TRY(hipMemcpy(out, c->modelsV.p + (size_t) id * CP_VMODEL_STRIDE, CP_VMODEL_STRIDE * sizeof(double), hipMemcpyDeviceToHost));
+    return CPECAN_OK;
+}
+
+/* every vanilla model receives the 150 logs of the set whose fudge factor is its own (header entry 0, compared as bits) */
+extern "C" __global__ void cpecan_k_set_skip_bins(double *models, int nModels, const double *factors, int nSets,
+                                                  const double *bins /* nSets x 150 */) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 150) return;
+    for (int m = blockIdx.y; m < nModels; m += gridDim.y) { /* grid.y is capped at 65535 */
+        double *blk = models + (long long) m * CP_VMODEL_STRIDE;
+        const long long mine = __double_as_longlong(blk[0]);
+        for (int s = 0; s < nSets; s++)
+            if (__double_as_longlong(factors[s]) == mine) {
+                blk[CP_VHDR_BINS + i] = bins[s * 150 + i];
+                break;
+            }
+    }
+}
+
+int cpecan_hip_modelsv_set_skip_probs(cpecan_ctx *c, const double *skipProbs) {
+    if (!c || !skipProbs) return fail(CPECAN_EINVAL, "bad argument");
+    if (c->nModelsV <= 0) return fail(CPECAN_EINVAL, "the context holds no vanilla models");
+    HIP_TRY(hipSetDevice(c->device));
+    /* log a_my and log a_mm depend on the model's m_to_y_not_x: one set of 150 logs per distinct value, taken by the
+     * code derive_vanilla runs */
+    std::vector<double> v; /* [factors: nSets | bins: nSets x 150] once the sets are known */
+    std::vector<double> factors;
+    for (double f : c->mToYV) {
+        bool seen = false;
+        for (double g : factors) seen = seen || memcmp(&f, &g, sizeof f) == 0;
+        if (!seen) factors.push_back(f);
+    }
+    const size_t nSets = factors.size();
+    v.assign(nSets * 151, 0.0);
+    for (size_t s = 0; s < nSets; s++) {
+        v[s] = factors[s];
+        derive_vanilla_bins(factors[s], skipProbs, v.data() + nSets + s * 150);
+    }
+    /* the tables are written in place: every run that reads them is over first (on whatever lanes it went); the
+     * update goes through the context's own prep stream, which no other context's run shares */
+    HIP_TRY(ctx_fence(c));
+    DevBuf<double> dv;
+    StreamFence fence{ c->prep, nullptr };
+    HIP_TRY(dv.alloc(v.size()));
+    HIP_TRY(hipMemcpyAsync(dv.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->prep));
+    hipLaunchKernelGGL(cpecan_k_set_skip_bins, dim3(1, (unsigned) std::min(c->nModelsV, 65535)), dim3(192), 0, c->prep,
+                       c->modelsV.p, c->nModelsV, (const double *) dv.p, (int) nSets, (const double *) (dv.p + nSets));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->prep)); /* dv is released on return */
     return CPECAN_OK;
 }
 
@@ -1167,7 +1378,7 @@ int cpecan_hip_models_clear(cpecan_ctx *c) {
     c->hostModels5.clear();
     c->nModels5 = 0;
     c->modelsV.release();
-    c->hostModelsV.clear();
+    c->mToYV.clear();
     c->nModelsV = 0;
     c->models4.release();
     c->hostModels4.clear();

@@ -1,4 +1,5 @@
-"""Baum-Welch loop for the strawMan signal machine on one or several GPUs (one process per GPU).
+"""Baum-Welch loop for the strawMan signal machine on one or several GPUs (one process per GPU), and the persistent
+E-step of the vanilla signal machine (PersistentVanillaEStep).
 
 Mirrors the loop of the reference's trainer (scripts/trainModels.py:244-330; cPecanEm.py:107-209 for the
 discrete machine): per iteration every worker computes expectations for its reads with the current model,
@@ -170,6 +171,63 @@ class PersistentEStep:
             b.sync()
             ptr, n = b.expectations_device_ptr()
             total += torch.as_tensor(_DeviceDoubles(ptr, n), device=self.dev).view(-1, EXP_LEN).sum(0)
+        torch.cuda.synchronize(self.dev)
+        allreduce_expectations(total, self.dist)
+        return total.cpu().numpy()
+
+    def close(self):
+        for _, b in self.batches:
+            b.close()
+        self.batches = []
+
+
+EXPV_LEN = 60 + 1
+
+
+class PersistentVanillaEStep:
+    """The persistent E-step for the vanilla signal machine (VanillaHmm, impl/continuousHmm.c:373-466): inputs, band
+    tables, rings and the per-read tables are set up ONCE -- the tables scaled on the device from one base model per
+    strand (cpecan_hip_modelsv_create_scaled, one call per strand) -- and an iteration rewrites the skip bins of every
+    model in place (cpecan_hip_modelsv_set_skip_probs), runs the batches again, sums the 61-double blocks
+    [30 beta | 30 alpha | likelihood] of all models in HBM and all-reduces them.  The M-step stays the caller's.
+
+    contexts: one or two binding.Context on the same device (two: the reads are dealt into two batches that run
+    concurrently); batch: tests/synth.make_batch layout, `scalings` [n_reads, 5] included; bases: per strand
+    (scalars[5], match[20481], skip[60], gap_y[20481]) of the unscaled model; strand_of[i]: the strand of read i."""
+
+    def __init__(self, cp, contexts, batch, bp, read_idx, bases, strand_of, dist=None, flags=0):
+        import torch
+        self.cp, self.ctxs, self.dist = cp, list(contexts), dist
+        self.dev = torch.device("cuda", self.ctxs[0].device)
+        self.batches = []
+        for k, cx in enumerate(self.ctxs):
+            part = list(read_idx)[k::len(self.ctxs)]
+            if not part:
+                continue
+            cx.models_clear()
+            items = np.zeros(len(part), cp.ITEM_DTYPE)
+            for s, base in enumerate(bases):
+                mine = [j for j, i in enumerate(part) if strand_of[i] == s]
+                if not mine:
+                    continue
+                ids = cx.modelsv_create_scaled(base, [batch["scalings"][part[j]] for j in mine])
+                for j, mid in zip(mine, ids):
+                    it = batch["items"][part[j]]
+                    items[j] = (it["x_offset"], it["lX"], it["y_offset"], it["lY"], it["anchor_offset"],
+                                it["n_anchors"], mid, 1, 1, 0)
+            self.batches.append((cx, cp.Batch(cx, items, batch["x_chars"], batch["events"], batch["anchors"], bp,
+                                              flags=cp.FLAG_EXPECTATIONS | flags, vanilla=True)))
+
+    def __call__(self, skip_probs):
+        import torch
+        total = torch.zeros(EXPV_LEN, dtype=torch.float64, device=self.dev)
+        for cx, b in self.batches:
+            cx.modelsv_set_skip_probs(skip_probs)
+            b.run()
+        for _, b in self.batches:
+            b.sync()
+            ptr, n = b.expectations_device_ptr()
+            total += torch.as_tensor(_DeviceDoubles(ptr, n), device=self.dev).view(-1, EXPV_LEN).sum(0)
         torch.cuda.synchronize(self.dev)
         allreduce_expectations(total, self.dist)
         return total.cpu().numpy()

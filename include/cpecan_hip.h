@@ -129,6 +129,31 @@ typedef struct {
 } cpecan_vanilla_model;
 int cpecan_hip_modelsv_create(cpecan_ctx *ctx, const cpecan_vanilla_model *models, int32_t n,
                               int32_t threads, int32_t *ids);
+/* The same for n reads of one strand: `base` holds the strand's unscaled tables, fudge factors and end values, and the
+ * reads differ by their scaling parameters only.  emissions_signal_scaleModel (impl/stateMachine.c:631-651) rewrites
+ * the match table alone (level_mean * scale + shift, level_sd * var, noise_mean * scale_sd, noise_lambda * var_sd; the
+ * noise sd it also rewrites is not part of a vanilla row), so the host takes only what needs its libm, in the
+ * reference's order of evaluation -- log(level_sd * var) and log(noise_lambda * var_sd), two doubles per k-mer and
+ * read, spread over `threads` OS threads -- and the device assembles the blocks: header, extra-event half of every row
+ * and the "not a k-mer" row from the base block, the match half with single IEEE operations.  The resulting device
+ * blocks are bit-identical to cpecan_hip_modelsv_create on the n host-scaled tables
+ * (tests/test_vanilla_scaled_models_gpu.py), at a sixth of the upload.  The vanilla table lives on the device only: both
+ * entry points append to it there (a table that grows is copied device to device), ids count up across the two. */
+int cpecan_hip_modelsv_create_scaled(cpecan_ctx *ctx, const cpecan_vanilla_model *base, const cpecan_read_scaling *scalings,
+                                     int32_t n, int32_t threads, int32_t *ids);
+/* Test aid: copies the derived device block of vanilla model `id` to out (n_doubles receives its length; out may be
+ * NULL to query the length only). */
+int cpecan_hip_modelsv_download(cpecan_ctx *ctx, int32_t id, double *out, int64_t capacity, int64_t *n_doubles);
+/* The M-step of this machine changes the 60 skip-bin values only (vanillaHmm_loadKmerSkipBinExpectations,
+ * impl/continuousHmm.c); the per-read scaled rows stay.  Rewrites, in every vanilla model of the context and in place,
+ * the 30 x 5 log transition probabilities derived from them.  log a_my and log a_mm depend on the model's own
+ * m_to_y_not_x, which differs between strands: the host takes the 150 logs once per distinct value with its libm, as
+ * the create calls do, and every model receives the set that belongs to its header.  Every run that reads the tables
+ * is over before they are written, and the write is over when the call returns.  Batches created on the context
+ * before the call can simply be run again for the next iteration -- no table derivation, no upload: the wave
+ * kernels' track, which carries the bin's five logs per column, is rebuilt from the context's current table at every
+ * run, and the general kernel reads the table itself. */
+int cpecan_hip_modelsv_set_skip_probs(cpecan_ctx *ctx, const double *skip_probs /*[60]: beta[30] | alpha[30]*/);
 
 /* The echelon signal machine: getStateMachineEchelon() (impl/stateMachine.c:1773) after emissions_signal_scaleModel().
  * Fields as in struct _StateMachineEchelon (inc/stateMachine.h:233-246): the two end values (used as log values, as the
