@@ -32,6 +32,7 @@ FLAG_SMALL_FOOTPRINT = 64
 FLAG_EXPECTATIONS = 8
 FLAG_WORKGROUP_KERNELS = 16
 FLAG_GENERAL_KERNEL = 32
+FLAG_WIDE_BANDS = 128
 NUM_KMERS = 4096
 MODEL_TABLE_LEN = 1 + NUM_KMERS * 5
 EXPECTATION_LEN = 9 + NUM_KMERS + 1

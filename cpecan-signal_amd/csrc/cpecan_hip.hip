@@ -69,16 +69,19 @@ extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *stat
  * machine, 2 and 3 for the vanilla machine (_v: four cells per lane do not fit its register file without spilling, so
  * that build does not exist and bands above 184 k-mers run on the general kernel).  A table is indexed by the rows a
  * band of that width asks for, minus one; a one-cell-per-lane build would only serve bands below 57 k-mers, which the
- * two-cell build takes too. */
+ * two-cell build takes too.  The workgroup family's source also builds six and eight waves per workgroup (bands up to
+ * 376 and 504 k-mers): the wide builds, a table of their own, which a strawMan batch reaches only with
+ * CPECAN_FLAG_WIDE_BANDS and only when its widest band is past every build of the tables above. */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
-SWEEP_BUILD(cpecan_systolic_build)
+SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
 SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(cpecan_wave_build_l4)
 SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
 typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
+static const SweepBuild *const SY_WIDE_BUILDS[2] = { &cpecan_systolic_build_r6, &cpecan_systolic_build_r8 };
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
@@ -1457,6 +1460,12 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     if (vanilla && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
         return fail(CPECAN_EINVAL, "expectations run over the banded matrix only");
     const int S = dna ? 5 : echelon ? 7 : sm4 ? 4 : 3; /* states per cell */
+    /* the wide builds of the workgroup family are the strawMan machine's: the flag means nothing to the others
+     * (CPECAN_WIDE_BANDS=1, read per batch, sets it for every strawMan batch) */
+    const bool strawMan = !dna && !vanilla && !hdp && !sm4 && !echelon;
+    if (strawMan && getenv("CPECAN_WIDE_BANDS") != nullptr && atoi(getenv("CPECAN_WIDE_BANDS")) == 1)
+        flags |= CPECAN_FLAG_WIDE_BANDS;
+    const bool wideBands = strawMan && (flags & CPECAN_FLAG_WIDE_BANDS) != 0;
     if (!c || !items || nItems <= 0 || !xChars || (!events && !yChars) || !params || !out)
         return fail(CPECAN_EINVAL, "bad argument");
     if (dna && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "DNA batches: no cell dumps");
@@ -1691,18 +1700,25 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     const SweepFamily &fam = hdp ? HV_BUILDS : vanilla ? VV_BUILDS
                              : (use_wave_kernels() && !(flags & CPECAN_FLAG_WORKGROUP_KERNELS)) ? WV_BUILDS : SY_BUILDS;
     const int famMaxWidth = fam[3]->maxWidth;
+    /* CPECAN_FLAG_WIDE_BANDS: a band past the family's widest build goes to the six- or the eight-wave build of the
+     * workgroup family, whichever family the batch would otherwise run on; a band the family holds is left to it */
+    const SweepBuild *wideBuild = nullptr;
+    if (wideBands && globalMaxWidth > famMaxWidth)
+        for (const SweepBuild *w : SY_WIDE_BUILDS)
+            if (!wideBuild && globalMaxWidth <= w->maxWidth) wideBuild = w;
+    const int sweepMaxWidth = wideBands ? SY_WIDE_BUILDS[1]->maxWidth : famMaxWidth;
     b->dna = dna;
     b->vanilla = vanilla;
     b->hdp = hdp;
     b->sm4 = sm4;
     b->echelon = echelon;
     if (useKernel == CPECAN_KERNEL_AUTO)
-        useKernel = (globalMaxWidth <= famMaxWidth && systolicOk && !b->P.debug && !unbanded)
+        useKernel = (globalMaxWidth <= sweepMaxWidth && systolicOk && !b->P.debug && !unbanded)
                         ? CPECAN_KERNEL_SYSTOLIC : CPECAN_KERNEL_GENERAL;
     /* (refusals from here on go through cpecan_hip_batch_destroy: it takes the batch off the context's list) */
-    if (useKernel == CPECAN_KERNEL_SYSTOLIC && (globalMaxWidth > famMaxWidth || !systolicOk)) {
+    if (useKernel == CPECAN_KERNEL_SYSTOLIC && (globalMaxWidth > sweepMaxWidth || !systolicOk)) {
         const int rc = fail(CPECAN_EINVAL, "band is %d cells wide (systolic kernel: at most %d, edges moving "
-                            "one k-mer per diagonal)", globalMaxWidth, famMaxWidth);
+                            "one k-mer per diagonal)", globalMaxWidth, sweepMaxWidth);
         cpecan_hip_batch_destroy(b);
         return rc;
     }
@@ -1715,7 +1731,10 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     b->maxWidth = globalMaxWidth;
     /* the build with the fewest waves per workgroup whose slots hold the widest band: the fewer waves an alignment
      * takes, the more alignments a CU holds (CPECAN_SYSTOLIC_ROWS=N asks for at least N waves: tests, timing) */
-    {
+    if (wideBuild && useKernel == CPECAN_KERNEL_SYSTOLIC) {
+        b->sy = wideBuild;
+        b->trackRow = b->sy->once->trackRowDoubles;
+    } else {
         const char *rows = getenv("CPECAN_SYSTOLIC_ROWS");
         int r = rows ? atoi(rows) : 1;
         r = r < 1 ? 1 : r > 4 ? 4 : r;

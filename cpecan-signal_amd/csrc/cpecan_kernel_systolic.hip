@@ -3,8 +3,8 @@
  * with the anti-diagonal wavefront of the recurrence held in registers.
  *
  * Mapping (designed for CDNA4's 64-lane waves, not translated from anything):
- *   - one 256-thread workgroup per alignment; lanes own reference k-mers, not DP cells: slot
- *     s = x mod 256 is lane s % 64 of wave s / 64 (bands up to 248 k-mers wide).  A k-mer's 17
+ *   - one workgroup of SY_R waves per alignment (256 threads in the four-wave build); lanes own reference k-mers,
+ *     not DP cells: slot s = x mod 64*SY_R is lane s % 64 of wave s / 64 (bands up to 64*SY_R - 8 k-mers wide).  A k-mer's 17
  *     emission constants stay in its lane's VGPRs while x is inside the band.
  *   - one loop iteration = one anti-diagonal.  Forward: a cell needs (x-1,y) and (x-1,y-1) from the
  *     lane below (one DPP wave-shift per value) and (x,y-1) from itself; only lane 0 of a wave
@@ -38,19 +38,27 @@
 #define SY_R 4 /* waves per workgroup: 4 (bands up to 248 k-mers) or 3 (up to 184; five workgroups fit a CU) */
 #endif
 #define SY_P (64 * SY_R)
-/* this file is compiled once per SY_R (1..4 waves per workgroup: bands up to 56, 120, 184, 248 k-mers); the symbols
- * of the builds below four carry _r1.._r3, and the pieces that do not depend on SY_R (track, counts, division
- * self-test) exist in the four-wave build only */
+/* this file is compiled once per SY_R (1..4 waves per workgroup: bands up to 56, 120, 184, 248 k-mers; 6 and 8 waves,
+ * the wide builds of CPECAN_FLAG_WIDE_BANDS: 376 and 504); the symbols of the builds other than four carry _r1.._r3,
+ * _r6, _r8, and the pieces that do not depend on SY_R (track, counts, division self-test) exist in the four-wave build
+ * only */
 #if SY_R == 4
 #define SY_SYM(n) n
+#elif SY_R == 8
+#define SY_SYM(n) n##_r8
+#elif SY_R == 6
+#define SY_SYM(n) n##_r6
 #elif SY_R == 3
 #define SY_SYM(n) n##_r3
 #elif SY_R == 2
 #define SY_SYM(n) n##_r2
-#else
+#elif SY_R == 1
 #define SY_SYM(n) n##_r1
+#else
+#error "SY_R: 1, 2, 3, 4, 6 or 8 waves per workgroup"
 #endif
-#if SY_R == 1 /* the one-wave backward kernel lands on 129 VGPRs by itself: hold it to four waves per SIMD */
+#if SY_R == 1 || SY_R == 8 /* the one-wave and the eight-wave backward kernel land on 129 VGPRs by themselves: hold
+                            * them to four waves per SIMD (128; two eight-wave workgroups then share a CU) */
 #define SY_BACKWARD_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #else
 #ifdef SY_FORCE_WAVES
@@ -59,9 +67,9 @@
 #define SY_BACKWARD_ATTR
 #endif
 #endif
-#if SY_R == 4
-#define SY_WAVE_OF(x) (((x) >> 6) & 3) /* the wave that owns k-mer x (x >= 0) */
-#define SY_WMOD(v) ((v) & 3)           /* a difference of wave indices, any sign, into 0..SY_R-1 */
+#if SY_R == 4 || SY_R == 8 /* a power of two: masks */
+#define SY_WAVE_OF(x) (((x) >> 6) & (SY_R - 1)) /* the wave that owns k-mer x (x >= 0) */
+#define SY_WMOD(v) ((v) & (SY_R - 1))           /* a difference of wave indices, any sign, into 0..SY_R-1 */
 #define SY_SLOT(x) ((x) & (SY_P - 1))
 #else
 #define SY_WAVE_OF(x) (((x) >> 6) % SY_R)
@@ -75,10 +83,21 @@
 #define SY_DECODE_U 2     /* diagonals per batch of the posterior decode */
 #define SY_EXPECT_CHUNKS 8 /* workgroups that share one window's diagonals in the expectation pass */
 #define SY_RING_VALUES 5 /* per cell in the forward ring: Fm, Fx, Fy, match emission, gap-Y emission */
+/* hit masks (one per wave) the decode keeps per diagonal in scratch: a power of two, so that a lane finds its
+ * (diagonal, wave) by shift and mask -- four whatever SY_R is up to four waves, eight for the wide builds */
+#if SY_R <= 4
+#define SY_MSK_SHIFT 2
+#else
+#define SY_MSK_SHIFT 3
+#endif
+#define SY_MSK (1 << SY_MSK_SHIFT)
 
 #ifdef SY_PROFILE
-/* timing build only: cycles per section of the forward step, summed over all waves */
-__device__ unsigned long long SY_SYM(sy_prof)[80];
+/* timing build only: cycles per section of the forward step, summed over all waves (16 counters per wave), then the
+ * 16 counters of the sweep back: 80 in all up to four waves, 16 * SY_R + 16 in the wide builds */
+#define SY_PROF_B (16 * (SY_R > 4 ? SY_R : 4))
+#define SY_PROF_N (SY_PROF_B + 16)
+__device__ unsigned long long SY_SYM(sy_prof)[SY_PROF_N];
 #define sy_prof SY_SYM(sy_prof)
 #define PROF_DECL unsigned long long prof_[12] = {0,0,0,0,0,0,0,0,0,0,0,0}, tprev_ = __builtin_readcyclecounter(); bool pact_ = false;
 #define PROF(k) { const unsigned long long now_ = __builtin_readcyclecounter(); if (pact_) prof_[k] += now_ - tprev_; else prof_[9] += now_ - tprev_; tprev_ = now_; }
@@ -86,7 +105,7 @@ __device__ unsigned long long SY_SYM(sy_prof)[80];
 #define PROF_FENCE(x) asm volatile("" : "+v"(x));
 #define BPROF_DECL unsigned long long bt_[9]; for (int k_ = 0; k_ < 9; k_++) bt_[k_] = 0; bt_[0] = __builtin_readcyclecounter(); const unsigned long long rt0_ = __builtin_amdgcn_s_memrealtime();
 #define BPROF(k) bt_[k] = __builtin_readcyclecounter();
-#define BPROF_FLUSH if (threadIdx.x == 0) { for (int k_ = 0; k_ < 8; k_++) atomicAdd(&sy_prof[64 + k_], bt_[k_ + 1] - bt_[k_]); atomicMax(&sy_prof[75], bt_[8] - bt_[0]); { const unsigned long long rd_ = __builtin_amdgcn_s_memrealtime() - rt0_; atomicAdd(&sy_prof[76], rd_); atomicMax(&sy_prof[77], rd_); } atomicAdd(&sy_prof[72], 1ull); atomicAdd(&sy_prof[73], (unsigned long long) (sh.scan != 0)); atomicAdd(&sy_prof[74], (unsigned long long) (sh.cnt[1][0][0] + sh.cnt[1][1][0] + sh.cnt[1][2][0] + sh.cnt[1][SY_R - 1][0])); }
+#define BPROF_FLUSH if (threadIdx.x == 0) { for (int k_ = 0; k_ < 8; k_++) atomicAdd(&sy_prof[SY_PROF_B + k_], bt_[k_ + 1] - bt_[k_]); atomicMax(&sy_prof[SY_PROF_B + 11], bt_[8] - bt_[0]); { const unsigned long long rd_ = __builtin_amdgcn_s_memrealtime() - rt0_; atomicAdd(&sy_prof[SY_PROF_B + 12], rd_); atomicMax(&sy_prof[SY_PROF_B + 13], rd_); } atomicAdd(&sy_prof[SY_PROF_B + 8], 1ull); atomicAdd(&sy_prof[SY_PROF_B + 9], (unsigned long long) (sh.scan != 0)); { int nc_ = 0; for (int w_ = 0; w_ < SY_R; w_++) nc_ += sh.cnt[1][w_][0]; atomicAdd(&sy_prof[SY_PROF_B + 10], (unsigned long long) nc_); } }
 #define PROF_FLUSH(wave) if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < 12; k_++) atomicAdd(&sy_prof[(wave) * 16 + k_], prof_[k_]); }
 #else
 #define PROF_DECL
@@ -229,7 +248,7 @@ __device__ __forceinline__ double lgauss(double x, double mu, double sd, double 
 struct BandFeed {
     int2 e[SY_BAND_RING];
 };
-/* entries of diagonals lo..hi (clipped to 0..D) into the ring; all 256 threads */
+/* entries of diagonals lo..hi (clipped to 0..D) into the ring; the whole workgroup */
 __device__ __forceinline__ void band_stage(BandFeed &bf, const int2 *__restrict__ tab, int D, int lo, int hi) {
     for (int d = lo + (int) threadIdx.x; d <= hi; d += SY_P)
         if (d >= 0 && d <= D) bf.e[d & (SY_BAND_RING - 1)] = tab[d];
@@ -335,7 +354,7 @@ __device__ __forceinline__ Geometry make_geometry(double *ring, int ringD) {
 }
 
 /* The next traceback point (:917-921) from the band alone: the first diagonal above dAfter that is at
- * least dMin and narrow enough, or the last diagonal D.  Whole workgroup, 256 diagonals per round. */
+ * least dMin and narrow enough, or the last diagonal D.  Whole workgroup, SY_P diagonals per round. */
 __device__ int next_traceback_point(const int2 *__restrict__ tab, int D, int dAfter, long long dMin,
                                     long long widthLimit, Shared &sh) {
     long long b0 = dAfter + 1 > dMin ? dAfter + 1 : dMin;
@@ -751,7 +770,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             }
             const bool vt = xs >= bxmin;
             const double fMc = vt ? qF : CP_NEG_INF, pmc = vt ? qPm : 0.0, pyc = vt ? qPy : 0.0;
-            /* the slot's k-mer SY_PREFETCH diagonals down is xs or out of band (bands <= 256 - depth) */
+            /* the slot's k-mer SY_PREFETCH diagonals down is xs or out of band (bands <= SY_P - 2 * depth) */
             fetch(t - SY_PREFETCH, xs >= bxmin - SY_PREFETCH, qF, qPm, qPy);
             if (t < dTop) {
                 lds_barrier();
@@ -968,7 +987,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
      *   pass 0  marks the hits: one 64-bit lane mask per (diagonal, wave) to scratch;
      *   prefix  hits per diagonal -> exclusive offsets in emission order (diagonals descending);
      *   pass 1  re-reads only the hit lanes, ranks each hit inside its diagonal by k-mer index
-     *           (the reference's x-y order) from the four masks, and writes the triples.
+     *           (the reference's x-y order) from the diagonal's masks, and writes the triples.
      */
     if (P.mode == 0 && nPost > 0) {
         int *const off = cntBuf;
@@ -983,9 +1002,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             return __hip_atomic_load(msk + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         };
         auto hits_of = [&](const int k) __attribute__((always_inline)) {
-            int n = 0; /* masks are kept four to a diagonal whatever SY_R is */
+            int n = 0; /* masks are kept SY_MSK to a diagonal */
 #pragma unroll
-            for (int w2 = 0; w2 < SY_R; w2++) n += __popcll(ld_msk(k * 4ll + w2));
+            for (int w2 = 0; w2 < SY_R; w2++) n += __popcll(ld_msk(k * (long long) SY_MSK + w2));
             return n;
         };
         auto prefix = [&]() __attribute__((always_inline)) {
@@ -1002,7 +1021,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                         h[j] = b0 + j < nPost ? hits_of(b0 + j) : 0;
                         sum += h[j];
                     }
-                    /* exclusive scan over the 256 threads: shuffles inside a wave, LDS across the four */
+                    /* exclusive scan over the workgroup's threads: shuffles inside a wave, LDS across the waves */
                     int inc = sum;
 #pragma unroll
                     for (int o2 = 1; o2 < 64; o2 <<= 1) {
@@ -1040,7 +1059,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
              * with the per-diagonal offsets known, each hit is ranked inside its diagonal and written.
              */
             const int nC = sh.cnt[1][wave][0];
-            for (int i = threadIdx.x; i < nPost * 4; i += SY_P) msk[i] = 0ull;
+            for (int i = threadIdx.x; i < nPost * SY_MSK; i += SY_P) msk[i] = 0ull;
             __syncthreads();
             for (int pass = 0; pass < 2; pass++) {
 #pragma unroll 1
@@ -1052,18 +1071,18 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     double p = exp(ee);
                     if (!(p >= P.threshold)) continue;
                     if (!pass) {
-                        atomicOr(msk + k * 4ll + wave, 1ull << (x & 63));
+                        atomicOr(msk + k * (long long) SY_MSK + wave, 1ull << (x & 63));
                         continue;
                     }
                     /* rank inside the diagonal, as in the scan below */
                     const int xmin = bandTab[t].x;
                     const int W0 = SY_WAVE_OF(xmin), s0 = xmin & 63, c = SY_WMOD(wave - W0);
                     const unsigned long long fromS0 = ~0ull << s0, below = (1ull << lane) - 1ull;
-                    const unsigned long long own = ld_msk(k * 4ll + wave);
+                    const unsigned long long own = ld_msk(k * (long long) SY_MSK + wave);
                     int first = 0, beforeMine = 0, others = 0;
 #pragma unroll
                     for (int w2 = 0; w2 < SY_R; w2++) {
-                        const unsigned long long m2 = ld_msk(k * 4ll + w2);
+                        const unsigned long long m2 = ld_msk(k * (long long) SY_MSK + w2);
                         const int c2 = SY_WMOD(w2 - W0);
                         if (c2 == 0) first = __popcll(m2 & fromS0);
                         else {
@@ -1103,15 +1122,15 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 if (xs > b) xs -= SY_P;
             }
             /* pass 1 works from the masks and offsets of a batch, fetched one batch ahead, one
-             * (diagonal, wave) mask per lane 0..4U-1 and one offset per lane 0..U-1 */
+             * (diagonal, wave) mask per lane 0..SY_MSK*U-1 and one offset per lane 0..U-1 */
             unsigned long long mvNext = 0ull;
             int ovNext = 0;
             /* the band of a batch's diagonals: one entry per lane 0..U-1, also a batch ahead */
             int2 bvNext = make_int2(1, 0);
             if (lane < SY_DECODE_U && lane < nPost) bvNext = bandTab[tPost0 - lane];
             if (pass) {
-                const int kk = lane >> 2;
-                if (lane < 4 * SY_DECODE_U && kk < nPost) mvNext = ld_msk(kk * 4ll + (lane & 3));
+                const int kk = lane >> SY_MSK_SHIFT;
+                if (lane < SY_MSK * SY_DECODE_U && kk < nPost) mvNext = ld_msk(kk * (long long) SY_MSK + (lane & (SY_MSK - 1)));
                 if (lane < SY_DECODE_U && lane < nPost) ovNext = off[lane];
             }
 #pragma unroll 1
@@ -1133,7 +1152,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     bool want = live && xs >= xminA[j];
                     own[j] = 0ull;
                     if (pass) {
-                        own[j] = lane64(mv, j * 4 + wave);
+                        own[j] = lane64(mv, j * SY_MSK + wave);
                         want = ((own[j] >> lane) & 1ull) != 0ull;
                     }
                     /* F.match + B.match, parked by the sweep in ring slot 3 */
@@ -1147,10 +1166,10 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     if (lane < SY_DECODE_U && ko < nPost) bvNext = bandTab[tPost0 - ko];
                 }
                 if (pass) {
-                    const int kk = k0 + SY_DECODE_U + (lane >> 2), ko = k0 + SY_DECODE_U + lane;
+                    const int kk = k0 + SY_DECODE_U + (lane >> SY_MSK_SHIFT), ko = k0 + SY_DECODE_U + lane;
                     mvNext = 0ull;
                     ovNext = 0;
-                    if (lane < 4 * SY_DECODE_U && kk < nPost) mvNext = ld_msk(kk * 4ll + (lane & 3));
+                    if (lane < SY_MSK * SY_DECODE_U && kk < nPost) mvNext = ld_msk(kk * (long long) SY_MSK + (lane & (SY_MSK - 1)));
                     if (lane < SY_DECODE_U && ko < nPost) ovNext = off[ko];
                 }
 #pragma unroll
@@ -1167,18 +1186,18 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                                 if (ok) hit = exp(ee) >= P.threshold;
                                 m = __ballot(hit);
                             }
-                            if (lane == 0) msk[k * 4 + wave] = m;
+                            if (lane == 0) msk[k * SY_MSK + wave] = m;
                         }
                     } else if (own[j] != 0ull) {
                         /* hits of this diagonal with a smaller k-mer index: the band starts in wave W0 at
-                         * lane s0 and wraps around the four waves, possibly back into W0's low lanes */
+                         * lane s0 and wraps around the waves, possibly back into W0's low lanes */
                         const int W0 = SY_WAVE_OF(xminA[j]), s0 = xminA[j] & 63;
                         const unsigned long long fromS0 = ~0ull << s0;
                         const int c = SY_WMOD(wave - W0);
                         int first = 0, beforeMine = 0, others = 0;
 #pragma unroll
                         for (int w2 = 0; w2 < SY_R; w2++) {
-                            const unsigned long long m2 = lane64(mv, j * 4 + w2);
+                            const unsigned long long m2 = lane64(mv, j * SY_MSK + w2);
                             const int c2 = SY_WMOD(w2 - W0);
                             if (c2 == 0) first = __popcll(m2 & fromS0);
                             else {
@@ -1220,7 +1239,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
 /* per-alignment scratch: [hit offsets | window totals | their terms | hit masks | candidate lists] */
 static __host__ __device__ long long scratch_cand_offset(int ringD) {
     return 2ll * ringD * sizeof(int) + ((long long) ringD / 10 + 8) * (sizeof(WinTotal) + 2 * SY_P * sizeof(double))
-           + 4ll * ringD * sizeof(unsigned long long);
+           + (long long) SY_MSK * ringD * sizeof(unsigned long long);
 }
 
 /* One workgroup per alignment: forward sweep up to its next traceback point. */
@@ -1488,7 +1507,7 @@ extern "C" int cpecan_systolic_divtest(hipStream_t stream, long long n, unsigned
 
 #ifdef SY_PROFILE
 extern "C" int SY_SYM(cpecan_systolic_prof_fetch)(unsigned long long *dst) {
-    unsigned long long zero[80] = {0};
+    unsigned long long zero[SY_PROF_N] = {0};
     if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(sy_prof), sizeof(zero)) != hipSuccess) return -1;
     return hipMemcpyToSymbol(HIP_SYMBOL(sy_prof), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
 }

@@ -225,7 +225,7 @@ typedef struct {
 
 #define CPECAN_KERNEL_AUTO 0
 #define CPECAN_KERNEL_GENERAL 1  /* any band width; diagonals live in HBM            */
-#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide; register-resident wavefront */
+#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide (<= 504 with CPECAN_FLAG_WIDE_BANDS); register-resident wavefront */
 
 #define CPECAN_FLAG_DEBUG_DUMP 1 /* keep forward/backward cells for cpecan_hip_batch_debug_cells */
 #define CPECAN_FLAG_UNBANDED 2   /* getAlignedPairsWithoutBanding (:1512): full matrix, one traceback from
@@ -255,6 +255,15 @@ typedef struct {
                                          (any band width) instead of the wave-per-alignment kernels of that machine
                                          (posterior decode; bands <= 248 k-mers for the HDP machine, <= 184 for the
                                          vanilla one); same results bit for bit */
+#define CPECAN_FLAG_WIDE_BANDS 128 /* cpecan_hip_batch_create (strawMan machine, posterior decode and expectations): a
+                                      batch whose widest band is 249..504 k-mers runs on the six- or eight-wave build of
+                                      the workgroup-per-alignment kernels (up to 376, up to 504) instead of the general
+                                      kernel, whichever family is the default; CPECAN_KERNEL_SYSTOLIC then refuses
+                                      only bands above 504.  A batch of narrower bands runs exactly what it runs
+                                      without the flag, one of wider bands goes to the general kernel as before; the
+                                      other machines ignore the flag.  Same results bit for bit.  The environment
+                                      variable CPECAN_WIDE_BANDS=1 (read per batch) sets it for every strawMan batch:
+                                      the way in for callers of libcpecan_host.so and vanillaAlign. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -346,7 +355,8 @@ int cpecan_hip_batch_shader_clock_mhz(cpecan_batch *batch, double *mhz);
 int cpecan_hip_batch_info(cpecan_batch *batch, int32_t *kernel, int32_t *workgroups, int32_t *max_width);
 /* Systolic path only: waves per workgroup of the kernel build the batch runs on -- the fewest whose 64 slots each
  * hold the widest band of the batch: 1 (bands up to 56 k-mers), 2 (120), 3 (184) or 4 (248).  The fewer waves an
- * alignment takes, the more alignments a CU holds (16, 8, 5, 4). */
+ * alignment takes, the more alignments a CU holds (16, 8, 5, 4).  With CPECAN_FLAG_WIDE_BANDS also 6 (bands of 249..376
+ * k-mers) and 8 (377..504): the wide builds, two workgroups per CU. */
 int cpecan_hip_batch_systolic_rows(cpecan_batch *batch, int32_t *rows);
 /* Register-resident path only: *wave = 1 if the batch runs on the wave-per-alignment kernels (rows is then the
  * number of cells a lane holds: 2, 3 or 4), 0 on the workgroup-per-alignment ones (rows = waves per workgroup).  For a
