@@ -71,17 +71,24 @@ extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *stat
  * band of that width asks for, minus one; a one-cell-per-lane build would only serve bands below 57 k-mers, which the
  * two-cell build takes too.  The workgroup family's source also builds six and eight waves per workgroup (bands up to
  * 376 and 504 k-mers): the wide builds, a table of their own, which a strawMan batch reaches only with
- * CPECAN_FLAG_WIDE_BANDS and only when its widest band is past every build of the tables above. */
+ * CPECAN_FLAG_WIDE_BANDS and only when its widest band is past every build of the tables above.  The same source built
+ * with -DSY_VANILLA gives the vanilla machine's wide builds (_v4, _v6, _v8: four, six and eight waves per workgroup,
+ * bands up to 248, 376 and 504 k-mers; their table starts one class earlier because the vanilla wave builds end at 184),
+ * reached the same way and for the posterior decode only: a vanilla E-step past 184 k-mers stays on the general kernel. */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
 SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(cpecan_wave_build_l4)
 SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
+SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
 typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
-static const SweepBuild *const SY_WIDE_BUILDS[2] = { &cpecan_systolic_build_r6, &cpecan_systolic_build_r8 };
+/* (a table of wide builds ends with a null entry) */
+static const SweepBuild *const SY_WIDE_BUILDS[3] = { &cpecan_systolic_build_r6, &cpecan_systolic_build_r8, nullptr };
+static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4, &cpecan_systolic_build_v6,
+                                                      &cpecan_systolic_build_v8, nullptr };
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
@@ -1460,12 +1467,14 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     if (vanilla && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
         return fail(CPECAN_EINVAL, "expectations run over the banded matrix only");
     const int S = dna ? 5 : echelon ? 7 : sm4 ? 4 : 3; /* states per cell */
-    /* the wide builds of the workgroup family are the strawMan machine's: the flag means nothing to the others
-     * (CPECAN_WIDE_BANDS=1, read per batch, sets it for every strawMan batch) */
+    /* the wide builds of the workgroup family are the strawMan machine's and, for the posterior decode, the vanilla
+     * machine's: the flag means nothing to the others, nor to a vanilla E-step, whose batches past the wave builds run
+     * on the general kernel as without it (CPECAN_WIDE_BANDS=1, read per batch, sets it for every such batch) */
     const bool strawMan = !dna && !vanilla && !hdp && !sm4 && !echelon;
-    if (strawMan && getenv("CPECAN_WIDE_BANDS") != nullptr && atoi(getenv("CPECAN_WIDE_BANDS")) == 1)
+    const bool vanillaWide = vanilla && mode == CPECAN_MODE_POSTERIOR;
+    if ((strawMan || vanillaWide) && getenv("CPECAN_WIDE_BANDS") != nullptr && atoi(getenv("CPECAN_WIDE_BANDS")) == 1)
         flags |= CPECAN_FLAG_WIDE_BANDS;
-    const bool wideBands = strawMan && (flags & CPECAN_FLAG_WIDE_BANDS) != 0;
+    const bool wideBands = (strawMan || vanillaWide) && (flags & CPECAN_FLAG_WIDE_BANDS) != 0;
     if (!c || !items || nItems <= 0 || !xChars || (!events && !yChars) || !params || !out)
         return fail(CPECAN_EINVAL, "bad argument");
     if (dna && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "DNA batches: no cell dumps");
@@ -1700,13 +1709,19 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     const SweepFamily &fam = hdp ? HV_BUILDS : vanilla ? VV_BUILDS
                              : (use_wave_kernels() && !(flags & CPECAN_FLAG_WORKGROUP_KERNELS)) ? WV_BUILDS : SY_BUILDS;
     const int famMaxWidth = fam[3]->maxWidth;
-    /* CPECAN_FLAG_WIDE_BANDS: a band past the family's widest build goes to the six- or the eight-wave build of the
-     * workgroup family, whichever family the batch would otherwise run on; a band the family holds is left to it */
+    /* CPECAN_FLAG_WIDE_BANDS: a band past the family's widest build goes to the narrowest wide build of the workgroup
+     * family that holds it (six or eight waves; four, six or eight for the vanilla machine), whichever family the batch
+     * would otherwise run on; a band the family holds is left to it.  A vanilla batch reaches here with the flag only
+     * in posterior mode (wideBands above) and without it when CPECAN_FLAG_GENERAL_KERNEL is set (useKernel) */
+    const SweepBuild *const *wideTable = vanilla ? SYV_WIDE_BUILDS : SY_WIDE_BUILDS;
     const SweepBuild *wideBuild = nullptr;
-    if (wideBands && globalMaxWidth > famMaxWidth)
-        for (const SweepBuild *w : SY_WIDE_BUILDS)
-            if (!wideBuild && globalMaxWidth <= w->maxWidth) wideBuild = w;
-    const int sweepMaxWidth = wideBands ? SY_WIDE_BUILDS[1]->maxWidth : famMaxWidth;
+    int sweepMaxWidth = famMaxWidth;
+    if (wideBands)
+        for (int i = 0; wideTable[i] != nullptr; i++) {
+            if (!wideBuild && globalMaxWidth > famMaxWidth && globalMaxWidth <= wideTable[i]->maxWidth)
+                wideBuild = wideTable[i];
+            sweepMaxWidth = std::max(sweepMaxWidth, wideTable[i]->maxWidth);
+        }
     b->dna = dna;
     b->vanilla = vanilla;
     b->hdp = hdp;
@@ -1741,6 +1756,12 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
         while (r < 4 && globalMaxWidth > fam[r - 1]->maxWidth) r++;
         b->sy = fam[r - 1];
         b->trackRow = b->sy->once->trackRowDoubles;
+    }
+    if (useKernel == CPECAN_KERNEL_SYSTOLIC && mode == CPECAN_MODE_EXPECTATIONS && !b->sy->expect && !b->sy->backward_fx) {
+        /* (cannot happen: the builds without an E-step are only chosen for posterior batches, see wideBands) */
+        const int rc = fail(CPECAN_EINVAL, "the chosen kernel build has no E-step");
+        cpecan_hip_batch_destroy(b);
+        return rc;
     }
     b->hItems = hItems;
 

@@ -41,8 +41,23 @@
 /* this file is compiled once per SY_R (1..4 waves per workgroup: bands up to 56, 120, 184, 248 k-mers; 6 and 8 waves,
  * the wide builds of CPECAN_FLAG_WIDE_BANDS: 376 and 504); the symbols of the builds other than four carry _r1.._r3,
  * _r6, _r8, and the pieces that do not depend on SY_R (track, counts, division self-test) exist in the four-wave build
- * only */
-#if SY_R == 4
+ * only.  With -DSY_VANILLA it is compiled three times more (4, 6 and 8 waves: _v4, _v6, _v8; see below) */
+/* -DSY_VANILLA: the same two sweeps for the 3-state vanilla signal machine (stateMachine3Vanilla_cellCalculate,
+ * impl/stateMachine.c:1368-1409), posterior decode only, with four, six and eight waves per workgroup (bands of up to
+ * 248, 376 and 504 k-mers; symbols suffixed _v4, _v6, _v8).  A lane holds the 21 doubles of its k-mer's row of the
+ * wave family's vanilla track (cpecan_k_wv_track_vanilla): two tables of Gaussian level and inverse-Gaussian noise
+ * constants and the five log transition probabilities of the column's skip bin, so transitions are per lane, not
+ * per wave; a_ym, a_yy and the end vector come from the model header.  The E-step of this machine stays on the general
+ * kernel: these builds have no ring of backward cells and no expectation kernel. */
+#if defined(SY_VANILLA) && SY_R == 4
+#define SY_SYM(n) n##_v4
+#elif defined(SY_VANILLA) && SY_R == 6
+#define SY_SYM(n) n##_v6
+#elif defined(SY_VANILLA) && SY_R == 8
+#define SY_SYM(n) n##_v8
+#elif defined(SY_VANILLA)
+#error "SY_VANILLA: 4, 6 or 8 waves per workgroup"
+#elif SY_R == 4
 #define SY_SYM(n) n
 #elif SY_R == 8
 #define SY_SYM(n) n##_r8
@@ -57,7 +72,9 @@
 #else
 #error "SY_R: 1, 2, 3, 4, 6 or 8 waves per workgroup"
 #endif
-#if SY_R == 1 || SY_R == 8 /* the one-wave and the eight-wave backward kernel land on 129 VGPRs by themselves: hold
+#if defined(SY_VANILLA) /* the vanilla row does not fit 128 VGPRs: whatever occupancy the allocation lands on */
+#define SY_BACKWARD_ATTR
+#elif SY_R == 1 || SY_R == 8 /* the one-wave and the eight-wave backward kernel land on 129 VGPRs by themselves: hold
                             * them to four waves per SIMD (128; two eight-wave workgroups then share a CU) */
 #define SY_BACKWARD_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #else
@@ -76,7 +93,20 @@
 #define SY_WMOD(v) ((((v) % SY_R) + SY_R) % SY_R)
 #define SY_SLOT(x) ((x) % SY_P)
 #endif
+#ifdef SY_VANILLA
+#define SY_ROW 22    /* doubles per column of the vanilla track (WV_ROW of cpecan_kernel_wave.hip) */
+#define SY_NPRM 21   /* ... of which a slot keeps all but the last (the bin itself, E-step only) */
+#define SY_TR 16     /* first of the row's five log transition probabilities: a_mx, a_xx, a_mm, a_xm, a_my */
+#define SY_EVW 4     /* doubles per staged event: mean, noise, 1 / noise, log(noise) */
+#define SY_MODEL_DOUBLES ((long long) CP_VMODEL_STRIDE)
+#define SY_MODE(P) 0 /* posterior decode only */
+#else
+#define SY_ROW CP_ROW
 #define SY_NPRM 17
+#define SY_EVW 2     /* doubles per staged event: mean, noise */
+#define SY_MODEL_DOUBLES ((long long) CP_MODEL_STRIDE)
+#define SY_MODE(P) (P).mode
+#endif
 #define SY_PREFETCH 4     /* diagonals the backward sweep fetches ahead (== its unroll factor) */
 #define SY_CAND_SLACK 0.25 /* candidates: cells within this (log units) below the posterior threshold */
 #define SY_CAND_PER_DIAG 4 /* candidate capacity per wave, in records per ring diagonal */
@@ -143,8 +173,8 @@ struct Shared {
 #define SY_FEED_EV 128  /* ring of events, by event index            */
 #define SY_FEED_ROW 64  /* ring of k-mer constant rows, by k-mer index */
 struct Feed {
-    double ev[SY_FEED_EV * 2];
-    double row[SY_FEED_ROW * CP_ROW];
+    double ev[SY_FEED_EV * SY_EVW];
+    double row[SY_FEED_ROW * SY_ROW];
 };
 
 __device__ __forceinline__ double bcast(double v, int srcLane) { /* srcLane wave-uniform */
@@ -238,6 +268,41 @@ __device__ __forceinline__ double lgauss(double x, double mu, double sd, double 
     return K + (-0.5 * a * a);
 }
 
+#ifdef SY_VANILLA
+/* emissions_signal_getEventMatchProbWithTwoDists (impl/stateMachine.c:499-528) on one table of a slot's row (p: mu, sd,
+ * 1/sd, K, noise mean, 1/mean, lambda, log(lambda) - log(2 pi)): logGaussPdf of the event's mean (:333-343) plus
+ * logInvGaussPdf of its noise (:322-331), ((log(lambda) - log(2 pi) - 3 log(noise)) - lambda a a / noise) / 2 with
+ * a = (noise - mu) / mu.  Both divisions are Markstein-corrected multiplies (by the track's 1/mu and by the 1/noise
+ * taken when the event was staged), log(noise) is the host's: the same doubles as the wave builds' and the oracle's. */
+__device__ __forceinline__ double vemit(double em, double en, double er, double c3, const double *p) {
+    const double level = lgauss(em, p[0], p[1], p[2], p[3]);
+    const double u = en - p[4];
+    const double q1 = u * p[5];
+    const double a = __fma_rn(__fma_rn(-q1, p[4], u), p[5], q1); /* (noise - mu) / mu */
+    const double w = p[6] * a * a;
+    const double q2 = w * er;
+    const double dv = __fma_rn(__fma_rn(-q2, en, w), er, q2);    /* lambda a a / noise */
+    return level + (p[7] - c3 - dv) / 2;
+}
+
+/* The sweep back keeps a slot's five log transition probabilities; those of the k-mers that enter at the band's low edge
+ * come from an LDS ring by k-mer index, which the whole workgroup refills from the track every 32 diagonals (k-mers
+ * enter in descending order, at most one per diagonal) */
+#define SY_TR_RING 128
+#define SY_TR_AHEAD 119 /* staged below the next k-mer to enter; the eight entries above it are left alone, a wave one
+                         * step behind may still be reading the last one */
+struct TransFeed {
+    double r[SY_TR_RING * 5];
+};
+/* k-mers lo..hi (0 <= lo) into the ring; the whole workgroup */
+__device__ __forceinline__ void trans_stage(TransFeed &tf, const double *__restrict__ track, int lo, int hi) {
+    for (int i = lo * 5 + (int) threadIdx.x; i < (hi + 1) * 5; i += SY_P) {
+        const int x = i / 5, j = i - x * 5;
+        tf.r[(x & (SY_TR_RING - 1)) * 5 + j] = track[(long long) x * SY_ROW + SY_TR + j];
+    }
+}
+#endif
+
 /*
  * The band: first and last matrix column (k-mer index) of every anti-diagonal, one int2 per diagonal
  * in HBM, built by the host from band_construct's output (cpecan_hip.hip).  The sweeps read it
@@ -300,7 +365,7 @@ struct ItemOut {
 };
 
 __device__ __forceinline__ void load_params(double (&dst)[SY_NPRM], const double *__restrict__ track, int x) {
-    const double *p = track + (long long) x * CP_ROW;
+    const double *p = track + (long long) x * SY_ROW;
 #pragma unroll
     for (int j = 0; j < SY_NPRM; j++) dst[j] = p[j];
 }
@@ -388,12 +453,17 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
     const int lX = (int) it.lX, lY = (int) it.lY, D = lX + lY;
     const double *__restrict__ ev = events + 3 * it.yOff;
     const double *cf = sh.coef;
+#ifdef SY_VANILLA
+    /* the position-independent transitions (cpecan_hip.hip: derive_vanilla); the others are the slot row's */
+    const double lYM = model[CP_VHDR_LOG_YM], lYY = model[CP_VHDR_LOG_YY];
+#else
     /* a -inf gapY->gapX transition (the nanopore default, stateMachine.c:1287) contributes
      * logAdd(acc, -inf) == acc: skip that term (wave-uniform) */
     const bool hasSwitchX = model[T_GAP_SWITCH_TO_X] > CP_NEG_INF;
     double T[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) T[i] = model[i];
+#endif
 
     const int d0 = uni(ld_agent(&state->d));
     int tracedBackTo = uni(ld_agent(&state->tracedBackTo));
@@ -405,6 +475,9 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
     double Fm, Fx, Fy; /* forward cell, current diagonal   */
     double Lm, Lx, Ly; /* slot-1's cell, previous diagonal */
     double em, en;     /* event scored on this diagonal    */
+#ifdef SY_VANILLA
+    double er, el;     /* ... its 1 / noise and log(noise); an event that does not exist is (0, 1, 1, 0): finite */
+#endif
     int xin, xminP;
 
     if (d0 == 0) {
@@ -413,7 +486,12 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
 #pragma unroll
         for (int j = 0; j < SY_NPRM; j++) prm[j] = 0.0;
         Fm = Fx = Fy = Lm = Lx = Ly = CP_NEG_INF;
+#ifdef SY_VANILLA
+        em = el = 0.0;
+        en = er = 1.0;
+#else
         em = en = 0.0;
+#endif
         if (wave == 0 && lane == 0) {
             load_params(prm, track, 0);
             Fm = it.raggedL ? CP_NEG_INF : 0.0;
@@ -450,7 +528,13 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
         const int ei = d0 - xs - 1;
         const bool okE = v && ei >= 0 && ei < lY;
         em = okE ? ev[3 * (long long) ei] : 0.0;
+#ifdef SY_VANILLA
+        en = okE ? ev[3 * (long long) ei + 1] : 1.0;
+        er = okE ? 1.0 / en : 1.0;
+        el = okE ? ev[3 * (long long) ei + 2] : 0.0;
+#else
         en = okE ? ev[3 * (long long) ei + 1] : 0.0;
+#endif
         xin = xmax + 1;
         xminP = xmin;
     }
@@ -479,7 +563,7 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
         tpB = topN < fromN ? topN : fromN;
         allFull = tpB < topW; /* windows shorter than the traceback margin: keep everything */
     }
-    if (P.mode != 0) allFull = true; /* the expectation pass reads every state of every diagonal */
+    if (SY_MODE(P) != 0) allFull = true; /* the expectation pass reads every state of every diagonal */
     /* (tpA - d) mod 10 and (tpB - d) mod 10 for the diagonal being computed, kept incrementally */
     /* (tpA - d) mod 10 and (tpB - d) mod 10 for the next diagonal whose mask bit is computed */
     int rA = ((tpA - (d0 + 1)) % 10 + 10) % 10, rB = endW ? 0x40000000 : ((tpB - (d0 + 1)) % 10 + 10) % 10;
@@ -487,6 +571,9 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
     if (lane == 63) {
         double *x = sh.xch[d0 & 1][wave];
         x[0] = Fm; x[1] = Fx; x[2] = Fy; x[3] = em; x[4] = en;
+#ifdef SY_VANILLA
+        x[5] = er; x[6] = el;
+#endif
     }
 
     const long long tbFromL = tracedBackTo + P.minDiags;
@@ -503,15 +590,27 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
             band_load(bandTab, db, fxmin, fxmax);
             band_stage(bf, bandTab, D, db, db + 2 * SY_FEED - 1);
             const int evTo = db - fxmin - 1 + 3 * SY_FEED, rowTo = xin + 2 * SY_FEED;
+#ifdef SY_VANILLA
+#pragma unroll 1
+            for (int i = evHi * SY_EVW + (int) threadIdx.x; i < evTo * SY_EVW; i += SY_P) {
+                /* 1 / noise is taken once, here; log(noise) is the host's (the batch's own copy of the events carries it
+                 * in place of the duration) */
+                const int e = i >> 2, c = i & 3;
+                const bool ok = e >= 0 && e < lY;
+                const double q = ok ? ev[3 * (long long) e + (c == 0 ? 0 : c == 3 ? 2 : 1)] : (c == 0 || c == 3 ? 0.0 : 1.0);
+                fd.ev[(i & (SY_EVW * SY_FEED_EV - 1))] = c == 2 ? 1.0 / q : q;
+            }
+#else
 #pragma unroll 1
             for (int i = evHi * 2 + (int) threadIdx.x; i < evTo * 2; i += SY_P) {
                 const int e = i >> 1;
                 fd.ev[(i & (2 * SY_FEED_EV - 1))] = e >= 0 && e < lY ? ev[3 * (long long) e + (i & 1)] : 0.0;
             }
+#endif
 #pragma unroll 1
-            for (int i = rowHi * CP_ROW + (int) threadIdx.x; i < rowTo * CP_ROW; i += SY_P) {
-                const int x = i / CP_ROW, j = i - x * CP_ROW;
-                fd.row[(x & (SY_FEED_ROW - 1)) * CP_ROW + j] = track[(long long) (x <= lX ? x : lX) * CP_ROW + j];
+            for (int i = rowHi * SY_ROW + (int) threadIdx.x; i < rowTo * SY_ROW; i += SY_P) {
+                const int x = i / SY_ROW, j = i - x * SY_ROW;
+                fd.row[(x & (SY_FEED_ROW - 1)) * SY_ROW + j] = track[(long long) (x <= lX ? x : lX) * SY_ROW + j];
             }
             evHi = evTo;
             rowHi = rowTo;
@@ -552,6 +651,10 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
         const double rm = shr1(xb[0], Fm), rx = shr1(xb[1], Fx), ry = shr1(xb[2], Fy);
         em = shr1(xb[3], em);
         en = shr1(xb[4], en);
+#ifdef SY_VANILLA
+        er = shr1(xb[5], er);
+        el = shr1(xb[6], el);
+#endif
 #endif
         PROF_FENCE(em) PROF_FENCE(en)
         PROF(3)
@@ -563,7 +666,7 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
 #else
             if (SY_WAVE_OF(xin) == wave && lane == (xin & 63)) {
 #endif
-                const double *r = fd.row + (xin & (SY_FEED_ROW - 1)) * CP_ROW;
+                const double *r = fd.row + (xin & (SY_FEED_ROW - 1)) * SY_ROW;
 #pragma unroll
                 for (int j = 0; j < SY_NPRM; j++) prm[j] = r[j];
             }
@@ -572,14 +675,31 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
         if (xmin == xminP && SY_WAVE_OF(xmin) == wave && lane == (xmin & 63)) {
             /* the top cell's event is new.  Index -1 is NULLEVENT (:261): its emissions only ever
              * meet -inf cells, the staged 0.0 keeps NaN out */
-            const double *e = fd.ev + ((2 * (d - xmin - 1)) & (2 * SY_FEED_EV - 1));
+            const double *e = fd.ev + ((SY_EVW * (d - xmin - 1)) & (SY_EVW * SY_FEED_EV - 1));
             em = e[0];
             en = e[1];
+#ifdef SY_VANILLA
+            er = e[2];
+            el = e[3];
+#endif
         }
         PROF_FENCE(em) PROF_FENCE(en) PROF_FENCE(prm[0])
         PROF(4)
         double nmv = CP_NEG_INF, nxv = CP_NEG_INF, nyv = CP_NEG_INF;
         if (row_active(wave, xmin, xmax)) {
+#ifdef SY_VANILLA
+            const double c3 = 3 * el;
+            const double pm = vemit(em, en, er, c3, prm), py = vemit(em, en, er, c3, prm + 8);
+            /* cell_calculateForward over stateMachine3Vanilla_cellCalculate (stateMachine.c:1368-1409): gap X from the
+             * lower cell (no emission: 0 + tP is tP), match from the middle cell, gap Y from the upper cell */
+            double gx = rm + prm[SY_TR + 0];
+            gx = ladd(gx, rx + prm[SY_TR + 1], cf);
+            double mm = Lm + (pm + prm[SY_TR + 2]);
+            mm = ladd(mm, Lx + (pm + prm[SY_TR + 3]), cf);
+            mm = ladd(mm, Ly + (pm + lYM), cf);
+            double gy = Fm + (py + prm[SY_TR + 4]);
+            gy = ladd(gy, Fy + (py + lYY), cf);
+#else
             const double px = prm[CP_GAPX];
 #ifdef SY_ABLATE_EMIT
             double pm = em + prm[CP_K1], py = en + prm[CP_YK1];
@@ -601,6 +721,7 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
             mm = ladd(mm, Ly + (pm + T[T_MATCH_FROM_GAP_Y]), cf);
             double gy = Fm + (py + T[T_GAP_OPEN_Y]);
             gy = ladd(gy, Fy + (py + T[T_GAP_EXTEND_Y]), cf);
+#endif /* SY_VANILLA */
             PROF_FENCE(mm) PROF_FENCE(gx) PROF_FENCE(gy)
             PROF(6)
             nmv = valid ? mm : CP_NEG_INF;
@@ -626,6 +747,9 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
         if (lane == 63) {
             double *x = sh.xch[d & 1][wave];
             x[0] = Fm; x[1] = Fx; x[2] = Fy; x[3] = em; x[4] = en;
+#ifdef SY_VANILLA
+            x[5] = er; x[6] = el;
+#endif
         }
         xminP = xmin;
         PROF(8)
@@ -669,15 +793,24 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                                 const double *__restrict__ track, const double *__restrict__ model,
                                 double *ring, int ringD, SyState *state, ItemOut &out, Shared &sh,
                                 BandFeed &bf, int *cntBuf, WinTotal *wtot, double *vw,
-                                unsigned long long *msk, int2 *candKx, double *candFb, double *bring) {
+                                unsigned long long *msk, int2 *candKx, double *candFb, double *bring
+#ifdef SY_VANILLA
+                                , TransFeed &tf
+#endif
+                                ) {
     const Geometry g = make_geometry(ring, ringD);
     const int lane = g.lane, wave = g.wave;
     const int lX = (int) it.lX, D = (int) (it.lX + it.lY);
     const double *cf = sh.coef;
+#ifdef SY_VANILLA
+    const double lYM = model[CP_VHDR_LOG_YM], lYY = model[CP_VHDR_LOG_YY];
+    (void) lX;
+#else
     const bool hasSwitchX = model[T_GAP_SWITCH_TO_X] > CP_NEG_INF;
     double T[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) T[i] = model[i];
+#endif
 
     const int dTop = uni(ld_agent(&state->winTop)), tracedBackFrom = uni(ld_agent(&state->winFrom)),
               tracedBackTo = uni(ld_agent(&state->winTo));
@@ -717,11 +850,29 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
          * emission and a transition.  The slot above sends the two ingredients (B.match with its match emission,
          * B.gapX with its gap-X emission) down the lanes and the receiver forms the sums: four values to shift and
          * to hold instead of eight; the sums are the same expressions, so the doubles are the same. */
+#ifdef SY_VANILLA
+        /* Under the vanilla machine a step's transitions are those of the cell it goes TO, and the slot above owns
+         * that cell's column: it sends the sums themselves, B + (eP + tP) per from-state, in the reference's grouping
+         * -- three for the middle block, two for the lower block (no emission: B + (0 + tP) is B + tP).  The middle
+         * block's sums are formed on the diagonal their cell is on, with the transitions the slot holds THEN: two
+         * diagonals later, when they are used, the slot may have passed to another k-mer. */
+        double hM0 = CP_NEG_INF, hM1 = CP_NEG_INF, hM2 = CP_NEG_INF; /* middle-block sums of slot+1 on t+2 */
+        double S0 = 0.0, S1 = 0.0, S2 = 0.0; /* match emission of t+1 plus each transition into match, as of t+1 */
+#else
         double hB = CP_NEG_INF, hP = 0.0;        /* B.match and match emission of slot+1 on t+2 (middle block) */
+        double pmPrev = 0.0;                     /* match emission of t+1 */
+#endif
         double Um = CP_NEG_INF, Uy = CP_NEG_INF; /* upper-block sums from t+1 (same slot)                       */
-        double pmPrev = 0.0, BmPrev = CP_NEG_INF;                 /* match emission / backward match of t+1 */
+        double BmPrev = CP_NEG_INF;              /* backward match of t+1 */
         {
             double e0, e1, e2; /* end state vector (stateMachine.c:1179-1207) */
+#ifdef SY_VANILLA
+            /* stateMachine3Vanilla_endStateProb / _raggedEndStateProb (stateMachine.c:1209-1236) */
+            const double endM = model[CP_VHDR_END_M], endX = model[CP_VHDR_END_X], endY = model[CP_VHDR_END_Y];
+            e0 = atEnd && it.raggedR ? (endX + endY) / 2.0 : endM;
+            e1 = endX;
+            e2 = endY;
+#else
             if (atEnd && it.raggedR) {
                 e0 = (T[T_GAP_OPEN_X] + T[T_GAP_OPEN_Y]) / 2.0;
                 e1 = T[T_GAP_EXTEND_X];
@@ -731,16 +882,27 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 e1 = T[T_MATCH_FROM_GAP_X];
                 e2 = T[T_MATCH_FROM_GAP_Y];
             }
+#endif
             Bm = tvalid ? e0 : CP_NEG_INF;
             Bx = tvalid ? e1 : CP_NEG_INF;
             By = tvalid ? e2 : CP_NEG_INF;
         }
         /* the sweep needs one constant per k-mer, its gap-X emission: held per slot, refreshed from
          * a 64-k-mer chunk when a k-mer enters at the low edge of the band */
+#ifdef SY_VANILLA
+        /* ... under the vanilla machine its five log transition probabilities, from the LDS ring (TransFeed) */
+        double tr[5];
+#pragma unroll
+        for (int j = 0; j < 5; j++) tr[j] = track[(long long) (tvalid ? xs : 0) * SY_ROW + SY_TR + j];
+        int xinB = bxmin - 1; /* k-mers above xinB are installed */
+        int trLo = xinB - SY_TR_AHEAD > 0 ? xinB - SY_TR_AHEAD : 0; /* lowest k-mer staged */
+        trans_stage(tf, track, trLo, xinB);
+#else
         double pxReg = track[(long long) (tvalid ? xs : 0) * CP_ROW + CP_GAPX];
         int xinB = bxmin - 1; /* k-mers above xinB are installed */
         int pxBase = (xinB >= 0 ? xinB : 0) & ~63;
         double pxChunk = track[(long long) min(pxBase + lane, lX) * CP_ROW + CP_GAPX];
+#endif
 
         /*
          * The forward match cell and the two emissions of a diagonal are fetched SY_PREFETCH diagonals
@@ -775,6 +937,21 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             if (t < dTop) {
                 lds_barrier();
                 const double *xa = sh.xch[(t + 1) & 1][g.waveAbove];
+#ifdef SY_VANILLA
+                /* of slot+1 on t+1: the lower block's sums (used now) and the middle block's (one diagonal further
+                 * down); tr[] is still that diagonal's here */
+                const double rX0 = shl1(xa[0], Bx + tr[0]), rX1 = shl1(xa[1], Bx + tr[1]);
+                const double rM0 = shl1(xa[2], Bm + S0), rM1 = shl1(xa[3], Bm + S1), rM2 = shl1(xa[4], Bm + S2);
+                const bool bvalid = xs >= bxmin;
+                while (xinB >= bxmin) {
+                    if (SY_WAVE_OF(xinB) == wave && lane == (xinB & 63)) {
+                        const double *r = tf.r + (xinB & (SY_TR_RING - 1)) * 5;
+#pragma unroll
+                        for (int j = 0; j < 5; j++) tr[j] = r[j];
+                    }
+                    xinB--;
+                }
+#else
                 /* of slot+1 on t+1: B.gapX with its k-mer's gap-X emission (lower block of t+1), B.match with its
                  * match emission (middle block, used one diagonal further down) */
                 const double rBx = shl1(xa[0], Bx), rPx = shl1(xa[1], pxReg);
@@ -789,31 +966,52 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     if (SY_WAVE_OF(xinB) == wave) pxReg = set_lane(pxReg, xinB & 63, v);
                     xinB--;
                 }
+#endif
                 BmPrev = Bm;
                 tvalid = bvalid;
                 double bm = CP_NEG_INF, bx = CP_NEG_INF, by = CP_NEG_INF;
                 if (active) {
                     /* gather form of cell_calculateBackward: (t+2) middle block, then (t+1, smaller
                      * x-y) upper block, then (t+1, larger x-y) lower block */
+#ifdef SY_VANILLA
+                    bm = ladd(ladd(hM0, Um, cf), rX0, cf);
+                    bx = ladd(hM1, rX1, cf);
+                    by = ladd(hM2, Uy, cf);
+#else
                     bm = ladd(ladd(hB + (hP + T[T_MATCH_CONTINUE]), Um, cf), rBx + (rPx + T[T_GAP_OPEN_X]), cf);
                     bx = ladd(hB + (hP + T[T_MATCH_FROM_GAP_X]), rBx + (rPx + T[T_GAP_EXTEND_X]), cf);
                     by = ladd(hB + (hP + T[T_MATCH_FROM_GAP_Y]), Uy, cf);
                     if (hasSwitchX) by = ladd(by, rBx + (rPx + T[T_GAP_SWITCH_TO_X]), cf);
+#endif
                     bm = bvalid ? bm : CP_NEG_INF;
                     bx = bvalid ? bx : CP_NEG_INF;
                     by = bvalid ? by : CP_NEG_INF;
                 }
                 Bm = bm; Bx = bx; By = by;
+#ifdef SY_VANILLA
+                hM0 = rM0; hM1 = rM1; hM2 = rM2;
+#else
                 hB = rBm; hP = rPm;
+#endif
             }
             /* what this diagonal hands down: the upper-block sums stay in the slot (a cell outside the band has
              * B = -inf and a zero emission: the sums are -inf by themselves); the rest leaves as B and emission */
+#ifdef SY_VANILLA
+            Um = By + (pyc + tr[4]);
+            Uy = By + (pyc + lYY);
+            const double nS0 = pmc + tr[2], nS1 = pmc + tr[3], nS2 = pmc + lYM;
+            if (lane == 0) {
+                double *x = sh.xch[t & 1][wave];
+                x[0] = Bx + tr[0]; x[1] = Bx + tr[1]; x[2] = Bm + nS0; x[3] = Bm + nS1; x[4] = Bm + nS2;
+            }
+#else
             Um = By + (pyc + T[T_GAP_OPEN_Y]);
             Uy = By + (pyc + T[T_GAP_EXTEND_Y]);
             if (lane == 0) {
                 double *x = sh.xch[t & 1][wave];
                 x[0] = Bx; x[1] = pxReg; x[2] = Bm; x[3] = pmc;
             }
+#endif
 
             if (t <= tracedBackFrom) {
                 const double fb = fMc + Bm;
@@ -843,9 +1041,16 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                          * ever above -inf) */
                         const double s0 = below ? r0 : CP_NEG_INF, s1 = below ? r1 : CP_NEG_INF,
                                      s2 = below ? r2 : CP_NEG_INF;
+#ifdef SY_VANILLA
+                        /* (the transitions of the cell on t+1, which this slot held then: S0..S2) */
+                        double mm = s0 + S0;
+                        mm = ladd(mm, s1 + S1, cf);
+                        mm = ladd(mm, s2 + S2, cf);
+#else
                         double mm = s0 + (pmPrev + T[T_MATCH_CONTINUE]);
                         mm = ladd(mm, s1 + (pmPrev + T[T_MATCH_FROM_GAP_X]), cf);
                         mm = ladd(mm, s2 + (pmPrev + T[T_MATCH_FROM_GAP_Y]), cf);
+#endif
                         w = mm + BmPrev;
                         vw[((long long) nTotWin * 2 + 1) * SY_P + wave * 64 + lane] = w;
                     }
@@ -874,7 +1079,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 /* exponent of the posterior, less the total: parked in the emission slot this diagonal
                  * no longer needs (the forward cells themselves stay intact: the next window's
                  * refresh at its lowest diagonal reads forward[tracedBackFrom], :944,:985) */
-                if (P.mode != 0) {
+                if (SY_MODE(P) != 0) {
                     /* Baum-Welch: the backward cell goes to its own ring for the expectation kernel
                      * (the emissions in slots 3, 4 stay: that kernel re-uses them) */
                     if (tvalid) {
@@ -887,7 +1092,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
 #ifndef SY_ABLATE_FB
                 else if (tvalid) *g.rp(t, 3) = fb;
 #endif
-                const bool cand = P.mode == 0 && tvalid && fb >= candThr && fb > CP_NEG_INF;
+                const bool cand = SY_MODE(P) == 0 && tvalid && fb >= candThr && fb > CP_NEG_INF;
                 const unsigned long long cm = __ballot(cand);
                 if (cm != 0ull) {
                     const int ci = nCand + __popcll(cm & ((1ull << lane) - 1ull));
@@ -898,7 +1103,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     nCand += __popcll(cm);
                 }
             }
+#ifdef SY_VANILLA
+            S0 = nS0; S1 = nS1; S2 = nS2;
+#else
             pmPrev = pmc;
+#endif
             nxmin = bxmin; nxmax = bxmax;
             bxmin = pxmin; bxmax = pxmax;
             if (t - 2 >= tracedBackTo) band_get(bf, t - 2, pxmin, pxmax);
@@ -917,6 +1126,14 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             if (t - 64 < bandLo) { /* 32 more band entries, long before the sweep reads them */
                 band_stage(bf, bandTab, D, bandLo - 32, bandLo - 1);
                 bandLo -= 32;
+#ifdef SY_VANILLA
+                /* ... and the transitions of the k-mers that can enter before the next refill */
+                const int lo = xinB - SY_TR_AHEAD > 0 ? xinB - SY_TR_AHEAD : 0;
+                if (lo < trLo) {
+                    trans_stage(tf, track, lo, trLo - 1);
+                    trLo = lo;
+                }
+#endif
             }
             step(t, q0F, q0Pm, q0Py);
             step(t - 1, q1F, q1Pm, q1Py);
@@ -989,7 +1206,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
      *   pass 1  re-reads only the hit lanes, ranks each hit inside its diagonal by k-mer index
      *           (the reference's x-y order) from the diagonal's masks, and writes the triples.
      */
-    if (P.mode == 0 && nPost > 0) {
+    if (SY_MODE(P) == 0 && nPost > 0) {
         int *const off = cntBuf;
         auto lane64 = [&](const unsigned long long v, const int src) __attribute__((always_inline)) {
             const unsigned lo = (unsigned) __builtin_amdgcn_readlane((int) (unsigned) v, src);
@@ -1259,8 +1476,8 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_forward)(
     if (state->finished || it.lX + it.lY == 0) return;
     init_coef(sh.coef);
     __syncthreads();
-    forward_window(it, P, bandTab + it.diagBase, track + trackBase[idx] * CP_ROW, events,
-                   models + (long long) it.model * CP_MODEL_STRIDE, Fring + idx * ringDoubles, ringD,
+    forward_window(it, P, bandTab + it.diagBase, track + trackBase[idx] * SY_ROW, events,
+                   models + (long long) it.model * SY_MODEL_DOUBLES, Fring + idx * ringDoubles, ringD,
                    state, sh, fd, bf);
 }
 
@@ -1273,6 +1490,9 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
     long long *totXay, double *totVal, char *scratch, long long scratchBytes, double *Bring, int window) {
     __shared__ Shared sh;
     __shared__ BandFeed bf;
+#ifdef SY_VANILLA
+    __shared__ TransFeed tf;
+#endif
     const long long idx = blockIdx.x;
     if (idx >= nItems) return;
     SyState *state = states + idx;
@@ -1289,8 +1509,8 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
     out.totCap = it.totCap;
     out.nPairs = uni64(state->nPairs);
     out.nTot = uni64(state->nTot);
-    backward_window(it, P, bandTab + it.diagBase, track + trackBase[idx] * CP_ROW,
-                    models + (long long) it.model * CP_MODEL_STRIDE, Fring + idx * ringDoubles, ringD,
+    backward_window(it, P, bandTab + it.diagBase, track + trackBase[idx] * SY_ROW,
+                    models + (long long) it.model * SY_MODEL_DOUBLES, Fring + idx * ringDoubles, ringD,
                     state, out, sh, bf, (int *) (scratch + idx * scratchBytes),
                     (WinTotal *) (scratch + idx * scratchBytes + 2ll * ringD * sizeof(int)),
                     (double *) (scratch + idx * scratchBytes + 2ll * ringD * sizeof(int)
@@ -1301,15 +1521,20 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
                     (int2 *) (scratch + idx * scratchBytes + scratch_cand_offset(ringD)),
                     (double *) (scratch + idx * scratchBytes + scratch_cand_offset(ringD)
                                 + (long long) SY_R * SY_CAND_PER_DIAG * ringD * sizeof(int2)),
-                    Bring ? Bring + idx * ((long long) ringD * SY_R * 3 * 64) : nullptr);
+                    Bring ? Bring + idx * ((long long) ringD * SY_R * 3 * 64) : nullptr
+#ifdef SY_VANILLA
+                    , tf
+#endif
+                    );
     if (threadIdx.x == 0) {
         state->nPairs = out.nPairs;
         state->nTot = out.nTot;
         state->winValid = 0;
-        state->expectPending = P.mode != 0 ? window + 1 : 0; /* which launch's window the B ring holds */
+        state->expectPending = SY_MODE(P) != 0 ? window + 1 : 0; /* which launch's window the B ring holds */
     }
 }
 
+#ifndef SY_VANILLA /* (the vanilla machine's E-step runs on the general kernel) */
 /*
  * Baum-Welch expectations of the traceback window the backward kernel just swept
  * (diagonalCalculation_Expectations :841-863 with cell_signal_updateTransAndKmerSkipExpectations
@@ -1435,8 +1660,9 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
     if (threadIdx.x < 9) atomicAdd(dst + threadIdx.x, sExp[threadIdx.x]);
     if (threadIdx.x == 0) atomicAdd(dst + 9 + 4096, lik);
 }
+#endif /* !SY_VANILLA */
 
-#if SY_R == 4
+#if SY_R == 4 && !defined(SY_VANILLA)
 /* results of the per-alignment states into the batch's count arrays */
 extern "C" __global__ void cpecan_k_sy_counts(const SyState *states, long long nItems,
                                               long long *nPairs, long long *nTot, long long *nCells) {
@@ -1522,7 +1748,19 @@ static long long sy_scratch_bytes(int ringD) {
 /* Launchers of the four stages of one pass over a batch (the C-ABI layer sequences them:
  * track, then per window {forward, backward}, then counts). */
 static int sy_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
-#if SY_R == 4
+#if SY_R == 4 && defined(SY_VANILLA)
+/* the vanilla machine on this family: the wave family's vanilla track (its kernel lives in that family's widest vanilla
+ * object), this family's state records and counts kernel */
+static int sy_launch_track(hipStream_t stream, const SweepArgs &a) {
+    if (cpecan_wave_launch_track_vanilla(stream, a) != 0) return -1;
+    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(SyState), stream) != hipSuccess) return -1;
+    return sy_status();
+}
+static int sy_launch_counts(hipStream_t stream, const SweepArgs &a) {
+    return cpecan_systolic_machine.launch_counts(stream, a);
+}
+#endif
+#if SY_R == 4 && !defined(SY_VANILLA)
 static int sy_launch_track(hipStream_t stream, const SweepArgs &a) {
     int bx = (int) ((((long long) a.maxLX + 1) * CP_ROW + 255) / 256);
     if (bx > 64) bx = 64;
@@ -1550,20 +1788,31 @@ static int sy_launch_backward(hipStream_t stream, const SweepArgs &a, int window
                        window);
     return sy_status();
 }
+#ifndef SY_VANILLA
 static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) {
     hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_expect), dim3((unsigned) a.nItems, SY_EXPECT_CHUNKS), dim3(SY_P), 0, stream,
                        a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.kidx, a.models, a.Fring, a.ringDoubles,
                        a.Bring, a.ringD, (SyState *) a.states, a.scratch, a.scratchBytes, a.expect, window);
     return sy_status();
 }
+#endif
 
 /* the records (host only: the device pass would emit them as constants, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
-#if SY_R == 4
+#if SY_R == 4 && defined(SY_VANILLA)
+const SweepMachine cpecan_systolic_machine_vanilla = { (int) sizeof(SyState), SY_ROW, sy_launch_track, sy_launch_counts };
+#elif SY_R == 4
 const SweepMachine cpecan_systolic_machine = { (int) sizeof(SyState), CP_ROW, sy_launch_track, sy_launch_counts };
 #endif
 extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
+#ifdef SY_VANILLA
+/* (no E-step on these builds: no expect launcher, no ring of backward cells; the dispatch keeps such batches away) */
+const SweepBuild SY_SYM(cpecan_systolic_build) = {
+    SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
+    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };
+#else
 const SweepBuild SY_SYM(cpecan_systolic_build) = {
     SY_R, false, SWEEP_STRAWMAN, &cpecan_systolic_machine, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, SY_R * 3 * 64,
     sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, sy_launch_expect, nullptr };
+#endif
 #endif

@@ -2553,9 +2553,13 @@ extern "C" __global__ void cpecan_k_wv_track_vanilla(const DevItem *__restrict__
         }
     }
 }
-static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
+extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const SweepArgs &a) {
     hipLaunchKernelGGL(cpecan_k_wv_track_vanilla, wv_track_grid(a), dim3(256), 0, stream, a.items, a.nItems, a.trackBase,
                        a.kidx, a.models, a.track);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
+    if (cpecan_wave_launch_track_vanilla(stream, a) != 0) return -1;
     return wv_clear_states(stream, a);
 }
 #endif

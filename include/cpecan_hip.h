@@ -260,10 +260,16 @@ typedef struct {
                                       the workgroup-per-alignment kernels (up to 376, up to 504) instead of the general
                                       kernel, whichever family is the default; CPECAN_KERNEL_SYSTOLIC then refuses
                                       only bands above 504.  A batch of narrower bands runs exactly what it runs
-                                      without the flag, one of wider bands goes to the general kernel as before; the
-                                      other machines ignore the flag.  Same results bit for bit.  The environment
-                                      variable CPECAN_WIDE_BANDS=1 (read per batch) sets it for every strawMan batch:
-                                      the way in for callers of libcpecan_host.so and vanillaAlign. */
+                                      without the flag, one of wider bands goes to the general kernel as before.
+                                      cpecan_hip_batch_create_vanilla (posterior decode only): a batch whose widest band
+                                      is 185..504 k-mers, past that machine's wave builds, runs on the vanilla builds of
+                                      the same kernels with four, six or eight waves per workgroup (up to 248, 376, 504)
+                                      unless it is un-banded or carries CPECAN_FLAG_GENERAL_KERNEL; a vanilla batch of
+                                      CPECAN_MODE_EXPECTATIONS ignores the flag (its E-step past 184 k-mers runs on the
+                                      general kernel), and so do the other machines.  Same results bit for bit.  The
+                                      environment variable CPECAN_WIDE_BANDS=1 (read per batch) sets it for every
+                                      strawMan batch and every vanilla posterior batch: the way in for callers of
+                                      libcpecan_host.so and vanillaAlign. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -285,7 +291,9 @@ int cpecan_hip_batch_create_dna(cpecan_ctx *ctx, const cpecan_item *items, int64
 
 /* k-mers against events with a vanilla model (getAlignedPairsUsingAnchors with a StateMachine3Vanilla,
  * sequence_getKmer2 / sequence_getEvent): same buffers as cpecan_hip_batch_create, model_id is a
- * cpecan_hip_modelsv_create id.  General kernel; flags: UNBANDED or EXPECTATIONS. */
+ * cpecan_hip_modelsv_create id.  flags: UNBANDED or EXPECTATIONS (general kernel), GENERAL_KERNEL, WIDE_BANDS.  There
+ * is no kernel argument: the batch picks its kernels itself (the wave builds up to 184 k-mers of band, the general kernel
+ * past that), and CPECAN_FLAG_WIDE_BANDS alone selects the workgroup builds for posterior batches of 185..504 k-mers. */
 int cpecan_hip_batch_create_vanilla(cpecan_ctx *ctx, const cpecan_item *items, int64_t n_items,
                                     const char *x_chars, int64_t n_x, const double *events, int64_t n_events,
                                     const int64_t *anchors, int64_t n_anchor_pairs,
@@ -356,7 +364,8 @@ int cpecan_hip_batch_info(cpecan_batch *batch, int32_t *kernel, int32_t *workgro
 /* Systolic path only: waves per workgroup of the kernel build the batch runs on -- the fewest whose 64 slots each
  * hold the widest band of the batch: 1 (bands up to 56 k-mers), 2 (120), 3 (184) or 4 (248).  The fewer waves an
  * alignment takes, the more alignments a CU holds (16, 8, 5, 4).  With CPECAN_FLAG_WIDE_BANDS also 6 (bands of 249..376
- * k-mers) and 8 (377..504): the wide builds, two workgroups per CU. */
+ * k-mers) and 8 (377..504): the wide builds, two workgroups per CU; for a vanilla batch with that flag 4 (185..248), 6
+ * and 8. */
 int cpecan_hip_batch_systolic_rows(cpecan_batch *batch, int32_t *rows);
 /* Register-resident path only: *wave = 1 if the batch runs on the wave-per-alignment kernels (rows is then the
  * number of cells a lane holds: 2, 3 or 4), 0 on the workgroup-per-alignment ones (rows = waves per workgroup).  For a
