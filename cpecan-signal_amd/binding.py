@@ -33,6 +33,7 @@ FLAG_EXPECTATIONS = 8
 FLAG_WORKGROUP_KERNELS = 16
 FLAG_GENERAL_KERNEL = 32
 FLAG_WIDE_BANDS = 128
+MACHINE_STRAWMAN, MACHINE_DNA5, MACHINE_VANILLA, MACHINE_HDP, MACHINE_SM4, MACHINE_ECHELON = range(6)
 NUM_KMERS = 4096
 MODEL_TABLE_LEN = 1 + NUM_KMERS * 5
 EXPECTATION_LEN = 9 + NUM_KMERS + 1
@@ -49,7 +50,7 @@ EXPORTS = [
     "cpecan_hip_batch_elapsed_ms", "cpecan_hip_batch_counts", "cpecan_hip_batch_fetch_pairs",
     "cpecan_hip_batch_fetch_totals", "cpecan_hip_batch_expectations_device_ptr",
     "cpecan_hip_batch_fetch_expectations", "cpecan_hip_batch_debug_cells",
-    "cpecan_hip_batch_destroy", "cpecan_hip_ctx_stream", "cpecan_hip_selftest_division", "cpecan_hip_batch_info", "cpecan_hip_batch_stage_ms",
+    "cpecan_hip_batch_destroy", "cpecan_hip_ctx_stream", "cpecan_hip_selftest_division", "cpecan_hip_batch_info", "cpecan_hip_plan_dispatch", "cpecan_hip_batch_stage_ms",
     "cpecan_hip_batch_systolic_rows", "cpecan_hip_batch_kernel_family", "cpecan_hip_batch_assembly_sweeps", "cpecan_hip_batch_expectation_pass", "cpecan_hip_trim_cache", "cpecan_hip_models_set_transitions",
     "cpecan_hip_models5_create", "cpecan_hip_batch_create_dna",
     "cpecan_hip_modelsv_create", "cpecan_hip_modelsv_create_scaled", "cpecan_hip_modelsv_download",
@@ -191,6 +192,7 @@ def lib():
         L.cpecan_hip_batch_elapsed_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.cpecan_hip_batch_systolic_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.cpecan_hip_batch_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cpecan_hip_plan_dispatch.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 4
         L.cpecan_hip_batch_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.cpecan_hip_batch_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cpecan_hip_batch_fetch_pairs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
@@ -222,6 +224,15 @@ def trim_cache():
     """gives the device and pinned host memory the library keeps for reuse back to the runtime (between phases, when
     something else in the process or on the card needs it)"""
     _check(lib().cpecan_hip_trim_cache())
+
+
+def plan_dispatch(machine, mode, kernel, flags, max_width, edges_step_by_one=True):
+    """what batch creation would choose (no device needed): dict(kernel, wave, rows, build_max_width); a refused
+    combination raises as the create call would"""
+    out = [C.c_int32(0) for _ in range(4)]
+    _check(lib().cpecan_hip_plan_dispatch(machine, mode, kernel, flags, max_width, int(edges_step_by_one),
+                                          *[C.byref(o) for o in out]))
+    return dict(zip(("kernel", "wave", "rows", "build_max_width"), (o.value for o in out)))
 
 
 def band_construct(anchors, lX, lY, expansion):

@@ -92,12 +92,6 @@ static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4,
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
-/* which family a batch runs on: the wave kernels unless CPECAN_KERNELS=systolic asks for the workgroup-per-alignment ones */
-static bool use_wave_kernels() {
-    const char *k = getenv("CPECAN_KERNELS");
-    return !(k && strcmp(k, "systolic") == 0);
-}
-
 
 namespace {
 
@@ -404,6 +398,180 @@ struct cpecan_ctx {
     int nModelsE = 0;
 };
 
+/* The machines a batch can run (the CPECAN_MACHINE_* numbers of cpecan_hip.h) and one row of facts per machine: what
+ * batch creation, the kernel choice and the launchers know about a machine they read from its row. */
+enum Machine {
+    STRAWMAN = CPECAN_MACHINE_STRAWMAN, DNA5 = CPECAN_MACHINE_DNA5, VANILLA = CPECAN_MACHINE_VANILLA,
+    HDP = CPECAN_MACHINE_HDP, SM4 = CPECAN_MACHINE_SM4, ECHELON = CPECAN_MACHINE_ECHELON, N_MACHINES
+};
+enum XSource { X_KIDX, X_KID, X_CHARS }; /* what a kernel reads per X position: k-mer index, HDP k-mer id, nucleotide */
+struct MachineRow {
+    int states;        /* per cell */
+    int expectLen;     /* doubles per model of the E-step's sums */
+    int pairCapFactor; /* first guess of the pairs of an item, per element of lX + lY (ensure_counts re-runs a batch that
+                          outgrows it).  16 for the HDP machine: it scores with linear densities (quirk Q6), its posteriors
+                          are flat and far more cells pass the threshold (2887 pairs for a ~800-event read in the
+                          reference's own test); and for echelon, which emits up to 15 pairs a cell */
+    int xReach;        /* how far past lX a pair's x may lie (echelon: lX + 3), for compactPairs */
+    const char *posteriorOnly; /* the refusal of an E-step (null: the machine has one) */
+    const char *noDumps;       /* the refusal of CPECAN_FLAG_DEBUG_DUMP (null: it has cell dumps) */
+    bool bandedEstep;          /* its E-step refuses CPECAN_FLAG_UNBANDED */
+    /* the register-resident kernels: the machine's wave family and, where a batch may ask for it, its workgroup family
+     * (null: none); the wide builds of the workgroup family (null: none) and the modes they serve, a bit per mode */
+    SweepFamily *wave, *workgroup;
+    const SweepBuild *const *wide;
+    int wideModes;
+    bool ownChoice; /* its create call has no kernel argument: AUTO, or the general kernel with CPECAN_FLAG_GENERAL_KERNEL */
+    /* the general kernel and what distinguishes its argument record */
+    void (*general)(DevGeneralArgs, DevParams); /* (null: cpecan_k_generale, which takes a third record) */
+    XSource x;
+    bool yAux;       /* log(event noise) per event */
+    int ldsMaxWidth; /* the widest band whose forward diagonals the general kernel keeps in LDS (0: it keeps none) */
+    int (*nModels)(const cpecan_ctx *);
+    const void *(*models)(const cpecan_ctx *); /* on the device */
+};
+#define BOTH_MODES (1 << CPECAN_MODE_POSTERIOR | 1 << CPECAN_MODE_EXPECTATIONS)
+static const MachineRow MACHINES[N_MACHINES] = {
+    /* STRAWMAN */ { 3, CPECAN_EXPECTATION_LEN, 4, 0, nullptr, nullptr, false, &WV_BUILDS, &SY_BUILDS, SY_WIDE_BUILDS, BOTH_MODES,
+                     false, cpecan_k_general, X_KIDX, false, 0, [](const cpecan_ctx *c) { return c->nModels; },
+                     [](const cpecan_ctx *c) { return (const void *) c->models.p; } },
+    /* DNA5 */     { 5, CPECAN_EXPECTATION5_LEN, 4, 0, nullptr, "DNA batches: no cell dumps", true, nullptr, nullptr, nullptr, 0,
+                     false, cpecan_k_general5, X_CHARS, false, 248, [](const cpecan_ctx *c) { return c->nModels5; },
+                     [](const cpecan_ctx *c) { return (const void *) c->models5.p; } },
+    /* VANILLA */  { 3, CPECAN_EXPECTATIONV_LEN, 4, 0, nullptr, "vanilla batches: no cell dumps", true, &VV_BUILDS, nullptr,
+                     SYV_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, true, cpecan_k_generalv, X_KIDX, true, 0,
+                     [](const cpecan_ctx *c) { return c->nModelsV; },
+                     [](const cpecan_ctx *c) { return (const void *) c->modelsV.p; } },
+    /* HDP */      { 3, CPECAN_EXPECTATIONH_LEN, 16, 0, nullptr, "HDP batches: no cell dumps", true, &HV_BUILDS, nullptr, nullptr, 0,
+                     true, cpecan_k_generalh, X_KID, false, 0, [](const cpecan_ctx *c) { return (int) c->hostModelsH.size(); },
+                     [](const cpecan_ctx *c) { return (const void *) c->modelsH.p; } },
+    /* SM4 */      { 4, CPECAN_EXPECTATION_LEN, 4, 0, "4-state batches: posterior decode only, no cell dumps",
+                     "4-state batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, false,
+                     cpecan_k_general4, X_KIDX, false, 0, [](const cpecan_ctx *c) { return c->nModels4; },
+                     [](const cpecan_ctx *c) { return (const void *) c->models4.p; } },
+    /* ECHELON */  { 7, CPECAN_EXPECTATION_LEN, 16, 4, "echelon batches: posterior decode only, no cell dumps",
+                     "echelon batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, false,
+                     nullptr, X_KIDX, true, 0, [](const cpecan_ctx *c) { return c->nModelsE; },
+                     [](const cpecan_ctx *c) { return (const void *) c->modelsE.p; } },
+};
+
+/* what a machine refuses whatever the batch holds */
+static int check_machine(Machine machine, int mode, int flags) {
+    const MachineRow &m = MACHINES[machine];
+    if (mode != CPECAN_MODE_POSTERIOR && mode != CPECAN_MODE_EXPECTATIONS) return fail(CPECAN_EINVAL, "unknown mode %d", mode);
+    if (m.posteriorOnly && mode != CPECAN_MODE_POSTERIOR) return fail(CPECAN_EINVAL, "%s", m.posteriorOnly);
+    if (m.noDumps && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "%s", m.noDumps);
+    if (m.bandedEstep && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
+        return fail(CPECAN_EINVAL, "expectations run over the banded matrix only");
+    return CPECAN_OK;
+}
+
+/* The environment switches the kernel choice reads, parsed once per batch (tests and timing tools set them between
+ * batches); CPECAN_DNA_GENERAL once per process. */
+struct BatchEnv {
+    bool wideBands;   /* CPECAN_WIDE_BANDS=1: CPECAN_FLAG_WIDE_BANDS for every batch the wide builds serve */
+    bool waveKernels; /* false under CPECAN_KERNELS=systolic: the workgroup-per-alignment family for every batch */
+    int systolicRows; /* CPECAN_SYSTOLIC_ROWS=N: a build of at least N rows (tests, timing) */
+    int asmMode;      /* CPECAN_ASM: 0 the compiled kernels, 1 the assembly forward sweep only (the compiled sweep back
+                         reads what it writes), otherwise and unset (-1) both assembly sweeps (tests, timing) */
+    bool wave5Off;    /* CPECAN_DNA_GENERAL: the 5-state machine on the general kernel (tests, timing) */
+};
+static BatchEnv read_batch_env() {
+    static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr;
+    const char *wide = getenv("CPECAN_WIDE_BANDS"), *kernels = getenv("CPECAN_KERNELS");
+    const char *rows = getenv("CPECAN_SYSTOLIC_ROWS"), *as = getenv("CPECAN_ASM");
+    return { wide && atoi(wide) == 1, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1,
+             as ? atoi(as) : -1, wave5Off };
+}
+
+/* The kernel choice: a function of the machine, what the caller asked for, the environment and two facts about the
+ * batch's bands.  Asked about the narrowest band there is (maxWidth 0, edges stepping by one) it tells what holds
+ * for every band: what it refuses then, it refuses always, and the general kernel then is the general kernel always. */
+struct DispatchQuery {
+    Machine machine;
+    int mode, kernel, flags;
+    int maxWidth;        /* the widest band of the batch, in cells */
+    bool edgesStepByOne; /* every band edge moves by at most one k-mer per diagonal */
+    BatchEnv env;
+};
+struct Dispatch {
+    int kernel = CPECAN_KERNEL_GENERAL; /* CPECAN_KERNEL_GENERAL or _SYSTOLIC, as cpecan_hip_batch_info reports */
+    const SweepBuild *build = nullptr;  /* (null on the general kernel) */
+    bool wave5 = false;     /* the 5-state machine's wave kernels (cpecan_kernel_wave5.hip) in place of the general one */
+    bool asmPlan = false;   /* the hand-scheduled assembly sweeps may take the batch, as far as the bands do not matter */
+    bool asmSweeps = false; /* ... and with its bands; what is left is known at set-up (one stream group, the module) */
+    bool asmBackward = false; /* ... both sweeps (CPECAN_ASM=1: the forward sweep only) */
+    int flags = 0;          /* the batch's flags (CPECAN_WIDE_BANDS=1 adds its flag where it means something) */
+    int refusal = CPECAN_OK;
+    char why[160] = "";
+};
+#define CP_WAVE5_MAX_WIDTH 192 /* cells: one to three per lane */
+static Dispatch choose_dispatch(const DispatchQuery &q) {
+    const MachineRow &m = MACHINES[q.machine];
+    const bool unbanded = (q.flags & CPECAN_FLAG_UNBANDED) != 0, debug = (q.flags & CPECAN_FLAG_DEBUG_DUMP) != 0;
+    Dispatch d;
+    d.flags = q.flags;
+    auto refuse = [&d](const char *fmt, int a = 0, int b = 0) {
+        d.refusal = CPECAN_EINVAL;
+        snprintf(d.why, sizeof d.why, fmt, a, b);
+        return d;
+    };
+    /* the HDP and vanilla machines have wave-per-alignment kernels of their own, for the posterior decode and for the
+     * E-step, and CPECAN_FLAG_GENERAL_KERNEL keeps such a batch on the general kernel; the 5-state, 4-state and
+     * echelon machines have no register-resident kernels */
+    const int asked = !m.wave ? CPECAN_KERNEL_GENERAL
+                      : !m.ownChoice ? q.kernel
+                      : (q.flags & CPECAN_FLAG_GENERAL_KERNEL) ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
+    if (unbanded && (q.mode != CPECAN_MODE_POSTERIOR || asked == CPECAN_KERNEL_SYSTOLIC))
+        return refuse("un-banded alignment: posterior mode on the general kernel only");
+    /* the wide builds of the workgroup family are the strawMan machine's and, for the posterior decode, the vanilla
+     * machine's: the flag means nothing to the others, nor to a vanilla E-step, whose batches past the wave builds run
+     * on the general kernel as without it */
+    const bool wideServes = m.wide != nullptr && (m.wideModes >> q.mode & 1);
+    if (wideServes && q.env.wideBands) d.flags |= CPECAN_FLAG_WIDE_BANDS;
+    if (asked != CPECAN_KERNEL_GENERAL) {
+        /* the family the batch would run on, and the widest band its builds take */
+        const bool workgroup = m.workgroup && (!q.env.waveKernels || (q.flags & CPECAN_FLAG_WORKGROUP_KERNELS));
+        const SweepFamily &fam = workgroup ? *m.workgroup : *m.wave;
+        /* CPECAN_FLAG_WIDE_BANDS: a band past the family's widest build goes to the narrowest wide build of the workgroup
+         * family that holds it (six or eight waves; four, six or eight for the vanilla machine), whichever family the
+         * batch would otherwise run on; a band the family holds is left to it */
+        const SweepBuild *wideBuild = nullptr;
+        int reach = fam[3]->maxWidth;
+        if (wideServes && (d.flags & CPECAN_FLAG_WIDE_BANDS))
+            for (int i = 0; m.wide[i] != nullptr; i++) {
+                if (!wideBuild && q.maxWidth > fam[3]->maxWidth && q.maxWidth <= m.wide[i]->maxWidth) wideBuild = m.wide[i];
+                reach = std::max(reach, m.wide[i]->maxWidth);
+            }
+        const bool fits = q.maxWidth <= reach && q.edgesStepByOne;
+        d.kernel = asked != CPECAN_KERNEL_AUTO ? asked
+                   : fits && !debug && !unbanded ? CPECAN_KERNEL_SYSTOLIC : CPECAN_KERNEL_GENERAL;
+        if (d.kernel == CPECAN_KERNEL_SYSTOLIC && !fits)
+            return refuse("band is %d cells wide (systolic kernel: at most %d, edges moving one k-mer per diagonal)",
+                          q.maxWidth, reach);
+        if (d.kernel == CPECAN_KERNEL_SYSTOLIC && debug) return refuse("cell dumps are only available from the general kernel");
+        if (d.kernel == CPECAN_KERNEL_SYSTOLIC) {
+            /* the build with the fewest waves per workgroup whose slots hold the widest band: the fewer waves an
+             * alignment takes, the more alignments a CU holds */
+            int r = q.env.systolicRows < 1 ? 1 : q.env.systolicRows > 4 ? 4 : q.env.systolicRows;
+            while (r < 4 && q.maxWidth > fam[r - 1]->maxWidth) r++;
+            d.build = wideBuild ? wideBuild : fam[r - 1];
+            /* (the builds without an E-step are the wide builds of a machine whose wideModes leave the E-step out) */
+            if (q.mode == CPECAN_MODE_EXPECTATIONS && !d.build->expect && !d.build->backward_fx)
+                return refuse("the chosen kernel build has no E-step");
+            /* the assembly sweeps take the posterior batches of a family that has a build for them (the strawMan
+             * machine's wave family) whose bands need ASM_L cells per lane and fit their staging scheme */
+            d.asmPlan = q.mode == CPECAN_MODE_POSTERIOR && fam[ASM_L - 1]->post_asm != nullptr;
+            d.asmSweeps = d.asmPlan && q.env.asmMode != 0 && d.build->post_asm && d.build->rows == ASM_L &&
+                          q.maxWidth <= ASM_MAX_WIDTH;
+            d.asmBackward = q.env.asmMode != 1;
+        }
+    }
+    d.wave5 = q.machine == DNA5 && !debug && !unbanded && q.maxWidth <= CP_WAVE5_MAX_WIDTH && !q.env.wave5Off &&
+              !(q.flags & CPECAN_FLAG_GENERAL_KERNEL);
+    return d;
+}
+
 struct cpecan_batch {
     cpecan_ctx *ctx = nullptr;
     int64_t nItems = 0;
@@ -414,8 +582,8 @@ struct cpecan_batch {
     DevBuf<int> bandL, bandR;
     DevBuf<long long> cellPrefix;
     DevBuf<char> chars, charsY; /* charsY: DNA batches (5-state machine) */
-    bool dna = false;
-    bool vanilla = false, hdp = false, sm4 = false, echelon = false;
+    Machine machine = STRAWMAN;
+    bool wave5 = false; /* a DNA batch on the 5-state machine's wave kernels (choose_dispatch) */
     DevBuf<double> logNoise; /* vanilla and echelon batches: log(event noise), host libm */
     DevBuf<double> duration; /* echelon batches: per event the duration terms of 0..5 k-mers, host libm */
     DevBuf<long long> xEnd;  /* echelon batches: per item the X characters that belong to its sequence */
@@ -1447,232 +1615,213 @@ int cpecan_hip_batch_destroy(cpecan_batch *b) {
         }                                                                                    \
     } while (0)
 
-/* events != NULL: k-mers against events with a 3-state signal model; yChars != NULL: DNA against DNA
- * with a 5-state symbol model (nEvents then counts the bases of yChars) */
-static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nItems,
-                             const char *xChars, int64_t nX, const double *events, const char *yChars,
-                             int64_t nEvents, const int64_t *anchors, int64_t nAnchorPairs,
-                             const cpecan_band_params *params, int32_t mode, int32_t kernel,
-                             int32_t flags, cpecan_batch **out, bool vanilla = false, bool hdp = false, bool sm4 = false,
-                             bool echelon = false) {
-    if (sm4 && (mode != CPECAN_MODE_POSTERIOR || (flags & CPECAN_FLAG_DEBUG_DUMP)))
-        return fail(CPECAN_EINVAL, "4-state batches: posterior decode only, no cell dumps");
-    if (echelon && (mode != CPECAN_MODE_POSTERIOR || (flags & CPECAN_FLAG_DEBUG_DUMP)))
-        return fail(CPECAN_EINVAL, "echelon batches: posterior decode only, no cell dumps");
-    const bool dna = yChars != nullptr;
-    if (hdp && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "HDP batches: no cell dumps");
-    if (hdp && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
-        return fail(CPECAN_EINVAL, "expectations run over the banded matrix only");
-    if (vanilla && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "vanilla batches: no cell dumps");
-    if (vanilla && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
-        return fail(CPECAN_EINVAL, "expectations run over the banded matrix only");
-    const int S = dna ? 5 : echelon ? 7 : sm4 ? 4 : 3; /* states per cell */
-    /* the wide builds of the workgroup family are the strawMan machine's and, for the posterior decode, the vanilla
-     * machine's: the flag means nothing to the others, nor to a vanilla E-step, whose batches past the wave builds run
-     * on the general kernel as without it (CPECAN_WIDE_BANDS=1, read per batch, sets it for every such batch) */
-    const bool strawMan = !dna && !vanilla && !hdp && !sm4 && !echelon;
-    const bool vanillaWide = vanilla && mode == CPECAN_MODE_POSTERIOR;
-    if ((strawMan || vanillaWide) && getenv("CPECAN_WIDE_BANDS") != nullptr && atoi(getenv("CPECAN_WIDE_BANDS")) == 1)
-        flags |= CPECAN_FLAG_WIDE_BANDS;
-    const bool wideBands = (strawMan || vanillaWide) && (flags & CPECAN_FLAG_WIDE_BANDS) != 0;
-    if (!c || !items || nItems <= 0 || !xChars || (!events && !yChars) || !params || !out)
-        return fail(CPECAN_EINVAL, "bad argument");
-    if (dna && (flags & CPECAN_FLAG_DEBUG_DUMP)) return fail(CPECAN_EINVAL, "DNA batches: no cell dumps");
-    if (dna && mode == CPECAN_MODE_EXPECTATIONS && (flags & CPECAN_FLAG_UNBANDED))
-        return fail(CPECAN_EINVAL, "expectations run over the banded matrix only");
-    if (nAnchorPairs > 0 && !anchors) return fail(CPECAN_EINVAL, "anchors is NULL");
-    if (mode != CPECAN_MODE_POSTERIOR && mode != CPECAN_MODE_EXPECTATIONS)
-        return fail(CPECAN_EINVAL, "unknown mode %d", mode);
-    if (params->diagonalExpansion < 0 || (params->diagonalExpansion & 1) ||
-        params->traceBackDiagonals < 1 || params->minDiagsBetweenTraceBack < 2 ||
-        params->traceBackDiagonals + 1 >= params->minDiagsBetweenTraceBack)
-        return fail(CPECAN_EINVAL, "banding parameters violate the prerequisites of "
-                                   "getPosteriorProbsWithBanding (pairwiseAligner.c:880-884)");
-    *out = nullptr;
-    HIP_TRY(hipSetDevice(c->device));
-    const bool unbanded = (flags & CPECAN_FLAG_UNBANDED) != 0;
-    if (unbanded && (mode != CPECAN_MODE_POSTERIOR || kernel == CPECAN_KERNEL_SYSTOLIC))
-        return fail(CPECAN_EINVAL, "un-banded alignment: posterior mode on the general kernel only");
+} // extern "C"
 
-    /* per-item validation + band tables (host integer work): offsets in one serial pass, then the items are dealt
-     * to the host threads (band, cell prefix, traceback schedule: ~15 000 diagonals per C3 read) */
-    std::vector<DevItem> hItems((size_t) nItems);
-    std::vector<int, NoInit<int>> hL, hR;
-    std::vector<long long, NoInit<long long>> hPre;
+/* what a create call was given (events, or for DNA against DNA yChars: nEvents then counts its bases) */
+struct BatchInput {
+    const cpecan_item *items;
+    int64_t nItems;
+    const char *xChars;
+    int64_t nX;
+    const double *events;
+    const char *yChars;
+    int64_t nEvents;
+    const int64_t *anchors;
+    int64_t nAnchorPairs;
+    const cpecan_band_params *params;
+    int mode;
+    bool unbanded;
+};
+
+/* The host's plan of a batch's bands (integer work): the band of every item as matrix columns (first, last) per diagonal
+ * -- what the register-resident kernels read -- written straight into a pinned block; the x-y intervals and the cell
+ * prefix sums of the general kernel only when the batch will (or, on a second build, turns out to) run on it; the
+ * traceback schedule; where every item's share of each buffer begins. */
+struct BandPlan {
+    std::vector<DevItem> items;
+    PinnedBuf<int> tab;
+    std::vector<int, NoInit<int>> L, R; /* (general) */
+    std::vector<long long, NoInit<long long>> pre;
+    bool general = false; /* L, R and pre are built */
+    long long diagTotal = 0, maxDiags = 0;
+    int maxWidth = 0, maxSpan = 1, maxWindows = 0, maxLX = 0;
+    long long maxLXY = 0;        /* the longest sequence of the batch, either side */
+    bool edgesStepByOne = true; /* band edges move by at most one k-mer per diagonal */
     long long cellTotal = 0, pairTotal = 0, totTotal = 0, bwsTotal = 0, trackTotal = 0;
-    int globalMaxWidth = 0, maxSpan = 1, maxLX = 0, maxWindows = 0;
-    long long maxLXY = 0; /* the longest sequence of the batch, either side */
-    bool systolicOk = true; /* band edges move by at most one k-mer per diagonal */
-    std::vector<long long> hTrackBase((size_t) nItems);
-    Lap lap("batch_create");
-    long long diagTotal = 0;
-    for (int64_t i = 0; i < nItems; i++) {
-        const cpecan_item &s = items[i];
+    std::vector<long long> trackBase;
+    /* the assembly sweeps' plan (build_asm_plan), for the batches that can run on them */
+    bool wantAsm = false;
+    std::vector<std::vector<AsmPlanWin>> asmWins;
+    std::vector<long long> asmOff;
+    PinnedBuf<AsmPlanCtl> asmCtl;
+    long long asmCtlTotal = 0;
+};
+
+/* per-item bounds and model ids; the items as the device reads them, offsets in one serial pass */
+static int check_items(const cpecan_ctx *c, Machine machine, const BatchInput &in, BandPlan &plan) {
+    const MachineRow &m = MACHINES[machine];
+    const int kmerTail = m.x == X_CHARS ? 0 : 5; /* the characters of the last k-mer past lX */
+    const int nModels = m.nModels(c);
+    plan.items.resize((size_t) in.nItems);
+    for (int64_t i = 0; i < in.nItems; i++) {
+        const cpecan_item &s = in.items[i];
         if (s.lX < 0 || s.lY < 0 || s.x_offset < 0 || s.y_offset < 0 || s.n_anchors < 0 ||
-            s.anchor_offset < 0 || s.x_offset + s.lX + (!dna && s.lX > 0 ? 5 : 0) > nX ||
-            s.y_offset + s.lY > nEvents || s.anchor_offset + s.n_anchors > nAnchorPairs)
+            s.anchor_offset < 0 || s.x_offset + s.lX + (s.lX > 0 ? kmerTail : 0) > in.nX ||
+            s.y_offset + s.lY > in.nEvents || s.anchor_offset + s.n_anchors > in.nAnchorPairs)
             return fail(CPECAN_EINVAL, "item %lld points outside the supplied buffers", (long long) i);
-        if (echelon && (s.reserved < 0 || s.reserved > 30 || (s.lX > 0 && s.x_offset + s.lX + 5 + s.reserved > nX)))
+        if (machine == ECHELON && (s.reserved < 0 || s.reserved > 30 || (s.lX > 0 && s.x_offset + s.lX + 5 + s.reserved > in.nX)))
             return fail(CPECAN_EINVAL, "item %lld: its look-ahead (reserved = %d) points outside the supplied characters",
                         (long long) i, s.reserved);
-        if (s.model_id < 0 || s.model_id >= (dna ? c->nModels5 : vanilla ? c->nModelsV : sm4 ? c->nModels4
-                                                      : echelon ? c->nModelsE
-                                                      : hdp ? (int) c->hostModelsH.size() : c->nModels))
+        if (s.model_id < 0 || s.model_id >= nModels)
             return fail(CPECAN_EINVAL, "item %lld: unknown model id %d", (long long) i, s.model_id);
         if (s.lX + s.lY >= (1ll << 30)) return fail(CPECAN_EINVAL, "item %lld too long", (long long) i);
-        DevItem &d = hItems[(size_t) i];
+        DevItem &d = plan.items[(size_t) i];
         d.lX = s.lX; d.lY = s.lY; d.xOff = s.x_offset; d.yOff = s.y_offset;
         d.anchorOff = s.anchor_offset; d.nAnchors = s.n_anchors;
         d.model = s.model_id; d.raggedL = s.ragged_left ? 1 : 0; d.raggedR = s.ragged_right ? 1 : 0;
-        d.diagBase = diagTotal;
-        diagTotal += s.lX + s.lY + 1;
+        d.diagBase = plan.diagTotal;
+        plan.diagTotal += s.lX + s.lY + 1;
+        plan.maxDiags = std::max<long long>(plan.maxDiags, s.lX + s.lY + 1);
     }
+    return CPECAN_OK;
+}
+
+/* The bands themselves, the items dealt to the host threads (band, cell prefix, traceback schedule: ~15 000 diagonals
+ * per C3 read).  A thread's working copy of one item's intervals stays in its cache. */
+static int build_bands(const BatchInput &in, BandPlan &plan, bool general) {
     struct ItemStats {
         int maxSpan = 1, windows = 0, badItem = -1, badRc = 0;
-        bool systolicOk = true;
+        bool edgesStepByOne = true;
     };
-    /* The band of every item: as matrix columns (first, last) per diagonal -- what the register-resident kernels
-     * read -- written straight into a pinned block; the x-y intervals and the cell prefix sums of the general kernel
-     * only when the batch will (or, on the second call, turns out to) run on it.  A thread's working copy of one
-     * item's intervals stays in its cache. */
-    PinnedBuf<int> hTab;
-    /* the assembly sweeps' plan (build_asm_plan), for the batches that can run on them */
-    const bool wantPlan = !dna && !vanilla && !hdp && !sm4 && !echelon && !unbanded && mode == CPECAN_MODE_POSTERIOR &&
-                          kernel != CPECAN_KERNEL_GENERAL && use_wave_kernels() && !(flags & CPECAN_FLAG_WORKGROUP_KERNELS) &&
-                          !(flags & CPECAN_FLAG_DEBUG_DUMP);
-    std::vector<std::vector<AsmPlanWin>> planWins(wantPlan ? (size_t) nItems : 0);
-    std::vector<long long> hPlanOff(wantPlan ? (size_t) nItems : 0);
-    PinnedBuf<AsmPlanCtl> hCtl;
-    StreamFence prepFence{ c->prep, nullptr }; /* (hTab, hCtl and the plan records below are uploaded through it) */
-    long long ctlTotal = 0;
-    if (wantPlan) {
-        for (int64_t i = 0; i < nItems; i++) {
-            hPlanOff[(size_t) i] = ctlTotal;
-            ctlTotal += (items[i].lX + items[i].lY) / ASM_BLOCK + 2;
-        }
-        HIP_TRY(hCtl.alloc((size_t) ctlTotal));
+    const cpecan_band_params &bp = *in.params;
+    const long long maxDiags = plan.maxDiags;
+    if (general) {
+        plan.L.resize((size_t) plan.diagTotal);
+        plan.R.resize((size_t) plan.diagTotal);
+        plan.pre.resize((size_t) plan.diagTotal);
+        plan.general = true;
     }
-    bool keptGeneral = false;
-    long long maxDiags = 0;
-    for (int64_t i = 0; i < nItems; i++) maxDiags = std::max<long long>(maxDiags, items[i].lX + items[i].lY + 1);
-    auto build_bands = [&](bool general) -> int {
-        if (general) {
-            hL.resize((size_t) diagTotal);
-            hR.resize((size_t) diagTotal);
-            hPre.resize((size_t) diagTotal);
-            keptGeneral = true;
-        }
-        maxSpan = 1;
-        maxWindows = 0;
-        systolicOk = true;
-        const int nt = (int) std::min<int64_t>(diagTotal > 2000000 ? host_threads() : 1, nItems);
-        std::vector<ItemStats> stats((size_t) nt);
-        auto work = [&](int w) {
-            ItemStats &st = stats[(size_t) w];
-            std::vector<int, NoInit<int>> own(general ? 0 : 2 * (size_t) maxDiags);
-            for (int64_t i = w; i < nItems; i += nt) {
-                const cpecan_item &s = items[i];
-                DevItem &d = hItems[(size_t) i];
-                const long long nDiag = s.lX + s.lY + 1;
-                int *Lp = general ? hL.data() + d.diagBase : own.data();
-                int *Rp = general ? hR.data() + d.diagBase : own.data() + maxDiags;
-                /* getAlignedPairsWithoutBanding builds its band from no anchors, expansion 2 (:1532) */
-                int rc = cpecan_band_construct(unbanded || !anchors ? nullptr : anchors + 2 * s.anchor_offset,
-                                               unbanded ? 0 : s.n_anchors, s.lX, s.lY,
-                                               unbanded ? 2 : params->diagonalExpansion, Lp, Rp);
-                if (rc != CPECAN_OK) {
-                    if (st.badItem < 0) { st.badItem = (int) i; st.badRc = rc; }
-                    continue;
-                }
-                long long cells = 0;
-                int maxW = 0;
-                long long *pre = general ? hPre.data() + d.diagBase : nullptr;
-                int *tab = hTab.p + d.diagBase * 2;
-                /* traceback schedule of getPosteriorProbsWithBanding (:917-918): longest span of forward
-                 * diagonals that must be resident at once, and the edge-step property the register-resident
-                 * kernels rely on */
-                long long tracedBackTo = 0;
-                int windows = 0, pmn = 0, pmx = 0;
-                for (long long k = 0; k < nDiag; k++) {
-                    if (pre) pre[k] = cells;
-                    const int wd = ((Rp[k] - Lp[k]) >> 1) + 1;
-                    cells += wd;
-                    maxW = std::max(maxW, wd);
-                    const int xmn = (int) ((k + Lp[k]) / 2), xmx = (int) ((k + Rp[k]) / 2);
-                    tab[k * 2] = xmn;
-                    tab[k * 2 + 1] = xmx;
-                    if (k >= 1) {
-                        if (xmn < pmn || xmn > pmn + 1 || xmx < pmx || xmx > pmx + 1) st.systolicOk = false;
-                        const bool atEnd = k == nDiag - 1;
-                        const bool tb = k >= tracedBackTo + params->minDiagsBetweenTraceBack &&
-                                        wd <= params->diagonalExpansion * 2 + 1;
-                        if (atEnd || tb) {
-                            windows++;
-                            st.maxSpan = (int) std::max<long long>(st.maxSpan, k - tracedBackTo + 1);
-                            tracedBackTo = k - (params->traceBackDiagonals + 1);
-                        }
-                    }
-                    pmn = xmn;
-                    pmx = xmx;
-                }
-                d.nCells = cells;
-                d.maxWidth = maxW;
-                st.windows = std::max(st.windows, windows);
-                if (wantPlan) build_asm_plan(tab, nDiag, *params, planWins[(size_t) i], hCtl.p + hPlanOff[(size_t) i]);
+    const int nt = (int) std::min<int64_t>(plan.diagTotal > 2000000 ? host_threads() : 1, in.nItems);
+    std::vector<ItemStats> stats((size_t) nt);
+    auto work = [&](int w) {
+        ItemStats &st = stats[(size_t) w];
+        std::vector<int, NoInit<int>> own(general ? 0 : 2 * (size_t) maxDiags);
+        for (int64_t i = w; i < in.nItems; i += nt) {
+            const cpecan_item &s = in.items[i];
+            DevItem &d = plan.items[(size_t) i];
+            const long long nDiag = s.lX + s.lY + 1;
+            int *Lp = general ? plan.L.data() + d.diagBase : own.data();
+            int *Rp = general ? plan.R.data() + d.diagBase : own.data() + maxDiags;
+            /* getAlignedPairsWithoutBanding builds its band from no anchors, expansion 2 (:1532) */
+            int rc = cpecan_band_construct(in.unbanded || !in.anchors ? nullptr : in.anchors + 2 * s.anchor_offset,
+                                           in.unbanded ? 0 : s.n_anchors, s.lX, s.lY,
+                                           in.unbanded ? 2 : bp.diagonalExpansion, Lp, Rp);
+            if (rc != CPECAN_OK) {
+                if (st.badItem < 0) { st.badItem = (int) i; st.badRc = rc; }
+                continue;
             }
-        };
-        if (nt <= 1) work(0);
-        else {
-            std::vector<std::thread> pool;
-            for (int w = 0; w < nt; w++) pool.emplace_back(work, w);
-            for (auto &t : pool) t.join();
+            long long cells = 0;
+            int maxW = 0;
+            long long *pre = general ? plan.pre.data() + d.diagBase : nullptr;
+            int *tab = plan.tab.p + d.diagBase * 2;
+            /* traceback schedule of getPosteriorProbsWithBanding (:917-918): longest span of forward
+             * diagonals that must be resident at once, and the edge-step property the register-resident
+             * kernels rely on */
+            long long tracedBackTo = 0;
+            int windows = 0, pmn = 0, pmx = 0;
+            for (long long k = 0; k < nDiag; k++) {
+                if (pre) pre[k] = cells;
+                const int wd = ((Rp[k] - Lp[k]) >> 1) + 1;
+                cells += wd;
+                maxW = std::max(maxW, wd);
+                const int xmn = (int) ((k + Lp[k]) / 2), xmx = (int) ((k + Rp[k]) / 2);
+                tab[k * 2] = xmn;
+                tab[k * 2 + 1] = xmx;
+                if (k >= 1) {
+                    if (xmn < pmn || xmn > pmn + 1 || xmx < pmx || xmx > pmx + 1) st.edgesStepByOne = false;
+                    const bool atEnd = k == nDiag - 1;
+                    const bool tb = k >= tracedBackTo + bp.minDiagsBetweenTraceBack && wd <= bp.diagonalExpansion * 2 + 1;
+                    if (atEnd || tb) {
+                        windows++;
+                        st.maxSpan = (int) std::max<long long>(st.maxSpan, k - tracedBackTo + 1);
+                        tracedBackTo = k - (bp.traceBackDiagonals + 1);
+                    }
+                }
+                pmn = xmn;
+                pmx = xmx;
+            }
+            d.nCells = cells;
+            d.maxWidth = maxW;
+            st.windows = std::max(st.windows, windows);
+            if (plan.wantAsm) build_asm_plan(tab, nDiag, bp, plan.asmWins[(size_t) i], plan.asmCtl.p + plan.asmOff[(size_t) i]);
         }
-        int bad = -1, badRc = 0;
-        for (const ItemStats &st : stats) {
-            maxSpan = std::max(maxSpan, st.maxSpan);
-            maxWindows = std::max(maxWindows, st.windows);
-            systolicOk = systolicOk && st.systolicOk;
-            if (st.badItem >= 0 && (bad < 0 || st.badItem < bad)) { bad = st.badItem; badRc = st.badRc; }
-        }
-        if (bad >= 0) return fail(badRc, "item %lld: anchors do not describe a valid band", (long long) bad);
-        return CPECAN_OK;
     };
-    /* (what the kernel choice below will come to, as far as it is known before the bands are) */
-    const bool surelyGeneral = dna || sm4 || echelon || kernel == CPECAN_KERNEL_GENERAL || unbanded || (flags & CPECAN_FLAG_DEBUG_DUMP) ||
-                               ((hdp || vanilla) && (flags & CPECAN_FLAG_GENERAL_KERNEL));
-    HIP_TRY(hTab.alloc((size_t) diagTotal * 2 + 2));
-    {
-        int rc = build_bands(surelyGeneral);
-        if (rc != CPECAN_OK) return rc;
+    if (nt <= 1) work(0);
+    else {
+        std::vector<std::thread> pool;
+        for (int w = 0; w < nt; w++) pool.emplace_back(work, w);
+        for (auto &t : pool) t.join();
     }
-    for (int64_t i = 0; i < nItems; i++) {
-        const cpecan_item &s = items[i];
-        DevItem &d = hItems[(size_t) i];
-        const long long nDiag = s.lX + s.lY + 1;
-        hTrackBase[(size_t) i] = trackTotal;
-        trackTotal += s.lX + 1;
-        maxLX = std::max<int>(maxLX, (int) s.lX);
-        maxLXY = std::max<long long>(maxLXY, std::max<long long>(s.lX, s.lY));
-        globalMaxWidth = std::max(globalMaxWidth, d.maxWidth);
-        d.cellBase = cellTotal;
-        cellTotal += d.nCells;
-        d.pairBase = pairTotal;
-        /* the HDP machine scores with linear densities (quirk Q6): its posteriors are flat and far more
-         * cells pass the threshold (2887 pairs for a ~800-event read in the reference's own test); a batch whose
-         * counts outgrow this first guess is re-run with the counted sizes (ensure_counts) */
-        d.pairCap = (hdp || echelon ? 16 : 4) * (s.lX + s.lY) + 64; /* (echelon: up to 15 pairs a cell) */
-        pairTotal += d.pairCap;
-        d.totBase = totTotal;
-        d.totCap = (nDiag + 9) / 10 + nDiag / std::max<long long>(1, params->minDiagsBetweenTraceBack -
-                                                                     params->traceBackDiagonals - 1) + 4;
-        totTotal += d.totCap;
-        d.bwsBase = bwsTotal;
-        bwsTotal += 3ll * d.maxWidth * S;
+    plan.maxSpan = 1;
+    plan.maxWindows = 0;
+    plan.edgesStepByOne = true;
+    int bad = -1, badRc = 0;
+    for (const ItemStats &st : stats) {
+        plan.maxSpan = std::max(plan.maxSpan, st.maxSpan);
+        plan.maxWindows = std::max(plan.maxWindows, st.windows);
+        plan.edgesStepByOne = plan.edgesStepByOne && st.edgesStepByOne;
+        if (st.badItem >= 0 && (bad < 0 || st.badItem < bad)) { bad = st.badItem; badRc = st.badRc; }
     }
+    if (bad >= 0) return fail(badRc, "item %lld: anchors do not describe a valid band", (long long) bad);
+    return CPECAN_OK;
+}
 
-    lap("band construction and window schedule (host)");
+/* the bands, then every item's share of the batch's buffers */
+static int plan_bands(const BatchInput &in, const MachineRow &m, bool general, bool wantAsm, BandPlan &plan) {
+    plan.wantAsm = wantAsm;
+    if (wantAsm) {
+        plan.asmWins.resize((size_t) in.nItems);
+        plan.asmOff.resize((size_t) in.nItems);
+        for (int64_t i = 0; i < in.nItems; i++) {
+            plan.asmOff[(size_t) i] = plan.asmCtlTotal;
+            plan.asmCtlTotal += (in.items[i].lX + in.items[i].lY) / ASM_BLOCK + 2;
+        }
+        HIP_TRY(plan.asmCtl.alloc((size_t) plan.asmCtlTotal));
+    }
+    HIP_TRY(plan.tab.alloc((size_t) plan.diagTotal * 2 + 2));
+    const int rc = build_bands(in, plan, general);
+    if (rc != CPECAN_OK) return rc;
+    plan.trackBase.resize((size_t) in.nItems);
+    for (int64_t i = 0; i < in.nItems; i++) {
+        const cpecan_item &s = in.items[i];
+        DevItem &d = plan.items[(size_t) i];
+        const long long nDiag = s.lX + s.lY + 1;
+        plan.trackBase[(size_t) i] = plan.trackTotal;
+        plan.trackTotal += s.lX + 1;
+        plan.maxLX = std::max<int>(plan.maxLX, (int) s.lX);
+        plan.maxLXY = std::max<long long>(plan.maxLXY, std::max<long long>(s.lX, s.lY));
+        plan.maxWidth = std::max(plan.maxWidth, d.maxWidth);
+        d.cellBase = plan.cellTotal;
+        plan.cellTotal += d.nCells;
+        d.pairBase = plan.pairTotal;
+        d.pairCap = m.pairCapFactor * (s.lX + s.lY) + 64;
+        plan.pairTotal += d.pairCap;
+        d.totBase = plan.totTotal;
+        d.totCap = (nDiag + 9) / 10 + nDiag / std::max<long long>(1, in.params->minDiagsBetweenTraceBack -
+                                                                     in.params->traceBackDiagonals - 1) + 4;
+        plan.totTotal += d.totCap;
+        d.bwsBase = plan.bwsTotal;
+        plan.bwsTotal += 3ll * d.maxWidth * m.states;
+    }
+    return CPECAN_OK;
+}
+
+/* the batch object, registered with its context; no device work yet */
+static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput &in, const BandPlan &plan, const Dispatch &d) {
+    const MachineRow &m = MACHINES[machine];
+    const cpecan_band_params &bp = *in.params;
     cpecan_batch *b = new (std::nothrow) cpecan_batch();
-    if (!b) return fail(CPECAN_EINVAL, "out of host memory");
+    if (!b) return nullptr;
     b->ctx = c;
     {
         std::lock_guard<std::mutex> g(g_batchesMu);
@@ -1680,301 +1829,269 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
     }
     b->device = c->device;
     b->modelEpoch = c->modelEpoch;
-    b->nItems = nItems;
-    b->mode = mode;
-    b->flags = flags;
-    b->compactPairs = maxLXY + (echelon ? 4 : 0) < 65536; /* (an echelon pair's x reaches lX + 3) */
-    b->nModels = dna ? c->nModels5 : vanilla ? c->nModelsV : sm4 ? c->nModels4 : echelon ? c->nModelsE : hdp ? (int) c->hostModelsH.size() : c->nModels;
-    b->expectLen = dna ? CPECAN_EXPECTATION5_LEN : vanilla ? CPECAN_EXPECTATIONV_LEN
-                   : hdp ? CPECAN_EXPECTATIONH_LEN : CPECAN_EXPECTATION_LEN;
-    b->P.threshold = params->threshold;
-    b->P.minDiags = params->minDiagsBetweenTraceBack;
-    b->P.tbDiags = params->traceBackDiagonals;
-    b->P.expansion = params->diagonalExpansion;
-    b->P.mode = mode;
-    b->P.debug = (flags & CPECAN_FLAG_DEBUG_DUMP) ? 1 : 0;
-    b->P.unbanded = unbanded ? 1 : 0;
-    b->P.scanDecode = (flags & CPECAN_FLAG_SCAN_DECODE) ? 1 : 0;
-    b->P.logThrSlack = params->threshold > 0.0 ? log(params->threshold) - 1e-3 : -INFINITY;
+    b->nItems = in.nItems;
+    b->mode = in.mode;
+    b->flags = d.flags;
+    b->machine = machine;
+    b->kernel = d.kernel;
+    b->wave5 = d.wave5;
+    b->maxWidth = plan.maxWidth;
+    b->compactPairs = plan.maxLXY + m.xReach < 65536;
+    b->nModels = m.nModels(c);
+    b->expectLen = m.expectLen;
+    b->P.threshold = bp.threshold;
+    b->P.minDiags = bp.minDiagsBetweenTraceBack;
+    b->P.tbDiags = bp.traceBackDiagonals;
+    b->P.expansion = bp.diagonalExpansion;
+    b->P.mode = in.mode;
+    b->P.debug = (d.flags & CPECAN_FLAG_DEBUG_DUMP) ? 1 : 0;
+    b->P.unbanded = in.unbanded ? 1 : 0;
+    b->P.scanDecode = (d.flags & CPECAN_FLAG_SCAN_DECODE) ? 1 : 0;
+    b->P.logThrSlack = bp.threshold > 0.0 ? log(bp.threshold) - 1e-3 : -INFINITY;
     b->P.ldsWidth = 0; /* (set per launch by the kernels that use it) */
     b->P.expectResweep = 0;
-
-    /* the HDP and vanilla machines have wave-per-alignment kernels of their own, for the posterior decode and for
-     * the E-step (the 5-state machine runs on the general kernel); CPECAN_FLAG_GENERAL_KERNEL keeps such a batch on
-     * the general kernel */
-    const bool machineWave = (hdp || vanilla) && !(flags & CPECAN_FLAG_GENERAL_KERNEL);
-    int useKernel = dna || sm4 || echelon || ((hdp || vanilla) && !machineWave) ? CPECAN_KERNEL_GENERAL
-                    : hdp || vanilla ? CPECAN_KERNEL_AUTO : kernel;
-    /* the builds of the register-resident kernels this batch would run on, and the widest band they take */
-    const SweepFamily &fam = hdp ? HV_BUILDS : vanilla ? VV_BUILDS
-                             : (use_wave_kernels() && !(flags & CPECAN_FLAG_WORKGROUP_KERNELS)) ? WV_BUILDS : SY_BUILDS;
-    const int famMaxWidth = fam[3]->maxWidth;
-    /* CPECAN_FLAG_WIDE_BANDS: a band past the family's widest build goes to the narrowest wide build of the workgroup
-     * family that holds it (six or eight waves; four, six or eight for the vanilla machine), whichever family the batch
-     * would otherwise run on; a band the family holds is left to it.  A vanilla batch reaches here with the flag only
-     * in posterior mode (wideBands above) and without it when CPECAN_FLAG_GENERAL_KERNEL is set (useKernel) */
-    const SweepBuild *const *wideTable = vanilla ? SYV_WIDE_BUILDS : SY_WIDE_BUILDS;
-    const SweepBuild *wideBuild = nullptr;
-    int sweepMaxWidth = famMaxWidth;
-    if (wideBands)
-        for (int i = 0; wideTable[i] != nullptr; i++) {
-            if (!wideBuild && globalMaxWidth > famMaxWidth && globalMaxWidth <= wideTable[i]->maxWidth)
-                wideBuild = wideTable[i];
-            sweepMaxWidth = std::max(sweepMaxWidth, wideTable[i]->maxWidth);
-        }
-    b->dna = dna;
-    b->vanilla = vanilla;
-    b->hdp = hdp;
-    b->sm4 = sm4;
-    b->echelon = echelon;
-    if (useKernel == CPECAN_KERNEL_AUTO)
-        useKernel = (globalMaxWidth <= sweepMaxWidth && systolicOk && !b->P.debug && !unbanded)
-                        ? CPECAN_KERNEL_SYSTOLIC : CPECAN_KERNEL_GENERAL;
-    /* (refusals from here on go through cpecan_hip_batch_destroy: it takes the batch off the context's list) */
-    if (useKernel == CPECAN_KERNEL_SYSTOLIC && (globalMaxWidth > sweepMaxWidth || !systolicOk)) {
-        const int rc = fail(CPECAN_EINVAL, "band is %d cells wide (systolic kernel: at most %d, edges moving "
-                            "one k-mer per diagonal)", globalMaxWidth, sweepMaxWidth);
-        cpecan_hip_batch_destroy(b);
-        return rc;
-    }
-    if (useKernel == CPECAN_KERNEL_SYSTOLIC && b->P.debug) {
-        const int rc = fail(CPECAN_EINVAL, "cell dumps are only available from the general kernel");
-        cpecan_hip_batch_destroy(b);
-        return rc;
-    }
-    b->kernel = useKernel;
-    b->maxWidth = globalMaxWidth;
-    /* the build with the fewest waves per workgroup whose slots hold the widest band: the fewer waves an alignment
-     * takes, the more alignments a CU holds (CPECAN_SYSTOLIC_ROWS=N asks for at least N waves: tests, timing) */
-    if (wideBuild && useKernel == CPECAN_KERNEL_SYSTOLIC) {
-        b->sy = wideBuild;
-        b->trackRow = b->sy->once->trackRowDoubles;
-    } else {
-        const char *rows = getenv("CPECAN_SYSTOLIC_ROWS");
-        int r = rows ? atoi(rows) : 1;
-        r = r < 1 ? 1 : r > 4 ? 4 : r;
-        while (r < 4 && globalMaxWidth > fam[r - 1]->maxWidth) r++;
-        b->sy = fam[r - 1];
+    if (d.build) {
+        b->sy = d.build;
         b->trackRow = b->sy->once->trackRowDoubles;
     }
-    if (useKernel == CPECAN_KERNEL_SYSTOLIC && mode == CPECAN_MODE_EXPECTATIONS && !b->sy->expect && !b->sy->backward_fx) {
-        /* (cannot happen: the builds without an E-step are only chosen for posterior batches, see wideBands) */
-        const int rc = fail(CPECAN_EINVAL, "the chosen kernel build has no E-step");
-        cpecan_hip_batch_destroy(b);
-        return rc;
-    }
-    b->hItems = hItems;
+    b->hItems = plan.items;
+    return b;
+}
 
+/* From here on the batch exists: a step that fails has destroyed it (B_TRY) before it returns its code. */
+
+static int upload_sequences(cpecan_batch *b, const BatchInput &in) {
+    cpecan_ctx *c = b->ctx;
+    const MachineRow &m = MACHINES[b->machine];
+    const int64_t nItems = in.nItems, nX = in.nX, nEvents = in.nEvents;
     B_TRY(b->items.alloc((size_t) nItems));
-    B_TRY(hipMemcpyAsync(b->items.p, hItems.data(), (size_t) nItems * sizeof(DevItem), hipMemcpyHostToDevice, c->prep));
+    B_TRY(hipMemcpyAsync(b->items.p, b->hItems.data(), (size_t) nItems * sizeof(DevItem), hipMemcpyHostToDevice, c->prep));
     B_TRY(b->chars.alloc((size_t) nX + 8));
     B_TRY(hipMemsetAsync(b->chars.p, 0, (size_t) nX + 8, c->prep));
-    B_TRY(hipMemcpyAsync(b->chars.p, xChars, (size_t) nX, hipMemcpyHostToDevice, c->prep));
+    B_TRY(hipMemcpyAsync(b->chars.p, in.xChars, (size_t) nX, hipMemcpyHostToDevice, c->prep));
     B_TRY(b->kidx.alloc((size_t) nX + 8));
-    if (dna) {
+    if (in.yChars) {
         B_TRY(b->charsY.alloc((size_t) nEvents + 8));
         B_TRY(hipMemsetAsync(b->charsY.p, 0, (size_t) nEvents + 8, c->prep));
-        B_TRY(hipMemcpyAsync(b->charsY.p, yChars, (size_t) nEvents, hipMemcpyHostToDevice, c->prep));
+        B_TRY(hipMemcpyAsync(b->charsY.p, in.yChars, (size_t) nEvents, hipMemcpyHostToDevice, c->prep));
+    } else if (m.yAux) {
+        /* emissions_signal_logInvGaussPdf takes log(eventNoise) per cell (host libm, :325): an array of its own for the
+         * general kernel, and in the batch's own copy of the events in place of the duration, which nothing on the
+         * device reads (the wave kernels stage events from this one array) */
+        std::vector<double, NoInit<double>> ev3((size_t) 3 * nEvents), ln((size_t) nEvents + 1);
+        for (int64_t i = 0; i < nEvents; i++) {
+            ln[(size_t) i] = log(in.events[3 * i + 1]);
+            ev3[(size_t) 3 * i] = in.events[3 * i];
+            ev3[(size_t) 3 * i + 1] = in.events[3 * i + 1];
+            ev3[(size_t) 3 * i + 2] = ln[(size_t) i];
+        }
+        B_TRY(b->events.alloc((size_t) 3 * nEvents + 8));
+        B_TRY(b->logNoise.alloc((size_t) nEvents + 8));
+        B_TRY(hipMemcpyAsync(b->events.p, ev3.data(), (size_t) 3 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
+        B_TRY(hipMemcpyAsync(b->logNoise.p, ln.data(), (size_t) nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
+        B_TRY(hipStreamSynchronize(c->prep)); /* ev3 and ln end here */
     } else {
         B_TRY(b->events.alloc((size_t) 3 * nEvents + 8));
-        if (vanilla || echelon) {
-            /* the batch's own copy of the events carries log(noise) (host libm, :325) in place of the duration, which
-             * nothing on the device reads: the wave kernels stage events from this one array */
-            std::vector<double, NoInit<double>> ev3((size_t) 3 * nEvents);
-            for (int64_t i = 0; i < nEvents; i++) {
-                ev3[(size_t) 3 * i] = events[3 * i];
-                ev3[(size_t) 3 * i + 1] = events[3 * i + 1];
-                ev3[(size_t) 3 * i + 2] = log(events[3 * i + 1]);
-            }
-            B_TRY(hipMemcpyAsync(b->events.p, ev3.data(), (size_t) 3 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
-            B_TRY(hipStreamSynchronize(c->prep)); /* ev3 ends here */
-        } else
-            B_TRY(hipMemcpyAsync(b->events.p, events, (size_t) 3 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
-        if (echelon) { /* emissions_signal_getDurationProb (:551-554) of 0..5 k-mers per event */
-            std::vector<double> du((size_t) 6 * nEvents + 6);
-            for (int64_t i = 0; i < nEvents; i++)
-                for (int k = 0; k < 6; k++) du[(size_t) (6 * i + k)] = echelon_duration(events + 3 * i, k);
-            B_TRY(b->duration.alloc((size_t) 6 * nEvents + 8));
-            B_TRY(hipMemcpyAsync(b->duration.p, du.data(), (size_t) 6 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
-            std::vector<long long> xe((size_t) nItems);
-            for (int64_t i = 0; i < nItems; i++) xe[(size_t) i] = items[i].lX > 0 ? items[i].lX + 5 + items[i].reserved : 0;
-            B_TRY(b->xEnd.alloc((size_t) nItems));
-            B_TRY(hipMemcpyAsync(b->xEnd.p, xe.data(), (size_t) nItems * sizeof(long long), hipMemcpyHostToDevice, c->prep));
-            B_TRY(hipStreamSynchronize(c->prep)); /* du and xe end here */
-        }
-        if (vanilla || echelon) { /* emissions_signal_logInvGaussPdf takes log(eventNoise) per cell (:325) */
-            std::vector<double> ln((size_t) nEvents + 1);
-            for (int64_t i = 0; i < nEvents; i++) ln[(size_t) i] = log(events[3 * i + 1]);
-            B_TRY(b->logNoise.alloc((size_t) nEvents + 8));
-            B_TRY(hipMemcpyAsync(b->logNoise.p, ln.data(), (size_t) nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
-            B_TRY(hipStreamSynchronize(c->prep)); /* ln ends here */
-        }
+        B_TRY(hipMemcpyAsync(b->events.p, in.events, (size_t) 3 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
+    }
+    if (b->machine == ECHELON) { /* emissions_signal_getDurationProb (:551-554) of 0..5 k-mers per event */
+        std::vector<double> du((size_t) 6 * nEvents + 6);
+        for (int64_t i = 0; i < nEvents; i++)
+            for (int k = 0; k < 6; k++) du[(size_t) (6 * i + k)] = echelon_duration(in.events + 3 * i, k);
+        B_TRY(b->duration.alloc((size_t) 6 * nEvents + 8));
+        B_TRY(hipMemcpyAsync(b->duration.p, du.data(), (size_t) 6 * nEvents * sizeof(double), hipMemcpyHostToDevice, c->prep));
+        std::vector<long long> xe((size_t) nItems);
+        for (int64_t i = 0; i < nItems; i++) xe[(size_t) i] = in.items[i].lX > 0 ? in.items[i].lX + 5 + in.items[i].reserved : 0;
+        B_TRY(b->xEnd.alloc((size_t) nItems));
+        B_TRY(hipMemcpyAsync(b->xEnd.p, xe.data(), (size_t) nItems * sizeof(long long), hipMemcpyHostToDevice, c->prep));
+        B_TRY(hipStreamSynchronize(c->prep)); /* du and xe end here */
     }
     B_TRY(hipStreamSynchronize(c->prep));
-    lap("upload sequences and events");
-    /* (the anchors stay on the host: the bands they describe were built there, above) */
-    B_TRY(b->pairs.alloc((size_t) pairTotal * 3));
-    B_TRY(b->pairLogp.alloc((size_t) pairTotal));
-    B_TRY(b->nPairs.alloc((size_t) nItems));
-    B_TRY(b->nTot.alloc((size_t) nItems));
-    B_TRY(b->nCells.alloc((size_t) nItems));
-    B_TRY(b->totXay.alloc((size_t) totTotal));
-    B_TRY(b->totVal.alloc((size_t) totTotal));
+    return CPECAN_OK;
+}
+
+/* (the anchors stay on the host: the bands they describe were built there) */
+static int alloc_outputs(cpecan_batch *b, const BandPlan &plan) {
+    cpecan_ctx *c = b->ctx;
+    const size_t nItems = (size_t) b->nItems;
+    B_TRY(b->pairs.alloc((size_t) plan.pairTotal * 3));
+    B_TRY(b->pairLogp.alloc((size_t) plan.pairTotal));
+    B_TRY(b->nPairs.alloc(nItems));
+    B_TRY(b->nTot.alloc(nItems));
+    B_TRY(b->nCells.alloc(nItems));
+    B_TRY(b->totXay.alloc((size_t) plan.totTotal));
+    B_TRY(b->totVal.alloc((size_t) plan.totTotal));
     B_TRY(b->expect.alloc((size_t) std::max(b->nModels, 1) * b->expectLen));
     B_TRY(hipMemsetAsync(b->expect.p, 0, b->expect.n * sizeof(double), c->prep));
-    b->hNCells.resize((size_t) nItems);
-    for (int64_t i = 0; i < nItems; i++) b->hNCells[(size_t) i] = hItems[(size_t) i].nCells;
+    b->hNCells.resize(nItems);
+    for (size_t i = 0; i < nItems; i++) b->hNCells[i] = b->hItems[i].nCells;
     B_TRY(hipStreamSynchronize(c->prep));
-    lap("output buffers");
+    return CPECAN_OK;
+}
 
-    if (useKernel == CPECAN_KERNEL_GENERAL) {
-        if (!keptGeneral) { /* the band turned out too wide (or too ragged) for the register-resident kernels */
-            int rc = build_bands(true);
-            if (rc != CPECAN_OK) {
-                cpecan_hip_batch_destroy(b);
-                return rc;
-            }
-        }
-        B_TRY(b->bandL.alloc(hL.size()));
-        B_TRY(b->bandR.alloc(hR.size()));
-        B_TRY(b->cellPrefix.alloc(hPre.size()));
-        B_TRY(hipMemcpyAsync(b->bandL.p, hL.data(), hL.size() * sizeof(int), hipMemcpyHostToDevice, c->prep));
-        B_TRY(hipMemcpyAsync(b->bandR.p, hR.data(), hR.size() * sizeof(int), hipMemcpyHostToDevice, c->prep));
-        B_TRY(hipMemcpyAsync(b->cellPrefix.p, hPre.data(), hPre.size() * sizeof(long long), hipMemcpyHostToDevice, c->prep));
-        B_TRY(b->Fstore.alloc((size_t) cellTotal * S));
-        B_TRY(b->Bstore.alloc((size_t) bwsTotal));
-        if (b->P.debug) {
-            B_TRY(b->dbgB.alloc((size_t) cellTotal * 3));
-            B_TRY(hipMemsetAsync(b->dbgB.p, 0xff, (size_t) cellTotal * 3 * sizeof(double), c->prep));
-        }
-    } else {
-        /* one workgroup per alignment and launch; the ring of forward diagonals lives per alignment
-         * because the forward and backward kernels of a window are separate launches */
-        b->nWorkers = (int) nItems;
-        b->nWindows = maxWindows;
-        b->ringD = 64;
-        /* the kernels mask with ringD-1.  The wave kernels sweep window w back while the forward sweep of window w+1
-         * is writing: the ring holds two windows -- three where the assembly sweeps may run (decided below; the same
-         * conditions but for what is not known yet): there the forward sweep of window w+2 does not wait for the totals
-         * and the decode of window w, whose re-sweep kernel may still read that window's rows */
-        const bool asmOffEarly = getenv("CPECAN_ASM") != nullptr && atoi(getenv("CPECAN_ASM")) == 0;
-        const bool asmLikely = wantPlan && !asmOffEarly && b->sy->wave && b->sy->rows == ASM_L && globalMaxWidth <= ASM_MAX_WIDTH;
-        const int ringWindows = !b->sy->wave || maxWindows <= 1 ? 1
-                                : asmLikely && maxWindows > 2 && !(flags & CPECAN_FLAG_SMALL_FOOTPRINT) ? 3 : 2;
-        while (b->ringD < (ringWindows > 1 ? ringWindows * maxSpan + 8 : maxSpan + 4)) b->ringD *= 2;
-        /* the wave kernels keep one more row behind the ring: the -inf row lanes without a cell read */
-        b->ringDoubles = (long long) (b->ringD + (b->sy->wave ? 1 : 0)) * b->sy->ringRowDoubles;
-        if (getenv("CPECAN_RING_PAD")) b->ringDoubles += atoll(getenv("CPECAN_RING_PAD"));
-        b->maxLX = maxLX;
-        B_TRY(b->Fstore.alloc((size_t) nItems * (size_t) b->ringDoubles));
-        lap("ring allocation");
-        /* the band as matrix columns per diagonal */
-        B_TRY(b->bandTab.alloc((size_t) diagTotal * 2 + 2));
-        B_TRY(hipMemcpyAsync(b->bandTab.p, hTab.p, (size_t) diagTotal * 2 * sizeof(int), hipMemcpyHostToDevice, c->prep));
-        {
-            const char *g = getenv("CPECAN_SYSTOLIC_GROUPS");
-            int G = g ? atoi(g) : b->sy->wave ? 1 : 2;
-            if (G < 1) G = 1;
-            if (G > 8) G = 8;
-            if ((int64_t) G > nItems) G = (int) nItems;
-            b->nGroups = G;
-            b->gStream.assign((size_t) G, nullptr);
-            b->evJoin.assign((size_t) G, nullptr);
-            /* a wave batch of one group runs on lane sets (batch_run): no streams of its own, so that a chain of
-             * batches stays within the four hardware queues a process gets */
-            b->gStreamOwned = !(b->sy->wave && G == 1);
-            if (b->gStreamOwned)
-                for (auto &st : b->gStream) B_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            else {
-                b->gStream.clear();
-                B_TRY(lanes_sweeps(c->lanes));
-            }
-            if (b->sy->wave && b->gStreamOwned) {
-                b->gStreamB.assign((size_t) G, nullptr);
-                for (auto &st : b->gStreamB) B_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            }
-            for (auto &e : b->evJoin) B_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            B_TRY(hipEventCreateWithFlags(&b->evFork, hipEventDisableTiming));
-        }
-        B_TRY(hipStreamSynchronize(c->prep));
-        lap("band table upload, streams");
-        /* the strawMan machine's E-step on the wave kernels sums its expectations inside the sweep back (same box,
-         * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 (read per
-         * batch) keeps the ring of backward cells and the expectation kernel */
-        const char *fxEnv = getenv("CPECAN_EXPECT_FUSED");
-        if (mode == CPECAN_MODE_EXPECTATIONS && !(fxEnv != nullptr && atoi(fxEnv) == 0) && b->sy->backward_fx) {
-            b->fused = true;
-            b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr ? atoi(getenv("CPECAN_EXPECT_RESWEEP")) : 0;
-        }
-        if (mode == CPECAN_MODE_EXPECTATIONS && !b->fused)
-            B_TRY(b->Bring.alloc((size_t) nItems * (size_t) b->ringD * (size_t) b->sy->bringRowDoubles));
-        b->stateBytes = b->sy->once->stateBytes;
-        B_TRY(b->syStates.alloc((size_t) nItems * (size_t) b->stateBytes));
-        b->scratchBytes = (b->sy->scratch_bytes(b->ringD) + (b->fused ? b->sy->fx_scratch_bytes(b->ringD) : 0) + 63) / 64 * 64;
-        B_TRY(b->syScratch.alloc((size_t) nItems * (size_t) b->scratchBytes));
-        B_TRY(b->track.alloc((size_t) trackTotal * (size_t) b->trackRow));
-        B_TRY(b->trackBase.alloc((size_t) nItems));
-        B_TRY(hipMemcpyAsync(b->trackBase.p, hTrackBase.data(), (size_t) nItems * sizeof(long long),
-                             hipMemcpyHostToDevice, c->prep));
-        B_TRY(hipStreamSynchronize(c->prep));
-        lap("state, scratch, track allocation");
-        /* the hand-scheduled assembly sweeps take the strawMan machine's posterior batches whose bands need three cells
-         * per lane and fit their staging scheme (CPECAN_ASM=0: the compiled kernels, for tests and timing) */
-        const bool asmOff = getenv("CPECAN_ASM") != nullptr && atoi(getenv("CPECAN_ASM")) == 0; /* (read per batch) */
-        if (wantPlan && !asmOff && b->sy->wave && b->sy->rows == ASM_L && globalMaxWidth <= ASM_MAX_WIDTH && b->nGroups == 1 &&
-            b->stateBytes == (int) sizeof(WvState) && b->sy->ringRowDoubles * 8 == ASM_ROW_BYTES /* (one ring format) */ &&
-            cpecan_asm_load(c->device) == 0) {
-            b->asmMaxWindows = std::max(maxWindows, 1);
-            PinnedBuf<AsmPlanWin> hWin;
-            StreamFence winFence{ c->prep, nullptr };
-            B_TRY(hWin.alloc((size_t) nItems * (size_t) b->asmMaxWindows));
-            memset(hWin.p, 0, (size_t) nItems * (size_t) b->asmMaxWindows * sizeof(AsmPlanWin));
-            for (int64_t i = 0; i < nItems; i++)
-                std::copy(planWins[(size_t) i].begin(), planWins[(size_t) i].end(), hWin.p + (size_t) i * (size_t) b->asmMaxWindows);
-            B_TRY(b->planWin.alloc(hWin.n));
-            B_TRY(b->planCtl.alloc((size_t) ctlTotal));
-            B_TRY(b->planOff.alloc((size_t) nItems));
-            B_TRY(b->asmCtx.alloc((size_t) nItems * 3 * ASM_CTX_BYTES));
-            B_TRY(b->asmMasks.alloc((size_t) (diagTotal + 2) * (ASM_MASK_BYTES / 4)));
-            B_TRY(hipMemsetAsync(b->asmMasks.p + (size_t) diagTotal * (ASM_MASK_BYTES / 4), 0, 2 * ASM_MASK_BYTES, c->prep));
-            B_TRY(hipMemcpyAsync(b->planWin.p, hWin.p, hWin.n * sizeof(AsmPlanWin), hipMemcpyHostToDevice, c->prep));
-            B_TRY(hipMemcpyAsync(b->planCtl.p, hCtl.p, (size_t) ctlTotal * sizeof(AsmPlanCtl), hipMemcpyHostToDevice, c->prep));
-            B_TRY(hipMemcpyAsync(b->planOff.p, hPlanOff.data(), (size_t) nItems * sizeof(long long), hipMemcpyHostToDevice, c->prep));
-            hipError_t asmErr = cpecan_asm_launch_masks(c->prep, b->items.p, nItems, maxDiags, b->bandTab.p, b->asmMasks.p);
-            if (asmErr == hipSuccess)
-                asmErr = cpecan_asm_launch_ctx_init(c->prep, b->items.p, nItems, b->asmCtx.p, ASM_CTX_BYTES, b->Fstore.p,
-                                                    b->ringDoubles, b->ringD);
-            B_TRY(hipStreamSynchronize(c->prep)); /* hWin ends here */
-            if (asmErr != hipSuccess) {
-                /* the compiled kernels need none of this: the batch runs on them (cpecan_hip_batch_assembly_sweeps
-                 * reports 0 and leaves the reason in last_error) */
-                b->asmSetupError = std::string("assembly sweeps not set up: ") + hipGetErrorString(asmErr);
-                if (getenv("CPECAN_ASM_TRACE")) fprintf(stderr, "[cpecan asm] %s\n", b->asmSetupError.c_str());
-            }
-        }
-        if (b->asmMaxWindows > 0 && b->asmSetupError.empty()) {
-            if (b->ringD >= 3 * maxSpan + 8 || maxWindows <= 2) {
-                /* the post kernel of a window runs beside the next window's sweeps (batch_run): the sweep back of window
-                 * w+1 fills one half of the scratch while the post kernel of window w reads the other */
-                B_TRY(b->syScratch.alloc(2 * (size_t) nItems * (size_t) b->scratchBytes));
-                b->postAside = true;
-                b->evPost.assign((size_t) b->asmMaxWindows, nullptr);
-                for (auto &e : b->evPost) B_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            }
-            b->useAsm = true;
-            /* CPECAN_ASM=1: the forward sweep only (the compiled sweep back reads what it writes: tests, timing) */
-            b->asmBackward = !(getenv("CPECAN_ASM") != nullptr && atoi(getenv("CPECAN_ASM")) == 1);
-            if (getenv("CPECAN_ASM_TRACE"))
-                fprintf(stderr, "[cpecan asm] batch of %lld alignments, widest band %d, %d windows: assembly sweeps\n",
-                        (long long) nItems, globalMaxWidth, b->asmMaxWindows);
-            lap("assembly sweeps: plan upload, contexts");
+/* the general kernel: the bands as x-y intervals with their cell prefix sums, every forward cell, a backward workspace */
+static int general_storage(cpecan_batch *b, const BatchInput &in, BandPlan &plan) {
+    cpecan_ctx *c = b->ctx;
+    if (!plan.general) { /* the band turned out too wide (or too ragged) for the register-resident kernels */
+        const int rc = build_bands(in, plan, true);
+        if (rc != CPECAN_OK) {
+            cpecan_hip_batch_destroy(b);
+            return rc;
         }
     }
-    B_TRY(hipEventCreate(&b->ev0));
-    B_TRY(hipEventCreate(&b->ev1));
-    B_TRY(hipEventCreate(&b->ev2));
+    B_TRY(b->bandL.alloc(plan.L.size()));
+    B_TRY(b->bandR.alloc(plan.R.size()));
+    B_TRY(b->cellPrefix.alloc(plan.pre.size()));
+    B_TRY(hipMemcpyAsync(b->bandL.p, plan.L.data(), plan.L.size() * sizeof(int), hipMemcpyHostToDevice, c->prep));
+    B_TRY(hipMemcpyAsync(b->bandR.p, plan.R.data(), plan.R.size() * sizeof(int), hipMemcpyHostToDevice, c->prep));
+    B_TRY(hipMemcpyAsync(b->cellPrefix.p, plan.pre.data(), plan.pre.size() * sizeof(long long), hipMemcpyHostToDevice, c->prep));
+    B_TRY(b->Fstore.alloc((size_t) plan.cellTotal * MACHINES[b->machine].states));
+    B_TRY(b->Bstore.alloc((size_t) plan.bwsTotal));
+    if (b->P.debug) {
+        B_TRY(b->dbgB.alloc((size_t) plan.cellTotal * 3));
+        B_TRY(hipMemsetAsync(b->dbgB.p, 0xff, (size_t) plan.cellTotal * 3 * sizeof(double), c->prep));
+    }
+    return CPECAN_OK;
+}
 
-    if (hdp) { /* k-mer ids over the HDP's alphabet, once per batch like the k-mer indices below */
+/* the register-resident kernels: one workgroup per alignment and launch; the ring of forward diagonals lives per
+ * alignment because the forward and backward kernels of a window are separate launches */
+static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, Lap &lap) {
+    cpecan_ctx *c = b->ctx;
+    const int64_t nItems = b->nItems;
+    const int maxWindows = plan.maxWindows, maxSpan = plan.maxSpan;
+    b->nWorkers = (int) nItems;
+    b->nWindows = maxWindows;
+    b->ringD = 64;
+    /* the kernels mask with ringD-1.  The wave kernels sweep window w back while the forward sweep of window w+1
+     * is writing: the ring holds two windows -- three where the assembly sweeps may run (set up in asm_setup; the same
+     * conditions but for what is not known yet): there the forward sweep of window w+2 does not wait for the totals
+     * and the decode of window w, whose re-sweep kernel may still read that window's rows */
+    const int ringWindows = !b->sy->wave || maxWindows <= 1 ? 1
+                            : d.asmSweeps && maxWindows > 2 && !(b->flags & CPECAN_FLAG_SMALL_FOOTPRINT) ? 3 : 2;
+    while (b->ringD < (ringWindows > 1 ? ringWindows * maxSpan + 8 : maxSpan + 4)) b->ringD *= 2;
+    /* the wave kernels keep one more row behind the ring: the -inf row lanes without a cell read */
+    b->ringDoubles = (long long) (b->ringD + (b->sy->wave ? 1 : 0)) * b->sy->ringRowDoubles;
+    if (getenv("CPECAN_RING_PAD")) b->ringDoubles += atoll(getenv("CPECAN_RING_PAD"));
+    b->maxLX = plan.maxLX;
+    B_TRY(b->Fstore.alloc((size_t) nItems * (size_t) b->ringDoubles));
+    lap("ring allocation");
+    /* the band as matrix columns per diagonal */
+    B_TRY(b->bandTab.alloc((size_t) plan.diagTotal * 2 + 2));
+    B_TRY(hipMemcpyAsync(b->bandTab.p, plan.tab.p, (size_t) plan.diagTotal * 2 * sizeof(int), hipMemcpyHostToDevice, c->prep));
+    {
+        const char *g = getenv("CPECAN_SYSTOLIC_GROUPS");
+        int G = g ? atoi(g) : b->sy->wave ? 1 : 2;
+        if (G < 1) G = 1;
+        if (G > 8) G = 8;
+        if ((int64_t) G > nItems) G = (int) nItems;
+        b->nGroups = G;
+        b->gStream.assign((size_t) G, nullptr);
+        b->evJoin.assign((size_t) G, nullptr);
+        /* a wave batch of one group runs on lane sets (batch_run): no streams of its own, so that a chain of
+         * batches stays within the four hardware queues a process gets */
+        b->gStreamOwned = !(b->sy->wave && G == 1);
+        if (b->gStreamOwned)
+            for (auto &st : b->gStream) B_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        else {
+            b->gStream.clear();
+            B_TRY(lanes_sweeps(c->lanes));
+        }
+        if (b->sy->wave && b->gStreamOwned) {
+            b->gStreamB.assign((size_t) G, nullptr);
+            for (auto &st : b->gStreamB) B_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        }
+        for (auto &e : b->evJoin) B_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        B_TRY(hipEventCreateWithFlags(&b->evFork, hipEventDisableTiming));
+    }
+    B_TRY(hipStreamSynchronize(c->prep));
+    lap("band table upload, streams");
+    /* the strawMan machine's E-step on the wave kernels sums its expectations inside the sweep back (same box,
+     * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 (read per
+     * batch) keeps the ring of backward cells and the expectation kernel */
+    const char *fxEnv = getenv("CPECAN_EXPECT_FUSED");
+    if (b->mode == CPECAN_MODE_EXPECTATIONS && !(fxEnv != nullptr && atoi(fxEnv) == 0) && b->sy->backward_fx) {
+        b->fused = true;
+        b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr ? atoi(getenv("CPECAN_EXPECT_RESWEEP")) : 0;
+    }
+    if (b->mode == CPECAN_MODE_EXPECTATIONS && !b->fused)
+        B_TRY(b->Bring.alloc((size_t) nItems * (size_t) b->ringD * (size_t) b->sy->bringRowDoubles));
+    b->stateBytes = b->sy->once->stateBytes;
+    B_TRY(b->syStates.alloc((size_t) nItems * (size_t) b->stateBytes));
+    b->scratchBytes = (b->sy->scratch_bytes(b->ringD) + (b->fused ? b->sy->fx_scratch_bytes(b->ringD) : 0) + 63) / 64 * 64;
+    B_TRY(b->syScratch.alloc((size_t) nItems * (size_t) b->scratchBytes));
+    B_TRY(b->track.alloc((size_t) plan.trackTotal * (size_t) b->trackRow));
+    B_TRY(b->trackBase.alloc((size_t) nItems));
+    B_TRY(hipMemcpyAsync(b->trackBase.p, plan.trackBase.data(), (size_t) nItems * sizeof(long long),
+                         hipMemcpyHostToDevice, c->prep));
+    B_TRY(hipStreamSynchronize(c->prep));
+    lap("state, scratch, track allocation");
+    return CPECAN_OK;
+}
+
+/* The hand-scheduled assembly sweeps, for a batch the kernel choice found fit for them (Dispatch::asmSweeps) and
+ * that runs as one stream group on the one ring format, where the module loads: the plan, the forward waves'
+ * contexts, the masks. */
+static int asm_setup(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, Lap &lap) {
+    cpecan_ctx *c = b->ctx;
+    const int64_t nItems = b->nItems;
+    if (!d.asmSweeps || b->nGroups != 1 || b->stateBytes != (int) sizeof(WvState) ||
+        b->sy->ringRowDoubles * 8 != ASM_ROW_BYTES /* (one ring format) */ || cpecan_asm_load(c->device) != 0)
+        return CPECAN_OK;
+    b->asmMaxWindows = std::max(plan.maxWindows, 1);
+    {
+        PinnedBuf<AsmPlanWin> hWin;
+        StreamFence winFence{ c->prep, nullptr };
+        B_TRY(hWin.alloc((size_t) nItems * (size_t) b->asmMaxWindows));
+        memset(hWin.p, 0, (size_t) nItems * (size_t) b->asmMaxWindows * sizeof(AsmPlanWin));
+        for (int64_t i = 0; i < nItems; i++)
+            std::copy(plan.asmWins[(size_t) i].begin(), plan.asmWins[(size_t) i].end(), hWin.p + (size_t) i * (size_t) b->asmMaxWindows);
+        B_TRY(b->planWin.alloc(hWin.n));
+        B_TRY(b->planCtl.alloc((size_t) plan.asmCtlTotal));
+        B_TRY(b->planOff.alloc((size_t) nItems));
+        B_TRY(b->asmCtx.alloc((size_t) nItems * 3 * ASM_CTX_BYTES));
+        B_TRY(b->asmMasks.alloc((size_t) (plan.diagTotal + 2) * (ASM_MASK_BYTES / 4)));
+        B_TRY(hipMemsetAsync(b->asmMasks.p + (size_t) plan.diagTotal * (ASM_MASK_BYTES / 4), 0, 2 * ASM_MASK_BYTES, c->prep));
+        B_TRY(hipMemcpyAsync(b->planWin.p, hWin.p, hWin.n * sizeof(AsmPlanWin), hipMemcpyHostToDevice, c->prep));
+        B_TRY(hipMemcpyAsync(b->planCtl.p, plan.asmCtl.p, (size_t) plan.asmCtlTotal * sizeof(AsmPlanCtl), hipMemcpyHostToDevice, c->prep));
+        B_TRY(hipMemcpyAsync(b->planOff.p, plan.asmOff.data(), (size_t) nItems * sizeof(long long), hipMemcpyHostToDevice, c->prep));
+        hipError_t asmErr = cpecan_asm_launch_masks(c->prep, b->items.p, nItems, plan.maxDiags, b->bandTab.p, b->asmMasks.p);
+        if (asmErr == hipSuccess)
+            asmErr = cpecan_asm_launch_ctx_init(c->prep, b->items.p, nItems, b->asmCtx.p, ASM_CTX_BYTES, b->Fstore.p,
+                                                b->ringDoubles, b->ringD);
+        B_TRY(hipStreamSynchronize(c->prep)); /* hWin ends here */
+        if (asmErr != hipSuccess) {
+            /* the compiled kernels need none of this: the batch runs on them (cpecan_hip_batch_assembly_sweeps
+             * reports 0 and leaves the reason in last_error) */
+            b->asmSetupError = std::string("assembly sweeps not set up: ") + hipGetErrorString(asmErr);
+            if (getenv("CPECAN_ASM_TRACE")) fprintf(stderr, "[cpecan asm] %s\n", b->asmSetupError.c_str());
+            return CPECAN_OK;
+        }
+    }
+    if (b->ringD >= 3 * plan.maxSpan + 8 || plan.maxWindows <= 2) {
+        /* the post kernel of a window runs beside the next window's sweeps (batch_run): the sweep back of window
+         * w+1 fills one half of the scratch while the post kernel of window w reads the other */
+        B_TRY(b->syScratch.alloc(2 * (size_t) nItems * (size_t) b->scratchBytes));
+        b->postAside = true;
+        b->evPost.assign((size_t) b->asmMaxWindows, nullptr);
+        for (auto &e : b->evPost) B_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    b->useAsm = true;
+    b->asmBackward = d.asmBackward;
+    if (getenv("CPECAN_ASM_TRACE"))
+        fprintf(stderr, "[cpecan asm] batch of %lld alignments, widest band %d, %d windows: assembly sweeps\n",
+                (long long) nItems, b->maxWidth, b->asmMaxWindows);
+    lap("assembly sweeps: plan upload, contexts");
+    return CPECAN_OK;
+}
+
+/* what the kernels read per X position, part of input preparation (done once, like H2D): k-mer indices, or k-mer ids
+ * over the HDP's alphabet */
+static int index_kmers(cpecan_batch *b, int64_t nX) {
+    cpecan_ctx *c = b->ctx;
+    const XSource x = MACHINES[b->machine].x;
+    const int blocks = (int) ((nX + 255) / 256);
+    if (x == X_KID) {
         unsigned long long lo = 0, hi = 0;
         for (size_t q = 0; q < c->hdpAlphabet.size(); q++) {
             const unsigned long long ch = (unsigned char) c->hdpAlphabet[q];
@@ -1982,38 +2099,83 @@ static int batch_create_impl(cpecan_ctx *c, const cpecan_item *items, int64_t nI
             else hi |= ch << (8 * (q - 8));
         }
         B_TRY(b->kid.alloc((size_t) nX + 8));
-        const int blocks = (int) ((nX + 255) / 256);
         if (blocks > 0)
             hipLaunchKernelGGL(cpecan_k_hdp_kmer_id, dim3(blocks), dim3(256), 0, c->prep,
                                (const char *) b->chars.p, (long long) nX, lo, hi, (int) c->hdpAlphabet.size(),
                                b->kid.p);
-        B_TRY(hipGetLastError());
-        B_TRY(hipStreamSynchronize(c->prep));
-    }
-    /* k-mer indices are part of input preparation (done once, like H2D) */
-    if (!dna && !hdp) {
-        long long n = (long long) nX;
-        int threads = 256;
-        int blocks = (int) ((n + threads - 1) / threads);
-        if (blocks > 0)
-            hipLaunchKernelGGL(cpecan_k_kmer_index, dim3(blocks), dim3(threads), 0, c->prep,
-                               (const char *) b->chars.p, n, b->kidx.p);
-        B_TRY(hipGetLastError());
-        B_TRY(hipStreamSynchronize(c->prep));
-    }
-    B_TRY(hipStreamSynchronize(c->prep)); /* every upload above has landed */
+    } else if (x == X_KIDX && blocks > 0)
+        hipLaunchKernelGGL(cpecan_k_kmer_index, dim3(blocks), dim3(256), 0, c->prep,
+                           (const char *) b->chars.p, (long long) nX, b->kidx.p);
+    B_TRY(hipGetLastError());
+    B_TRY(hipStreamSynchronize(c->prep)); /* every upload of batch creation has landed */
+    return CPECAN_OK;
+}
+
+/* events != NULL: k-mers against events with a signal machine; yChars != NULL: DNA against DNA with the 5-state symbol
+ * machine (nEvents then counts the bases of yChars) */
+static int batch_create_impl(cpecan_ctx *c, Machine machine, const cpecan_item *items, int64_t nItems,
+                             const char *xChars, int64_t nX, const double *events, const char *yChars,
+                             int64_t nEvents, const int64_t *anchors, int64_t nAnchorPairs,
+                             const cpecan_band_params *params, int32_t mode, int32_t kernel,
+                             int32_t flags, cpecan_batch **out) {
+    const MachineRow &m = MACHINES[machine];
+    if (!c || !items || nItems <= 0 || !xChars || (machine == DNA5 ? !yChars : !events) || !params || !out)
+        return fail(CPECAN_EINVAL, "bad argument");
+    int rc = check_machine(machine, mode, flags);
+    if (rc != CPECAN_OK) return rc;
+    if (nAnchorPairs > 0 && !anchors) return fail(CPECAN_EINVAL, "anchors is NULL");
+    if (params->diagonalExpansion < 0 || (params->diagonalExpansion & 1) ||
+        params->traceBackDiagonals < 1 || params->minDiagsBetweenTraceBack < 2 ||
+        params->traceBackDiagonals + 1 >= params->minDiagsBetweenTraceBack)
+        return fail(CPECAN_EINVAL, "banding parameters violate the prerequisites of "
+                                   "getPosteriorProbsWithBanding (pairwiseAligner.c:880-884)");
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(c->device));
+    const BatchInput in = { items, nItems, xChars, nX, events, yChars, nEvents, anchors, nAnchorPairs, params, mode,
+                            (flags & CPECAN_FLAG_UNBANDED) != 0 };
+    /* what the kernel choice comes to before the bands are known: its refusals, whether the general kernel's tables
+     * are wanted at once, whether the assembly sweeps' plan is */
+    DispatchQuery q = { machine, mode, kernel, flags, 0, true, read_batch_env() };
+    const Dispatch early = choose_dispatch(q);
+    if (early.refusal != CPECAN_OK) return fail(early.refusal, "%s", early.why);
+
+    Lap lap("batch_create");
+    BandPlan plan;
+    StreamFence prepFence{ c->prep, nullptr }; /* (the plan's pinned blocks are uploaded through it) */
+    if ((rc = check_items(c, machine, in, plan)) != CPECAN_OK) return rc;
+    if ((rc = plan_bands(in, m, early.kernel == CPECAN_KERNEL_GENERAL, early.asmPlan, plan)) != CPECAN_OK) return rc;
+    lap("band construction and window schedule (host)");
+    q.maxWidth = plan.maxWidth;
+    q.edgesStepByOne = plan.edgesStepByOne;
+    const Dispatch d = choose_dispatch(q);
+    if (d.refusal != CPECAN_OK) return fail(d.refusal, "%s", d.why);
+
+    cpecan_batch *b = new_batch(c, machine, in, plan, d);
+    if (!b) return fail(CPECAN_EINVAL, "out of host memory");
+    if ((rc = upload_sequences(b, in)) != CPECAN_OK) return rc;
+    lap("upload sequences and events");
+    if ((rc = alloc_outputs(b, plan)) != CPECAN_OK) return rc;
+    lap("output buffers");
+    if (d.kernel == CPECAN_KERNEL_GENERAL) rc = general_storage(b, in, plan);
+    else if ((rc = sweep_storage(b, plan, d, lap)) == CPECAN_OK) rc = asm_setup(b, plan, d, lap);
+    if (rc != CPECAN_OK) return rc;
+    B_TRY(hipEventCreate(&b->ev0));
+    B_TRY(hipEventCreate(&b->ev1));
+    B_TRY(hipEventCreate(&b->ev2));
+    if ((rc = index_kmers(b, nX)) != CPECAN_OK) return rc;
     lap("k-mer index kernel");
     *out = b;
     return CPECAN_OK;
 }
+
+extern "C" {
 
 int cpecan_hip_batch_create(cpecan_ctx *c, const cpecan_item *items, int64_t nItems,
                             const char *xChars, int64_t nX, const double *events, int64_t nEvents,
                             const int64_t *anchors, int64_t nAnchorPairs,
                             const cpecan_band_params *params, int32_t mode, int32_t kernel,
                             int32_t flags, cpecan_batch **out) {
-    if (!events) return fail(CPECAN_EINVAL, "bad argument");
-    return batch_create_impl(c, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs,
+    return batch_create_impl(c, STRAWMAN, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs,
                              params, mode, kernel, flags, out);
 }
 
@@ -2021,28 +2183,25 @@ int cpecan_hip_batch_create_vanilla(cpecan_ctx *c, const cpecan_item *items, int
                                     const char *xChars, int64_t nX, const double *events, int64_t nEvents,
                                     const int64_t *anchors, int64_t nAnchorPairs,
                                     const cpecan_band_params *params, int32_t flags, cpecan_batch **out) {
-    if (!events) return fail(CPECAN_EINVAL, "bad argument");
-    return batch_create_impl(c, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
+    return batch_create_impl(c, VANILLA, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
                              (flags & CPECAN_FLAG_EXPECTATIONS) ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
-                             CPECAN_KERNEL_GENERAL, flags & ~CPECAN_FLAG_EXPECTATIONS, out, true);
+                             CPECAN_KERNEL_AUTO, flags & ~CPECAN_FLAG_EXPECTATIONS, out);
 }
 
 int cpecan_hip_batch_create_hdp(cpecan_ctx *c, const cpecan_item *items, int64_t nItems,
                                 const char *xChars, int64_t nX, const double *events, int64_t nEvents,
                                 const int64_t *anchors, int64_t nAnchorPairs,
                                 const cpecan_band_params *params, int32_t flags, cpecan_batch **out) {
-    if (!events) return fail(CPECAN_EINVAL, "bad argument");
-    return batch_create_impl(c, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
+    return batch_create_impl(c, HDP, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
                              (flags & CPECAN_FLAG_EXPECTATIONS) ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
-                             CPECAN_KERNEL_GENERAL, flags & ~CPECAN_FLAG_EXPECTATIONS, out, false, true);
+                             CPECAN_KERNEL_AUTO, flags & ~CPECAN_FLAG_EXPECTATIONS, out);
 }
 
 int cpecan_hip_batch_create_dna(cpecan_ctx *c, const cpecan_item *items, int64_t nItems,
                                 const char *xChars, int64_t nX, const char *yChars, int64_t nY,
                                 const int64_t *anchors, int64_t nAnchorPairs,
                                 const cpecan_band_params *params, int32_t flags, cpecan_batch **out) {
-    if (!yChars) return fail(CPECAN_EINVAL, "bad argument");
-    return batch_create_impl(c, items, nItems, xChars, nX, nullptr, yChars, nY, anchors, nAnchorPairs, params,
+    return batch_create_impl(c, DNA5, items, nItems, xChars, nX, nullptr, yChars, nY, anchors, nAnchorPairs, params,
                              (flags & CPECAN_FLAG_EXPECTATIONS) ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
                              CPECAN_KERNEL_GENERAL, flags & ~CPECAN_FLAG_EXPECTATIONS, out);
 }
@@ -2051,8 +2210,8 @@ int cpecan_hip_batch_create_sm4(cpecan_ctx *c, const cpecan_item *items, int64_t
                                 const double *events, int64_t nEvents, const int64_t *anchors, int64_t nAnchorPairs,
                                 const cpecan_band_params *params, int32_t flags, cpecan_batch **out) {
     if (flags & CPECAN_FLAG_EXPECTATIONS) return fail(CPECAN_EINVAL, "4-state batches: posterior decode only");
-    return batch_create_impl(c, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
-                             CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out, false, false, true);
+    return batch_create_impl(c, SM4, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
+                             CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out);
 }
 
 int cpecan_hip_batch_create_echelon(cpecan_ctx *c, const cpecan_item *items, int64_t nItems, const char *xChars,
@@ -2061,9 +2220,8 @@ int cpecan_hip_batch_create_echelon(cpecan_ctx *c, const cpecan_item *items, int
                                     cpecan_batch **out) {
     if (flags & CPECAN_FLAG_EXPECTATIONS)
         return fail(CPECAN_EINVAL, "echelon batches: posterior decode only (the reference has no expectations for this machine)");
-    if (!events) return fail(CPECAN_EINVAL, "bad argument");
-    return batch_create_impl(c, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
-                             CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out, false, false, false, true);
+    return batch_create_impl(c, ECHELON, items, nItems, xChars, nX, events, nullptr, nEvents, anchors, nAnchorPairs, params,
+                             CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out);
 }
 
 } // extern "C"
@@ -2092,52 +2250,30 @@ static int enqueue_wave5(cpecan_batch *b, hipStream_t st) {
     return CPECAN_OK;
 }
 
-/* The general kernels (cpecan_general.h): one per machine, one parameter list */
+/* The general kernels (cpecan_general.h): one per machine, one parameter list filled from the machine's row */
 static int enqueue_general(cpecan_batch *b, hipStream_t st) {
     cpecan_ctx *c = b->ctx;
-    if (b->echelon) { /* (cpecan_kernel_generale.hip) */
-        DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
-                             (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p,
-                             (const double *) b->logNoise.p, c->modelsE.p, b->Fstore.p, b->Bstore.p, b->pairs.p,
-                             b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p, nullptr, nullptr };
-        DevEchelonArgs e = { (const char *) b->chars.p, (const long long *) b->xEnd.p, (const double *) b->duration.p };
-        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, st, a, b->P, e);
-        HIP_TRY(hipGetLastError());
-        return CPECAN_OK;
-    }
+    const MachineRow &m = MACHINES[b->machine];
     const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
+    const void *x = m.x == X_CHARS ? (const void *) b->chars.p : m.x == X_KID ? (const void *) b->kid.p : (const void *) b->kidx.p;
+    const void *y = m.x == X_CHARS ? (const void *) b->charsY.p : (const void *) b->events.p; /* (nucleotides on both sides) */
     DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
-                         (const long long *) b->cellPrefix.p, b->kidx.p, b->events.p, nullptr, c->models.p,
-                         b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p,
-                         b->nTot.p, nullptr, em ? b->expect.p : nullptr };
+                         (const long long *) b->cellPrefix.p, x, y, m.yAux ? (const double *) b->logNoise.p : nullptr,
+                         m.models(c), b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p,
+                         b->totVal.p, b->nTot.p, b->dbgB.p, em ? b->expect.p : nullptr };
     DevParams P = b->P;
-    size_t lds = 0;
-    auto kernel = cpecan_k_general;
-    if (b->dna) {
-        /* the forward sweep's two previous diagonals live in LDS where the widest band fits (3 diagonals of 5
-         * states: 120 bytes per cell of width); CPECAN_GENERAL_LDS=0 keeps them in HBM (timing, tests) */
-        static const bool ldsOff = getenv("CPECAN_GENERAL_LDS") != nullptr && atoi(getenv("CPECAN_GENERAL_LDS")) == 0;
-        P.ldsWidth = (!ldsOff && b->maxWidth <= 248) ? b->maxWidth : 0;
-        lds = (size_t) P.ldsWidth * 120;
-        kernel = cpecan_k_general5;
-        a.x = b->chars.p;
-        a.y = b->charsY.p;
-        a.models = c->models5.p;
-    } else if (b->hdp && b->kernel == CPECAN_KERNEL_GENERAL) {
-        kernel = cpecan_k_generalh;
-        a.x = b->kid.p;
-        a.models = c->modelsH.p;
-    } else if (b->sm4) {
-        kernel = cpecan_k_general4;
-        a.models = c->models4.p;
-    } else if (b->vanilla && b->kernel == CPECAN_KERNEL_GENERAL) {
-        kernel = cpecan_k_generalv;
-        a.yAux = (const double *) b->logNoise.p;
-        a.models = c->modelsV.p;
-    } else {
-        a.dbgB = b->dbgB.p;
+    /* the forward sweep's two previous diagonals live in LDS where the widest band fits (three diagonals of the
+     * machine's states: 120 bytes per cell of width for the 5-state machine); CPECAN_GENERAL_LDS=0 keeps them in HBM
+     * (timing, tests) */
+    static const bool ldsOff = getenv("CPECAN_GENERAL_LDS") != nullptr && atoi(getenv("CPECAN_GENERAL_LDS")) == 0;
+    P.ldsWidth = (!ldsOff && b->maxWidth <= m.ldsMaxWidth) ? b->maxWidth : 0;
+    const size_t lds = (size_t) P.ldsWidth * 3 * m.states * sizeof(double);
+    if (m.general)
+        hipLaunchKernelGGL(m.general, dim3((unsigned) b->nItems), dim3(256), lds, st, a, P);
+    else { /* (cpecan_kernel_generale.hip) */
+        DevEchelonArgs e = { (const char *) b->chars.p, (const long long *) b->xEnd.p, (const double *) b->duration.p };
+        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, st, a, P, e);
     }
-    hipLaunchKernelGGL(kernel, dim3((unsigned) b->nItems), dim3(256), lds, st, a, P);
     HIP_TRY(hipGetLastError());
     return CPECAN_OK;
 }
@@ -2168,7 +2304,7 @@ static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *
     /* the models as the sweeps read them, and whether any of them lets gap Y switch to gap X (the nanopore default
      * does not, stateMachine.c:1287: the kernels then run the build without that term; the vanilla machine has no such
      * transition) */
-    all.models = sy->machine == SWEEP_HDP ? (const double *) c->modelsH.p : sy->machine == SWEEP_VANILLA ? c->modelsV.p : c->models.p;
+    all.models = (const double *) MACHINES[b->machine].models(c);
     if (sy->machine == SWEEP_HDP) {
         for (const DevHdpModel &m : c->hostModelsH)
             if (m.t[T_GAP_SWITCH_TO_X] > -INFINITY) all.withSwitch = 1;
@@ -2298,10 +2434,9 @@ static int batch_enqueue(cpecan_batch *b, cpecan_batch *after, LaneSet *L) {
     if (b->mode == CPECAN_MODE_EXPECTATIONS)
         HIP_TRY(hipMemsetAsync(b->expect.p, 0, b->expect.n * sizeof(double), L->fwd));
     HIP_TRY(hipEventRecord(b->ev1, L->fwd));
-    static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr; /* (tests, timing: the general kernel) */
-    if (b->dna && !b->P.debug && !b->P.unbanded && b->maxWidth <= 192 && !wave5Off && !(b->flags & CPECAN_FLAG_GENERAL_KERNEL))
+    if (b->wave5)
         rc = enqueue_wave5(b, L->fwd);
-    else if (b->echelon || b->dna || b->sm4 || b->kernel == CPECAN_KERNEL_GENERAL)
+    else if (b->kernel == CPECAN_KERNEL_GENERAL)
         rc = enqueue_general(b, L->fwd);
     else
         rc = enqueue_sweeps(b, L, &sEnd, &laneRun);
@@ -2387,9 +2522,8 @@ int cpecan_hip_batch_systolic_rows(cpecan_batch *b, int32_t *rows) {
 
 int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
     if (!b || !wave) return fail(CPECAN_EINVAL, "bad argument");
-    if (b->dna) { /* the 5-state machine: one wave per alignment (cpecan_kernel_wave5.hip) where batch_run picks it */
-        static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr;
-        *wave = (!b->P.debug && !b->P.unbanded && b->maxWidth <= 192 && !wave5Off && !(b->flags & CPECAN_FLAG_GENERAL_KERNEL)) ? 1 : 0;
+    if (b->machine == DNA5) { /* the 5-state machine: one wave per alignment (cpecan_kernel_wave5.hip) where the choice fell on it */
+        *wave = b->wave5 ? 1 : 0;
         return CPECAN_OK;
     }
     if (b->kernel != CPECAN_KERNEL_SYSTOLIC) return fail(CPECAN_EINVAL, "not a register-resident batch");
@@ -2458,6 +2592,27 @@ int cpecan_hip_batch_info(cpecan_batch *b, int32_t *kernel, int32_t *workgroups,
     if (kernel) *kernel = b->kernel;
     if (workgroups) *workgroups = b->kernel == CPECAN_KERNEL_GENERAL ? (int32_t) b->nItems : b->nWorkers;
     if (maxWidth) *maxWidth = b->maxWidth;
+    return CPECAN_OK;
+}
+
+int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t maxWidth,
+                             int32_t edgesStepByOne, int32_t *kernelOut, int32_t *waveOut, int32_t *rowsOut,
+                             int32_t *buildMaxWidthOut) {
+    if (machine < 0 || machine >= N_MACHINES) return fail(CPECAN_EINVAL, "unknown machine %d", machine);
+    if (maxWidth < 0) return fail(CPECAN_EINVAL, "bad argument");
+    const int rc = check_machine((Machine) machine, mode, flags);
+    if (rc != CPECAN_OK) return rc;
+    DispatchQuery q = { (Machine) machine, mode, kernel, flags, 0, true, read_batch_env() };
+    const Dispatch early = choose_dispatch(q); /* (batch creation asks in this order) */
+    if (early.refusal != CPECAN_OK) return fail(early.refusal, "%s", early.why);
+    q.maxWidth = maxWidth;
+    q.edgesStepByOne = edgesStepByOne != 0;
+    const Dispatch d = choose_dispatch(q);
+    if (d.refusal != CPECAN_OK) return fail(d.refusal, "%s", d.why);
+    if (kernelOut) *kernelOut = d.kernel;
+    if (waveOut) *waveOut = d.wave5 || (d.build && d.build->wave) ? 1 : 0;
+    if (rowsOut) *rowsOut = d.build ? d.build->rows : 0;
+    if (buildMaxWidthOut) *buildMaxWidthOut = d.build ? d.build->maxWidth : 0;
     return CPECAN_OK;
 }
 
@@ -2614,7 +2769,7 @@ static int ensure_counts(cpecan_batch *b) {
                                    hipMemcpyDeviceToHost, rs));
         }
         HIP_TRY(hipStreamSynchronize(rs));
-        if (b->hdp && b->kernel == CPECAN_KERNEL_SYSTOLIC) {
+        if (b->machine == HDP && b->kernel == CPECAN_KERNEL_SYSTOLIC) {
             /* the HDP machine's event assignments from the wave kernels: appended by whichever thread got there, each
              * tagged with its traceback window (first field = from-state + 4 * window).  The reference walks windows
              * upwards, inside a window the diagonals downwards, a diagonal by ascending x, a cell by from-state

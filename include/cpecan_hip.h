@@ -361,6 +361,24 @@ int cpecan_hip_batch_shader_clock_mhz(cpecan_batch *batch, double *mhz);
 /* Which kernel the batch uses (CPECAN_KERNEL_GENERAL / _SYSTOLIC after AUTO is resolved), how many
  * workgroups it launches and the widest band (cells) among its items. */
 int cpecan_hip_batch_info(cpecan_batch *batch, int32_t *kernel, int32_t *workgroups, int32_t *max_width);
+/* The machines of the create calls above, in the order of: cpecan_hip_batch_create, _dna, _vanilla, _hdp, _sm4, _echelon. */
+#define CPECAN_MACHINE_STRAWMAN 0
+#define CPECAN_MACHINE_DNA5 1
+#define CPECAN_MACHINE_VANILLA 2
+#define CPECAN_MACHINE_HDP 3
+#define CPECAN_MACHINE_SM4 4
+#define CPECAN_MACHINE_ECHELON 5
+/* The kernel choice of batch creation, without a batch and without a device: what a batch of that machine, mode
+ * (CPECAN_MODE_*; the create calls that take CPECAN_FLAG_EXPECTATIONS turn it into the mode), requested kernel (the
+ * strawMan machine's; the others ignore it) and flags would run on if its widest band were max_width cells and its band
+ * edges did (1) or did not (0) all move by at most one k-mer per diagonal.  Reads the environment as batch creation
+ * does.  *kernel_out: as batch_info reports it; *wave_out, *rows_out: as batch_kernel_family and batch_systolic_rows
+ * do (rows 0 on the general kernel); *build_max_width_out: the widest band the chosen build takes (0 on the general
+ * kernel).  Any of the four may be NULL.  A combination batch creation refuses is refused here with the same code and
+ * last_error. */
+int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t max_width,
+                             int32_t edges_step_by_one, int32_t *kernel_out, int32_t *wave_out, int32_t *rows_out,
+                             int32_t *build_max_width_out);
 /* Systolic path only: waves per workgroup of the kernel build the batch runs on -- the fewest whose 64 slots each
  * hold the widest band of the batch: 1 (bands up to 56 k-mers), 2 (120), 3 (184) or 4 (248).  The fewer waves an
  * alignment takes, the more alignments a CU holds (16, 8, 5, 4).  With CPECAN_FLAG_WIDE_BANDS also 6 (bands of 249..376
