@@ -74,7 +74,9 @@ extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *stat
  * CPECAN_FLAG_WIDE_BANDS and only when its widest band is past every build of the tables above.  The same source built
  * with -DSY_VANILLA gives the vanilla machine's wide builds (_v4, _v6, _v8: four, six and eight waves per workgroup,
  * bands up to 248, 376 and 504 k-mers; their table starts one class earlier because the vanilla wave builds end at 184),
- * reached the same way and for the posterior decode only: a vanilla E-step past 184 k-mers stays on the general kernel. */
+ * reached the same way and for the posterior decode only: a vanilla E-step past 184 k-mers stays on the general kernel.
+ * Built with -DSY_HDP it gives the HDP machine's wide builds (_h6, _h8: bands of 249..376 and 377..504 k-mers, past the
+ * HDP wave builds), which answer to a flag of their own, CPECAN_FLAG_WIDE_BANDS_HDP, again for the posterior decode only. */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
@@ -82,6 +84,7 @@ SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(
 SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
 SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
+SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
@@ -89,6 +92,7 @@ static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_bui
 static const SweepBuild *const SY_WIDE_BUILDS[3] = { &cpecan_systolic_build_r6, &cpecan_systolic_build_r8, nullptr };
 static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4, &cpecan_systolic_build_v6,
                                                       &cpecan_systolic_build_v8, nullptr };
+static const SweepBuild *const SYH_WIDE_BUILDS[3] = { &cpecan_systolic_build_h6, &cpecan_systolic_build_h8, nullptr };
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
@@ -421,6 +425,7 @@ struct MachineRow {
     SweepFamily *wave, *workgroup;
     const SweepBuild *const *wide;
     int wideModes;
+    int wideFlag;   /* the flag its wide builds answer to: CPECAN_FLAG_WIDE_BANDS, or CPECAN_FLAG_WIDE_BANDS_HDP (0: none) */
     bool ownChoice; /* its create call has no kernel argument: AUTO, or the general kernel with CPECAN_FLAG_GENERAL_KERNEL */
     /* the general kernel and what distinguishes its argument record */
     void (*general)(DevGeneralArgs, DevParams); /* (null: cpecan_k_generale, which takes a third record) */
@@ -433,24 +438,24 @@ struct MachineRow {
 #define BOTH_MODES (1 << CPECAN_MODE_POSTERIOR | 1 << CPECAN_MODE_EXPECTATIONS)
 static const MachineRow MACHINES[N_MACHINES] = {
     /* STRAWMAN */ { 3, CPECAN_EXPECTATION_LEN, 4, 0, nullptr, nullptr, false, &WV_BUILDS, &SY_BUILDS, SY_WIDE_BUILDS, BOTH_MODES,
-                     false, cpecan_k_general, X_KIDX, false, 0, [](const cpecan_ctx *c) { return c->nModels; },
+                     CPECAN_FLAG_WIDE_BANDS, false, cpecan_k_general, X_KIDX, false, 0, [](const cpecan_ctx *c) { return c->nModels; },
                      [](const cpecan_ctx *c) { return (const void *) c->models.p; } },
     /* DNA5 */     { 5, CPECAN_EXPECTATION5_LEN, 4, 0, nullptr, "DNA batches: no cell dumps", true, nullptr, nullptr, nullptr, 0,
-                     false, cpecan_k_general5, X_CHARS, false, 248, [](const cpecan_ctx *c) { return c->nModels5; },
+                     0, false, cpecan_k_general5, X_CHARS, false, 248, [](const cpecan_ctx *c) { return c->nModels5; },
                      [](const cpecan_ctx *c) { return (const void *) c->models5.p; } },
     /* VANILLA */  { 3, CPECAN_EXPECTATIONV_LEN, 4, 0, nullptr, "vanilla batches: no cell dumps", true, &VV_BUILDS, nullptr,
-                     SYV_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, true, cpecan_k_generalv, X_KIDX, true, 0,
+                     SYV_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS, true, cpecan_k_generalv, X_KIDX, true, 0,
                      [](const cpecan_ctx *c) { return c->nModelsV; },
                      [](const cpecan_ctx *c) { return (const void *) c->modelsV.p; } },
-    /* HDP */      { 3, CPECAN_EXPECTATIONH_LEN, 16, 0, nullptr, "HDP batches: no cell dumps", true, &HV_BUILDS, nullptr, nullptr, 0,
-                     true, cpecan_k_generalh, X_KID, false, 0, [](const cpecan_ctx *c) { return (int) c->hostModelsH.size(); },
+    /* HDP */      { 3, CPECAN_EXPECTATIONH_LEN, 16, 0, nullptr, "HDP batches: no cell dumps", true, &HV_BUILDS, nullptr,
+                     SYH_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS_HDP, true, cpecan_k_generalh, X_KID, false, 0, [](const cpecan_ctx *c) { return (int) c->hostModelsH.size(); },
                      [](const cpecan_ctx *c) { return (const void *) c->modelsH.p; } },
     /* SM4 */      { 4, CPECAN_EXPECTATION_LEN, 4, 0, "4-state batches: posterior decode only, no cell dumps",
-                     "4-state batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, false,
+                     "4-state batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, 0, false,
                      cpecan_k_general4, X_KIDX, false, 0, [](const cpecan_ctx *c) { return c->nModels4; },
                      [](const cpecan_ctx *c) { return (const void *) c->models4.p; } },
     /* ECHELON */  { 7, CPECAN_EXPECTATION_LEN, 16, 4, "echelon batches: posterior decode only, no cell dumps",
-                     "echelon batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, false,
+                     "echelon batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, 0, false,
                      nullptr, X_KIDX, true, 0, [](const cpecan_ctx *c) { return c->nModelsE; },
                      [](const cpecan_ctx *c) { return (const void *) c->modelsE.p; } },
 };
@@ -470,6 +475,7 @@ static int check_machine(Machine machine, int mode, int flags) {
  * batches); CPECAN_DNA_GENERAL once per process. */
 struct BatchEnv {
     bool wideBands;   /* CPECAN_WIDE_BANDS=1: CPECAN_FLAG_WIDE_BANDS for every batch the wide builds serve */
+    bool wideBandsHdp; /* CPECAN_WIDE_BANDS_HDP=1: CPECAN_FLAG_WIDE_BANDS_HDP for every HDP batch its wide builds serve */
     bool waveKernels; /* false under CPECAN_KERNELS=systolic: the workgroup-per-alignment family for every batch */
     int systolicRows; /* CPECAN_SYSTOLIC_ROWS=N: a build of at least N rows (tests, timing) */
     int asmMode;      /* CPECAN_ASM: 0 the compiled kernels, 1 the assembly forward sweep only (the compiled sweep back
@@ -479,8 +485,8 @@ struct BatchEnv {
 static BatchEnv read_batch_env() {
     static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr;
     const char *wide = getenv("CPECAN_WIDE_BANDS"), *kernels = getenv("CPECAN_KERNELS");
-    const char *rows = getenv("CPECAN_SYSTOLIC_ROWS"), *as = getenv("CPECAN_ASM");
-    return { wide && atoi(wide) == 1, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1,
+    const char *rows = getenv("CPECAN_SYSTOLIC_ROWS"), *as = getenv("CPECAN_ASM"), *wideH = getenv("CPECAN_WIDE_BANDS_HDP");
+    return { wide && atoi(wide) == 1, wideH && atoi(wideH) == 1, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1,
              as ? atoi(as) : -1, wave5Off };
 }
 
@@ -525,20 +531,22 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
     if (unbanded && (q.mode != CPECAN_MODE_POSTERIOR || asked == CPECAN_KERNEL_SYSTOLIC))
         return refuse("un-banded alignment: posterior mode on the general kernel only");
     /* the wide builds of the workgroup family are the strawMan machine's and, for the posterior decode, the vanilla
-     * machine's: the flag means nothing to the others, nor to a vanilla E-step, whose batches past the wave builds run
-     * on the general kernel as without it */
+     * machine's and the HDP machine's.  A machine's wide builds answer to the flag of its row (the HDP machine's to one
+     * of its own) and each flag has its environment variable: a flag means nothing to the machines of the other flag
+     * or of none, nor to a vanilla or HDP E-step, whose batches past the wave builds run on the general kernel as
+     * without it */
     const bool wideServes = m.wide != nullptr && (m.wideModes >> q.mode & 1);
-    if (wideServes && q.env.wideBands) d.flags |= CPECAN_FLAG_WIDE_BANDS;
+    if (wideServes && (m.wideFlag == CPECAN_FLAG_WIDE_BANDS ? q.env.wideBands : q.env.wideBandsHdp)) d.flags |= m.wideFlag;
     if (asked != CPECAN_KERNEL_GENERAL) {
         /* the family the batch would run on, and the widest band its builds take */
         const bool workgroup = m.workgroup && (!q.env.waveKernels || (q.flags & CPECAN_FLAG_WORKGROUP_KERNELS));
         const SweepFamily &fam = workgroup ? *m.workgroup : *m.wave;
-        /* CPECAN_FLAG_WIDE_BANDS: a band past the family's widest build goes to the narrowest wide build of the workgroup
-         * family that holds it (six or eight waves; four, six or eight for the vanilla machine), whichever family the
-         * batch would otherwise run on; a band the family holds is left to it */
+        /* the machine's wide-bands flag: a band past the family's widest build goes to the narrowest wide build of the
+         * workgroup family that holds it (six or eight waves; four, six or eight for the vanilla machine), whichever
+         * family the batch would otherwise run on; a band the family holds is left to it */
         const SweepBuild *wideBuild = nullptr;
         int reach = fam[3]->maxWidth;
-        if (wideServes && (d.flags & CPECAN_FLAG_WIDE_BANDS))
+        if (wideServes && (d.flags & m.wideFlag))
             for (int i = 0; m.wide[i] != nullptr; i++) {
                 if (!wideBuild && q.maxWidth > fam[3]->maxWidth && q.maxWidth <= m.wide[i]->maxWidth) wideBuild = m.wide[i];
                 reach = std::max(reach, m.wide[i]->maxWidth);
@@ -1450,6 +1458,9 @@ int cpecan_hip_modelsh_create(cpecan_ctx *c, const cpecan_hdp_model *models, int
         if (!m.alphabet || m.alphabet_size < 1 || m.alphabet_size > 16 || m.grid_length < 2 || !m.grid ||
             m.n_rows < 1 || !m.posterior_predictive || !m.spline_slopes || !m.kmer_row)
             return fail(CPECAN_EINVAL, "HDP model %d is incomplete", i);
+        /* the register-resident kernels carry a table row's offset (row x grid_length, in doubles) as a 32-bit index */
+        if ((long long) m.n_rows * m.grid_length > 0xffffffffLL)
+            return fail(CPECAN_EINVAL, "HDP model %d: tables of more than 2^32 - 1 values", i);
         const std::string a(m.alphabet, (size_t) m.alphabet_size);
         if (!c->hdpAlphabet.empty() && c->hdpAlphabet != a)
             return fail(CPECAN_EINVAL, "all HDP models of a context must share one alphabet");

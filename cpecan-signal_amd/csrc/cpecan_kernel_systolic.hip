@@ -49,7 +49,24 @@
  * constants and the five log transition probabilities of the column's skip bin, so transitions are per lane, not
  * per wave; a_ym, a_yy and the end vector come from the model header.  The E-step of this machine stays on the general
  * kernel: these builds have no ring of backward cells and no expectation kernel. */
-#if defined(SY_VANILLA) && SY_R == 4
+/* -DSY_HDP: the forward sweep of the 3-state HDP signal machine (stateMachine3HDP_cellCalculate, impl/stateMachine.c:
+ * 1338-1370) with six and eight waves per workgroup (bands of 249..376 and 377..504 k-mers; symbols suffixed _h6, _h8;
+ * the HDP wave builds reach 248, so there is no four-wave build), posterior decode only.  One spline density of the
+ * NanoporeHDP is the match and the gap-Y emission, the gap-X emission is a flat log(0.1): a slot keeps one value, the
+ * offset of its k-mer's table row, and the gap-X sums are the same for every k-mer, so they are wave-uniform.  The
+ * sweep back, the totals and the decode are the strawMan's source unchanged: they read the nine transitions from the
+ * head of the model record (DevHdpModel starts with them; only the stride between models differs, which is why these
+ * builds compile the sweep back themselves) and the gap-X emission from entry CP_GAPX of the track row
+ * (cpecan_k_sy_track_hdp writes log(0.1) there). */
+#if defined(SY_HDP) && defined(SY_VANILLA)
+#error "SY_HDP and SY_VANILLA are builds of their own"
+#elif defined(SY_HDP) && SY_R == 6
+#define SY_SYM(n) n##_h6
+#elif defined(SY_HDP) && SY_R == 8
+#define SY_SYM(n) n##_h8
+#elif defined(SY_HDP)
+#error "SY_HDP: 6 or 8 waves per workgroup"
+#elif defined(SY_VANILLA) && SY_R == 4
 #define SY_SYM(n) n##_v4
 #elif defined(SY_VANILLA) && SY_R == 6
 #define SY_SYM(n) n##_v6
@@ -100,12 +117,22 @@
 #define SY_EVW 4     /* doubles per staged event: mean, noise, 1 / noise, log(noise) */
 #define SY_MODEL_DOUBLES ((long long) CP_VMODEL_STRIDE)
 #define SY_MODE(P) 0 /* posterior decode only */
+#elif defined(SY_HDP)
+#define SY_ROW CP_ROW /* the strawMan track's row: entry 0 the k-mer's table row offset, entry CP_GAPX log(0.1) */
+#define SY_NPRM 1    /* a slot keeps the table row offset */
+#define SY_EVW 2     /* doubles per staged event: grid cell of its mean, offset in the cell */
+#define SY_MODEL_DOUBLES ((long long) (sizeof(DevHdpModel) / sizeof(double)))
+#define SY_MODE(P) 0 /* posterior decode only */
+#define SY_HDP_GAPX (-2.3025850929940455) /* log(0.1), stateMachine.c:1347 */
 #else
 #define SY_ROW CP_ROW
 #define SY_NPRM 17
 #define SY_EVW 2     /* doubles per staged event: mean, noise */
 #define SY_MODEL_DOUBLES ((long long) CP_MODEL_STRIDE)
 #define SY_MODE(P) (P).mode
+#endif
+#if defined(SY_VANILLA) || defined(SY_HDP)
+#define SY_NO_ESTEP /* these builds have no expectation kernel and no ring of backward cells */
 #endif
 #define SY_PREFETCH 4     /* diagonals the backward sweep fetches ahead (== its unroll factor) */
 #define SY_CAND_SLACK 0.25 /* candidates: cells within this (log units) below the posterior threshold */
@@ -172,9 +199,14 @@ struct Shared {
 #define SY_FEED 32
 #define SY_FEED_EV 128  /* ring of events, by event index            */
 #define SY_FEED_ROW 64  /* ring of k-mer constant rows, by k-mer index */
+#ifdef SY_HDP
+#define SY_FEEDW 1 /* doubles of a track row the ring keeps: the table row offset */
+#else
+#define SY_FEEDW SY_ROW
+#endif
 struct Feed {
     double ev[SY_FEED_EV * SY_EVW];
-    double row[SY_FEED_ROW * SY_ROW];
+    double row[SY_FEED_ROW * SY_FEEDW];
 };
 
 __device__ __forceinline__ double bcast(double v, int srcLane) { /* srcLane wave-uniform */
@@ -267,6 +299,35 @@ __device__ __forceinline__ double lgauss(double x, double mu, double sd, double 
     const double a = __fma_rn(rem, rsd, q);
     return K + (-0.5 * a * a);
 }
+
+#ifdef SY_HDP
+/* the NanoporeHDP as densities need it (dir_proc_density impl/hdp.c:2577-2601 -> grid_spline_interp
+ * impl/hdp_math_utils.c:471-495): an evenly spaced sampling grid, values and spline slopes per table row */
+struct HdpGrid {
+    const double *__restrict__ grid, *__restrict__ y, *__restrict__ slope;
+    int n;              /* index of the grid's last point */
+    double x0, xn, dx;  /* its first and last point, its spacing */
+};
+__device__ __forceinline__ HdpGrid hdp_grid(const double *model) {
+    const DevHdpModel *hm = (const DevHdpModel *) model;
+    HdpGrid h;
+    h.grid = hm->grid; h.y = hm->y; h.slope = hm->slope;
+    h.n = uni(hm->gridLength) - 1;
+    h.x0 = h.grid[0]; h.xn = h.grid[h.n]; h.dx = h.grid[1] - h.grid[0];
+    return h;
+}
+/* (grid cell, offset in it) of an event's mean, as grid_spline_interp takes them -- its two IEEE divisions, once per
+ * event; -1 / -2 with the distance to the grid's end for a mean below / above the grid (cpecan_k_wv_forward_h*) */
+__device__ __forceinline__ void hdp_event(const HdpGrid &h, double q, double &cell, double &off) {
+    if (q <= h.x0) { cell = -1.0; off = h.x0 - q; }
+    else if (q >= h.xn) { cell = -2.0; off = q - h.xn; }
+    else {
+        const long long il = (long long) ((q - h.x0) / h.dx);
+        cell = (double) il;
+        off = (q - h.grid[il]) / h.dx;
+    }
+}
+#endif
 
 #ifdef SY_VANILLA
 /* emissions_signal_getEventMatchProbWithTwoDists (impl/stateMachine.c:499-528) on one table of a slot's row (p: mu, sd,
@@ -464,6 +525,9 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
 #pragma unroll
     for (int i = 0; i < 9; i++) T[i] = model[i];
 #endif
+#ifdef SY_HDP
+    const HdpGrid hg = hdp_grid(model);
+#endif
 
     const int d0 = uni(ld_agent(&state->d));
     int tracedBackTo = uni(ld_agent(&state->tracedBackTo));
@@ -485,6 +549,9 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
         xs = wave * 64 + lane;
 #pragma unroll
         for (int j = 0; j < SY_NPRM; j++) prm[j] = 0.0;
+#ifdef SY_HDP
+        prm[0] = -1.0; /* no k-mer yet: a parked slot scores -inf */
+#endif
         Fm = Fx = Fy = Lm = Lx = Ly = CP_NEG_INF;
 #ifdef SY_VANILLA
         em = el = 0.0;
@@ -528,7 +595,10 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
         const int ei = d0 - xs - 1;
         const bool okE = v && ei >= 0 && ei < lY;
         em = okE ? ev[3 * (long long) ei] : 0.0;
-#ifdef SY_VANILLA
+#ifdef SY_HDP
+        en = 0.0;
+        if (okE) hdp_event(hg, em, em, en);
+#elif defined(SY_VANILLA)
         en = okE ? ev[3 * (long long) ei + 1] : 1.0;
         er = okE ? 1.0 / en : 1.0;
         el = okE ? ev[3 * (long long) ei + 2] : 0.0;
@@ -580,7 +650,8 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
     const int tbFrom = uni((int) (tbFromL < 0x7fffffff ? tbFromL : 0x7fffffff));
     const int tbWidth = uni((int) (widthLimit < 0x7fffffff ? widthLimit : 0x7fffffff));
     PROF_DECL
-    /* blocks of SY_FEED diagonals: the loads sit between the blocks, the inner loop has none */
+    /* blocks of SY_FEED diagonals: the loads sit between the blocks, the inner loop has none (but for the -DSY_HDP
+     * build's four table values per cell, see its emission below) */
 #pragma unroll 1
     for (int db = d0 + 1; db <= D; db += SY_FEED) {
         {
@@ -600,6 +671,16 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
                 const double q = ok ? ev[3 * (long long) e + (c == 0 ? 0 : c == 3 ? 2 : 1)] : (c == 0 || c == 3 ? 0.0 : 1.0);
                 fd.ev[(i & (SY_EVW * SY_FEED_EV - 1))] = c == 2 ? 1.0 / q : q;
             }
+#elif defined(SY_HDP)
+#pragma unroll 1
+            for (int e = evHi + (int) threadIdx.x; e < evTo; e += SY_P) {
+                /* an event that does not exist stays at (0, 0): it only ever meets -inf cells and must score
+                 * something finite */
+                double c = 0.0, o = 0.0;
+                if (e >= 0 && e < lY) hdp_event(hg, ev[3 * (long long) e], c, o);
+                fd.ev[(2 * e) & (2 * SY_FEED_EV - 1)] = c;
+                fd.ev[(2 * e + 1) & (2 * SY_FEED_EV - 1)] = o;
+            }
 #else
 #pragma unroll 1
             for (int i = evHi * 2 + (int) threadIdx.x; i < evTo * 2; i += SY_P) {
@@ -608,9 +689,9 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
             }
 #endif
 #pragma unroll 1
-            for (int i = rowHi * SY_ROW + (int) threadIdx.x; i < rowTo * SY_ROW; i += SY_P) {
-                const int x = i / SY_ROW, j = i - x * SY_ROW;
-                fd.row[(x & (SY_FEED_ROW - 1)) * SY_ROW + j] = track[(long long) (x <= lX ? x : lX) * SY_ROW + j];
+            for (int i = rowHi * SY_FEEDW + (int) threadIdx.x; i < rowTo * SY_FEEDW; i += SY_P) {
+                const int x = i / SY_FEEDW, j = i - x * SY_FEEDW;
+                fd.row[(x & (SY_FEED_ROW - 1)) * SY_FEEDW + j] = track[(long long) (x <= lX ? x : lX) * SY_ROW + j];
             }
             evHi = evTo;
             rowHi = rowTo;
@@ -666,7 +747,7 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
 #else
             if (SY_WAVE_OF(xin) == wave && lane == (xin & 63)) {
 #endif
-                const double *r = fd.row + (xin & (SY_FEED_ROW - 1)) * SY_ROW;
+                const double *r = fd.row + (xin & (SY_FEED_ROW - 1)) * SY_FEEDW;
 #pragma unroll
                 for (int j = 0; j < SY_NPRM; j++) prm[j] = r[j];
             }
@@ -700,6 +781,31 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
             double gy = Fm + (py + prm[SY_TR + 4]);
             gy = ladd(gy, Fy + (py + lYY), cf);
 #else
+#ifdef SY_HDP
+            /* get_nanopore_kmer_density (impl/nanopore_hdp.c:390): the spline of the slot's table row at the cell's
+             * event, clamped at zero -- a linear density where a log-probability belongs, match and gap-Y emission
+             * alike; a column that is no k-mer (row offset < 0) scores -inf.  Four values of the model's tables per
+             * cell: the only global loads of the sweep (the tables stay in L2). */
+            const double px = SY_HDP_GAPX;
+            double pm, py;
+            {
+                const double ro = prm[0], ex = em, w = en;
+                /* (32-bit indices: cpecan_hip_modelsh_create refuses tables of 2^32 values or more) */
+                const unsigned base = ro < 0.0 ? 0u : (unsigned) ro;
+                const unsigned il = ex < 0.0 ? (ex == -2.0 ? (unsigned) hg.n : 0u) : (unsigned) ex;
+                const unsigned ir = ex < 0.0 ? il : il + 1u;
+                const double yl = hg.y[base + il], yr = hg.y[base + ir];
+                const double sl = hg.slope[base + il], sr = hg.slope[base + ir];
+                const double dy = yr - yl;
+                const double ca = sl * hg.dx - dy, cb = dy - sr * hg.dx;
+                const double tl = w, tr = 1.0 - tl;
+                const double inside = tr * yl + tl * yr + tl * tr * (ca * tr + cb * tl);
+                const double edge = ex == -1.0 ? yl - sl * w : yl + sl * w;
+                double r = ex < 0.0 ? edge : inside;
+                r = r > 0.0 ? r : 0.0;
+                pm = py = ro < 0.0 ? CP_NEG_INF : r;
+            }
+#else
             const double px = prm[CP_GAPX];
 #ifdef SY_ABLATE_EMIT
             double pm = em + prm[CP_K1], py = en + prm[CP_YK1];
@@ -709,6 +815,7 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
             double py = lgauss(em, prm[CP_YMU], prm[CP_YSD], prm[CP_RYSD], prm[CP_YK1])
                             + lgauss(en, prm[CP_YNMU], prm[CP_YNSD], prm[CP_RYNSD], prm[CP_YK2]);
 #endif
+#endif /* SY_HDP */
             PROF_FENCE(pm) PROF_FENCE(py)
             PROF(5)
             /* cell_calculateForward: to[t] = logAdd(to[t], from[f] + (eP + tP)) (:365-376) in the
@@ -1534,7 +1641,7 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
     }
 }
 
-#ifndef SY_VANILLA /* (the vanilla machine's E-step runs on the general kernel) */
+#ifndef SY_NO_ESTEP /* (the vanilla machine's E-step and the HDP machine's past 248 k-mers run on the general kernel) */
 /*
  * Baum-Welch expectations of the traceback window the backward kernel just swept
  * (diagonalCalculation_Expectations :841-863 with cell_signal_updateTransAndKmerSkipExpectations
@@ -1660,7 +1767,7 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
     if (threadIdx.x < 9) atomicAdd(dst + threadIdx.x, sExp[threadIdx.x]);
     if (threadIdx.x == 0) atomicAdd(dst + 9 + 4096, lik);
 }
-#endif /* !SY_VANILLA */
+#endif /* !SY_NO_ESTEP */
 
 #if SY_R == 4 && !defined(SY_VANILLA)
 /* results of the per-alignment states into the batch's count arrays */
@@ -1760,6 +1867,46 @@ static int sy_launch_counts(hipStream_t stream, const SweepArgs &a) {
     return cpecan_systolic_machine.launch_counts(stream, a);
 }
 #endif
+#if SY_R == 8 && defined(SY_HDP)
+/* the HDP machine on this family (defined once, in the eight-wave object).  Its track in the strawMan row format:
+ * entry 0 of column x (0..lX) = the offset (in doubles) of the table row of the k-mer that matrix column x scores --
+ * sequence_getKmer3 (:327-331): column 0 (index -1) reads the first k-mer, like column 1 -- or -1 where the column is
+ * no k-mer; entry CP_GAPX = the flat gap-X emission log(0.1) (stateMachine.c:1347), which the sweep back adds to the
+ * transitions as it does a strawMan k-mer's; the rest unused */
+extern "C" __global__ void cpecan_k_sy_track_hdp(const DevItem *__restrict__ items, long long nItems,
+                                                 const long long *__restrict__ trackBase,
+                                                 const int *__restrict__ kid, const DevHdpModel *__restrict__ models,
+                                                 double *track) {
+    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
+        const DevItem it = items[item];
+        const DevHdpModel &m = models[it.model];
+        const long long n = (it.lX + 1) * CP_ROW;
+        double *dst = track + trackBase[item] * CP_ROW;
+        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+             i += (long long) gridDim.x * blockDim.x) {
+            const long long x = i / CP_ROW;
+            const int j = (int) (i - x * CP_ROW);
+            double v = 0.0;
+            if (j == 0) {
+                const int id = kid[it.xOff + (x > 0 ? x - 1 : 0)];
+                v = id < 0 ? -1.0 : (double) ((long long) m.kmerRow[id] * m.gridLength);
+            } else if (j == CP_GAPX) v = SY_HDP_GAPX;
+            dst[i] = v;
+        }
+    }
+}
+static int sy_launch_track_hdp(hipStream_t stream, const SweepArgs &a) {
+    int bx = (int) ((((long long) a.maxLX + 1) * CP_ROW + 255) / 256);
+    if (bx > 64) bx = 64;
+    hipLaunchKernelGGL(cpecan_k_sy_track_hdp, dim3(bx, (unsigned) std::min(a.nItems, 65535LL)), dim3(256), 0, stream,
+                       a.items, a.nItems, a.trackBase, a.kid, (const DevHdpModel *) a.models, a.track);
+    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(SyState), stream) != hipSuccess) return -1;
+    return sy_status();
+}
+static int sy_launch_counts_hdp(hipStream_t stream, const SweepArgs &a) {
+    return cpecan_systolic_machine.launch_counts(stream, a);
+}
+#endif
 #if SY_R == 4 && !defined(SY_VANILLA)
 static int sy_launch_track(hipStream_t stream, const SweepArgs &a) {
     int bx = (int) ((((long long) a.maxLX + 1) * CP_ROW + 255) / 256);
@@ -1788,7 +1935,7 @@ static int sy_launch_backward(hipStream_t stream, const SweepArgs &a, int window
                        window);
     return sy_status();
 }
-#ifndef SY_VANILLA
+#ifndef SY_NO_ESTEP
 static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) {
     hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_expect), dim3((unsigned) a.nItems, SY_EXPECT_CHUNKS), dim3(SY_P), 0, stream,
                        a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.kidx, a.models, a.Fring, a.ringDoubles,
@@ -1801,7 +1948,9 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 #ifndef __HIP_DEVICE_COMPILE__
 #if SY_R == 4 && defined(SY_VANILLA)
 const SweepMachine cpecan_systolic_machine_vanilla = { (int) sizeof(SyState), SY_ROW, sy_launch_track, sy_launch_counts };
-#elif SY_R == 4
+#elif SY_R == 8 && defined(SY_HDP)
+const SweepMachine cpecan_systolic_machine_hdp = { (int) sizeof(SyState), CP_ROW, sy_launch_track_hdp, sy_launch_counts_hdp };
+#elif SY_R == 4 && !defined(SY_HDP)
 const SweepMachine cpecan_systolic_machine = { (int) sizeof(SyState), CP_ROW, sy_launch_track, sy_launch_counts };
 #endif
 extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
@@ -1809,6 +1958,11 @@ extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
 /* (no E-step on these builds: no expect launcher, no ring of backward cells; the dispatch keeps such batches away) */
 const SweepBuild SY_SYM(cpecan_systolic_build) = {
     SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
+    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };
+#elif defined(SY_HDP)
+/* (no E-step on these builds either) */
+const SweepBuild SY_SYM(cpecan_systolic_build) = {
+    SY_R, false, SWEEP_HDP, &cpecan_systolic_machine_hdp, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
     sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };
 #else
 const SweepBuild SY_SYM(cpecan_systolic_build) = {

@@ -107,13 +107,13 @@ struct SweepMachine {
 extern "C" int cpecan_wave_launch_counts(hipStream_t stream, const SweepArgs &a); /* (one for the three wave machines) */
 /* the vanilla track alone, states untouched (the vanilla builds of the workgroup family keep SyState records) */
 extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const SweepArgs &a);
-extern "C" const SweepMachine cpecan_systolic_machine, cpecan_systolic_machine_vanilla, cpecan_wave_machine,
+extern "C" const SweepMachine cpecan_systolic_machine, cpecan_systolic_machine_vanilla, cpecan_systolic_machine_hdp, cpecan_wave_machine,
     cpecan_wave_machine_hdp, cpecan_wave_machine_vanilla;
 
 enum { SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA };
 
 /* One compiled build of the throughput kernels, defined next to them (cpecan_kernel_systolic.hip: cpecan_systolic_build
- * and _r1.._r3, _r6, _r8, the vanilla machine's _v4, _v6, _v8; cpecan_kernel_wave.hip: cpecan_wave_build_l2.._l4, _h2.._h4,
+ * and _r1.._r3, _r6, _r8, the vanilla machine's _v4, _v6, _v8, the HDP machine's _h6, _h8; cpecan_kernel_wave.hip: cpecan_wave_build_l2.._l4, _h2.._h4,
  * _v2, _v3) */
 struct SweepBuild {
     int rows;    /* waves per workgroup (workgroup family) or cells per lane (wave family) */

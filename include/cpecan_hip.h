@@ -174,7 +174,8 @@ int cpecan_hip_modelse_create(cpecan_ctx *ctx, const cpecan_echelon_model *model
  * are taken over it, impl/nanopore_hdp.c:348-380), the sampling grid, and per k-mer id the row -- in
  * posterior_predictive / spline_slopes, rows x grid_length doubles -- of the Dirichlet process's nearest
  * OBSERVED ancestor.  Ids live in their own space (used by cpecan_hip_batch_create_hdp only); all models of
- * a context must share one alphabet. */
+ * a context must share one alphabet; a model's tables hold at most 2^32 - 1 values (n_rows x grid_length: the
+ * register-resident kernels index them with 32 bits), a larger one is refused with CPECAN_EINVAL. */
 typedef struct {
     double transitions[9];
     const char *alphabet;
@@ -225,7 +226,7 @@ typedef struct {
 
 #define CPECAN_KERNEL_AUTO 0
 #define CPECAN_KERNEL_GENERAL 1  /* any band width; diagonals live in HBM            */
-#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide (<= 504 with CPECAN_FLAG_WIDE_BANDS); register-resident wavefront */
+#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide (<= 504 with CPECAN_FLAG_WIDE_BANDS[_HDP]); register-resident wavefront */
 
 #define CPECAN_FLAG_DEBUG_DUMP 1 /* keep forward/backward cells for cpecan_hip_batch_debug_cells */
 #define CPECAN_FLAG_UNBANDED 2   /* getAlignedPairsWithoutBanding (:1512): full matrix, one traceback from
@@ -270,6 +271,18 @@ typedef struct {
                                       environment variable CPECAN_WIDE_BANDS=1 (read per batch) sets it for every
                                       strawMan batch and every vanilla posterior batch: the way in for callers of
                                       libcpecan_host.so and vanillaAlign. */
+#define CPECAN_FLAG_WIDE_BANDS_HDP 256 /* cpecan_hip_batch_create_hdp (posterior decode only): a batch whose widest band is
+                                          249..504 k-mers, past the HDP machine's wave builds, runs on the HDP builds of the
+                                          workgroup-per-alignment kernels with six or eight waves per workgroup (up to
+                                          376, up to 504) instead of the general kernel, unless it is un-banded, carries
+                                          CPECAN_FLAG_GENERAL_KERNEL or has band edges that step by more than one k-mer.
+                                          A batch of narrower bands runs on the wave builds as without the flag, one of
+                                          wider bands on the general kernel as before.  An HDP batch of
+                                          CPECAN_FLAG_EXPECTATIONS ignores the flag (its E-step past 248 k-mers runs on
+                                          the general kernel), and so do all other machines; CPECAN_FLAG_WIDE_BANDS in
+                                          turn means nothing to an HDP batch.  Same results bit for bit.  The environment
+                                          variable CPECAN_WIDE_BANDS_HDP=1 (read per batch) sets it for every HDP posterior
+                                          batch: the way in for callers of libcpecan_host.so and vanillaAlign. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
