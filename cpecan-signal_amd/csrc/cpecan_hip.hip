@@ -1,33 +1,25 @@
 /*
- * cpecan_hip.hip -- the C-ABI of include/cpecan_hip.h: contexts, model upload, batches.
+ * cpecan_hip.hip -- the C-ABI of include/cpecan_hip.h: contexts and batches (the model tables: cpecan_models.hip).
  *
  * Host side of the thin layer between the reference-shaped C host code and the gfx950 kernels.
  * Nothing here computes DP cells: when no GPU is usable every compute entry point fails with
  * CPECAN_ENODEVICE (there is deliberately no CPU fallback).
  */
-#include "cpecan_hip.h"
+#include "cpecan_ctx.h"
 
-#include "cpecan_device.h"
 #include "cpecan_asm.h"
 #include "cpecan_sweep.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
 #include <atomic>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <string>
 #include <sched.h>
 #include <thread>
-#include <vector>
 
 extern "C" __global__ void cpecan_k_general(DevGeneralArgs, DevParams);
 extern "C" __global__ void cpecan_k_general4(DevGeneralArgs, DevParams);
@@ -111,24 +103,15 @@ template <class T> struct NoInit : std::allocator<T> {
     }
 };
 
-/* CPECAN_TIMING=1: wall-clock laps of the host-side set-up calls on stderr (where the time before the first kernel goes) */
-struct Lap {
-    const char *who;
-    bool on;
-    std::chrono::steady_clock::time_point t, t0;
-    explicit Lap(const char *w) : who(w), on(getenv("CPECAN_TIMING") != nullptr), t(std::chrono::steady_clock::now()), t0(t) {}
-    ~Lap() {
-        if (on)
-            fprintf(stderr, "[cpecan timing] %s: TOTAL %.1f ms\n", who,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    }
-    void operator()(const char *what) {
-        if (!on) return;
-        const auto n = std::chrono::steady_clock::now();
-        fprintf(stderr, "[cpecan timing] %s: %s %.1f ms\n", who, what, std::chrono::duration<double, std::milli>(n - t).count());
-        t = n;
-    }
+/* one candidate pair on its way to the host: its coordinates.  With it goes the device's verdict (an int, see
+ * cpecan_k_pack_pairs); the exponent (F + B) - totalProbability stays in HBM and is fetched for the few candidates the
+ * host has to settle itself, and for callers that ask for it: 12 bytes per candidate cross PCIe instead of 20. */
+struct PackedPair {
+    int x, y;
 };
+#define CP_UNDECIDED_CAP 65536ull /* candidates per batch the host settles with its libm before it fetches exponents item by item */
+
+} // namespace
 
 /* worker threads for host-side table derivation: the CPUs this process may run on (its affinity mask, which is
  * what a job's CPU share shows up as), at most 32 -- a node's hardware_concurrency() is the whole machine, and
@@ -153,102 +136,6 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(CPECAN_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),  \
-                        __FILE__, __LINE__);                                                 \
-    } while (0)
-
-/* one candidate pair on its way to the host: its coordinates.  With it goes the device's verdict (an int, see
- * cpecan_k_pack_pairs); the exponent (F + B) - totalProbability stays in HBM and is fetched for the few candidates the
- * host has to settle itself, and for callers that ask for it: 12 bytes per candidate cross PCIe instead of 20. */
-struct PackedPair {
-    int x, y;
-};
-#define CP_UNDECIDED_CAP 65536ull /* candidates per batch the host settles with its libm before it fetches exponents item by item */
-
-/* Device memory of batches and model tables goes through a small caching allocator: hipMalloc and hipFree wait for
- * the device, so a host thread that prepares the next batch while the GPU works on the current one (one-shot
- * alignment of a stream of batches) would otherwise stall on every buffer.  A released block is kept (up to
- * CPECAN_ALLOC_CACHE_GB; by default half of the device's memory -- one process per GPU is the deployment, and RCCL's
- * buffers, torch in the same process or other processes on the card keep the other half; cpecan_hip_trim_cache()
- * gives everything back)
- * and handed to the next request it fits within 25 %.  A block keeps its real size through every reuse. */
-struct DevCache {
-    struct Block { void *p; size_t bytes; int device; };
-    std::mutex lock;
-    std::vector<Block> blocks;
-    size_t held = 0;
-    const bool pinnedHost; /* the same for pinned host memory (the packed pairs of a batch): pinning and unpinning
-                              150 MB per batch costs tens of milliseconds; up to CPECAN_PINNED_CACHE_GB, default 8 */
-    size_t capBytes = 0; /* 0: not worked out yet */
-    explicit DevCache(bool host) : pinnedHost(host) {}
-    size_t cap() { /* (under `lock`) */
-        if (capBytes == 0) {
-            const char *e = getenv(pinnedHost ? "CPECAN_PINNED_CACHE_GB" : "CPECAN_ALLOC_CACHE_GB");
-            double gb = e ? atof(e) : 8.0;
-            if (!e && !pinnedHost) {
-                size_t freeB = 0, totalB = 0;
-                /* half the card: three C3 batches on the assembly sweeps (ring of three windows: 45 GB each) alive at once,
-                 * as a one-shot service keeps them, still turn over inside the cache */
-                gb = hipMemGetInfo(&freeB, &totalB) == hipSuccess ? (double) totalB / 2.0 / (double) (1ull << 30) : 32.0;
-            }
-            capBytes = (size_t) (gb * (double) (1ull << 30)) + 1;
-        }
-        return capBytes;
-    }
-    hipError_t raw_alloc(void **out, size_t bytes) { return pinnedHost ? hipHostMalloc(out, bytes, hipHostMallocDefault) : hipMalloc(out, bytes); }
-    void raw_free(void *p) { (void) (pinnedHost ? hipHostFree(p) : hipFree(p)); }
-    hipError_t get(void **out, size_t bytes, size_t *got) {
-        *got = bytes;
-        int device = 0;
-        (void) hipGetDevice(&device);
-        {
-            std::lock_guard<std::mutex> g(lock);
-            size_t best = blocks.size();
-            for (size_t i = 0; i < blocks.size(); i++)
-                if (blocks[i].device == device && blocks[i].bytes >= bytes && blocks[i].bytes <= bytes + bytes / 4 + 4096 &&
-                    (best == blocks.size() || blocks[i].bytes < blocks[best].bytes))
-                    best = i;
-            if (best != blocks.size()) {
-                *out = blocks[best].p;
-                *got = blocks[best].bytes;
-                held -= blocks[best].bytes;
-                blocks.erase(blocks.begin() + (long) best);
-                return hipSuccess;
-            }
-        }
-        hipError_t e = raw_alloc(out, bytes);
-        if (e != hipSuccess) { /* out of memory with blocks in the cache: give them back and try once more */
-            trim(0);
-            (void) hipGetLastError();
-            e = raw_alloc(out, bytes);
-        }
-        return e;
-    }
-    void put(void *p, size_t bytes) {
-        int device = 0;
-        (void) hipGetDevice(&device);
-        std::lock_guard<std::mutex> g(lock);
-        if (held + bytes > cap()) { /* the cache is bounded (small blocks are kept too: hipFree waits for the device
-                                       whatever the size, and the device is busy with the previous batch) */
-            raw_free(p);
-            return;
-        }
-        blocks.push_back({ p, bytes, device });
-        held += bytes;
-    }
-    void trim(size_t keep) {
-        std::lock_guard<std::mutex> g(lock);
-        while (!blocks.empty() && held > keep) {
-            raw_free(blocks.back().p);
-            held -= blocks.back().bytes;
-            blocks.pop_back();
-        }
-    }
-};
 DevCache &dev_cache() {
     static DevCache *c = new DevCache(false); /* (never destroyed: the runtime may be gone by the time statics are) */
     return *c;
@@ -257,57 +144,6 @@ DevCache &pinned_cache() {
     static DevCache *c = new DevCache(true);
     return *c;
 }
-
-/* a block of pinned host memory from the cache (host-built tables on their way to the device) */
-template <typename T> struct PinnedBuf {
-    T *p = nullptr;
-    size_t n = 0, blockBytes = 0;
-    hipError_t alloc(size_t count) {
-        release();
-        n = count;
-        if (count == 0) return hipSuccess;
-        return pinned_cache().get((void **) &p, count * sizeof(T), &blockBytes);
-    }
-    void release() {
-        if (p) pinned_cache().put(p, blockBytes);
-        p = nullptr;
-        n = blockBytes = 0;
-    }
-    ~PinnedBuf() { release(); }
-};
-
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0, blockBytes = 0;
-    hipError_t alloc(size_t count) {
-        release();
-        n = count;
-        if (count == 0) return hipSuccess;
-        return dev_cache().get((void **) &p, count * sizeof(T), &blockBytes);
-    }
-    void release() {
-        if (p) dev_cache().put(p, blockBytes);
-        p = nullptr;
-        n = blockBytes = 0;
-    }
-    void swap(DevBuf &o) {
-        std::swap(p, o.p);
-        std::swap(n, o.n);
-        std::swap(blockBytes, o.blockBytes);
-    }
-    ~DevBuf() { release(); }
-};
-
-/* Declared after a function's own DevBuf / PinnedBuf objects and before its first asynchronous use of them: whichever
- * way the function returns, the streams it fed are idle before those buffers go back to the cache (a released block
- * can be handed to another thread at once; hipFree used to wait for the device here). */
-struct StreamFence {
-    hipStream_t a = nullptr, b = nullptr;
-    ~StreamFence() {
-        if (a) (void) hipStreamSynchronize(a);
-        if (b) (void) hipStreamSynchronize(b);
-    }
-};
 
 /* The three streams a chain of batches runs on: forward (track, begin, the forward sweeps), back (the sweeps back) and
  * post (decode and re-sweep of a window, then the run's join, counts, packing and end event).  Every context has one;
@@ -359,55 +195,11 @@ static hipError_t lanes_sweeps(LaneSet *L) {
     return e;
 }
 
-} // namespace
-
 #define CP_WAVE5_PAIRED_BELOW 1536 /* alignments: below this (fewer than 1.5 per SIMD) the 5-state machine runs on two waves
                                     * per alignment: 1.14-1.24x at 1024 alignments, 0.8-0.9x at 4096 */
-struct cpecan_ctx {
-    int device = 0;
-    long long modelEpoch = 0; /* counts cpecan_hip_models_clear calls */
-    LaneSet *lanes = nullptr;
-    hipStream_t stream = nullptr; /* lanes->fwd */
-    std::vector<cpecan_batch *> batches; /* its live batches (under g_batchesMu): ctx_fence waits for their runs */
-    /* input preparation (uploads, table assembly, k-mer indices) goes through a stream of the highest priority: it
-     * gets a hardware queue of its own and its copies and small kernels are not held up behind the sweeps of the
-     * batches that are running while the next one is prepared; every call that uses it waits for it before it returns */
-    hipStream_t prep = nullptr;
-    DevBuf<double> models; /* nModels * CP_MODEL_STRIDE */
-    void *pinned = nullptr; /* staging slots of cpecan_hip_models_create */
-    size_t pinnedBytes = 0;
-    std::vector<double> switchToX; /* per strawMan model: its GAP_SWITCH_TO_X (the tables themselves live on the device only) */
-    int nModels = 0;
-    DevBuf<double> models5; /* 5-state symbol models, nModels5 * CP_MODEL5_STRIDE */
-    std::vector<double> hostModels5;
-    int nModels5 = 0;
-    /* HDP models: descriptors on the device, their tables in buffers of their own */
-    struct HdpTables {
-        DevBuf<int> kmerRow;
-        DevBuf<double> grid, y, slope;
-    };
-    std::vector<HdpTables *> hdpTables;
-    std::vector<DevHdpModel> hostModelsH;
-    DevBuf<DevHdpModel> modelsH;
-    std::string hdpAlphabet;
-    DevBuf<double> modelsV; /* vanilla signal models, nModelsV * CP_VMODEL_STRIDE (on the device only, as `models`) */
-    std::vector<double> mToYV; /* per vanilla model: its m_to_y_not_x (header entry 0), which log a_my and log a_mm of
-                                  the skip bins depend on (cpecan_hip_modelsv_set_skip_probs) */
-    DevBuf<double> models4; /* 4-state signal models: strawMan tables whose header holds eleven transitions */
-    std::vector<double> hostModels4;
-    int nModels4 = 0;
-    int nModelsV = 0;
-    DevBuf<double> modelsE; /* echelon signal models, nModelsE * CP_EMODEL_STRIDE */
-    std::vector<double> hostModelsE;
-    int nModelsE = 0;
-};
 
-/* The machines a batch can run (the CPECAN_MACHINE_* numbers of cpecan_hip.h) and one row of facts per machine: what
- * batch creation, the kernel choice and the launchers know about a machine they read from its row. */
-enum Machine {
-    STRAWMAN = CPECAN_MACHINE_STRAWMAN, DNA5 = CPECAN_MACHINE_DNA5, VANILLA = CPECAN_MACHINE_VANILLA,
-    HDP = CPECAN_MACHINE_HDP, SM4 = CPECAN_MACHINE_SM4, ECHELON = CPECAN_MACHINE_ECHELON, N_MACHINES
-};
+/* One row of facts per machine (enum Machine, cpecan_ctx.h): what batch creation, the kernel choice and the launchers
+ * know about a machine they read from its row.  Its models are the context's tables[machine]. */
 enum XSource { X_KIDX, X_KID, X_CHARS }; /* what a kernel reads per X position: k-mer index, HDP k-mer id, nucleotide */
 struct MachineRow {
     int states;        /* per cell */
@@ -432,32 +224,23 @@ struct MachineRow {
     XSource x;
     bool yAux;       /* log(event noise) per event */
     int ldsMaxWidth; /* the widest band whose forward diagonals the general kernel keeps in LDS (0: it keeps none) */
-    int (*nModels)(const cpecan_ctx *);
-    const void *(*models)(const cpecan_ctx *); /* on the device */
 };
 #define BOTH_MODES (1 << CPECAN_MODE_POSTERIOR | 1 << CPECAN_MODE_EXPECTATIONS)
 static const MachineRow MACHINES[N_MACHINES] = {
     /* STRAWMAN */ { 3, CPECAN_EXPECTATION_LEN, 4, 0, nullptr, nullptr, false, &WV_BUILDS, &SY_BUILDS, SY_WIDE_BUILDS, BOTH_MODES,
-                     CPECAN_FLAG_WIDE_BANDS, false, cpecan_k_general, X_KIDX, false, 0, [](const cpecan_ctx *c) { return c->nModels; },
-                     [](const cpecan_ctx *c) { return (const void *) c->models.p; } },
+                     CPECAN_FLAG_WIDE_BANDS, false, cpecan_k_general, X_KIDX, false, 0 },
     /* DNA5 */     { 5, CPECAN_EXPECTATION5_LEN, 4, 0, nullptr, "DNA batches: no cell dumps", true, nullptr, nullptr, nullptr, 0,
-                     0, false, cpecan_k_general5, X_CHARS, false, 248, [](const cpecan_ctx *c) { return c->nModels5; },
-                     [](const cpecan_ctx *c) { return (const void *) c->models5.p; } },
+                     0, false, cpecan_k_general5, X_CHARS, false, 248 },
     /* VANILLA */  { 3, CPECAN_EXPECTATIONV_LEN, 4, 0, nullptr, "vanilla batches: no cell dumps", true, &VV_BUILDS, nullptr,
-                     SYV_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS, true, cpecan_k_generalv, X_KIDX, true, 0,
-                     [](const cpecan_ctx *c) { return c->nModelsV; },
-                     [](const cpecan_ctx *c) { return (const void *) c->modelsV.p; } },
+                     SYV_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS, true, cpecan_k_generalv, X_KIDX, true, 0 },
     /* HDP */      { 3, CPECAN_EXPECTATIONH_LEN, 16, 0, nullptr, "HDP batches: no cell dumps", true, &HV_BUILDS, nullptr,
-                     SYH_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS_HDP, true, cpecan_k_generalh, X_KID, false, 0, [](const cpecan_ctx *c) { return (int) c->hostModelsH.size(); },
-                     [](const cpecan_ctx *c) { return (const void *) c->modelsH.p; } },
+                     SYH_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS_HDP, true, cpecan_k_generalh, X_KID, false, 0 },
     /* SM4 */      { 4, CPECAN_EXPECTATION_LEN, 4, 0, "4-state batches: posterior decode only, no cell dumps",
                      "4-state batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, 0, false,
-                     cpecan_k_general4, X_KIDX, false, 0, [](const cpecan_ctx *c) { return c->nModels4; },
-                     [](const cpecan_ctx *c) { return (const void *) c->models4.p; } },
+                     cpecan_k_general4, X_KIDX, false, 0 },
     /* ECHELON */  { 7, CPECAN_EXPECTATION_LEN, 16, 4, "echelon batches: posterior decode only, no cell dumps",
                      "echelon batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, 0, false,
-                     nullptr, X_KIDX, true, 0, [](const cpecan_ctx *c) { return c->nModelsE; },
-                     [](const cpecan_ctx *c) { return (const void *) c->modelsE.p; } },
+                     nullptr, X_KIDX, true, 0 },
 };
 
 /* what a machine refuses whatever the batch holds */
@@ -764,7 +547,7 @@ int cpecan_hip_device_count(int *count) {
  * waits for the prep stream after it: other threads' contexts are not held up for the length of a pass. */
 static std::mutex g_batchesMu; /* the contexts' batch lists */
 
-static hipError_t ctx_fence(cpecan_ctx *c) {
+hipError_t ctx_fence(cpecan_ctx *c) {
     hipError_t r = hipSuccess;
     {
         std::lock_guard<std::mutex> g(g_batchesMu);
@@ -777,6 +560,16 @@ static hipError_t ctx_fence(cpecan_ctx *c) {
     }
     const hipError_t e = hipStreamSynchronize(c->prep);
     return r != hipSuccess ? r : e;
+}
+
+int pinned_slots(cpecan_ctx *c, size_t want) {
+    if (c->pinnedBytes >= want) return CPECAN_OK;
+    if (c->pinned) (void) hipHostFree(c->pinned);
+    c->pinned = nullptr;
+    c->pinnedBytes = 0;
+    HIP_TRY(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
+    c->pinnedBytes = want;
+    return CPECAN_OK;
 }
 
 extern "C" {
@@ -848,259 +641,6 @@ int cpecan_hip_ctx_stream(cpecan_ctx *c, void **stream) {
     return CPECAN_OK;
 }
 
-/* One derived row per k-mer.  K = log_inv_sqrt_2pi - log(sigma) is the part of
- * emissions_signal_logGaussPdf (impl/stateMachine.c:333-343) that does not depend on the event;
- * evaluated here with the host libm exactly as the reference's per-cell code would. */
-static void derive_rows(const cpecan_sm3_model *m, double *dst) {
-    const double c = -0.91893853320467267;
-    for (int i = 0; i < 9; i++) dst[i] = m->transitions[i];
-    for (int i = 9; i < CP_MODEL_HEADER; i++) dst[i] = 0.0;
-    double *rows = dst + CP_MODEL_HEADER;
-    for (int k = 0; k <= CPECAN_NUM_KMERS; k++) {
-        double *r = rows + (size_t) k * CP_ROW;
-        if (k == CPECAN_NUM_KMERS) { /* "not a k-mer": model reads 0.0, gap prob LOG_ZERO (:185,:223) */
-            for (int j = 0; j < CP_ROW; j++) r[j] = 0.0;
-            r[CP_K1] = r[CP_K2] = r[CP_YK1] = r[CP_YK2] = -INFINITY;
-            r[CP_GAPX] = -INFINITY;
-            continue;
-        }
-        const double *a = m->match_probs + 1 + (size_t) k * CPECAN_MODEL_PARAMS;
-        const double *b = m->gap_y_probs + 1 + (size_t) k * CPECAN_MODEL_PARAMS;
-        const double sd[4] = { a[1], a[3], b[1], b[3] };
-        const double mu[4] = { a[0], a[2], b[0], b[2] };
-        for (int g = 0; g < 4; g++) {
-            double *q = r + 4 * g;
-            q[0] = mu[g];
-            q[1] = sd[g];
-            q[2] = sd[g] == 0.0 ? 0.0 : 1.0 / sd[g];
-            q[3] = sd[g] == 0.0 ? -INFINITY : c - log(sd[g]);
-        }
-        r[CP_GAPX] = m->gap_x_probs[k];
-        r[17] = 0.0;
-    }
-}
-
-/* Room for n more strawMan models at the end of the device table: a new block, the old rows copied across on the
- * device (no host mirror of the tables is kept).  *fresh receives the device address of the first new model. */
-static int grow_models(cpecan_ctx *c, int32_t n, double **fresh) {
-    const size_t old = (size_t) c->nModels * CP_MODEL_STRIDE, total = old + (size_t) n * CP_MODEL_STRIDE;
-    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
-    DevBuf<double> grown;
-    hipError_t e = grown.alloc(total);
-    if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
-    {
-        StreamFence fence{ c->prep, nullptr };
-        /* on the stream the uploads that follow use, and over before the old block is released */
-        if (old) HIP_TRY(hipMemcpyAsync(grown.p, c->models.p, old * sizeof(double), hipMemcpyDeviceToDevice, c->prep));
-    }
-    grown.swap(c->models);
-    *fresh = c->models.p + old;
-    return CPECAN_OK;
-}
-
-/* the context's pinned staging slots (cpecan_hip_models_create, cpecan_hip_modelsv_create), at least `want` bytes */
-static int pinned_slots(cpecan_ctx *c, size_t want) {
-    if (c->pinnedBytes >= want) return CPECAN_OK;
-    if (c->pinned) (void) hipHostFree(c->pinned);
-    c->pinned = nullptr;
-    c->pinnedBytes = 0;
-    HIP_TRY(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-    c->pinnedBytes = want;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_models_create(cpecan_ctx *c, const cpecan_sm3_model *models, int32_t n,
-                             int32_t threads, int32_t *ids) {
-    if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    for (int i = 0; i < n; i++)
-        if (!models[i].match_probs || !models[i].gap_x_probs || !models[i].gap_y_probs)
-            return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
-    HIP_TRY(hipSetDevice(c->device));
-    Lap lap("models_create");
-    int nt = threads > 0 ? threads : host_threads();
-    nt = std::max(1, std::min(nt, (int) n));
-    double *fresh = nullptr;
-    int rc = grow_models(c, n, &fresh);
-    if (rc != CPECAN_OK) return rc;
-    /* every host thread derives a model into one of its two pinned slots and sends it on its way; the slot is
-     * written again once its copy has gone (no host copy of the whole table exists at any time) */
-    const size_t slotBytes = CP_MODEL_STRIDE * sizeof(double), want = slotBytes * 2 * (size_t) nt;
-    rc = pinned_slots(c, want);
-    if (rc != CPECAN_OK) return rc;
-    std::vector<hipEvent_t> gone(2 * (size_t) nt, nullptr);
-    for (auto &ev : gone) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    lap("device table, pinned slots");
-    std::atomic<int> bad{0};
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; w++)
-        pool.emplace_back([&, w]() {
-            if (hipSetDevice(c->device) != hipSuccess) { bad = 1; return; }
-            int turn = 0;
-            for (int i = w; i < n; i += nt, turn++) {
-                const size_t slot = 2 * (size_t) w + (turn & 1);
-                double *dst = (double *) ((char *) c->pinned + slot * slotBytes);
-                if (turn >= 2 && hipEventSynchronize(gone[slot]) != hipSuccess) { bad = 1; return; }
-                derive_rows(&models[i], dst);
-                if (hipMemcpyAsync(fresh + (size_t) i * CP_MODEL_STRIDE, dst, slotBytes, hipMemcpyHostToDevice, c->prep) != hipSuccess ||
-                    hipEventRecord(gone[slot], c->prep) != hipSuccess) { bad = 1; return; }
-            }
-        });
-    for (auto &t : pool) t.join();
-    hipError_t se = hipStreamSynchronize(c->prep);
-    for (auto &ev : gone) (void) hipEventDestroy(ev);
-    if (bad || se != hipSuccess) {
-        c->models.release(); /* the table is in an unknown state: the context's strawMan models are gone */
-        c->switchToX.clear();
-        c->nModels = 0;
-        c->modelEpoch++;
-        return fail(CPECAN_EHIP, "model table upload failed: %s", hipGetErrorString(se != hipSuccess ? se : hipGetLastError()));
-    }
-    lap("derive rows (threads) || upload");
-    for (int i = 0; i < n; i++) {
-        ids[i] = c->nModels + i;
-        c->switchToX.push_back(models[i].transitions[T_GAP_SWITCH_TO_X]);
-    }
-    c->nModels += n;
-    return CPECAN_OK;
-}
-
-/* One element of one read's derived table from the base model's derived table, the read's scaling parameters
- * (emissions_signal_scaleModel impl/stateMachine.c:631-651) and the three values per k-mer the host took with its
- * libm (K1, the scaled noise sd, K2): every other entry is one IEEE multiply, add or divide, rounded as on the host. */
-extern "C" __global__ void cpecan_k_scale_models(const double *base, const double *scalings /* n x 5 */,
-                                                 const double *hostPart /* n x 4096 x 3 */, int n, double *out) {
-    const long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= CP_MODEL_STRIDE) return;
-    const double b = base[e];
-    const long long r = e - CP_MODEL_HEADER;
-    const int k = r >= 0 ? (int) (r / CP_ROW) : -1, j = r >= 0 ? (int) (r % CP_ROW) : -1;
-    const bool plain = k < 0 || k >= CPECAN_NUM_KMERS || j >= 8;
-    /* the neighbours a derived entry needs: the level sd (j 1, 2), the noise mean's row mates */
-    const double sd = plain ? 0.0 : base[CP_MODEL_HEADER + (long long) k * CP_ROW + 1];
-    for (int m = blockIdx.y; m < n; m += gridDim.y) {
-        double v = b;
-        if (!plain) {
-            const double *sc = scalings + 5 * (long long) m;
-            const double *h = hostPart + ((long long) m * CPECAN_NUM_KMERS + k) * 3;
-            switch (j) {
-            case 0: v = __dadd_rn(__dmul_rn(b, sc[0]), sc[1]); break;
-            case 1: v = __dmul_rn(b, sc[2]); break;
-            case 2: { const double s = __dmul_rn(sd, sc[2]); v = s == 0.0 ? 0.0 : __ddiv_rn(1.0, s); break; }
-            case 3: v = h[0]; break;
-            case 4: v = __dmul_rn(b, sc[3]); break;
-            case 5: v = h[1]; break;
-            case 6: v = h[1] == 0.0 ? 0.0 : __ddiv_rn(1.0, h[1]); break;
-            default: v = h[2]; break;
-            }
-        }
-        out[(long long) m * CP_MODEL_STRIDE + e] = v;
-    }
-}
-
-int cpecan_hip_models_create_scaled(cpecan_ctx *c, const cpecan_sm3_model *base, const cpecan_read_scaling *scalings,
-                                    int32_t n, int32_t threads, int32_t *ids) {
-    if (!c || !base || !scalings || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    if (!base->match_probs || !base->gap_x_probs || !base->gap_y_probs) return fail(CPECAN_EINVAL, "the base model has a NULL table");
-    HIP_TRY(hipSetDevice(c->device));
-    Lap lap("models_create_scaled");
-    std::vector<double> baseRows(CP_MODEL_STRIDE);
-    derive_rows(base, baseRows.data());
-    PinnedBuf<double> part; /* (recycled pinned memory: no page faults, and the copy engine reads it directly) */
-    HIP_TRY(part.alloc((size_t) n * CPECAN_NUM_KMERS * 3));
-    int nt = threads > 0 ? threads : host_threads();
-    nt = std::max(1, std::min(nt, (int) n));
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; w++)
-        pool.emplace_back([&, w]() {
-            const double lg = -0.91893853320467267;
-            for (int i = w; i < n; i += nt) {
-                const cpecan_read_scaling &s = scalings[i];
-                double *dst = part.p + (size_t) i * CPECAN_NUM_KMERS * 3;
-                for (int k = 0; k < CPECAN_NUM_KMERS; k++) {
-                    const double *a = base->match_probs + 1 + (size_t) k * CPECAN_MODEL_PARAMS;
-                    const double sd = a[1] * s.var;
-                    const double nmu = a[2] * s.scale_sd, lambda = a[4] * s.var_sd;
-                    const double nsd = sqrt(pow(nmu, 3.0) / lambda);
-                    dst[3 * k] = sd == 0.0 ? -INFINITY : lg - log(sd);
-                    dst[3 * k + 1] = nsd;
-                    dst[3 * k + 2] = nsd == 0.0 ? -INFINITY : lg - log(nsd);
-                }
-            }
-        });
-    for (auto &t : pool) t.join();
-    lap("host libm part (threads)");
-    double *fresh = nullptr;
-    int rc = grow_models(c, n, &fresh);
-    if (rc != CPECAN_OK) return rc;
-    DevBuf<double> dBase, dScal, dPart;
-    StreamFence fence{ c->prep, nullptr };
-    HIP_TRY(dBase.alloc(baseRows.size()));
-    HIP_TRY(dScal.alloc((size_t) n * 5));
-    HIP_TRY(dPart.alloc(part.n));
-    lap("device table");
-    static_assert(sizeof(cpecan_read_scaling) == 5 * sizeof(double), "cpecan_read_scaling is five doubles");
-    HIP_TRY(hipMemcpyAsync(dBase.p, baseRows.data(), baseRows.size() * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    HIP_TRY(hipMemcpyAsync(dScal.p, scalings, (size_t) n * 5 * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    HIP_TRY(hipMemcpyAsync(dPart.p, part.p, part.n * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    hipLaunchKernelGGL(cpecan_k_scale_models, dim3((unsigned) ((CP_MODEL_STRIDE + 255) / 256), (unsigned) std::min(n, 65535)),
-                       dim3(256), 0, c->prep, (const double *) dBase.p, (const double *) dScal.p, (const double *) dPart.p,
-                       (int) n, fresh);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->prep)); /* the staging blocks are released on return */
-    lap("upload + assemble");
-    for (int i = 0; i < n; i++) {
-        ids[i] = c->nModels + i;
-        c->switchToX.push_back(base->transitions[T_GAP_SWITCH_TO_X]);
-    }
-    c->nModels += n;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_models_download(cpecan_ctx *c, int32_t id, double *out, int64_t capacity, int64_t *nDoubles) {
-    if (!c || !nDoubles) return fail(CPECAN_EINVAL, "bad argument");
-    *nDoubles = CP_MODEL_STRIDE;
-    if (!out) return CPECAN_OK;
-    if (id < 0 || id >= c->nModels) return fail(CPECAN_EINVAL, "model id %d out of range (%d)", id, c->nModels);
-    if (capacity < CP_MODEL_STRIDE) return fail(CPECAN_EINVAL, "capacity %lld < %d doubles", (long long) capacity, (int) CP_MODEL_STRIDE);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(ctx_fence(c));
-    HIP_TRY(hipMemcpy(out, c->models.p + (size_t) id * CP_MODEL_STRIDE, CP_MODEL_STRIDE * sizeof(double), hipMemcpyDeviceToHost));
-    return CPECAN_OK;
-}
-
-extern "C" __global__ void cpecan_k_set_transitions(double *models, int nModels, const double *values /* 9 + 4096 */,
-                                                    int withGap) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int m = blockIdx.y; m < nModels; m += gridDim.y) { /* grid.y is capped at 65535 */
-        double *blk = models + (long long) m * CP_MODEL_STRIDE;
-        if (i < 9) blk[i] = values[i];
-        else if (withGap && i < 9 + CPECAN_NUM_KMERS)
-            blk[CP_MODEL_HEADER + (long long) (i - 9) * CP_ROW + CP_GAPX] = values[i];
-    }
-}
-
-int cpecan_hip_models_set_transitions(cpecan_ctx *c, const double *transitions, const double *gapX) {
-    if (!c || !transitions) return fail(CPECAN_EINVAL, "bad argument");
-    if (c->nModels <= 0) return fail(CPECAN_EINVAL, "the context holds no strawMan models");
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<double> v(9 + CPECAN_NUM_KMERS, 0.0);
-    for (int i = 0; i < 9; i++) v[(size_t) i] = transitions[i];
-    if (gapX) std::copy(gapX, gapX + CPECAN_NUM_KMERS, v.begin() + 9);
-    for (double &t : c->switchToX) t = transitions[T_GAP_SWITCH_TO_X];
-    /* the tables are written in place: every run that reads them is over first (on whatever lanes it went); the
-     * update goes through the context's own prep stream, which no other context's run shares */
-    HIP_TRY(ctx_fence(c));
-    DevBuf<double> dv;
-    StreamFence fence{ c->prep, nullptr };
-    HIP_TRY(dv.alloc(v.size()));
-    HIP_TRY(hipMemcpyAsync(dv.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    hipLaunchKernelGGL(cpecan_k_set_transitions, dim3((9 + CPECAN_NUM_KMERS + 255) / 256, (unsigned) std::min(c->nModels, 65535)),
-                       dim3(256), 0, c->prep, c->models.p, c->nModels, (const double *) dv.p, gapX ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->prep)); /* dv is released on return */
-    return CPECAN_OK;
-}
-
 int cpecan_hip_selftest_division(cpecan_ctx *c, int64_t n, uint64_t seed, int64_t *mismatches) {
     if (!c || n <= 0 || !mismatches) return fail(CPECAN_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
@@ -1123,464 +663,6 @@ static double echelon_duration(const double *event, int n) {
     static const double logFactorial[6] = { 0.0, 0.0, 0.69314718056, 1.79175946923, 3.17805383035, 4.78749174278 };
     const double lambda = event[2] / 0.00332005312085;
     return (n + 1) * 0.1397619423751586 + n * log(lambda) - logFactorial[n] - 2 * lambda;
-}
-
-/* Device block of one vanilla model.  Every log() the reference takes per cell
- * (stateMachine3Vanilla_cellCalculate :1391-1407, logGaussPdf :338, logInvGaussPdf :328) depends on the
- * skip bin or the k-mer only: taken here once, with the host libm the reference would call. */
-static void derive_vanilla_bins(double m_to_y_not_x, const double *skip_probs, double *bins /* 30 x 5 */) {
-    for (int bin = 0; bin < 30; bin++) {
-        const double a_mx = skip_probs[bin];
-        const double a_my = (1 - a_mx) * m_to_y_not_x;
-        const double a_mm = 1.0f - a_my - a_mx;
-        const double a_xx = skip_probs[bin + 30];
-        const double a_xm = 1.0f - a_xx;
-        double *b = bins + bin * 5;
-        b[0] = log(a_mx);
-        b[1] = log(a_xx);
-        b[2] = log(a_mm);
-        b[3] = log(a_xm);
-        b[4] = log(a_my);
-    }
-}
-
-static void derive_vanilla(const cpecan_vanilla_model *m, double *dst) {
-    for (int i = 0; i < CP_VHDR; i++) dst[i] = 0.0;
-    dst[0] = m->m_to_y_not_x;
-    dst[1] = m->e_to_e;
-    dst[CP_VHDR_END_M] = m->end_match_prob;
-    dst[CP_VHDR_END_X] = m->end_from_x_prob;
-    dst[CP_VHDR_END_Y] = m->end_from_y_prob;
-    const double a_yy = m->e_to_e, a_ym = 1.0f - a_yy;
-    dst[CP_VHDR_LOG_YY] = log(a_yy);
-    dst[CP_VHDR_LOG_YM] = log(a_ym);
-    derive_vanilla_bins(m->m_to_y_not_x, m->skip_probs, dst + CP_VHDR_BINS);
-    const double c = -0.91893853320467267;
-    double *rows = dst + CP_VHDR;
-    for (int k = 0; k <= CPECAN_NUM_KMERS; k++) {
-        double *r = rows + (size_t) k * CP_VROW;
-        for (int t = 0; t < 2; t++) {
-            double *q = r + 6 * t;
-            if (k == CPECAN_NUM_KMERS) { /* not a k-mer: level -inf, the noise term kept finite */
-                q[CP_V_MU] = 0.0; q[CP_V_SD] = 0.0; q[CP_V_K] = -INFINITY;
-                q[CP_V_NMU] = 1.0; q[CP_V_LAMBDA] = 1.0; q[CP_V_LLAMBDA] = 0.0;
-                continue;
-            }
-            const double *a = (t ? m->gap_y_probs : m->match_probs) + 1 + (size_t) k * CPECAN_MODEL_PARAMS;
-            q[CP_V_MU] = a[0];
-            q[CP_V_SD] = a[1];
-            q[CP_V_K] = a[1] == 0.0 ? -INFINITY : c - log(a[1]);
-            q[CP_V_NMU] = a[2];
-            q[CP_V_LAMBDA] = a[4];
-            q[CP_V_LLAMBDA] = log(a[4]);
-        }
-    }
-}
-
-/* Room for n more vanilla models at the end of the device table, as grow_models does for the strawMan table: a new
- * block, the old rows copied across on the device (no host mirror of the tables is kept).  *fresh receives the device
- * address of the first new model. */
-static int grow_models_v(cpecan_ctx *c, int32_t n, double **fresh) {
-    const size_t old = (size_t) c->nModelsV * CP_VMODEL_STRIDE, total = old + (size_t) n * CP_VMODEL_STRIDE;
-    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
-    DevBuf<double> grown;
-    hipError_t e = grown.alloc(total);
-    if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
-    {
-        StreamFence fence{ c->prep, nullptr };
-        /* on the stream the uploads that follow use, and over before the old block is released */
-        if (old) HIP_TRY(hipMemcpyAsync(grown.p, c->modelsV.p, old * sizeof(double), hipMemcpyDeviceToDevice, c->prep));
-    }
-    grown.swap(c->modelsV);
-    *fresh = c->modelsV.p + old;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_modelsv_create(cpecan_ctx *c, const cpecan_vanilla_model *models, int32_t n, int32_t threads,
-                              int32_t *ids) {
-    if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    for (int i = 0; i < n; i++)
-        if (!models[i].match_probs || !models[i].skip_probs || !models[i].gap_y_probs)
-            return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
-    HIP_TRY(hipSetDevice(c->device));
-    Lap lap("modelsv_create");
-    int nt = threads > 0 ? threads : host_threads();
-    nt = std::max(1, std::min(nt, (int) n));
-    double *fresh = nullptr;
-    int rc = grow_models_v(c, n, &fresh);
-    if (rc != CPECAN_OK) return rc;
-    /* as cpecan_hip_models_create: every host thread derives models into one of its two pinned slots and sends the
-     * slot on its way; the slot is written again once its copy has gone.  A slot holds up to four neighbouring models:
-     * the copy engine's cost per copy is that of a block's transfer, so one copy per model would double the upload */
-    const int per = std::max(1, std::min(4, (int) n / (2 * nt)));
-    const size_t blockBytes = CP_VMODEL_STRIDE * sizeof(double), slotBytes = blockBytes * (size_t) per;
-    rc = pinned_slots(c, slotBytes * 2 * (size_t) nt);
-    if (rc != CPECAN_OK) return rc;
-    std::vector<hipEvent_t> gone(2 * (size_t) nt, nullptr);
-    for (auto &ev : gone) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    lap("device table, pinned slots");
-    std::atomic<int> bad{0};
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; w++)
-        pool.emplace_back([&, w]() {
-            if (hipSetDevice(c->device) != hipSuccess) { bad = 1; return; }
-            int turn = 0;
-            for (int i = w * per; i < n; i += nt * per, turn++) {
-                const size_t slot = 2 * (size_t) w + (turn & 1);
-                double *dst = (double *) ((char *) c->pinned + slot * slotBytes);
-                const int m = std::min(per, (int) n - i); /* models of this slot */
-                if (turn >= 2 && hipEventSynchronize(gone[slot]) != hipSuccess) { bad = 1; return; }
-                for (int j = 0; j < m; j++) derive_vanilla(&models[i + j], dst + (size_t) j * CP_VMODEL_STRIDE);
-                if (hipMemcpyAsync(fresh + (size_t) i * CP_VMODEL_STRIDE, dst, blockBytes * (size_t) m, hipMemcpyHostToDevice, c->prep) != hipSuccess ||
-                    hipEventRecord(gone[slot], c->prep) != hipSuccess) { bad = 1; return; }
-            }
-        });
-    for (auto &t : pool) t.join();
-    hipError_t se = hipStreamSynchronize(c->prep);
-    for (auto &ev : gone) (void) hipEventDestroy(ev);
-    if (bad || se != hipSuccess) {
-        c->modelsV.release(); /* the table is in an unknown state: the context's vanilla models are gone */
-        c->mToYV.clear();
-        c->nModelsV = 0;
-        c->modelEpoch++;
-        return fail(CPECAN_EHIP, "model table upload failed: %s", hipGetErrorString(se != hipSuccess ? se : hipGetLastError()));
-    }
-    lap("derive blocks (threads) || upload");
-    for (int i = 0; i < n; i++) {
-        ids[i] = c->nModelsV + i;
-        c->mToYV.push_back(models[i].m_to_y_not_x);
-    }
-    c->nModelsV += n;
-    return CPECAN_OK;
-}
-
-/* Two neighbouring elements of one read's vanilla block from the base model's block, the read's scaling parameters
- * (emissions_signal_scaleModel impl/stateMachine.c:631-651, which rewrites the match table only) and the two values
- * per k-mer the host took with its libm (K and log lambda of the scaled match row): header, the extra-event half of
- * every row and the "not a k-mer" row are the base's; every other entry is one IEEE multiply or add, rounded as on the
- * host.  An element pair never straddles a row half (header, row and half are even), and a block starts on 16 bytes. */
-extern "C" __global__ void cpecan_k_scale_models_v(const double *base, const double *scalings /* n x 5 */,
-                                                   const double *hostPart /* n x 4096 x 2 */, int n, double *out) {
-    const long long e = 2 * ((long long) blockIdx.x * blockDim.x + threadIdx.x);
-    if (e >= CP_VMODEL_STRIDE) return;
-    const double2 b = *(const double2 *) (base + e);
-    const long long r = e - CP_VHDR;
-    const int k = r >= 0 ? (int) (r / CP_VROW) : -1, j = r >= 0 ? (int) (r % CP_VROW) : -1;
-    const bool plain = k < 0 || k >= CPECAN_NUM_KMERS || j >= 6;
-    for (int m = blockIdx.y; m < n; m += gridDim.y) {
-        double2 v = b;
-        if (!plain) {
-            const double *sc = scalings + 5 * (long long) m;
-            const double *h = hostPart + ((long long) m * CPECAN_NUM_KMERS + k) * 2;
-            if (j == CP_V_MU) { /* level mean, level sd */
-                v.x = __dadd_rn(__dmul_rn(b.x, sc[0]), sc[1]);
-                v.y = __dmul_rn(b.y, sc[2]);
-            } else if (j == CP_V_K) { /* K, noise mean */
-                v.x = h[0];
-                v.y = __dmul_rn(b.y, sc[3]);
-            } else { /* noise lambda and its log */
-                v.x = __dmul_rn(b.x, sc[4]);
-                v.y = h[1];
-            }
-        }
-        *(double2 *) (out + (long long) m * CP_VMODEL_STRIDE + e) = v;
-    }
-}
-
-int cpecan_hip_modelsv_create_scaled(cpecan_ctx *c, const cpecan_vanilla_model *base, const cpecan_read_scaling *scalings,
-                                     int32_t n, int32_t threads, int32_t *ids) {
-    if (!c || !base || !scalings || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    if (!base->match_probs || !base->skip_probs || !base->gap_y_probs) return fail(CPECAN_EINVAL, "the base model has a NULL table");
-    HIP_TRY(hipSetDevice(c->device));
-    Lap lap("modelsv_create_scaled");
-    static_assert(CP_VHDR % 2 == 0 && CP_VROW % 2 == 0 && CP_V_MU == 0 && CP_V_K == 2 && CP_V_LAMBDA == 4,
-                  "cpecan_k_scale_models_v writes a block as pairs of doubles");
-    std::vector<double> baseBlock(CP_VMODEL_STRIDE);
-    derive_vanilla(base, baseBlock.data());
-    PinnedBuf<double> part; /* (recycled pinned memory: no page faults, and the copy engine reads it directly) */
-    HIP_TRY(part.alloc((size_t) n * CPECAN_NUM_KMERS * 2));
-    int nt = threads > 0 ? threads : host_threads();
-    nt = std::max(1, std::min(nt, (int) n));
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; w++)
-        pool.emplace_back([&, w]() {
-            const double lg = -0.91893853320467267;
-            for (int i = w; i < n; i += nt) {
-                const cpecan_read_scaling &s = scalings[i];
-                double *dst = part.p + (size_t) i * CPECAN_NUM_KMERS * 2;
-                for (int k = 0; k < CPECAN_NUM_KMERS; k++) { /* what derive_vanilla takes of the scaled match row */
-                    const double *a = base->match_probs + 1 + (size_t) k * CPECAN_MODEL_PARAMS;
-                    const double sd = a[1] * s.var, lambda = a[4] * s.var_sd;
-                    dst[2 * k] = sd == 0.0 ? -INFINITY : lg - log(sd);
-                    dst[2 * k + 1] = log(lambda);
-                }
-            }
-        });
-    for (auto &t : pool) t.join();
-    lap("host libm part (threads)");
-    double *fresh = nullptr;
-    int rc = grow_models_v(c, n, &fresh);
-    if (rc != CPECAN_OK) return rc;
-    DevBuf<double> dBase, dScal, dPart;
-    StreamFence fence{ c->prep, nullptr };
-    HIP_TRY(dBase.alloc(baseBlock.size()));
-    HIP_TRY(dScal.alloc((size_t) n * 5));
-    HIP_TRY(dPart.alloc(part.n));
-    lap("device table");
-    HIP_TRY(hipMemcpyAsync(dBase.p, baseBlock.data(), baseBlock.size() * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    HIP_TRY(hipMemcpyAsync(dScal.p, scalings, (size_t) n * 5 * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    HIP_TRY(hipMemcpyAsync(dPart.p, part.p, part.n * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    hipLaunchKernelGGL(cpecan_k_scale_models_v, dim3((unsigned) ((CP_VMODEL_STRIDE / 2 + 255) / 256), (unsigned) std::min(n, 65535)),
-                       dim3(256), 0, c->prep, (const double *) dBase.p, (const double *) dScal.p, (const double *) dPart.p,
-                       (int) n, fresh);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->prep)); /* the staging blocks are released on return */
-    lap("upload + assemble");
-    for (int i = 0; i < n; i++) {
-        ids[i] = c->nModelsV + i;
-        c->mToYV.push_back(base->m_to_y_not_x);
-    }
-    c->nModelsV += n;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_modelsv_download(cpecan_ctx *c, int32_t id, double *out, int64_t capacity, int64_t *nDoubles) {
-    if (!c || !nDoubles) return fail(CPECAN_EINVAL, "bad argument");
-    *nDoubles = CP_VMODEL_STRIDE;
-    if (!out) return CPECAN_OK;
-    if (id < 0 || id >= c->nModelsV) return fail(CPECAN_EINVAL, "vanilla model id %d out of range (%d)", id, c->nModelsV);
-    if (capacity < CP_VMODEL_STRIDE) return fail(CPECAN_EINVAL, "capacity %lld < %d doubles", (long long) capacity, (int) CP_VMODEL_STRIDE);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(ctx_fence(c));
-    HIP_TRY(hipMemcpy(out, c->modelsV.p + (size_t) id * CP_VMODEL_STRIDE, CP_VMODEL_STRIDE * sizeof(double), hipMemcpyDeviceToHost));
-    return CPECAN_OK;
-}
-
-/* every vanilla model receives the 150 logs of the set whose fudge factor is its own (header entry 0, compared as bits) */
-extern "C" __global__ void cpecan_k_set_skip_bins(double *models, int nModels, const double *factors, int nSets,
-                                                  const double *bins /* nSets x 150 */) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 150) return;
-    for (int m = blockIdx.y; m < nModels; m += gridDim.y) { /* grid.y is capped at 65535 */
-        double *blk = models + (long long) m * CP_VMODEL_STRIDE;
-        const long long mine = __double_as_longlong(blk[0]);
-        for (int s = 0; s < nSets; s++)
-            if (__double_as_longlong(factors[s]) == mine) {
-                blk[CP_VHDR_BINS + i] = bins[s * 150 + i];
-                break;
-            }
-    }
-}
-
-int cpecan_hip_modelsv_set_skip_probs(cpecan_ctx *c, const double *skipProbs) {
-    if (!c || !skipProbs) return fail(CPECAN_EINVAL, "bad argument");
-    if (c->nModelsV <= 0) return fail(CPECAN_EINVAL, "the context holds no vanilla models");
-    HIP_TRY(hipSetDevice(c->device));
-    /* log a_my and log a_mm depend on the model's m_to_y_not_x: one set of 150 logs per distinct value, taken by the
-     * code derive_vanilla runs */
-    std::vector<double> v; /* [factors: nSets | bins: nSets x 150] once the sets are known */
-    std::vector<double> factors;
-    for (double f : c->mToYV) {
-        bool seen = false;
-        for (double g : factors) seen = seen || memcmp(&f, &g, sizeof f) == 0;
-        if (!seen) factors.push_back(f);
-    }
-    const size_t nSets = factors.size();
-    v.assign(nSets * 151, 0.0);
-    for (size_t s = 0; s < nSets; s++) {
-        v[s] = factors[s];
-        derive_vanilla_bins(factors[s], skipProbs, v.data() + nSets + s * 150);
-    }
-    /* the tables are written in place: every run that reads them is over first (on whatever lanes it went); the
-     * update goes through the context's own prep stream, which no other context's run shares */
-    HIP_TRY(ctx_fence(c));
-    DevBuf<double> dv;
-    StreamFence fence{ c->prep, nullptr };
-    HIP_TRY(dv.alloc(v.size()));
-    HIP_TRY(hipMemcpyAsync(dv.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->prep));
-    hipLaunchKernelGGL(cpecan_k_set_skip_bins, dim3(1, (unsigned) std::min(c->nModelsV, 65535)), dim3(192), 0, c->prep,
-                       c->modelsV.p, c->nModelsV, (const double *) dv.p, (int) nSets, (const double *) (dv.p + nSets));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->prep)); /* dv is released on return */
-    return CPECAN_OK;
-}
-
-/* Device block of one echelon model: the vanilla layout (rows, end values) with the machine's own per-bin logs
- * (stateMachineEchelon_cellCalculate :1418-1425: log beta, log alpha, log(1 - beta), log(1 - alpha)) and log(n) of
- * emissions_signal_multipleKmerMatchProb (:548), all taken with the host libm. */
-static void derive_echelon(const cpecan_echelon_model *m, double *dst) {
-    cpecan_vanilla_model v = {};
-    v.end_match_prob = m->end_match_prob;
-    v.end_from_x_prob = m->end_from_x_prob;
-    v.match_probs = m->match_probs;
-    v.skip_probs = m->skip_probs;
-    v.gap_y_probs = m->gap_y_probs;
-    derive_vanilla(&v, dst);
-    for (int i = 0; i < CP_VHDR; i++) dst[i] = 0.0;
-    dst[CP_VHDR_END_M] = m->end_match_prob;
-    dst[CP_VHDR_END_X] = m->end_from_x_prob;
-    for (int bin = 0; bin < 30; bin++) {
-        const double a_mx = m->skip_probs[bin], a_mh = 1 - a_mx;
-        const double a_xx = m->skip_probs[bin + 30], a_xh = 1 - a_xx;
-        double *b = dst + CP_VHDR_BINS + bin * 5;
-        b[0] = log(a_mx);
-        b[1] = log(a_xx);
-        b[2] = log(a_mh);
-        b[3] = log(a_xh);
-        b[4] = 0.0;
-    }
-    for (int n = 0; n < 8; n++) dst[CP_EMODEL_LOGN + n] = n >= 1 && n <= 5 ? log((double) n) : 0.0;
-}
-
-int cpecan_hip_modelse_create(cpecan_ctx *c, const cpecan_echelon_model *models, int32_t n, int32_t *ids) {
-    if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    for (int i = 0; i < n; i++)
-        if (!models[i].match_probs || !models[i].skip_probs || !models[i].gap_y_probs)
-            return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t old = c->hostModelsE.size();
-    c->hostModelsE.resize(old + (size_t) n * CP_EMODEL_STRIDE);
-    for (int i = 0; i < n; i++) {
-        derive_echelon(&models[i], c->hostModelsE.data() + old + (size_t) i * CP_EMODEL_STRIDE);
-        ids[i] = c->nModelsE + i;
-    }
-    HIP_TRY(ctx_fence(c)); /* (the old table goes back to the allocator's cache) */
-    HIP_TRY(c->modelsE.alloc(c->hostModelsE.size()));
-    HIP_TRY(hipMemcpy(c->modelsE.p, c->hostModelsE.data(), c->hostModelsE.size() * sizeof(double), hipMemcpyHostToDevice));
-    c->nModelsE += n;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_modelsh_create(cpecan_ctx *c, const cpecan_hdp_model *models, int32_t n, int32_t *ids) {
-    if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    for (int i = 0; i < n; i++) {
-        const cpecan_hdp_model &m = models[i];
-        if (!m.alphabet || m.alphabet_size < 1 || m.alphabet_size > 16 || m.grid_length < 2 || !m.grid ||
-            m.n_rows < 1 || !m.posterior_predictive || !m.spline_slopes || !m.kmer_row)
-            return fail(CPECAN_EINVAL, "HDP model %d is incomplete", i);
-        /* the register-resident kernels carry a table row's offset (row x grid_length, in doubles) as a 32-bit index */
-        if ((long long) m.n_rows * m.grid_length > 0xffffffffLL)
-            return fail(CPECAN_EINVAL, "HDP model %d: tables of more than 2^32 - 1 values", i);
-        const std::string a(m.alphabet, (size_t) m.alphabet_size);
-        if (!c->hdpAlphabet.empty() && c->hdpAlphabet != a)
-            return fail(CPECAN_EINVAL, "all HDP models of a context must share one alphabet");
-        c->hdpAlphabet = a;
-        long long nK = 1;
-        for (int q = 0; q < 6; q++) nK *= m.alphabet_size;
-        for (long long k = 0; k < nK; k++)
-            if (m.kmer_row[k] < 0 || m.kmer_row[k] >= m.n_rows)
-                return fail(CPECAN_EINVAL, "HDP model %d: k-mer %lld points outside the tables", i, k);
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    for (int i = 0; i < n; i++) {
-        const cpecan_hdp_model &m = models[i];
-        long long nK = 1;
-        for (int q = 0; q < 6; q++) nK *= m.alphabet_size;
-        auto *t = new cpecan_ctx::HdpTables();
-        c->hdpTables.push_back(t);
-        const size_t cells = (size_t) m.n_rows * (size_t) m.grid_length;
-        HIP_TRY(t->kmerRow.alloc((size_t) nK));
-        HIP_TRY(t->grid.alloc((size_t) m.grid_length));
-        HIP_TRY(t->y.alloc(cells));
-        HIP_TRY(t->slope.alloc(cells));
-        HIP_TRY(hipMemcpy(t->kmerRow.p, m.kmer_row, (size_t) nK * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t->grid.p, m.grid, (size_t) m.grid_length * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t->y.p, m.posterior_predictive, cells * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t->slope.p, m.spline_slopes, cells * sizeof(double), hipMemcpyHostToDevice));
-        DevHdpModel d;
-        for (int q = 0; q < 9; q++) d.t[q] = m.transitions[q];
-        d.gridLength = m.grid_length;
-        d.pad = 0;
-        d.kmerRow = t->kmerRow.p;
-        d.grid = t->grid.p;
-        d.y = t->y.p;
-        d.slope = t->slope.p;
-        ids[i] = (int32_t) c->hostModelsH.size();
-        c->hostModelsH.push_back(d);
-    }
-    (void) ctx_fence(c);
-    HIP_TRY(c->modelsH.alloc(c->hostModelsH.size()));
-    HIP_TRY(hipMemcpy(c->modelsH.p, c->hostModelsH.data(), c->hostModelsH.size() * sizeof(DevHdpModel),
-                      hipMemcpyHostToDevice));
-    return CPECAN_OK;
-}
-
-int cpecan_hip_models5_create(cpecan_ctx *c, const cpecan_sm5_model *models, int32_t n, int32_t *ids) {
-    if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t old = c->hostModels5.size();
-    c->hostModels5.resize(old + (size_t) n * CP_MODEL5_STRIDE, 0.0);
-    for (int i = 0; i < n; i++) {
-        double *m = c->hostModels5.data() + old + (size_t) i * CP_MODEL5_STRIDE;
-        for (int k = 0; k < 17; k++) m[k] = models[i].transitions[k];
-        for (int k = 0; k < 16; k++) m[24 + k] = models[i].match_probs[k];
-        for (int k = 0; k < 4; k++) m[40 + k] = models[i].gap_x_probs[k];
-        for (int k = 0; k < 4; k++) m[44 + k] = models[i].gap_y_probs[k];
-        ids[i] = c->nModels5 + i;
-    }
-    c->nModels5 += n;
-    (void) ctx_fence(c); /* (the old table goes back to the allocator's cache) */
-    hipError_t e = c->models5.alloc(c->hostModels5.size());
-    if (e != hipSuccess) return fail(CPECAN_EHIP, "model table allocation: %s", hipGetErrorString(e));
-    HIP_TRY(hipMemcpy(c->models5.p, c->hostModels5.data(), c->hostModels5.size() * sizeof(double),
-                      hipMemcpyHostToDevice));
-    return CPECAN_OK;
-}
-
-/* 4-state signal models (getStateMachine4): the strawMan rows with the machine's eleven transitions in the header.  A
- * host mirror is kept and the whole table uploaded again when models are added (a handful of models per call). */
-int cpecan_hip_models4_create(cpecan_ctx *c, const cpecan_sm4_model *models, int32_t n, int32_t *ids) {
-    if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
-    for (int i = 0; i < n; i++)
-        if (!models[i].match_probs || !models[i].gap_x_probs || !models[i].gap_y_probs)
-            return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t old = c->hostModels4.size();
-    c->hostModels4.resize(old + (size_t) n * CP_MODEL_STRIDE);
-    for (int i = 0; i < n; i++) {
-        cpecan_sm3_model m3;
-        for (int k = 0; k < 9; k++) m3.transitions[k] = models[i].transitions[k];
-        m3.match_probs = models[i].match_probs;
-        m3.gap_x_probs = models[i].gap_x_probs;
-        m3.gap_y_probs = models[i].gap_y_probs;
-        double *dst = c->hostModels4.data() + old + (size_t) i * CP_MODEL_STRIDE;
-        derive_rows(&m3, dst);
-        for (int k = 0; k < 11; k++) dst[k] = models[i].transitions[k];
-        ids[i] = c->nModels4 + i;
-    }
-    HIP_TRY(ctx_fence(c)); /* (the old table goes back to the allocator's cache) */
-    HIP_TRY(c->models4.alloc(c->hostModels4.size()));
-    HIP_TRY(hipMemcpy(c->models4.p, c->hostModels4.data(), c->hostModels4.size() * sizeof(double), hipMemcpyHostToDevice));
-    c->nModels4 += n;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_models_clear(cpecan_ctx *c) {
-    if (!c) return fail(CPECAN_EINVAL, "ctx is NULL");
-    (void) hipSetDevice(c->device);
-    (void) ctx_fence(c); /* the tables go back to the allocator's cache: no reader may be left */
-    c->modelEpoch++; /* batches created before this call hold ids into tables that are gone: batch_run refuses them */
-    c->models.release();
-    c->switchToX.clear();
-    c->nModels = 0;
-    c->models5.release();
-    c->hostModels5.clear();
-    c->nModels5 = 0;
-    c->modelsV.release();
-    c->mToYV.clear();
-    c->nModelsV = 0;
-    c->models4.release();
-    c->hostModels4.clear();
-    c->nModels4 = 0;
-    c->modelsE.release();
-    c->hostModelsE.clear();
-    c->nModelsE = 0;
-    for (auto *t : c->hdpTables) delete t;
-    c->hdpTables.clear();
-    c->hostModelsH.clear();
-    c->modelsH.release();
-    c->hdpAlphabet.clear();
-    return CPECAN_OK;
 }
 
 int cpecan_hip_batch_destroy(cpecan_batch *b) {
@@ -1672,7 +754,7 @@ struct BandPlan {
 static int check_items(const cpecan_ctx *c, Machine machine, const BatchInput &in, BandPlan &plan) {
     const MachineRow &m = MACHINES[machine];
     const int kmerTail = m.x == X_CHARS ? 0 : 5; /* the characters of the last k-mer past lX */
-    const int nModels = m.nModels(c);
+    const int nModels = c->tables[machine].n;
     plan.items.resize((size_t) in.nItems);
     for (int64_t i = 0; i < in.nItems; i++) {
         const cpecan_item &s = in.items[i];
@@ -1848,7 +930,7 @@ static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput 
     b->wave5 = d.wave5;
     b->maxWidth = plan.maxWidth;
     b->compactPairs = plan.maxLXY + m.xReach < 65536;
-    b->nModels = m.nModels(c);
+    b->nModels = c->tables[machine].n;
     b->expectLen = m.expectLen;
     b->P.threshold = bp.threshold;
     b->P.minDiags = bp.minDiagsBetweenTraceBack;
@@ -2254,7 +1336,7 @@ static int enqueue_wave5(cpecan_batch *b, hipStream_t st) {
     auto kernel5 = kernels5[(size_t) ((paired ? 6 : 0) + (em ? 3 : 0) + l5)];
     hipLaunchKernelGGL(kernel5, dim3((unsigned) b->nItems), dim3(paired ? 128 : 64), 0, st, (const DevItem *) b->items.p, b->P,
                        (const int *) b->bandL.p, (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
-                       (const char *) b->chars.p, (const char *) b->charsY.p, (const double *) c->models5.p,
+                       (const char *) b->chars.p, (const char *) b->charsY.p, (const double *) c->tables[DNA5].block.p,
                        b->Fstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
                        em ? b->expect.p : nullptr);
     HIP_TRY(hipGetLastError());
@@ -2270,7 +1352,7 @@ static int enqueue_general(cpecan_batch *b, hipStream_t st) {
     const void *y = m.x == X_CHARS ? (const void *) b->charsY.p : (const void *) b->events.p; /* (nucleotides on both sides) */
     DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
                          (const long long *) b->cellPrefix.p, x, y, m.yAux ? (const double *) b->logNoise.p : nullptr,
-                         m.models(c), b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p,
+                         c->tables[b->machine].block.p, b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p,
                          b->totVal.p, b->nTot.p, b->dbgB.p, em ? b->expect.p : nullptr };
     DevParams P = b->P;
     /* the forward sweep's two previous diagonals live in LDS where the widest band fits (three diagonals of the
@@ -2315,14 +1397,11 @@ static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *
     /* the models as the sweeps read them, and whether any of them lets gap Y switch to gap X (the nanopore default
      * does not, stateMachine.c:1287: the kernels then run the build without that term; the vanilla machine has no such
      * transition) */
-    all.models = (const double *) MACHINES[b->machine].models(c);
-    if (sy->machine == SWEEP_HDP) {
-        for (const DevHdpModel &m : c->hostModelsH)
-            if (m.t[T_GAP_SWITCH_TO_X] > -INFINITY) all.withSwitch = 1;
-    } else if (sy->machine == SWEEP_STRAWMAN) {
-        for (int m = 0; m < c->nModels; m++)
-            if (c->switchToX[(size_t) m] > -INFINITY) all.withSwitch = 1;
-    }
+    const ModelTable &table = c->tables[b->machine];
+    all.models = table.block.p;
+    if (sy->machine == SWEEP_HDP || sy->machine == SWEEP_STRAWMAN)
+        for (double switchToX : table.side)
+            if (switchToX > -INFINITY) all.withSwitch = 1;
     int rc = sy->once->launch_track(L->fwd, all);
     /* the assembly sweeps (no model of the batch may let gap Y switch to gap X: they have no such term) */
     const bool asmRun = b->useAsm && !all.withSwitch && rc == 0;
@@ -2330,7 +1409,7 @@ static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *
     if (asmRun) {
         asmArgs.items = b->items.p; asmArgs.trackBase = b->trackBase.p; asmArgs.planWin = b->planWin.p;
         asmArgs.planCtl = b->planCtl.p; asmArgs.planOff = b->planOff.p; asmArgs.events = b->events.p;
-        asmArgs.models = c->models.p; asmArgs.track = b->track.p; asmArgs.ring = b->Fstore.p;
+        asmArgs.models = table.block.p; asmArgs.track = b->track.p; asmArgs.ring = b->Fstore.p;
         asmArgs.ringDoubles = b->ringDoubles; asmArgs.states = b->syStates.p; asmArgs.ctx = b->asmCtx.p;
         asmArgs.ctxBytes = ASM_CTX_BYTES; asmArgs.coef = cpecan_asm_coef(c->device); asmArgs.nItems = (int) b->nItems;
         asmArgs.ringD = b->ringD; asmArgs.maxWindows = b->asmMaxWindows; asmArgs.scratch = b->syScratch.p;
@@ -2347,7 +1426,7 @@ static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *
             span("planCtl", b->planCtl.p, b->planCtl.n * sizeof(AsmPlanCtl));
             span("planOff", b->planOff.p, b->planOff.n * 8);
             span("events", b->events.p, b->events.n * 8);
-            span("models", c->models.p, c->models.n * 8);
+            span("models", table.block.p, table.block.n * 8);
             span("track", b->track.p, b->track.n * 8);
             span("ring", b->Fstore.p, b->Fstore.n * 8);
             span("states", b->syStates.p, b->syStates.n);

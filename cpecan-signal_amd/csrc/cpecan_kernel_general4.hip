@@ -9,7 +9,7 @@
  * reference has no Hmm container for this machine
  * (hmmContinuous_getEmptyHmm, impl/continuousHmm.c:913-945, knows threeState, threeStateHdp and vanilla).
  *
- * The model is a strawMan table (cpecan_hip.hip: derive_rows) whose header holds the machine's eleven transitions in the
+ * The model is a strawMan table (cpecan_models.hip: derive_rows) whose header holds the machine's eleven transitions in the
  * member order of _StateMachine4 (inc/stateMachine.h:134-152).
  */
 #include "cpecan_general.h"

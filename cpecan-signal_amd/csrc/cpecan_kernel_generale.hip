@@ -14,7 +14,7 @@
  *
  * Every log() the reference takes per cell is one of the skip bin (log beta, log alpha, log(1-beta), log(1-alpha)),
  * the k-mer, the event (log noise, the six duration terms) or n (log n): the host takes them with its libm
- * (cpecan_hip.hip: derive_echelon, batch creation) and the device adds them in the reference's order.
+ * (cpecan_models.hip: derive_echelon; cpecan_hip.hip: batch creation) and the device adds them in the reference's order.
  *
  * Quirks kept: the end state vector is {0.790..., 0.196...} used as log values (:1620, "these aren't log"); the sum of
  * multipleKmerMatchProb starts from 0.0, not log zero; its only look-ahead is whether the character 6n places after

@@ -10,7 +10,7 @@
  * expectations.  The inputs and the emission are shared with the echelon kernel (cpecan_general_twodists.h).
  *
  * Every log() the reference takes per cell is a function of the skip bin, the k-mer or the event
- * alone, so the host takes them once with its libm (cpecan_hip.hip: derive_vanilla); the device
+ * alone, so the host takes them once with its libm (cpecan_models.hip: derive_vanilla); the device
  * adds them in the reference's order.
  */
 #include "cpecan_general_twodists.h"

@@ -515,7 +515,7 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
     const double *__restrict__ ev = events + 3 * it.yOff;
     const double *cf = sh.coef;
 #ifdef SY_VANILLA
-    /* the position-independent transitions (cpecan_hip.hip: derive_vanilla); the others are the slot row's */
+    /* the position-independent transitions (cpecan_models.hip: derive_vanilla); the others are the slot row's */
     const double lYM = model[CP_VHDR_LOG_YM], lYY = model[CP_VHDR_LOG_YY];
 #else
     /* a -inf gapY->gapX transition (the nanopore default, stateMachine.c:1287) contributes

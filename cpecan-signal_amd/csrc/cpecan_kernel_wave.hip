@@ -457,7 +457,7 @@ template <bool SW> __device__ void forward_window(const DevItem &it, const DevPa
 #pragma unroll
     for (int i = 0; i < 9; i++) T[i] = model[i];
 #ifdef WV_VANILLA
-    /* the position-independent part of the machine: a_ym, a_yy and the end vector (cpecan_hip.hip: derive_vanilla) */
+    /* the position-independent part of the machine: a_ym, a_yy and the end vector (cpecan_models.hip: derive_vanilla) */
     const double lYM = uni64_d(model[CP_VHDR_LOG_YM]), lYY = uni64_d(model[CP_VHDR_LOG_YY]);
     const double endM = uni64_d(model[CP_VHDR_END_M]), endX = uni64_d(model[CP_VHDR_END_X]),
                  endY = uni64_d(model[CP_VHDR_END_Y]);
@@ -2512,7 +2512,7 @@ int cpecan_wave_launch_counts(hipStream_t stream, const SweepArgs &a) {
  * exposes for sequence index x - 1 -- a pointer to character max(x - 2, 0): the skip bin looks at the k-mers there
  * and one further, the emissions at the one further (columns 0, 1 and 2 all score k-mers 0 and 1, as in the
  * reference).  Row: per table (match, extra event) mu, sd, 1/sd, K, noise mean, 1/mean, lambda,
- * log(lambda) - log(2 pi); then the bin's five log transition probabilities (cpecan_hip.hip: derive_vanilla) */
+ * log(lambda) - log(2 pi); then the bin's five log transition probabilities (cpecan_models.hip: derive_vanilla) */
 extern "C" __global__ void cpecan_k_wv_track_vanilla(const DevItem *__restrict__ items, long long nItems,
                                                      const long long *__restrict__ trackBase,
                                                      const unsigned short *__restrict__ kidx,

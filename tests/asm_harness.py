@@ -38,7 +38,7 @@ def generated_text(cache={}):
 
 
 def derive_model(transitions, match, gap_x, gap_y):
-    """derive_rows() of cpecan_hip.hip: mu, sd, 1/sd, K = -0.918... - log(sd) (host libm) per Gaussian; gap-X value"""
+    """derive_rows() of cpecan_models.hip: mu, sd, 1/sd, K = -0.918... - log(sd) (host libm) per Gaussian; gap-X value"""
     m = np.zeros(MODEL_STRIDE)
     m[:9] = transitions
     rows = m[MODEL_HEADER:].reshape(NKMERS + 1, ROW)
