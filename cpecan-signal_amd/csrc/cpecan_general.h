@@ -93,7 +93,7 @@ __device__ __forceinline__ void general_multi_decode(const DevGeneralArgs &a, co
 #pragma unroll
                 for (int s = 1; s < 6; s++) {
                     e[s] = (fdd[cc * S + s] + bdd[cc * S + s]) - total;
-                    if (exp(e[s]) >= P.threshold) {
+                    if (e[s] >= P.logThrSlack) { /* (the exact threshold test is the readback's, with the host libm) */
                         hits |= 1u << s;
                         cnt += s;
                     }
@@ -307,7 +307,7 @@ __device__ __forceinline__ void general_pass(M &m, const DevGeneralArgs &a, cons
                         if (x > 0 && y > 0) {
                             e = (fdd[cc * S] + bdd[cc * S]) - total;
                             p = exp(e);
-                            hit = p >= P.threshold;
+                            hit = e >= P.logThrSlack; /* (the exact threshold test is the readback's, with the host libm) */
                         }
                     }
                     const unsigned long long mk = __ballot(hit);

@@ -1378,9 +1378,10 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
         if (!scan) {
             /*
              * Decode from the sweep's candidate lists (a few cells per diagonal instead of the whole
-             * band): every wave walks its own list twice.  First the exact test of
-             * diagonalCalculationPosteriorMatchProbs marks the hits in the (diagonal, wave) masks, then,
-             * with the per-diagonal offsets known, each hit is ranked inside its diagonal and written.
+             * band): every wave walks its own list twice.  First the cells whose exponent reaches
+             * logThrSlack are marked in the (diagonal, wave) masks (the exact threshold test of
+             * diagonalCalculationPosteriorMatchProbs is the readback's), then, with the per-diagonal
+             * offsets known, each hit is ranked inside its diagonal and written.
              */
             const int nC = sh.cnt[1][wave][0];
             for (int i = threadIdx.x; i < nPost * SY_MSK; i += SY_P) msk[i] = 0ull;
@@ -1392,8 +1393,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     const int k = kx.x, x = kx.y, t = tPost0 - k;
                     const double ee = myFb[i] - wtot[k / 10].total;
                     if (!(x >= 1 && x <= t - 1 && ee >= P.logThrSlack)) continue;
+                    /* (a candidate by its exponent alone: the device's exp() can come out an ulp below the host's, and
+                     * the exact threshold test is the readback's, with the host libm) */
                     double p = exp(ee);
-                    if (!(p >= P.threshold)) continue;
                     if (!pass) {
                         atomicOr(msk + k * (long long) SY_MSK + wave, 1ull << (x & 63));
                         continue;
@@ -1504,12 +1506,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                         if (k < nPost) {
                             const int xlo = xminA[j] > 1 ? xminA[j] : 1, xhi = xmaxA[j] < t - 1 ? xmaxA[j] : t - 1;
                             const bool ok = x >= xlo && x <= xhi && ee >= P.logThrSlack;
-                            unsigned long long m = 0ull;
-                            if (__ballot(ok) != 0ull) {
-                                bool hit = false;
-                                if (ok) hit = exp(ee) >= P.threshold;
-                                m = __ballot(hit);
-                            }
+                            const unsigned long long m = __ballot(ok); /* (the exact threshold test is the readback's) */
                             if (lane == 0) msk[k * SY_MSK + wave] = m;
                         }
                     } else if (own[j] != 0ull) {

@@ -532,7 +532,7 @@ template <int L, bool EM, int ROLE> __device__ __forceinline__ void wave5_body(
                         if (x > 0 && y > 0) {
                             ee = stage[cc] - total;
                             p = exp(ee);
-                            hit = p >= P.threshold;
+                            hit = ee >= P.logThrSlack; /* (the exact threshold test is the readback's, with the host libm) */
                         }
                     }
                     const unsigned long long m = __ballot(hit);

@@ -117,9 +117,26 @@ def _decode(L, sm, d, F, B, seqs, total, p):
     return out
 
 
-def banded(machine, seqs, anchors, threshold, min_diags, tb_diags, expansion, ragged=(0, 0)):
+def _exponents(L, d, F, B, l, r, total, threshold):
+    """the exponent (F[s] + B[s]) - total of every pair diagonalCalculationMultiPosteriorMatchProbs emits on diagonal
+    d, in its order, read from the DP cells (the function keeps the integer posterior only)"""
+    f, b = L.dpMatrix_getDiagonal(F, d), L.dpMatrix_getDiagonal(B, d)
+    out = []
+    for xmy in range(l, r + 1, 2):
+        if (d + xmy) // 2 <= 0 or (d - xmy) // 2 <= 0:
+            continue
+        fc, bc = L.dpDiagonal_getCell(f, xmy), L.dpDiagonal_getCell(b, xmy)
+        for s in range(1, 6):
+            e = fc[s] + bc[s] - total
+            if not math.exp(e) < threshold:
+                out += [e] * s
+    return out
+
+
+def banded(machine, seqs, anchors, threshold, min_diags, tb_diags, expansion, ragged=(0, 0), exponents=False):
     """getPosteriorProbsWithBanding with diagonalCalculationMultiPosteriorMatchProbs: pairs in emission order and the
-    (diagonal, totalProbability) refreshes in the order computed"""
+    (diagonal, totalProbability) refreshes in the order computed; with `exponents`, also every pair's exponent
+    ('logp'), read from the DP cells on the host"""
     L, sm = lib(), machine.sm
     lX, lY = seqs.lX, seqs.lY
     Lb, Rb = cp.band_construct(np.asarray(anchors, np.int64).reshape(-1, 2), lX, lY, expansion)
@@ -130,7 +147,7 @@ def banded(machine, seqs, anchors, threshold, min_diags, tb_diags, expansion, ra
     p.contents.threshold = threshold
     L.dpDiagonal_initialiseValues(L.dpMatrix_createDiagonal(F, diag(0)), sm,
                                   _fn(sm, "raggedStartStateProb" if ragged[0] else "startStateProb"))
-    pairs, totals = [], []
+    pairs, totals, logp = [], [], []
     traced = 0
     for d in range(1, D + 1):
         L.dpDiagonal_zeroValues(L.dpMatrix_createDiagonal(F, diag(d)))
@@ -157,6 +174,9 @@ def banded(machine, seqs, anchors, threshold, min_diags, tb_diags, expansion, ra
                     totals.append((d2, total))
                 calcs += 1
                 pairs.append(_decode(L, sm, d2, F, B, seqs, total, p))
+                if exponents:
+                    logp += _exponents(L, d2, F, B, int(Lb[d2]), int(Rb[d2]), total, threshold)
+                    assert len(logp) == sum(len(q) for q in pairs), d2
                 if d2 < frm or at_end:
                     L.dpMatrix_deleteDiagonal(F, d2)
             if d2 + 1 <= D:
@@ -171,8 +191,11 @@ def banded(machine, seqs, anchors, threshold, min_diags, tb_diags, expansion, ra
     L.dpMatrix_destruct(B)
     L.pairwiseAlignmentBandingParameters_destruct(p)
     tri = np.concatenate(pairs) if pairs else np.zeros((0, 3), np.int64)
-    return dict(triples=tri, totals_xay=np.array([t[0] for t in totals], np.int64),
-                totals=np.array([t[1] for t in totals], np.float64))
+    out = dict(triples=tri, totals_xay=np.array([t[0] for t in totals], np.int64),
+               totals=np.array([t[1] for t in totals], np.float64))
+    if exponents:
+        out["logp"] = np.array(logp, np.float64)
+    return out
 
 
 def unbanded(machine, seqs, threshold, ragged=(0, 0)):

@@ -69,17 +69,17 @@ def run_batch(ctx, pieces, bp, flags=0):
     npairs, ntot, _ = b.counts()
     out = []
     for i in range(len(pieces)):
-        tri, _ = b.pairs(i, npairs[i])
+        tri, logp = b.pairs(i, npairs[i])
         xay, tot = b.totals(i, ntot[i])
-        out.append(dict(triples=tri, totals_xay=xay, totals=tot))
+        out.append(dict(triples=tri, logp=logp, totals_xay=xay, totals=tot))
     b.close()
     return out
 
 
-def host_piece(r, x1, y1, x2, y2, an, rl, rr, bp):
+def host_piece(r, x1, y1, x2, y2, an, rl, rr, bp, exponents=False):
     s = e.Seqs(r["seq"][x1:], x2 - x1, r["events"][y1:y2])
     ref = e.banded(r["machine"], s, an, bp.threshold, bp.minDiagsBetweenTraceBack, bp.traceBackDiagonals,
-                   bp.diagonalExpansion, (rl, rr))
+                   bp.diagonalExpansion, (rl, rr), exponents)
     s.close()
     return ref
 
