@@ -160,12 +160,14 @@ __device__ __forceinline__ double cp_logGauss(double x, double mu, double sd, do
  *     for lane in 0..63: if valid[lane]: acc = logAdd(acc, v[lane])
  * (the order-dependent fold of dpDiagonal_dotProduct, impl/pairwiseAligner.c:587-597).  A term
  * leaves acc unchanged exactly when it is -inf or lies >= 7.5 below acc, so the loop only visits
- * the lanes that change the running value; acc is wave-uniform on entry and exit. */
+ * the lanes that change the running value; acc is wave-uniform on entry and exit.  A NaN term is neither (logAdd
+ * answers NaN for it, and for every term after it): it fails `v <= -inf`, and acc - v >= 7.5 with it or with a NaN
+ * acc, so it is visited, and so is every finite term after it. */
 __device__ __forceinline__ double cp_wave_seq_fold(double acc, double v, bool valid) {
     const int lane = threadIdx.x & 63;
     unsigned long long after = ~0ull; /* lanes still to be visited */
     for (;;) {
-        bool eff = valid && ((after >> lane) & 1ull) && (v > CP_NEG_INF) && !(acc - v >= 7.5);
+        bool eff = valid && ((after >> lane) & 1ull) && !(v <= CP_NEG_INF) && !(acc - v >= 7.5);
         unsigned long long m = __ballot(eff);
         if (m == 0ull) break;
         int first = __ffsll((long long) m) - 1;

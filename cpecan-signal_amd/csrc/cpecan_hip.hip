@@ -273,8 +273,8 @@ static BatchEnv read_batch_env() {
              as ? atoi(as) : -1, wave5Off };
 }
 
-/* The kernel choice: a function of the machine, what the caller asked for, the environment and two facts about the
- * batch's bands.  Asked about the narrowest band there is (maxWidth 0, edges stepping by one) it tells what holds
+/* The kernel choice: a function of the machine, what the caller asked for, the environment, two facts about the
+ * batch's bands and one about its characters (a vanilla batch that meets a k-mer that is none).  Asked about the narrowest band there is (maxWidth 0, edges stepping by one) it tells what holds
  * for every band: what it refuses then, it refuses always, and the general kernel then is the general kernel always. */
 struct DispatchQuery {
     Machine machine;
@@ -282,6 +282,7 @@ struct DispatchQuery {
     int maxWidth;        /* the widest band of the batch, in cells */
     bool edgesStepByOne; /* every band edge moves by at most one k-mer per diagonal */
     BatchEnv env;
+    bool noKmer = false; /* a vanilla item meets a k-mer that is none (vanilla_meets_no_kmer) */
 };
 struct Dispatch {
     int kernel = CPECAN_KERNEL_GENERAL; /* CPECAN_KERNEL_GENERAL or _SYSTOLIC, as cpecan_hip_batch_info reports */
@@ -308,7 +309,10 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
     /* the HDP and vanilla machines have wave-per-alignment kernels of their own, for the posterior decode and for the
      * E-step, and CPECAN_FLAG_GENERAL_KERNEL keeps such a batch on the general kernel; the 5-state, 4-state and
      * echelon machines have no register-resident kernels */
-    const int asked = !m.wave ? CPECAN_KERNEL_GENERAL
+    /* the reference scores a k-mer that is none as NaN under the vanilla machine, and NaN spreads through its logAdd;
+     * cpecan_k_generalv adds as the reference does, the register-resident kernels' branch-free logAdd (v_max / v_min)
+     * drops a NaN operand: such a batch runs on the general kernel */
+    const int asked = !m.wave || (q.machine == VANILLA && q.noKmer) ? CPECAN_KERNEL_GENERAL
                       : !m.ownChoice ? q.kernel
                       : (q.flags & CPECAN_FLAG_GENERAL_KERNEL) ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
     if (unbanded && (q.mode != CPECAN_MODE_POSTERIOR || asked == CPECAN_KERNEL_SYSTOLIC))
@@ -779,6 +783,20 @@ static int check_items(const cpecan_ctx *c, Machine machine, const BatchInput &i
     return CPECAN_OK;
 }
 
+/* Whether an item of a vanilla batch meets a k-mer that is none: a character outside ACGT among its lX + 5, or fewer
+ * than two k-mers (sequence_getKmer2 looks one k-mer ahead, so an item of no or one k-mer reads the k-mer that runs
+ * into its string's terminator). */
+static bool vanilla_meets_no_kmer(const BatchInput &in) {
+    for (int64_t i = 0; i < in.nItems; i++) {
+        const cpecan_item &s = in.items[i];
+        if (s.lX < 2) return true;
+        const char *x = in.xChars + s.x_offset;
+        for (int64_t k = 0; k < s.lX + 5; k++)
+            if (x[k] != 'A' && x[k] != 'C' && x[k] != 'G' && x[k] != 'T') return true;
+    }
+    return false;
+}
+
 /* The bands themselves, the items dealt to the host threads (band, cell prefix, traceback schedule: ~15 000 diagonals
  * per C3 read).  A thread's working copy of one item's intervals stays in its cache. */
 static int build_bands(const BatchInput &in, BandPlan &plan, bool general) {
@@ -1240,6 +1258,7 @@ static int batch_create_impl(cpecan_ctx *c, Machine machine, const cpecan_item *
     lap("band construction and window schedule (host)");
     q.maxWidth = plan.maxWidth;
     q.edgesStepByOne = plan.edgesStepByOne;
+    q.noKmer = machine == VANILLA && vanilla_meets_no_kmer(in);
     const Dispatch d = choose_dispatch(q);
     if (d.refusal != CPECAN_OK) return fail(d.refusal, "%s", d.why);
 

@@ -29,8 +29,18 @@ struct Vanilla : TwoDistCells<3> {
     static constexpr bool kExpect = true;
     double (*sExp)[CP_EXPECTV_LEN + 1]; /* the E-step's sums in LDS, one copy per wave */
 
+    long long lX;
+
     __device__ Vanilla(const DevGeneralArgs &a, const DevItem &it, double (*sExp_)[CP_EXPECTV_LEN + 1])
-        : TwoDistCells<3>(a, it, CP_VMODEL_STRIDE), sExp(sExp_) {}
+        : TwoDistCells<3>(a, it, CP_VMODEL_STRIDE), sExp(sExp_), lX(it.lX) {}
+
+    /* TwoDistCells::kmers_of within the item's own sequence: a k-mer that starts at or past character lX runs into the
+     * terminator of the reference's string and is no k-mer there (an item of no or one k-mer reads such a one) */
+    __device__ __forceinline__ void kmers_of(long long ix, int &kPrev, int &kCur) const {
+        const long long p = ix > 0 ? ix - 1 : 0;
+        kPrev = p < lX ? (int) kidx[p] : 4096;
+        kCur = p + 1 < lX ? (int) kidx[p + 1] : 4096;
+    }
 
     __device__ __forceinline__ double match_into(const double *middle, long long x, long long y) const {
         int kPrev, kCur;

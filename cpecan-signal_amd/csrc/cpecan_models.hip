@@ -310,7 +310,7 @@ static void derive_vanilla_bins(double m_to_y_not_x, const double *skip_probs, d
     }
 }
 
-static void derive_vanilla(const cpecan_vanilla_model *m, double *dst) {
+static void derive_vanilla(const cpecan_vanilla_model *m, double *dst, bool echelon = false) {
     for (int i = 0; i < CP_VHDR; i++) dst[i] = 0.0;
     dst[0] = m->m_to_y_not_x;
     dst[1] = m->e_to_e;
@@ -327,9 +327,13 @@ static void derive_vanilla(const cpecan_vanilla_model *m, double *dst) {
         double *r = rows + (size_t) k * CP_VROW;
         for (int t = 0; t < 2; t++) {
             double *q = r + 6 * t;
-            if (k == CPECAN_NUM_KMERS) { /* not a k-mer: level -inf, the noise term kept finite */
+            if (k == CPECAN_NUM_KMERS) {
+                /* not a k-mer: the reference's model accessors read 0.0 for an index past the table (:221-240), so the
+                 * level term is LOG_ZERO (sd 0) and the noise term NaN (mean 0, lambda 0: 0 * inf), and their sum, the
+                 * emission, NaN -- reproduced here; the echelon machine keeps its noise term finite (its host DP's) */
                 q[CP_V_MU] = 0.0; q[CP_V_SD] = 0.0; q[CP_V_K] = -INFINITY;
-                q[CP_V_NMU] = 1.0; q[CP_V_LAMBDA] = 1.0; q[CP_V_LLAMBDA] = 0.0;
+                q[CP_V_NMU] = echelon ? 1.0 : 0.0; q[CP_V_LAMBDA] = echelon ? 1.0 : 0.0;
+                q[CP_V_LLAMBDA] = echelon ? 0.0 : -INFINITY;
                 continue;
             }
             const double *a = (t ? m->gap_y_probs : m->match_probs) + 1 + (size_t) k * CPECAN_MODEL_PARAMS;
@@ -486,7 +490,7 @@ static void derive_echelon(const cpecan_echelon_model *m, double *dst) {
     v.match_probs = m->match_probs;
     v.skip_probs = m->skip_probs;
     v.gap_y_probs = m->gap_y_probs;
-    derive_vanilla(&v, dst);
+    derive_vanilla(&v, dst, true);
     for (int i = 0; i < CP_VHDR; i++) dst[i] = 0.0;
     dst[CP_VHDR_END_M] = m->end_match_prob;
     dst[CP_VHDR_END_X] = m->end_from_x_prob;

@@ -255,7 +255,9 @@ typedef struct {
 #define CPECAN_FLAG_GENERAL_KERNEL 32 /* cpecan_hip_batch_create_hdp / _vanilla: keep the batch on the general kernel
                                          (any band width) instead of the wave-per-alignment kernels of that machine
                                          (posterior decode; bands <= 248 k-mers for the HDP machine, <= 184 for the
-                                         vanilla one); same results bit for bit */
+                                         vanilla one); same results bit for bit on reads of ACGT (an HDP column that
+                                         is no k-mer scores NaN here and -inf on the wave builds; a vanilla batch with
+                                         one runs here anyway, see cpecan_hip_batch_create_vanilla) */
 #define CPECAN_FLAG_WIDE_BANDS 128 /* cpecan_hip_batch_create (strawMan machine, posterior decode and expectations): a
                                       batch whose widest band is 249..504 k-mers runs on the six- or eight-wave build of
                                       the workgroup-per-alignment kernels (up to 376, up to 504) instead of the general
@@ -267,7 +269,9 @@ typedef struct {
                                       the same kernels with four, six or eight waves per workgroup (up to 248, 376, 504)
                                       unless it is un-banded or carries CPECAN_FLAG_GENERAL_KERNEL; a vanilla batch of
                                       CPECAN_MODE_EXPECTATIONS ignores the flag (its E-step past 184 k-mers runs on the
-                                      general kernel), and so do the other machines.  Same results bit for bit.  The
+                                      general kernel), and so does a vanilla batch that meets a k-mer that is none (see
+                                      cpecan_hip_batch_create_vanilla), and so do the other machines.  Same results bit
+                                      for bit.  The
                                       environment variable CPECAN_WIDE_BANDS=1 (read per batch) sets it for every
                                       strawMan batch and every vanilla posterior batch: the way in for callers of
                                       libcpecan_host.so and vanillaAlign. */
@@ -306,7 +310,15 @@ int cpecan_hip_batch_create_dna(cpecan_ctx *ctx, const cpecan_item *items, int64
  * sequence_getKmer2 / sequence_getEvent): same buffers as cpecan_hip_batch_create, model_id is a
  * cpecan_hip_modelsv_create id.  flags: UNBANDED or EXPECTATIONS (general kernel), GENERAL_KERNEL, WIDE_BANDS.  There
  * is no kernel argument: the batch picks its kernels itself (the wave builds up to 184 k-mers of band, the general kernel
- * past that), and CPECAN_FLAG_WIDE_BANDS alone selects the workgroup builds for posterior batches of 185..504 k-mers. */
+ * past that), and CPECAN_FLAG_WIDE_BANDS alone selects the workgroup builds for posterior batches of 185..504 k-mers.
+ * One exception, whatever the flags: a batch in which any item has a character outside ACGT among its lX + 5, or fewer
+ * than two k-mers (lX < 2: sequence_getKmer2 looks one k-mer ahead, past such an item's end), runs as a whole on the
+ * general kernel.  The reference scores a k-mer that is none as NaN under this machine and NaN spreads through its
+ * logAdd; the general kernel reproduces that bit for bit, the register-resident kernels cannot (their branch-free
+ * logAdd drops a NaN operand).  One such read moves its whole batch: callers that care for the speed of the others
+ * put reads with foreign characters into a batch of their own (the general kernel is several times slower than
+ * the wave kernels; what the move costs a vanilla batch has not been measured).  cpecan_hip_batch_info reports the
+ * kernel. */
 int cpecan_hip_batch_create_vanilla(cpecan_ctx *ctx, const cpecan_item *items, int64_t n_items,
                                     const char *x_chars, int64_t n_x, const double *events, int64_t n_events,
                                     const int64_t *anchors, int64_t n_anchor_pairs,

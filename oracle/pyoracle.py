@@ -327,12 +327,22 @@ class HdpModel:
 
 
 class Sm5Model:
-    def __init__(self):
+    """5-state symbol model: the reference's defaults, or the given tables in their place (transitions[17] in the
+    order of the C-ABI's Sm5ModelDesc, match[16], gx[4], gy[4])"""
+
+    def __init__(self, transitions=None, match=None, gx=None, gy=None):
         self.match = np.zeros(16)
         self.gx = np.zeros(4)
         self.gy = np.zeros(4)
         self.c = OrcModel()
         lib().orc_defaults_sm5(C.byref(self.c), _ptr(self.match), _ptr(self.gx), _ptr(self.gy))
+        if transitions is not None:
+            assert len(transitions) == 17
+            for i, v in enumerate(transitions):
+                self.c.t[i] = v
+        for own, given in ((self.match, match), (self.gx, gx), (self.gy, gy)):
+            if given is not None:
+                own[:] = np.asarray(given, dtype=np.float64).reshape(own.shape)  # (in place: the C struct points here)
 
 
 def _collect(res):
