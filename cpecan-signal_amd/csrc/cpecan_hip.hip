@@ -68,7 +68,9 @@ extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *stat
  * bands up to 248, 376 and 504 k-mers; their table starts one class earlier because the vanilla wave builds end at 184),
  * reached the same way and for the posterior decode only: a vanilla E-step past 184 k-mers stays on the general kernel.
  * Built with -DSY_HDP it gives the HDP machine's wide builds (_h6, _h8: bands of 249..376 and 377..504 k-mers, past the
- * HDP wave builds), which answer to a flag of their own, CPECAN_FLAG_WIDE_BANDS_HDP, again for the posterior decode only. */
+ * HDP wave builds), which answer to a flag of their own, CPECAN_FLAG_WIDE_BANDS_HDP, again for the posterior decode only;
+ * with -DSY_HDP -DSY_ESTEP the HDP machine's E-step at the same two widths (_he6, _he8: the sweeps in E-step form and the
+ * HDP form of the expectation kernel), a table of its own that answers to CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP. */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
@@ -77,6 +79,7 @@ SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
 SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
 SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
+SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
 typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
@@ -85,6 +88,7 @@ static const SweepBuild *const SY_WIDE_BUILDS[3] = { &cpecan_systolic_build_r6, 
 static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4, &cpecan_systolic_build_v6,
                                                       &cpecan_systolic_build_v8, nullptr };
 static const SweepBuild *const SYH_WIDE_BUILDS[3] = { &cpecan_systolic_build_h6, &cpecan_systolic_build_h8, nullptr };
+static const SweepBuild *const SYHE_WIDE_BUILDS[3] = { &cpecan_systolic_build_he6, &cpecan_systolic_build_he8, nullptr };
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
@@ -213,11 +217,14 @@ struct MachineRow {
     const char *noDumps;       /* the refusal of CPECAN_FLAG_DEBUG_DUMP (null: it has cell dumps) */
     bool bandedEstep;          /* its E-step refuses CPECAN_FLAG_UNBANDED */
     /* the register-resident kernels: the machine's wave family and, where a batch may ask for it, its workgroup family
-     * (null: none); the wide builds of the workgroup family (null: none) and the modes they serve, a bit per mode */
+     * (null: none); per mode (CPECAN_MODE_POSTERIOR, CPECAN_MODE_EXPECTATIONS) the wide builds of the workgroup family
+     * that serve it (null: none) and the flag they answer to: CPECAN_FLAG_WIDE_BANDS, CPECAN_FLAG_WIDE_BANDS_HDP or
+     * CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP (0: none) */
     SweepFamily *wave, *workgroup;
-    const SweepBuild *const *wide;
-    int wideModes;
-    int wideFlag;   /* the flag its wide builds answer to: CPECAN_FLAG_WIDE_BANDS, or CPECAN_FLAG_WIDE_BANDS_HDP (0: none) */
+    struct Wide {
+        const SweepBuild *const *builds;
+        int flag;
+    } wide[2];
     bool ownChoice; /* its create call has no kernel argument: AUTO, or the general kernel with CPECAN_FLAG_GENERAL_KERNEL */
     /* the general kernel and what distinguishes its argument record */
     void (*general)(DevGeneralArgs, DevParams); /* (null: cpecan_k_generale, which takes a third record) */
@@ -225,21 +232,22 @@ struct MachineRow {
     bool yAux;       /* log(event noise) per event */
     int ldsMaxWidth; /* the widest band whose forward diagonals the general kernel keeps in LDS (0: it keeps none) */
 };
-#define BOTH_MODES (1 << CPECAN_MODE_POSTERIOR | 1 << CPECAN_MODE_EXPECTATIONS)
+#define NO_WIDE { nullptr, 0 }
 static const MachineRow MACHINES[N_MACHINES] = {
-    /* STRAWMAN */ { 3, CPECAN_EXPECTATION_LEN, 4, 0, nullptr, nullptr, false, &WV_BUILDS, &SY_BUILDS, SY_WIDE_BUILDS, BOTH_MODES,
-                     CPECAN_FLAG_WIDE_BANDS, false, cpecan_k_general, X_KIDX, false, 0 },
-    /* DNA5 */     { 5, CPECAN_EXPECTATION5_LEN, 4, 0, nullptr, "DNA batches: no cell dumps", true, nullptr, nullptr, nullptr, 0,
-                     0, false, cpecan_k_general5, X_CHARS, false, 248 },
+    /* STRAWMAN */ { 3, CPECAN_EXPECTATION_LEN, 4, 0, nullptr, nullptr, false, &WV_BUILDS, &SY_BUILDS,
+                     { { SY_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS }, { SY_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS } }, false, cpecan_k_general, X_KIDX, false, 0 },
+    /* DNA5 */     { 5, CPECAN_EXPECTATION5_LEN, 4, 0, nullptr, "DNA batches: no cell dumps", true, nullptr, nullptr, { NO_WIDE, NO_WIDE },
+                     false, cpecan_k_general5, X_CHARS, false, 248 },
     /* VANILLA */  { 3, CPECAN_EXPECTATIONV_LEN, 4, 0, nullptr, "vanilla batches: no cell dumps", true, &VV_BUILDS, nullptr,
-                     SYV_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS, true, cpecan_k_generalv, X_KIDX, true, 0 },
+                     { { SYV_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS }, NO_WIDE }, true, cpecan_k_generalv, X_KIDX, true, 0 },
     /* HDP */      { 3, CPECAN_EXPECTATIONH_LEN, 16, 0, nullptr, "HDP batches: no cell dumps", true, &HV_BUILDS, nullptr,
-                     SYH_WIDE_BUILDS, 1 << CPECAN_MODE_POSTERIOR, CPECAN_FLAG_WIDE_BANDS_HDP, true, cpecan_k_generalh, X_KID, false, 0 },
+                     { { SYH_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS_HDP }, { SYHE_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP } }, true,
+                     cpecan_k_generalh, X_KID, false, 0 },
     /* SM4 */      { 4, CPECAN_EXPECTATION_LEN, 4, 0, "4-state batches: posterior decode only, no cell dumps",
-                     "4-state batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, 0, false,
+                     "4-state batches: posterior decode only, no cell dumps", false, nullptr, nullptr, { NO_WIDE, NO_WIDE }, false,
                      cpecan_k_general4, X_KIDX, false, 0 },
     /* ECHELON */  { 7, CPECAN_EXPECTATION_LEN, 16, 4, "echelon batches: posterior decode only, no cell dumps",
-                     "echelon batches: posterior decode only, no cell dumps", false, nullptr, nullptr, nullptr, 0, 0, false,
+                     "echelon batches: posterior decode only, no cell dumps", false, nullptr, nullptr, { NO_WIDE, NO_WIDE }, false,
                      nullptr, X_KIDX, true, 0 },
 };
 
@@ -257,8 +265,9 @@ static int check_machine(Machine machine, int mode, int flags) {
 /* The environment switches the kernel choice reads, parsed once per batch (tests and timing tools set them between
  * batches); CPECAN_DNA_GENERAL once per process. */
 struct BatchEnv {
-    bool wideBands;   /* CPECAN_WIDE_BANDS=1: CPECAN_FLAG_WIDE_BANDS for every batch the wide builds serve */
-    bool wideBandsHdp; /* CPECAN_WIDE_BANDS_HDP=1: CPECAN_FLAG_WIDE_BANDS_HDP for every HDP batch its wide builds serve */
+    int wideFlags;    /* the wide-band flags whose variable is 1, for every batch whose machine and mode have wide builds
+                         behind that flag: CPECAN_WIDE_BANDS (CPECAN_FLAG_WIDE_BANDS), CPECAN_WIDE_BANDS_HDP (.._HDP: HDP
+                         posterior batches), CPECAN_WIDE_BANDS_HDP_ESTEP (.._HDP_ESTEP: HDP batches of expectations) */
     bool waveKernels; /* false under CPECAN_KERNELS=systolic: the workgroup-per-alignment family for every batch */
     int systolicRows; /* CPECAN_SYSTOLIC_ROWS=N: a build of at least N rows (tests, timing) */
     int asmMode;      /* CPECAN_ASM: 0 the compiled kernels, 1 the assembly forward sweep only (the compiled sweep back
@@ -269,8 +278,11 @@ static BatchEnv read_batch_env() {
     static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr;
     const char *wide = getenv("CPECAN_WIDE_BANDS"), *kernels = getenv("CPECAN_KERNELS");
     const char *rows = getenv("CPECAN_SYSTOLIC_ROWS"), *as = getenv("CPECAN_ASM"), *wideH = getenv("CPECAN_WIDE_BANDS_HDP");
-    return { wide && atoi(wide) == 1, wideH && atoi(wideH) == 1, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1,
-             as ? atoi(as) : -1, wave5Off };
+    const char *wideHE = getenv("CPECAN_WIDE_BANDS_HDP_ESTEP");
+    const int wideFlags = (wide && atoi(wide) == 1 ? CPECAN_FLAG_WIDE_BANDS : 0) |
+                          (wideH && atoi(wideH) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP : 0) |
+                          (wideHE && atoi(wideHE) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP : 0);
+    return { wideFlags, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1, as ? atoi(as) : -1, wave5Off };
 }
 
 /* The kernel choice: a function of the machine, what the caller asked for, the environment, two facts about the
@@ -317,13 +329,14 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
                       : (q.flags & CPECAN_FLAG_GENERAL_KERNEL) ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
     if (unbanded && (q.mode != CPECAN_MODE_POSTERIOR || asked == CPECAN_KERNEL_SYSTOLIC))
         return refuse("un-banded alignment: posterior mode on the general kernel only");
-    /* the wide builds of the workgroup family are the strawMan machine's and, for the posterior decode, the vanilla
-     * machine's and the HDP machine's.  A machine's wide builds answer to the flag of its row (the HDP machine's to one
-     * of its own) and each flag has its environment variable: a flag means nothing to the machines of the other flag
-     * or of none, nor to a vanilla or HDP E-step, whose batches past the wave builds run on the general kernel as
-     * without it */
-    const bool wideServes = m.wide != nullptr && (m.wideModes >> q.mode & 1);
-    if (wideServes && (m.wideFlag == CPECAN_FLAG_WIDE_BANDS ? q.env.wideBands : q.env.wideBandsHdp)) d.flags |= m.wideFlag;
+    /* the wide builds of the workgroup family are the strawMan machine's and the HDP machine's and, for the posterior
+     * decode, the vanilla machine's.  A machine's wide builds of a mode answer to the flag its row names for that mode
+     * (the HDP machine's to two of its own, one per mode) and each flag has its environment variable: a flag means
+     * nothing to the machines and modes of another flag or of none -- a vanilla E-step past the wave builds runs on the
+     * general kernel whatever the flags */
+    const MachineRow::Wide &wide = m.wide[q.mode];
+    const bool wideServes = wide.builds != nullptr;
+    if (wideServes) d.flags |= wide.flag & q.env.wideFlags;
     if (asked != CPECAN_KERNEL_GENERAL) {
         /* the family the batch would run on, and the widest band its builds take */
         const bool workgroup = m.workgroup && (!q.env.waveKernels || (q.flags & CPECAN_FLAG_WORKGROUP_KERNELS));
@@ -333,10 +346,10 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
          * family the batch would otherwise run on; a band the family holds is left to it */
         const SweepBuild *wideBuild = nullptr;
         int reach = fam[3]->maxWidth;
-        if (wideServes && (d.flags & m.wideFlag))
-            for (int i = 0; m.wide[i] != nullptr; i++) {
-                if (!wideBuild && q.maxWidth > fam[3]->maxWidth && q.maxWidth <= m.wide[i]->maxWidth) wideBuild = m.wide[i];
-                reach = std::max(reach, m.wide[i]->maxWidth);
+        if (wideServes && (d.flags & wide.flag))
+            for (int i = 0; wide.builds[i] != nullptr; i++) {
+                if (!wideBuild && q.maxWidth > fam[3]->maxWidth && q.maxWidth <= wide.builds[i]->maxWidth) wideBuild = wide.builds[i];
+                reach = std::max(reach, wide.builds[i]->maxWidth);
             }
         const bool fits = q.maxWidth <= reach && q.edgesStepByOne;
         d.kernel = asked != CPECAN_KERNEL_AUTO ? asked
@@ -351,7 +364,7 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
             int r = q.env.systolicRows < 1 ? 1 : q.env.systolicRows > 4 ? 4 : q.env.systolicRows;
             while (r < 4 && q.maxWidth > fam[r - 1]->maxWidth) r++;
             d.build = wideBuild ? wideBuild : fam[r - 1];
-            /* (the builds without an E-step are the wide builds of a machine whose wideModes leave the E-step out) */
+            /* (the builds without an E-step are the wide builds of a machine's posterior mode) */
             if (q.mode == CPECAN_MODE_EXPECTATIONS && !d.build->expect && !d.build->backward_fx)
                 return refuse("the chosen kernel build has no E-step");
             /* the assembly sweeps take the posterior batches of a family that has a build for them (the strawMan

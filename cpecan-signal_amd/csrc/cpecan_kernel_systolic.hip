@@ -41,7 +41,8 @@
 /* this file is compiled once per SY_R (1..4 waves per workgroup: bands up to 56, 120, 184, 248 k-mers; 6 and 8 waves,
  * the wide builds of CPECAN_FLAG_WIDE_BANDS: 376 and 504); the symbols of the builds other than four carry _r1.._r3,
  * _r6, _r8, and the pieces that do not depend on SY_R (track, counts, division self-test) exist in the four-wave build
- * only.  With -DSY_VANILLA it is compiled three times more (4, 6 and 8 waves: _v4, _v6, _v8; see below) */
+ * only.  With -DSY_VANILLA it is compiled three times more (4, 6 and 8 waves: _v4, _v6, _v8; see below), with -DSY_HDP
+ * twice (_h6, _h8) and with -DSY_HDP -DSY_ESTEP twice again (_he6, _he8) */
 /* -DSY_VANILLA: the same two sweeps for the 3-state vanilla signal machine (stateMachine3Vanilla_cellCalculate,
  * impl/stateMachine.c:1368-1409), posterior decode only, with four, six and eight waves per workgroup (bands of up to
  * 248, 376 and 504 k-mers; symbols suffixed _v4, _v6, _v8).  A lane holds the 21 doubles of its k-mer's row of the
@@ -58,8 +59,21 @@
  * head of the model record (DevHdpModel starts with them; only the stride between models differs, which is why these
  * builds compile the sweep back themselves) and the gap-X emission from entry CP_GAPX of the track row
  * (cpecan_k_sy_track_hdp writes log(0.1) there). */
+/* -DSY_HDP -DSY_ESTEP: the HDP machine's E-step at the same two widths, in objects of their own (symbols suffixed _he6,
+ * _he8; the _h6 / _h8 objects keep their device code).  E-step only: SY_MODE(P) is the constant 1, so the forward sweep
+ * keeps every state of every diagonal, the sweep back parks its cells in the B ring, and the candidate lists and both
+ * decodes fold away; cpecan_k_sy_expect is compiled in its HDP form (nine transitions and the likelihood, no k-mer bins,
+ * event-to-k-mer assignments).  The track kernel and the machine record stay the _h8 object's. */
 #if defined(SY_HDP) && defined(SY_VANILLA)
 #error "SY_HDP and SY_VANILLA are builds of their own"
+#elif defined(SY_ESTEP) && !defined(SY_HDP)
+#error "SY_ESTEP: the E-step builds of the HDP machine (-DSY_HDP)"
+#elif defined(SY_ESTEP) && SY_R == 6
+#define SY_SYM(n) n##_he6
+#elif defined(SY_ESTEP) && SY_R == 8
+#define SY_SYM(n) n##_he8
+#elif defined(SY_ESTEP)
+#error "SY_HDP SY_ESTEP: 6 or 8 waves per workgroup"
 #elif defined(SY_HDP) && SY_R == 6
 #define SY_SYM(n) n##_h6
 #elif defined(SY_HDP) && SY_R == 8
@@ -122,7 +136,11 @@
 #define SY_NPRM 1    /* a slot keeps the table row offset */
 #define SY_EVW 2     /* doubles per staged event: grid cell of its mean, offset in the cell */
 #define SY_MODEL_DOUBLES ((long long) (sizeof(DevHdpModel) / sizeof(double)))
+#ifdef SY_ESTEP
+#define SY_MODE(P) 1 /* E-step only */
+#else
 #define SY_MODE(P) 0 /* posterior decode only */
+#endif
 #define SY_HDP_GAPX (-2.3025850929940455) /* log(0.1), stateMachine.c:1347 */
 #else
 #define SY_ROW CP_ROW
@@ -131,7 +149,7 @@
 #define SY_MODEL_DOUBLES ((long long) CP_MODEL_STRIDE)
 #define SY_MODE(P) (P).mode
 #endif
-#if defined(SY_VANILLA) || defined(SY_HDP)
+#if defined(SY_VANILLA) || (defined(SY_HDP) && !defined(SY_ESTEP))
 #define SY_NO_ESTEP /* these builds have no expectation kernel and no ring of backward cells */
 #endif
 #define SY_PREFETCH 4     /* diagonals the backward sweep fetches ahead (== its unroll factor) */
@@ -1638,7 +1656,8 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
     }
 }
 
-#ifndef SY_NO_ESTEP /* (the vanilla machine's E-step and the HDP machine's past 248 k-mers run on the general kernel) */
+#ifndef SY_NO_ESTEP /* (the vanilla machine's E-step runs on the general kernel, the HDP machine's past 248 k-mers there or on
+                    * the _he builds of this kernel) */
 /*
  * Baum-Welch expectations of the traceback window the backward kernel just swept
  * (diagonalCalculation_Expectations :841-863 with cell_signal_updateTransAndKmerSkipExpectations
@@ -1649,13 +1668,24 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
  * gap-X expectations in a register and adds it to the k-mer's bin when its slot moves to another k-mer.
  * The match block is skipped on the window's two lowest diagonals' worth of reach, as in the
  * reference, where forward[t-2] has been freed by then (quirk kept by the general kernel too).
+ *
+ * The HDP machine (-DSY_HDP -DSY_ESTEP; cell_signal_updateTransAndKmerSkipExpectations2 :445-476) collects the nine
+ * transitions and the likelihood the same way, no k-mer bins, and an ASSIGNMENT for every transition into match whose
+ * own posterior reaches the threshold: (from-state + 4 * window, x, y) with its exponent, appended to the alignment's
+ * pair list in whatever order the threads of the window's workgroups get there (the host puts them into the
+ * reference's order when it fetches them) -- the test and the record of cpecan_k_wv_expect_h*, expression for
+ * expression.  Its transitions are the head of the DevHdpModel record, its gap-X emission the track's flat log(0.1).
  */
 extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
     const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTab,
     const double *__restrict__ track, const long long *__restrict__ trackBase,
     const unsigned short *__restrict__ kidx, const double *__restrict__ models, const double *Fring,
     long long ringDoubles, const double *Bring, int ringD, SyState *states, const char *scratch,
-    long long scratchBytes, double *expect, int window) {
+    long long scratchBytes, double *expect, int window
+#ifdef SY_HDP
+    , long long *pairs, double *pairLogp
+#endif
+    ) {
     __shared__ double sExp[16];
     const long long idx = blockIdx.x;
     if (idx >= nItems) return;
@@ -1664,7 +1694,12 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
      * state record is only read here (the backward kernel stamps it with the launch it belongs to) */
     if (state->expectPending != window + 1) return;
     const DevItem it = uniform_item(items[idx]);
+#ifdef SY_HDP
+    const double *model = ((const DevHdpModel *) models)[it.model].t;
+    SyState *stateW = states + idx;
+#else
     const double *model = models + (long long) it.model * CP_MODEL_STRIDE;
+#endif
     double T[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) T[i] = model[i];
@@ -1677,7 +1712,11 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
     const WinTotal *wtot = (const WinTotal *) (scratch + idx * scratchBytes + 2ll * ringD * sizeof(int));
     const int dTop = uni(state->winTop), from = uni(state->winFrom), to = uni(state->winTo);
     const int tPost0 = dTop < from ? dTop : from;
+#ifdef SY_HDP
+    double *dst = expect + (long long) it.model * (9 + 1);
+#else
     double *dst = expect + (long long) it.model * (9 + 4096 + 1);
+#endif
 
     double acc[8]; /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
 #pragma unroll
@@ -1717,6 +1756,7 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
                 acc[0] += p0;
                 acc[1] += p1;
                 acc[2] += p2;
+#ifndef SY_HDP
                 if (x != gapX) {
                     if (gapX > 0) {
                         const int k = kx[gapX - 1];
@@ -1728,13 +1768,37 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
                 gapSum += p0;
                 gapSum += p1;
                 gapSum += p2;
+#endif
             }
             if (vMiddle) {
                 const double m0 = *g.rpb(t - 2, 0), m1 = *g.rpb(t - 2, 1), m2 = *g.rpb(t - 2, 2);
                 const double eP = *g.rp(t, 3);
+#ifdef SY_HDP
+                const double e0 = m0 + Bm + (eP + T[T_MATCH_CONTINUE]) - total;
+                const double e1 = m1 + Bm + (eP + T[T_MATCH_FROM_GAP_X]) - total;
+                const double e2 = m2 + Bm + (eP + T[T_MATCH_FROM_GAP_Y]) - total;
+                const double q0 = exp(e0), q1 = exp(e1), q2 = exp(e2);
+                acc[3] += q0;
+                acc[4] += q1;
+                acc[5] += q2;
+                const double ee[3] = { e0, e1, e2 }, qq[3] = { q0, q1, q2 };
+#pragma unroll
+                for (int f = 0; f < 3; f++)
+                    if (qq[f] >= P.threshold) {
+                        const long long at = (long long) atomicAdd((unsigned long long *) &stateW->nPairs, 1ull);
+                        if (at < it.pairCap) {
+                            long long *o = pairs + (it.pairBase + at) * 3;
+                            o[0] = f + 4ll * window;
+                            o[1] = x - 1;
+                            o[2] = (t - x) - 1;
+                            pairLogp[it.pairBase + at] = ee[f];
+                        }
+                    }
+#else
                 acc[3] += exp(m0 + Bm + (eP + T[T_MATCH_CONTINUE]) - total);
                 acc[4] += exp(m1 + Bm + (eP + T[T_MATCH_FROM_GAP_X]) - total);
                 acc[5] += exp(m2 + Bm + (eP + T[T_MATCH_FROM_GAP_Y]) - total);
+#endif
             }
             if (vUpper) {
                 const double u0 = *g.rp(t - 1, 0), u2 = *g.rp(t - 1, 2);
@@ -1746,10 +1810,14 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
         b0min = b1min; b0max = b1max;
         b1min = b2min; b1max = b2max;
     }
+#ifndef SY_HDP
     if (gapX > 0) {
         const int k = kx[gapX - 1];
         if (k < 4096) atomicAdd(dst + 9 + k, gapSum);
     }
+#else
+    (void) gapX; (void) gapSum; (void) kx;
+#endif
     /* block reduction of the per-thread sums, then one atomic per value */
     if (threadIdx.x < 16) sExp[threadIdx.x] = 0.0;
     __syncthreads();
@@ -1762,7 +1830,11 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
     }
     __syncthreads();
     if (threadIdx.x < 9) atomicAdd(dst + threadIdx.x, sExp[threadIdx.x]);
+#ifdef SY_HDP
+    if (threadIdx.x == 0) atomicAdd(dst + 9, lik);
+#else
     if (threadIdx.x == 0) atomicAdd(dst + 9 + 4096, lik);
+#endif
 }
 #endif /* !SY_NO_ESTEP */
 
@@ -1864,7 +1936,7 @@ static int sy_launch_counts(hipStream_t stream, const SweepArgs &a) {
     return cpecan_systolic_machine.launch_counts(stream, a);
 }
 #endif
-#if SY_R == 8 && defined(SY_HDP)
+#if SY_R == 8 && defined(SY_HDP) && !defined(SY_ESTEP)
 /* the HDP machine on this family (defined once, in the eight-wave object).  Its track in the strawMan row format:
  * entry 0 of column x (0..lX) = the offset (in doubles) of the table row of the k-mer that matrix column x scores --
  * sequence_getKmer3 (:327-331): column 0 (index -1) reads the first k-mer, like column 1 -- or -1 where the column is
@@ -1936,7 +2008,11 @@ static int sy_launch_backward(hipStream_t stream, const SweepArgs &a, int window
 static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) {
     hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_expect), dim3((unsigned) a.nItems, SY_EXPECT_CHUNKS), dim3(SY_P), 0, stream,
                        a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.kidx, a.models, a.Fring, a.ringDoubles,
-                       a.Bring, a.ringD, (SyState *) a.states, a.scratch, a.scratchBytes, a.expect, window);
+                       a.Bring, a.ringD, (SyState *) a.states, a.scratch, a.scratchBytes, a.expect, window
+#ifdef SY_HDP
+                       , a.pairs, a.pairLogp
+#endif
+                       );
     return sy_status();
 }
 #endif
@@ -1945,7 +2021,7 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 #ifndef __HIP_DEVICE_COMPILE__
 #if SY_R == 4 && defined(SY_VANILLA)
 const SweepMachine cpecan_systolic_machine_vanilla = { (int) sizeof(SyState), SY_ROW, sy_launch_track, sy_launch_counts };
-#elif SY_R == 8 && defined(SY_HDP)
+#elif SY_R == 8 && defined(SY_HDP) && !defined(SY_ESTEP)
 const SweepMachine cpecan_systolic_machine_hdp = { (int) sizeof(SyState), CP_ROW, sy_launch_track_hdp, sy_launch_counts_hdp };
 #elif SY_R == 4 && !defined(SY_HDP)
 const SweepMachine cpecan_systolic_machine = { (int) sizeof(SyState), CP_ROW, sy_launch_track, sy_launch_counts };
@@ -1956,8 +2032,13 @@ extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
 const SweepBuild SY_SYM(cpecan_systolic_build) = {
     SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
     sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };
+#elif defined(SY_HDP) && defined(SY_ESTEP)
+/* (E-step only: the dispatch sends these builds no posterior batch) */
+const SweepBuild SY_SYM(cpecan_systolic_build) = {
+    SY_R, false, SWEEP_HDP, &cpecan_systolic_machine_hdp, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, SY_R * 3 * 64,
+    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, sy_launch_expect, nullptr };
 #elif defined(SY_HDP)
-/* (no E-step on these builds either) */
+/* (no E-step on these builds: theirs are the _he objects) */
 const SweepBuild SY_SYM(cpecan_systolic_build) = {
     SY_R, false, SWEEP_HDP, &cpecan_systolic_machine_hdp, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
     sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };

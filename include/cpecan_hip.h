@@ -226,7 +226,7 @@ typedef struct {
 
 #define CPECAN_KERNEL_AUTO 0
 #define CPECAN_KERNEL_GENERAL 1  /* any band width; diagonals live in HBM            */
-#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide (<= 504 with CPECAN_FLAG_WIDE_BANDS[_HDP]); register-resident wavefront */
+#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide (<= 504 with CPECAN_FLAG_WIDE_BANDS[_HDP[_ESTEP]]); register-resident wavefront */
 
 #define CPECAN_FLAG_DEBUG_DUMP 1 /* keep forward/backward cells for cpecan_hip_batch_debug_cells */
 #define CPECAN_FLAG_UNBANDED 2   /* getAlignedPairsWithoutBanding (:1512): full matrix, one traceback from
@@ -283,10 +283,30 @@ typedef struct {
                                           A batch of narrower bands runs on the wave builds as without the flag, one of
                                           wider bands on the general kernel as before.  An HDP batch of
                                           CPECAN_FLAG_EXPECTATIONS ignores the flag (its E-step past 248 k-mers runs on
-                                          the general kernel), and so do all other machines; CPECAN_FLAG_WIDE_BANDS in
-                                          turn means nothing to an HDP batch.  Same results bit for bit.  The environment
+                                          the general kernel, or with CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP on the E-step
+                                          builds of the same kernels), and so do all other machines; CPECAN_FLAG_WIDE_BANDS
+                                          in turn means nothing to an HDP batch.  Same results bit for bit.  The environment
                                           variable CPECAN_WIDE_BANDS_HDP=1 (read per batch) sets it for every HDP posterior
                                           batch: the way in for callers of libcpecan_host.so and vanillaAlign. */
+#define CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP 512 /* cpecan_hip_batch_create_hdp with CPECAN_FLAG_EXPECTATIONS only: a batch
+                                          whose widest band is 249..504 k-mers, past the HDP machine's wave builds, runs
+                                          its E-step on the E-step builds of the workgroup-per-alignment kernels with six
+                                          or eight waves per workgroup (up to 376, up to 504: the forward sweep keeping
+                                          every state, the sweep back leaving its cells in a ring, one expectation
+                                          kernel per window) instead of the general kernel, unless it carries
+                                          CPECAN_FLAG_GENERAL_KERNEL or has band edges that step by more than one k-mer
+                                          (an un-banded E-step is refused as without the flag).  A batch of narrower
+                                          bands runs on the wave builds as without the flag, one of wider bands on the
+                                          general kernel as before.  An HDP posterior batch ignores the flag, and so do
+                                          all other machines; CPECAN_FLAG_WIDE_BANDS and CPECAN_FLAG_WIDE_BANDS_HDP in turn
+                                          mean nothing to an HDP E-step.  The event-to-k-mer assignments are the general
+                                          kernel's bit for bit, in the reference's order; the ten sums are atomic
+                                          additions of the same terms and agree to rounding (as between any two runs).
+                                          The environment variable CPECAN_WIDE_BANDS_HDP_ESTEP=1 (read per batch) sets it
+                                          for every HDP batch of expectations: the way in for callers of
+                                          libcpecan_host.so (cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels)
+                                          and vanillaAlign.  One flag for the wide builds of every machine and mode is a
+                                          follow-up: tests pin what the two older flags do not mean. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -347,8 +367,11 @@ int cpecan_hip_batch_create_echelon(cpecan_ctx *ctx, const cpecan_item *items, i
 
 /* k-mers against events with an HDP model (getAlignedPairsUsingAnchors with a StateMachine3_HDP,
  * sequence_getKmer3 / sequence_getEvent): same buffers as cpecan_hip_batch_create (x characters over the
- * model's alphabet), model_id is a cpecan_hip_modelsh_create id.  General kernel; flags: UNBANDED or
- * EXPECTATIONS. */
+ * model's alphabet), model_id is a cpecan_hip_modelsh_create id.  flags: UNBANDED (general kernel, posterior decode
+ * only), EXPECTATIONS, GENERAL_KERNEL, WIDE_BANDS_HDP, WIDE_BANDS_HDP_ESTEP.  There is no kernel argument: the batch picks
+ * its kernels itself (the HDP wave builds up to 248 k-mers of band, the general kernel past that), and the two
+ * wide-bands flags alone select the workgroup builds for bands of 249..504 k-mers: CPECAN_FLAG_WIDE_BANDS_HDP for the
+ * posterior decode, CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for the E-step.  cpecan_hip_batch_info reports the kernel. */
 int cpecan_hip_batch_create_hdp(cpecan_ctx *ctx, const cpecan_item *items, int64_t n_items,
                                 const char *x_chars, int64_t n_x, const double *events, int64_t n_events,
                                 const int64_t *anchors, int64_t n_anchor_pairs,
