@@ -34,6 +34,12 @@
 #define CP_RYNSD 14
 #define CP_YK2 15
 #define CP_GAPX 16
+/* doubles per matrix column of the wave family's track (cpecan_kernel_prep.hip) -- strawMan and HDP: 16 emission
+ * constants, gap-X sums (open, extend, switch), gap-X; vanilla: two tables of eight, the skip bin's five log transition
+ * probabilities, the bin */
+#define CP_WV_ROW 20
+#define CP_WV_ROW_VANILLA 22
+#define CP_HDP_GAPX (-2.3025850929940455) /* the HDP machine's flat gap-X emission, log(0.1) (stateMachine.c:1347) */
 #define CP_MODEL5_STRIDE 48 /* 5-state symbol model: 17 transitions, pad to 24, 16 match, 4 gapX, 4 gapY */
 #define CP_EXPECTV_LEN 61   /* vanilla machine's Baum-Welch sums: 30 beta + 30 alpha skip bins, likelihood */
 #define CP_EXPECT5_LEN 106  /* its Baum-Welch sums: 25 transitions, 5 x 16 emissions, likelihood */

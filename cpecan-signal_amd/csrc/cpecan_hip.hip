@@ -47,13 +47,6 @@ extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
 W5_DECLARE(1)
 W5_DECLARE(2)
 W5_DECLARE(3)
-extern "C" __global__ void cpecan_k_hdp_kmer_id(const char *, long long, unsigned long long,
-                                                unsigned long long, int, int *);
-extern "C" __global__ void cpecan_k_kmer_index(const char *, long long, unsigned short *);
-
-extern "C" int cpecan_systolic_divtest(hipStream_t stream, long long n, unsigned long long seed,
-                                       unsigned long long *bad);
-extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *states, long long nItems, double *mhz);
 
 /* The builds of the throughput kernels (SweepBuild, cpecan_sweep.h), each defined next to its kernels: the workgroup
  * family with 1..4 waves per workgroup (bands up to 56, 120, 184, 248 k-mers; the narrower the band, the more

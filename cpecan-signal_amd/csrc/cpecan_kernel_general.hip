@@ -217,22 +217,3 @@ extern "C" __global__ __launch_bounds__(256) void cpecan_k_general(DevGeneralArg
     StrawMan m(a, it, sExp);
     general_pass(m, a, P, it);
 }
-
-/* k-mer index of every position of the concatenated nucleotide buffer
- * (emissions_discrete_getKmerIndex impl/stateMachine.c:104-139): A,C,G,T = 0..3, most significant
- * first; any other character makes the 6-mer "not a k-mer" (index 4096 here, > 4096 there). */
-extern "C" __global__ void cpecan_k_kmer_index(const char *chars, long long n, unsigned short *kidx) {
-    long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int v = 0;
-    bool ok = i + 5 < n;
-    if (ok) {
-        for (int j = 0; j < 6; j++) {
-            char ch = chars[i + j];
-            int b = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1;
-            if (b < 0) ok = false;
-            v = v * 4 + (b & 3);
-        }
-    }
-    kidx[i] = ok ? (unsigned short) v : (unsigned short) 4096;
-}

@@ -232,27 +232,3 @@ extern "C" __global__ __launch_bounds__(256) void cpecan_k_generalh(DevGeneralAr
     Hdp m(a, it, sExp);
     general_pass(m, a, P, it);
 }
-
-/* k-mer id over the model's alphabet for every position of the concatenated nucleotide buffer
- * (kmer_id impl/nanopore_hdp.c:348-380: most significant character first); -1 where one of the six
- * characters is outside the alphabet (the reference exits there) or the buffer ends */
-extern "C" __global__ void cpecan_k_hdp_kmer_id(const char *chars, long long n, unsigned long long alphabet,
-                                                unsigned long long alphabetHi, int alphabetSize, int *kid) {
-    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int v = 0;
-    bool ok = i + 5 < n;
-    if (ok) {
-        for (int j = 0; j < 6; j++) {
-            const char ch = chars[i + j];
-            int d = -1;
-            for (int a = 0; a < alphabetSize; a++) {
-                const char ac = (char) ((a < 8 ? alphabet >> (8 * a) : alphabetHi >> (8 * (a - 8))) & 0xff);
-                if (ac == ch) d = a;
-            }
-            if (d < 0) ok = false;
-            v = v * alphabetSize + (d < 0 ? 0 : d);
-        }
-    }
-    kid[i] = ok ? v : -1;
-}

@@ -32,6 +32,7 @@
  * ablations compute wrong results by construction and are never built into the product.
  */
 #include "cpecan_device.h"
+#include "cpecan_lanes.h"
 #include "cpecan_sweep.h"
 
 #ifndef SY_R
@@ -40,13 +41,15 @@
 #define SY_P (64 * SY_R)
 /* this file is compiled once per SY_R (1..4 waves per workgroup: bands up to 56, 120, 184, 248 k-mers; 6 and 8 waves,
  * the wide builds of CPECAN_FLAG_WIDE_BANDS: 376 and 504); the symbols of the builds other than four carry _r1.._r3,
- * _r6, _r8, and the pieces that do not depend on SY_R (track, counts, division self-test) exist in the four-wave build
- * only.  With -DSY_VANILLA it is compiled three times more (4, 6 and 8 waves: _v4, _v6, _v8; see below), with -DSY_HDP
- * twice (_h6, _h8) and with -DSY_HDP -DSY_ESTEP twice again (_he6, _he8) */
+ * _r6, _r8.  With -DSY_VANILLA it is compiled three times more (4, 6 and 8 waves: _v4, _v6, _v8; see below), with
+ * -DSY_HDP twice (_h6, _h8) and with -DSY_HDP -DSY_ESTEP twice again (_he6, _he8).  Every build holds the sweeps -- a
+ * forward, a backward and, where the machine has its E-step here, an expectation kernel -- their launchers and one
+ * SweepBuild record; what does not depend on the build (track, counts, the machines' records) is
+ * cpecan_kernel_prep.hip's */
 /* -DSY_VANILLA: the same two sweeps for the 3-state vanilla signal machine (stateMachine3Vanilla_cellCalculate,
  * impl/stateMachine.c:1368-1409), posterior decode only, with four, six and eight waves per workgroup (bands of up to
  * 248, 376 and 504 k-mers; symbols suffixed _v4, _v6, _v8).  A lane holds the 21 doubles of its k-mer's row of the
- * wave family's vanilla track (cpecan_k_wv_track_vanilla): two tables of Gaussian level and inverse-Gaussian noise
+ * vanilla track (cpecan_k_wv_track_vanilla): two tables of Gaussian level and inverse-Gaussian noise
  * constants and the five log transition probabilities of the column's skip bin, so transitions are per lane, not
  * per wave; a_ym, a_yy and the end vector come from the model header.  The E-step of this machine stays on the general
  * kernel: these builds have no ring of backward cells and no expectation kernel. */
@@ -63,45 +66,31 @@
  * _he8; the _h6 / _h8 objects keep their device code).  E-step only: SY_MODE(P) is the constant 1, so the forward sweep
  * keeps every state of every diagonal, the sweep back parks its cells in the B ring, and the candidate lists and both
  * decodes fold away; cpecan_k_sy_expect is compiled in its HDP form (nine transitions and the likelihood, no k-mer bins,
- * event-to-k-mer assignments).  The track kernel and the machine record stay the _h8 object's. */
+ * event-to-k-mer assignments). */
 #if defined(SY_HDP) && defined(SY_VANILLA)
 #error "SY_HDP and SY_VANILLA are builds of their own"
 #elif defined(SY_ESTEP) && !defined(SY_HDP)
 #error "SY_ESTEP: the E-step builds of the HDP machine (-DSY_HDP)"
-#elif defined(SY_ESTEP) && SY_R == 6
-#define SY_SYM(n) n##_he6
-#elif defined(SY_ESTEP) && SY_R == 8
-#define SY_SYM(n) n##_he8
-#elif defined(SY_ESTEP)
+#elif defined(SY_ESTEP) && SY_R != 6 && SY_R != 8
 #error "SY_HDP SY_ESTEP: 6 or 8 waves per workgroup"
-#elif defined(SY_HDP) && SY_R == 6
-#define SY_SYM(n) n##_h6
-#elif defined(SY_HDP) && SY_R == 8
-#define SY_SYM(n) n##_h8
-#elif defined(SY_HDP)
+#elif defined(SY_HDP) && SY_R != 6 && SY_R != 8
 #error "SY_HDP: 6 or 8 waves per workgroup"
-#elif defined(SY_VANILLA) && SY_R == 4
-#define SY_SYM(n) n##_v4
-#elif defined(SY_VANILLA) && SY_R == 6
-#define SY_SYM(n) n##_v6
-#elif defined(SY_VANILLA) && SY_R == 8
-#define SY_SYM(n) n##_v8
-#elif defined(SY_VANILLA)
+#elif defined(SY_VANILLA) && SY_R != 4 && SY_R != 6 && SY_R != 8
 #error "SY_VANILLA: 4, 6 or 8 waves per workgroup"
-#elif SY_R == 4
-#define SY_SYM(n) n
-#elif SY_R == 8
-#define SY_SYM(n) n##_r8
-#elif SY_R == 6
-#define SY_SYM(n) n##_r6
-#elif SY_R == 3
-#define SY_SYM(n) n##_r3
-#elif SY_R == 2
-#define SY_SYM(n) n##_r2
-#elif SY_R == 1
-#define SY_SYM(n) n##_r1
-#else
+#elif SY_R != 1 && SY_R != 2 && SY_R != 3 && SY_R != 4 && SY_R != 6 && SY_R != 8
 #error "SY_R: 1, 2, 3, 4, 6 or 8 waves per workgroup"
+#endif
+/* a symbol's suffix: the machine's tag and the number of waves; the strawMan's four-wave build alone has none */
+#if defined(SY_ESTEP)
+#define SY_SYM(n) SWEEP_SYM(n, he, SY_R)
+#elif defined(SY_HDP)
+#define SY_SYM(n) SWEEP_SYM(n, h, SY_R)
+#elif defined(SY_VANILLA)
+#define SY_SYM(n) SWEEP_SYM(n, v, SY_R)
+#elif SY_R != 4
+#define SY_SYM(n) SWEEP_SYM(n, r, SY_R)
+#else
+#define SY_SYM(n) n
 #endif
 #if defined(SY_VANILLA) /* the vanilla row does not fit 128 VGPRs: whatever occupancy the allocation lands on */
 #define SY_BACKWARD_ATTR
@@ -125,7 +114,7 @@
 #define SY_SLOT(x) ((x) % SY_P)
 #endif
 #ifdef SY_VANILLA
-#define SY_ROW 22    /* doubles per column of the vanilla track (WV_ROW of cpecan_kernel_wave.hip) */
+#define SY_ROW CP_WV_ROW_VANILLA /* doubles per column of the vanilla track */
 #define SY_NPRM 21   /* ... of which a slot keeps all but the last (the bin itself, E-step only) */
 #define SY_TR 16     /* first of the row's five log transition probabilities: a_mx, a_xx, a_mm, a_xm, a_my */
 #define SY_EVW 4     /* doubles per staged event: mean, noise, 1 / noise, log(noise) */
@@ -141,7 +130,7 @@
 #else
 #define SY_MODE(P) 0 /* posterior decode only */
 #endif
-#define SY_HDP_GAPX (-2.3025850929940455) /* log(0.1), stateMachine.c:1347 */
+#define SY_HDP_GAPX CP_HDP_GAPX
 #else
 #define SY_ROW CP_ROW
 #define SY_NPRM 17
@@ -227,17 +216,6 @@ struct Feed {
     double row[SY_FEED_ROW * SY_FEEDW];
 };
 
-__device__ __forceinline__ double bcast(double v, int srcLane) { /* srcLane wave-uniform */
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srcLane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srcLane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ long long uni64(long long v) {
-    const unsigned lo = (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) v);
-    const int hi = __builtin_amdgcn_readfirstlane((int) (v >> 32));
-    return ((long long) hi << 32) | lo;
-}
 /* the work item as wave-uniform (scalar) values: everything derived from it -- band geometry, loop
  * bounds, base addresses -- then stays on the scalar unit instead of occupying vector lanes */
 __device__ __forceinline__ DevItem uniform_item(const DevItem &s) {
@@ -296,26 +274,12 @@ __device__ __forceinline__ double ladd(double x, double y, const double *coef) {
     return d < 7.5 ? r : hi;
 }
 __device__ __forceinline__ void init_coef(double *coef) {
-    const float t[16] = { -0.009350833524763f, 0.130659527668286f, 0.498799810682272f, 0.693203116424741f,
-                          -0.014532321752540f, 0.139942324101744f, 0.495635523139337f, 0.692140569840976f,
-                          -0.004605031767994f, 0.063427417320019f, 0.695956496475118f, 0.514272634594009f,
-                          -0.000458661602210f, 0.009695946122598f, 0.930734667215156f, 0.168037164329057f };
+    const float t[16] = CP_LOOKUP_CUBICS;
     /* entry n = ceil(2d) carries the cubic [c3,c2,c1,c0] of the piece d falls in */
     if (threadIdx.x < 64) {
         const int n = threadIdx.x >> 2, piece = n <= 2 ? 0 : n <= 5 ? 1 : n <= 9 ? 2 : 3;
         coef[threadIdx.x] = (double) t[piece * 4 + (threadIdx.x & 3)];
     }
-}
-
-/* log N(x; mu, sd) = K + (-0.5*a*a), a = (x-mu)/sd (impl/stateMachine.c:333-343); the quotient is
- * q + fma(-q, sd, t) * rsd with q = t*rsd, rsd = RN(1/sd): Markstein's correction step, which
- * rounds to the same double as the division.  sd == 0 rows carry rsd = 0, K = -inf => -inf. */
-__device__ __forceinline__ double lgauss(double x, double mu, double sd, double rsd, double K) {
-    const double t = x - mu;
-    const double q = t * rsd;
-    const double rem = __fma_rn(-q, sd, t);
-    const double a = __fma_rn(rem, rsd, q);
-    return K + (-0.5 * a * a);
 }
 
 #ifdef SY_HDP
@@ -433,16 +397,6 @@ __device__ __forceinline__ double wave_fold(double acc, double v, const double *
     return acc;
 }
 
-struct ItemOut {
-    long long *pairs;
-    double *logp;
-    long long pairCap;
-    long long *totXay;
-    double *totVal;
-    long long totCap;
-    long long nPairs, nTot;
-};
-
 __device__ __forceinline__ void load_params(double (&dst)[SY_NPRM], const double *__restrict__ track, int x) {
     const double *p = track + (long long) x * SY_ROW;
 #pragma unroll
@@ -464,12 +418,6 @@ __device__ __forceinline__ double shl1(double old, double src) {
     int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), 0x130, 0xf, 0xf, false);
     int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), 0x130, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
-}
-
-/* a load that cannot be served from a line this CU cached before another wave (or an earlier phase
- * of the same workgroup) rewrote it */
-template <typename V> __device__ __forceinline__ V ld_agent(V *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 struct Geometry {
@@ -1838,75 +1786,6 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
 }
 #endif /* !SY_NO_ESTEP */
 
-#if SY_R == 4 && !defined(SY_VANILLA)
-/* results of the per-alignment states into the batch's count arrays */
-extern "C" __global__ void cpecan_k_sy_counts(const SyState *states, long long nItems,
-                                              long long *nPairs, long long *nTot, long long *nCells) {
-    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nItems) return;
-    nPairs[i] = states[i].nPairs;
-    nTot[i] = states[i].nTot;
-    nCells[i] = states[i].cells;
-}
-
-/* per-item track of emission constants: row x (0..lX) = model row of the k-mer that matrix column x
- * scores (column 0 = the "not a k-mer" sentinel, sequence_getKmer index -1, :314-318) */
-extern "C" __global__ void cpecan_k_track(const DevItem *__restrict__ items, long long nItems,
-                                          const long long *__restrict__ trackBase,
-                                          const unsigned short *__restrict__ kidx,
-                                          const double *__restrict__ models, double *track) {
-    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
-        const DevItem it = items[item];
-        const double *rows = models + (long long) it.model * CP_MODEL_STRIDE + CP_MODEL_HEADER;
-        const long long n = (it.lX + 1) * CP_ROW;
-        double *dst = track + trackBase[item] * CP_ROW;
-        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-             i += (long long) gridDim.x * blockDim.x) {
-            const long long x = i / CP_ROW;
-            const int j = (int) (i - x * CP_ROW);
-            const int k = x == 0 ? 4096 : (int) kidx[it.xOff + x - 1];
-            dst[i] = rows[(long long) k * CP_ROW + j];
-        }
-    }
-}
-
-/* division self-test (see cpecan_hip_selftest_division) */
-extern "C" __global__ void cpecan_k_divtest(long long n, unsigned long long seed, unsigned long long *bad) {
-    long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long local = 0;
-    for (; i < n; i += (long long) gridDim.x * blockDim.x) {
-        unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long) (i + 1);
-        double u[3];
-        for (int k = 0; k < 3; k++) { /* splitmix64 */
-            z += 0x9E3779B97F4A7C15ull;
-            unsigned long long r = z;
-            r = (r ^ (r >> 30)) * 0xBF58476D1CE4E5B9ull;
-            r = (r ^ (r >> 27)) * 0x94D049BB133111EBull;
-            r ^= r >> 31;
-            u[k] = (double) (r >> 11) * (1.0 / 9007199254740992.0);
-        }
-        const bool noise = (i & 1) != 0;
-        const double x = noise ? 0.001 + 4.0 * u[0] : 30.0 + 70.0 * u[0];
-        const double mu = noise ? 0.3 + 2.0 * u[1] : 40.0 + 45.0 * u[1];
-        const double sd = noise ? 0.05 + 1.5 * u[2] : 0.3 + 4.0 * u[2];
-        const double rsd = 1.0 / sd;
-        const double t = x - mu;
-        const double q = t * rsd;
-        const double rem = __fma_rn(-q, sd, t);
-        const double a = __fma_rn(rem, rsd, q);
-        const double ref = t / sd;
-        if (!(a == ref)) local++;
-    }
-    if (local) atomicAdd(bad, local);
-}
-
-extern "C" int cpecan_systolic_divtest(hipStream_t stream, long long n, unsigned long long seed,
-                                       unsigned long long *bad) {
-    hipLaunchKernelGGL(cpecan_k_divtest, dim3(1024), dim3(256), 0, stream, n, seed, bad);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-#endif /* SY_R == 4 */
-
 #ifdef SY_PROFILE
 extern "C" int SY_SYM(cpecan_systolic_prof_fetch)(unsigned long long *dst) {
     unsigned long long zero[SY_PROF_N] = {0};
@@ -1921,76 +1800,9 @@ static long long sy_scratch_bytes(int ringD) {
            + (long long) SY_R * SY_CAND_PER_DIAG * ringD * (sizeof(int2) + sizeof(double));
 }
 
-/* Launchers of the four stages of one pass over a batch (the C-ABI layer sequences them:
- * track, then per window {forward, backward}, then counts). */
+/* Launchers of the per-window stages of one pass over a batch (the C-ABI layer sequences them: the machine's track
+ * (cpecan_kernel_prep.hip), then per window {forward, backward}, then its counts). */
 static int sy_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
-#if SY_R == 4 && defined(SY_VANILLA)
-/* the vanilla machine on this family: the wave family's vanilla track (its kernel lives in that family's widest vanilla
- * object), this family's state records and counts kernel */
-static int sy_launch_track(hipStream_t stream, const SweepArgs &a) {
-    if (cpecan_wave_launch_track_vanilla(stream, a) != 0) return -1;
-    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(SyState), stream) != hipSuccess) return -1;
-    return sy_status();
-}
-static int sy_launch_counts(hipStream_t stream, const SweepArgs &a) {
-    return cpecan_systolic_machine.launch_counts(stream, a);
-}
-#endif
-#if SY_R == 8 && defined(SY_HDP) && !defined(SY_ESTEP)
-/* the HDP machine on this family (defined once, in the eight-wave object).  Its track in the strawMan row format:
- * entry 0 of column x (0..lX) = the offset (in doubles) of the table row of the k-mer that matrix column x scores --
- * sequence_getKmer3 (:327-331): column 0 (index -1) reads the first k-mer, like column 1 -- or -1 where the column is
- * no k-mer; entry CP_GAPX = the flat gap-X emission log(0.1) (stateMachine.c:1347), which the sweep back adds to the
- * transitions as it does a strawMan k-mer's; the rest unused */
-extern "C" __global__ void cpecan_k_sy_track_hdp(const DevItem *__restrict__ items, long long nItems,
-                                                 const long long *__restrict__ trackBase,
-                                                 const int *__restrict__ kid, const DevHdpModel *__restrict__ models,
-                                                 double *track) {
-    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
-        const DevItem it = items[item];
-        const DevHdpModel &m = models[it.model];
-        const long long n = (it.lX + 1) * CP_ROW;
-        double *dst = track + trackBase[item] * CP_ROW;
-        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-             i += (long long) gridDim.x * blockDim.x) {
-            const long long x = i / CP_ROW;
-            const int j = (int) (i - x * CP_ROW);
-            double v = 0.0;
-            if (j == 0) {
-                const int id = kid[it.xOff + (x > 0 ? x - 1 : 0)];
-                v = id < 0 ? -1.0 : (double) ((long long) m.kmerRow[id] * m.gridLength);
-            } else if (j == CP_GAPX) v = SY_HDP_GAPX;
-            dst[i] = v;
-        }
-    }
-}
-static int sy_launch_track_hdp(hipStream_t stream, const SweepArgs &a) {
-    int bx = (int) ((((long long) a.maxLX + 1) * CP_ROW + 255) / 256);
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_sy_track_hdp, dim3(bx, (unsigned) std::min(a.nItems, 65535LL)), dim3(256), 0, stream,
-                       a.items, a.nItems, a.trackBase, a.kid, (const DevHdpModel *) a.models, a.track);
-    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(SyState), stream) != hipSuccess) return -1;
-    return sy_status();
-}
-static int sy_launch_counts_hdp(hipStream_t stream, const SweepArgs &a) {
-    return cpecan_systolic_machine.launch_counts(stream, a);
-}
-#endif
-#if SY_R == 4 && !defined(SY_VANILLA)
-static int sy_launch_track(hipStream_t stream, const SweepArgs &a) {
-    int bx = (int) ((((long long) a.maxLX + 1) * CP_ROW + 255) / 256);
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(cpecan_k_track, dim3(bx, (unsigned) std::min(a.nItems, 65535LL)), dim3(256), 0, stream, a.items,
-                       a.nItems, a.trackBase, a.kidx, a.models, a.track);
-    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(SyState), stream) != hipSuccess) return -1;
-    return sy_status();
-}
-static int sy_launch_counts(hipStream_t stream, const SweepArgs &a) {
-    hipLaunchKernelGGL(cpecan_k_sy_counts, dim3((unsigned) ((a.nItems + 255) / 256)), dim3(256), 0, stream,
-                       (const SyState *) a.states, a.nItems, a.nPairs, a.nTot, a.nCells);
-    return sy_status();
-}
-#endif
 static int sy_launch_forward(hipStream_t stream, const SweepArgs &a, int) {
     hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_forward), dim3((unsigned) a.nItems), dim3(SY_P), 0, stream, a.items, a.nItems,
                        a.P, a.bandTab, a.track, a.trackBase, a.events, a.models, a.Fring, a.ringDoubles, a.ringD,
@@ -2017,15 +1829,8 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 }
 #endif
 
-/* the records (host only: the device pass would emit them as constants, with pointers to host functions) */
+/* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
-#if SY_R == 4 && defined(SY_VANILLA)
-const SweepMachine cpecan_systolic_machine_vanilla = { (int) sizeof(SyState), SY_ROW, sy_launch_track, sy_launch_counts };
-#elif SY_R == 8 && defined(SY_HDP) && !defined(SY_ESTEP)
-const SweepMachine cpecan_systolic_machine_hdp = { (int) sizeof(SyState), CP_ROW, sy_launch_track_hdp, sy_launch_counts_hdp };
-#elif SY_R == 4 && !defined(SY_HDP)
-const SweepMachine cpecan_systolic_machine = { (int) sizeof(SyState), CP_ROW, sy_launch_track, sy_launch_counts };
-#endif
 extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
 #ifdef SY_VANILLA
 /* (no E-step on these builds: no expect launcher, no ring of backward cells; the dispatch keeps such batches away) */

@@ -32,9 +32,8 @@
  * stateMachine3_cellCalculate impl/stateMachine.c:1305-1334, logAdd impl/pairwiseAligner.c:238-255.
  */
 #include "cpecan_device.h"
+#include "cpecan_lanes.h"
 #include "cpecan_sweep.h"
-
-#include <vector>
 
 #ifndef WV_L
 #define WV_L 3 /* cells per lane: 1..4 (bands up to 56, 120, 184, 248 k-mers) */
@@ -46,33 +45,14 @@
 /* -DWV_VANILLA: the 3-state vanilla signal machine (stateMachine3Vanilla_cellCalculate, impl/stateMachine.c:1368-1409):
  * transition probabilities per reference position (30 skip bins of the k-mer pair sequence_getKmer2 exposes), a
  * Gaussian level term plus an inverse-Gaussian noise term per emission; symbols suffixed _v2, _v3 (four cells per lane spill: not built) */
-#if defined(WV_VANILLA) && WV_L == 4
-#define WV_SYM(n) n##_v4
-#elif defined(WV_VANILLA) && WV_L == 3
-#define WV_SYM(n) n##_v3
-#elif defined(WV_VANILLA)
-#define WV_SYM(n) n##_v2
-#elif defined(WV_HDP) && WV_L == 4
-#define WV_SYM(n) n##_h4
-#elif defined(WV_HDP) && WV_L == 3
-#define WV_SYM(n) n##_h3
-#elif defined(WV_HDP)
-#define WV_SYM(n) n##_h2
-#elif WV_L == 4
-#define WV_SYM(n) n##_l4
-#elif WV_L == 3
-#define WV_SYM(n) n##_l3
-#elif WV_L == 2
-#define WV_SYM(n) n##_l2
-#else
-#define WV_SYM(n) n##_l1
-#endif
-/* what a machine needs once, not per build (track kernel, counts, its SweepMachine record), is compiled into its
- * widest linked build: four cells per lane, three for the vanilla machine (whose four-cell build spills) */
+/* Every build holds the sweeps, their launchers and one SweepBuild record; what does not depend on the build (track,
+ * counts, the machines' records) is cpecan_kernel_prep.hip's */
 #if defined(WV_VANILLA)
-#define WV_WIDEST 3
+#define WV_SYM(n) SWEEP_SYM(n, v, WV_L)
+#elif defined(WV_HDP)
+#define WV_SYM(n) SWEEP_SYM(n, h, WV_L)
 #else
-#define WV_WIDEST 4
+#define WV_SYM(n) SWEEP_SYM(n, l, WV_L)
 #endif
 #if defined(WV_VANILLA)
 #define WV_MODEL_DOUBLES ((long long) CP_VMODEL_STRIDE)
@@ -85,10 +65,10 @@
 /* doubles per column of the track: per table (match, extra event) level mu, sd, 1/sd, K and noise mean, 1/mean, lambda,
  * log(lambda) - log(2 pi); then the five log transition probabilities of the column's skip bin: into gap X from match
  * and from gap X, into match from match and from gap X, into gap Y from match */
-#define WV_ROW 22
+#define WV_ROW CP_WV_ROW_VANILLA
 #define WV_PXW 6             /* of which the sweep back keeps the last six (three pairs) per slot */
 #else
-#define WV_ROW 20            /* doubles per column of the track: 16 emission constants, gap-X sums (open, extend, switch), gap-X */
+#define WV_ROW CP_WV_ROW     /* doubles per column of the track: 16 emission constants, gap-X sums (open, extend, switch), gap-X */
 #define WV_PXW 4
 #endif
 #define WV_ROWN 32           /* LDS ring of k-mer rows (>= the feed block)                              */
@@ -149,12 +129,6 @@ typedef const d2 *lds_d2p; /* (the host pass only parses the kernels) */
 #define lds_d2p_cast(a) ((lds_d2p) (a))
 #endif
 
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ long long uni64(long long v) {
-    const unsigned lo = (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) v);
-    const int hi = __builtin_amdgcn_readfirstlane((int) (v >> 32));
-    return ((long long) hi << 32) | lo;
-}
 __device__ __forceinline__ double uni64_d(double v) {
     return __longlong_as_double(uni64(__double_as_longlong(v)));
 }
@@ -171,10 +145,6 @@ __device__ __forceinline__ DevItem uniform_item(const DevItem &s) {
     d.model = uni(s.model); d.raggedL = uni(s.raggedL); d.raggedR = uni(s.raggedR); d.maxWidth = uni(s.maxWidth);
     return d;
 }
-template <typename V> __device__ __forceinline__ V ld_agent(V *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 /* d < 7.5 ? r : hi as one compare and two lane selects the compiler cannot turn into a divergent branch
  * around the cubic (it does, given the chance, and the sweep then pays a branch per logAdd) */
 __device__ __forceinline__ double sel_below(double d, double r, double hi) {
@@ -241,23 +211,9 @@ template <int N> __device__ __forceinline__ void laddN(double (&acc)[N], const d
     ladd_finish<N>(p, acc);
 }
 __device__ __forceinline__ void init_coef(double *coef) {
-    const float t[16] = { -0.009350833524763f, 0.130659527668286f, 0.498799810682272f, 0.693203116424741f,
-                          -0.014532321752540f, 0.139942324101744f, 0.495635523139337f, 0.692140569840976f,
-                          -0.004605031767994f, 0.063427417320019f, 0.695956496475118f, 0.514272634594009f,
-                          -0.000458661602210f, 0.009695946122598f, 0.930734667215156f, 0.168037164329057f };
+    const float t[16] = CP_LOOKUP_CUBICS;
     const int l = threadIdx.x & 63, n = l >> 2, piece = n <= 2 ? 0 : n <= 5 ? 1 : n <= 9 ? 2 : 3;
     coef[l] = (double) t[piece * 4 + (l & 3)];
-}
-
-/* log N(x; mu, sd) = K + (-0.5*a*a), a = (x-mu)/sd (impl/stateMachine.c:333-343); the quotient is
- * q + fma(-q, sd, t) * rsd with q = t*rsd, rsd = RN(1/sd): Markstein's correction step, which rounds to
- * the same double as the division.  sd == 0 rows carry rsd = 0, K = -inf => -inf. */
-__device__ __forceinline__ double lgauss(double x, double mu, double sd, double rsd, double K) {
-    const double t = x - mu;
-    const double q = t * rsd;
-    const double rem = __fma_rn(-q, sd, t);
-    const double a = __fma_rn(rem, rsd, q);
-    return K + (-0.5 * a * a);
 }
 
 /* lane i <- lane i-1, lane 0 <- lane 63 (DPP wave_ror:1) */
@@ -272,12 +228,6 @@ __device__ __forceinline__ double rol1(double v) {
     const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), 0x134, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double bcast(double v, int srcLane) { /* srcLane wave-uniform */
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), srcLane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), srcLane);
-    return __hiloint2double(hi, lo);
-}
-
 /* logAdd-fold of one value per lane into acc (wave-uniform in and out), lanes in ascending order; visits only
  * the lanes that can change the running value */
 __device__ __forceinline__ double wave_fold(double acc, double v, unsigned cf) {
@@ -1002,16 +952,6 @@ __device__ __forceinline__ void store_b3(unsigned long long laneMask, const doub
                  : "s"(laneMask), "v"(voff), "v"(bm), "v"(bx), "v"(by), "s"(rowBase)
                  : "memory");
 }
-
-struct ItemOut {
-    long long *pairs;
-    double *logp;
-    long long pairCap;
-    long long *totXay;
-    double *totVal;
-    long long totCap;
-    long long nPairs, nTot;
-};
 
 /* Fused Baum-Welch expectations (KIND_EXPECT_FUSED): per refresh segment of a window (the ten decoded diagonals that
  * share one totalProbability), in the alignment's HBM scratch after what cpecan_wave_scratch_bytes counts:
@@ -2427,180 +2367,6 @@ extern "C" __global__ __launch_bounds__(WV_P) void WV_SYM(cpecan_k_wv_expect)(
 
 #endif /* strawMan and HDP builds */
 
-#if WV_L == WV_WIDEST
-/* the track kernels' grid, and the states cleared behind them */
-static dim3 wv_track_grid(const SweepArgs &a) {
-    const long long bx = (((long long) a.maxLX + 1) * WV_ROW + 255) / 256;
-    return dim3((unsigned) std::min(bx, 64LL), (unsigned) std::min(a.nItems, 65535LL));
-}
-static int wv_clear_states(hipStream_t stream, const SweepArgs &a) {
-    if (hipMemsetAsync(a.states, 0, (size_t) a.nItems * sizeof(WvState), stream) != hipSuccess) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-#endif
-
-#if WV_L == WV_WIDEST && !defined(WV_HDP) && !defined(WV_VANILLA)
-/* per-item track of emission constants, wave layout: column x (0..lX) = the 16 emission constants of the k-mer
- * that matrix column x scores (column 0 = the "not a k-mer" sentinel, sequence_getKmer index -1, :314-318),
- * its gap-X emission plus each of the three transitions into gap X (the eP + tP of cell_calculate*), and the
- * emission itself */
-extern "C" __global__ void cpecan_k_wv_track(const DevItem *__restrict__ items, long long nItems,
-                                             const long long *__restrict__ trackBase,
-                                             const unsigned short *__restrict__ kidx,
-                                             const double *__restrict__ models, double *track) {
-    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
-        const DevItem it = items[item];
-        const double *model = models + (long long) it.model * CP_MODEL_STRIDE;
-        const double *rows = model + CP_MODEL_HEADER;
-        const long long n = (it.lX + 1) * WV_ROW;
-        double *dst = track + trackBase[item] * WV_ROW;
-        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-             i += (long long) gridDim.x * blockDim.x) {
-            const long long x = i / WV_ROW;
-            const int jj = (int) (i - x * WV_ROW);
-            const int k = x == 0 ? 4096 : (int) kidx[it.xOff + x - 1];
-            const double *r = rows + (long long) k * CP_ROW;
-            double v;
-            if (jj < 16) v = r[jj];
-            else if (jj == 16) v = r[CP_GAPX] + model[T_GAP_OPEN_X];
-            else if (jj == 17) v = r[CP_GAPX] + model[T_GAP_EXTEND_X];
-            else if (jj == 18) v = r[CP_GAPX] + model[T_GAP_SWITCH_TO_X];
-            else v = r[CP_GAPX];
-            dst[i] = v;
-        }
-    }
-}
-static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
-    hipLaunchKernelGGL(cpecan_k_wv_track, wv_track_grid(a), dim3(256), 0, stream, a.items, a.nItems, a.trackBase, a.kidx,
-                       a.models, a.track);
-    return wv_clear_states(stream, a);
-}
-/* the shader clock the forward sweeps of the last run saw, in MHz (s_memtime ticks over 100 MHz s_memrealtime ticks,
- * summed over the first alignments of the batch); 0 when nothing ran */
-extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *states, long long nItems, double *mhz) {
-    const long long n = nItems < 64 ? nItems : 64;
-    std::vector<WvState> h((size_t) n);
-    if (hipMemcpyAsync(h.data(), states, (size_t) n * sizeof(WvState), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess)
-        return -1;
-    double c = 0, r = 0;
-    for (const WvState &s : h) {
-        c += (double) s.clkShader;
-        r += (double) s.clkRef;
-    }
-    *mhz = r > 0 ? 100.0 * c / r : 0.0;
-    return 0;
-}
-/* results of the per-alignment states into the batch's count arrays */
-extern "C" __global__ void cpecan_k_wv_counts(const WvState *states, long long nItems, long long *nPairs,
-                                              long long *nTot, long long *nCells) {
-    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nItems) return;
-    nPairs[i] = states[i].nPairs;
-    nTot[i] = states[i].nTot;
-    nCells[i] = states[i].cells;
-}
-int cpecan_wave_launch_counts(hipStream_t stream, const SweepArgs &a) {
-    hipLaunchKernelGGL(cpecan_k_wv_counts, dim3((unsigned) ((a.nItems + 255) / 256)), dim3(256), 0, stream,
-                       (const WvState *) a.states, a.nItems, a.nPairs, a.nTot, a.nCells);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-#endif
-
-#if WV_L == WV_WIDEST && defined(WV_VANILLA)
-/* the vanilla machine's track: matrix column x scores the k-mer pair sequence_getKmer2 (impl/pairwiseAligner.c:320-325)
- * exposes for sequence index x - 1 -- a pointer to character max(x - 2, 0): the skip bin looks at the k-mers there
- * and one further, the emissions at the one further (columns 0, 1 and 2 all score k-mers 0 and 1, as in the
- * reference).  Row: per table (match, extra event) mu, sd, 1/sd, K, noise mean, 1/mean, lambda,
- * log(lambda) - log(2 pi); then the bin's five log transition probabilities (cpecan_models.hip: derive_vanilla) */
-extern "C" __global__ void cpecan_k_wv_track_vanilla(const DevItem *__restrict__ items, long long nItems,
-                                                     const long long *__restrict__ trackBase,
-                                                     const unsigned short *__restrict__ kidx,
-                                                     const double *__restrict__ models, double *track) {
-    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
-        const DevItem it = items[item];
-        const double *hdr = models + (long long) it.model * CP_VMODEL_STRIDE;
-        const double *rows = hdr + CP_VHDR;
-        const long long n = (it.lX + 1) * WV_ROW;
-        double *dst = track + trackBase[item] * WV_ROW;
-        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-             i += (long long) gridDim.x * blockDim.x) {
-            const long long x = i / WV_ROW;
-            const int jj = (int) (i - x * WV_ROW);
-            const long long p = x > 2 ? x - 2 : 0;
-            const int kPrev = kidx[it.xOff + p], kCur = kidx[it.xOff + p + 1];
-            const double *r = rows + (long long) kCur * CP_VROW;
-            double v = 0.0;
-            if (jj < 16) {
-                const double *q = r + 6 * (jj >> 3);
-                switch (jj & 7) {
-                case 0: v = q[CP_V_MU]; break;
-                case 1: v = q[CP_V_SD]; break;
-                case 2: v = q[CP_V_SD] == 0.0 ? 0.0 : 1.0 / q[CP_V_SD]; break;
-                case 3: v = q[CP_V_K]; break;
-                case 4: v = q[CP_V_NMU]; break;
-                case 5: v = 1.0 / q[CP_V_NMU]; break;
-                case 6: v = q[CP_V_LAMBDA]; break;
-                default: v = q[CP_V_LLAMBDA] - 1.8378770664093453; break;
-                }
-            } else {
-                const double d = fabs(r[CP_V_MU] - rows[(long long) kPrev * CP_VROW + CP_V_MU]);
-                long long bin = (long long) (d / 0.5);
-                if (bin >= 30) bin = 29;
-                v = jj < 21 ? hdr[CP_VHDR_BINS + bin * 5 + (jj - 16)] : (double) bin; /* (entry 21: the bin itself, E-step) */
-            }
-            dst[i] = v;
-        }
-    }
-}
-extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const SweepArgs &a) {
-    hipLaunchKernelGGL(cpecan_k_wv_track_vanilla, wv_track_grid(a), dim3(256), 0, stream, a.items, a.nItems, a.trackBase,
-                       a.kidx, a.models, a.track);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
-    if (cpecan_wave_launch_track_vanilla(stream, a) != 0) return -1;
-    return wv_clear_states(stream, a);
-}
-#endif
-
-#if WV_L == WV_WIDEST && defined(WV_HDP)
-/* the HDP machine's track: column x (0..lX) = the offset (in doubles) of the table row of the k-mer that matrix
- * column x scores -- sequence_getKmer3 (:327-331): column 0 (index -1) reads the first k-mer, like column 1 -- and
- * the flat gap-X emission log(0.1) (stateMachine.c:1347) plus each of the three transitions into gap X */
-extern "C" __global__ void cpecan_k_wv_track_hdp(const DevItem *__restrict__ items, long long nItems,
-                                                 const long long *__restrict__ trackBase,
-                                                 const int *__restrict__ kid, const DevHdpModel *__restrict__ models,
-                                                 double *track) {
-    for (long long item = blockIdx.y; item < nItems; item += gridDim.y) { /* grid.y is capped at 65535 */
-        const DevItem it = items[item];
-        const DevHdpModel &m = models[it.model];
-        const long long n = (it.lX + 1) * WV_ROW;
-        double *dst = track + trackBase[item] * WV_ROW;
-        const double px = -2.3025850929940455;
-        for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n;
-             i += (long long) gridDim.x * blockDim.x) {
-            const long long x = i / WV_ROW;
-            const int jj = (int) (i - x * WV_ROW);
-            double v = 0.0;
-            if (jj == 0) {
-                const int id = kid[it.xOff + (x > 0 ? x - 1 : 0)];
-                v = id < 0 ? -1.0 : (double) ((long long) m.kmerRow[id] * m.gridLength);
-            } else if (jj == 16) v = px + m.t[T_GAP_OPEN_X];
-            else if (jj == 17) v = px + m.t[T_GAP_EXTEND_X];
-            else if (jj == 18) v = px + m.t[T_GAP_SWITCH_TO_X];
-            else if (jj == 19) v = px;
-            dst[i] = v;
-        }
-    }
-}
-static int wv_launch_track(hipStream_t stream, const SweepArgs &a) {
-    hipLaunchKernelGGL(cpecan_k_wv_track_hdp, wv_track_grid(a), dim3(256), 0, stream, a.items, a.nItems, a.trackBase, a.kid,
-                       (const DevHdpModel *) a.models, a.track);
-    return wv_clear_states(stream, a);
-}
-#endif
-
 /* The launchers: each kernel signature is fed from the record in one place, so which kernel runs (_sw, _em, re-sweep)
  * is a choice of function pointer */
 static dim3 wv_sweep_grid(const SweepArgs &a) { return dim3((unsigned) ((a.nItems + WV_WPB - 1) / WV_WPB)); }
@@ -2675,26 +2441,20 @@ static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int win
 #define WV_STRAWMAN_ONLY(f) nullptr
 #endif
 
-/* the records (host only: the device pass would emit them as constants, with pointers to host functions) */
+/* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
 #if defined(WV_VANILLA)
-#define WV_MACHINE SWEEP_VANILLA
-#define WV_ONCE cpecan_wave_machine_vanilla
+#define WV_MACHINE SWEEP_VANILLA, &cpecan_wave_machine_vanilla
 #elif defined(WV_HDP)
-#define WV_MACHINE SWEEP_HDP
-#define WV_ONCE cpecan_wave_machine_hdp
+#define WV_MACHINE SWEEP_HDP, &cpecan_wave_machine_hdp
 #else
-#define WV_MACHINE SWEEP_STRAWMAN
-#define WV_ONCE cpecan_wave_machine
-#endif
-#if WV_L == WV_WIDEST
-const SweepMachine WV_ONCE = { (int) sizeof(WvState), WV_ROW, wv_launch_track, cpecan_wave_launch_counts };
+#define WV_MACHINE SWEEP_STRAWMAN, &cpecan_wave_machine
 #endif
 /* scratch: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list], and after it,
  * in batches with fused expectations, the segments' sums (WvFx) */
 extern "C" const SweepBuild WV_SYM(cpecan_wave_build);
 const SweepBuild WV_SYM(cpecan_wave_build) = {
-    WV_L, true, WV_MACHINE, &WV_ONCE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
+    WV_L, true, WV_MACHINE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
     wv_scratch_base_bytes, WV_STRAWMAN_ONLY(wv_fx_bytes),
     wv_launch_forward, wv_launch_backward, WV_STRAWMAN_ONLY(wv_launch_backward_fx), wv_launch_expect,
     WV_STRAWMAN_ONLY(wv_launch_post) };

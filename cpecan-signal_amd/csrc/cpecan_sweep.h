@@ -1,6 +1,7 @@
 /*
  * cpecan_sweep.h -- records shared by the throughput kernels (cpecan_kernel_wave.hip,
- * cpecan_kernel_systolic.hip) and the C-ABI layer that sequences their launches.
+ * cpecan_kernel_systolic.hip: the sweeps, one build per object; cpecan_kernel_prep.hip: what a pass needs once) and the
+ * C-ABI layer that sequences their launches.
  */
 #ifndef CPECAN_SWEEP_H_
 #define CPECAN_SWEEP_H_
@@ -97,24 +98,36 @@ struct SweepArgs {
 
 typedef int (*SweepLaunch)(hipStream_t stream, const SweepArgs &a, int window);
 
-/* the once-per-pass pieces of a machine on a kernel family: the track before the sweeps, the counts after them */
+/* the once-per-pass pieces of a machine on a kernel family (cpecan_kernel_prep.hip): the track before the sweeps, the
+ * counts after them */
 struct SweepMachine {
     int stateBytes;      /* per alignment: SyState or WvState */
     int trackRowDoubles; /* per matrix column of the track */
     int (*launch_track)(hipStream_t stream, const SweepArgs &a); /* (and the states cleared) */
     int (*launch_counts)(hipStream_t stream, const SweepArgs &a);
 };
-extern "C" int cpecan_wave_launch_counts(hipStream_t stream, const SweepArgs &a); /* (one for the three wave machines) */
-/* the vanilla track alone, states untouched (the vanilla builds of the workgroup family keep SyState records) */
-extern "C" int cpecan_wave_launch_track_vanilla(hipStream_t stream, const SweepArgs &a);
 extern "C" const SweepMachine cpecan_systolic_machine, cpecan_systolic_machine_vanilla, cpecan_systolic_machine_hdp, cpecan_wave_machine,
     cpecan_wave_machine_hdp, cpecan_wave_machine_vanilla;
 
+/* ... and what the same file has for batch creation and the self-tests: per X position the k-mer index, or the k-mer id
+ * over an HDP's alphabet (up to 16 characters, eight to a word); the division self-test; the shader clock the forward
+ * sweeps of the last run saw */
+extern "C" __global__ void cpecan_k_kmer_index(const char *chars, long long n, unsigned short *kidx);
+extern "C" __global__ void cpecan_k_hdp_kmer_id(const char *chars, long long n, unsigned long long alphabet,
+                                                unsigned long long alphabetHi, int alphabetSize, int *kid);
+extern "C" int cpecan_systolic_divtest(hipStream_t stream, long long n, unsigned long long seed, unsigned long long *bad);
+extern "C" int cpecan_wave_shader_clock_mhz(hipStream_t stream, const void *states, long long nItems, double *mhz);
+
 enum { SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA };
 
+/* the symbols of a build carry its machine's tag and its number: SWEEP_SYM(cpecan_k_sy_forward, he, 6) is
+ * cpecan_k_sy_forward_he6 (two levels, so that a number given with -D is expanded before it is pasted) */
+#define SWEEP_SYM_(n, tag, k) n##_##tag##k
+#define SWEEP_SYM(n, tag, k) SWEEP_SYM_(n, tag, k)
+
 /* One compiled build of the throughput kernels, defined next to them (cpecan_kernel_systolic.hip: cpecan_systolic_build
- * and _r1.._r3, _r6, _r8, the vanilla machine's _v4, _v6, _v8, the HDP machine's _h6, _h8 and, for its E-step, _he6, _he8; cpecan_kernel_wave.hip: cpecan_wave_build_l2.._l4, _h2.._h4,
- * _v2, _v3) */
+ * and _r1.._r3, _r6, _r8, the vanilla machine's _v4, _v6, _v8, the HDP machine's _h6, _h8 and, for its E-step, _he6, _he8;
+ * cpecan_kernel_wave.hip: cpecan_wave_build_l2.._l4, _h2.._h4, _v2, _v3) */
 struct SweepBuild {
     int rows;    /* waves per workgroup (workgroup family) or cells per lane (wave family) */
     bool wave;   /* one wave per alignment */

@@ -1,8 +1,8 @@
 """The E-step builds of the HDP machine on the workgroup-per-alignment kernels (six and eight waves per workgroup,
 -DSY_HDP -DSY_ESTEP: CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP on an HDP batch of expectations) keep the family's budget: nothing
 in scratch, at most 128 VGPRs -- four waves per SIMD -- and a static LDS that leaves room for the workgroups that
-occupancy puts on a CU.  Each has one forward, one backward and one expectation kernel, and the HDP track kernel stays
-the posterior object's.  Register and memory metadata only.  CPU-only: hipcc cross-compiles gfx950."""
+occupancy puts on a CU.  Each has one forward, one backward and one expectation kernel and nothing else: the HDP track
+kernel is cpecan_kernel_prep.hip's.  Register and memory metadata only.  CPU-only: hipcc cross-compiles gfx950."""
 import os
 import shutil
 import subprocess
@@ -42,7 +42,7 @@ def test_hdp_estep_objects_are_built():
 def test_hdp_estep_builds_keep_their_budget(tmp_path, rows):
     text = device_asm(tmp_path, rows)
     meta = text[text.index("amdhsa.kernels:"):]
-    assert ".name:           cpecan_k_sy_track_hdp\n" not in meta  # defined once, in the posterior eight-wave object
+    assert ".name:           cpecan_k_sy_track_hdp\n" not in meta  # defined once, in cpecan_kernel_prep.hip
     assert meta.count(".name: ") == 3, "three kernels to a build"
     for stem in ("cpecan_k_sy_forward", "cpecan_k_sy_backward", "cpecan_k_sy_expect"):
         name = "%s_he%d" % (stem, rows)

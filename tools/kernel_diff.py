@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
-"""Device code of the throughput kernels in two source trees, kernel for kernel: every build the Makefile makes of
-cpecan_kernel_systolic.hip and cpecan_kernel_wave.hip is compiled to gfx950 assembly in both trees (the Makefile's flags
-plus -S --cuda-device-only) and, per kernel name, the instructions between the label and s_endpgm and the resource
-lines of the metadata block are compared.  A refactor of the host side must leave all of them as they were.
+"""Device code of the throughput kernels in two source trees, kernel for kernel: each build the Makefile makes of
+cpecan_kernel_systolic.hip (thirteen) and cpecan_kernel_wave.hip (eight), and the files around them that are compiled once
+(cpecan_kernel_prep.hip where a tree has it, cpecan_kernel_general.hip, cpecan_kernel_generalh.hip), is compiled to gfx950
+assembly in both trees (the Makefile's flags plus -S --cuda-device-only) and, per kernel name, the instructions between
+the label and the function's end and the resource lines of the metadata block are compared.  A kernel that moved to
+another file is compared with whichever parent build had it: the number of its function in the file, which the
+compiler puts into its local labels (.LBB<n>_), is taken out first.  A refactor of the host side, or one that moves
+kernels between files, must leave all of them as they were.
 usage: tools/kernel_diff.py PARENT_TREE BRANCH_TREE [WORKDIR]     (needs hipcc, no GPU; about 17 s per wave build)"""
 import os
 import re
@@ -14,15 +18,21 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
          "-Wno-unused-function"]
 BUILDS = [("systolic", ["-DSY_R=%d" % r]) for r in (1, 2, 3)] + [("systolic", [])] + \
-         [("wave", ["-DWV_L=%d" % l] + m) for m in ([], ["-DWV_HDP"]) for l in (2, 3, 4)] + \
-         [("wave", ["-DWV_L=%d" % l, "-DWV_VANILLA"]) for l in (2, 3, 4)]
+         [("systolic", ["-DSY_R=%d" % r] + m) for m, rows in (([], (6, 8)), (["-DSY_VANILLA"], (4, 6, 8)),
+                                                            (["-DSY_HDP"], (6, 8)), (["-DSY_HDP", "-DSY_ESTEP"], (6, 8)))
+          for r in rows] + \
+         [("wave", ["-DWV_L=%d" % l] + m) for m, cells in (([], (2, 3, 4)), (["-DWV_HDP"], (2, 3, 4)),
+                                                         (["-DWV_VANILLA"], (2, 3))) for l in cells] + \
+         [("prep", []), ("general", []), ("generalh", [])]
 META = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size",
         "kernarg_segment_size")
 
 
 def kernels(tree, unit, defs, work):
-    """{kernel name: (instruction text, metadata figures)} of one build of one tree"""
+    """{kernel name: (instruction text, metadata figures)} of one build of one tree; none where the tree lacks the file"""
     src = os.path.join(tree, "cpecan-signal_amd", "csrc", "cpecan_kernel_%s.hip" % unit)
+    if not os.path.exists(src):
+        return {}
     out = os.path.join(work, "%s%s.s" % (unit, "".join(defs).replace("-D", "_").replace("=", "")))
     subprocess.check_call([HIPCC] + FLAGS + defs + ["-I" + os.path.join(tree, "include"), "-I" + os.path.dirname(src),
                                                     "-S", "--cuda-device-only", "-o", out, src],
@@ -32,7 +42,8 @@ def kernels(tree, unit, defs, work):
     for block in text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
         body = text[text.index("\n%s:" % name):]
-        body = "\n".join(l for l in body[:body.index("s_endpgm")].splitlines() if not l.lstrip().startswith(";"))
+        body = "\n".join(l.split(";")[0].rstrip() for l in body[:body.index("\n.Lfunc_end")].splitlines())
+        body = re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\n+", "\n", body))  # (comments gone: they name blocks by function too)
         found[name] = (body, tuple(re.search(r"\.%s:\s+(\d+)" % k, block).group(1) for k in META))
     return found
 
@@ -44,9 +55,7 @@ def main():
         os.makedirs(os.path.join(work, t), exist_ok=True)
     jobs = [(t, sub, u, d) for u, d in BUILDS for t, sub in ((parent, "P"), (branch, "B"))]
     with ThreadPoolExecutor(max_workers=int(os.environ.get("JOBS", "8"))) as pool:
-        # (the four-cell vanilla build is no longer made: its sweeps are expected among "only in the parent")
-        res = list(pool.map(lambda j: {} if j[1] == "B" and j[3] == ["-DWV_L=4", "-DWV_VANILLA"] else
-                            kernels(j[0], j[2], j[3], os.path.join(work, j[1])), jobs))
+        res = list(pool.map(lambda j: kernels(j[0], j[2], j[3], os.path.join(work, j[1])), jobs))
     # a kernel is compared with the same build of the parent, or (it moved) with the parent build that has it
     everywhere = {}
     for p in res[0::2]:
