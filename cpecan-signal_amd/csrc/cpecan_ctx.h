@@ -1,7 +1,8 @@
 /*
- * cpecan_ctx.h -- what the two halves of the C-ABI layer share: the context, its model tables and the small helpers
- * around device memory (cpecan_hip.hip: contexts and batches; cpecan_models.hip: the model tables).  Private to the
- * library: the functions declared here are defined in cpecan_hip.hip and hidden from its exports.
+ * cpecan_ctx.h -- what the files of the C-ABI layer share: the context, its model tables and the small helpers
+ * around device memory (cpecan_hip.hip: contexts and batches; cpecan_readback.hip: what a finished run gives back;
+ * cpecan_models.hip: the model tables).  The batch itself: cpecan_batch.h.  Private to the library: the functions
+ * declared here are defined in cpecan_hip.hip and hidden from its exports.
  */
 #ifndef CPECAN_CTX_H
 #define CPECAN_CTX_H

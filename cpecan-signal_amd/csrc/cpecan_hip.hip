@@ -1,13 +1,13 @@
 /*
- * cpecan_hip.hip -- the C-ABI of include/cpecan_hip.h: contexts and batches (the model tables: cpecan_models.hip).
+ * cpecan_hip.hip -- the C-ABI of include/cpecan_hip.h: contexts and batches, from creation to the end of a run (the model
+ * tables: cpecan_models.hip; what a finished run gives back: cpecan_readback.hip).
  *
  * Host side of the thin layer between the reference-shaped C host code and the gfx950 kernels.
  * Nothing here computes DP cells: when no GPU is usable every compute entry point fails with
  * CPECAN_ENODEVICE (there is deliberately no CPU fallback).
  */
-#include "cpecan_ctx.h"
+#include "cpecan_batch.h"
 
-#include "cpecan_asm.h"
 #include "cpecan_sweep.h"
 
 #include <algorithm>
@@ -99,14 +99,6 @@ template <class T> struct NoInit : std::allocator<T> {
         else ::new ((void *) p) U(std::forward<A>(a)...);
     }
 };
-
-/* one candidate pair on its way to the host: its coordinates.  With it goes the device's verdict (an int, see
- * cpecan_k_pack_pairs); the exponent (F + B) - totalProbability stays in HBM and is fetched for the few candidates the
- * host has to settle itself, and for callers that ask for it: 12 bytes per candidate cross PCIe instead of 20. */
-struct PackedPair {
-    int x, y;
-};
-#define CP_UNDECIDED_CAP 65536ull /* candidates per batch the host settles with its libm before it fetches exponents item by item */
 
 } // namespace
 
@@ -373,98 +365,6 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
     return d;
 }
 
-struct cpecan_batch {
-    cpecan_ctx *ctx = nullptr;
-    int64_t nItems = 0;
-    int mode = 0, kernel = 0, flags = 0;
-    DevParams P{};
-    std::vector<DevItem> hItems;
-    DevBuf<DevItem> items;
-    DevBuf<int> bandL, bandR;
-    DevBuf<long long> cellPrefix;
-    DevBuf<char> chars, charsY; /* charsY: DNA batches (5-state machine) */
-    Machine machine = STRAWMAN;
-    bool wave5 = false; /* a DNA batch on the 5-state machine's wave kernels (choose_dispatch) */
-    DevBuf<double> logNoise; /* vanilla and echelon batches: log(event noise), host libm */
-    DevBuf<double> duration; /* echelon batches: per event the duration terms of 0..5 k-mers, host libm */
-    DevBuf<long long> xEnd;  /* echelon batches: per item the X characters that belong to its sequence */
-    DevBuf<int> kid;         /* HDP batches: k-mer id over the model's alphabet per X position */
-    DevBuf<unsigned short> kidx;
-    DevBuf<double> events;
-    DevBuf<double> Fstore, Bstore, dbgB;
-    DevBuf<double> Bring; /* systolic Baum-Welch: backward cells of one window per item */
-    bool fused = false; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0): expectations summed
-                           inside the sweep back, no B ring, no expectation kernel */
-    DevBuf<long long> pairs;
-    DevBuf<double> pairLogp;
-    DevBuf<long long> nPairs, totXay, nTot, nCells;
-    DevBuf<double> totVal;
-    DevBuf<double> expect;
-    DevBuf<int> workCounter;
-    DevBuf<char> syStates, syScratch;
-    DevBuf<int> bandTab; /* systolic kernels: (first, last) matrix column of every diagonal of every item */
-    long long scratchBytes = 0;
-    int nWindows = 0;
-    DevBuf<double> track;
-    DevBuf<long long> trackBase;
-    long long ringDoubles = 0;
-    int ringD = 0, maxLX = 0;
-    int nWorkers = 0, maxWidth = 0;
-    const SweepBuild *sy = SY_BUILDS[3]; /* systolic path: the build of the kernels the batch runs on */
-    int device = 0;                    /* the context's device, kept for the destructor */
-    int nModels = 0;
-    int expectLen = CPECAN_EXPECTATION_LEN; /* doubles per model in `expect` */
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    /* systolic path: the batch runs as nGroups independent groups of alignments, each on a stream of
-     * its own, so that the tail of one group's kernel overlaps the other groups' kernels (a launch
-     * lasts as long as its slowest workgroup).  evStage: per group, one event after every kernel. */
-    int nGroups = 1;
-    /* (a wave batch of one group runs on lane sets instead: gStream empty, gStreamOwned false) */
-    std::vector<hipStream_t> gStream, gStreamB; /* gStreamB: the wave kernels' backward sweeps (see batch_run) */
-    bool postAside = false;            /* assembly sweeps: the totals and the decode of a window on the post lane, beside
-                                          the next window's sweeps */
-    std::vector<hipEvent_t> evPost;    /* ... done, per window */
-    bool gStreamOwned = true;
-    LaneSet *runLanes = nullptr; /* the lanes of its last run (a reference) */
-    bool laneRun = false;        /* ... which went over their three streams: a follower is issued on them */
-    long long modelEpoch = 0; /* the context's when the batch was created */
-    int stateBytes = 0;
-    std::vector<hipEvent_t> evStage, evJoin;
-    hipEvent_t evFork = nullptr;
-    std::vector<long long> hNPairs, hNTot, hNCells;
-    /* aligned pairs as the callers get them: the device selects by the exponent with a margin, the host finishes
-     * exp(), the threshold test and floor(p * 1e7) with the reference's libm (impl/pairwiseAligner.c:776-786) */
-    std::vector<long long> hPairs; /* triples, packed per item at hPairBase */
-    std::vector<double> hLogp;
-    std::vector<long long> hPairBase;
-    /* the way back to the host: the candidates of all items packed into one device buffer of 16-byte records and
-     * copied in one piece into pinned memory */
-    DevBuf<long long> packBase;
-    DevBuf<PackedPair> packed;
-    DevBuf<int> packedPost;
-    DevBuf<long long> undecided;   /* cpecan_k_pack_pairs: [count | CP_UNDECIDED_CAP x (packed index, exponent bits)] */
-    long long *hUndecided = nullptr; /* its pinned copy */
-    PackedPair *hPacked = nullptr; /* hipHostMalloc */
-    int *hPost = nullptr;          /* hipHostMalloc: the device's verdict per candidate (cpecan_k_pack_pairs) */
-    size_t hPackedCap = 0;
-    size_t hPackedBlock = 0, hPostBlock = 0, hUndecidedBlock = 0; /* the real sizes of those blocks (the allocator's cache) */
-    int trackRow = CP_ROW; /* doubles per column of the track */
-    bool countsValid = false, ran = false;
-    bool packedInRun = false; /* the last run ended with cpecan_k_pack_base + cpecan_k_pack_pairs */
-    bool compactPairs = false; /* every sequence of the batch is shorter than 65536 elements: a packed candidate crosses
-                                  PCIe as (x | y << 16) and its verdict, 8 bytes instead of 12 */
-    /* the hand-scheduled assembly sweeps (cpecan_asm.h): the host's plan of windows and band steps, the forward waves'
-     * contexts */
-    bool useAsm = false, asmBackward = false;
-    int asmMaxWindows = 0;
-    std::string asmSetupError; /* why a batch planned for them does not run on them (a failed setup launch) */
-    DevBuf<AsmPlanWin> planWin;
-    DevBuf<AsmPlanCtl> planCtl;
-    DevBuf<long long> planOff;
-    DevBuf<char> asmCtx;
-    DevBuf<unsigned> asmMasks;
-};
-
 /* The plan of one alignment for the assembly sweeps: its traceback windows (getPosteriorProbsWithBanding's schedule,
  * impl/pairwiseAligner.c:917-921 -- a function of the band alone; the same walk as the window count in batch_create) and,
  * per diagonal, whether the band's edges step and whether the forward sweep keeps all three states of the diagonal
@@ -525,12 +425,6 @@ static void build_asm_plan(const int *tab, long long nDiag, const cpecan_band_pa
         }
     }
 }
-
-extern "C" __global__ void cpecan_k_pack_pairs(const DevItem *items, const long long *packBase, const long long *pairs,
-                                               const double *logp, double threshold, long long capacity,
-                                               PackedPair *out, int *post, long long *undecided, int compact);
-extern "C" __global__ void cpecan_k_pack_base(const DevItem *items, const long long *nPairs, long long nItems,
-                                              long long *packBase);
 
 extern "C" {
 
@@ -699,9 +593,7 @@ int cpecan_hip_batch_destroy(cpecan_batch *b) {
         if (b->ctx) b->ctx->batches.erase(std::remove(b->ctx->batches.begin(), b->ctx->batches.end(), b), b->ctx->batches.end());
     }
     for (hipEvent_t e : b->evPost) (void) hipEventDestroy(e);
-    if (b->hPacked) pinned_cache().put(b->hPacked, b->hPackedBlock);
-    if (b->hPost) pinned_cache().put(b->hPost, b->hPostBlock);
-    if (b->hUndecided) pinned_cache().put(b->hUndecided, b->hUndecidedBlock);
+    release_readback(b);
     delete b;
     (void) hipGetLastError(); /* a failed clean-up call must not surface as the "last error" of a later launch */
     return CPECAN_OK;
@@ -967,10 +859,8 @@ static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput 
     b->P.logThrSlack = bp.threshold > 0.0 ? log(bp.threshold) - 1e-3 : -INFINITY;
     b->P.ldsWidth = 0; /* (set per launch by the kernels that use it) */
     b->P.expectResweep = 0;
-    if (d.build) {
-        b->sy = d.build;
-        b->trackRow = b->sy->once->trackRowDoubles;
-    }
+    b->sy = d.build ? d.build : SY_BUILDS[3];
+    if (d.build) b->trackRow = b->sy->once->trackRowDoubles;
     b->hItems = plan.items;
     return b;
 }
@@ -1556,31 +1446,7 @@ static int batch_enqueue(cpecan_batch *b, cpecan_batch *after, LaneSet *L) {
     else
         rc = enqueue_sweeps(b, L, &sEnd, &laneRun);
     if (rc != CPECAN_OK) return rc;
-    /* posterior decode: the run ends with its candidates packed for the host (16-byte records + the device's verdict),
-     * into a buffer sized by a guess the first time (about one candidate per diagonal) and by the last run's count
-     * afterwards; ensure_counts packs again if the guess was short.  Done here, inside the pass, because a kernel
-     * launched later would wait for wave slots behind the next batch's sweeps. */
-    b->packedInRun = false;
-    static const bool packInRun = getenv("CPECAN_PACK_LATER") == nullptr;
-    if (packInRun && b->mode == CPECAN_MODE_POSTERIOR && !b->P.debug) {
-        if (b->packed.n == 0) {
-            long long guess = 0;
-            for (const DevItem &d : b->hItems) guess += std::min<long long>(d.pairCap, d.lX + d.lY + 64);
-            HIP_TRY(b->packed.alloc((size_t) guess));
-            HIP_TRY(b->packedPost.alloc((size_t) guess));
-        }
-        if (b->packBase.n < (size_t) b->nItems + 1) HIP_TRY(b->packBase.alloc((size_t) b->nItems + 1));
-        if (b->undecided.n == 0) HIP_TRY(b->undecided.alloc(1 + 2 * CP_UNDECIDED_CAP));
-        HIP_TRY(hipMemsetAsync(b->undecided.p, 0, sizeof(long long), sEnd));
-        hipLaunchKernelGGL(cpecan_k_pack_base, dim3(1), dim3(256), 0, sEnd, (const DevItem *) b->items.p,
-                           (const long long *) b->nPairs.p, (long long) b->nItems, b->packBase.p);
-        hipLaunchKernelGGL(cpecan_k_pack_pairs, dim3((unsigned) b->nItems), dim3(256), 0, sEnd,
-                           (const DevItem *) b->items.p, (const long long *) b->packBase.p, (const long long *) b->pairs.p,
-                           (const double *) b->pairLogp.p, b->P.threshold, (long long) b->packed.n, b->packed.p,
-                           b->packedPost.p, b->undecided.p, b->compactPairs ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        b->packedInRun = true;
-    }
+    if ((rc = pack_in_run(b, sEnd)) != CPECAN_OK) return rc;
     HIP_TRY(hipEventRecord(b->ev2, sEnd));
     b->ran = true;
     b->laneRun = laneRun;
@@ -1748,388 +1614,6 @@ int cpecan_hip_batch_elapsed_ms(cpecan_batch *b, float *msTotal, float *msKernel
     HIP_TRY(hipEventElapsedTime(&k, b->ev1, b->ev2));
     if (msTotal) *msTotal = a;
     if (msKernel) *msKernel = k;
-    return CPECAN_OK;
-}
-
-/* Counts and aligned pairs of a finished run.  If an alignment produced more pairs than its share of the pair buffer
- * holds (flat posteriors: a tiny threshold, the HDP machine's linear densities), the buffer is re-laid-out to the
- * reported counts and the batch is run once more -- the reference returns the list whatever its length.  The device
- * selects pairs by the exponent (F+B)-total with a margin below log(threshold); exp(), the exact threshold test and
- * floor(p * 1e7) are finished here with the host libm, the one the reference calls
- * (diagonalCalculationPosteriorMatchProbs, impl/pairwiseAligner.c:776-786). */
-/* item i's first packBase[i + 1] - packBase[i] candidates, from its own region of the pair buffers to the packed one */
-/* With every candidate goes a verdict on its integer posterior: the device's exp() and the host libm's differ by at
- * most a few units in the last place, so wherever exp(logp) is not within a (far wider) margin of the threshold, of 1
- * or of a multiple of 1e-7, floor(p * 1e7) is the same number on both and is taken here (post >= 0), or the pair is
- * surely below the threshold (post -2); the few that are close (post -1) are finished by the host with its libm. */
-extern "C" __global__ void cpecan_k_pack_pairs(const DevItem *items, const long long *packBase, const long long *pairs,
-                                               const double *logp, double threshold, long long capacity,
-                                               PackedPair *out, int *post, long long *undecided /* [0] count, then
-                                               CP_UNDECIDED_CAP x (packed index, exponent bits) */,
-                                               int compact /* both coordinates below 65536: four bytes a pair */) {
-    const DevItem &d = items[blockIdx.x];
-    if (packBase[gridDim.x] > capacity) return; /* (packed at the end of a run into a buffer sized by a guess: the host
-                                                   sees the same total and packs again into one that fits) */
-    const long long o = packBase[blockIdx.x], n = packBase[blockIdx.x + 1] - o;
-    for (long long k = threadIdx.x; k < n; k += blockDim.x) {
-        PackedPair r;
-        r.x = (int) pairs[(d.pairBase + k) * 3 + 1];
-        r.y = (int) pairs[(d.pairBase + k) * 3 + 2];
-        if (compact) ((unsigned *) out)[o + k] = (unsigned) r.x | ((unsigned) r.y << 16);
-        else out[o + k] = r;
-        const double e = logp[d.pairBase + k];
-        const double p = exp(e);
-        int v = -1;
-        if (p == p) {
-            if (p < threshold - (1e-9 * threshold + 1e-300)) v = -2;
-            else if (p > threshold + (1e-9 * threshold + 1e-300) || threshold == 0.0) {
-                if (p > 1.0 + 1e-9) v = 10000000;
-                else if (p < 1.0 - 1e-9) {
-                    const double q = p * 10000000.0, fl = floor(q);
-                    if (q - fl > 1e-5 && fl + 1.0 - q > 1e-5) v = (int) fl;
-                } else if (e >= 0.0) v = 10000000; /* exp(e) >= 1 on any libm: clamped to 1 */
-                else if (e <= -1e-15) v = 9999999; /* exp(e) <= 1 - 9e-16 < 1, and p * 1e7 rounds below 1e7 (its
-                                                      ulp there is 1.9e-9, the deficit at least 1e-8): a quarter of a
-                                                      C3 batch's candidates are this sure a match */
-            }
-        }
-        post[o + k] = v;
-        if (v == -1) { /* the host settles it: its exponent goes along (a short list; a batch that overflows it has
-                          the host fetch the exponents item by item) */
-            const unsigned long long j = atomicAdd((unsigned long long *) undecided, 1ull);
-            if (j < CP_UNDECIDED_CAP) {
-                undecided[1 + 2 * j] = o + k;
-                undecided[2 + 2 * j] = __double_as_longlong(e);
-            }
-        }
-    }
-}
-
-/* packBase[i] = candidates of the items before i (each item's count capped at its capacity), packBase[n] = all of
- * them: the offsets cpecan_k_pack_pairs writes to, formed on the device so that a run can end with its candidates
- * packed (the host forms the same sums from the counts it fetches) */
-extern "C" __global__ __launch_bounds__(256) void cpecan_k_pack_base(const DevItem *items, const long long *nPairs,
-                                                                     long long nItems, long long *packBase) {
-    __shared__ long long part[256];
-    const long long per = (nItems + 255) / 256, i0 = threadIdx.x * per, i1 = i0 + per < nItems ? i0 + per : nItems;
-    long long sum = 0;
-    for (long long i = i0; i < i1; i++) sum += nPairs[i] < items[i].pairCap ? nPairs[i] : items[i].pairCap;
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long run = 0;
-        for (int t = 0; t < 256; t++) {
-            const long long v = part[t];
-            part[t] = run;
-            run += v;
-        }
-        packBase[nItems] = run;
-    }
-    __syncthreads();
-    long long run = part[threadIdx.x];
-    for (long long i = i0; i < i1; i++) {
-        packBase[i] = run;
-        run += nPairs[i] < items[i].pairCap ? nPairs[i] : items[i].pairCap;
-    }
-}
-
-static int ensure_counts(cpecan_batch *b) {
-    if (!b->ran) return fail(CPECAN_EINVAL, "batch has not run");
-    if (b->countsValid) return CPECAN_OK;
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    Lap lap("ensure_counts");
-    /* readbacks wait for the run's end event and go through the context's prep stream: the lanes the run went on may
-     * carry the next batch's run already */
-    hipStream_t rs = b->ctx->prep;
-    b->hNPairs.resize((size_t) b->nItems);
-    b->hNTot.resize((size_t) b->nItems);
-    for (int attempt = 0;; attempt++) {
-        HIP_TRY(hipEventSynchronize(b->ev2));
-        HIP_TRY(hipMemcpy(b->hNPairs.data(), b->nPairs.p, (size_t) b->nItems * sizeof(long long), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(b->hNTot.data(), b->nTot.p, (size_t) b->nItems * sizeof(long long), hipMemcpyDeviceToHost));
-        bool over = false;
-        for (int64_t i = 0; i < b->nItems; i++)
-            if (b->hNPairs[(size_t) i] > b->hItems[(size_t) i].pairCap) over = true;
-        if (!over) break;
-        if (attempt == 2) return fail(CPECAN_EOVERFLOW, "aligned-pair counts keep growing between identical runs");
-        long long total = 0;
-        for (int64_t i = 0; i < b->nItems; i++) {
-            DevItem &d = b->hItems[(size_t) i];
-            d.pairCap = std::max(d.pairCap, b->hNPairs[(size_t) i] + 64);
-            d.pairBase = total;
-            total += d.pairCap;
-        }
-        HIP_TRY(b->pairs.alloc((size_t) total * 3));
-        HIP_TRY(b->pairLogp.alloc((size_t) total));
-        HIP_TRY(hipMemcpy(b->items.p, b->hItems.data(), (size_t) b->nItems * sizeof(DevItem), hipMemcpyHostToDevice));
-        int rc = cpecan_hip_batch_run(b);
-        if (rc != CPECAN_OK) return rc;
-    }
-    b->hPairBase.assign((size_t) b->nItems + 1, 0);
-    for (int64_t i = 0; i < b->nItems; i++)
-        b->hPairBase[(size_t) i + 1] = b->hPairBase[(size_t) i] + std::min(b->hNPairs[(size_t) i], b->hItems[(size_t) i].pairCap);
-    const long long all = b->hPairBase[(size_t) b->nItems];
-    if (b->mode != CPECAN_MODE_POSTERIOR) {
-        b->hPairs.resize((size_t) all * 3);
-        b->hLogp.resize((size_t) all);
-        /* (in expectation mode the HDP machine's pair buffer carries event-to-k-mer assignments, not posteriors:
-         * short lists, copied as they are) */
-        for (int64_t i = 0; i < b->nItems; i++) {
-            const DevItem &d = b->hItems[(size_t) i];
-            const long long n = b->hPairBase[(size_t) i + 1] - b->hPairBase[(size_t) i], o = b->hPairBase[(size_t) i];
-            if (n == 0) continue;
-            HIP_TRY(hipMemcpyAsync(b->hPairs.data() + o * 3, b->pairs.p + d.pairBase * 3, (size_t) n * 3 * sizeof(long long),
-                                   hipMemcpyDeviceToHost, rs));
-            HIP_TRY(hipMemcpyAsync(b->hLogp.data() + o, b->pairLogp.p + d.pairBase, (size_t) n * sizeof(double),
-                                   hipMemcpyDeviceToHost, rs));
-        }
-        HIP_TRY(hipStreamSynchronize(rs));
-        if (b->machine == HDP && b->kernel == CPECAN_KERNEL_SYSTOLIC) {
-            /* the HDP machine's event assignments from the wave kernels: appended by whichever thread got there, each
-             * tagged with its traceback window (first field = from-state + 4 * window).  The reference walks windows
-             * upwards, inside a window the diagonals downwards, a diagonal by ascending x, a cell by from-state
-             * (cell_signal_updateTransAndKmerSkipExpectations2 inside diagonalCalculation_Expectations): put them so */
-            std::vector<long long> order;
-            std::vector<long long> tri;
-            std::vector<double> lp;
-            for (int64_t i = 0; i < b->nItems; i++) {
-                const long long o = b->hPairBase[(size_t) i], n = b->hPairBase[(size_t) i + 1] - o;
-                if (n <= 1) {
-                    if (n == 1) b->hPairs[(size_t) o * 3] &= 3;
-                    continue;
-                }
-                long long *p3 = b->hPairs.data() + o * 3;
-                double *pl = b->hLogp.data() + o;
-                order.resize((size_t) n);
-                for (long long k = 0; k < n; k++) order[(size_t) k] = k;
-                std::sort(order.begin(), order.end(), [p3](long long a, long long c2) {
-                    const long long wa = p3[3 * a] >> 2, wc = p3[3 * c2] >> 2;
-                    if (wa != wc) return wa < wc;
-                    const long long da = p3[3 * a + 1] + p3[3 * a + 2], dc = p3[3 * c2 + 1] + p3[3 * c2 + 2];
-                    if (da != dc) return da > dc;
-                    if (p3[3 * a + 1] != p3[3 * c2 + 1]) return p3[3 * a + 1] < p3[3 * c2 + 1];
-                    return (p3[3 * a] & 3) < (p3[3 * c2] & 3);
-                });
-                tri.assign(p3, p3 + 3 * n);
-                lp.assign(pl, pl + n);
-                for (long long k = 0; k < n; k++) {
-                    const long long src = order[(size_t) k];
-                    p3[3 * k] = tri[(size_t) (3 * src)] & 3;
-                    p3[3 * k + 1] = tri[(size_t) (3 * src + 1)];
-                    p3[3 * k + 2] = tri[(size_t) (3 * src + 2)];
-                    pl[k] = lp[(size_t) src];
-                }
-            }
-        }
-        b->countsValid = true;
-        return CPECAN_OK;
-    }
-    if (all > 0) {
-        const bool packedAlready = b->packedInRun && (size_t) all <= b->packed.n; /* the run ended with them packed */
-        if (b->packBase.n < (size_t) b->nItems + 1) HIP_TRY(b->packBase.alloc((size_t) b->nItems + 1));
-        if (b->packed.n < (size_t) all) {
-            HIP_TRY(b->packed.alloc((size_t) all + (size_t) all / 8));
-            HIP_TRY(b->packedPost.alloc((size_t) all + (size_t) all / 8));
-        }
-        if (b->hPackedCap < (size_t) all) {
-            if (b->hPacked) pinned_cache().put(b->hPacked, b->hPackedBlock);
-            if (b->hPost) pinned_cache().put(b->hPost, b->hPostBlock);
-            b->hPacked = nullptr;
-            b->hPost = nullptr;
-            b->hPackedCap = (size_t) all + (size_t) all / 8;
-            HIP_TRY(pinned_cache().get((void **) &b->hPacked, b->hPackedCap * sizeof(PackedPair), &b->hPackedBlock));
-            HIP_TRY(pinned_cache().get((void **) &b->hPost, b->hPackedCap * sizeof(int), &b->hPostBlock));
-        }
-        if (b->undecided.n == 0) HIP_TRY(b->undecided.alloc(1 + 2 * CP_UNDECIDED_CAP));
-        if (!b->hUndecided)
-            HIP_TRY(pinned_cache().get((void **) &b->hUndecided, (1 + 2 * CP_UNDECIDED_CAP) * sizeof(long long), &b->hUndecidedBlock));
-        if (!packedAlready) {
-        HIP_TRY(hipMemcpyAsync(b->packBase.p, b->hPairBase.data(), ((size_t) b->nItems + 1) * sizeof(long long),
-                               hipMemcpyHostToDevice, rs));
-        HIP_TRY(hipMemsetAsync(b->undecided.p, 0, sizeof(long long), rs));
-        hipLaunchKernelGGL(cpecan_k_pack_pairs, dim3((unsigned) b->nItems), dim3(256), 0, rs,
-                           (const DevItem *) b->items.p, (const long long *) b->packBase.p, (const long long *) b->pairs.p,
-                           (const double *) b->pairLogp.p, b->P.threshold, (long long) b->packed.n, b->packed.p,
-                           b->packedPost.p, b->undecided.p, b->compactPairs ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(b->hUndecided, b->undecided.p, (1 + 2 * CP_UNDECIDED_CAP) * sizeof(long long),
-                               hipMemcpyDeviceToHost, rs));
-        HIP_TRY(hipMemcpyAsync(b->hPacked, b->packed.p, (size_t) all * (b->compactPairs ? sizeof(unsigned) : sizeof(PackedPair)),
-                               hipMemcpyDeviceToHost, rs));
-        HIP_TRY(hipMemcpyAsync(b->hPost, b->packedPost.p, (size_t) all * sizeof(int), hipMemcpyDeviceToHost,
-                               rs));
-        HIP_TRY(hipStreamSynchronize(rs));
-    }
-    /* The close calls: exp(), the threshold test and floor(p * 1e7) with the host's libm, the one the reference calls
-     * (impl/pairwiseAligner.c:776-786), written back over the device's "undecided" verdict; and the number of pairs
-     * every item keeps.  The records stay packed in pinned memory; cpecan_hip_batch_fetch_pairs expands an item's
-     * pairs into the reference's triples when they are asked for.  Items are independent: dealt to the host threads. */
-    const double threshold = b->P.threshold;
-    int *verdict = b->hPost;
-    static const bool hostOnly = getenv("CPECAN_HOST_FINALISE") != nullptr; /* (tests: every pair through the host libm) */
-    const int nt = (int) std::min<int64_t>(all > 200000 ? host_threads() : 1, b->nItems);
-    /* contiguous runs of items with about the same number of candidates each */
-    std::vector<int64_t> cut(1, 0);
-    for (int t = 0; t < nt; t++) {
-        const long long want = all * (t + 1) / nt;
-        int64_t i1 = cut.back();
-        while (i1 < b->nItems && (b->hPairBase[(size_t) i1 + 1] <= want || t == nt - 1)) i1++;
-        cut.push_back(i1);
-    }
-    cut.back() = b->nItems;
-    /* what the device settled is counted by the host threads; what it left open (verdict -1) comes with its exponent
-     * in the short list the pack kernel made, and is settled here with the host libm */
-    const long long listed = all > 0 ? b->hUndecided[0] : 0;
-    const bool byList = !hostOnly && listed <= (long long) CP_UNDECIDED_CAP;
-    if (getenv("CPECAN_TIMING")) fprintf(stderr, "[cpecan timing] ensure_counts: %lld candidates, %lld left to the host\n", all, listed);
-    auto settle = [threshold](double e) {
-        double p = exp(e);
-        if (!(p >= threshold)) return -2;
-        if (p > 1.0) p = 1.0;
-        return (int) floor(p * 10000000.0);
-    };
-    if (byList)
-        for (long long j = 0; j < listed; j++) {
-            double e;
-            memcpy(&e, &b->hUndecided[2 + 2 * j], sizeof e);
-            verdict[b->hUndecided[1 + 2 * j]] = settle(e);
-        }
-    std::atomic<int> failed{0};
-    auto scan = [b, verdict, byList, &settle, &failed](int64_t i0, int64_t i1) {
-        std::vector<double> e;
-        for (int64_t i = i0; i < i1; i++) {
-            const long long o = b->hPairBase[(size_t) i], n = b->hPairBase[(size_t) i + 1] - o;
-            if (!byList && n > 0) { /* (tests, or more close calls than the list holds: this item's exponents from HBM) */
-                e.resize((size_t) n);
-                if (hipSetDevice(b->ctx->device) != hipSuccess ||
-                    hipMemcpy(e.data(), b->pairLogp.p + b->hItems[(size_t) i].pairBase, (size_t) n * sizeof(double),
-                              hipMemcpyDeviceToHost) != hipSuccess) {
-                    failed = 1;
-                    return;
-                }
-            }
-            long long kept = 0;
-            for (long long k = 0; k < n; k++) {
-                if (!byList && (hostOnly || verdict[o + k] == -1)) verdict[o + k] = settle(e[(size_t) k]);
-                kept += verdict[o + k] >= 0;
-            }
-            b->hNPairs[(size_t) i] = kept;
-        }
-    };
-    {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; t++)
-            if (cut[(size_t) t + 1] > cut[(size_t) t]) pool.emplace_back(scan, cut[(size_t) t], cut[(size_t) t + 1]);
-        scan(cut[0], cut[1]);
-        for (std::thread &th : pool) th.join();
-    }
-    if (failed) return fail(CPECAN_EHIP, "fetching the candidates' exponents failed: %s", hipGetErrorString(hipGetLastError()));
-    b->countsValid = true;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_counts(cpecan_batch *b, int64_t *nPairs, int64_t *nTotals, int64_t *nCells) {
-    if (!b) return fail(CPECAN_EINVAL, "batch is NULL");
-    int rc = ensure_counts(b);
-    if (rc) return rc;
-    for (int64_t i = 0; i < b->nItems; i++) {
-        if (nPairs) nPairs[i] = b->hNPairs[(size_t) i];
-        if (nTotals) nTotals[i] = b->hNTot[(size_t) i];
-        if (nCells) nCells[i] = b->hNCells[(size_t) i];
-    }
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_fetch_pairs(cpecan_batch *b, int64_t item, int64_t *triples, double *logp,
-                                 int64_t cap) {
-    if (!b || item < 0 || item >= b->nItems || !triples) return fail(CPECAN_EINVAL, "bad argument");
-    int rc = ensure_counts(b);
-    if (rc) return rc;
-    const long long n = b->hNPairs[(size_t) item], o = b->hPairBase[(size_t) item];
-    if (n > cap) return fail(CPECAN_EOVERFLOW, "need room for %lld triples", n);
-    if (n == 0) return CPECAN_OK;
-    if (b->mode != CPECAN_MODE_POSTERIOR) {
-        memcpy(triples, b->hPairs.data() + o * 3, (size_t) n * 3 * sizeof(long long));
-        if (logp) memcpy(logp, b->hLogp.data() + o, (size_t) n * sizeof(double));
-        return CPECAN_OK;
-    }
-    /* the item's packed candidates with their settled verdicts -> (floor(p * 1e7), x, y), emission order */
-    const long long cand = b->hPairBase[(size_t) item + 1] - o;
-    std::vector<double> e;
-    if (logp) { /* the exponents stayed in HBM: this item's, now */
-        e.resize((size_t) cand);
-        HIP_TRY(hipSetDevice(b->ctx->device));
-        HIP_TRY(hipMemcpy(e.data(), b->pairLogp.p + b->hItems[(size_t) item].pairBase, (size_t) cand * sizeof(double),
-                          hipMemcpyDeviceToHost));
-    }
-    long long kept = 0;
-    for (long long k = 0; k < cand; k++) {
-        const int v = b->hPost[o + k];
-        if (v < 0) continue;
-        triples[kept * 3] = v;
-        if (b->compactPairs) {
-            const unsigned xy = ((const unsigned *) b->hPacked)[o + k];
-            triples[kept * 3 + 1] = xy & 0xFFFFu;
-            triples[kept * 3 + 2] = xy >> 16;
-        } else {
-            triples[kept * 3 + 1] = b->hPacked[o + k].x;
-            triples[kept * 3 + 2] = b->hPacked[o + k].y;
-        }
-        if (logp) logp[kept] = e[(size_t) k];
-        kept++;
-    }
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_fetch_totals(cpecan_batch *b, int64_t item, int64_t *xay, double *total,
-                                  int64_t cap) {
-    if (!b || item < 0 || item >= b->nItems) return fail(CPECAN_EINVAL, "bad argument");
-    int rc = ensure_counts(b);
-    if (rc) return rc;
-    const DevItem &d = b->hItems[(size_t) item];
-    long long n = b->hNTot[(size_t) item];
-    if (n > d.totCap) return fail(CPECAN_EOVERFLOW, "totals overflow (%lld > %lld)", n, d.totCap);
-    if (n > cap) return fail(CPECAN_EOVERFLOW, "need room for %lld totals", n);
-    if (n == 0) return CPECAN_OK;
-    if (xay)
-        HIP_TRY(hipMemcpy(xay, b->totXay.p + d.totBase, (size_t) n * sizeof(long long), hipMemcpyDeviceToHost));
-    if (total)
-        HIP_TRY(hipMemcpy(total, b->totVal.p + d.totBase, (size_t) n * sizeof(double), hipMemcpyDeviceToHost));
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_expectations_device_ptr(cpecan_batch *b, void **devPtr, int64_t *nDoubles) {
-    if (!b || !devPtr) return fail(CPECAN_EINVAL, "bad argument");
-    *devPtr = (void *) b->expect.p;
-    if (nDoubles) *nDoubles = (int64_t) b->expect.n;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_fetch_expectations(cpecan_batch *b, int32_t modelId, double *out) {
-    if (!b || !out || modelId < 0 || modelId >= b->nModels) return fail(CPECAN_EINVAL, "bad argument");
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    if (b->ran) HIP_TRY(hipEventSynchronize(b->ev2));
-    HIP_TRY(hipMemcpy(out, b->expect.p + (size_t) modelId * b->expectLen, (size_t) b->expectLen * sizeof(double),
-                      hipMemcpyDeviceToHost));
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_debug_cells(cpecan_batch *b, int64_t item, double *forward, double *backward,
-                                 int64_t nCells) {
-    if (!b || item < 0 || item >= b->nItems) return fail(CPECAN_EINVAL, "bad argument");
-    if (!b->P.debug || b->kernel != CPECAN_KERNEL_GENERAL)
-        return fail(CPECAN_EINVAL, "batch was not created with CPECAN_FLAG_DEBUG_DUMP");
-    const DevItem &d = b->hItems[(size_t) item];
-    if (nCells < d.nCells) return fail(CPECAN_EOVERFLOW, "need room for %lld cells", d.nCells);
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    if (b->ran) HIP_TRY(hipEventSynchronize(b->ev2));
-    if (forward)
-        HIP_TRY(hipMemcpy(forward, b->Fstore.p + d.cellBase * 3, (size_t) d.nCells * 3 * sizeof(double),
-                          hipMemcpyDeviceToHost));
-    if (backward)
-        HIP_TRY(hipMemcpy(backward, b->dbgB.p + d.cellBase * 3, (size_t) d.nCells * 3 * sizeof(double),
-                          hipMemcpyDeviceToHost));
     return CPECAN_OK;
 }
 

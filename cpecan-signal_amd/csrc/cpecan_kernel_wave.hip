@@ -1020,7 +1020,7 @@ __device__ __forceinline__ int rank_in_diagonal(const unsigned long long (&m)[WV
  * be trusted is swept once more (WV_KIND_REDO) with the exact totals in hand and decoded in the loop.
  * The device selects pairs by the exponent (F+B)-total >= log(threshold) - margin; exp(), the exact
  * threshold test and floor(p * 1e7) (:776-786) are finished on the host with the reference's libm
- * (cpecan_hip.hip), so the integer posteriors are the reference's to the bit.
+ * (cpecan_readback.hip), so the integer posteriors are the reference's to the bit.
  */
 #define WV_KIND_POSTERIOR 0 /* sweep, collect decode candidates */
 #define WV_KIND_REDO 1      /* sweep once more with the exact totals in hand, pairs leave in the loop */

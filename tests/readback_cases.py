@@ -23,7 +23,7 @@ import synth
 from harness import band_params, orc_params
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-UNDECIDED_CAP = 65536      # CP_UNDECIDED_CAP of cpecan_hip.hip
+UNDECIDED_CAP = 65536      # CP_UNDECIDED_CAP of cpecan_batch.h
 THREADED_ABOVE = 200000    # candidates past which ensure_counts deals the items to host threads
 
 _CACHE = {}

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Device code of the throughput kernels in two source trees, kernel for kernel: each build the Makefile makes of
 cpecan_kernel_systolic.hip (thirteen) and cpecan_kernel_wave.hip (eight), and the files around them that are compiled once
-(cpecan_kernel_prep.hip where a tree has it, cpecan_kernel_general.hip, cpecan_kernel_generalh.hip), is compiled to gfx950
-assembly in both trees (the Makefile's flags plus -S --cuda-device-only) and, per kernel name, the instructions between
+(cpecan_kernel_prep.hip, cpecan_kernel_general.hip, cpecan_kernel_generalh.hip and the two files of the C-ABI layer that
+have held the pack kernels, cpecan_hip.hip and cpecan_readback.hip; a unit is a file of csrc, and one that a tree lacks or
+that defines no kernel there counts for nothing), is compiled to gfx950 assembly in both trees (the Makefile's flags plus -S --cuda-device-only) and, per kernel name, the instructions between
 the label and the function's end and the resource lines of the metadata block are compared.  A kernel that moved to
 another file is compared with whichever parent build had it: the number of its function in the file, which the
 compiler puts into its local labels (.LBB<n>_), is taken out first.  A refactor of the host side, or one that moves
@@ -17,28 +18,32 @@ from concurrent.futures import ThreadPoolExecutor
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
          "-Wno-unused-function"]
-BUILDS = [("systolic", ["-DSY_R=%d" % r]) for r in (1, 2, 3)] + [("systolic", [])] + \
-         [("systolic", ["-DSY_R=%d" % r] + m) for m, rows in (([], (6, 8)), (["-DSY_VANILLA"], (4, 6, 8)),
-                                                            (["-DSY_HDP"], (6, 8)), (["-DSY_HDP", "-DSY_ESTEP"], (6, 8)))
+SY, WV = "cpecan_kernel_systolic.hip", "cpecan_kernel_wave.hip"
+BUILDS = [(SY, ["-DSY_R=%d" % r]) for r in (1, 2, 3)] + [(SY, [])] + \
+         [(SY, ["-DSY_R=%d" % r] + m) for m, rows in (([], (6, 8)), (["-DSY_VANILLA"], (4, 6, 8)),
+                                                     (["-DSY_HDP"], (6, 8)), (["-DSY_HDP", "-DSY_ESTEP"], (6, 8)))
           for r in rows] + \
-         [("wave", ["-DWV_L=%d" % l] + m) for m, cells in (([], (2, 3, 4)), (["-DWV_HDP"], (2, 3, 4)),
-                                                         (["-DWV_VANILLA"], (2, 3))) for l in cells] + \
-         [("prep", []), ("general", []), ("generalh", [])]
+         [(WV, ["-DWV_L=%d" % l] + m) for m, cells in (([], (2, 3, 4)), (["-DWV_HDP"], (2, 3, 4)),
+                                                      (["-DWV_VANILLA"], (2, 3))) for l in cells] + \
+         [(u, []) for u in ("cpecan_kernel_prep.hip", "cpecan_kernel_general.hip", "cpecan_kernel_generalh.hip",
+                            "cpecan_hip.hip", "cpecan_readback.hip")]
 META = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size",
         "kernarg_segment_size")
 
 
 def kernels(tree, unit, defs, work):
     """{kernel name: (instruction text, metadata figures)} of one build of one tree; none where the tree lacks the file"""
-    src = os.path.join(tree, "cpecan-signal_amd", "csrc", "cpecan_kernel_%s.hip" % unit)
+    src = os.path.join(tree, "cpecan-signal_amd", "csrc", unit)
     if not os.path.exists(src):
         return {}
-    out = os.path.join(work, "%s%s.s" % (unit, "".join(defs).replace("-D", "_").replace("=", "")))
+    out = os.path.join(work, "%s%s.s" % (unit[:-4], "".join(defs).replace("-D", "_").replace("=", "")))
     subprocess.check_call([HIPCC] + FLAGS + defs + ["-I" + os.path.join(tree, "include"), "-I" + os.path.dirname(src),
                                                     "-S", "--cuda-device-only", "-o", out, src],
                           stderr=subprocess.DEVNULL)
     text = open(out).read()
     found = {}
+    if "amdhsa.kernels:" not in text:
+        return found
     for block in text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
         body = text[text.index("\n%s:" % name):]
