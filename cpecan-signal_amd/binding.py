@@ -35,6 +35,7 @@ FLAG_GENERAL_KERNEL = 32
 FLAG_WIDE_BANDS = 128
 FLAG_WIDE_BANDS_HDP = 256
 FLAG_WIDE_BANDS_HDP_ESTEP = 512
+FLAG_WIDE_BANDS_VANILLA_ESTEP = 1024
 MACHINE_STRAWMAN, MACHINE_DNA5, MACHINE_VANILLA, MACHINE_HDP, MACHINE_SM4, MACHINE_ECHELON = range(6)
 NUM_KMERS = 4096
 MODEL_TABLE_LEN = 1 + NUM_KMERS * 5

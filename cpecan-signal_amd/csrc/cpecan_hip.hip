@@ -59,7 +59,10 @@ W5_DECLARE(3)
  * CPECAN_FLAG_WIDE_BANDS and only when its widest band is past every build of the tables above.  The same source built
  * with -DSY_VANILLA gives the vanilla machine's wide builds (_v4, _v6, _v8: four, six and eight waves per workgroup,
  * bands up to 248, 376 and 504 k-mers; their table starts one class earlier because the vanilla wave builds end at 184),
- * reached the same way and for the posterior decode only: a vanilla E-step past 184 k-mers stays on the general kernel.
+ * reached the same way and for the posterior decode only; with -DSY_VANILLA -DSY_ESTEP the vanilla machine's E-step at
+ * the same three widths (_ve4, _ve6, _ve8: the sweeps in E-step form, a B ring of one value per cell and the vanilla form
+ * of the expectation kernel), a table of its own that answers to CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP -- without that
+ * flag a vanilla E-step past 184 k-mers stays on the general kernel.
  * Built with -DSY_HDP it gives the HDP machine's wide builds (_h6, _h8: bands of 249..376 and 377..504 k-mers, past the
  * HDP wave builds), which answer to a flag of their own, CPECAN_FLAG_WIDE_BANDS_HDP, again for the posterior decode only;
  * with -DSY_HDP -DSY_ESTEP the HDP machine's E-step at the same two widths (_he6, _he8: the sweeps in E-step form and the
@@ -73,6 +76,7 @@ SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
 SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
 SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
+SWEEP_BUILD(cpecan_systolic_build_ve4) SWEEP_BUILD(cpecan_systolic_build_ve6) SWEEP_BUILD(cpecan_systolic_build_ve8)
 typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
@@ -82,6 +86,8 @@ static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4,
                                                       &cpecan_systolic_build_v8, nullptr };
 static const SweepBuild *const SYH_WIDE_BUILDS[3] = { &cpecan_systolic_build_h6, &cpecan_systolic_build_h8, nullptr };
 static const SweepBuild *const SYHE_WIDE_BUILDS[3] = { &cpecan_systolic_build_he6, &cpecan_systolic_build_he8, nullptr };
+static const SweepBuild *const SYVE_WIDE_BUILDS[4] = { &cpecan_systolic_build_ve4, &cpecan_systolic_build_ve6,
+                                                       &cpecan_systolic_build_ve8, nullptr };
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
@@ -203,8 +209,8 @@ struct MachineRow {
     bool bandedEstep;          /* its E-step refuses CPECAN_FLAG_UNBANDED */
     /* the register-resident kernels: the machine's wave family and, where a batch may ask for it, its workgroup family
      * (null: none); per mode (CPECAN_MODE_POSTERIOR, CPECAN_MODE_EXPECTATIONS) the wide builds of the workgroup family
-     * that serve it (null: none) and the flag they answer to: CPECAN_FLAG_WIDE_BANDS, CPECAN_FLAG_WIDE_BANDS_HDP or
-     * CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP (0: none) */
+     * that serve it (null: none) and the flag they answer to: CPECAN_FLAG_WIDE_BANDS, CPECAN_FLAG_WIDE_BANDS_HDP,
+     * CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP or CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP (0: none) */
     SweepFamily *wave, *workgroup;
     struct Wide {
         const SweepBuild *const *builds;
@@ -224,7 +230,8 @@ static const MachineRow MACHINES[N_MACHINES] = {
     /* DNA5 */     { 5, CPECAN_EXPECTATION5_LEN, 4, 0, nullptr, "DNA batches: no cell dumps", true, nullptr, nullptr, { NO_WIDE, NO_WIDE },
                      false, cpecan_k_general5, X_CHARS, false, 248 },
     /* VANILLA */  { 3, CPECAN_EXPECTATIONV_LEN, 4, 0, nullptr, "vanilla batches: no cell dumps", true, &VV_BUILDS, nullptr,
-                     { { SYV_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS }, NO_WIDE }, true, cpecan_k_generalv, X_KIDX, true, 0 },
+                     { { SYV_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS }, { SYVE_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP } }, true,
+                     cpecan_k_generalv, X_KIDX, true, 0 },
     /* HDP */      { 3, CPECAN_EXPECTATIONH_LEN, 16, 0, nullptr, "HDP batches: no cell dumps", true, &HV_BUILDS, nullptr,
                      { { SYH_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS_HDP }, { SYHE_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP } }, true,
                      cpecan_k_generalh, X_KID, false, 0 },
@@ -252,7 +259,8 @@ static int check_machine(Machine machine, int mode, int flags) {
 struct BatchEnv {
     int wideFlags;    /* the wide-band flags whose variable is 1, for every batch whose machine and mode have wide builds
                          behind that flag: CPECAN_WIDE_BANDS (CPECAN_FLAG_WIDE_BANDS), CPECAN_WIDE_BANDS_HDP (.._HDP: HDP
-                         posterior batches), CPECAN_WIDE_BANDS_HDP_ESTEP (.._HDP_ESTEP: HDP batches of expectations) */
+                         posterior batches), CPECAN_WIDE_BANDS_HDP_ESTEP (.._HDP_ESTEP: HDP batches of expectations),
+                         CPECAN_WIDE_BANDS_VANILLA_ESTEP (.._VANILLA_ESTEP: vanilla batches of expectations) */
     bool waveKernels; /* false under CPECAN_KERNELS=systolic: the workgroup-per-alignment family for every batch */
     int systolicRows; /* CPECAN_SYSTOLIC_ROWS=N: a build of at least N rows (tests, timing) */
     int asmMode;      /* CPECAN_ASM: 0 the compiled kernels, 1 the assembly forward sweep only (the compiled sweep back
@@ -263,10 +271,11 @@ static BatchEnv read_batch_env() {
     static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr;
     const char *wide = getenv("CPECAN_WIDE_BANDS"), *kernels = getenv("CPECAN_KERNELS");
     const char *rows = getenv("CPECAN_SYSTOLIC_ROWS"), *as = getenv("CPECAN_ASM"), *wideH = getenv("CPECAN_WIDE_BANDS_HDP");
-    const char *wideHE = getenv("CPECAN_WIDE_BANDS_HDP_ESTEP");
+    const char *wideHE = getenv("CPECAN_WIDE_BANDS_HDP_ESTEP"), *wideVE = getenv("CPECAN_WIDE_BANDS_VANILLA_ESTEP");
     const int wideFlags = (wide && atoi(wide) == 1 ? CPECAN_FLAG_WIDE_BANDS : 0) |
                           (wideH && atoi(wideH) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP : 0) |
-                          (wideHE && atoi(wideHE) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP : 0);
+                          (wideHE && atoi(wideHE) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP : 0) |
+                          (wideVE && atoi(wideVE) == 1 ? CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP : 0);
     return { wideFlags, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1, as ? atoi(as) : -1, wave5Off };
 }
 
@@ -314,11 +323,11 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
                       : (q.flags & CPECAN_FLAG_GENERAL_KERNEL) ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
     if (unbanded && (q.mode != CPECAN_MODE_POSTERIOR || asked == CPECAN_KERNEL_SYSTOLIC))
         return refuse("un-banded alignment: posterior mode on the general kernel only");
-    /* the wide builds of the workgroup family are the strawMan machine's and the HDP machine's and, for the posterior
-     * decode, the vanilla machine's.  A machine's wide builds of a mode answer to the flag its row names for that mode
-     * (the HDP machine's to two of its own, one per mode) and each flag has its environment variable: a flag means
-     * nothing to the machines and modes of another flag or of none -- a vanilla E-step past the wave builds runs on the
-     * general kernel whatever the flags */
+    /* the wide builds of the workgroup family are the strawMan machine's, the HDP machine's and the vanilla machine's.
+     * A machine's wide builds of a mode answer to the flag its row names for that mode (the HDP machine's to two of its
+     * own, one per mode; the vanilla machine's E-step to one of its own) and each flag has its environment variable: a
+     * flag means nothing to the machines and modes of another flag or of none -- a vanilla E-step past the wave builds
+     * runs on the general kernel whatever the other three flags say */
     const MachineRow::Wide &wide = m.wide[q.mode];
     const bool wideServes = wide.builds != nullptr;
     if (wideServes) d.flags |= wide.flag & q.env.wideFlags;
@@ -327,8 +336,8 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
         const bool workgroup = m.workgroup && (!q.env.waveKernels || (q.flags & CPECAN_FLAG_WORKGROUP_KERNELS));
         const SweepFamily &fam = workgroup ? *m.workgroup : *m.wave;
         /* the machine's wide-bands flag: a band past the family's widest build goes to the narrowest wide build of the
-         * workgroup family that holds it (six or eight waves; four, six or eight for the vanilla machine), whichever
-         * family the batch would otherwise run on; a band the family holds is left to it */
+         * workgroup family that holds it (six or eight waves; four, six or eight for the vanilla machine, in either
+         * mode), whichever family the batch would otherwise run on; a band the family holds is left to it */
         const SweepBuild *wideBuild = nullptr;
         int reach = fam[3]->maxWidth;
         if (wideServes && (d.flags & wide.flag))

@@ -42,7 +42,8 @@
 /* this file is compiled once per SY_R (1..4 waves per workgroup: bands up to 56, 120, 184, 248 k-mers; 6 and 8 waves,
  * the wide builds of CPECAN_FLAG_WIDE_BANDS: 376 and 504); the symbols of the builds other than four carry _r1.._r3,
  * _r6, _r8.  With -DSY_VANILLA it is compiled three times more (4, 6 and 8 waves: _v4, _v6, _v8; see below), with
- * -DSY_HDP twice (_h6, _h8) and with -DSY_HDP -DSY_ESTEP twice again (_he6, _he8).  Every build holds the sweeps -- a
+ * -DSY_HDP twice (_h6, _h8), with -DSY_HDP -DSY_ESTEP twice again (_he6, _he8) and with -DSY_VANILLA -DSY_ESTEP three
+ * times (_ve4, _ve6, _ve8).  Every build holds the sweeps -- a
  * forward, a backward and, where the machine has its E-step here, an expectation kernel -- their launchers and one
  * SweepBuild record; what does not depend on the build (track, counts, the machines' records) is
  * cpecan_kernel_prep.hip's */
@@ -51,8 +52,8 @@
  * 248, 376 and 504 k-mers; symbols suffixed _v4, _v6, _v8).  A lane holds the 21 doubles of its k-mer's row of the
  * vanilla track (cpecan_k_wv_track_vanilla): two tables of Gaussian level and inverse-Gaussian noise
  * constants and the five log transition probabilities of the column's skip bin, so transitions are per lane, not
- * per wave; a_ym, a_yy and the end vector come from the model header.  The E-step of this machine stays on the general
- * kernel: these builds have no ring of backward cells and no expectation kernel. */
+ * per wave; a_ym, a_yy and the end vector come from the model header.  These builds have no ring of backward cells and
+ * no expectation kernel: the E-step of this machine at these widths is the _ve builds' (below). */
 /* -DSY_HDP: the forward sweep of the 3-state HDP signal machine (stateMachine3HDP_cellCalculate, impl/stateMachine.c:
  * 1338-1370) with six and eight waves per workgroup (bands of 249..376 and 377..504 k-mers; symbols suffixed _h6, _h8;
  * the HDP wave builds reach 248, so there is no four-wave build), posterior decode only.  One spline density of the
@@ -67,11 +68,17 @@
  * keeps every state of every diagonal, the sweep back parks its cells in the B ring, and the candidate lists and both
  * decodes fold away; cpecan_k_sy_expect is compiled in its HDP form (nine transitions and the likelihood, no k-mer bins,
  * event-to-k-mer assignments). */
+/* -DSY_VANILLA -DSY_ESTEP: the vanilla machine's E-step with four, six and eight waves per workgroup (bands of 185..248,
+ * 249..376 and 377..504 k-mers), in objects of their own (symbols suffixed _ve4, _ve6, _ve8; the _v4 / _v6 / _v8 objects
+ * keep their device code).  E-step only, as the _he builds: SY_MODE(P) is the constant 1.  This machine's E-step reads
+ * one backward value per cell, B.gapX, so the sweep back parks that one alone: a B ring of [diagonal][wave][lane], a
+ * third of the strawMan builds'.  cpecan_k_sy_expect is compiled in its vanilla form (30 + 30 skip bins and the
+ * likelihood: match -> gap X and gap X -> gap X, from the cell's lower neighbour). */
 #if defined(SY_HDP) && defined(SY_VANILLA)
 #error "SY_HDP and SY_VANILLA are builds of their own"
-#elif defined(SY_ESTEP) && !defined(SY_HDP)
-#error "SY_ESTEP: the E-step builds of the HDP machine (-DSY_HDP)"
-#elif defined(SY_ESTEP) && SY_R != 6 && SY_R != 8
+#elif defined(SY_ESTEP) && !defined(SY_HDP) && !defined(SY_VANILLA)
+#error "SY_ESTEP: the E-step builds of the HDP machine (-DSY_HDP) and of the vanilla machine (-DSY_VANILLA)"
+#elif defined(SY_ESTEP) && defined(SY_HDP) && SY_R != 6 && SY_R != 8
 #error "SY_HDP SY_ESTEP: 6 or 8 waves per workgroup"
 #elif defined(SY_HDP) && SY_R != 6 && SY_R != 8
 #error "SY_HDP: 6 or 8 waves per workgroup"
@@ -81,7 +88,9 @@
 #error "SY_R: 1, 2, 3, 4, 6 or 8 waves per workgroup"
 #endif
 /* a symbol's suffix: the machine's tag and the number of waves; the strawMan's four-wave build alone has none */
-#if defined(SY_ESTEP)
+#if defined(SY_ESTEP) && defined(SY_VANILLA)
+#define SY_SYM(n) SWEEP_SYM(n, ve, SY_R)
+#elif defined(SY_ESTEP)
 #define SY_SYM(n) SWEEP_SYM(n, he, SY_R)
 #elif defined(SY_HDP)
 #define SY_SYM(n) SWEEP_SYM(n, h, SY_R)
@@ -119,7 +128,11 @@
 #define SY_TR 16     /* first of the row's five log transition probabilities: a_mx, a_xx, a_mm, a_xm, a_my */
 #define SY_EVW 4     /* doubles per staged event: mean, noise, 1 / noise, log(noise) */
 #define SY_MODEL_DOUBLES ((long long) CP_VMODEL_STRIDE)
+#ifdef SY_ESTEP
+#define SY_MODE(P) 1 /* E-step only */
+#else
 #define SY_MODE(P) 0 /* posterior decode only */
+#endif
 #elif defined(SY_HDP)
 #define SY_ROW CP_ROW /* the strawMan track's row: entry 0 the k-mer's table row offset, entry CP_GAPX log(0.1) */
 #define SY_NPRM 1    /* a slot keeps the table row offset */
@@ -138,8 +151,14 @@
 #define SY_MODEL_DOUBLES ((long long) CP_MODEL_STRIDE)
 #define SY_MODE(P) (P).mode
 #endif
-#if defined(SY_VANILLA) || (defined(SY_HDP) && !defined(SY_ESTEP))
+#if (defined(SY_VANILLA) || defined(SY_HDP)) && !defined(SY_ESTEP)
 #define SY_NO_ESTEP /* these builds have no expectation kernel and no ring of backward cells */
+#endif
+/* per cell in the ring of backward cells: the three states, or the one the vanilla E-step reads (gap X) */
+#if defined(SY_VANILLA)
+#define SY_BRING_VALUES 1
+#else
+#define SY_BRING_VALUES 3
 #endif
 #define SY_PREFETCH 4     /* diagonals the backward sweep fetches ahead (== its unroll factor) */
 #define SY_CAND_SLACK 0.25 /* candidates: cells within this (log units) below the posterior threshold */
@@ -1156,10 +1175,15 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     /* Baum-Welch: the backward cell goes to its own ring for the expectation kernel
                      * (the emissions in slots 3, 4 stay: that kernel re-uses them) */
                     if (tvalid) {
-                        double *b = bring + (long long) (t & g.ringMask) * (SY_R * 3 * 64) + wave * (3 * 64) + lane;
+                        double *b = bring + (long long) (t & g.ringMask) * (SY_R * SY_BRING_VALUES * 64)
+                                    + wave * (SY_BRING_VALUES * 64) + lane;
+#ifdef SY_VANILLA
+                        b[0] = Bx; /* (all that machine's expectation kernel reads of the cell) */
+#else
                         b[0] = Bm;
                         b[64] = Bx;
                         b[128] = By;
+#endif
                     }
                 }
 #ifndef SY_ABLATE_FB
@@ -1591,7 +1615,7 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
                     (int2 *) (scratch + idx * scratchBytes + scratch_cand_offset(ringD)),
                     (double *) (scratch + idx * scratchBytes + scratch_cand_offset(ringD)
                                 + (long long) SY_R * SY_CAND_PER_DIAG * ringD * sizeof(int2)),
-                    Bring ? Bring + idx * ((long long) ringD * SY_R * 3 * 64) : nullptr
+                    Bring ? Bring + idx * ((long long) ringD * SY_R * SY_BRING_VALUES * 64) : nullptr
 #ifdef SY_VANILLA
                     , tf
 #endif
@@ -1604,8 +1628,94 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
     }
 }
 
-#ifndef SY_NO_ESTEP /* (the vanilla machine's E-step runs on the general kernel, the HDP machine's past 248 k-mers there or on
-                    * the _he builds of this kernel) */
+#if defined(SY_VANILLA) && !defined(SY_NO_ESTEP)
+/*
+ * The vanilla machine's expectations of the traceback window the backward kernel just swept (-DSY_VANILLA -DSY_ESTEP;
+ * diagonalCalculation_Expectations :841-863 with cell_signal_updateBetaAndAlphaProb :478-498): of all transitions only
+ * match -> gap X (into the skip bin of the cell's k-mer pair) and gap X -> gap X (bin + 30) are collected, both from the
+ * cell's lower neighbour; the gap-X emission of this machine is 0.  The arithmetic of cpecan_k_wv_expect_v*
+ * (cpecan_kernel_wave.hip), term for term, on this family's geometry: element-wise over the forward ring, the B ring
+ * (B.gapX alone) and the window's exact totals, SY_EXPECT_CHUNKS workgroups to a window.  A thread keeps the two sums of
+ * its column in registers and adds them to the column's bin (track row entry 21) when its slot moves on.
+ */
+extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
+    const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTab,
+    const double *__restrict__ track, const long long *__restrict__ trackBase,
+    const unsigned short *__restrict__ kidx, const double *__restrict__ models, const double *Fring,
+    long long ringDoubles, const double *Bring, int ringD, SyState *states, const char *scratch,
+    long long scratchBytes, double *expect, int window) {
+    __shared__ double sBins[64];
+    (void) P; (void) kidx; (void) models;
+    const long long idx = blockIdx.x;
+    if (idx >= nItems) return;
+    const SyState *state = states + idx;
+    /* gridDim.y workgroups share a window's diagonals, a contiguous run each; the state record is only read here (the
+     * backward kernel stamps it with the launch it belongs to) */
+    if (state->expectPending != window + 1) return;
+    const DevItem it = uniform_item(items[idx]);
+    const Geometry g = make_geometry(const_cast<double *>(Fring) + idx * ringDoubles, ringD);
+    const int lane = g.lane, wave = g.wave;
+    const double *bown = Bring + idx * ((long long) ringD * SY_R * SY_BRING_VALUES * 64) + wave * (SY_BRING_VALUES * 64) + lane;
+    const double *tr = track + trackBase[idx] * SY_ROW;
+    const int2 *tab = bandTab + it.diagBase;
+    const WinTotal *wtot = (const WinTotal *) (scratch + idx * scratchBytes + 2ll * ringD * sizeof(int));
+    const int dTop = uni(state->winTop), from = uni(state->winFrom), to = uni(state->winTo);
+    const int tPost0 = dTop < from ? dTop : from;
+    double *dst = expect + (long long) it.model * CP_EXPECTV_LEN;
+    if (threadIdx.x < 64) sBins[threadIdx.x] = 0.0;
+    __syncthreads();
+
+    double lik = 0.0, beta = 0.0, alpha = 0.0;
+    int col = -1; /* matrix column whose sums beta / alpha hold */
+    const int perChunk = (tPost0 - to + (int) gridDim.y - 1) / (int) gridDim.y;
+    const int tHi = tPost0 - (int) blockIdx.y * perChunk;             /* this workgroup: diagonals tHi .. tLo+1 */
+    const int tLo = tHi - perChunk > to ? tHi - perChunk : to;
+    if (tHi > to) {
+        int b0min, b0max, b1min, b1max;
+        band_load(tab, tHi, b0min, b0max);
+        int xs = wave * 64 + lane; /* this slot's k-mer: the one in (xmax-P, xmax] */
+        xs += ((b0min - xs + SY_P - 1) / SY_P) * SY_P;
+        if (xs > b0max) xs -= SY_P;
+#pragma unroll 1
+        for (int t = tHi; t > tLo; t--) {
+            band_load(tab, t - 1, b1min, b1max);
+            if (xs > b0max) xs -= SY_P;
+            const int x = xs;
+            const double total = wtot[(tPost0 - t) / 10].total;
+            if (threadIdx.x == 0) lik += total;
+            if (x >= b0min && x - 1 >= b1min && x - 1 <= b1max) { /* the cell (t, x) and its lower neighbour exist */
+                const double Bx = bown[(long long) (t & g.ringMask) * (SY_R * SY_BRING_VALUES * 64)];
+                const double l0 = *g.rpb(t - 1, 0), l1 = *g.rpb(t - 1, 1);
+                const double *row = tr + (long long) x * SY_ROW;
+                if (x != col) {
+                    if (col >= 0) {
+                        const int bin = (int) tr[(long long) col * SY_ROW + 21];
+                        atomicAdd(&sBins[bin], beta);
+                        atomicAdd(&sBins[bin + 30], alpha);
+                    }
+                    col = x;
+                    beta = alpha = 0.0;
+                }
+                beta += exp(l0 + Bx + (0 + row[16]) - total);
+                alpha += exp(l1 + Bx + (0 + row[17]) - total);
+            }
+            b0min = b1min; b0max = b1max;
+        }
+        if (col >= 0) {
+            const int bin = (int) tr[(long long) col * SY_ROW + 21];
+            atomicAdd(&sBins[bin], beta);
+            atomicAdd(&sBins[bin + 30], alpha);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 60 && sBins[threadIdx.x] != 0.0) atomicAdd(dst + threadIdx.x, sBins[threadIdx.x]);
+    if (threadIdx.x == 0 && lik != 0.0) atomicAdd(dst + 60, lik);
+}
+#endif
+
+#if !defined(SY_NO_ESTEP) && !defined(SY_VANILLA) /* (the vanilla machine's E-step past 184 k-mers runs on the general
+                    * kernel or on the _ve builds, in the form above; the HDP machine's past 248 k-mers on the general
+                    * kernel or on the _he builds) */
 /*
  * Baum-Welch expectations of the traceback window the backward kernel just swept
  * (diagonalCalculation_Expectations :841-863 with cell_signal_updateTransAndKmerSkipExpectations
@@ -1784,7 +1894,7 @@ extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_expect)(
     if (threadIdx.x == 0) atomicAdd(dst + 9 + 4096, lik);
 #endif
 }
-#endif /* !SY_NO_ESTEP */
+#endif /* !SY_NO_ESTEP && !SY_VANILLA */
 
 #ifdef SY_PROFILE
 extern "C" int SY_SYM(cpecan_systolic_prof_fetch)(unsigned long long *dst) {
@@ -1832,8 +1942,14 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 /* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
 extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
-#ifdef SY_VANILLA
-/* (no E-step on these builds: no expect launcher, no ring of backward cells; the dispatch keeps such batches away) */
+#if defined(SY_VANILLA) && defined(SY_ESTEP)
+/* (E-step only: the dispatch sends these builds no posterior batch; one backward value per cell in the B ring) */
+const SweepBuild SY_SYM(cpecan_systolic_build) = {
+    SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64,
+    SY_R * SY_BRING_VALUES * 64, sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, sy_launch_expect,
+    nullptr };
+#elif defined(SY_VANILLA)
+/* (no E-step on these builds: no expect launcher, no ring of backward cells; theirs are the _ve objects) */
 const SweepBuild SY_SYM(cpecan_systolic_build) = {
     SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
     sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };

@@ -226,7 +226,7 @@ typedef struct {
 
 #define CPECAN_KERNEL_AUTO 0
 #define CPECAN_KERNEL_GENERAL 1  /* any band width; diagonals live in HBM            */
-#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide (<= 504 with CPECAN_FLAG_WIDE_BANDS[_HDP[_ESTEP]]); register-resident wavefront */
+#define CPECAN_KERNEL_SYSTOLIC 2 /* band <= 248 k-mers wide (<= 504 with a CPECAN_FLAG_WIDE_BANDS* flag); register-resident wavefront */
 
 #define CPECAN_FLAG_DEBUG_DUMP 1 /* keep forward/backward cells for cpecan_hip_batch_debug_cells */
 #define CPECAN_FLAG_UNBANDED 2   /* getAlignedPairsWithoutBanding (:1512): full matrix, one traceback from
@@ -269,7 +269,8 @@ typedef struct {
                                       the same kernels with four, six or eight waves per workgroup (up to 248, 376, 504)
                                       unless it is un-banded or carries CPECAN_FLAG_GENERAL_KERNEL; a vanilla batch of
                                       CPECAN_MODE_EXPECTATIONS ignores the flag (its E-step past 184 k-mers runs on the
-                                      general kernel), and so does a vanilla batch that meets a k-mer that is none (see
+                                      general kernel, or with CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP on the E-step builds
+                                      of the same kernels), and so does a vanilla batch that meets a k-mer that is none (see
                                       cpecan_hip_batch_create_vanilla), and so do the other machines.  Same results bit
                                       for bit.  The
                                       environment variable CPECAN_WIDE_BANDS=1 (read per batch) sets it for every
@@ -307,6 +308,24 @@ typedef struct {
                                           libcpecan_host.so (cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels)
                                           and vanillaAlign.  One flag for the wide builds of every machine and mode is a
                                           follow-up: tests pin what the two older flags do not mean. */
+#define CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP 1024 /* cpecan_hip_batch_create_vanilla with CPECAN_FLAG_EXPECTATIONS only: a
+                                          batch whose widest band is 185..504 k-mers, past the vanilla machine's wave
+                                          builds, runs its E-step on the vanilla E-step builds of the
+                                          workgroup-per-alignment kernels with four, six or eight waves per workgroup (up
+                                          to 248, 376, 504: the forward sweep keeping every state, the sweep back leaving
+                                          B.gapX of its cells in a ring, one expectation kernel per window) instead of the
+                                          general kernel, unless it carries CPECAN_FLAG_GENERAL_KERNEL, has band edges
+                                          that step by more than one k-mer or meets a k-mer that is none (see
+                                          cpecan_hip_batch_create_vanilla; an un-banded E-step is refused as without the
+                                          flag).  A batch of narrower bands runs on the wave builds as without the flag,
+                                          one of wider bands on the general kernel as before.  A vanilla posterior batch
+                                          ignores the flag, and so do all other machines.  The 61 sums are atomic
+                                          additions of the same terms as on the other kernels and agree to rounding (as
+                                          between any two runs).  The environment variable
+                                          CPECAN_WIDE_BANDS_VANILLA_ESTEP=1 (read per batch) sets it for every vanilla
+                                          batch of expectations: the way in for callers of libcpecan_host.so
+                                          (cpecan_trainModels) and vanillaAlign.  It has a number of its own because
+                                          tests pin that 128, 256 and 512 mean nothing to a vanilla E-step. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -328,9 +347,11 @@ int cpecan_hip_batch_create_dna(cpecan_ctx *ctx, const cpecan_item *items, int64
 
 /* k-mers against events with a vanilla model (getAlignedPairsUsingAnchors with a StateMachine3Vanilla,
  * sequence_getKmer2 / sequence_getEvent): same buffers as cpecan_hip_batch_create, model_id is a
- * cpecan_hip_modelsv_create id.  flags: UNBANDED or EXPECTATIONS (general kernel), GENERAL_KERNEL, WIDE_BANDS.  There
- * is no kernel argument: the batch picks its kernels itself (the wave builds up to 184 k-mers of band, the general kernel
- * past that), and CPECAN_FLAG_WIDE_BANDS alone selects the workgroup builds for posterior batches of 185..504 k-mers.
+ * cpecan_hip_modelsv_create id.  flags: UNBANDED (general kernel, posterior decode only), EXPECTATIONS, GENERAL_KERNEL,
+ * WIDE_BANDS, WIDE_BANDS_VANILLA_ESTEP.  There is no kernel argument: the batch picks its kernels itself (the wave builds
+ * up to 184 k-mers of band, the general kernel past that), and the two wide-bands flags alone select the workgroup builds
+ * for bands of 185..504 k-mers: CPECAN_FLAG_WIDE_BANDS for the posterior decode, CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for
+ * the E-step.
  * One exception, whatever the flags: a batch in which any item has a character outside ACGT among its lX + 5, or fewer
  * than two k-mers (lX < 2: sequence_getKmer2 looks one k-mer ahead, past such an item's end), runs as a whole on the
  * general kernel.  The reference scores a k-mer that is none as NaN under this machine and NaN spreads through its
@@ -431,7 +452,7 @@ int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int3
  * hold the widest band of the batch: 1 (bands up to 56 k-mers), 2 (120), 3 (184) or 4 (248).  The fewer waves an
  * alignment takes, the more alignments a CU holds (16, 8, 5, 4).  With CPECAN_FLAG_WIDE_BANDS also 6 (bands of 249..376
  * k-mers) and 8 (377..504): the wide builds, two workgroups per CU; for a vanilla batch with that flag 4 (185..248), 6
- * and 8. */
+ * and 8, and the same three for a vanilla batch of expectations with CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP. */
 int cpecan_hip_batch_systolic_rows(cpecan_batch *batch, int32_t *rows);
 /* Register-resident path only: *wave = 1 if the batch runs on the wave-per-alignment kernels (rows is then the
  * number of cells a lane holds: 2, 3 or 4), 0 on the workgroup-per-alignment ones (rows = waves per workgroup).  For a

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Device code of the throughput kernels in two source trees, kernel for kernel: each build the Makefile makes of
-cpecan_kernel_systolic.hip (thirteen) and cpecan_kernel_wave.hip (eight), and the files around them that are compiled once
+cpecan_kernel_systolic.hip (sixteen) and cpecan_kernel_wave.hip (eight), and the files around them that are compiled once
 (cpecan_kernel_prep.hip, cpecan_kernel_general.hip, cpecan_kernel_generalh.hip and the two files of the C-ABI layer that
 have held the pack kernels, cpecan_hip.hip and cpecan_readback.hip; a unit is a file of csrc, and one that a tree lacks or
-that defines no kernel there counts for nothing), is compiled to gfx950 assembly in both trees (the Makefile's flags plus -S --cuda-device-only) and, per kernel name, the instructions between
+that defines no kernel there counts for nothing, and so does a build that a tree's source refuses with #error: the
+vanilla E-step builds before they existed), is compiled to gfx950 assembly in both trees (the Makefile's flags plus -S --cuda-device-only) and, per kernel name, the instructions between
 the label and the function's end and the resource lines of the metadata block are compared.  A kernel that moved to
 another file is compared with whichever parent build had it: the number of its function in the file, which the
 compiler puts into its local labels (.LBB<n>_), is taken out first.  A refactor of the host side, or one that moves
@@ -21,7 +22,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 SY, WV = "cpecan_kernel_systolic.hip", "cpecan_kernel_wave.hip"
 BUILDS = [(SY, ["-DSY_R=%d" % r]) for r in (1, 2, 3)] + [(SY, [])] + \
          [(SY, ["-DSY_R=%d" % r] + m) for m, rows in (([], (6, 8)), (["-DSY_VANILLA"], (4, 6, 8)),
-                                                     (["-DSY_HDP"], (6, 8)), (["-DSY_HDP", "-DSY_ESTEP"], (6, 8)))
+                                                     (["-DSY_HDP"], (6, 8)), (["-DSY_HDP", "-DSY_ESTEP"], (6, 8)),
+                                                     (["-DSY_VANILLA", "-DSY_ESTEP"], (4, 6, 8)))
           for r in rows] + \
          [(WV, ["-DWV_L=%d" % l] + m) for m, cells in (([], (2, 3, 4)), (["-DWV_HDP"], (2, 3, 4)),
                                                       (["-DWV_VANILLA"], (2, 3))) for l in cells] + \
@@ -37,9 +39,13 @@ def kernels(tree, unit, defs, work):
     if not os.path.exists(src):
         return {}
     out = os.path.join(work, "%s%s.s" % (unit[:-4], "".join(defs).replace("-D", "_").replace("=", "")))
-    subprocess.check_call([HIPCC] + FLAGS + defs + ["-I" + os.path.join(tree, "include"), "-I" + os.path.dirname(src),
-                                                    "-S", "--cuda-device-only", "-o", out, src],
-                          stderr=subprocess.DEVNULL)
+    r = subprocess.run([HIPCC] + FLAGS + defs + ["-I" + os.path.join(tree, "include"), "-I" + os.path.dirname(src),
+                                                 "-S", "--cuda-device-only", "-o", out, src],
+                       stderr=subprocess.PIPE, text=True)
+    if r.returncode != 0 and "#error" in r.stderr:
+        return {}
+    if r.returncode != 0:
+        raise subprocess.CalledProcessError(r.returncode, r.args, stderr=r.stderr)
     text = open(out).read()
     found = {}
     if "amdhsa.kernels:" not in text:
