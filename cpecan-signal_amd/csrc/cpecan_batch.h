@@ -39,7 +39,8 @@ struct cpecan_batch {
     DevBuf<double> events;
     DevBuf<double> Fstore, Bstore, dbgB;
     DevBuf<double> Bring; /* systolic Baum-Welch: backward cells of one window per item */
-    bool fused = false; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0): expectations summed
+    bool fused = false; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0) or, with
+                           CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, on the workgroup kernels' fused builds: expectations summed
                            inside the sweep back, no B ring, no expectation kernel */
     DevBuf<long long> pairs;
     DevBuf<double> pairLogp;

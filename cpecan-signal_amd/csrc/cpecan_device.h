@@ -101,7 +101,7 @@ struct DevParams {
                      two previous diagonals from there instead of HBM (0: band too wide, through HBM).  The backward
                      diagonals stay in HBM: with them in LDS too a CU holds three workgroups instead of five and the
                      batch runs slower (4.1 against 6.3 Gcells/s) */
-    int expectResweep; /* wave kernels, fused expectations (tests: the fallback's path): 1 every window swept back once
+    int expectResweep; /* fused expectations, wave kernels and the workgroup family's _f builds (tests: the fallback's path): 1 every window swept back once
                           more against the exact totals, 2 the windows with (item ^ window) odd, so that one launch has
                           items on both paths and one item alternates between them; 0 (and any other value) none forced */
 };

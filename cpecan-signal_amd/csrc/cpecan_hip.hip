@@ -66,7 +66,10 @@ W5_DECLARE(3)
  * Built with -DSY_HDP it gives the HDP machine's wide builds (_h6, _h8: bands of 249..376 and 377..504 k-mers, past the
  * HDP wave builds), which answer to a flag of their own, CPECAN_FLAG_WIDE_BANDS_HDP, again for the posterior decode only;
  * with -DSY_HDP -DSY_ESTEP the HDP machine's E-step at the same two widths (_he6, _he8: the sweeps in E-step form and the
- * HDP form of the expectation kernel), a table of its own that answers to CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP. */
+ * HDP form of the expectation kernel), a table of its own that answers to CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP.
+ * Built with -DSY_FUSED it gives the strawMan machine's E-step with the expectations summed inside the sweep back, at
+ * one to four waves (_f1.._f4): no choice of the dispatch's -- a strawMan batch of expectations that the dispatch put on
+ * the workgroup build of r waves runs on _f<r> instead when it carries CPECAN_FLAG_WORKGROUP_FUSED_ESTEP (new_batch). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
@@ -77,9 +80,14 @@ SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEE
 SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
 SWEEP_BUILD(cpecan_systolic_build_ve4) SWEEP_BUILD(cpecan_systolic_build_ve6) SWEEP_BUILD(cpecan_systolic_build_ve8)
+SWEEP_BUILD(cpecan_systolic_build_f1) SWEEP_BUILD(cpecan_systolic_build_f2) SWEEP_BUILD(cpecan_systolic_build_f3)
+SWEEP_BUILD(cpecan_systolic_build_f4)
 typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
+/* (the fused E-step of the build of as many waves in SY_BUILDS) */
+static SweepFamily SY_FUSED_BUILDS = { &cpecan_systolic_build_f1, &cpecan_systolic_build_f2, &cpecan_systolic_build_f3,
+                                       &cpecan_systolic_build_f4 };
 /* (a table of wide builds ends with a null entry) */
 static const SweepBuild *const SY_WIDE_BUILDS[3] = { &cpecan_systolic_build_r6, &cpecan_systolic_build_r8, nullptr };
 static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4, &cpecan_systolic_build_v6,
@@ -869,6 +877,17 @@ static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput 
     b->P.ldsWidth = 0; /* (set per launch by the kernels that use it) */
     b->P.expectResweep = 0;
     b->sy = d.build ? d.build : SY_BUILDS[3];
+    /* CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, or CPECAN_EXPECT_FUSED_WORKGROUP=1 (read per batch): a strawMan batch of
+     * expectations that the dispatch put on one of the workgroup family's four builds (bands up to 248 k-mers) sums its
+     * expectations inside the sweep back, on the fused build of as many waves.  Every other batch -- another machine
+     * or mode, the wave family, the six- and eight-wave builds, the general kernel -- runs what it runs without it. */
+    {
+        const char *fxw = getenv("CPECAN_EXPECT_FUSED_WORKGROUP");
+        const bool asked = (d.flags & CPECAN_FLAG_WORKGROUP_FUSED_ESTEP) || (fxw != nullptr && atoi(fxw) == 1);
+        if (asked && machine == STRAWMAN && in.mode == CPECAN_MODE_EXPECTATIONS && d.build)
+            for (int r = 0; r < 4; r++)
+                if (d.build == SY_BUILDS[r]) b->sy = SY_FUSED_BUILDS[r];
+    }
     if (d.build) b->trackRow = b->sy->once->trackRowDoubles;
     b->hItems = plan.items;
     return b;
@@ -1026,7 +1045,8 @@ static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &
      * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 (read per
      * batch) keeps the ring of backward cells and the expectation kernel */
     const char *fxEnv = getenv("CPECAN_EXPECT_FUSED");
-    if (b->mode == CPECAN_MODE_EXPECTATIONS && !(fxEnv != nullptr && atoi(fxEnv) == 0) && b->sy->backward_fx) {
+    /* (a fused build of the workgroup family, new_batch's choice, has no other form of the E-step) */
+    if (b->mode == CPECAN_MODE_EXPECTATIONS && b->sy->backward_fx && (!b->sy->expect || !(fxEnv != nullptr && atoi(fxEnv) == 0))) {
         b->fused = true;
         b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr ? atoi(getenv("CPECAN_EXPECT_RESWEEP")) : 0;
     }
@@ -1523,7 +1543,7 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
 
 int cpecan_hip_batch_expectation_pass(cpecan_batch *b, int32_t *fused) {
     if (!b || !fused) return fail(CPECAN_EINVAL, "bad argument");
-    *fused = b->fused ? 1 : 0; /* (set only where the wave kernels run the batch) */
+    *fused = b->fused ? 1 : 0; /* (the wave kernels' E-step, or the workgroup kernels' on their fused builds) */
     return CPECAN_OK;
 }
 

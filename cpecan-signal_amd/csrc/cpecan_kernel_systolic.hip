@@ -74,7 +74,19 @@
  * one backward value per cell, B.gapX, so the sweep back parks that one alone: a B ring of [diagonal][wave][lane], a
  * third of the strawMan builds'.  cpecan_k_sy_expect is compiled in its vanilla form (30 + 30 skip bins and the
  * likelihood: match -> gap X and gap X -> gap X, from the cell's lower neighbour). */
-#if defined(SY_HDP) && defined(SY_VANILLA)
+/* -DSY_FUSED: the strawMan machine's E-step with its expectations summed inside the sweep back, with one to four waves
+ * per workgroup, in objects of their own (symbols suffixed _f1.._f4; the _r1.._r3 and the unsuffixed objects keep their
+ * device code).  E-step only: SY_MODE(P) is the constant 1, so the forward sweep keeps every state of every diagonal.
+ * The sweep back fetches F.gapX and F.gapY of a row with its F.match and forms, per cell, the terms of
+ * diagonalCalculation_Expectations (see fx_terms in backward_window): no ring of backward cells, no expectation kernel.
+ * The terms are taken against the window's estimated total and kept per refresh segment (FxRecords); after phase T they
+ * are scaled to the exact totals and added to the model's sums (fx_finish), and a window whose estimate cannot be
+ * trusted is swept back once more, in the same launch, against the exact totals. */
+#if defined(SY_FUSED) && (defined(SY_HDP) || defined(SY_VANILLA) || defined(SY_ESTEP))
+#error "SY_FUSED: a build of the strawMan machine"
+#elif defined(SY_FUSED) && (SY_R < 1 || SY_R > 4)
+#error "SY_FUSED: 1 to 4 waves per workgroup"
+#elif defined(SY_HDP) && defined(SY_VANILLA)
 #error "SY_HDP and SY_VANILLA are builds of their own"
 #elif defined(SY_ESTEP) && !defined(SY_HDP) && !defined(SY_VANILLA)
 #error "SY_ESTEP: the E-step builds of the HDP machine (-DSY_HDP) and of the vanilla machine (-DSY_VANILLA)"
@@ -88,7 +100,9 @@
 #error "SY_R: 1, 2, 3, 4, 6 or 8 waves per workgroup"
 #endif
 /* a symbol's suffix: the machine's tag and the number of waves; the strawMan's four-wave build alone has none */
-#if defined(SY_ESTEP) && defined(SY_VANILLA)
+#if defined(SY_FUSED)
+#define SY_SYM(n) SWEEP_SYM(n, f, SY_R)
+#elif defined(SY_ESTEP) && defined(SY_VANILLA)
 #define SY_SYM(n) SWEEP_SYM(n, ve, SY_R)
 #elif defined(SY_ESTEP)
 #define SY_SYM(n) SWEEP_SYM(n, he, SY_R)
@@ -102,6 +116,8 @@
 #define SY_SYM(n) n
 #endif
 #if defined(SY_VANILLA) /* the vanilla row does not fit 128 VGPRs: whatever occupancy the allocation lands on */
+#define SY_BACKWARD_ATTR
+#elif defined(SY_FUSED) /* nor do the fused sweep's accumulators and wider fetch buffers: no occupancy is forced */
 #define SY_BACKWARD_ATTR
 #elif SY_R == 1 || SY_R == 8 /* the one-wave and the eight-wave backward kernel land on 129 VGPRs by themselves: hold
                             * them to four waves per SIMD (128; two eight-wave workgroups then share a CU) */
@@ -149,11 +165,27 @@
 #define SY_NPRM 17
 #define SY_EVW 2     /* doubles per staged event: mean, noise */
 #define SY_MODEL_DOUBLES ((long long) CP_MODEL_STRIDE)
+#ifdef SY_FUSED
+#define SY_MODE(P) 1 /* E-step only */
+#else
 #define SY_MODE(P) (P).mode
 #endif
-#if (defined(SY_VANILLA) || defined(SY_HDP)) && !defined(SY_ESTEP)
+#endif
+#if ((defined(SY_VANILLA) || defined(SY_HDP)) && !defined(SY_ESTEP)) || defined(SY_FUSED)
 #define SY_NO_ESTEP /* these builds have no expectation kernel and no ring of backward cells */
 #endif
+#ifdef SY_FUSED
+#define SY_FX true
+#else
+#define SY_FX false
+#endif
+/* SY_FXQ(...): arguments only the fused builds' fetch and step take (a row's F.gapX and F.gapY) */
+#ifdef SY_FUSED
+#define SY_FXQ(...) , __VA_ARGS__
+#else
+#define SY_FXQ(...)
+#endif
+#define SY_FX_EST_BOUND 30.0 /* nats an exact total may lie from the estimate the fused sums were taken against */
 /* per cell in the ring of backward cells: the three states, or the one the vanilla E-step reads (gap X) */
 #if defined(SY_VANILLA)
 #define SY_BRING_VALUES 1
@@ -212,6 +244,9 @@ struct Shared {
     int cnt[2][SY_R][2];     /* aligned-pair counts per wave, double-buffered */
     int item;
     int scan;                /* this window's posteriors must be decoded by the full scan */
+#ifdef SY_FUSED
+    int fxRedo;              /* this window's sums must be taken again, against the exact totals */
+#endif
 };
 
 /*
@@ -868,6 +903,89 @@ __device__ void forward_window(const DevItem &it, const DevParams &P, const int2
     }
 }
 
+#ifdef SY_FUSED
+__device__ __forceinline__ double uni_d(double v) {
+    return __hiloint2double(uni(__double2hiint(v)), uni(__double2loint(v)));
+}
+
+/*
+ * Fused Baum-Welch expectations (-DSY_FUSED): what the sweep back leaves per refresh segment of a window (the ten decoded
+ * diagonals that share one totalProbability), in the alignment's HBM scratch behind what sy_scratch_bytes counts:
+ *   tr  the eight transition sums of every wave, [segment][wave][8]
+ *   g   per slot two gap-X sums, [segment][A | B][slot]: B the sum of the slot's column at the segment's end, A that of
+ *       the column it held before, when the slot changed columns within the segment.  One change at most: a slot's
+ *       column steps by SY_P >= 64 and a band edge moves by at most one column per diagonal, so a second change would
+ *       need the band to travel SY_P columns within the segment's eleven diagonals
+ *   c   their matrix columns (-1: none)
+ * The sweep writes every record of every segment it closes, so nothing is left over from an earlier window or run.
+ */
+struct FxRecords {
+    double *tr, *g;
+    int *c;
+};
+static __host__ __device__ long long sy_fx_bytes(int ringD) {
+    return ((long long) ringD / 10 + 8) * (SY_R * 8 * sizeof(double) + 2 * SY_P * (sizeof(double) + sizeof(int)));
+}
+__device__ __forceinline__ FxRecords fx_records(char *base, int ringD) {
+    const long long nW = (long long) ringD / 10 + 8;
+    FxRecords f;
+    f.tr = (double *) base;
+    f.g = f.tr + nW * SY_R * 8;
+    f.c = (int *) (f.g + nW * 2 * SY_P);
+    return f;
+}
+/* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y into the model's nine transition sums (from * 3 + to) */
+#define SY_EXPECT_SLOTS { 0 * 3 + 1, 1 * 3 + 1, 2 * 3 + 1, 0 * 3 + 0, 1 * 3 + 0, 2 * 3 + 0, 0 * 3 + 2, 2 * 3 + 2 }
+
+/* A window's fused sums into the model's expectations (layout of cpecan_k_sy_expect's); the whole workgroup.  Segment
+ * k's sums were taken against the estimate and scale by exp(est - total_k), or, on the second sweep (exact), against
+ * total_k itself.  Threads 0-7 the transitions, thread 8 the likelihood (the exact total once per decoded diagonal,
+ * :849), every thread the gap-X sums of its slot, one atomic per column, into the bins of the columns' k-mers. */
+__device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal *wtot, const int nSeg, const int tPost0,
+                          const int to, const double est, const bool exact, double *expect,
+                          const unsigned short *__restrict__ kidx) {
+    double *dst = expect + (long long) it.model * (9 + 4096 + 1);
+    const unsigned short *kx = kidx + it.xOff;
+    const int slot[8] = SY_EXPECT_SLOTS;
+    const int tid = threadIdx.x;
+    if (tid < 8) {
+        double sum = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < nSeg; k++) {
+            double seg = 0.0;
+            for (int w = 0; w < SY_R; w++) seg += fx.tr[(k * SY_R + w) * 8 + tid];
+            sum += seg * (exact ? 1.0 : exp(est - wtot[k].total));
+        }
+        atomicAdd(dst + slot[tid], sum);
+    } else if (tid == 8) {
+        double lik = 0.0;
+#pragma unroll 1
+        for (int u = tPost0; u > to; u--) lik += wtot[(tPost0 - u) / 10].total;
+        atomicAdd(dst + 9 + 4096, lik);
+    }
+    int cur = -1;
+    double sum = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < nSeg; k++) {
+        const double f = exact ? 1.0 : exp(est - wtot[k].total);
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            const int col = fx.c[(k * 2 + r) * SY_P + tid];
+            const double v = fx.g[(k * 2 + r) * SY_P + tid];
+            if (col > 0 && v != 0.0) {
+                if (col != cur) {
+                    if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
+                    cur = col;
+                    sum = 0.0;
+                }
+                sum += f * v;
+            }
+        }
+    }
+    if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
+}
+#endif /* SY_FUSED */
+
 /*
  * Backward sweep + posterior decode of one traceback window (:921-992), in three phases:
  *  S  the sweep back: one anti-diagonal per iteration, cells and messages in registers.  It leaves
@@ -888,6 +1006,10 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                                 unsigned long long *msk, int2 *candKx, double *candFb, double *bring
 #ifdef SY_VANILLA
                                 , TransFeed &tf
+#endif
+#ifdef SY_FUSED
+                                , const FxRecords &fxo, double *expect, const unsigned short *__restrict__ kidx,
+                                const bool fxForce
 #endif
                                 ) {
     const Geometry g = make_geometry(ring, ringD);
@@ -914,6 +1036,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
     /* threshold 0: every in-band cell is a pair, one of exponent -inf too (exp(-inf) = 0 >= 0, :776-786), and the
      * candidates leave those out: the scan decodes the window, as in the wave kernels */
     if (threadIdx.x == 0) sh.scan = P.logThrSlack > CP_NEG_INF ? 0 : 1;
+#ifdef SY_FUSED
+    if (threadIdx.x == 0) sh.fxRedo = fxForce ? 1 : 0;
+#endif
     __syncthreads();
     /* Candidates for the posterior decode, collected by the sweep: a cell whose F.match + B.match
      * lies within SY_CAND_SLACK of the threshold, measured against an estimate of the window's
@@ -926,7 +1051,17 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
     double candThr = CP_NEG_INF, totEst = CP_NEG_INF;
 
     /* ------------------------------ phase S: the sweep back ------------------------------ */
+    /* (in the fused builds the sweep is a function that runs once or twice; exact: the second sweep of a window, its
+     * terms taken against the exact totals phase T left) */
+#ifdef SY_FUSED
+    auto sweep = [&](const bool exact) __attribute__((always_inline)) {
+        if (exact) { /* the band ring has moved down with the first sweep: back to the window's top */
+            band_stage(bf, bandTab, D, dTop - (SY_BAND_RING - 1), dTop);
+            __syncthreads();
+        }
+#else
     {
+#endif
         int bxmin, bxmax;                 /* band of diagonal t   */
         band_get(bf, dTop, bxmin, bxmax);
         int nxmin = bxmin, nxmax = bxmax; /* band of diagonal t+1 */
@@ -1006,16 +1141,123 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
          * that diagonal reads a fixed dummy line instead, and every value is masked when consumed
          * (only cells of the band are ever stored to the ring; other slots hold stale data).
          */
-        auto fetch = [&](const int tt, const bool want, double &f, double &pm, double &py)
+        auto fetch = [&](const int tt, const bool want, double &f, double &pm, double &py SY_FXQ(double &fx, double &fy))
                          __attribute__((always_inline)) {
             const double *p = want ? g.rp(tt, 0) : g.rw;
             f = p[0];
             pm = p[3 * 64];
             py = p[4 * 64];
+#ifdef SY_FUSED /* the fused E-step reads the row's two gap states too */
+            fx = p[1 * 64];
+            fy = p[2 * 64];
+#endif
         };
         int calcs = 0, nTotWin = 0;
         int xsN = xs; /* this slot's k-mer on diagonal t+1 */
-        auto step = [&](const int t, double &qF, double &qPm, double &qPy) __attribute__((always_inline)) {
+#ifdef SY_FUSED
+        /*
+         * The terms of diagonalCalculation_Expectations (:841-863 with cell_signal_updateTransAndKmerSkipExpectations
+         * :426-443), those cpecan_k_sy_expect forms from the two rings.  A slot that holds the forward cell (t, x) also
+         * holds, shifted down from the slot above or kept from the diagonal above, the backward half of every term that
+         * starts at that cell: of the cell (t+2, x+1) B.match and the match emission (middle block: hB, hP), of (t+1, x+1)
+         * B.gapX and the gap-X emission (lower block: rBx, rPx), of (t+1, x) the sums B.gapY + (gap-Y emission +
+         * transition) (upper block: Um, Uy) -- what the backward recurrence gathers from.  Each term is taken against the
+         * total of the diagonal of the cell it goes TO: the window's estimate, or on the second sweep the exact total of
+         * that diagonal's segment.  Sums per segment: eight per lane (ea), and the gap-X terms of the column the slot
+         * points at once more for that column's k-mer bin (gSum of column gCol = x + 1).
+         */
+        double ea[8]; /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
+#pragma unroll
+        for (int i = 0; i < 8; i++) ea[i] = 0.0;
+        double gSum = 0.0, refX = exact ? uni_d(ld_agent(&wtot[0].total)) : 0.0;
+        int gCol = -1, segAcc = 0;
+        const int fxSlot = wave * 64 + lane;
+        fxo.c[fxSlot] = -1; /* segment 0 has no A record yet */
+        auto fx_flush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                double v = ea[i];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+                if (lane == 0) fxo.tr[(segAcc * SY_R + wave) * 8 + i] = v;
+                ea[i] = 0.0;
+            }
+            fxo.g[(segAcc * 2 + 1) * SY_P + fxSlot] = gSum;
+            fxo.c[(segAcc * 2 + 1) * SY_P + fxSlot] = gCol;
+            fxo.c[(segAcc * 2 + 2) * SY_P + fxSlot] = -1; /* the next segment's A record */
+            gSum = 0.0;
+            segAcc++;
+            if (exact) refX = uni_d(ld_agent(&wtot[segAcc].total));
+        };
+        /* fM, fX, fY: the slot's forward cell on diagonal t (-inf outside the band), x its column, in: it is in the band;
+         * nMin..nMax the band of t+1.  Called with t+1 <= tPost0, before this diagonal's backward cell replaces what the
+         * slot holds of the two above. */
+        auto fx_terms = [&](const int t, const bool on, const int x, const bool in, const double fM, const double fX,
+                            const double fY, const double mB, const double mP, const double lB, const double lP,
+                            const double uM, const double uY, const int nMin, const int nMax)
+                            __attribute__((always_inline)) {
+            /* (second sweep only) a total of -inf or NaN: every term is NaN, as in the reference, and the terms must then
+             * be those the reference forms -- a cell of the band whose neighbour is in the band too, the gap Y -> gap X
+             * term included where the model has none (its transition is -inf) -- instead of one per slot */
+            if (t + 2 <= tPost0) { /* middle block of t+2 (skipped at the window's lowest diagonal: no forward[t-2]) */
+                const double ref = exact ? refX : totEst;
+                const bool nf = exact && !(ref > CP_NEG_INF);
+                if (on) {
+                    double p3 = exp(fM + mB + (mP + T[T_MATCH_CONTINUE]) - ref);
+                    double p4 = exp(fX + mB + (mP + T[T_MATCH_FROM_GAP_X]) - ref);
+                    double p5 = exp(fY + mB + (mP + T[T_MATCH_FROM_GAP_Y]) - ref);
+                    if (nf) {
+                        int cMin, cMax;
+                        band_load(bandTab, t + 2, cMin, cMax);
+                        const bool ok = in && x + 1 >= cMin && x + 1 <= cMax;
+                        p3 = ok ? p3 : 0.0;
+                        p4 = ok ? p4 : 0.0;
+                        p5 = ok ? p5 : 0.0;
+                    }
+                    ea[3] += p3;
+                    ea[4] += p4;
+                    ea[5] += p5;
+                }
+                if ((tPost0 - (t + 2)) % 10 == 9) fx_flush(); /* t+2 ends its segment */
+            }
+            if (on) { /* lower and upper blocks of t+1 */
+                const double ref = exact ? refX : totEst;
+                const bool nf = exact && !(ref > CP_NEG_INF);
+                double p0 = exp(fM + lB + (lP + T[T_GAP_OPEN_X]) - ref);
+                double p1 = exp(fX + lB + (lP + T[T_GAP_EXTEND_X]) - ref);
+                double p2 = hasSwitchX ? exp(fY + lB + (lP + T[T_GAP_SWITCH_TO_X]) - ref) : 0.0;
+                double p6 = exp(fM + uM - ref);
+                double p7 = exp(fY + uY - ref);
+                const bool inL = in && x + 1 >= nMin && x + 1 <= nMax; /* the cell (t+1, x+1) exists */
+                if (nf) {
+                    const bool inU = in && x >= nMin && x <= nMax;     /* the cell (t+1, x) */
+                    p0 = inL ? p0 : 0.0;
+                    p1 = inL ? p1 : 0.0;
+                    p2 = inL ? (hasSwitchX ? p2 : exp(CP_NEG_INF - ref)) : 0.0;
+                    p6 = inU ? p6 : 0.0;
+                    p7 = inU ? p7 : 0.0;
+                }
+                ea[0] += p0;
+                ea[1] += p1;
+                if (hasSwitchX || nf) ea[2] += p2;
+                if (inL && x + 1 != gCol) { /* the slot points at another column than before */
+                    if (gSum != 0.0) {
+                        fxo.g[(segAcc * 2) * SY_P + fxSlot] = gSum;
+                        fxo.c[(segAcc * 2) * SY_P + fxSlot] = gCol;
+                    }
+                    gSum = 0.0;
+                    gCol = x + 1;
+                }
+                gSum += p0;
+                gSum += p1;
+                if (hasSwitchX || nf) gSum += p2;
+                ea[6] += p6;
+                ea[7] += p7;
+            }
+        };
+#endif
+        auto step = [&](const int t, double &qF, double &qPm, double &qPy SY_FXQ(double &qFx, double &qFy))
+                        __attribute__((always_inline)) {
             const bool active = row_active(wave, bxmin, bxmax);
             const bool activeN = row_active(wave, nxmin, nxmax);
             if (t < dTop) {
@@ -1024,8 +1266,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             }
             const bool vt = xs >= bxmin;
             const double fMc = vt ? qF : CP_NEG_INF, pmc = vt ? qPm : 0.0, pyc = vt ? qPy : 0.0;
+#ifdef SY_FUSED
+            const double fXc = vt ? qFx : CP_NEG_INF, fYc = vt ? qFy : CP_NEG_INF;
+#endif
             /* the slot's k-mer SY_PREFETCH diagonals down is xs or out of band (bands <= SY_P - 2 * depth) */
-            fetch(t - SY_PREFETCH, xs >= bxmin - SY_PREFETCH, qF, qPm, qPy);
+            fetch(t - SY_PREFETCH, xs >= bxmin - SY_PREFETCH, qF, qPm, qPy SY_FXQ(qFx, qFy));
             if (t < dTop) {
                 lds_barrier();
                 const double *xa = sh.xch[(t + 1) & 1][g.waveAbove];
@@ -1058,6 +1303,10 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     if (SY_WAVE_OF(xinB) == wave) pxReg = set_lane(pxReg, xinB & 63, v);
                     xinB--;
                 }
+#endif
+#ifdef SY_FUSED
+                if (t + 1 <= tPost0)
+                    fx_terms(t, active, xs, bvalid, fMc, fXc, fYc, hB, hP, rBx, rPx, Um, Uy, nxmin, nxmax);
 #endif
                 BmPrev = Bm;
                 tvalid = bvalid;
@@ -1107,7 +1356,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
 
             if (t <= tracedBackFrom) {
                 const double fb = fMc + Bm;
+#ifdef SY_FUSED
+                if (calcs++ % 10 == 0 && !exact) { /* (the second sweep of a window has its totals) */
+#else
                 if (calcs++ % 10 == 0) {
+#endif
                     /* per-cell terms of diagonalCalculationTotalProbability (:736-754), folded in
                      * phase T: v = cell_dotProduct(forward[t], backward[t]) (:391-397) ... */
                     const bool second = t + 1 <= dTop;
@@ -1173,8 +1426,8 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                  * refresh at its lowest diagonal reads forward[tracedBackFrom], :944,:985) */
                 if (SY_MODE(P) != 0) {
                     /* Baum-Welch: the backward cell goes to its own ring for the expectation kernel
-                     * (the emissions in slots 3, 4 stay: that kernel re-uses them) */
-                    if (tvalid) {
+                     * (the emissions in slots 3, 4 stay: that kernel re-uses them); the fused E-step has used it */
+                    if (tvalid && !SY_FX) {
                         double *b = bring + (long long) (t & g.ringMask) * (SY_R * SY_BRING_VALUES * 64)
                                     + wave * (SY_BRING_VALUES * 64) + lane;
 #ifdef SY_VANILLA
@@ -1210,12 +1463,15 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             if (t - 2 >= tracedBackTo) band_get(bf, t - 2, pxmin, pxmax);
         };
         double q0F, q0Pm, q0Py, q1F, q1Pm, q1Py, q2F, q2Pm, q2Py, q3F, q3Pm, q3Py;
+#ifdef SY_FUSED
+        double q0Fx, q0Fy, q1Fx, q1Fy, q2Fx, q2Fy, q3Fx, q3Fy;
+#endif
         {
             const bool want = xs >= bxmin - SY_PREFETCH;
-            fetch(dTop, want, q0F, q0Pm, q0Py);
-            fetch(dTop - 1, want, q1F, q1Pm, q1Py);
-            fetch(dTop - 2, want, q2F, q2Pm, q2Py);
-            fetch(dTop - 3, want, q3F, q3Pm, q3Py);
+            fetch(dTop, want, q0F, q0Pm, q0Py SY_FXQ(q0Fx, q0Fy));
+            fetch(dTop - 1, want, q1F, q1Pm, q1Py SY_FXQ(q1Fx, q1Fy));
+            fetch(dTop - 2, want, q2F, q2Pm, q2Py SY_FXQ(q2Fx, q2Fy));
+            fetch(dTop - 3, want, q3F, q3Pm, q3Py SY_FXQ(q3Fx, q3Fy));
         }
         int t = dTop, bandLo = dTop - (SY_BAND_RING - 1); /* lowest diagonal whose band is staged */
 #pragma unroll 1
@@ -1232,22 +1488,45 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 }
 #endif
             }
-            step(t, q0F, q0Pm, q0Py);
-            step(t - 1, q1F, q1Pm, q1Py);
-            step(t - 2, q2F, q2Pm, q2Py);
-            step(t - 3, q3F, q3Pm, q3Py);
+            step(t, q0F, q0Pm, q0Py SY_FXQ(q0Fx, q0Fy));
+            step(t - 1, q1F, q1Pm, q1Py SY_FXQ(q1Fx, q1Fy));
+            step(t - 2, q2F, q2Pm, q2Py SY_FXQ(q2Fx, q2Fy));
+            step(t - 3, q3F, q3Pm, q3Py SY_FXQ(q3Fx, q3Fy));
         }
         /* the last diagonals of the window (fewer than the prefetch depth): fetched on the spot */
 #pragma unroll 1
         for (; t > tracedBackTo; t--) {
-            double f, pm, py;
-            fetch(t, true, f, pm, py);
-            step(t, f, pm, py);
+            double f, pm, py SY_FXQ(fx, fy);
+            fetch(t, true, f, pm, py SY_FXQ(fx, fy));
+            step(t, f, pm, py SY_FXQ(fx, fy));
         }
+#ifdef SY_FUSED
+        if (tPost0 > tracedBackTo) {
+            /* the terms that start at the forward cells of tracedBackTo, the diagonal below the window: lower and upper
+             * block of the window's lowest diagonal, middle block of the one above it (the bands have moved on: bxmin ..
+             * bxmax is that diagonal's, nxmin .. nxmax the lowest decoded one's) */
+            if (xs > bxmax) xs -= SY_P;
+            const bool vt = xs >= bxmin;
+            double f, pm, py, fx, fy;
+            fetch(tracedBackTo, vt, f, pm, py, fx, fy);
+            lds_barrier();
+            const double *xa = sh.xch[(tracedBackTo + 1) & 1][g.waveAbove];
+            const double rBx = shl1(xa[0], Bx), rPx = shl1(xa[1], pxReg);
+            fx_terms(tracedBackTo, row_active(wave, bxmin, bxmax), xs, vt, vt ? f : CP_NEG_INF, vt ? fx : CP_NEG_INF,
+                     vt ? fy : CP_NEG_INF, hB, hP, rBx, rPx, Um, Uy, nxmin, nxmax);
+            fx_flush();
+        }
+#endif
+#ifdef SY_FUSED
+        if (!exact) sh.item = nTotWin;
+    };
+    sweep(false);
+#else
         sh.item = nTotWin;
         if (lane == 0) sh.cnt[1][wave][0] = nCand;
         if (nCand > candCap) sh.scan = 1;
     }
+#endif
     __syncthreads(); /* the ring rows written above are read by other waves below */
     const int nTotWin = sh.item;
 
@@ -1282,6 +1561,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             if (w.second) tot = ladd(acc, sh.vbuf[threadIdx.x + 1], cf);
             wtot[k >> 1].total = tot;
             if (!(fabs(tot - totEst) <= SY_CAND_SLACK)) sh.scan = 1; /* also catches NaN and infinities */
+#ifdef SY_FUSED
+            if (!(fabs(tot - totEst) <= SY_FX_EST_BOUND)) sh.fxRedo = 1;
+#endif
             const long long o = out.nTot + (k >> 1);
             if (o < out.totCap) {
                 out.totXay[o] = w.t;
@@ -1291,6 +1573,18 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
     }
     out.nTot += nTotWin;
     __syncthreads();
+#ifdef SY_FUSED
+    /* the window's sums into the model's: scaled from the estimate, or taken once more against the exact totals where
+     * the estimate is not finite or lies more than SY_FX_EST_BOUND from one of them (or the caller forces it) */
+    if (nPost > 0) {
+        const bool redo = sh.fxRedo != 0;
+        if (redo) {
+            sweep(true);
+            __syncthreads();
+        }
+        fx_finish(it, fxo, wtot, nTotWin, tPost0, tracedBackTo, totEst, redo, expect, kidx);
+    }
+#endif
 
     BPROF(2)
     /* ------------------------------ phase D: the aligned pairs ------------------------------ */
@@ -1553,6 +1847,10 @@ static __host__ __device__ long long scratch_cand_offset(int ringD) {
            + (long long) SY_MSK * ringD * sizeof(unsigned long long);
 }
 
+static __host__ __device__ long long scratch_end_offset(int ringD) {
+    return scratch_cand_offset(ringD) + (long long) SY_R * SY_CAND_PER_DIAG * ringD * (sizeof(int2) + sizeof(double));
+}
+
 /* One workgroup per alignment: forward sweep up to its next traceback point. */
 extern "C" __global__ __launch_bounds__(SY_P) void SY_SYM(cpecan_k_sy_forward)(
     const DevItem *__restrict__ items, long long nItems, DevParams P,
@@ -1581,7 +1879,11 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
     const int2 *__restrict__ bandTab, const double *__restrict__ track,
     const long long *__restrict__ trackBase, const double *__restrict__ models, double *Fring,
     long long ringDoubles, int ringD, SyState *states, long long *pairs, double *pairLogp,
-    long long *totXay, double *totVal, char *scratch, long long scratchBytes, double *Bring, int window) {
+    long long *totXay, double *totVal, char *scratch, long long scratchBytes, double *Bring, int window
+#ifdef SY_FUSED
+    , const unsigned short *__restrict__ kidx, double *expect
+#endif
+    ) {
     __shared__ Shared sh;
     __shared__ BandFeed bf;
 #ifdef SY_VANILLA
@@ -1619,12 +1921,18 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
 #ifdef SY_VANILLA
                     , tf
 #endif
+#ifdef SY_FUSED
+                    /* (DevParams::expectResweep: 1 every window down the second sweep, 2 those whose item and window
+                     * parity differ) */
+                    , fx_records(scratch + idx * scratchBytes + scratch_end_offset(ringD), ringD), expect, kidx,
+                    P.expectResweep == 1 || (P.expectResweep == 2 && ((idx ^ window) & 1))
+#endif
                     );
     if (threadIdx.x == 0) {
         state->nPairs = out.nPairs;
         state->nTot = out.nTot;
         state->winValid = 0;
-        state->expectPending = SY_MODE(P) != 0 ? window + 1 : 0; /* which launch's window the B ring holds */
+        state->expectPending = SY_MODE(P) != 0 && !SY_FX ? window + 1 : 0; /* which launch's window the B ring holds */
     }
 }
 
@@ -1906,8 +2214,7 @@ extern "C" int SY_SYM(cpecan_systolic_prof_fetch)(unsigned long long *dst) {
 /* HBM scratch per alignment: a hit count and an output offset per ring diagonal, and per refresh of the window one
  * WinTotal and the two rows of per-cell terms */
 static long long sy_scratch_bytes(int ringD) {
-    return scratch_cand_offset(ringD)
-           + (long long) SY_R * SY_CAND_PER_DIAG * ringD * (sizeof(int2) + sizeof(double));
+    return scratch_end_offset(ringD);
 }
 
 /* Launchers of the per-window stages of one pass over a batch (the C-ABI layer sequences them: the machine's track
@@ -1923,7 +2230,11 @@ static int sy_launch_backward(hipStream_t stream, const SweepArgs &a, int window
     hipLaunchKernelGGL(SY_SYM(cpecan_k_sy_backward), dim3((unsigned) a.nItems), dim3(SY_P), 0, stream, a.items, a.nItems,
                        a.P, a.bandTab, a.track, a.trackBase, a.models, a.Fring, a.ringDoubles, a.ringD,
                        (SyState *) a.states, a.pairs, a.pairLogp, a.totXay, a.totVal, a.scratch, a.scratchBytes, a.Bring,
-                       window);
+                       window
+#ifdef SY_FUSED
+                       , a.kidx, a.expect
+#endif
+                       );
     return sy_status();
 }
 #ifndef SY_NO_ESTEP
@@ -1942,7 +2253,13 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 /* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
 extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
-#if defined(SY_VANILLA) && defined(SY_ESTEP)
+#if defined(SY_FUSED)
+/* (E-step only, and only for a batch that asks for it: cpecan_hip.hip puts the build in the place of the one of as many
+ * waves that the dispatch chose; no ring of backward cells, no expect launcher, the segment records behind the scratch) */
+const SweepBuild SY_SYM(cpecan_systolic_build) = {
+    SY_R, false, SWEEP_STRAWMAN, &cpecan_systolic_machine, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
+    sy_scratch_bytes, sy_fx_bytes, sy_launch_forward, sy_launch_backward, sy_launch_backward, nullptr, nullptr };
+#elif defined(SY_VANILLA) && defined(SY_ESTEP)
 /* (E-step only: the dispatch sends these builds no posterior batch; one backward value per cell in the B ring) */
 const SweepBuild SY_SYM(cpecan_systolic_build) = {
     SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64,

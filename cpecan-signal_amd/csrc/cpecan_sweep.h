@@ -127,7 +127,7 @@ enum { SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA };
 
 /* One compiled build of the throughput kernels, defined next to them (cpecan_kernel_systolic.hip: cpecan_systolic_build
  * and _r1.._r3, _r6, _r8, the vanilla machine's _v4, _v6, _v8 and, for its E-step, _ve4, _ve6, _ve8, the HDP machine's
- * _h6, _h8 and, for its E-step, _he6, _he8;
+ * _h6, _h8 and, for its E-step, _he6, _he8, the strawMan machine's fused E-step _f1.._f4;
  * cpecan_kernel_wave.hip: cpecan_wave_build_l2.._l4, _h2.._h4, _v2, _v3) */
 struct SweepBuild {
     int rows;    /* waves per workgroup (workgroup family) or cells per lane (wave family) */
@@ -141,7 +141,8 @@ struct SweepBuild {
     long long (*fx_scratch_bytes)(int ringD); /* ... and what fused expectations add behind it (null: none) */
     SweepLaunch forward;
     SweepLaunch backward;    /* the sweep back of a window and what follows it (totals, decode, re-sweep) */
-    SweepLaunch backward_fx; /* the E-step with the expectations summed inside the sweep back (null: none) */
+    SweepLaunch backward_fx; /* the E-step with the expectations summed inside the sweep back (null: none; the wave
+                                builds of the strawMan machine, and the workgroup family's _f builds, which have no other) */
     SweepLaunch expect;      /* the E-step from the ring of backward cells */
     SweepLaunch post_asm;    /* what follows the assembly sweep back of a window (null: no assembly sweeps) */
 };

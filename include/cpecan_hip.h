@@ -326,6 +326,32 @@ typedef struct {
                                           batch of expectations: the way in for callers of libcpecan_host.so
                                           (cpecan_trainModels) and vanillaAlign.  It has a number of its own because
                                           tests pin that 128, 256 and 512 mean nothing to a vanilla E-step. */
+#define CPECAN_FLAG_WORKGROUP_FUSED_ESTEP 2048 /* cpecan_hip_batch_create (strawMan machine) with
+                                          CPECAN_MODE_EXPECTATIONS only: a batch that runs on the workgroup-per-alignment
+                                          kernels with one to four waves per workgroup (CPECAN_FLAG_WORKGROUP_KERNELS or
+                                          CPECAN_KERNELS=systolic, bands up to 248 k-mers) sums its Baum-Welch
+                                          expectations inside the sweep back, on the fused build of as many waves
+                                          (cpecan_k_sy_backward_f1.._f4), as the wave kernels do by default: no ring of
+                                          backward cells (ring diagonals x waves x 3 x 64 doubles per alignment), no
+                                          expectation kernel.  The terms of a window are taken against an estimate of
+                                          its total and scaled to the exact totals after the sweep; a window whose
+                                          estimate is not finite or lies more than 30 nats from one of them is swept
+                                          back once more in the same launch (CPECAN_EXPECT_RESWEEP=1 sends every window
+                                          there, =2 every other one: tests).  The kernel choice does not change:
+                                          cpecan_hip_plan_dispatch answers what it answers without the flag, and every
+                                          other batch -- a posterior batch, another machine, the wave kernels, the six-
+                                          and eight-wave builds of CPECAN_FLAG_WIDE_BANDS, the general kernel -- ignores
+                                          it.  The sums are those of the other E-step paths to rounding (the same terms
+                                          in another order, scaled once per segment of ten diagonals), NaN in the same
+                                          places.  Opt-in: the fused sweep back holds 174-177 VGPRs against 125-127, so
+                                          two waves run per SIMD where four did.  Measured: a batch
+                                          alone runs 1.02x, 1.11x and 1.36x as fast at two, three and four waves per
+                                          workgroup, bench.py --mode em 1.05x (four and two contexts, three waves) --
+                                          and SLOWER, 0.90x, at one wave per workgroup (bands up to 56 k-mers): leave
+                                          the flag off for such batches.  The environment
+                                          variable CPECAN_EXPECT_FUSED_WORKGROUP=1 (read per batch) sets it for every
+                                          strawMan batch of expectations: the way in for callers of libcpecan_host.so
+                                          (cpecan_trainModels) and for em.PersistentEStep. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -464,9 +490,11 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *batch, int32_t *wave);
  * the compiled kernels.  CPECAN_ASM=0 in the environment keeps every batch on the compiled kernels.  A batch planned for
  * them whose setup launch failed runs on the compiled kernels: 0, and last_error says why. */
 int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
-/* *fused = 1 if the batch's E-step sums its Baum-Welch expectations inside the sweep back of the wave kernels (the
- * strawMan machine, not the workgroup kernels; CPECAN_EXPECT_FUSED=0 in the environment when the batch is created opts out):
- * no ring of backward cells, no expectation kernel.  0 for the ring-of-backward-cells path and for posterior batches. */
+/* *fused = 1 if the batch's E-step sums its Baum-Welch expectations inside the sweep back: the strawMan machine on the
+ * wave kernels (CPECAN_EXPECT_FUSED=0 in the environment when the batch is created opts out) and, with
+ * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP=1, on the workgroup kernels of one to four waves
+ * (cpecan_hip_batch_kernel_family tells which): no ring of backward cells, no expectation kernel.  0 for the
+ * ring-of-backward-cells path and for posterior batches. */
 int cpecan_hip_batch_expectation_pass(cpecan_batch *batch, int32_t *fused);
 /* Systolic path only: HIP-event time of the last run spent in the forward-window kernels and in
  * the backward-window kernels (each launched `launches_each` times, once per traceback window). */
