@@ -48,28 +48,22 @@ W5_DECLARE(1)
 W5_DECLARE(2)
 W5_DECLARE(3)
 
-/* The builds of the throughput kernels (SweepBuild, cpecan_sweep.h), each defined next to its kernels: the workgroup
- * family with 1..4 waves per workgroup (bands up to 56, 120, 184, 248 k-mers; the narrower the band, the more
- * alignments are resident per CU); the wave family with 2..4 cells per lane for the strawMan (_l) and the HDP (_h)
- * machine, 2 and 3 for the vanilla machine (_v: four cells per lane do not fit its register file without spilling, so
- * that build does not exist and bands above 184 k-mers run on the general kernel).  A table is indexed by the rows a
- * band of that width asks for, minus one; a one-cell-per-lane build would only serve bands below 57 k-mers, which the
- * two-cell build takes too.  The workgroup family's source also builds six and eight waves per workgroup (bands up to
- * 376 and 504 k-mers): the wide builds, a table of their own, which a strawMan batch reaches only with
- * CPECAN_FLAG_WIDE_BANDS and only when its widest band is past every build of the tables above.  The same source built
- * with -DSY_VANILLA gives the vanilla machine's wide builds (_v4, _v6, _v8: four, six and eight waves per workgroup,
- * bands up to 248, 376 and 504 k-mers; their table starts one class earlier because the vanilla wave builds end at 184),
- * reached the same way and for the posterior decode only; with -DSY_VANILLA -DSY_ESTEP the vanilla machine's E-step at
- * the same three widths (_ve4, _ve6, _ve8: the sweeps in E-step form, a B ring of one value per cell and the vanilla form
- * of the expectation kernel), a table of its own that answers to CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP -- without that
- * flag a vanilla E-step past 184 k-mers stays on the general kernel.
- * Built with -DSY_HDP it gives the HDP machine's wide builds (_h6, _h8: bands of 249..376 and 377..504 k-mers, past the
- * HDP wave builds), which answer to a flag of their own, CPECAN_FLAG_WIDE_BANDS_HDP, again for the posterior decode only;
- * with -DSY_HDP -DSY_ESTEP the HDP machine's E-step at the same two widths (_he6, _he8: the sweeps in E-step form and the
- * HDP form of the expectation kernel), a table of its own that answers to CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP.
- * Built with -DSY_FUSED it gives the strawMan machine's E-step with the expectations summed inside the sweep back, at
- * one to four waves (_f1.._f4): no choice of the dispatch's -- a strawMan batch of expectations that the dispatch put on
- * the workgroup build of r waves runs on _f<r> instead when it carries CPECAN_FLAG_WORKGROUP_FUSED_ESTEP (new_batch). */
+/* The builds of the throughput kernels (SweepBuild, cpecan_sweep.h), each defined next to its kernels.  Which builds
+ * exist, and what each is compiled with, is the Makefile's list (SY_BUILDS, WV_BUILDS: make print-builds); the
+ * declarations and tables below say which build serves which band.
+ * A family's table is indexed by the rows a band of that width asks for, minus one: the workgroup family with 1..4 waves
+ * per workgroup (bands up to 56, 120, 184, 248 k-mers; the narrower the band, the more alignments are resident per CU),
+ * the wave family with 2..4 cells per lane (a one-cell build would only serve bands below 57 k-mers, which the two-cell
+ * build takes too; the vanilla machine has no four-cell build, it spills: its bands above 184 k-mers run on the general
+ * kernel).  A table of wide builds (six and eight waves per workgroup: bands up to 376 and 504 k-mers; the vanilla
+ * tables start at four waves, because the vanilla wave builds end at 184) is reached only when the batch's widest band
+ * is past every build of the tables above and the batch carries the table's flag: CPECAN_FLAG_WIDE_BANDS for the
+ * strawMan machine (_r) and the vanilla machine's posterior decode (_v), CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for the
+ * vanilla E-step (_ve; without it that E-step stays on the general kernel), CPECAN_FLAG_WIDE_BANDS_HDP for the HDP
+ * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f: the
+ * strawMan E-step summed inside the sweep back) are no choice of the dispatch's: a strawMan batch of expectations that
+ * the dispatch put on the workgroup build of r waves runs on _f<r> instead when it carries
+ * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP (new_batch). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)

@@ -39,14 +39,11 @@
 #define SY_R 4 /* waves per workgroup: 4 (bands up to 248 k-mers) or 3 (up to 184; five workgroups fit a CU) */
 #endif
 #define SY_P (64 * SY_R)
-/* this file is compiled once per SY_R (1..4 waves per workgroup: bands up to 56, 120, 184, 248 k-mers; 6 and 8 waves,
- * the wide builds of CPECAN_FLAG_WIDE_BANDS: 376 and 504); the symbols of the builds other than four carry _r1.._r3,
- * _r6, _r8.  With -DSY_VANILLA it is compiled three times more (4, 6 and 8 waves: _v4, _v6, _v8; see below), with
- * -DSY_HDP twice (_h6, _h8), with -DSY_HDP -DSY_ESTEP twice again (_he6, _he8) and with -DSY_VANILLA -DSY_ESTEP three
- * times (_ve4, _ve6, _ve8).  Every build holds the sweeps -- a
- * forward, a backward and, where the machine has its E-step here, an expectation kernel -- their launchers and one
- * SweepBuild record; what does not depend on the build (track, counts, the machines' records) is
- * cpecan_kernel_prep.hip's */
+/* this file is compiled once per build of the Makefile's list (SY_BUILDS, and once with neither -DSY_R nor a suffix:
+ * the four-wave strawMan build): with 1..4 waves per workgroup for bands up to 56, 120, 184, 248 k-mers, with 6 and 8
+ * for the wide bands (376 and 504), and with the switches described below.  Every build holds the sweeps -- a forward, a
+ * backward and, where the machine has its E-step here, an expectation kernel -- their launchers and one SweepBuild
+ * record; what does not depend on the build (track, counts, the machines' records) is cpecan_kernel_prep.hip's */
 /* -DSY_VANILLA: the same two sweeps for the 3-state vanilla signal machine (stateMachine3Vanilla_cellCalculate,
  * impl/stateMachine.c:1368-1409), posterior decode only, with four, six and eight waves per workgroup (bands of up to
  * 248, 376 and 504 k-mers; symbols suffixed _v4, _v6, _v8).  A lane holds the 21 doubles of its k-mer's row of the
@@ -144,6 +141,8 @@
 #define SY_TR 16     /* first of the row's five log transition probabilities: a_mx, a_xx, a_mm, a_xm, a_my */
 #define SY_EVW 4     /* doubles per staged event: mean, noise, 1 / noise, log(noise) */
 #define SY_MODEL_DOUBLES ((long long) CP_VMODEL_STRIDE)
+#define SY_MACHINE_ID SWEEP_VANILLA /* (the build's record, at the end of the file) */
+#define SY_MACHINE cpecan_systolic_machine_vanilla
 #ifdef SY_ESTEP
 #define SY_MODE(P) 1 /* E-step only */
 #else
@@ -154,6 +153,8 @@
 #define SY_NPRM 1    /* a slot keeps the table row offset */
 #define SY_EVW 2     /* doubles per staged event: grid cell of its mean, offset in the cell */
 #define SY_MODEL_DOUBLES ((long long) (sizeof(DevHdpModel) / sizeof(double)))
+#define SY_MACHINE_ID SWEEP_HDP
+#define SY_MACHINE cpecan_systolic_machine_hdp
 #ifdef SY_ESTEP
 #define SY_MODE(P) 1 /* E-step only */
 #else
@@ -165,6 +166,8 @@
 #define SY_NPRM 17
 #define SY_EVW 2     /* doubles per staged event: mean, noise */
 #define SY_MODEL_DOUBLES ((long long) CP_MODEL_STRIDE)
+#define SY_MACHINE_ID SWEEP_STRAWMAN
+#define SY_MACHINE cpecan_systolic_machine
 #ifdef SY_FUSED
 #define SY_MODE(P) 1 /* E-step only */
 #else
@@ -173,6 +176,15 @@
 #endif
 #if ((defined(SY_VANILLA) || defined(SY_HDP)) && !defined(SY_ESTEP)) || defined(SY_FUSED)
 #define SY_NO_ESTEP /* these builds have no expectation kernel and no ring of backward cells */
+#endif
+/* SY_ESTEP_BY(fused, ring): a field of the build's record that depends on its E-step -- summed inside the sweep back,
+ * taken from the ring of backward cells, or none (null) */
+#if defined(SY_FUSED)
+#define SY_ESTEP_BY(fused, ring) fused
+#elif defined(SY_NO_ESTEP)
+#define SY_ESTEP_BY(fused, ring) nullptr
+#else
+#define SY_ESTEP_BY(fused, ring) ring
 #endif
 #ifdef SY_FUSED
 #define SY_FX true
@@ -191,6 +203,11 @@
 #define SY_BRING_VALUES 1
 #else
 #define SY_BRING_VALUES 3
+#endif
+#ifdef SY_NO_ESTEP
+#define SY_BRING_ROW_DOUBLES 0
+#else
+#define SY_BRING_ROW_DOUBLES (SY_R * SY_BRING_VALUES * 64) /* per diagonal */
 #endif
 #define SY_PREFETCH 4     /* diagonals the backward sweep fetches ahead (== its unroll factor) */
 #define SY_CAND_SLACK 0.25 /* candidates: cells within this (log units) below the posterior threshold */
@@ -2253,36 +2270,11 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 /* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
 extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
-#if defined(SY_FUSED)
-/* (E-step only, and only for a batch that asks for it: cpecan_hip.hip puts the build in the place of the one of as many
- * waves that the dispatch chose; no ring of backward cells, no expect launcher, the segment records behind the scratch) */
+/* (the _f builds serve a batch that asks for them only: cpecan_hip.hip puts one in the place of the build of as many
+ * waves that the dispatch chose; their segment records lie behind the scratch.  The dispatch sends the other E-step
+ * builds of the vanilla and the HDP machine no posterior batch, and their posterior builds no E-step) */
 const SweepBuild SY_SYM(cpecan_systolic_build) = {
-    SY_R, false, SWEEP_STRAWMAN, &cpecan_systolic_machine, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
-    sy_scratch_bytes, sy_fx_bytes, sy_launch_forward, sy_launch_backward, sy_launch_backward, nullptr, nullptr };
-#elif defined(SY_VANILLA) && defined(SY_ESTEP)
-/* (E-step only: the dispatch sends these builds no posterior batch; one backward value per cell in the B ring) */
-const SweepBuild SY_SYM(cpecan_systolic_build) = {
-    SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64,
-    SY_R * SY_BRING_VALUES * 64, sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, sy_launch_expect,
-    nullptr };
-#elif defined(SY_VANILLA)
-/* (no E-step on these builds: no expect launcher, no ring of backward cells; theirs are the _ve objects) */
-const SweepBuild SY_SYM(cpecan_systolic_build) = {
-    SY_R, false, SWEEP_VANILLA, &cpecan_systolic_machine_vanilla, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
-    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };
-#elif defined(SY_HDP) && defined(SY_ESTEP)
-/* (E-step only: the dispatch sends these builds no posterior batch) */
-const SweepBuild SY_SYM(cpecan_systolic_build) = {
-    SY_R, false, SWEEP_HDP, &cpecan_systolic_machine_hdp, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, SY_R * 3 * 64,
-    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, sy_launch_expect, nullptr };
-#elif defined(SY_HDP)
-/* (no E-step on these builds: theirs are the _he objects) */
-const SweepBuild SY_SYM(cpecan_systolic_build) = {
-    SY_R, false, SWEEP_HDP, &cpecan_systolic_machine_hdp, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, 0,
-    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, nullptr, nullptr };
-#else
-const SweepBuild SY_SYM(cpecan_systolic_build) = {
-    SY_R, false, SWEEP_STRAWMAN, &cpecan_systolic_machine, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, SY_R * 3 * 64,
-    sy_scratch_bytes, nullptr, sy_launch_forward, sy_launch_backward, nullptr, sy_launch_expect, nullptr };
-#endif
+    SY_R, false, SY_MACHINE_ID, &SY_MACHINE, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, SY_BRING_ROW_DOUBLES,
+    sy_scratch_bytes, SY_ESTEP_BY(sy_fx_bytes, nullptr), sy_launch_forward, sy_launch_backward,
+    SY_ESTEP_BY(sy_launch_backward, nullptr), SY_ESTEP_BY(nullptr, sy_launch_expect), nullptr };
 #endif

@@ -125,10 +125,9 @@ enum { SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA };
 #define SWEEP_SYM_(n, tag, k) n##_##tag##k
 #define SWEEP_SYM(n, tag, k) SWEEP_SYM_(n, tag, k)
 
-/* One compiled build of the throughput kernels, defined next to them (cpecan_kernel_systolic.hip: cpecan_systolic_build
- * and _r1.._r3, _r6, _r8, the vanilla machine's _v4, _v6, _v8 and, for its E-step, _ve4, _ve6, _ve8, the HDP machine's
- * _h6, _h8 and, for its E-step, _he6, _he8, the strawMan machine's fused E-step _f1.._f4;
- * cpecan_kernel_wave.hip: cpecan_wave_build_l2.._l4, _h2.._h4, _v2, _v3) */
+/* One compiled build of the throughput kernels, defined next to them: cpecan_systolic_build<suffix> in
+ * cpecan_kernel_systolic.hip, cpecan_wave_build<suffix> in cpecan_kernel_wave.hip, one per build of the Makefile's list
+ * (SY_BUILDS, WV_BUILDS, and the unsuffixed four-wave build) */
 struct SweepBuild {
     int rows;    /* waves per workgroup (workgroup family) or cells per lane (wave family) */
     bool wave;   /* one wave per alignment */

@@ -2,7 +2,9 @@
 1024-read batch resident at once): that holds only while each stays within 128 VGPRs and uses no
 scratch.  The register allocator has crossed that line silently before (an inlined helper with its
 own constants, a loop the optimiser decided to clone), halving the measured throughput -- so the
-budget is checked from the compiler's own metadata.  CPU-only: hipcc cross-compiles gfx950."""
+budget is checked from the compiler's own metadata.  The two tests of the sweep files' builds take
+their assembly from sweep_builds.device_asm, as tests/test_sweep_build_resources.py does, which
+holds every build of the Makefile's list to its budget.  CPU-only: hipcc cross-compiles gfx950."""
 import os
 import re
 import shutil
@@ -11,61 +13,45 @@ import subprocess
 import pytest
 
 from cpecan_load import ROOT
+from sweep_builds import builds, device_asm, kernel_meta
 
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
+def sweep_build(name):
+    return next(b for b in builds() if b.name == name)
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("rows,suffix", [(4, ""), (3, "_r3"), (2, "_r2"), (1, "_r1")])
-def test_systolic_kernels_fit_four_waves_per_simd(tmp_path, rows, suffix):
-    src = os.path.join(ROOT, "cpecan-signal_amd", "csrc", "cpecan_kernel_systolic.hip")
-    out = str(tmp_path / "sy.s")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-Wno-unused-function", "-DSY_R=%d" % rows,
-                           "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", out, src],
-                          stderr=subprocess.DEVNULL)
-    text = open(out).read()
+def test_systolic_kernels_fit_four_waves_per_simd(rows, suffix):
+    text = device_asm(sweep_build(suffix[1:]))
     for name in ("cpecan_k_sy_forward" + suffix, "cpecan_k_sy_backward" + suffix):
-        meta = text[text.index(".name:           " + name):]
-        vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
-        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
-        body = text[text.index("\n" + name + ":"):]
-        body = body[:body.index("s_endpgm")]
-        assert vgpr <= 128, "%s uses %d VGPRs: fewer than 4 waves per SIMD" % (name, vgpr)
-        assert spill == 0 and "scratch_" not in body, "%s spills to scratch" % name
+        m = kernel_meta(text, name)
+        assert m["vgpr"] <= 128, "%s uses %d VGPRs: fewer than 4 waves per SIMD" % (name, m["vgpr"])
+        assert m["spill"] == 0 and "scratch_" not in m["body"], "%s spills to scratch" % name
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("cells,hdp", [(3, False), (2, False), (3, True), (2, "vanilla")])
-def test_wave_kernels_fit_two_waves_per_simd(tmp_path, cells, hdp):
+def test_wave_kernels_fit_two_waves_per_simd(cells, hdp):
     """The wave-per-alignment sweeps run as one forward and one backward wave per SIMD (the forward sweep of window
     w+1 beside the backward sweep of window w): the two allocations (unified register file of 512 per lane, handed
     out in blocks of 8) must fit together, with nothing in scratch.  The four-cell build is the documented exception
     (its backward sweep takes 306 registers: one wave per SIMD while it runs)."""
-    src = os.path.join(ROOT, "cpecan-signal_amd", "csrc", "cpecan_kernel_wave.hip")
-    out = str(tmp_path / "wv.s")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-Wno-unused-function", "-DWV_L=%d" % cells] +
-                          (["-DWV_VANILLA"] if hdp == "vanilla" else ["-DWV_HDP"] if hdp else []) +
-                          ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(src), "-S",
-                           "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL)
-    text = open(out).read()
     sfx = "_%s%d" % ("v" if hdp == "vanilla" else "h" if hdp else "l", cells)
+    text = device_asm(sweep_build(sfx[1:]))
     alloc = {}
     for name in ("cpecan_k_wv_forward" + sfx, "cpecan_k_wv_backward" + sfx, "cpecan_k_wv_resweep" + sfx,
                  "cpecan_k_wv_backward_em" + sfx):  # (every machine's E-step sweeps back with this one)
-        meta = text[text.index(".name:           " + name + "\n"):]
-        vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
-        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
-        alloc[name] = (vgpr + 7) // 8 * 8
-        assert spill == 0, "%s spills %d VGPRs to scratch" % (name, spill)
+        m = kernel_meta(text, name)
+        alloc[name] = (m["vgpr"] + 7) // 8 * 8
+        assert m["spill"] == 0, "%s spills %d VGPRs to scratch" % (name, m["spill"])
     fwd = alloc.pop("cpecan_k_wv_forward" + sfx)
     for name, a in alloc.items():
         assert fwd + a <= 512, "%s (%d registers) and the forward sweep (%d) no longer share a SIMD" % (name, a, fwd)
     if hdp is True:  # three register pairs per slot instead of ten: the forward sweep is the light one
-        meta = text[text.index(".name:           cpecan_k_wv_forward" + sfx + "\n"):]
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1)) <= 192
+        assert kernel_meta(text, "cpecan_k_wv_forward" + sfx)["vgpr"] <= 192
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")

@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 from cpecan_load import ROOT
+from sweep_builds import builds, defined
 
 AMD = os.path.join(ROOT, "cpecan-signal_amd")
 ONCE = ("cpecan_k_kmer_index", "cpecan_k_hdp_kmer_id", "cpecan_k_track", "cpecan_k_sy_track_hdp", "cpecan_k_wv_track",
@@ -17,11 +18,8 @@ ONCE = ("cpecan_k_kmer_index", "cpecan_k_hdp_kmer_id", "cpecan_k_track", "cpecan
         "cpecan_k_divtest")
 MACHINES = ("cpecan_systolic_machine", "cpecan_systolic_machine_vanilla", "cpecan_systolic_machine_hdp",
             "cpecan_wave_machine", "cpecan_wave_machine_hdp", "cpecan_wave_machine_vanilla")
-
-
-def defined(path, *flags):
-    out = subprocess.check_output(["nm", "--defined-only"] + list(flags) + [path], text=True)
-    return set(l.split()[-1] for l in out.splitlines() if l.strip())
+# tags of the workgroup builds without an expectation kernel: posterior decode only, or the E-step fused into the sweep
+NO_EXPECT = ("v", "h", "f")
 
 
 @pytest.fixture(scope="module")
@@ -45,17 +43,25 @@ def test_once_kernels_are_in_the_prep_object_alone(objects):
 
 
 def test_sweep_objects_define_their_own_build_only(objects):
+    listed = dict((b.obj, b) for b in builds() if b.name)
+    assert len(listed) >= 27 and set(listed) <= set(objects)
     seen = 0
     for p, names in objects.items():
         m = re.fullmatch(r"cpecan_kernel_(systolic|wave)(_[a-z]+\d)\.o", os.path.basename(p))
         if m is None:
             continue
         seen += 1
+        assert listed[p].suffix == m.group(2)
         kernels = set(n for n in names if n.startswith("cpecan_k_"))
         assert kernels, os.path.basename(p)
         stray = sorted(n for n in kernels if not n.endswith(m.group(2)))
         assert not stray, "%s defines %s" % (os.path.basename(p), stray)
-    assert seen == 20  # twelve suffixed builds of the workgroup file, eight of the wave file
+        assert not set(ONCE) & names
+        assert "cpecan_%s_build%s" % m.groups() in names
+        if m.group(1) == "systolic":  # forward and backward, and an expectation kernel where the E-step is not elsewhere
+            stems = ("forward", "backward") + (() if listed[p].tag in NO_EXPECT else ("expect",))
+            assert kernels == set("cpecan_k_sy_%s%s" % (s, m.group(2)) for s in stems), os.path.basename(p)
+    assert seen == len(listed)  # every suffixed build of the Makefile's list, and no other object of that name
 
 
 def test_unsuffixed_workgroup_object_has_three_kernels(objects):

@@ -11,8 +11,7 @@ cd $root/cpecan-signal_amd
 out=$root/gpurun_out/abl; mkdir -p $out; : > $out/result_systolic.txt
 for v in NONE "$@"; do
   flag=""; [ "$v" != NONE ] && flag="-DSY_ABLATE_$v"
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
-      -Wno-unused-function -I../include -Icsrc $flag -c csrc/cpecan_kernel_systolic.hip -o $out/systolic.o || { echo "$v build failed" | tee -a $out/result_systolic.txt; continue; }
+  /opt/rocm/bin/hipcc $(make -s print-hipflags) $flag -c csrc/cpecan_kernel_systolic.hip -o $out/systolic.o || { echo "$v build failed" | tee -a $out/result_systolic.txt; continue; }
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libcpecan_hip_abl.so \
       $(make -s print-objects | sed "s|csrc/cpecan_kernel_systolic.o|$out/systolic.o|") -lpthread
   r=$(cd $root && CPECAN_HIP_LIB=$out/libcpecan_hip_abl.so CPECAN_SYSTOLIC_GROUPS=1 timeout -k 10 120 python bench.py --steps 12 --warmup 3 --check 0 --cpu-reads 0 --inflight 1 --family workgroup --single-steps 0 2>/dev/null | python -c "

@@ -1,14 +1,13 @@
 #!/usr/bin/env python3
-"""Device code of the throughput kernels in two source trees, kernel for kernel: each build the Makefile makes of
-cpecan_kernel_systolic.hip (sixteen) and cpecan_kernel_wave.hip (eight), and the files around them that are compiled once
-(cpecan_kernel_prep.hip, cpecan_kernel_general.hip, cpecan_kernel_generalh.hip and the two files of the C-ABI layer that
-have held the pack kernels, cpecan_hip.hip and cpecan_readback.hip; a unit is a file of csrc, and one that a tree lacks or
-that defines no kernel there counts for nothing, and so does a build that a tree's source refuses with #error: the
-vanilla E-step builds before they existed), is compiled to gfx950 assembly in both trees (the Makefile's flags plus -S --cuda-device-only) and, per kernel name, the instructions between
-the label and the function's end and the resource lines of the metadata block are compared.  A kernel that moved to
-another file is compared with whichever parent build had it: the number of its function in the file, which the
-compiler puts into its local labels (.LBB<n>_), is taken out first.  A refactor of the host side, or one that moves
-kernels between files, must leave all of them as they were.
+"""Device code of the throughput kernels in two source trees, kernel for kernel: every build the branch tree's Makefile
+makes of cpecan_kernel_systolic.hip and cpecan_kernel_wave.hip (make print-builds), and the files around them that are
+compiled once (ONCE below: a unit is a file of csrc, and one that a tree lacks or that defines no kernel there counts for
+nothing, and so does a build that a tree's source refuses with #error: a build from before it existed), is compiled to
+gfx950 assembly in both trees (the branch Makefile's flags, make print-hipflags, plus -S --cuda-device-only) and, per
+kernel name, the instructions between the label and the function's end and the resource lines of the metadata block are
+compared.  A kernel that moved to another file is compared with whichever parent build had it: the number of its
+function in the file, which the compiler puts into its local labels (.LBB<n>_), is taken out first.  A refactor of the
+host side, or one that moves kernels between files, must leave all of them as they were.
 usage: tools/kernel_diff.py PARENT_TREE BRANCH_TREE [WORKDIR]     (needs hipcc, no GPU; about 17 s per wave build)"""
 import os
 import re
@@ -17,31 +16,24 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-         "-Wno-unused-function"]
-SY, WV = "cpecan_kernel_systolic.hip", "cpecan_kernel_wave.hip"
-BUILDS = [(SY, ["-DSY_R=%d" % r]) for r in (1, 2, 3)] + [(SY, [])] + \
-         [(SY, ["-DSY_R=%d" % r] + m) for m, rows in (([], (6, 8)), (["-DSY_VANILLA"], (4, 6, 8)),
-                                                     (["-DSY_HDP"], (6, 8)), (["-DSY_HDP", "-DSY_ESTEP"], (6, 8)),
-                                                     (["-DSY_VANILLA", "-DSY_ESTEP"], (4, 6, 8)))
-          for r in rows] + \
-         [(WV, ["-DWV_L=%d" % l] + m) for m, cells in (([], (2, 3, 4)), (["-DWV_HDP"], (2, 3, 4)),
-                                                      (["-DWV_VANILLA"], (2, 3))) for l in cells] + \
-         [(u, []) for u in ("cpecan_kernel_prep.hip", "cpecan_kernel_general.hip", "cpecan_kernel_generalh.hip",
-                            "cpecan_hip.hip", "cpecan_readback.hip")]
+ONCE = ("cpecan_kernel_prep.hip", "cpecan_kernel_general.hip", "cpecan_kernel_generalh.hip", "cpecan_hip.hip",
+        "cpecan_readback.hip")
 META = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size",
         "kernarg_segment_size")
 
 
-def kernels(tree, unit, defs, work):
+def make_print(tree, target):
+    return subprocess.check_output(["make", "-s", "-C", os.path.join(tree, "cpecan-signal_amd"), target], text=True)
+
+
+def kernels(tree, unit, defs, flags, work):
     """{kernel name: (instruction text, metadata figures)} of one build of one tree; none where the tree lacks the file"""
-    src = os.path.join(tree, "cpecan-signal_amd", "csrc", unit)
-    if not os.path.exists(src):
+    amd = os.path.join(tree, "cpecan-signal_amd")
+    if not os.path.exists(os.path.join(amd, "csrc", unit)):
         return {}
-    out = os.path.join(work, "%s%s.s" % (unit[:-4], "".join(defs).replace("-D", "_").replace("=", "")))
-    r = subprocess.run([HIPCC] + FLAGS + defs + ["-I" + os.path.join(tree, "include"), "-I" + os.path.dirname(src),
-                                                 "-S", "--cuda-device-only", "-o", out, src],
-                       stderr=subprocess.PIPE, text=True)
+    out = os.path.abspath(os.path.join(work, "%s%s.s" % (unit[:-4], "".join(defs).replace("-D", "_").replace("=", ""))))
+    r = subprocess.run([HIPCC] + flags + defs + ["-S", "--cuda-device-only", "-o", out, os.path.join("csrc", unit)],
+                       cwd=amd, stderr=subprocess.PIPE, text=True)  # (from where make runs: the flags' -I are relative)
     if r.returncode != 0 and "#error" in r.stderr:
         return {}
     if r.returncode != 0:
@@ -64,16 +56,19 @@ def main():
     work = sys.argv[3] if len(sys.argv) > 3 else "kernel_diff_out"
     for t in ("P", "B"):
         os.makedirs(os.path.join(work, t), exist_ok=True)
-    jobs = [(t, sub, u, d) for u, d in BUILDS for t, sub in ((parent, "P"), (branch, "B"))]
+    flags = make_print(branch, "print-hipflags").split()
+    builds = [(os.path.basename(src), defs.split()) for _, _, src, defs in
+              (line.split("\t") for line in make_print(branch, "print-builds").splitlines())] + [(u, []) for u in ONCE]
+    jobs = [(t, sub, u, d) for u, d in builds for t, sub in ((parent, "P"), (branch, "B"))]
     with ThreadPoolExecutor(max_workers=int(os.environ.get("JOBS", "8"))) as pool:
-        res = list(pool.map(lambda j: kernels(j[0], j[2], j[3], os.path.join(work, j[1])), jobs))
+        res = list(pool.map(lambda j: kernels(j[0], j[2], j[3], flags, os.path.join(work, j[1])), jobs))
     # a kernel is compared with the same build of the parent, or (it moved) with the parent build that has it
     everywhere = {}
     for p in res[0::2]:
         for name, v in p.items():
             everywhere.setdefault(name, v)
     same, differ, new, kept = 0, [], [], set()
-    for (u, d), p, b in zip(BUILDS, res[0::2], res[1::2]):
+    for (u, d), p, b in zip(builds, res[0::2], res[1::2]):
         for name, v in b.items():
             ref = p.get(name, everywhere.get(name))
             kept.add(name)
@@ -84,8 +79,8 @@ def main():
             else:
                 differ.append("%s (%s %s)" % (name, u, " ".join(d)))
     gone = sorted(set(everywhere) - kept)
-    print("kernels identical: %d; differing: %d %s; only in the parent: %d %s; only in the branch: %d %s" %
-          (same, len(differ), differ, len(gone), gone, len(new), new))
+    print("units compiled: %d; kernels identical: %d; differing: %d %s; only in the parent: %d %s; only in the branch: %d %s" %
+          (len(builds), same, len(differ), differ, len(gone), gone, len(new), new))
     return 1 if differ or new else 0
 
 
