@@ -40,8 +40,8 @@ struct cpecan_batch {
     DevBuf<double> Fstore, Bstore, dbgB;
     DevBuf<double> Bring; /* systolic Baum-Welch: backward cells of one window per item */
     bool fused = false; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0) or, with
-                           CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, on the workgroup kernels' fused builds: expectations summed
-                           inside the sweep back, no B ring, no expectation kernel */
+                           CPECAN_FLAG_WORKGROUP_FUSED_ESTEP / CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, on the workgroup kernels'
+                           fused builds: expectations summed inside the sweep back, no B ring, no expectation kernel */
     DevBuf<long long> pairs;
     DevBuf<double> pairLogp;
     DevBuf<long long> nPairs, totXay, nTot, nCells;

@@ -63,7 +63,8 @@ W5_DECLARE(3)
  * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f: the
  * strawMan E-step summed inside the sweep back) are no choice of the dispatch's: a strawMan batch of expectations that
  * the dispatch put on the workgroup build of r waves runs on _f<r> instead when it carries
- * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP (new_batch). */
+ * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, and one that it put on _r6 / _r8 runs on _f6 / _f8 when it carries
+ * CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP (new_batch). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
@@ -75,7 +76,7 @@ SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
 SWEEP_BUILD(cpecan_systolic_build_ve4) SWEEP_BUILD(cpecan_systolic_build_ve6) SWEEP_BUILD(cpecan_systolic_build_ve8)
 SWEEP_BUILD(cpecan_systolic_build_f1) SWEEP_BUILD(cpecan_systolic_build_f2) SWEEP_BUILD(cpecan_systolic_build_f3)
-SWEEP_BUILD(cpecan_systolic_build_f4)
+SWEEP_BUILD(cpecan_systolic_build_f4) SWEEP_BUILD(cpecan_systolic_build_f6) SWEEP_BUILD(cpecan_systolic_build_f8)
 typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
@@ -84,6 +85,8 @@ static SweepFamily SY_FUSED_BUILDS = { &cpecan_systolic_build_f1, &cpecan_systol
                                        &cpecan_systolic_build_f4 };
 /* (a table of wide builds ends with a null entry) */
 static const SweepBuild *const SY_WIDE_BUILDS[3] = { &cpecan_systolic_build_r6, &cpecan_systolic_build_r8, nullptr };
+/* (the fused E-step of the build of as many waves in SY_WIDE_BUILDS) */
+static const SweepBuild *const SY_FUSED_WIDE_BUILDS[3] = { &cpecan_systolic_build_f6, &cpecan_systolic_build_f8, nullptr };
 static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4, &cpecan_systolic_build_v6,
                                                       &cpecan_systolic_build_v8, nullptr };
 static const SweepBuild *const SYH_WIDE_BUILDS[3] = { &cpecan_systolic_build_h6, &cpecan_systolic_build_h8, nullptr };
@@ -874,13 +877,20 @@ static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput 
     /* CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, or CPECAN_EXPECT_FUSED_WORKGROUP=1 (read per batch): a strawMan batch of
      * expectations that the dispatch put on one of the workgroup family's four builds (bands up to 248 k-mers) sums its
      * expectations inside the sweep back, on the fused build of as many waves.  Every other batch -- another machine
-     * or mode, the wave family, the six- and eight-wave builds, the general kernel -- runs what it runs without it. */
+     * or mode, the wave family, the six- and eight-wave builds, the general kernel -- runs what it runs without it.
+     * CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, or CPECAN_EXPECT_FUSED_WIDE=1, is the same for the six- and eight-wave builds
+     * and for them alone: a strawMan batch of expectations that the dispatch put on _r6 / _r8 (CPECAN_FLAG_WIDE_BANDS, a
+     * widest band of 249..504 k-mers) runs on _f6 / _f8. */
     {
-        const char *fxw = getenv("CPECAN_EXPECT_FUSED_WORKGROUP");
+        const char *fxw = getenv("CPECAN_EXPECT_FUSED_WORKGROUP"), *fxd = getenv("CPECAN_EXPECT_FUSED_WIDE");
         const bool asked = (d.flags & CPECAN_FLAG_WORKGROUP_FUSED_ESTEP) || (fxw != nullptr && atoi(fxw) == 1);
+        const bool askedWide = (d.flags & CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP) || (fxd != nullptr && atoi(fxd) == 1);
         if (asked && machine == STRAWMAN && in.mode == CPECAN_MODE_EXPECTATIONS && d.build)
             for (int r = 0; r < 4; r++)
                 if (d.build == SY_BUILDS[r]) b->sy = SY_FUSED_BUILDS[r];
+        if (askedWide && machine == STRAWMAN && in.mode == CPECAN_MODE_EXPECTATIONS && d.build)
+            for (int r = 0; SY_WIDE_BUILDS[r]; r++)
+                if (d.build == SY_WIDE_BUILDS[r]) b->sy = SY_FUSED_WIDE_BUILDS[r];
     }
     if (d.build) b->trackRow = b->sy->once->trackRowDoubles;
     b->hItems = plan.items;

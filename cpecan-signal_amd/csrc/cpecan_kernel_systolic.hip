@@ -71,9 +71,14 @@
  * one backward value per cell, B.gapX, so the sweep back parks that one alone: a B ring of [diagonal][wave][lane], a
  * third of the strawMan builds'.  cpecan_k_sy_expect is compiled in its vanilla form (30 + 30 skip bins and the
  * likelihood: match -> gap X and gap X -> gap X, from the cell's lower neighbour). */
-/* -DSY_FUSED: the strawMan machine's E-step with its expectations summed inside the sweep back, with one to four waves
- * per workgroup, in objects of their own (symbols suffixed _f1.._f4; the _r1.._r3 and the unsuffixed objects keep their
- * device code).  E-step only: SY_MODE(P) is the constant 1, so the forward sweep keeps every state of every diagonal.
+/* -DSY_FUSED: the strawMan machine's E-step with its expectations summed inside the sweep back, with one to four, six
+ * and eight waves per workgroup, in objects of their own (symbols suffixed _f1.._f4, _f6, _f8; the _r1.._r8 and the
+ * unsuffixed objects keep their device code).  _f6 and _f8 serve the bands of _r6 and _r8 (249..376 and 377..504
+ * k-mers); nothing of the fused pass depends on the number of waves beyond SY_R and SY_P: the segment records are
+ * [segment][wave][8] and [segment][A | B][slot] (sy_fx_bytes), the hit masks (SY_MSK) belong to the decode, which these
+ * builds do not have, and the band ring is staged again for a second sweep by the whole workgroup.  _f6 alone keeps a
+ * lane's eight sums in LDS (SY_FX_LDS).  E-step only: SY_MODE(P) is the constant 1, so the forward sweep keeps every
+ * state of every diagonal.
  * The sweep back fetches F.gapX and F.gapY of a row with its F.match and forms, per cell, the terms of
  * diagonalCalculation_Expectations (see fx_terms in backward_window): no ring of backward cells, no expectation kernel.
  * The terms are taken against the window's estimated total and kept per refresh segment (FxRecords); after phase T they
@@ -81,8 +86,6 @@
  * trusted is swept back once more, in the same launch, against the exact totals. */
 #if defined(SY_FUSED) && (defined(SY_HDP) || defined(SY_VANILLA) || defined(SY_ESTEP))
 #error "SY_FUSED: a build of the strawMan machine"
-#elif defined(SY_FUSED) && (SY_R < 1 || SY_R > 4)
-#error "SY_FUSED: 1 to 4 waves per workgroup"
 #elif defined(SY_HDP) && defined(SY_VANILLA)
 #error "SY_HDP and SY_VANILLA are builds of their own"
 #elif defined(SY_ESTEP) && !defined(SY_HDP) && !defined(SY_VANILLA)
@@ -114,6 +117,10 @@
 #endif
 #if defined(SY_VANILLA) /* the vanilla row does not fit 128 VGPRs: whatever occupancy the allocation lands on */
 #define SY_BACKWARD_ATTR
+#elif defined(SY_FUSED) && SY_R == 6 && !defined(SY_FX_REG_SUMS)
+/* the six-wave fused sweep back with its eight sums in LDS (SY_FX_LDS below) fits three waves per SIMD without a spill (165
+ * VGPRs): two six-wave workgroups share a CU, as on _r6.  Left alone it takes 173, and 179 with the sums in registers */
+#define SY_BACKWARD_ATTR __attribute__((amdgpu_waves_per_eu(3, 3)))
 #elif defined(SY_FUSED) /* nor do the fused sweep's accumulators and wider fetch buffers: no occupancy is forced */
 #define SY_BACKWARD_ATTR
 #elif SY_R == 1 || SY_R == 8 /* the one-wave and the eight-wave backward kernel land on 129 VGPRs by themselves: hold
@@ -196,6 +203,13 @@
 #define SY_FXQ(...) , __VA_ARGS__
 #else
 #define SY_FXQ(...)
+#endif
+/* SY_FX_LDS: the fused sweep back keeps a lane's eight transition sums in LDS, [sum][thread], instead of sixteen VGPRs --
+ * the six-wave build only: up to four waves no occupancy is in reach of sixteen registers, at eight only 128 registers
+ * would bring a second workgroup to the CU.  -DSY_FX_REG_SUMS (a timing-study switch, like SY_ABLATE_*, with the same
+ * results) keeps them in registers there too */
+#if defined(SY_FUSED) && SY_R == 6 && !defined(SY_FX_REG_SUMS)
+#define SY_FX_LDS
 #endif
 #define SY_FX_EST_BOUND 30.0 /* nats an exact total may lie from the estimate the fused sums were taken against */
 /* per cell in the ring of backward cells: the three states, or the one the vanilla E-step reads (gap X) */
@@ -1027,6 +1041,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
 #ifdef SY_FUSED
                                 , const FxRecords &fxo, double *expect, const unsigned short *__restrict__ kidx,
                                 const bool fxForce
+#ifdef SY_FX_LDS
+                                , double *fxAcc
+#endif
 #endif
                                 ) {
     const Geometry g = make_geometry(ring, ringD);
@@ -1183,9 +1200,16 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
          * that diagonal's segment.  Sums per segment: eight per lane (ea), and the gap-X terms of the column the slot
          * points at once more for that column's k-mer bin (gSum of column gCol = x + 1).
          */
-        double ea[8]; /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
+        /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
+#ifdef SY_FX_LDS
+        double *const ea = fxAcc + threadIdx.x; /* (a thread reads and writes its own eight entries only: no barrier) */
+#define SY_EA(i) ea[(i) * SY_P]
+#else
+        double ea[8];
+#define SY_EA(i) ea[i]
+#endif
 #pragma unroll
-        for (int i = 0; i < 8; i++) ea[i] = 0.0;
+        for (int i = 0; i < 8; i++) SY_EA(i) = 0.0;
         double gSum = 0.0, refX = exact ? uni_d(ld_agent(&wtot[0].total)) : 0.0;
         int gCol = -1, segAcc = 0;
         const int fxSlot = wave * 64 + lane;
@@ -1193,11 +1217,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
         auto fx_flush = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                double v = ea[i];
+                double v = SY_EA(i);
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
                 if (lane == 0) fxo.tr[(segAcc * SY_R + wave) * 8 + i] = v;
-                ea[i] = 0.0;
+                SY_EA(i) = 0.0;
             }
             fxo.g[(segAcc * 2 + 1) * SY_P + fxSlot] = gSum;
             fxo.c[(segAcc * 2 + 1) * SY_P + fxSlot] = gCol;
@@ -1231,9 +1255,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                         p4 = ok ? p4 : 0.0;
                         p5 = ok ? p5 : 0.0;
                     }
-                    ea[3] += p3;
-                    ea[4] += p4;
-                    ea[5] += p5;
+                    SY_EA(3) += p3;
+                    SY_EA(4) += p4;
+                    SY_EA(5) += p5;
                 }
                 if ((tPost0 - (t + 2)) % 10 == 9) fx_flush(); /* t+2 ends its segment */
             }
@@ -1254,9 +1278,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     p6 = inU ? p6 : 0.0;
                     p7 = inU ? p7 : 0.0;
                 }
-                ea[0] += p0;
-                ea[1] += p1;
-                if (hasSwitchX || nf) ea[2] += p2;
+                SY_EA(0) += p0;
+                SY_EA(1) += p1;
+                if (hasSwitchX || nf) SY_EA(2) += p2;
                 if (inL && x + 1 != gCol) { /* the slot points at another column than before */
                     if (gSum != 0.0) {
                         fxo.g[(segAcc * 2) * SY_P + fxSlot] = gSum;
@@ -1268,10 +1292,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 gSum += p0;
                 gSum += p1;
                 if (hasSwitchX || nf) gSum += p2;
-                ea[6] += p6;
-                ea[7] += p7;
+                SY_EA(6) += p6;
+                SY_EA(7) += p7;
             }
         };
+#undef SY_EA
 #endif
         auto step = [&](const int t, double &qF, double &qPm, double &qPy SY_FXQ(double &qFx, double &qFy))
                         __attribute__((always_inline)) {
@@ -1906,6 +1931,9 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
 #ifdef SY_VANILLA
     __shared__ TransFeed tf;
 #endif
+#ifdef SY_FX_LDS
+    __shared__ double fxAcc[8 * SY_P];
+#endif
     const long long idx = blockIdx.x;
     if (idx >= nItems) return;
     SyState *state = states + idx;
@@ -1943,6 +1971,9 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
                      * parity differ) */
                     , fx_records(scratch + idx * scratchBytes + scratch_end_offset(ringD), ringD), expect, kidx,
                     P.expectResweep == 1 || (P.expectResweep == 2 && ((idx ^ window) & 1))
+#ifdef SY_FX_LDS
+                    , fxAcc
+#endif
 #endif
                     );
     if (threadIdx.x == 0) {

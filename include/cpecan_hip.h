@@ -352,6 +352,33 @@ typedef struct {
                                           variable CPECAN_EXPECT_FUSED_WORKGROUP=1 (read per batch) sets it for every
                                           strawMan batch of expectations: the way in for callers of libcpecan_host.so
                                           (cpecan_trainModels) and for em.PersistentEStep. */
+#define CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP 4096 /* cpecan_hip_batch_create (strawMan machine) with
+                                          CPECAN_MODE_EXPECTATIONS only: a batch that the kernel choice put on the six-
+                                          or eight-wave build of the workgroup-per-alignment kernels (CPECAN_FLAG_WIDE_BANDS
+                                          or CPECAN_WIDE_BANDS=1, a widest band of 249..504 k-mers) sums its Baum-Welch
+                                          expectations inside the sweep back, on the fused build of as many waves
+                                          (cpecan_k_sy_backward_f6 / _f8), as CPECAN_FLAG_WORKGROUP_FUSED_ESTEP does up
+                                          to four waves: no ring of backward cells (ring diagonals x 6 or 8 x 3 x 64
+                                          doubles per alignment, 9 or 12 KB per diagonal), no expectation kernel; the
+                                          estimate, the scaling, the second sweep and CPECAN_EXPECT_RESWEEP are those
+                                          described there.  The kernel choice does not change: cpecan_hip_plan_dispatch
+                                          answers what it answers without the flag.  Every other batch ignores it: a
+                                          posterior batch, a band of 248 k-mers or less (flag 2048's ground), a band
+                                          past 504 k-mers and a wide band without CPECAN_FLAG_WIDE_BANDS (both on the
+                                          general kernel), every other machine.  It has a number of its own because a
+                                          test pins that 2048 | 128 keeps the ring of backward cells at six waves.
+                                          The sums are those of the ring path to rounding, NaN in the same places.
+                                          Opt-in.  The eight-wave fused sweep back holds 179 VGPRs against 127, so one
+                                          workgroup runs per CU where two did; the six-wave one keeps its eight sums in
+                                          LDS and fits three waves per SIMD (165 VGPRs), two workgroups per CU as before.
+                                          Measured: a batch alone runs 1.36x as fast at eight
+                                          waves per workgroup (bands of 377..504 k-mers) -- and SLOWER, 0.97-0.98x, at
+                                          six (249..376: the sweep back alone takes as long as the ring's sweep back and
+                                          expectation kernel together): leave the flag off for such batches.  The
+                                          environment variable
+                                          CPECAN_EXPECT_FUSED_WIDE=1 (read per batch) sets it for every strawMan batch of
+                                          expectations: the way in for callers of libcpecan_host.so (cpecan_trainModels),
+                                          vanillaAlign and em.PersistentEStep, together with CPECAN_WIDE_BANDS=1. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -492,7 +519,8 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *batch, int32_t *wave);
 int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
 /* *fused = 1 if the batch's E-step sums its Baum-Welch expectations inside the sweep back: the strawMan machine on the
  * wave kernels (CPECAN_EXPECT_FUSED=0 in the environment when the batch is created opts out) and, with
- * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP=1, on the workgroup kernels of one to four waves
+ * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP=1, on the workgroup kernels of one to four waves,
+ * with CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WIDE=1 on those of six and eight waves
  * (cpecan_hip_batch_kernel_family tells which): no ring of backward cells, no expectation kernel.  0 for the
  * ring-of-backward-cells path and for posterior batches. */
 int cpecan_hip_batch_expectation_pass(cpecan_batch *batch, int32_t *fused);
