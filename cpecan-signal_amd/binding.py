@@ -38,6 +38,7 @@ FLAG_WIDE_BANDS_HDP_ESTEP = 512
 FLAG_WIDE_BANDS_VANILLA_ESTEP = 1024
 FLAG_WORKGROUP_FUSED_ESTEP = 2048
 FLAG_WIDE_BANDS_FUSED_ESTEP = 4096
+FLAG_ASM_NARROW_BANDS = 8192
 MACHINE_STRAWMAN, MACHINE_DNA5, MACHINE_VANILLA, MACHINE_HDP, MACHINE_SM4, MACHINE_ECHELON = range(6)
 NUM_KMERS = 4096
 MODEL_TABLE_LEN = 1 + NUM_KMERS * 5
@@ -55,7 +56,7 @@ EXPORTS = [
     "cpecan_hip_batch_elapsed_ms", "cpecan_hip_batch_counts", "cpecan_hip_batch_fetch_pairs",
     "cpecan_hip_batch_fetch_totals", "cpecan_hip_batch_expectations_device_ptr",
     "cpecan_hip_batch_fetch_expectations", "cpecan_hip_batch_debug_cells",
-    "cpecan_hip_batch_destroy", "cpecan_hip_ctx_stream", "cpecan_hip_selftest_division", "cpecan_hip_batch_info", "cpecan_hip_plan_dispatch", "cpecan_hip_batch_stage_ms",
+    "cpecan_hip_batch_destroy", "cpecan_hip_ctx_stream", "cpecan_hip_selftest_division", "cpecan_hip_batch_info", "cpecan_hip_plan_dispatch", "cpecan_hip_plan_assembly_sweeps", "cpecan_hip_batch_stage_ms",
     "cpecan_hip_batch_systolic_rows", "cpecan_hip_batch_kernel_family", "cpecan_hip_batch_assembly_sweeps", "cpecan_hip_batch_expectation_pass", "cpecan_hip_trim_cache", "cpecan_hip_models_set_transitions",
     "cpecan_hip_models5_create", "cpecan_hip_batch_create_dna",
     "cpecan_hip_modelsv_create", "cpecan_hip_modelsv_create_scaled", "cpecan_hip_modelsv_download",
@@ -198,6 +199,7 @@ def lib():
         L.cpecan_hip_batch_systolic_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.cpecan_hip_batch_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.cpecan_hip_plan_dispatch.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 4
+        L.cpecan_hip_plan_assembly_sweeps.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)]
         L.cpecan_hip_batch_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.cpecan_hip_batch_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cpecan_hip_batch_fetch_pairs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
@@ -238,6 +240,15 @@ def plan_dispatch(machine, mode, kernel, flags, max_width, edges_step_by_one=Tru
     _check(lib().cpecan_hip_plan_dispatch(machine, mode, kernel, flags, max_width, int(edges_step_by_one),
                                           *[C.byref(o) for o in out]))
     return dict(zip(("kernel", "wave", "rows", "build_max_width"), (o.value for o in out)))
+
+
+def plan_assembly_sweeps(machine, mode, kernel, flags, max_width, edges_step_by_one=True):
+    """the cells per lane of the hand-scheduled assembly sweeps batch creation would put such a batch on (no device
+    needed): 3, 2 (FLAG_ASM_NARROW_BANDS or CPECAN_ASM_NARROW=1, bands up to 120 k-mers) or 0, the compiled sweeps"""
+    out = C.c_int32(-1)
+    cells = lib().cpecan_hip_plan_assembly_sweeps(machine, mode, kernel, flags, max_width, int(edges_step_by_one), C.byref(out))
+    assert cells == out.value
+    return cells
 
 
 def band_construct(anchors, lX, lY, expansion):

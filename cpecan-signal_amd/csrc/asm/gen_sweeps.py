@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generates the hand-scheduled gfx950 assembly of the sweeps of the banded pair-HMM (strawMan signal machine,
-posterior decode): cpecan_k_asm_forward_l3 and cpecan_k_asm_backward_l3.
+posterior decode): cpecan_k_asm_forward_l3 and cpecan_k_asm_backward_l3 at three cells per lane (bands of 121-158 k-mers)
+and, generated under CPECAN_ASM_L=2, cpecan_k_asm_forward_l2 and cpecan_k_asm_backward_l2 at two (bands up to 120).
 
 Same algorithm, same memory formats and -- bit for bit -- the same arithmetic as the compiled wave kernels
 (cpecan_kernel_wave.hip: one wave per alignment, L cells per lane, slot = matrix column mod 64 L, lane = slot / L,
@@ -18,7 +19,8 @@ Reference arithmetic: cell_calculateForward / Backward impl/pairwiseAligner.c:36
 impl/stateMachine.c:1305-1334, logAdd / lookup impl/pairwiseAligner.c:235-255, emissions_signal_logGaussPdf
 impl/stateMachine.c:333-343.
 
-usage: gen_sweeps.py OUT.s [OUT.h]   (OUT.h: the sizes and offsets the C++ side shares, cpecan_asm_gen.h)
+usage: gen_sweeps.py OUT.s [OUT.h]   (OUT.h: the sizes and offsets the C++ side shares, cpecan_asm_gen.h: ASM_* those of
+three cells per lane, ASM2_* those of two, whichever L the assembly is generated for)
 """
 import os
 import struct
@@ -26,22 +28,57 @@ import sys
 
 from emit import Emitter, Neg, Pool, S, V
 
-L = 3
+L = int(os.environ.get("CPECAN_ASM_L", "3"))                   # cells per lane
+assert L in (2, 3)
 P = 64 * L
 
 # ---------------------------------------------------------------- memory formats shared with the C++ side (cpecan_asm.h)
 # a ring row (the layout of cpecan_kernel_wave.hip, WV_ROW_*): per layer (Fm, pm) x 64 | (Fx, Fy) x 64, then the gap-Y
 # emissions of the layers two by two: (py0, py1) x 64 | (py2, unused) x 64 -- every access is 16 bytes per lane
 LAYER_BYTES = 2 * 64 * 16
-OFF_FXY = 64 * 16
-OFF_PY = L * LAYER_BYTES                 # + 1024 per pair of layers
-PY2_X2 = os.environ.get("CPECAN_ASM_PY2", "x2") == "x2"   # the odd last layer's emissions as 8 bytes per lane (less traffic) or
-                                                           # padded to 16 (fewer, faster instructions)
-ROW_BYTES = L * LAYER_BYTES + 1024 + (512 if PY2_X2 else 1024)
-ROW_DOUBLES = ROW_BYTES // 8
-assert L == 3                            # (the pairing of the gap-Y emissions below is written for three layers)
 TRACK_ROW_BYTES = 20 * 8                 # a track row: 16 emission constants, gap-X sums (open, extend, switch), gap-X
 NCONST = 18                              # ... of which a slot keeps the first 18 doubles
+LDS_EV, ROWN = 512, 64                   # (LDS of the forward kernel, below: the events' offset, the ring of k-mer rows)
+LDS_PX, PXN = 512, 64                    # (... of the backward kernel)
+OFF_FXY = 64 * 16
+PY2_X2 = os.environ.get("CPECAN_ASM_PY2", "x2") == "x2"   # the odd last layer's emissions as 8 bytes per lane (less traffic) or
+                                                           # padded to 16 (fewer, faster instructions)
+EVN = 256                                # events a forward wave keeps in LDS, by index mod EVN
+BLOCK = 64                               # diagonals per staging block
+
+
+def formats(l):
+    """what depends on the cells per lane of the formats and sizes shared with the C++ side"""
+    f = dict(L=l)
+    f["OFF_PY"] = l * LAYER_BYTES        # + 1024 per pair of layers
+    # two layers: one (py0, py1) pair and no odd last layer -- 5120 bytes, the row of the compiled _l2 build
+    f["ROW_BYTES"] = l * LAYER_BYTES + (l // 2) * 1024 + (l % 2) * (512 if PY2_X2 else 1024)
+    # the forward sweep's context (registers of a wave between two launches)
+    f["CTX_X"] = l * 9 * 1024            # (after l x 36 dwords of constants, 1024 bytes per 4 dwords) per (parity, layer): m (512 bytes), (x, y) (1024 bytes)
+    f["CTX_S"] = f["CTX_X"] + 2 * l * 1536   # scalars: masks (six dwords whatever l), band slots
+    f["CTX_BYTES"] = f["CTX_S"] + 256
+    f["LDS_F_BYTES"] = LDS_EV + ((2 * EVN + l) * 16 + 63) // 64 * 64 + ROWN * TRACK_ROW_BYTES
+    f["LDS_B_BYTES"] = LDS_PX + PXN * 16 + l * 1024
+    # The widest band.  Two things bound it.  (1) Slots: the band's k-mers and the two parked slots next to it, which
+    # the forward sweep stores and the sweep back loads as the band's -inf guards, are distinct slots: width + 2 <= 64 l.
+    # (2) The events in LDS: a block is staged when its first diagonal d0 is due, under the band of d0 - 1, up to index
+    # (d0 | 63) + 1 - xmin(d0 - 1) <= d0 + BLOCK - xmin (what the block's last step reads ahead for the next block's
+    # first diagonal, and one to spare), while the lowest index a diagonal d >= d0 reads, d - 1 - xmax(d), never falls
+    # (xmax moves by at most one a diagonal) below d0 - 2 - xmax(d0 - 1); an index lives at itself mod EVN, so nothing
+    # wanted is overwritten while (BLOCK + 2) + (xmax - xmin) < EVN: width <= EVN - BLOCK - 2 = 190, for any l.  (The
+    # rows of k-mers in LDS -- ROWN forward, PXN back -- hold what can enter during BLOCK diagonals whatever the
+    # width.)  So 126 k-mers at two cells per lane and 190 at three; the limits are set to what the kernel choice can
+    # send: 120, the whole ground of the compiled two-cell build (its 64 l - 8) -- no lower bound: a band of one k-mer is
+    # one slot and its two guards -- and at three cells the 158 of round 3, inside the bound and pinned by the tests.
+    bound = min(64 * l - 2, EVN - BLOCK - 2)
+    f["MAX_WIDTH"] = {2: 120, 3: 158}[l]
+    assert f["MAX_WIDTH"] <= bound
+    return f
+
+
+OFF_PY = formats(L)["OFF_PY"]
+ROW_BYTES = formats(L)["ROW_BYTES"]
+ROW_DOUBLES = ROW_BYTES // 8
 
 # kernel arguments: struct AsmArgs
 A_ITEMS, A_TRACKBASE, A_PLANWIN, A_PLANCTL, A_PLANOFF, A_EVENTS, A_MODELS, A_TRACK = 0, 8, 16, 24, 32, 40, 48, 56
@@ -60,28 +97,22 @@ CTL_BYTES = 32                           # per 64 diagonals: u64 stepMin, stepMa
 # WvState / WvWindow (cpecan_sweep.h)
 ST_D, ST_TB, ST_FIN, ST_WIN, ST_CELLS, ST_CLKS, ST_CLKR, STATE_BYTES = 0, 4, 8, 16, 192, 200, 208, 216   # (WvState: win[4])
 WIN_BYTES = 40
-# the forward sweep's context (registers of a wave between two launches)
+# the forward sweep's context (registers of a wave between two launches): formats()
 CTX_C = 0                                # L x 36 dwords of constants, 1024 bytes per 4 dwords
-CTX_X = L * 9 * 1024                     # per (parity, layer): m (512 bytes), (x, y) (1024 bytes)
-CTX_S = CTX_X + 2 * L * 1536             # scalars: masks, band slots
-CTX_BYTES = CTX_S + 256
+CTX_X, CTX_S, CTX_BYTES = formats(L)["CTX_X"], formats(L)["CTX_S"], formats(L)["CTX_BYTES"]
 
 # LDS of the forward kernel
 LDS_COEF = 0
-LDS_EV = 512                             # events by index mod 256, mirrored: (2 * 256 + L) x 16 bytes
-EVN = 256
+# (LDS_EV: events by index mod 256, mirrored: (2 * 256 + L) x 16 bytes)
 LDS_ROWS = LDS_EV + ((2 * EVN + L) * 16 + 63) // 64 * 64
-ROWN = 64
 LDS_F_BYTES = LDS_ROWS + ROWN * TRACK_ROW_BYTES
 # ... and of the backward kernel
-LDS_PX = 512
-PXN = 64
 LDS_RF = LDS_PX + PXN * 16               # the forward cells a refresh of totalProbability wants, fetched ahead by loads to LDS:
 LDS_RF_XY_T = LDS_RF                     # (Fx, Fy) of the refresh's diagonal t, 1024 bytes per layer
 LDS_B_BYTES = LDS_RF + L * 1024
+assert (LDS_F_BYTES, LDS_B_BYTES) == (formats(L)["LDS_F_BYTES"], formats(L)["LDS_B_BYTES"])
 
-MAX_WIDTH = 158                          # band widths the staging scheme holds
-BLOCK = 64                               # diagonals per staging block
+MAX_WIDTH = formats(L)["MAX_WIDTH"]      # band widths the staging scheme and the slots hold: derived in formats()
 
 # timing studies (tools/ablate_asm.sh): wrong results by construction, never part of the product build
 ABLATE = set(os.environ.get("CPECAN_ASM_ABLATE", "").split())
@@ -331,6 +362,8 @@ def forward_kernel(name):
         k.salu("s_lshl_b32", sT[0], sD, 6)
         k.salu("s_add_u32", sT[0], sT[0], 32)
         k.smem("s_load_dwordx4", S(sMaskS[q][0].i, 4), sMaskTab, sT[0])
+        if L == 2:                             # (no third layer, no odd last layer's emissions)
+            return
         k.salu("s_add_u32", sT[0], sT[0], 16)
         if PY2_X2:
             k.smem("s_load_dwordx2", sMaskS[q][2], sMaskTab, sT[0])
@@ -638,7 +671,7 @@ def forward_kernel(name):
         for j in range(L):
             k.add(csum[j], middle(j, 2), csum[j])
         # (the last layer's leave with the two registers after them, which hold a constant: 16 bytes per lane again)
-        if "NOPY" in ABLATE:
+        if "NOPY" in ABLATE or L % 2 == 0:
             pass
         elif PY2_X2:
             masked_store(sMaskPy2[p], 2, vOff8, PY[L - 1], OFF_PY + 1024)
@@ -979,7 +1012,7 @@ def forward_tail(k, v):
     # scalars and records leave through lane 0
     k.salu("s_mov_b64", "exec", 1)
     q4 = [pool.take(4) for _ in range(3)]
-    srcs = [sMask[0].lo, sMask[0].hi, sMask[1].lo, sMask[1].hi, sMask[2].lo, sMask[2].hi, sInL, sInJ, sOutL, sOutJ, 0, 0]
+    srcs = [h for j in range(L_) for h in (sMask[j].lo, sMask[j].hi)] + [0] * (6 - 2 * L_) + [sInL, sInJ, sOutL, sOutJ, 0, 0]
     for i, s in enumerate(srcs):
         k.valu("v_mov_b32_e32", q4[i // 4].sub(i % 4), s)
     vZ = pool.take(2)
@@ -1075,9 +1108,9 @@ def backward_kernel(name):
     t0 = b0 + 8 * L
     T = [[V(t0 + 4 * L * q + 4 * j, 4) for j in range(L)] for q in range(3)]
     p0 = t0 + 12 * L
-    # gap-Y emissions as the ring holds them: (py0, py1), (py2, unused)
-    pyw = 6 if PY2_X2 else 8
-    PYB4 = [[V(p0 + pyw * q + 4 * h, 4 if h == 0 or not PY2_X2 else 2) for h in range(2)] for q in range(3)]
+    # gap-Y emissions as the ring holds them: (py0, py1), (py2, unused) -- at two layers the one pair
+    pyw = 4 * (L // 2) + (L % 2) * (2 if PY2_X2 else 4)
+    PYB4 = [[V(p0 + pyw * q + 4 * h, 4 if h < L // 2 or not PY2_X2 else 2) for h in range((L + 1) // 2)] for q in range(3)]
     PYB = [[V(p0 + pyw * q + 2 * j, 2) for j in range(L)] for q in range(3)]
     q0 = p0 + pyw * 3
     sLmPy2 = S(64, 2)                                   # the lanes the last layer's 8-byte emissions are loaded under
@@ -1326,21 +1359,27 @@ def backward_kernel(name):
         k.add64(sRow0, sRing0, sA[0])
         k.add64(sRow1, sRing1, sA[0])
 
+    def fetch_py(q, j, masks):
+        """the gap-Y emissions that are asked for with layer j of the ring row at sRow0 -> PYB[q]: the pair of layers
+        (j - 1, j) with its second layer, under the lanes of both; an odd last layer's alone"""
+        off = OFF_PY + (j // 2) * 1024
+        if j % 2 == 1:
+            k.salu("s_or_b64", "exec", masks[j - 1], masks[j])
+            k.gload(4, PYB4[q][j // 2], vOff16, sRow0 if off < 4096 else sRow1, off % 4096)
+        elif j and j == L - 1:
+            if PY2_X2:
+                k.salu("s_mov_b64", "exec", sLmPy2)
+                k.gload(2, PYB4[q][j // 2], vOff8, sRow0 if off < 4096 else sRow1, off % 4096)
+            else:
+                k.gload(4, PYB4[q][j // 2], vOff16, sRow0 if off < 4096 else sRow1, off % 4096)
+
     def fetch_row(q, masks):
         """ring row at sRow0 -> T[q], PYB[q], each layer under its exec mask"""
         for j in range(L):
             k.salu("s_mov_b64", "exec", masks[j])
             off = j * LAYER_BYTES
             k.gload(4, T[q][j], vOff16, sRow0 if off < 4096 else sRow1, off % 4096)
-            if j:
-                if j == 1:
-                    k.salu("s_or_b64", "exec", masks[0], masks[1])
-                off = OFF_PY + (j - 1) * 1024
-                if j == 2 and PY2_X2:
-                    k.salu("s_mov_b64", "exec", sLmPy2)
-                    k.gload(2, PYB4[q][1], vOff8, sRow0 if off < 4096 else sRow1, off % 4096)
-                else:
-                    k.gload(4, PYB4[q][j - 1], vOff16, sRow0 if off < 4096 else sRow1, off % 4096)
+            fetch_py(q, j, masks)
         k.salu("s_mov_b64", "exec", -1)
 
     def load_masks(q, dreg):
@@ -1355,6 +1394,8 @@ def backward_kernel(name):
         k.salu("s_lshl_b32", sA[0], sA[0], 6)
         k.salu("s_add_u32", sA[0], sA[0], 32)
         k.smem("s_load_dwordx4", S(96, 4), sMaskTab, sA[0])
+        if L == 2:                             # (no third layer, no odd last layer's emissions)
+            return
         k.salu("s_add_u32", sA[0], sA[0], 16)
         k.smem("s_load_dwordx2", S(100, 2), sMaskTab, sA[0])
         if PY2_X2:
@@ -1472,15 +1513,8 @@ def backward_loop(k, v):
             off = j * LAYER_BYTES
             if "NOLOAD" not in ABLATE:
                 k.gload(4, T[k1][j], vOff16, sRow0 if off < 4096 else sRow1, off % 4096)
-                if j and "NOPY" not in ABLATE:
-                    if j == 1:
-                        k.salu("s_or_b64", "exec", sLm[0], sLm[1])
-                    off = OFF_PY + (j - 1) * 1024
-                    if j == 2 and PY2_X2:
-                        k.salu("s_mov_b64", "exec", sLmPy2)
-                        k.gload(2, PYB4[k1][1], vOff8, sRow0 if off < 4096 else sRow1, off % 4096)
-                    else:
-                        k.gload(4, PYB4[k1][j - 1], vOff16, sRow0 if off < 4096 else sRow1, off % 4096)
+                if "NOPY" not in ABLATE:
+                    g["fetch_py"](k1, j, sLm)
             k.salu("s_mov_b64", "exec", -1)
         k.salu("s_sub_u32", sA[1], sTd, 3)
         if "NOMASKB" not in ABLATE:
@@ -1499,7 +1533,7 @@ def backward_loop(k, v):
         k.ladd_back_group(rd, [M[kk][j] for j in range(L)])
         # ------------------------------------------------------------ tail: what diagonal t hands down, its candidates
         k.label(lbl("tail%d" % kk))
-        k.raw_wait_vm(2 * L if "NOPY" in ABLATE else 2 * (L + 2))   # this diagonal's ring row (the L + 2 loads of each of the next two may still be under way)
+        k.raw_wait_vm(2 * L if "NOPY" in ABLATE else 2 * (L + (L + 1) // 2))   # this diagonal's ring row (the L + 2 loads of each of the next two -- three at two layers -- may still be under way)
         for j in range(L):
             k.valu("v_mov_b32_e32", PMB[kk][j].lo, Tpm(kk, j).lo)
             k.valu("v_mov_b32_e32", PMB[kk][j].hi, Tpm(kk, j).hi)
@@ -1635,11 +1669,14 @@ def backward_loop(k, v):
         k.salu("s_mov_b32", sRefCnt, 9)
         # the refresh's first half: per cell of t, v = F(t) . B(t) -- (Fx, Fy) of t were fetched to LDS a refresh ago
         vPrev = pool.take(2)
-        k.valu("v_add_u32_e32", vPrev.hi, vOff16, vOff8)       # 24 * lane: a lane's three terms lie together
+        if L == 3:
+            k.valu("v_add_u32_e32", vPrev.hi, vOff16, vOff8)   # 24 * lane: a lane's three terms lie together
+        else:
+            k.valu("v_mov_b32_e32", vPrev.hi, vOff16)          # 16 * lane: its two
         xyT = [pool.take(4) for _ in range(L)]
         for j in range(L):
             k.ds_read(128, xyT[j], vOff16, LDS_RF_XY_T + j * 1024)
-        out = [pool.take(3 * 2), FBS]
+        out = [pool.take(L * 2), FBS]
         a1, a2 = [pool.take(2) for _ in range(L)], [pool.take(2) for _ in range(L)]
         for j in range(L):
             k.add(a1[j], xyT[j].sub(0, 2), BX[j])
@@ -1660,7 +1697,8 @@ def backward_loop(k, v):
         for f in range(2):
             if "NOSTORE" not in ABLATE:
                 k.gstore(4, vPrev.hi, out[f].sub(0, 4), sAp(4), f * P * 8)
-                k.gstore(2, vPrev.hi, out[f].sub(4, 2), sAp(4), f * P * 8 + 16)
+                if L == 3:
+                    k.gstore(2, vPrev.hi, out[f].sub(4, 2), sAp(4), f * P * 8 + 16)
         pool.give(vPrev, out[0])
         pool.give(*fb)
         pool.hold(*fb)
@@ -1831,8 +1869,9 @@ def main():
     name = "cpecan_k_asm_forward_l%d" % L
     k, v = forward_kernel(name)
     forward_tail(k, v)
-    kernels.append(dict(name=name, body=k.text(), lds=LDS_F_BYTES, kernarg=ARGS_BYTES, vgprs=256, sgprs=102, accum=256,
-                        stats=k.stats))
+    nv = 256 if L == 3 else (k.pool.first + 2 * k.pool.high + 7) // 8 * 8   # (three cells per lane: the whole file)
+    kernels.append(dict(name=name, body=k.text(), lds=LDS_F_BYTES, kernarg=ARGS_BYTES, vgprs=nv, sgprs=102, accum=nv,
+                        stats=dict(k.stats, vgprs=nv)))
     name = "cpecan_k_asm_backward_l%d" % L
     k, v = backward_kernel(name)
     backward_loop(k, v)
@@ -1848,9 +1887,13 @@ def main():
     text.append("amdhsa.target:   amdgcn-amd-amdhsa--gfx950\namdhsa.version:\n  - 1\n  - 2\n...\n\n\t.end_amdgpu_metadata")
     open(out, "w").write("\n".join(text) + "\n")
     if len(sys.argv) > 2:
-        defs = dict(ASM_L=L, ASM_ROW_BYTES=ROW_BYTES, ASM_LAYER_BYTES=LAYER_BYTES, ASM_OFF_FXY=OFF_FXY, ASM_OFF_PY=OFF_PY, ASM_PY2_X2=int(PY2_X2), ASM_CTX_X=CTX_X, ASM_CTX_S=CTX_S, ASM_CTX_BYTES=CTX_BYTES,
-                    ASM_MAX_WIDTH=MAX_WIDTH, ASM_PLANWIN_BYTES=PLANWIN_BYTES, ASM_CTL_BYTES=CTL_BYTES, ASM_BLOCK=BLOCK,
-                    ASM_ARGS_BYTES=ARGS_BYTES, ASM_NCONST=NCONST, ASM_MASK_BYTES=MASK_BYTES, ASM_MASK_GROUP=MASK_GROUP, ASM_LDS_F_BYTES=LDS_F_BYTES, ASM_LDS_B_BYTES=LDS_B_BYTES)
+        # ASM_*: three cells per lane and what does not depend on the cells per lane; ASM2_*: what does, at two
+        f3, f2 = formats(3), formats(2)
+        defs = dict(ASM_L=3, ASM_ROW_BYTES=f3["ROW_BYTES"], ASM_LAYER_BYTES=LAYER_BYTES, ASM_OFF_FXY=OFF_FXY, ASM_OFF_PY=f3["OFF_PY"], ASM_PY2_X2=int(PY2_X2), ASM_CTX_X=f3["CTX_X"], ASM_CTX_S=f3["CTX_S"], ASM_CTX_BYTES=f3["CTX_BYTES"],
+                    ASM_MAX_WIDTH=f3["MAX_WIDTH"], ASM_PLANWIN_BYTES=PLANWIN_BYTES, ASM_CTL_BYTES=CTL_BYTES, ASM_BLOCK=BLOCK,
+                    ASM_ARGS_BYTES=ARGS_BYTES, ASM_NCONST=NCONST, ASM_MASK_BYTES=MASK_BYTES, ASM_MASK_GROUP=MASK_GROUP, ASM_LDS_F_BYTES=f3["LDS_F_BYTES"], ASM_LDS_B_BYTES=f3["LDS_B_BYTES"])
+        for name in ("L", "ROW_BYTES", "OFF_PY", "CTX_X", "CTX_S", "CTX_BYTES", "MAX_WIDTH", "LDS_F_BYTES", "LDS_B_BYTES"):
+            defs["ASM2_" + name] = f2[name]
         with open(sys.argv[2], "w") as h:
             h.write("/* generated by asm/gen_sweeps.py: what the assembly sweeps and the C++ side agree on */\n")
             h.write("#ifndef CPECAN_ASM_GEN_H_\n#define CPECAN_ASM_GEN_H_\n")

@@ -104,6 +104,7 @@ struct cpecan_batch {
      * contexts */
     bool useAsm = false, asmBackward = false;
     int asmMaxWindows = 0;
+    int asmCells = 0;          /* cells per lane of the assembly sweeps the batch runs (useAsm): 2 or 3 */
     std::string asmSetupError; /* why a batch planned for them does not run on them (a failed setup launch) */
     DevBuf<AsmPlanWin> planWin;
     DevBuf<AsmPlanCtl> planCtl;

@@ -271,17 +271,20 @@ struct BatchEnv {
     int asmMode;      /* CPECAN_ASM: 0 the compiled kernels, 1 the assembly forward sweep only (the compiled sweep back
                          reads what it writes), otherwise and unset (-1) both assembly sweeps (tests, timing) */
     bool wave5Off;    /* CPECAN_DNA_GENERAL: the 5-state machine on the general kernel (tests, timing) */
+    bool asmNarrow;   /* CPECAN_ASM_NARROW=1: CPECAN_FLAG_ASM_NARROW_BANDS for every batch it means something to */
 };
 static BatchEnv read_batch_env() {
     static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr;
     const char *wide = getenv("CPECAN_WIDE_BANDS"), *kernels = getenv("CPECAN_KERNELS");
     const char *rows = getenv("CPECAN_SYSTOLIC_ROWS"), *as = getenv("CPECAN_ASM"), *wideH = getenv("CPECAN_WIDE_BANDS_HDP");
     const char *wideHE = getenv("CPECAN_WIDE_BANDS_HDP_ESTEP"), *wideVE = getenv("CPECAN_WIDE_BANDS_VANILLA_ESTEP");
+    const char *narrow = getenv("CPECAN_ASM_NARROW");
     const int wideFlags = (wide && atoi(wide) == 1 ? CPECAN_FLAG_WIDE_BANDS : 0) |
                           (wideH && atoi(wideH) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP : 0) |
                           (wideHE && atoi(wideHE) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP : 0) |
                           (wideVE && atoi(wideVE) == 1 ? CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP : 0);
-    return { wideFlags, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1, as ? atoi(as) : -1, wave5Off };
+    return { wideFlags, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1, as ? atoi(as) : -1, wave5Off,
+             narrow != nullptr && atoi(narrow) == 1 };
 }
 
 /* The kernel choice: a function of the machine, what the caller asked for, the environment, two facts about the
@@ -302,6 +305,7 @@ struct Dispatch {
     bool asmPlan = false;   /* the hand-scheduled assembly sweeps may take the batch, as far as the bands do not matter */
     bool asmSweeps = false; /* ... and with its bands; what is left is known at set-up (one stream group, the module) */
     bool asmBackward = false; /* ... both sweeps (CPECAN_ASM=1: the forward sweep only) */
+    int asmCells = 0;       /* cells per lane of the assembly sweeps that take it (asmSweeps): ASM_L or ASM2_L */
     int flags = 0;          /* the batch's flags (CPECAN_WIDE_BANDS=1 adds its flag where it means something) */
     int refusal = CPECAN_OK;
     char why[160] = "";
@@ -367,11 +371,16 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
             if (q.mode == CPECAN_MODE_EXPECTATIONS && !d.build->expect && !d.build->backward_fx)
                 return refuse("the chosen kernel build has no E-step");
             /* the assembly sweeps take the posterior batches of a family that has a build for them (the strawMan
-             * machine's wave family) whose bands need ASM_L cells per lane and fit their staging scheme */
+             * machine's wave family) whose bands need ASM_L cells per lane and fit their staging scheme -- and, for a
+             * batch that asked for it (CPECAN_FLAG_ASM_NARROW_BANDS, CPECAN_ASM_NARROW=1), those whose bands need
+             * ASM2_L: both sweeps at two cells per lane */
             d.asmPlan = q.mode == CPECAN_MODE_POSTERIOR && fam[ASM_L - 1]->post_asm != nullptr;
-            d.asmSweeps = d.asmPlan && q.env.asmMode != 0 && d.build->post_asm && d.build->rows == ASM_L &&
-                          q.maxWidth <= ASM_MAX_WIDTH;
             d.asmBackward = q.env.asmMode != 1;
+            const bool narrow = ((q.flags & CPECAN_FLAG_ASM_NARROW_BANDS) || q.env.asmNarrow) && d.asmBackward;
+            const int cells = d.build->rows == ASM_L && q.maxWidth <= ASM_MAX_WIDTH ? ASM_L
+                              : d.build->rows == ASM2_L && q.maxWidth <= ASM2_MAX_WIDTH && narrow ? ASM2_L : 0;
+            d.asmSweeps = d.asmPlan && q.env.asmMode != 0 && d.build->post_asm && cells != 0;
+            d.asmCells = d.asmSweeps ? cells : 0;
         }
     }
     d.wave5 = q.machine == DNA5 && !debug && !unbanded && q.maxWidth <= CP_WAVE5_MAX_WIDTH && !q.env.wave5Off &&
@@ -1075,8 +1084,9 @@ static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &
 static int asm_setup(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, Lap &lap) {
     cpecan_ctx *c = b->ctx;
     const int64_t nItems = b->nItems;
+    const AsmFormat f = asm_format(d.asmCells); /* (of the batch's cells per lane) */
     if (!d.asmSweeps || b->nGroups != 1 || b->stateBytes != (int) sizeof(WvState) ||
-        b->sy->ringRowDoubles * 8 != ASM_ROW_BYTES /* (one ring format) */ || cpecan_asm_load(c->device) != 0)
+        b->sy->ringRowDoubles * 8 != f.rowBytes /* (one ring format) */ || cpecan_asm_load(c->device) != 0)
         return CPECAN_OK;
     b->asmMaxWindows = std::max(plan.maxWindows, 1);
     {
@@ -1089,16 +1099,17 @@ static int asm_setup(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, L
         B_TRY(b->planWin.alloc(hWin.n));
         B_TRY(b->planCtl.alloc((size_t) plan.asmCtlTotal));
         B_TRY(b->planOff.alloc((size_t) nItems));
-        B_TRY(b->asmCtx.alloc((size_t) nItems * 3 * ASM_CTX_BYTES));
+        B_TRY(b->asmCtx.alloc((size_t) nItems * 3 * (size_t) f.ctxBytes));
         B_TRY(b->asmMasks.alloc((size_t) (plan.diagTotal + 2) * (ASM_MASK_BYTES / 4)));
         B_TRY(hipMemsetAsync(b->asmMasks.p + (size_t) plan.diagTotal * (ASM_MASK_BYTES / 4), 0, 2 * ASM_MASK_BYTES, c->prep));
         B_TRY(hipMemcpyAsync(b->planWin.p, hWin.p, hWin.n * sizeof(AsmPlanWin), hipMemcpyHostToDevice, c->prep));
         B_TRY(hipMemcpyAsync(b->planCtl.p, plan.asmCtl.p, (size_t) plan.asmCtlTotal * sizeof(AsmPlanCtl), hipMemcpyHostToDevice, c->prep));
         B_TRY(hipMemcpyAsync(b->planOff.p, plan.asmOff.data(), (size_t) nItems * sizeof(long long), hipMemcpyHostToDevice, c->prep));
-        hipError_t asmErr = cpecan_asm_launch_masks(c->prep, b->items.p, nItems, plan.maxDiags, b->bandTab.p, b->asmMasks.p);
+        hipError_t asmErr = cpecan_asm_launch_masks(c->prep, b->items.p, nItems, plan.maxDiags, b->bandTab.p, b->asmMasks.p,
+                                                    f.cells);
         if (asmErr == hipSuccess)
-            asmErr = cpecan_asm_launch_ctx_init(c->prep, b->items.p, nItems, b->asmCtx.p, ASM_CTX_BYTES, b->Fstore.p,
-                                                b->ringDoubles, b->ringD);
+            asmErr = cpecan_asm_launch_ctx_init(c->prep, b->items.p, nItems, b->asmCtx.p, f.ctxBytes, b->Fstore.p,
+                                                b->ringDoubles, b->ringD, f.cells);
         B_TRY(hipStreamSynchronize(c->prep)); /* hWin ends here */
         if (asmErr != hipSuccess) {
             /* the compiled kernels need none of this: the batch runs on them (cpecan_hip_batch_assembly_sweeps
@@ -1117,10 +1128,11 @@ static int asm_setup(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, L
         for (auto &e : b->evPost) B_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     b->useAsm = true;
+    b->asmCells = f.cells;
     b->asmBackward = d.asmBackward;
     if (getenv("CPECAN_ASM_TRACE"))
-        fprintf(stderr, "[cpecan asm] batch of %lld alignments, widest band %d, %d windows: assembly sweeps\n",
-                (long long) nItems, b->maxWidth, b->asmMaxWindows);
+        fprintf(stderr, "[cpecan asm] batch of %lld alignments, widest band %d, %d windows: assembly sweeps, %d cells per lane\n",
+                (long long) nItems, b->maxWidth, b->asmMaxWindows, b->asmCells);
     lap("assembly sweeps: plan upload, contexts");
     return CPECAN_OK;
 }
@@ -1359,11 +1371,11 @@ static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *
         asmArgs.planCtl = b->planCtl.p; asmArgs.planOff = b->planOff.p; asmArgs.events = b->events.p;
         asmArgs.models = table.block.p; asmArgs.track = b->track.p; asmArgs.ring = b->Fstore.p;
         asmArgs.ringDoubles = b->ringDoubles; asmArgs.states = b->syStates.p; asmArgs.ctx = b->asmCtx.p;
-        asmArgs.ctxBytes = ASM_CTX_BYTES; asmArgs.coef = cpecan_asm_coef(c->device); asmArgs.nItems = (int) b->nItems;
+        asmArgs.ctxBytes = asm_format(b->asmCells).ctxBytes; asmArgs.coef = cpecan_asm_coef(c->device); asmArgs.nItems = (int) b->nItems;
         asmArgs.ringD = b->ringD; asmArgs.maxWindows = b->asmMaxWindows; asmArgs.scratch = b->syScratch.p;
         asmArgs.scratchBytes = b->scratchBytes; asmArgs.logThrSlack = b->P.logThrSlack; asmArgs.modelStride = CP_MODEL_STRIDE;
         asmArgs.maskTab = b->asmMasks.p;
-        rc = cpecan_asm_launch_begin(L->fwd, b->items.p, b->nItems, b->Fstore.p, b->ringDoubles);
+        rc = cpecan_asm_launch_begin(L->fwd, b->items.p, b->nItems, b->Fstore.p, b->ringDoubles, b->asmCells);
         if (getenv("CPECAN_ASM_TRACE")) {
             auto span = [](const char *what, const void *p, size_t bytes) {
                 fprintf(stderr, "[cpecan asm]   %-10s %p .. %p (%zu bytes)\n", what, p, (const char *) p + bytes, bytes);
@@ -1424,7 +1436,7 @@ static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *
             HIP_TRY(hipEventRecord(e4[0], sF));
             if (n > 0 && asmRun) {
                 asmArgs.window = w;
-                rc = cpecan_asm_launch_forward(c->device, sF, &asmArgs);
+                rc = cpecan_asm_launch_forward(c->device, sF, &asmArgs, b->asmCells);
             } else if (n > 0)
                 rc = sy->forward(sF, a, w);
             HIP_TRY(hipEventRecord(e4[1], sF));
@@ -1434,7 +1446,7 @@ static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *
                 asmArgs.window = w;
                 asmArgs.scratch = a.scratch;
                 if (postAside && w >= 2) HIP_TRY(hipStreamWaitEvent(sB, b->evPost[(size_t) w - 2], 0));
-                rc = cpecan_asm_launch_backward(c->device, sB, &asmArgs);
+                rc = cpecan_asm_launch_backward(c->device, sB, &asmArgs, b->asmCells);
                 hipStream_t sP = postAside ? L->post : sB;
                 if (postAside) {
                     HIP_TRY(hipEventRecord(e4[3], sB));
@@ -1628,6 +1640,25 @@ int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int3
     if (rowsOut) *rowsOut = d.build ? d.build->rows : 0;
     if (buildMaxWidthOut) *buildMaxWidthOut = d.build ? d.build->maxWidth : 0;
     return CPECAN_OK;
+}
+
+int cpecan_hip_plan_assembly_sweeps(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t maxWidth,
+                                    int32_t edgesStepByOne, int32_t *cellsPerLaneOut) {
+    if (cellsPerLaneOut) *cellsPerLaneOut = 0;
+    if (machine < 0 || machine >= N_MACHINES) return fail(CPECAN_EINVAL, "unknown machine %d", machine), 0;
+    if (maxWidth < 0) return fail(CPECAN_EINVAL, "bad argument"), 0;
+    if (check_machine((Machine) machine, mode, flags) != CPECAN_OK) return 0;
+    DispatchQuery q = { (Machine) machine, mode, kernel, flags, 0, true, read_batch_env() };
+    const Dispatch early = choose_dispatch(q); /* (batch creation asks in this order) */
+    if (early.refusal != CPECAN_OK) return fail(early.refusal, "%s", early.why), 0;
+    q.maxWidth = maxWidth;
+    q.edgesStepByOne = edgesStepByOne != 0;
+    const Dispatch d = choose_dispatch(q);
+    if (d.refusal != CPECAN_OK) return fail(d.refusal, "%s", d.why), 0;
+    /* (the plan is made only where the early answer asked for it: the same answer for every band, as it stands) */
+    const int cells = early.asmPlan ? d.asmCells : 0;
+    if (cellsPerLaneOut) *cellsPerLaneOut = cells;
+    return cells;
 }
 
 int cpecan_hip_batch_sync(cpecan_batch *b) {

@@ -379,6 +379,29 @@ typedef struct {
                                           CPECAN_EXPECT_FUSED_WIDE=1 (read per batch) sets it for every strawMan batch of
                                           expectations: the way in for callers of libcpecan_host.so (cpecan_trainModels),
                                           vanillaAlign and em.PersistentEStep, together with CPECAN_WIDE_BANDS=1. */
+#define CPECAN_FLAG_ASM_NARROW_BANDS 8192 /* cpecan_hip_batch_create (strawMan machine) with CPECAN_MODE_POSTERIOR
+                                          only: a batch of the wave-per-alignment kernels whose widest band is at most
+                                          120 k-mers -- two cells per lane, the ground of the _l2 build: what the
+                                          reference's default diagonalExpansion of 20 and its driver's 50 give (bands of
+                                          about 72 and 102 k-mers around anchors every 50 columns) -- runs the
+                                          hand-scheduled assembly sweeps at two cells per lane
+                                          (cpecan_k_asm_forward_l2 / cpecan_k_asm_backward_l2) in place of the compiled
+                                          sweeps of that build, with everything a three-cell assembly batch has: the
+                                          three-window ring (CPECAN_FLAG_SMALL_FOOTPRINT: the two-window one), the lane
+                                          sets, the compiled post and re-sweep kernels, the compiled kernels when a
+                                          set-up launch fails, under CPECAN_ASM=0 or when the model lets gap Y switch to
+                                          gap X.  cpecan_hip_batch_assembly_sweeps reports 2,
+                                          cpecan_hip_plan_assembly_sweeps answers beforehand; the kernel, family and
+                                          build cpecan_hip_plan_dispatch names do not change.  Results are bit-identical
+                                          to the compiled kernels': pairs, their order, posteriors, totals.  Every other
+                                          batch ignores the flag: another machine, a batch of expectations, the
+                                          workgroup-per-alignment family (CPECAN_FLAG_WORKGROUP_KERNELS,
+                                          CPECAN_KERNELS=systolic), the general kernel, a band of 121 k-mers or more
+                                          (121..158 run the three-cell assembly sweeps with or without it).  Opt-in:
+                                          tests pin that such a batch without the flag runs the compiled sweeps.  The
+                                          environment variable CPECAN_ASM_NARROW=1 (read per batch) sets it for every
+                                          strawMan posterior batch: the way in for callers of libcpecan_host.so,
+                                          vanillaAlign and bench.py --band. */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -501,6 +524,15 @@ int cpecan_hip_batch_info(cpecan_batch *batch, int32_t *kernel, int32_t *workgro
 int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t max_width,
                              int32_t edges_step_by_one, int32_t *kernel_out, int32_t *wave_out, int32_t *rows_out,
                              int32_t *build_max_width_out);
+/* The same question about the hand-scheduled assembly sweeps, answered as batch creation would before it knows the
+ * device (one stream group and a module that loads are left to set-up): returns 0 if such a batch would run the
+ * compiled sweeps (or the general kernel), otherwise the cells per lane of the assembly sweeps it would run -- 3 for a
+ * strawMan posterior batch of the wave kernels with a widest band of 121..158 k-mers, 2 with
+ * CPECAN_FLAG_ASM_NARROW_BANDS or CPECAN_ASM_NARROW=1 for one of at most 120 -- and stores the same number in
+ * *cells_per_lane_out (may be NULL).  Reads the environment as batch creation does (CPECAN_ASM=0: 0).  A combination
+ * batch creation refuses gives 0 here, with the refusal in last_error. */
+int cpecan_hip_plan_assembly_sweeps(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t max_width,
+                                    int32_t edges_step_by_one, int32_t *cells_per_lane_out);
 /* Systolic path only: waves per workgroup of the kernel build the batch runs on -- the fewest whose 64 slots each
  * hold the widest band of the batch: 1 (bands up to 56 k-mers), 2 (120), 3 (184) or 4 (248).  The fewer waves an
  * alignment takes, the more alignments a CU holds (16, 8, 5, 4).  With CPECAN_FLAG_WIDE_BANDS also 6 (bands of 249..376
@@ -513,8 +545,8 @@ int cpecan_hip_batch_systolic_rows(cpecan_batch *batch, int32_t *rows);
  * on the general one. */
 int cpecan_hip_batch_kernel_family(cpecan_batch *batch, int32_t *wave);
 /* *sweeps = 1 if the batch's sweeps run on the hand-scheduled assembly kernels (strawMan machine, posterior decode,
- * bands of 121..158 k-mers: the BASELINE configs[2] shape), 2 if both the forward and the backward sweep do, 0 if on
- * the compiled kernels.  CPECAN_ASM=0 in the environment keeps every batch on the compiled kernels.  A batch planned for
+ * bands of 121..158 k-mers: the BASELINE configs[2] shape; with CPECAN_FLAG_ASM_NARROW_BANDS also bands of at most 120),
+ * 2 if both the forward and the backward sweep do, 0 if on the compiled kernels.  CPECAN_ASM=0 in the environment keeps every batch on the compiled kernels.  A batch planned for
  * them whose setup launch failed runs on the compiled kernels: 0, and last_error says why. */
 int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
 /* *fused = 1 if the batch's E-step sums its Baum-Welch expectations inside the sweep back: the strawMan machine on the
