@@ -57,7 +57,7 @@ EXPORTS = [
     "cpecan_hip_batch_fetch_totals", "cpecan_hip_batch_expectations_device_ptr",
     "cpecan_hip_batch_fetch_expectations", "cpecan_hip_batch_debug_cells",
     "cpecan_hip_batch_destroy", "cpecan_hip_ctx_stream", "cpecan_hip_selftest_division", "cpecan_hip_batch_info", "cpecan_hip_plan_dispatch", "cpecan_hip_plan_assembly_sweeps", "cpecan_hip_batch_stage_ms",
-    "cpecan_hip_batch_systolic_rows", "cpecan_hip_batch_kernel_family", "cpecan_hip_batch_assembly_sweeps", "cpecan_hip_batch_expectation_pass", "cpecan_hip_trim_cache", "cpecan_hip_models_set_transitions",
+    "cpecan_hip_batch_systolic_rows", "cpecan_hip_batch_kernel_family", "cpecan_hip_batch_assembly_sweeps", "cpecan_hip_batch_expectation_pass", "cpecan_hip_plan_expectation_pass", "cpecan_hip_trim_cache", "cpecan_hip_models_set_transitions",
     "cpecan_hip_models5_create", "cpecan_hip_batch_create_dna",
     "cpecan_hip_modelsv_create", "cpecan_hip_modelsv_create_scaled", "cpecan_hip_modelsv_download",
     "cpecan_hip_modelsv_set_skip_probs", "cpecan_hip_batch_create_vanilla", "cpecan_hip_models4_create", "cpecan_hip_batch_create_sm4",
@@ -200,6 +200,7 @@ def lib():
         L.cpecan_hip_batch_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.cpecan_hip_plan_dispatch.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 4
         L.cpecan_hip_plan_assembly_sweeps.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)]
+        L.cpecan_hip_plan_expectation_pass.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)]
         L.cpecan_hip_batch_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         L.cpecan_hip_batch_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cpecan_hip_batch_fetch_pairs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
@@ -249,6 +250,15 @@ def plan_assembly_sweeps(machine, mode, kernel, flags, max_width, edges_step_by_
     cells = lib().cpecan_hip_plan_assembly_sweeps(machine, mode, kernel, flags, max_width, int(edges_step_by_one), C.byref(out))
     assert cells == out.value
     return cells
+
+
+def plan_expectation_pass(machine, mode, kernel, flags, max_width, edges_step_by_one=True):
+    """what Batch.info()["fused_expectations"] of such a batch would be (no device needed): 1 if its E-step sums the
+    expectations inside the sweep back, 0 otherwise and for a combination that creation refuses (cpecan_hip_last_error says why)"""
+    out = C.c_int32(-1)
+    fused = lib().cpecan_hip_plan_expectation_pass(machine, mode, kernel, flags, max_width, int(edges_step_by_one), C.byref(out))
+    assert fused == out.value
+    return fused
 
 
 def band_construct(anchors, lX, lY, expansion):

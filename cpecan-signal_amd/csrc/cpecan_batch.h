@@ -1,6 +1,8 @@
 /*
- * cpecan_batch.h -- the batch, as the two files that work on it see it: cpecan_hip.hip creates, runs and destroys it,
- * cpecan_readback.hip takes a finished run to the caller's counts and pairs.  Private to the library, like cpecan_ctx.h.
+ * cpecan_batch.h -- the batch, as the three files that work on it see it: cpecan_hip.hip chooses its kernels, creates and
+ * destroys it, cpecan_run.hip queues its runs, cpecan_readback.hip takes a finished run to the caller's counts and pairs;
+ * with it the lanes a run goes on and the table of machines, which creation and the launchers both read.  Private to the
+ * library, like cpecan_ctx.h.
  */
 #ifndef CPECAN_BATCH_H
 #define CPECAN_BATCH_H
@@ -8,6 +10,8 @@
 #include "cpecan_ctx.h"
 
 #include "cpecan_asm.h"
+
+#include <atomic>
 
 struct SweepBuild; /* one compiled build of the throughput kernels (cpecan_sweep.h) */
 
@@ -39,7 +43,7 @@ struct cpecan_batch {
     DevBuf<double> events;
     DevBuf<double> Fstore, Bstore, dbgB;
     DevBuf<double> Bring; /* systolic Baum-Welch: backward cells of one window per item */
-    bool fused = false; /* strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0) or, with
+    bool fused = false; /* (Dispatch::fused) strawMan E-step on the wave kernels (unless CPECAN_EXPECT_FUSED=0) or, with
                            CPECAN_FLAG_WORKGROUP_FUSED_ESTEP / CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, on the workgroup kernels'
                            fused builds: expectations summed inside the sweep back, no B ring, no expectation kernel */
     DevBuf<long long> pairs;
@@ -57,7 +61,7 @@ struct cpecan_batch {
     long long ringDoubles = 0;
     int ringD = 0, maxLX = 0;
     int nWorkers = 0, maxWidth = 0;
-    const SweepBuild *sy = nullptr; /* systolic path: the build of the kernels the batch runs on (new_batch) */
+    const SweepBuild *sy = nullptr; /* systolic path: the build of the kernels the batch runs on (Dispatch::build, choose_dispatch) */
     int device = 0;                    /* the context's device, kept for the destructor */
     int nModels = 0;
     int expectLen = CPECAN_EXPECTATION_LEN; /* doubles per model in `expect` */
@@ -67,7 +71,7 @@ struct cpecan_batch {
      * lasts as long as its slowest workgroup).  evStage: per group, one event after every kernel. */
     int nGroups = 1;
     /* (a wave batch of one group runs on lane sets instead: gStream empty, gStreamOwned false) */
-    std::vector<hipStream_t> gStream, gStreamB; /* gStreamB: the wave kernels' backward sweeps (see batch_run) */
+    std::vector<hipStream_t> gStream, gStreamB; /* gStreamB: the wave kernels' backward sweeps (enqueue_sweeps, cpecan_run.hip) */
     bool postAside = false;            /* assembly sweeps: the totals and the decode of a window on the post lane, beside
                                           the next window's sweeps */
     std::vector<hipEvent_t> evPost;    /* ... done, per window */
@@ -116,6 +120,60 @@ struct cpecan_batch {
 /* (hidden like what cpecan_ctx.h declares; the struct above stands outside, as it did in cpecan_hip.hip: its implicit
  * destructor is among the library's weak exports, and the export list stays what it was) */
 #pragma GCC visibility push(hidden)
+
+/* The three streams a chain of batches runs on: forward (track, begin, the forward sweeps), back (the sweeps back) and
+ * post (decode and re-sweep of a window, then the run's join, counts, packing and end event).  Every context has one;
+ * a run behind a wave batch of one stream group (cpecan_hip_batch_run_after) is issued on the lanes that batch ran on,
+ * so that a chain needs three hardware queues however many batches and contexts take part, and the order on each lane
+ * orders the chain.  The forward lane is the context's first stream; back and post come with the context's first
+ * wave batch of one group (the runtime deals its few hardware queues out in the order streams are made: a context
+ * whose batches never use them -- the workgroup kernels of the E-step contexts -- leaves the queues to the others).
+ * Held by reference: by its context, and by every batch whose last run went on it (until the batch runs again or is
+ * destroyed). */
+struct LaneSet {
+    int device = 0;
+    hipStream_t fwd = nullptr, back = nullptr, post = nullptr;
+    std::mutex mu; /* held for the whole enqueue of one run: runs from two host threads do not interleave */
+    std::atomic<int> refs{ 1 };
+};
+
+/* (cpecan_run.hip) */
+hipError_t lanes_create(int device, LaneSet **out);
+void lanes_release(LaneSet *L);
+hipError_t lanes_sweeps(LaneSet *L); /* the back and post lanes, made when a batch that runs on them is created */
+
+typedef const SweepBuild *const SweepFamily[4]; /* (a family's builds by rows, cpecan_hip.hip) */
+/* One row of facts per machine (enum Machine, cpecan_ctx.h): what batch creation, the kernel choice and the launchers
+ * know about a machine they read from its row.  Its models are the context's tables[machine]. */
+enum XSource { X_KIDX, X_KID, X_CHARS }; /* what a kernel reads per X position: k-mer index, HDP k-mer id, nucleotide */
+struct MachineRow {
+    int states;        /* per cell */
+    int expectLen;     /* doubles per model of the E-step's sums */
+    int pairCapFactor; /* first guess of the pairs of an item, per element of lX + lY (ensure_counts re-runs a batch that
+                          outgrows it).  16 for the HDP machine: it scores with linear densities (quirk Q6), its posteriors
+                          are flat and far more cells pass the threshold (2887 pairs for a ~800-event read in the
+                          reference's own test); and for echelon, which emits up to 15 pairs a cell */
+    int xReach;        /* how far past lX a pair's x may lie (echelon: lX + 3), for compactPairs */
+    const char *posteriorOnly; /* the refusal of an E-step (null: the machine has one) */
+    const char *noDumps;       /* the refusal of CPECAN_FLAG_DEBUG_DUMP (null: it has cell dumps) */
+    bool bandedEstep;          /* its E-step refuses CPECAN_FLAG_UNBANDED */
+    /* the register-resident kernels: the machine's wave family and, where a batch may ask for it, its workgroup family
+     * (null: none); per mode (CPECAN_MODE_POSTERIOR, CPECAN_MODE_EXPECTATIONS) the wide builds of the workgroup family
+     * that serve it (null: none) and the flag they answer to: CPECAN_FLAG_WIDE_BANDS, CPECAN_FLAG_WIDE_BANDS_HDP,
+     * CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP or CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP (0: none) */
+    SweepFamily *wave, *workgroup;
+    struct Wide {
+        const SweepBuild *const *builds;
+        int flag;
+    } wide[2];
+    bool ownChoice; /* its create call has no kernel argument: AUTO, or the general kernel with CPECAN_FLAG_GENERAL_KERNEL */
+    /* the general kernel and what distinguishes its argument record */
+    void (*general)(DevGeneralArgs, DevParams); /* (null: cpecan_k_generale, which takes a third record) */
+    XSource x;
+    bool yAux;       /* log(event noise) per event */
+    int ldsMaxWidth; /* the widest band whose forward diagonals the general kernel keeps in LDS (0: it keeps none) */
+};
+extern const MachineRow MACHINES[N_MACHINES]; /* (cpecan_hip.hip, next to the tables of builds its rows point to) */
 
 /* the end of a posterior run, queued on the stream it ends on before its end event: its candidates packed for the host
  * (cpecan_readback.hip) */

@@ -1,7 +1,7 @@
 /*
  * cpecan_ctx.h -- what the files of the C-ABI layer share: the context, its model tables and the small helpers
- * around device memory (cpecan_hip.hip: contexts and batches; cpecan_readback.hip: what a finished run gives back;
- * cpecan_models.hip: the model tables).  The batch itself: cpecan_batch.h.  Private to the library: the functions
+ * around device memory (cpecan_hip.hip: contexts, the kernel choice and batch creation; cpecan_run.hip: how a run is queued;
+ * cpecan_readback.hip: what a finished run gives back; cpecan_models.hip: the model tables).  The batch itself: cpecan_batch.h.  Private to the library: the functions
  * declared here are defined in cpecan_hip.hip and hidden from its exports.
  */
 #ifndef CPECAN_CTX_H
@@ -193,7 +193,7 @@ struct StreamFence {
     }
 };
 
-struct LaneSet; /* the three streams a chain of batches runs on (cpecan_hip.hip) */
+struct LaneSet; /* the three streams a chain of batches runs on (cpecan_batch.h, cpecan_run.hip) */
 struct cpecan_ctx;
 
 /* The models of one machine in a context: blocks of `stride` doubles next to each other on the device (no host mirror

@@ -1,6 +1,7 @@
 /*
- * cpecan_hip.hip -- the C-ABI of include/cpecan_hip.h: contexts and batches, from creation to the end of a run (the model
- * tables: cpecan_models.hip; what a finished run gives back: cpecan_readback.hip).
+ * cpecan_hip.hip -- the C-ABI of include/cpecan_hip.h: contexts, the kernel choice (choose_dispatch, and the plan calls
+ * that ask it without a device) and batches from creation to destruction (the model tables: cpecan_models.hip; how a run
+ * is queued: cpecan_run.hip; what a finished run gives back: cpecan_readback.hip).
  *
  * Host side of the thin layer between the reference-shaped C host code and the gfx950 kernels.
  * Nothing here computes DP cells: when no GPU is usable every compute entry point fails with
@@ -11,8 +12,6 @@
 #include "cpecan_sweep.h"
 
 #include <algorithm>
-#include <array>
-#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -23,30 +22,9 @@
 
 extern "C" __global__ void cpecan_k_general(DevGeneralArgs, DevParams);
 extern "C" __global__ void cpecan_k_general4(DevGeneralArgs, DevParams);
-extern "C" __global__ void cpecan_k_generale(DevGeneralArgs, DevParams, DevEchelonArgs);
 extern "C" __global__ void cpecan_k_general5(DevGeneralArgs, DevParams);
 extern "C" __global__ void cpecan_k_generalv(DevGeneralArgs, DevParams);
 extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
-#define W5_DECLARE(L)                                                                                             \
-    extern "C" __global__ void cpecan_k_wave5_l##L(const DevItem *, DevParams, const int *, const int *,          \
-                                                   const long long *, const char *, const char *, const double *, \
-                                                   double *, long long *, double *, long long *, long long *,     \
-                                                   double *, long long *, double *);                              \
-    extern "C" __global__ void cpecan_k_wave5e_l##L(const DevItem *, DevParams, const int *, const int *,         \
-                                                    const long long *, const char *, const char *, const double *, \
-                                                    double *, long long *, double *, long long *, long long *,    \
-                                                    double *, long long *, double *);                             \
-    extern "C" __global__ void cpecan_k_wave5p_l##L(const DevItem *, DevParams, const int *, const int *,         \
-                                                    const long long *, const char *, const char *, const double *, \
-                                                    double *, long long *, double *, long long *, long long *,    \
-                                                    double *, long long *, double *);                             \
-    extern "C" __global__ void cpecan_k_wave5pe_l##L(const DevItem *, DevParams, const int *, const int *,        \
-                                                     const long long *, const char *, const char *, const double *, \
-                                                     double *, long long *, double *, long long *, long long *,   \
-                                                     double *, long long *, double *);
-W5_DECLARE(1)
-W5_DECLARE(2)
-W5_DECLARE(3)
 
 /* The builds of the throughput kernels (SweepBuild, cpecan_sweep.h), each defined next to its kernels.  Which builds
  * exist, and what each is compiled with, is the Makefile's list (SY_BUILDS, WV_BUILDS: make print-builds); the
@@ -61,10 +39,13 @@ W5_DECLARE(3)
  * strawMan machine (_r) and the vanilla machine's posterior decode (_v), CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for the
  * vanilla E-step (_ve; without it that E-step stays on the general kernel), CPECAN_FLAG_WIDE_BANDS_HDP for the HDP
  * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f: the
- * strawMan E-step summed inside the sweep back) are no choice of the dispatch's: a strawMan batch of expectations that
- * the dispatch put on the workgroup build of r waves runs on _f<r> instead when it carries
- * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, and one that it put on _r6 / _r8 runs on _f6 / _f8 when it carries
- * CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP (new_batch). */
+ * strawMan E-step summed inside the sweep back, and no other form of it) stand in for the build of as many waves that the
+ * rules above come to, as the last step of choose_dispatch and for a strawMan batch of expectations alone: _f<r> for
+ * the workgroup family's build of r waves (bands up to 248 k-mers) when the batch carries
+ * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP is 1, _f6 / _f8 for _r6 / _r8
+ * (CPECAN_FLAG_WIDE_BANDS, a widest band of 249..504 k-mers) when it carries CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP or
+ * CPECAN_EXPECT_FUSED_WIDE is 1.  Neither flag means anything to the other's range, to another machine or mode, to the
+ * wave family or to the general kernel: such a batch runs what it runs without it. */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
@@ -77,7 +58,6 @@ SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
 SWEEP_BUILD(cpecan_systolic_build_ve4) SWEEP_BUILD(cpecan_systolic_build_ve6) SWEEP_BUILD(cpecan_systolic_build_ve8)
 SWEEP_BUILD(cpecan_systolic_build_f1) SWEEP_BUILD(cpecan_systolic_build_f2) SWEEP_BUILD(cpecan_systolic_build_f3)
 SWEEP_BUILD(cpecan_systolic_build_f4) SWEEP_BUILD(cpecan_systolic_build_f6) SWEEP_BUILD(cpecan_systolic_build_f8)
-typedef const SweepBuild *const SweepFamily[4];
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
 /* (the fused E-step of the build of as many waves in SY_BUILDS) */
@@ -145,91 +125,8 @@ DevCache &pinned_cache() {
     return *c;
 }
 
-/* The three streams a chain of batches runs on: forward (track, begin, the forward sweeps), back (the sweeps back) and
- * post (decode and re-sweep of a window, then the run's join, counts, packing and end event).  Every context has one;
- * a run behind a wave batch of one stream group (cpecan_hip_batch_run_after) is issued on the lanes that batch ran on,
- * so that a chain needs three hardware queues however many batches and contexts take part, and the order on each lane
- * orders the chain.  The forward lane is the context's first stream; back and post come with the context's first
- * wave batch of one group (the runtime deals its few hardware queues out in the order streams are made: a context
- * whose batches never use them -- the workgroup kernels of the E-step contexts -- leaves the queues to the others).
- * Held by reference: by its context, and by every batch whose last run went on it (until the batch runs again or is
- * destroyed). */
-struct LaneSet {
-    int device = 0;
-    hipStream_t fwd = nullptr, back = nullptr, post = nullptr;
-    std::mutex mu; /* held for the whole enqueue of one run: runs from two host threads do not interleave */
-    std::atomic<int> refs{ 1 };
-};
-
-static void lanes_release(LaneSet *L) {
-    if (!L || --L->refs > 0) return;
-    (void) hipSetDevice(L->device);
-    for (hipStream_t s : { L->fwd, L->back, L->post })
-        if (s) {
-            (void) hipStreamSynchronize(s);
-            (void) hipStreamDestroy(s);
-        }
-    delete L;
-}
-
-static hipError_t lanes_create(int device, LaneSet **out) {
-    *out = nullptr;
-    LaneSet *L = new (std::nothrow) LaneSet();
-    if (!L) return hipErrorOutOfMemory;
-    L->device = device;
-    const hipError_t e = hipStreamCreateWithFlags(&L->fwd, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        lanes_release(L);
-        return e;
-    }
-    *out = L;
-    return hipSuccess;
-}
-
-/* the back and post lanes, made when a batch that runs on them is created */
-static hipError_t lanes_sweeps(LaneSet *L) {
-    std::lock_guard<std::mutex> hold(L->mu);
-    hipError_t e = hipSuccess;
-    for (hipStream_t *s : { &L->back, &L->post })
-        if (e == hipSuccess && !*s) e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    return e;
-}
-
-#define CP_WAVE5_PAIRED_BELOW 1536 /* alignments: below this (fewer than 1.5 per SIMD) the 5-state machine runs on two waves
-                                    * per alignment: 1.14-1.24x at 1024 alignments, 0.8-0.9x at 4096 */
-
-/* One row of facts per machine (enum Machine, cpecan_ctx.h): what batch creation, the kernel choice and the launchers
- * know about a machine they read from its row.  Its models are the context's tables[machine]. */
-enum XSource { X_KIDX, X_KID, X_CHARS }; /* what a kernel reads per X position: k-mer index, HDP k-mer id, nucleotide */
-struct MachineRow {
-    int states;        /* per cell */
-    int expectLen;     /* doubles per model of the E-step's sums */
-    int pairCapFactor; /* first guess of the pairs of an item, per element of lX + lY (ensure_counts re-runs a batch that
-                          outgrows it).  16 for the HDP machine: it scores with linear densities (quirk Q6), its posteriors
-                          are flat and far more cells pass the threshold (2887 pairs for a ~800-event read in the
-                          reference's own test); and for echelon, which emits up to 15 pairs a cell */
-    int xReach;        /* how far past lX a pair's x may lie (echelon: lX + 3), for compactPairs */
-    const char *posteriorOnly; /* the refusal of an E-step (null: the machine has one) */
-    const char *noDumps;       /* the refusal of CPECAN_FLAG_DEBUG_DUMP (null: it has cell dumps) */
-    bool bandedEstep;          /* its E-step refuses CPECAN_FLAG_UNBANDED */
-    /* the register-resident kernels: the machine's wave family and, where a batch may ask for it, its workgroup family
-     * (null: none); per mode (CPECAN_MODE_POSTERIOR, CPECAN_MODE_EXPECTATIONS) the wide builds of the workgroup family
-     * that serve it (null: none) and the flag they answer to: CPECAN_FLAG_WIDE_BANDS, CPECAN_FLAG_WIDE_BANDS_HDP,
-     * CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP or CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP (0: none) */
-    SweepFamily *wave, *workgroup;
-    struct Wide {
-        const SweepBuild *const *builds;
-        int flag;
-    } wide[2];
-    bool ownChoice; /* its create call has no kernel argument: AUTO, or the general kernel with CPECAN_FLAG_GENERAL_KERNEL */
-    /* the general kernel and what distinguishes its argument record */
-    void (*general)(DevGeneralArgs, DevParams); /* (null: cpecan_k_generale, which takes a third record) */
-    XSource x;
-    bool yAux;       /* log(event noise) per event */
-    int ldsMaxWidth; /* the widest band whose forward diagonals the general kernel keeps in LDS (0: it keeps none) */
-};
 #define NO_WIDE { nullptr, 0 }
-static const MachineRow MACHINES[N_MACHINES] = {
+const MachineRow MACHINES[N_MACHINES] = {
     /* STRAWMAN */ { 3, CPECAN_EXPECTATION_LEN, 4, 0, nullptr, nullptr, false, &WV_BUILDS, &SY_BUILDS,
                      { { SY_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS }, { SY_WIDE_BUILDS, CPECAN_FLAG_WIDE_BANDS } }, false, cpecan_k_general, X_KIDX, false, 0 },
     /* DNA5 */     { 5, CPECAN_EXPECTATION5_LEN, 4, 0, nullptr, "DNA batches: no cell dumps", true, nullptr, nullptr, { NO_WIDE, NO_WIDE },
@@ -259,8 +156,9 @@ static int check_machine(Machine machine, int mode, int flags) {
     return CPECAN_OK;
 }
 
-/* The environment switches the kernel choice reads, parsed once per batch (tests and timing tools set them between
- * batches); CPECAN_DNA_GENERAL once per process. */
+/* The environment switches that change what a batch runs on or how its storage is sized, parsed once per batch (tests
+ * and timing tools set them between batches); CPECAN_DNA_GENERAL once per process.  Nothing else between
+ * batch_create_impl and index_kmers reads the environment for such a switch (what is left there: diagnostics). */
 struct BatchEnv {
     int wideFlags;    /* the wide-band flags whose variable is 1, for every batch whose machine and mode have wide builds
                          behind that flag: CPECAN_WIDE_BANDS (CPECAN_FLAG_WIDE_BANDS), CPECAN_WIDE_BANDS_HDP (.._HDP: HDP
@@ -272,6 +170,12 @@ struct BatchEnv {
                          reads what it writes), otherwise and unset (-1) both assembly sweeps (tests, timing) */
     bool wave5Off;    /* CPECAN_DNA_GENERAL: the 5-state machine on the general kernel (tests, timing) */
     bool asmNarrow;   /* CPECAN_ASM_NARROW=1: CPECAN_FLAG_ASM_NARROW_BANDS for every batch it means something to */
+    bool fusedWorkgroup, fusedWide; /* CPECAN_EXPECT_FUSED_WORKGROUP=1, CPECAN_EXPECT_FUSED_WIDE=1: CPECAN_FLAG_WORKGROUP_FUSED_ESTEP,
+                                       CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP for every batch they mean something to */
+    bool ringEstep;      /* CPECAN_EXPECT_FUSED=0: the E-step from the ring of backward cells on the builds that have both forms */
+    int expectResweep;   /* CPECAN_EXPECT_RESWEEP, for a fused E-step (DevParams::expectResweep; unset: 0) */
+    int systolicGroups;  /* CPECAN_SYSTOLIC_GROUPS: the stream groups of a batch, 1..8 (0, unset: the family's own number) */
+    long long ringPad;   /* CPECAN_RING_PAD: doubles added to every alignment's ring (tests; unset: 0) */
 };
 static BatchEnv read_batch_env() {
     static const bool wave5Off = getenv("CPECAN_DNA_GENERAL") != nullptr;
@@ -279,12 +183,17 @@ static BatchEnv read_batch_env() {
     const char *rows = getenv("CPECAN_SYSTOLIC_ROWS"), *as = getenv("CPECAN_ASM"), *wideH = getenv("CPECAN_WIDE_BANDS_HDP");
     const char *wideHE = getenv("CPECAN_WIDE_BANDS_HDP_ESTEP"), *wideVE = getenv("CPECAN_WIDE_BANDS_VANILLA_ESTEP");
     const char *narrow = getenv("CPECAN_ASM_NARROW");
+    const char *fxw = getenv("CPECAN_EXPECT_FUSED_WORKGROUP"), *fxd = getenv("CPECAN_EXPECT_FUSED_WIDE");
+    const char *fx = getenv("CPECAN_EXPECT_FUSED"), *resweep = getenv("CPECAN_EXPECT_RESWEEP");
+    const char *groups = getenv("CPECAN_SYSTOLIC_GROUPS"), *pad = getenv("CPECAN_RING_PAD");
     const int wideFlags = (wide && atoi(wide) == 1 ? CPECAN_FLAG_WIDE_BANDS : 0) |
                           (wideH && atoi(wideH) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP : 0) |
                           (wideHE && atoi(wideHE) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP : 0) |
                           (wideVE && atoi(wideVE) == 1 ? CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP : 0);
     return { wideFlags, !(kernels && strcmp(kernels, "systolic") == 0), rows ? atoi(rows) : 1, as ? atoi(as) : -1, wave5Off,
-             narrow != nullptr && atoi(narrow) == 1 };
+             narrow != nullptr && atoi(narrow) == 1, fxw != nullptr && atoi(fxw) == 1, fxd != nullptr && atoi(fxd) == 1,
+             fx != nullptr && atoi(fx) == 0, resweep ? atoi(resweep) : 0,
+             groups ? std::min(std::max(atoi(groups), 1), 8) : 0, pad ? atoll(pad) : 0 };
 }
 
 /* The kernel choice: a function of the machine, what the caller asked for, the environment, two facts about the
@@ -300,7 +209,10 @@ struct DispatchQuery {
 };
 struct Dispatch {
     int kernel = CPECAN_KERNEL_GENERAL; /* CPECAN_KERNEL_GENERAL or _SYSTOLIC, as cpecan_hip_batch_info reports */
-    const SweepBuild *build = nullptr;  /* (null on the general kernel) */
+    const SweepBuild *build = nullptr;  /* the build the batch runs on (null on the general kernel) */
+    bool fused = false;     /* an E-step that sums its expectations inside the sweep back: no ring of backward cells, no
+                               expectation kernel (cpecan_hip_batch_expectation_pass) */
+    int expectResweep = 0;  /* ... and its DevParams::expectResweep */
     bool wave5 = false;     /* the 5-state machine's wave kernels (cpecan_kernel_wave5.hip) in place of the general one */
     bool asmPlan = false;   /* the hand-scheduled assembly sweeps may take the batch, as far as the bands do not matter */
     bool asmSweeps = false; /* ... and with its bands; what is left is known at set-up (one stream group, the module) */
@@ -381,6 +293,21 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
                               : d.build->rows == ASM2_L && q.maxWidth <= ASM2_MAX_WIDTH && narrow ? ASM2_L : 0;
             d.asmSweeps = d.asmPlan && q.env.asmMode != 0 && d.build->post_asm && cells != 0;
             d.asmCells = d.asmSweeps ? cells : 0;
+            /* the fused builds of the workgroup family, for the build of as many waves (see the tables of builds) */
+            if (q.machine == STRAWMAN && q.mode == CPECAN_MODE_EXPECTATIONS) {
+                if ((d.flags & CPECAN_FLAG_WORKGROUP_FUSED_ESTEP) || q.env.fusedWorkgroup)
+                    for (int i = 0; i < 4; i++)
+                        if (d.build == SY_BUILDS[i]) d.build = SY_FUSED_BUILDS[i];
+                if ((d.flags & CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP) || q.env.fusedWide)
+                    for (int i = 0; SY_WIDE_BUILDS[i]; i++)
+                        if (d.build == SY_WIDE_BUILDS[i]) d.build = SY_FUSED_WIDE_BUILDS[i];
+            }
+            /* the strawMan machine's E-step on the wave kernels sums its expectations inside the sweep back (same box,
+             * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 keeps
+             * the ring of backward cells and the expectation kernel.  A fused build of the workgroup family has no
+             * other form of the E-step. */
+            d.fused = q.mode == CPECAN_MODE_EXPECTATIONS && d.build->backward_fx && (!d.build->expect || !q.env.ringEstep);
+            d.expectResweep = d.fused ? q.env.expectResweep : 0;
         }
     }
     d.wave5 = q.machine == DNA5 && !debug && !unbanded && q.maxWidth <= CP_WAVE5_MAX_WIDTH && !q.env.wave5Off &&
@@ -392,9 +319,10 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
  * impl/pairwiseAligner.c:917-921 -- a function of the band alone; the same walk as the window count in batch_create) and,
  * per diagonal, whether the band's edges step and whether the forward sweep keeps all three states of the diagonal
  * (forward_window() of cpecan_kernel_wave.hip works the same rule out on the device).  tab: (first, last) column per
- * diagonal. */
-static void build_asm_plan(const int *tab, long long nDiag, const cpecan_band_params &bp, std::vector<AsmPlanWin> &wins,
-                           AsmPlanCtl *ctl) {
+ * diagonal.  belowToo: the compiled sweep back reads what the forward sweep leaves (CPECAN_ASM=1: Dispatch::asmBackward
+ * is false).  Runs on the worker threads of build_bands: it reads no environment. */
+static void build_asm_plan(const int *tab, long long nDiag, const cpecan_band_params &bp, bool belowToo,
+                           std::vector<AsmPlanWin> &wins, AsmPlanCtl *ctl) {
     const long long D = nDiag - 1;
     memset(ctl, 0, (size_t) (D / ASM_BLOCK + 2) * sizeof(AsmPlanCtl));
     wins.clear();
@@ -432,7 +360,6 @@ static void build_asm_plan(const int *tab, long long nDiag, const cpecan_band_pa
          * sweep back (CPECAN_ASM=1: tests, timing) also reads the diagonal below a refresh, the assembly one does not
          * (gen_sweeps.py: the refresh's second half is F.match + B.match of the diagonal above); everything where windows
          * are shorter than the traceback margin */
-        const bool belowToo = getenv("CPECAN_ASM") != nullptr && atoi(getenv("CPECAN_ASM")) == 1;
         const bool endW = w.atEnd != 0;
         const int tpA = w.tpost0;
         int tpB = tpA;
@@ -668,7 +595,7 @@ struct BandPlan {
     long long cellTotal = 0, pairTotal = 0, totTotal = 0, bwsTotal = 0, trackTotal = 0;
     std::vector<long long> trackBase;
     /* the assembly sweeps' plan (build_asm_plan), for the batches that can run on them */
-    bool wantAsm = false;
+    bool wantAsm = false, asmBelowToo = false;
     std::vector<std::vector<AsmPlanWin>> asmWins;
     std::vector<long long> asmOff;
     PinnedBuf<AsmPlanCtl> asmCtl;
@@ -785,7 +712,8 @@ static int build_bands(const BatchInput &in, BandPlan &plan, bool general) {
             d.nCells = cells;
             d.maxWidth = maxW;
             st.windows = std::max(st.windows, windows);
-            if (plan.wantAsm) build_asm_plan(tab, nDiag, bp, plan.asmWins[(size_t) i], plan.asmCtl.p + plan.asmOff[(size_t) i]);
+            if (plan.wantAsm)
+                build_asm_plan(tab, nDiag, bp, plan.asmBelowToo, plan.asmWins[(size_t) i], plan.asmCtl.p + plan.asmOff[(size_t) i]);
         }
     };
     if (nt <= 1) work(0);
@@ -808,10 +736,12 @@ static int build_bands(const BatchInput &in, BandPlan &plan, bool general) {
     return CPECAN_OK;
 }
 
-/* the bands, then every item's share of the batch's buffers */
-static int plan_bands(const BatchInput &in, const MachineRow &m, bool general, bool wantAsm, BandPlan &plan) {
-    plan.wantAsm = wantAsm;
-    if (wantAsm) {
+/* the bands, then every item's share of the batch's buffers (early: the kernel choice before the bands are known) */
+static int plan_bands(const BatchInput &in, const MachineRow &m, const Dispatch &early, BandPlan &plan) {
+    const bool general = early.kernel == CPECAN_KERNEL_GENERAL;
+    plan.wantAsm = early.asmPlan;
+    plan.asmBelowToo = !early.asmBackward;
+    if (plan.wantAsm) {
         plan.asmWins.resize((size_t) in.nItems);
         plan.asmOff.resize((size_t) in.nItems);
         for (int64_t i = 0; i < in.nItems; i++) {
@@ -881,26 +811,10 @@ static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput 
     b->P.scanDecode = (d.flags & CPECAN_FLAG_SCAN_DECODE) ? 1 : 0;
     b->P.logThrSlack = bp.threshold > 0.0 ? log(bp.threshold) - 1e-3 : -INFINITY;
     b->P.ldsWidth = 0; /* (set per launch by the kernels that use it) */
-    b->P.expectResweep = 0;
+    /* what the kernel choice came to is the batch's: nothing after it changes the build or the form of the E-step */
     b->sy = d.build ? d.build : SY_BUILDS[3];
-    /* CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, or CPECAN_EXPECT_FUSED_WORKGROUP=1 (read per batch): a strawMan batch of
-     * expectations that the dispatch put on one of the workgroup family's four builds (bands up to 248 k-mers) sums its
-     * expectations inside the sweep back, on the fused build of as many waves.  Every other batch -- another machine
-     * or mode, the wave family, the six- and eight-wave builds, the general kernel -- runs what it runs without it.
-     * CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, or CPECAN_EXPECT_FUSED_WIDE=1, is the same for the six- and eight-wave builds
-     * and for them alone: a strawMan batch of expectations that the dispatch put on _r6 / _r8 (CPECAN_FLAG_WIDE_BANDS, a
-     * widest band of 249..504 k-mers) runs on _f6 / _f8. */
-    {
-        const char *fxw = getenv("CPECAN_EXPECT_FUSED_WORKGROUP"), *fxd = getenv("CPECAN_EXPECT_FUSED_WIDE");
-        const bool asked = (d.flags & CPECAN_FLAG_WORKGROUP_FUSED_ESTEP) || (fxw != nullptr && atoi(fxw) == 1);
-        const bool askedWide = (d.flags & CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP) || (fxd != nullptr && atoi(fxd) == 1);
-        if (asked && machine == STRAWMAN && in.mode == CPECAN_MODE_EXPECTATIONS && d.build)
-            for (int r = 0; r < 4; r++)
-                if (d.build == SY_BUILDS[r]) b->sy = SY_FUSED_BUILDS[r];
-        if (askedWide && machine == STRAWMAN && in.mode == CPECAN_MODE_EXPECTATIONS && d.build)
-            for (int r = 0; SY_WIDE_BUILDS[r]; r++)
-                if (d.build == SY_WIDE_BUILDS[r]) b->sy = SY_FUSED_WIDE_BUILDS[r];
-    }
+    b->fused = d.fused;
+    b->P.expectResweep = d.expectResweep;
     if (d.build) b->trackRow = b->sy->once->trackRowDoubles;
     b->hItems = plan.items;
     return b;
@@ -1004,7 +918,7 @@ static int general_storage(cpecan_batch *b, const BatchInput &in, BandPlan &plan
 
 /* the register-resident kernels: one workgroup per alignment and launch; the ring of forward diagonals lives per
  * alignment because the forward and backward kernels of a window are separate launches */
-static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, Lap &lap) {
+static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, const BatchEnv &env, Lap &lap) {
     cpecan_ctx *c = b->ctx;
     const int64_t nItems = b->nItems;
     const int maxWindows = plan.maxWindows, maxSpan = plan.maxSpan;
@@ -1020,7 +934,7 @@ static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &
     while (b->ringD < (ringWindows > 1 ? ringWindows * maxSpan + 8 : maxSpan + 4)) b->ringD *= 2;
     /* the wave kernels keep one more row behind the ring: the -inf row lanes without a cell read */
     b->ringDoubles = (long long) (b->ringD + (b->sy->wave ? 1 : 0)) * b->sy->ringRowDoubles;
-    if (getenv("CPECAN_RING_PAD")) b->ringDoubles += atoll(getenv("CPECAN_RING_PAD"));
+    b->ringDoubles += env.ringPad;
     b->maxLX = plan.maxLX;
     B_TRY(b->Fstore.alloc((size_t) nItems * (size_t) b->ringDoubles));
     lap("ring allocation");
@@ -1028,15 +942,12 @@ static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &
     B_TRY(b->bandTab.alloc((size_t) plan.diagTotal * 2 + 2));
     B_TRY(hipMemcpyAsync(b->bandTab.p, plan.tab.p, (size_t) plan.diagTotal * 2 * sizeof(int), hipMemcpyHostToDevice, c->prep));
     {
-        const char *g = getenv("CPECAN_SYSTOLIC_GROUPS");
-        int G = g ? atoi(g) : b->sy->wave ? 1 : 2;
-        if (G < 1) G = 1;
-        if (G > 8) G = 8;
+        int G = env.systolicGroups ? env.systolicGroups : b->sy->wave ? 1 : 2;
         if ((int64_t) G > nItems) G = (int) nItems;
         b->nGroups = G;
         b->gStream.assign((size_t) G, nullptr);
         b->evJoin.assign((size_t) G, nullptr);
-        /* a wave batch of one group runs on lane sets (batch_run): no streams of its own, so that a chain of
+        /* a wave batch of one group runs on lane sets (cpecan_run.hip): no streams of its own, so that a chain of
          * batches stays within the four hardware queues a process gets */
         b->gStreamOwned = !(b->sy->wave && G == 1);
         if (b->gStreamOwned)
@@ -1054,15 +965,6 @@ static int sweep_storage(cpecan_batch *b, const BandPlan &plan, const Dispatch &
     }
     B_TRY(hipStreamSynchronize(c->prep));
     lap("band table upload, streams");
-    /* the strawMan machine's E-step on the wave kernels sums its expectations inside the sweep back (same box,
-     * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 (read per
-     * batch) keeps the ring of backward cells and the expectation kernel */
-    const char *fxEnv = getenv("CPECAN_EXPECT_FUSED");
-    /* (a fused build of the workgroup family, new_batch's choice, has no other form of the E-step) */
-    if (b->mode == CPECAN_MODE_EXPECTATIONS && b->sy->backward_fx && (!b->sy->expect || !(fxEnv != nullptr && atoi(fxEnv) == 0))) {
-        b->fused = true;
-        b->P.expectResweep = getenv("CPECAN_EXPECT_RESWEEP") != nullptr ? atoi(getenv("CPECAN_EXPECT_RESWEEP")) : 0;
-    }
     if (b->mode == CPECAN_MODE_EXPECTATIONS && !b->fused)
         B_TRY(b->Bring.alloc((size_t) nItems * (size_t) b->ringD * (size_t) b->sy->bringRowDoubles));
     b->stateBytes = b->sy->once->stateBytes;
@@ -1120,7 +1022,7 @@ static int asm_setup(cpecan_batch *b, const BandPlan &plan, const Dispatch &d, L
         }
     }
     if (b->ringD >= 3 * plan.maxSpan + 8 || plan.maxWindows <= 2) {
-        /* the post kernel of a window runs beside the next window's sweeps (batch_run): the sweep back of window
+        /* the post kernel of a window runs beside the next window's sweeps (enqueue_sweeps, cpecan_run.hip): the sweep back of window
          * w+1 fills one half of the scratch while the post kernel of window w reads the other */
         B_TRY(b->syScratch.alloc(2 * (size_t) nItems * (size_t) b->scratchBytes));
         b->postAside = true;
@@ -1195,7 +1097,7 @@ static int batch_create_impl(cpecan_ctx *c, Machine machine, const cpecan_item *
     BandPlan plan;
     StreamFence prepFence{ c->prep, nullptr }; /* (the plan's pinned blocks are uploaded through it) */
     if ((rc = check_items(c, machine, in, plan)) != CPECAN_OK) return rc;
-    if ((rc = plan_bands(in, m, early.kernel == CPECAN_KERNEL_GENERAL, early.asmPlan, plan)) != CPECAN_OK) return rc;
+    if ((rc = plan_bands(in, m, early, plan)) != CPECAN_OK) return rc;
     lap("band construction and window schedule (host)");
     q.maxWidth = plan.maxWidth;
     q.edgesStepByOne = plan.edgesStepByOne;
@@ -1210,7 +1112,7 @@ static int batch_create_impl(cpecan_ctx *c, Machine machine, const cpecan_item *
     if ((rc = alloc_outputs(b, plan)) != CPECAN_OK) return rc;
     lap("output buffers");
     if (d.kernel == CPECAN_KERNEL_GENERAL) rc = general_storage(b, in, plan);
-    else if ((rc = sweep_storage(b, plan, d, lap)) == CPECAN_OK) rc = asm_setup(b, plan, d, lap);
+    else if ((rc = sweep_storage(b, plan, d, q.env, lap)) == CPECAN_OK) rc = asm_setup(b, plan, d, lap);
     if (rc != CPECAN_OK) return rc;
     B_TRY(hipEventCreate(&b->ev0));
     B_TRY(hipEventCreate(&b->ev1));
@@ -1277,268 +1179,6 @@ int cpecan_hip_batch_create_echelon(cpecan_ctx *c, const cpecan_item *items, int
                              CPECAN_MODE_POSTERIOR, CPECAN_KERNEL_GENERAL, flags, out);
 }
 
-} // extern "C"
-
-/* The 5-state machine for bands a wave covers in one to three cells per lane: one wave per alignment, the recurrence in
- * registers (cpecan_kernel_wave5.hip), posterior decode or expectations */
-static int enqueue_wave5(cpecan_batch *b, hipStream_t st) {
-    cpecan_ctx *c = b->ctx;
-    const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
-    /* a batch that leaves SIMDs with fewer than two waves runs the sweeps of an alignment on a pair of waves
-     * (forward and back overlapping); CPECAN_WAVE5_PAIRED=0/1 forces either form (tests, timing) */
-    const char *pairedEnv = getenv("CPECAN_WAVE5_PAIRED");
-    const int l5 = b->maxWidth <= 64 ? 0 : b->maxWidth <= 128 ? 1 : 2;
-    /* (the one-wave E-step at three cells per lane needs more registers than two waves of a SIMD can have) */
-    const bool paired = pairedEnv ? atoi(pairedEnv) != 0 : (b->nItems < CP_WAVE5_PAIRED_BELOW || (em && l5 == 2));
-    static const auto kernels5 = std::array<decltype(&cpecan_k_wave5_l1), 12>{
-        cpecan_k_wave5_l1, cpecan_k_wave5_l2, cpecan_k_wave5_l3, cpecan_k_wave5e_l1, cpecan_k_wave5e_l2, cpecan_k_wave5e_l3,
-        cpecan_k_wave5p_l1, cpecan_k_wave5p_l2, cpecan_k_wave5p_l3, cpecan_k_wave5pe_l1, cpecan_k_wave5pe_l2, cpecan_k_wave5pe_l3 };
-    auto kernel5 = kernels5[(size_t) ((paired ? 6 : 0) + (em ? 3 : 0) + l5)];
-    hipLaunchKernelGGL(kernel5, dim3((unsigned) b->nItems), dim3(paired ? 128 : 64), 0, st, (const DevItem *) b->items.p, b->P,
-                       (const int *) b->bandL.p, (const int *) b->bandR.p, (const long long *) b->cellPrefix.p,
-                       (const char *) b->chars.p, (const char *) b->charsY.p, (const double *) c->tables[DNA5].block.p,
-                       b->Fstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p, b->totVal.p, b->nTot.p,
-                       em ? b->expect.p : nullptr);
-    HIP_TRY(hipGetLastError());
-    return CPECAN_OK;
-}
-
-/* The general kernels (cpecan_general.h): one per machine, one parameter list filled from the machine's row */
-static int enqueue_general(cpecan_batch *b, hipStream_t st) {
-    cpecan_ctx *c = b->ctx;
-    const MachineRow &m = MACHINES[b->machine];
-    const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
-    const void *x = m.x == X_CHARS ? (const void *) b->chars.p : m.x == X_KID ? (const void *) b->kid.p : (const void *) b->kidx.p;
-    const void *y = m.x == X_CHARS ? (const void *) b->charsY.p : (const void *) b->events.p; /* (nucleotides on both sides) */
-    DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
-                         (const long long *) b->cellPrefix.p, x, y, m.yAux ? (const double *) b->logNoise.p : nullptr,
-                         c->tables[b->machine].block.p, b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p,
-                         b->totVal.p, b->nTot.p, b->dbgB.p, em ? b->expect.p : nullptr };
-    DevParams P = b->P;
-    /* the forward sweep's two previous diagonals live in LDS where the widest band fits (three diagonals of the
-     * machine's states: 120 bytes per cell of width for the 5-state machine); CPECAN_GENERAL_LDS=0 keeps them in HBM
-     * (timing, tests) */
-    static const bool ldsOff = getenv("CPECAN_GENERAL_LDS") != nullptr && atoi(getenv("CPECAN_GENERAL_LDS")) == 0;
-    P.ldsWidth = (!ldsOff && b->maxWidth <= m.ldsMaxWidth) ? b->maxWidth : 0;
-    const size_t lds = (size_t) P.ldsWidth * 3 * m.states * sizeof(double);
-    if (m.general)
-        hipLaunchKernelGGL(m.general, dim3((unsigned) b->nItems), dim3(256), lds, st, a, P);
-    else { /* (cpecan_kernel_generale.hip) */
-        DevEchelonArgs e = { (const char *) b->chars.p, (const long long *) b->xEnd.p, (const double *) b->duration.p };
-        hipLaunchKernelGGL(cpecan_k_generale, dim3((unsigned) b->nItems), dim3(256), 0, st, a, P, e);
-    }
-    HIP_TRY(hipGetLastError());
-    return CPECAN_OK;
-}
-
-/* The throughput kernels, one pass: the per-item track of emission constants (a function of the inputs, rebuilt every
- * run inside the timed region), then for every traceback window the forward kernel and the backward kernel.  The wave
- * kernels run the two on streams of their own: the sweep back of window w overlaps the forward sweep of window w+1 of the
- * same alignments (each SIMD then holds a forward and a backward wave), and forward w+2, which re-uses window w's ring
- * rows, waits for the sweep back of w.  Events around every kernel give per-kernel times and carry the dependencies.
- * *sEnd: the stream the run ends on (the post lane where it went over the three lanes: *laneRun). */
-static int enqueue_sweeps(cpecan_batch *b, LaneSet *L, hipStream_t *sEnd, bool *laneRun) {
-    cpecan_ctx *c = b->ctx;
-    const SweepBuild *sy = b->sy;
-    const int G = b->nGroups, perGroup = 4 * b->nWindows + 1;
-    if (b->evStage.size() != (size_t) (G * perGroup)) {
-        for (hipEvent_t e : b->evStage) (void) hipEventDestroy(e);
-        b->evStage.assign((size_t) (G * perGroup), nullptr);
-        for (auto &e : b->evStage) HIP_TRY(hipEventCreate(&e));
-    }
-    SweepArgs all{};
-    all.items = b->items.p; all.nItems = b->nItems; all.P = b->P; all.bandTab = (const int2 *) b->bandTab.p;
-    all.track = b->track.p; all.trackBase = b->trackBase.p; all.maxLX = b->maxLX; all.events = b->events.p;
-    all.kidx = b->kidx.p; all.kid = b->kid.p; all.Fring = b->Fstore.p; all.ringDoubles = b->ringDoubles;
-    all.ringD = b->ringD; all.states = b->syStates.p; all.stateBytes = b->stateBytes; all.pairs = b->pairs.p;
-    all.pairLogp = b->pairLogp.p; all.totXay = b->totXay.p; all.totVal = b->totVal.p; all.scratch = b->syScratch.p;
-    all.scratchBytes = b->scratchBytes; all.Bring = b->Bring.p; all.bringRow = sy->bringRowDoubles;
-    all.expect = b->expect.p; all.nPairs = b->nPairs.p; all.nTot = b->nTot.p; all.nCells = b->nCells.p;
-    /* the models as the sweeps read them, and whether any of them lets gap Y switch to gap X (the nanopore default
-     * does not, stateMachine.c:1287: the kernels then run the build without that term; the vanilla machine has no such
-     * transition) */
-    const ModelTable &table = c->tables[b->machine];
-    all.models = table.block.p;
-    if (sy->machine == SWEEP_HDP || sy->machine == SWEEP_STRAWMAN)
-        for (double switchToX : table.side)
-            if (switchToX > -INFINITY) all.withSwitch = 1;
-    int rc = sy->once->launch_track(L->fwd, all);
-    /* the assembly sweeps (no model of the batch may let gap Y switch to gap X: they have no such term) */
-    const bool asmRun = b->useAsm && !all.withSwitch && rc == 0;
-    AsmArgs asmArgs{};
-    if (asmRun) {
-        asmArgs.items = b->items.p; asmArgs.trackBase = b->trackBase.p; asmArgs.planWin = b->planWin.p;
-        asmArgs.planCtl = b->planCtl.p; asmArgs.planOff = b->planOff.p; asmArgs.events = b->events.p;
-        asmArgs.models = table.block.p; asmArgs.track = b->track.p; asmArgs.ring = b->Fstore.p;
-        asmArgs.ringDoubles = b->ringDoubles; asmArgs.states = b->syStates.p; asmArgs.ctx = b->asmCtx.p;
-        asmArgs.ctxBytes = asm_format(b->asmCells).ctxBytes; asmArgs.coef = cpecan_asm_coef(c->device); asmArgs.nItems = (int) b->nItems;
-        asmArgs.ringD = b->ringD; asmArgs.maxWindows = b->asmMaxWindows; asmArgs.scratch = b->syScratch.p;
-        asmArgs.scratchBytes = b->scratchBytes; asmArgs.logThrSlack = b->P.logThrSlack; asmArgs.modelStride = CP_MODEL_STRIDE;
-        asmArgs.maskTab = b->asmMasks.p;
-        rc = cpecan_asm_launch_begin(L->fwd, b->items.p, b->nItems, b->Fstore.p, b->ringDoubles, b->asmCells);
-        if (getenv("CPECAN_ASM_TRACE")) {
-            auto span = [](const char *what, const void *p, size_t bytes) {
-                fprintf(stderr, "[cpecan asm]   %-10s %p .. %p (%zu bytes)\n", what, p, (const char *) p + bytes, bytes);
-            };
-            span("items", b->items.p, b->items.n * sizeof(DevItem));
-            span("trackBase", b->trackBase.p, b->trackBase.n * 8);
-            span("planWin", b->planWin.p, b->planWin.n * sizeof(AsmPlanWin));
-            span("planCtl", b->planCtl.p, b->planCtl.n * sizeof(AsmPlanCtl));
-            span("planOff", b->planOff.p, b->planOff.n * 8);
-            span("events", b->events.p, b->events.n * 8);
-            span("models", table.block.p, table.block.n * 8);
-            span("track", b->track.p, b->track.n * 8);
-            span("ring", b->Fstore.p, b->Fstore.n * 8);
-            span("states", b->syStates.p, b->syStates.n);
-            span("ctx", b->asmCtx.p, b->asmCtx.n);
-            span("scratch", b->syScratch.p, b->syScratch.n);
-            span("masks", b->asmMasks.p, b->asmMasks.n * 4);
-            span("coef", asmArgs.coef, 512);
-            fprintf(stderr, "[cpecan asm]   ringD %d ringDoubles %lld windows %d scratchBytes %lld\n", b->ringD, b->ringDoubles,
-                    b->asmMaxWindows, b->scratchBytes);
-        }
-    }
-    HIP_TRY(hipEventRecord(b->evFork, L->fwd));
-    *laneRun = !b->gStreamOwned;
-    if (*laneRun && (!L->back || !L->post)) return fail(CPECAN_EHIP, "lane set without its sweep lanes");
-    if (*laneRun) *sEnd = L->post;
-#ifdef CPECAN_TIMING_BUILD
-    static const bool fwdOnly = getenv("CPECAN_TIMING_FORWARD_ONLY") != nullptr; /* timing study: wrong results */
-    static const bool noPost = getenv("CPECAN_TIMING_NO_POST") != nullptr;       /* timing study: sweeps only */
-#else
-    const bool fwdOnly = false, noPost = false;
-#endif
-    const long long per = (b->nItems + G - 1) / G;
-    for (int gi = 0; gi < G && rc == 0; gi++) {
-        const long long i0 = gi * per, n = std::min<long long>(per, b->nItems - i0);
-        SweepArgs a = all.slice(i0, n);
-        hipStream_t sF = *laneRun ? L->fwd : b->gStream[(size_t) gi];
-        hipStream_t sB = *laneRun ? L->back : sy->wave ? b->gStreamB[(size_t) gi] : sF;
-#ifdef CPECAN_TIMING_BUILD
-        if (getenv("CPECAN_TIMING_SERIAL")) sB = sF; /* timing study: every sweep alone on the chip */
-#endif
-        hipEvent_t *ev = b->evStage.data() + (size_t) gi * perGroup;
-        HIP_TRY(hipStreamWaitEvent(sF, b->evFork, 0));
-        if (sB != sF) HIP_TRY(hipStreamWaitEvent(sB, b->evFork, 0));
-        HIP_TRY(hipEventRecord(ev[0], sF));
-        for (int w = 0; w < b->nWindows && rc == 0; w++) {
-            hipEvent_t *e4 = ev + 1 + 4 * w;
-            /* assembly sweeps: the window's totals and decode (and the re-sweep of what cannot be trusted) run on a
-             * stream of their own.  The sweep back of the next window does not wait for them (it fills the other
-             * half of the scratch), nor does the forward sweep of window w+2 (the ring holds three windows, the
-             * state four window records); what does: the sweep back of w+2 (scratch), the forward sweep of w+3
-             * (ring rows, window record).  The forward sweep of w+2 still waits for the sweep back of w, which reads
-             * the context that sweep will overwrite when it ends. */
-            const bool postAside = asmRun && b->asmBackward && sB != sF && b->postAside && *laneRun;
-            if (postAside) a.scratch = b->syScratch.p + (size_t) (w & 1) * (size_t) b->nItems * (size_t) b->scratchBytes;
-            if (sB != sF && w >= 2) HIP_TRY(hipStreamWaitEvent(sF, ev[1 + 4 * (w - 2) + 3], 0));
-            if (postAside && w >= 3) HIP_TRY(hipStreamWaitEvent(sF, b->evPost[(size_t) w - 3], 0));
-            HIP_TRY(hipEventRecord(e4[0], sF));
-            if (n > 0 && asmRun) {
-                asmArgs.window = w;
-                rc = cpecan_asm_launch_forward(c->device, sF, &asmArgs, b->asmCells);
-            } else if (n > 0)
-                rc = sy->forward(sF, a, w);
-            HIP_TRY(hipEventRecord(e4[1], sF));
-            if (sB != sF) HIP_TRY(hipStreamWaitEvent(sB, e4[1], 0));
-            HIP_TRY(hipEventRecord(e4[2], sB));
-            if (rc == 0 && n > 0 && asmRun && b->asmBackward && !fwdOnly) {
-                asmArgs.window = w;
-                asmArgs.scratch = a.scratch;
-                if (postAside && w >= 2) HIP_TRY(hipStreamWaitEvent(sB, b->evPost[(size_t) w - 2], 0));
-                rc = cpecan_asm_launch_backward(c->device, sB, &asmArgs, b->asmCells);
-                hipStream_t sP = postAside ? L->post : sB;
-                if (postAside) {
-                    HIP_TRY(hipEventRecord(e4[3], sB));
-                    HIP_TRY(hipStreamWaitEvent(sP, e4[3], 0));
-                }
-                if (rc == 0 && !noPost) rc = sy->post_asm(sP, a, w);
-                if (postAside) HIP_TRY(hipEventRecord(b->evPost[(size_t) w], sP));
-            } else if (rc == 0 && n > 0 && !fwdOnly)
-                rc = (b->fused ? sy->backward_fx : sy->backward)(sB, a, w);
-            if (rc == 0 && n > 0 && b->mode == CPECAN_MODE_EXPECTATIONS && !b->fused) rc = sy->expect(sB, a, w);
-            if (!postAside) HIP_TRY(hipEventRecord(e4[3], sB));
-        }
-        /* the last sweep back follows every forward sweep; the run ends behind it on the post lane (after the last
-         * post kernel there), which leaves the forward lane to the next run's first forward sweep */
-        HIP_TRY(hipEventRecord(b->evJoin[(size_t) gi], sB));
-        HIP_TRY(hipStreamWaitEvent(*sEnd, b->evJoin[(size_t) gi], 0));
-    }
-    if (rc == 0) rc = sy->once->launch_counts(*sEnd, all);
-    if (rc != 0) return fail(CPECAN_EHIP, "throughput kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return CPECAN_OK;
-}
-
-/* One run of the batch, queued on the lane set L (its mutex held).  A wave batch of one stream group runs over the
- * three lanes and ends on the post lane; every other batch runs on the forward lane (and streams of its own). */
-static int batch_enqueue(cpecan_batch *b, cpecan_batch *after, LaneSet *L) {
-    /* its own last run first, wherever it went (the ring, state and scratch are the batch's); then the batch it follows,
-     * unless stream order on the lanes already puts this run behind it */
-    if (b->ran) HIP_TRY(hipStreamWaitEvent(L->fwd, b->ev2, 0));
-    if (after && !(after->laneRun && after->runLanes == L)) HIP_TRY(hipStreamWaitEvent(L->fwd, after->ev2, 0));
-    hipStream_t sEnd = L->fwd; /* where the run ends: counts, packing, ev2 */
-    bool laneRun = false;
-    b->countsValid = false;
-    int rc;
-    HIP_TRY(hipEventRecord(b->ev0, L->fwd));
-    if (b->mode == CPECAN_MODE_EXPECTATIONS)
-        HIP_TRY(hipMemsetAsync(b->expect.p, 0, b->expect.n * sizeof(double), L->fwd));
-    HIP_TRY(hipEventRecord(b->ev1, L->fwd));
-    if (b->wave5)
-        rc = enqueue_wave5(b, L->fwd);
-    else if (b->kernel == CPECAN_KERNEL_GENERAL)
-        rc = enqueue_general(b, L->fwd);
-    else
-        rc = enqueue_sweeps(b, L, &sEnd, &laneRun);
-    if (rc != CPECAN_OK) return rc;
-    if ((rc = pack_in_run(b, sEnd)) != CPECAN_OK) return rc;
-    HIP_TRY(hipEventRecord(b->ev2, sEnd));
-    b->ran = true;
-    b->laneRun = laneRun;
-    return CPECAN_OK;
-}
-
-extern "C" {
-
-int cpecan_hip_batch_run(cpecan_batch *b) { return cpecan_hip_batch_run_after(b, nullptr); }
-
-int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
-    if (!b) return fail(CPECAN_EINVAL, "batch is NULL");
-    cpecan_ctx *c = b->ctx;
-    if (!c) return fail(CPECAN_EINVAL, "the batch's context has been destroyed");
-    if (b->modelEpoch != c->modelEpoch)
-        return fail(CPECAN_EINVAL, "cpecan_hip_models_clear was called on the context after this batch was created: "
-                    "its model ids are gone");
-    if (after && after->device != b->device) return fail(CPECAN_EINVAL, "the two batches live on different devices");
-    HIP_TRY(hipSetDevice(c->device));
-    if (after == b || (after && !after->ran)) after = nullptr;
-    /* behind a wave batch of one stream group, the whole run goes on the lanes that batch ran on: this batch's first
-     * forward sweep follows that batch's LAST FORWARD sweep on the forward lane and shares the SIMDs with its last
-     * sweep back, as the forward sweep of that batch's own next window would have; its sweeps back and post kernels
-     * queue behind that batch's on the other two lanes.  Otherwise on this context's lanes, behind the whole run of
-     * `after`. */
-    LaneSet *L = (after && after->laneRun && after->runLanes) ? after->runLanes : c->lanes;
-    std::lock_guard<std::mutex> hold(L->mu);
-    if (b->runLanes != L) {
-        L->refs++;
-        lanes_release(b->runLanes);
-        b->runLanes = L;
-    }
-    const int rc = batch_enqueue(b, after, L);
-    if (rc != CPECAN_OK) {
-        /* what was queued of the run is over before the error goes back (sync and destroy wait for its end event,
-         * which it never recorded) */
-        for (hipStream_t s : { L->fwd, L->back, L->post })
-            if (s) (void) hipStreamSynchronize(s);
-        if (b->gStreamOwned)
-            for (hipStream_t s : b->gStream) (void) hipStreamSynchronize(s);
-        for (hipStream_t s : b->gStreamB) (void) hipStreamSynchronize(s);
-        b->ran = false;
-        b->laneRun = false;
-    }
-    return rc;
-}
-
 int cpecan_hip_batch_systolic_rows(cpecan_batch *b, int32_t *rows) {
     if (!b || !rows) return fail(CPECAN_EINVAL, "bad argument");
     if (b->kernel != CPECAN_KERNEL_SYSTOLIC) return fail(CPECAN_EINVAL, "not a systolic batch");
@@ -1570,49 +1210,6 @@ int cpecan_hip_batch_assembly_sweeps(cpecan_batch *b, int32_t *sweeps) {
     return CPECAN_OK;
 }
 
-int cpecan_hip_batch_stage_ms(cpecan_batch *b, float *msForward, float *msBackward, int32_t *launchesEach) {
-    if (!b || !b->ran) return fail(CPECAN_EINVAL, "batch has not run");
-    if (b->kernel != CPECAN_KERNEL_SYSTOLIC) return fail(CPECAN_EINVAL, "only the systolic path has stages");
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipEventSynchronize(b->ev2));
-    float f = 0, k = 0;
-    const int perGroup = 4 * b->nWindows + 1;
-    for (int gi = 0; gi < b->nGroups; gi++)
-        for (int w = 0; w < b->nWindows; w++) {
-            const hipEvent_t *ev = b->evStage.data() + (size_t) gi * perGroup + 1 + 4 * w;
-            float a = 0, c2 = 0;
-            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-            HIP_TRY(hipEventElapsedTime(&c2, ev[2], ev[3]));
-            f += a;
-            k += c2;
-        }
-    static const bool timeline = getenv("CPECAN_TIMELINE") != nullptr; /* timing study: when every stage began and ended */
-    if (timeline) {
-        const hipEvent_t *ev = b->evStage.data();
-        for (int w = 0; w < b->nWindows; w++) {
-            float t[4] = { 0, 0, 0, 0 };
-            for (int q = 0; q < 4; q++) (void) hipEventElapsedTime(&t[q], ev[0], ev[1 + 4 * w + q]);
-            fprintf(stderr, "[cpecan timeline] window %2d: forward %7.3f .. %7.3f   backward+post %7.3f .. %7.3f\n", w, t[0], t[1],
-                    t[2], t[3]);
-        }
-    }
-    if (msForward) *msForward = f;
-    if (msBackward) *msBackward = k;
-    if (launchesEach) *launchesEach = b->nWindows * b->nGroups;
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_shader_clock_mhz(cpecan_batch *b, double *mhz) {
-    if (!b || !mhz) return fail(CPECAN_EINVAL, "bad argument");
-    *mhz = 0.0;
-    if (!b->ran || b->kernel != CPECAN_KERNEL_SYSTOLIC || !b->sy->wave) return CPECAN_OK; /* not measured on this path */
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipEventSynchronize(b->ev2));
-    if (cpecan_wave_shader_clock_mhz(b->ctx->prep, b->syStates.p, b->nItems, mhz) != 0)
-        return fail(CPECAN_EHIP, "reading the sweeps' clock counters failed");
-    return CPECAN_OK;
-}
-
 int cpecan_hip_batch_info(cpecan_batch *b, int32_t *kernel, int32_t *workgroups, int32_t *maxWidth) {
     if (!b) return fail(CPECAN_EINVAL, "batch is NULL");
     if (kernel) *kernel = b->kernel;
@@ -1621,20 +1218,30 @@ int cpecan_hip_batch_info(cpecan_batch *b, int32_t *kernel, int32_t *workgroups,
     return CPECAN_OK;
 }
 
-int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t maxWidth,
-                             int32_t edgesStepByOne, int32_t *kernelOut, int32_t *waveOut, int32_t *rowsOut,
-                             int32_t *buildMaxWidthOut) {
+/* The question of the plan calls, asked as batch creation asks it: what the machine refuses, the kernel choice before
+ * the bands are known (*early), then with them (*d).  A refusal leaves its code and text as creation would. */
+static int plan_query(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t maxWidth, int32_t edgesStepByOne,
+                      Dispatch *early, Dispatch *d) {
     if (machine < 0 || machine >= N_MACHINES) return fail(CPECAN_EINVAL, "unknown machine %d", machine);
     if (maxWidth < 0) return fail(CPECAN_EINVAL, "bad argument");
     const int rc = check_machine((Machine) machine, mode, flags);
     if (rc != CPECAN_OK) return rc;
     DispatchQuery q = { (Machine) machine, mode, kernel, flags, 0, true, read_batch_env() };
-    const Dispatch early = choose_dispatch(q); /* (batch creation asks in this order) */
-    if (early.refusal != CPECAN_OK) return fail(early.refusal, "%s", early.why);
+    *early = choose_dispatch(q);
+    if (early->refusal != CPECAN_OK) return fail(early->refusal, "%s", early->why);
     q.maxWidth = maxWidth;
     q.edgesStepByOne = edgesStepByOne != 0;
-    const Dispatch d = choose_dispatch(q);
-    if (d.refusal != CPECAN_OK) return fail(d.refusal, "%s", d.why);
+    *d = choose_dispatch(q);
+    if (d->refusal != CPECAN_OK) return fail(d->refusal, "%s", d->why);
+    return CPECAN_OK;
+}
+
+int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t maxWidth,
+                             int32_t edgesStepByOne, int32_t *kernelOut, int32_t *waveOut, int32_t *rowsOut,
+                             int32_t *buildMaxWidthOut) {
+    Dispatch early, d;
+    const int rc = plan_query(machine, mode, kernel, flags, maxWidth, edgesStepByOne, &early, &d);
+    if (rc != CPECAN_OK) return rc;
     if (kernelOut) *kernelOut = d.kernel;
     if (waveOut) *waveOut = d.wave5 || (d.build && d.build->wave) ? 1 : 0;
     if (rowsOut) *rowsOut = d.build ? d.build->rows : 0;
@@ -1645,40 +1252,21 @@ int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int3
 int cpecan_hip_plan_assembly_sweeps(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t maxWidth,
                                     int32_t edgesStepByOne, int32_t *cellsPerLaneOut) {
     if (cellsPerLaneOut) *cellsPerLaneOut = 0;
-    if (machine < 0 || machine >= N_MACHINES) return fail(CPECAN_EINVAL, "unknown machine %d", machine), 0;
-    if (maxWidth < 0) return fail(CPECAN_EINVAL, "bad argument"), 0;
-    if (check_machine((Machine) machine, mode, flags) != CPECAN_OK) return 0;
-    DispatchQuery q = { (Machine) machine, mode, kernel, flags, 0, true, read_batch_env() };
-    const Dispatch early = choose_dispatch(q); /* (batch creation asks in this order) */
-    if (early.refusal != CPECAN_OK) return fail(early.refusal, "%s", early.why), 0;
-    q.maxWidth = maxWidth;
-    q.edgesStepByOne = edgesStepByOne != 0;
-    const Dispatch d = choose_dispatch(q);
-    if (d.refusal != CPECAN_OK) return fail(d.refusal, "%s", d.why), 0;
+    Dispatch early, d;
+    if (plan_query(machine, mode, kernel, flags, maxWidth, edgesStepByOne, &early, &d) != CPECAN_OK) return 0;
     /* (the plan is made only where the early answer asked for it: the same answer for every band, as it stands) */
     const int cells = early.asmPlan ? d.asmCells : 0;
     if (cellsPerLaneOut) *cellsPerLaneOut = cells;
     return cells;
 }
 
-int cpecan_hip_batch_sync(cpecan_batch *b) {
-    if (!b) return fail(CPECAN_EINVAL, "batch is NULL");
-    HIP_TRY(hipSetDevice(b->device));
-    /* its own end event: the lanes it ran on may already carry the next batch's run */
-    if (b->ran) HIP_TRY(hipEventSynchronize(b->ev2));
-    return CPECAN_OK;
-}
-
-int cpecan_hip_batch_elapsed_ms(cpecan_batch *b, float *msTotal, float *msKernel) {
-    if (!b || !b->ran) return fail(CPECAN_EINVAL, "batch has not run");
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    HIP_TRY(hipEventSynchronize(b->ev2));
-    float a = 0, k = 0;
-    HIP_TRY(hipEventElapsedTime(&a, b->ev0, b->ev2));
-    HIP_TRY(hipEventElapsedTime(&k, b->ev1, b->ev2));
-    if (msTotal) *msTotal = a;
-    if (msKernel) *msKernel = k;
-    return CPECAN_OK;
+int cpecan_hip_plan_expectation_pass(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t maxWidth,
+                                     int32_t edgesStepByOne, int32_t *fusedOut) {
+    if (fusedOut) *fusedOut = 0;
+    Dispatch early, d;
+    if (plan_query(machine, mode, kernel, flags, maxWidth, edgesStepByOne, &early, &d) != CPECAN_OK) return 0;
+    if (fusedOut) *fusedOut = d.fused ? 1 : 0;
+    return d.fused ? 1 : 0;
 }
 
 } /* extern "C" */

@@ -23,7 +23,7 @@ struct SyState {
 
 /* The wave kernels' record: the forward kernel of launch w describes its window in win[w & 3] while the backward
  * kernel of launch w - 1 is working from the entry before and the post kernel of launch w - 2 may still be reading the
- * one before that (the assembly sweeps' schedule, cpecan_hip.hip: they all run concurrently). */
+ * one before that (the assembly sweeps' schedule, cpecan_run.hip: they all run concurrently). */
 struct WvWindow {
     int valid; /* 1: described by the forward kernel; 3: swept back, its totals and pairs are the post kernel's to do;
                   2: its candidates could not be trusted, the re-sweep kernel decodes it; 0: done */

@@ -338,7 +338,8 @@ typedef struct {
                                           estimate is not finite or lies more than 30 nats from one of them is swept
                                           back once more in the same launch (CPECAN_EXPECT_RESWEEP=1 sends every window
                                           there, =2 every other one: tests).  The kernel choice does not change:
-                                          cpecan_hip_plan_dispatch answers what it answers without the flag, and every
+                                          cpecan_hip_plan_dispatch answers what it answers without the flag
+                                          (cpecan_hip_plan_expectation_pass tells what the flag does), and every
                                           other batch -- a posterior batch, another machine, the wave kernels, the six-
                                           and eight-wave builds of CPECAN_FLAG_WIDE_BANDS, the general kernel -- ignores
                                           it.  The sums are those of the other E-step paths to rounding (the same terms
@@ -362,7 +363,8 @@ typedef struct {
                                           doubles per alignment, 9 or 12 KB per diagonal), no expectation kernel; the
                                           estimate, the scaling, the second sweep and CPECAN_EXPECT_RESWEEP are those
                                           described there.  The kernel choice does not change: cpecan_hip_plan_dispatch
-                                          answers what it answers without the flag.  Every other batch ignores it: a
+                                          answers what it answers without the flag (cpecan_hip_plan_expectation_pass
+                                          tells what the flag does).  Every other batch ignores it: a
                                           posterior batch, a band of 248 k-mers or less (flag 2048's ground), a band
                                           past 504 k-mers and a wide band without CPECAN_FLAG_WIDE_BANDS (both on the
                                           general kernel), every other machine.  It has a number of its own because a
@@ -556,6 +558,11 @@ int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
  * (cpecan_hip_batch_kernel_family tells which): no ring of backward cells, no expectation kernel.  0 for the
  * ring-of-backward-cells path and for posterior batches. */
 int cpecan_hip_batch_expectation_pass(cpecan_batch *batch, int32_t *fused);
+/* The same beforehand, without a batch and without a device, asked as cpecan_hip_plan_dispatch is: returns (and stores
+ * in *fused_out, which may be NULL) what cpecan_hip_batch_expectation_pass would report for such a batch.  A combination
+ * batch creation refuses gives 0 here, with the refusal in last_error. */
+int cpecan_hip_plan_expectation_pass(int32_t machine, int32_t mode, int32_t kernel, int32_t flags, int32_t max_width,
+                                     int32_t edges_step_by_one, int32_t *fused_out);
 /* Systolic path only: HIP-event time of the last run spent in the forward-window kernels and in
  * the backward-window kernels (each launched `launches_each` times, once per traceback window). */
 int cpecan_hip_batch_stage_ms(cpecan_batch *batch, float *ms_forward, float *ms_backward,

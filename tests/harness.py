@@ -7,6 +7,14 @@ from cpecan_load import binding
 
 cp = binding()
 
+# every environment variable batch creation's kernel choice reads (read_batch_env in cpecan_hip.hip; the plan calls read
+# them the same way): what a test of the choice clears first.  tests/test_expectation_pass_dispatch_cpu.py holds it
+# against the source
+BATCH_ENV = ("CPECAN_DNA_GENERAL", "CPECAN_WIDE_BANDS", "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS", "CPECAN_ASM",
+             "CPECAN_WIDE_BANDS_HDP", "CPECAN_WIDE_BANDS_HDP_ESTEP", "CPECAN_WIDE_BANDS_VANILLA_ESTEP", "CPECAN_ASM_NARROW",
+             "CPECAN_EXPECT_FUSED_WORKGROUP", "CPECAN_EXPECT_FUSED_WIDE", "CPECAN_EXPECT_FUSED", "CPECAN_EXPECT_RESWEEP",
+             "CPECAN_SYSTOLIC_GROUPS", "CPECAN_RING_PAD")
+
 
 def band_params(threshold=0.01, min_diags=1000, tb_diags=40, expansion=20):
     return cp.BandParams(threshold, min_diags, tb_diags, expansion)

@@ -7,6 +7,7 @@ import re
 import pytest
 
 from cpecan_load import binding
+from harness import BATCH_ENV
 
 cp = binding()
 
@@ -19,9 +20,7 @@ WIDTHS = (0, 1, 56, 57, 72, 102, LIMIT, LIMIT + 1, 140, 158, 159, 184, 185, 248,
 
 @pytest.fixture(autouse=True)
 def clean_env(monkeypatch):
-    for k in ("CPECAN_WIDE_BANDS", "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS", "CPECAN_ASM", "CPECAN_ASM_NARROW", "CPECAN_WIDE_BANDS_HDP",
-              "CPECAN_WIDE_BANDS_HDP_ESTEP", "CPECAN_WIDE_BANDS_VANILLA_ESTEP", "CPECAN_EXPECT_FUSED_WORKGROUP",
-              "CPECAN_EXPECT_FUSED_WIDE"):
+    for k in BATCH_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

@@ -14,6 +14,7 @@ read from the tables under test:
 import pytest
 
 from cpecan_load import binding
+from harness import BATCH_ENV
 
 cp = binding()
 
@@ -32,7 +33,7 @@ def sweep(wave, rows, width):
 
 @pytest.fixture(autouse=True)
 def clean_env(monkeypatch):
-    for k in ("CPECAN_WIDE_BANDS", "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS", "CPECAN_ASM"):
+    for k in BATCH_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

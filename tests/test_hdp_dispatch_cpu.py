@@ -10,6 +10,7 @@ one (tests/test_dispatch_cpu.py)."""
 import pytest
 
 from cpecan_load import binding
+from harness import BATCH_ENV
 
 cp = binding()
 
@@ -27,7 +28,7 @@ def sweep(wave, rows, width):
 
 @pytest.fixture(autouse=True)
 def clean_env(monkeypatch):
-    for k in ("CPECAN_WIDE_BANDS", "CPECAN_WIDE_BANDS_HDP", "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS", "CPECAN_ASM"):
+    for k in BATCH_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

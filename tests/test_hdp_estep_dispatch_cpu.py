@@ -10,6 +10,7 @@ or to the other machines, and the two older wide-band flags nothing to an HDP E-
 import pytest
 
 from cpecan_load import binding
+from harness import BATCH_ENV
 
 cp = binding()
 
@@ -28,8 +29,7 @@ def sweep(wave, rows, width):
 
 @pytest.fixture(autouse=True)
 def clean_env(monkeypatch):
-    for k in ("CPECAN_WIDE_BANDS", "CPECAN_WIDE_BANDS_HDP", VARIABLE, "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS",
-              "CPECAN_ASM"):
+    for k in BATCH_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

@@ -1,6 +1,6 @@
 """The two kernels that pack a run's candidates for the host are compiled in cpecan_readback.hip, with the readback
-that launches them; cpecan_hip.hip, the rest of the C-ABI layer, is host code and defines no kernel.  Symbol tables of
-the built objects only: CPU-only."""
+that launches them; cpecan_hip.hip and cpecan_run.hip, the rest of the C-ABI layer (contexts, the kernel choice and batch
+creation; how a run is queued), are host code and define no kernel.  Symbol tables of the built objects only: CPU-only."""
 import os
 import shutil
 import subprocess
@@ -39,6 +39,7 @@ def test_pack_kernels_are_in_the_readback_object_alone(objects):
 
 
 def test_the_batch_layer_defines_no_kernel(objects):
-    names = objects[os.path.join(AMD, "csrc", "cpecan_hip.o")]
-    assert names, "cpecan_hip.o defines nothing?"
-    assert sorted(n for n in names if n.startswith("cpecan_k_")) == []
+    for obj in ("cpecan_hip.o", "cpecan_run.o"):
+        names = objects[os.path.join(AMD, "csrc", obj)]
+        assert names, "%s defines nothing?" % obj
+        assert sorted(n for n in names if n.startswith("cpecan_k_")) == [], obj

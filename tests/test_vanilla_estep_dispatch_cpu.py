@@ -11,6 +11,7 @@ vanilla E-step."""
 import pytest
 
 from cpecan_load import binding
+from harness import BATCH_ENV
 
 cp = binding()
 
@@ -30,7 +31,7 @@ def sweep(wave, rows, width):
 
 @pytest.fixture(autouse=True)
 def clean_env(monkeypatch):
-    for k in OLDER_VARIABLES + (VARIABLE, "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS", "CPECAN_ASM"):
+    for k in BATCH_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

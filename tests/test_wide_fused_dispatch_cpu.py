@@ -6,6 +6,7 @@ batch on the six- and eight-wave builds, is batch creation's: tests/test_wide_fu
 import pytest
 
 from cpecan_load import binding
+from harness import BATCH_ENV
 from test_workgroup_fused_dispatch_cpu import FLAGS, MACHINES, WIDTHS, answer
 
 cp = binding()
@@ -17,9 +18,7 @@ KERNELS = (cp.KERNEL_AUTO, cp.KERNEL_GENERAL, cp.KERNEL_SYSTOLIC)
 
 @pytest.fixture(autouse=True)
 def clean_env(monkeypatch):
-    for k in ("CPECAN_WIDE_BANDS", "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS", "CPECAN_ASM", "CPECAN_WIDE_BANDS_HDP",
-              "CPECAN_WIDE_BANDS_HDP_ESTEP", "CPECAN_WIDE_BANDS_VANILLA_ESTEP", "CPECAN_EXPECT_FUSED_WORKGROUP",
-              "CPECAN_EXPECT_FUSED_WIDE"):
+    for k in BATCH_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

@@ -6,6 +6,7 @@ No device."""
 import pytest
 
 from cpecan_load import binding
+from harness import BATCH_ENV
 
 cp = binding()
 
@@ -21,8 +22,7 @@ FLAGS = (0, cp.FLAG_WORKGROUP_KERNELS, cp.FLAG_WIDE_BANDS, cp.FLAG_WORKGROUP_KER
 
 @pytest.fixture(autouse=True)
 def clean_env(monkeypatch):
-    for k in ("CPECAN_WIDE_BANDS", "CPECAN_KERNELS", "CPECAN_SYSTOLIC_ROWS", "CPECAN_ASM", "CPECAN_WIDE_BANDS_HDP",
-              "CPECAN_WIDE_BANDS_HDP_ESTEP", "CPECAN_WIDE_BANDS_VANILLA_ESTEP", "CPECAN_EXPECT_FUSED_WORKGROUP"):
+    for k in BATCH_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

@@ -17,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ONCE = ("cpecan_kernel_prep.hip", "cpecan_kernel_general.hip", "cpecan_kernel_generalh.hip", "cpecan_hip.hip",
-        "cpecan_readback.hip")
+        "cpecan_run.hip", "cpecan_readback.hip")
 META = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size",
         "kernarg_segment_size")
 
