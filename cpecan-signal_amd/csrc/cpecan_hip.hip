@@ -45,13 +45,18 @@ extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
  * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP is 1, _f6 / _f8 for _r6 / _r8
  * (CPECAN_FLAG_WIDE_BANDS, a widest band of 249..504 k-mers) when it carries CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP or
  * CPECAN_EXPECT_FUSED_WIDE is 1.  Neither flag means anything to the other's range, to another machine or mode, to the
- * wave family or to the general kernel: such a batch runs what it runs without it. */
+ * wave family or to the general kernel: such a batch runs what it runs without it.
+ * The wave family has two fused builds of the same kind for the vanilla machine (_vf2, _vf3: cpecan_wavefx_build_vf<n>, the
+ * Makefile's WV_FUSED_BUILDS): a vanilla batch of expectations that the rules above put on _v2 or _v3 and that carries
+ * CPECAN_FLAG_VANILLA_FUSED_ESTEP runs on the one of as many cells per lane.  That flag means nothing to a posterior
+ * batch, to another machine, to the general kernel or to the _ve builds of the workgroup family. */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
 SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(cpecan_wave_build_l4)
 SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
+SWEEP_BUILD(cpecan_wavefx_build_vf2) SWEEP_BUILD(cpecan_wavefx_build_vf3)
 SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
 SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
@@ -76,6 +81,9 @@ static const SweepBuild *const SYVE_WIDE_BUILDS[4] = { &cpecan_systolic_build_ve
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
+/* (the fused E-step of the build of as many cells per lane in VV_BUILDS) */
+static SweepFamily VV_FUSED_BUILDS = { &cpecan_wavefx_build_vf2, &cpecan_wavefx_build_vf2, &cpecan_wavefx_build_vf3,
+                                       &cpecan_wavefx_build_vf3 };
 
 namespace {
 
@@ -302,10 +310,15 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
                     for (int i = 0; SY_WIDE_BUILDS[i]; i++)
                         if (d.build == SY_WIDE_BUILDS[i]) d.build = SY_FUSED_WIDE_BUILDS[i];
             }
+            /* ... and the vanilla machine's of the wave family (a wide build of the workgroup family is in no entry of
+             * VV_BUILDS, so a batch on the _ve builds keeps its build) */
+            if (q.machine == VANILLA && q.mode == CPECAN_MODE_EXPECTATIONS && (d.flags & CPECAN_FLAG_VANILLA_FUSED_ESTEP))
+                for (int i = 0; i < 4; i++)
+                    if (d.build == VV_BUILDS[i]) d.build = VV_FUSED_BUILDS[i];
             /* the strawMan machine's E-step on the wave kernels sums its expectations inside the sweep back (same box,
              * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 keeps
-             * the ring of backward cells and the expectation kernel.  A fused build of the workgroup family has no
-             * other form of the E-step. */
+             * the ring of backward cells and the expectation kernel.  A fused build of the workgroup family, or of the
+             * vanilla machine, has no other form of the E-step. */
             d.fused = q.mode == CPECAN_MODE_EXPECTATIONS && d.build->backward_fx && (!d.build->expect || !q.env.ringEstep);
             d.expectResweep = d.fused ? q.env.expectResweep : 0;
         }
@@ -1199,7 +1212,7 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
 
 int cpecan_hip_batch_expectation_pass(cpecan_batch *b, int32_t *fused) {
     if (!b || !fused) return fail(CPECAN_EINVAL, "bad argument");
-    *fused = b->fused ? 1 : 0; /* (the wave kernels' E-step, or the workgroup kernels' on their fused builds) */
+    *fused = b->fused ? 1 : 0; /* (the strawMan wave kernels' E-step, or a fused build's: _f<n>, _vf<n>) */
     return CPECAN_OK;
 }
 

@@ -45,9 +45,17 @@
 /* -DWV_VANILLA: the 3-state vanilla signal machine (stateMachine3Vanilla_cellCalculate, impl/stateMachine.c:1368-1409):
  * transition probabilities per reference position (30 skip bins of the k-mer pair sequence_getKmer2 exposes), a
  * Gaussian level term plus an inverse-Gaussian noise term per emission; symbols suffixed _v2, _v3 (four cells per lane spill: not built) */
+/* -DWV_VANILLA -DWV_FUSED: the vanilla machine's E-step with its expectations summed inside the sweep back and no other
+ * kernel than that E-step needs (forward sweep, fused sweep back, post kernel, fused re-sweep), in objects of their own:
+ * symbols suffixed _vf2, _vf3, the record cpecan_wavefx_build_vf<n>; the _v2 / _v3 objects keep their device code */
 /* Every build holds the sweeps, their launchers and one SweepBuild record; what does not depend on the build (track,
  * counts, the machines' records) is cpecan_kernel_prep.hip's */
-#if defined(WV_VANILLA)
+#if defined(WV_FUSED) && !defined(WV_VANILLA)
+#error "WV_FUSED: a build of the vanilla machine (the strawMan builds hold their fused sweeps themselves)"
+#endif
+#if defined(WV_FUSED)
+#define WV_SYM(n) SWEEP_SYM(n, vf, WV_L)
+#elif defined(WV_VANILLA)
 #define WV_SYM(n) SWEEP_SYM(n, v, WV_L)
 #elif defined(WV_HDP)
 #define WV_SYM(n) SWEEP_SYM(n, h, WV_L)
@@ -960,7 +968,10 @@ __device__ __forceinline__ void store_b3(unsigned long long laneMask, const doub
  *       the column it held before, when the slot changed columns within the segment.  One change at most: a slot's
  *       column steps by P >= 128 and a band edge moves by at most one column per diagonal, so a second change would
  *       need the band to travel P columns within the segment's ten diagonals
- *   c   their matrix columns (-1: none) */
+ *   c   their matrix columns (-1: none)
+ * The vanilla machine (-DWV_FUSED) collects two sums per cell and no transition (cpecan_k_wv_expect): no tr, a record of
+ * g is the pair (beta: match -> gap X, alpha: gap X -> gap X) of its column, and c holds the column's skip bin (entry 21
+ * of its track row, which the sweep has in the slot's registers and the post kernel has not; -1: none). */
 struct WvFx {
     double *tr, *g;
     int *c;
@@ -971,15 +982,22 @@ __host__ __device__ inline long long wv_scratch_base_bytes(int ringD) {
            + 4ll * ringD * sizeof(unsigned long long)
            + (long long) WV_L * WV_CAND_PER_DIAG * ringD * (sizeof(int2) + sizeof(double));
 }
+#ifdef WV_VANILLA
+#define WV_FX_TR 0 /* doubles per segment of tr, per record of g */
+#define WV_FX_G 2
+#else
+#define WV_FX_TR 8
+#define WV_FX_G 1
+#endif
 __host__ __device__ inline long long wv_fx_bytes(int ringD) {
-    return ((long long) ringD / 10 + 8) * (8 * sizeof(double) + 2 * WV_P * (sizeof(double) + sizeof(int)));
+    return ((long long) ringD / 10 + 8) * (WV_FX_TR * sizeof(double) + 2 * WV_P * (WV_FX_G * sizeof(double) + sizeof(int)));
 }
 __device__ inline WvFx wv_fx_at(char *sc, int ringD) {
     const long long nW = (long long) ringD / 10 + 8;
     WvFx f;
     f.tr = (double *) (sc + wv_scratch_base_bytes(ringD));
-    f.g = f.tr + nW * 8;
-    f.c = (int *) (f.g + nW * 2 * WV_P);
+    f.g = f.tr + nW * WV_FX_TR;
+    f.c = (int *) (f.g + nW * 2 * WV_P * WV_FX_G);
     return f;
 }
 
@@ -1223,10 +1241,82 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
          * (its forward cells are row t too); the loop's tail takes what is left of to+2 and to+1 from row `to`.  ref is
          * the forward kernel's estimate of the window's total (the post kernel rescales each segment once the exact
          * totals are known), or the segment's exact total on the re-sweep. */
-        double ea[8], gA[L], py1[L]; /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
-        int cA[L];
         int segAcc = 0;
         double refAcc = totEst;
+#ifdef WV_VANILLA
+        /* The vanilla machine (cell_signal_updateBetaAndAlphaProb :478-498) collects two of those terms, both of the
+         * lower block: match -> gap X (beta) and gap X -> gap X (alpha), per column, into the column's skip bin. */
+        double gA[L], gB[L], py1[L]; /* beta and alpha of the slot's column; (py1: unused, the step keeps it for the strawMan terms) */
+        int cA[L], bA[L];            /* that column and its skip bin */
+        if (FX) {
+#pragma unroll
+            for (int j = 0; j < L; j++) {
+                gA[j] = gB[j] = 0.0;
+                cA[j] = bA[j] = -1;
+                fxo.c[lane * L + j] = -1; /* segment 0 has no A record yet */
+            }
+            if (KIND == WV_KIND_EXPECT_REDO) refAcc = uni64_d(ld_agent(&wtot[0].total));
+        }
+        auto fx_flush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < L; j++) {
+                const int sl = lane * L + j;
+                fxo.g[((segAcc * 2 + 1) * WV_P + sl) * 2 + 0] = gA[j];
+                fxo.g[((segAcc * 2 + 1) * WV_P + sl) * 2 + 1] = gB[j];
+                fxo.c[(segAcc * 2 + 1) * WV_P + sl] = bA[j];
+                fxo.c[(segAcc * 2 + 2) * WV_P + sl] = -1; /* the next segment's A records */
+                gA[j] = gB[j] = 0.0;
+            }
+            segAcc++;
+            if (KIND == WV_KIND_EXPECT_REDO) refAcc = uni64_d(ld_agent(&wtot[segAcc].total));
+        };
+        /* rF, rX: this slot's forward cells of row u1 - 1; nMin, nMax: the band of u1 */
+        auto fx_terms = [&](const double (&rF)[L], const double (&rX)[L], const double (&)[L], const int u1,
+                            const int nMin, const int nMax) __attribute__((always_inline)) {
+            double sF[L], sX[L]; /* ... and those of the slot below (k-mer x-1) */
+#pragma unroll
+            for (int j = 0; j < L; j++) {
+                sF[j] = j > 0 ? rF[j > 0 ? j - 1 : 0] : ror1(rF[L - 1]);
+                sX[j] = j > 0 ? rX[j > 0 ? j - 1 : 0] : ror1(rX[L - 1]);
+            }
+            if (u1 + 1 <= tPost0 && (tPost0 - (u1 + 1)) % 10 == 9) fx_flush(); /* u1+1 ends its segment */
+            if (u1 <= tPost0) { /* lower block of u1 */
+                const int sMin = nMin % WV_P;
+                /* (re-sweep only) a total of -inf or NaN: every term is NaN, as in the reference, and the terms must then
+                 * be those the reference forms -- a cell of the band whose lower neighbour is in the band too -- instead
+                 * of one per slot */
+                const bool nf = KIND == WV_KIND_EXPECT_REDO && !(refAcc > CP_NEG_INF);
+                int qMin = 0, qMax = -1; /* band of u1-1 */
+                if (nf) band_load(bandTab, u1 - 1, qMin, qMax);
+#pragma unroll
+                for (int j = 0; j < L; j++) {
+                    const int sl = lane * L + j;
+                    const int x = nMin + (sl - sMin + (sl < sMin ? WV_P : 0));
+                    double p0 = exp(sF[j] + Bx[j] + px[j].a.x - refAcc);
+                    double p1 = exp(sX[j] + Bx[j] + px[j].a.y - refAcc);
+                    if (nf) {
+                        const bool inL = x <= nMax && x - 1 >= qMin && x - 1 <= qMax; /* lower neighbour (x-1, y) */
+                        p0 = inL ? p0 : 0.0;
+                        p1 = inL ? p1 : 0.0;
+                    }
+                    if (x <= nMax && x != cA[j]) { /* the slot took another column within the segment */
+                        if (gA[j] != 0.0 || gB[j] != 0.0) {
+                            fxo.g[((segAcc * 2) * WV_P + sl) * 2 + 0] = gA[j];
+                            fxo.g[((segAcc * 2) * WV_P + sl) * 2 + 1] = gB[j];
+                            fxo.c[(segAcc * 2) * WV_P + sl] = bA[j];
+                        }
+                        gA[j] = gB[j] = 0.0;
+                        cA[j] = x;
+                        bA[j] = (int) px[j].c.y; /* (the slot holds column x's k-mer pair until the installs of this step) */
+                    }
+                    gA[j] += p0;
+                    gB[j] += p1;
+                }
+            }
+        };
+#else
+        double ea[8], gA[L], py1[L]; /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
+        int cA[L];
         if (FX) {
 #pragma unroll
             for (int i = 0; i < 8; i++) ea[i] = 0.0;
@@ -1341,6 +1431,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 }
             }
         };
+#endif /* WV_VANILLA */
 
         auto step = [&](const int t, Rec &r, Q &q) __attribute__((always_inline)) {
             /* this diagonal's forward values (their loads were issued WV_PREFETCH diagonals ago), then the fetch
@@ -1733,6 +1824,43 @@ __device__ void fx_finish(const int tid, const int nth, const DevItem &it, const
         if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
     }
 }
+#elif defined(WV_FUSED)
+/* ... and the vanilla machine's (layout of its cpecan_k_wv_expect: 60 bins and the likelihood per model), in two steps
+ * with the caller's barrier between them.  First every thread adds the records of slots tid, tid + nth, ..., scaled as
+ * above, to the window's 60 bin sums in LDS (bins: zero on entry); then threads 0-59 add those to the model's, thread 60
+ * the likelihood. */
+__device__ void fx_finish_bins(const int tid, const int nth, const WvFx &fx, const WinTotal *wtot, const int nSeg,
+                               const double est, const bool exact, double *bins) {
+#pragma unroll 1
+    for (int s = tid; s < WV_P; s += nth) {
+#pragma unroll 1
+        for (int k = 0; k < nSeg; k++) {
+            const double f = exact ? 1.0 : exp(est - wtot[k].total);
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const long long i = (long long) (k * 2 + r) * WV_P + s;
+                const int bin = fx.c[i];
+                const double beta = fx.g[i * 2], alpha = fx.g[i * 2 + 1];
+                if (bin >= 0 && bin < 30) {
+                    if (beta != 0.0) atomicAdd(bins + bin, f * beta);
+                    if (alpha != 0.0) atomicAdd(bins + bin + 30, f * alpha);
+                }
+            }
+        }
+    }
+}
+__device__ void fx_finish_model(const int tid, const DevItem &it, const WinTotal *wtot, const int tPost0, const int to,
+                                const double *bins, double *expect) {
+    double *dst = expect + (long long) it.model * (60 + 1);
+    if (tid < 60) {
+        if (bins[tid] != 0.0) atomicAdd(dst + tid, bins[tid]);
+    } else if (tid == 60) {
+        double lik = 0.0;
+#pragma unroll 1
+        for (int u = tPost0; u > to; u--) lik += wtot[(tPost0 - u) / 10].total;
+        atomicAdd(dst + 60, lik);
+    }
+}
 #endif
 
 } // namespace
@@ -1772,6 +1900,7 @@ extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(cpecan_k_wv_for
     wv_forward_kernel<false>(items, nItems, P, bandTab, track, trackBase, events, models, Fring, ringDoubles, ringD,
                              states, window, sh);
 }
+#ifndef WV_FUSED
 extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(cpecan_k_wv_forward_sw)(
     const DevItem *__restrict__ items, long long nItems, DevParams P,
     const int2 *__restrict__ bandTab, const double *__restrict__ track,
@@ -1781,6 +1910,7 @@ extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(cpecan_k_wv_for
     wv_forward_kernel<true>(items, nItems, P, bandTab, track, trackBase, events, models, Fring, ringDoubles, ringD,
                             states, window, sh);
 }
+#endif
 
 /* One wave per alignment: the sweep back of the window the forward kernel just described (win[].valid: see
  * cpecan_sweep.h).  What follows the sweep -- the refresh terms, the totals, the decode -- is the post kernel's. */
@@ -1841,6 +1971,22 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
         fx_finish(threadIdx.x & 63, 64, it, fxo, wtot, uni(win.nRefresh), dTop < from ? dTop : from, uni(win.to),
                   uni64_d(win.est), true, expect, kidx);
     }
+#elif defined(WV_FUSED)
+    if constexpr (KIND == WV_KIND_EXPECT_REDO) {
+        /* ... the same, through the wave's 60 bin sums in LDS (the records of phase T0, which a re-sweep does not run;
+         * one wave: its LDS accesses keep their order, the fences keep the compiler to it) */
+        double *bins = (double *) sh.rec;
+        const int lane = threadIdx.x & 63;
+        if (lane < 60) bins[lane] = 0.0;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const int dTop = uni(win.top), from = uni(win.from);
+        fx_finish_bins(lane, 64, fxo, wtot, uni(win.nRefresh), uni64_d(win.est), true, bins);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        fx_finish_model(lane, it, wtot, dTop < from ? dTop : from, uni(win.to), bins, expect);
+    }
+    (void) kidx;
 #endif
     if ((threadIdx.x & 63) == 0) {
         WvWindow *w = &state->win[window & 3];
@@ -1866,6 +2012,7 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
         wv_backward_kernel<SW, KIND>(items, nItems, P, bandTab, track, trackBase, models, Fring, ringDoubles,     \
                                      ringD, states, pairs, pairLogp, scratch, scratchBytes, Bring, window, sh);   \
     }
+#ifndef WV_FUSED
 WV_BACKWARD_KERNEL(cpecan_k_wv_backward, false, WV_KIND_POSTERIOR)
 WV_BACKWARD_KERNEL(cpecan_k_wv_backward_sw, true, WV_KIND_POSTERIOR)
 WV_BACKWARD_KERNEL(cpecan_k_wv_resweep, false, WV_KIND_REDO)
@@ -1874,9 +2021,11 @@ WV_BACKWARD_KERNEL(cpecan_k_wv_backward_em, false, WV_KIND_EXPECT)
 #if !defined(WV_VANILLA) /* (no gap Y -> gap X transition in the vanilla machine) */
 WV_BACKWARD_KERNEL(cpecan_k_wv_backward_em_sw, true, WV_KIND_EXPECT)
 #endif
-#if !defined(WV_VANILLA) && !defined(WV_HDP)
-/* the strawMan machine's E-step: expectations summed inside the sweep back (no B ring, no expectation kernel), and the
- * re-sweep of the windows whose sums the estimate could not carry (cpecan_k_wv_post) */
+#endif /* WV_FUSED */
+#if (!defined(WV_VANILLA) && !defined(WV_HDP)) || defined(WV_FUSED)
+/* the strawMan machine's E-step, and the vanilla machine's on its fused builds: expectations summed inside the sweep
+ * back (no B ring, no expectation kernel), and the re-sweep of the windows whose sums the estimate could not carry
+ * (cpecan_k_wv_post) */
 #define WV_BACKWARD_FX_KERNEL(name, SW, KIND)                                                                     \
     extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(name)(                                       \
         const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTab,       \
@@ -1890,9 +2039,11 @@ WV_BACKWARD_KERNEL(cpecan_k_wv_backward_em_sw, true, WV_KIND_EXPECT)
                                      expect, kidx);                                                               \
     }
 WV_BACKWARD_FX_KERNEL(cpecan_k_wv_backward_fx, false, WV_KIND_EXPECT_FUSED)
-WV_BACKWARD_FX_KERNEL(cpecan_k_wv_backward_fx_sw, true, WV_KIND_EXPECT_FUSED)
 WV_BACKWARD_FX_KERNEL(cpecan_k_wv_resweep_fx, false, WV_KIND_EXPECT_REDO)
+#ifndef WV_FUSED /* (no gap Y -> gap X transition in the vanilla machine) */
+WV_BACKWARD_FX_KERNEL(cpecan_k_wv_backward_fx_sw, true, WV_KIND_EXPECT_FUSED)
 WV_BACKWARD_FX_KERNEL(cpecan_k_wv_resweep_fx_sw, true, WV_KIND_EXPECT_REDO)
+#endif
 #endif
 
 /*
@@ -1912,6 +2063,9 @@ struct PostShared {
     double vbuf[256];
     int part[4];
     int scan, carry, fxRedo;
+#ifdef WV_FUSED
+    double bins[60]; /* the window's sums per skip bin (fx_finish_bins) */
+#endif
 };
 extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTabAll,
@@ -1937,6 +2091,9 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     if (tid == 0) sh.scan = (P.scanDecode != 0 || !(P.logThrSlack > CP_NEG_INF) || nCand > candCap) ? 1 : 0;
     /* (tests: 1 every window down the re-sweep, 2 every other one -- the items and windows alternate) */
     if (tid == 0) sh.fxRedo = P.expectResweep == 1 || (P.expectResweep == 2 && ((idx ^ window) & 1)) ? 1 : 0;
+#ifdef WV_FUSED
+    if (tid < 60) sh.bins[tid] = 0.0;
+#endif
     __syncthreads();
     const unsigned cf = lds_addr(sh.coef);
     const int2 *bandTab = bandTabAll + it.diagBase;
@@ -2008,6 +2165,20 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
         const bool redo = nPost > 0 && sh.fxRedo != 0;
         if (nPost > 0 && !redo)
             fx_finish(tid, 256, it, wv_fx_at(sc, ringD), wtot, nTotWin, tPost0, tracedBackTo, totEst, false, expect, kidx);
+        if (tid == 0) {
+            state->nTot = nTot0 + nTotWin;
+            wp->valid = redo ? 2 : 0;
+        }
+        return;
+    }
+#elif defined(WV_FUSED)
+    if (P.mode != 0 && fused) { /* ... the same for the vanilla machine's two sums per column */
+        const bool redo = nPost > 0 && sh.fxRedo != 0;
+        if (nPost > 0 && !redo) {
+            fx_finish_bins(tid, 256, wv_fx_at(sc, ringD), wtot, nTotWin, totEst, false, sh.bins);
+            __syncthreads();
+            fx_finish_model(tid, it, wtot, tPost0, tracedBackTo, sh.bins, expect);
+        }
         if (tid == 0) {
             state->nTot = nTot0 + nTotWin;
             wp->valid = redo ? 2 : 0;
@@ -2107,7 +2278,7 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     }
 }
 
-#if defined(WV_VANILLA)
+#if defined(WV_VANILLA) && !defined(WV_FUSED)
 /*
  * The vanilla machine's expectations of the traceback window the backward kernel just swept
  * (diagonalCalculation_Expectations :841-863 with cell_signal_updateBetaAndAlphaProb :478-498): of all transitions only
@@ -2371,11 +2542,13 @@ extern "C" __global__ __launch_bounds__(WV_P) void WV_SYM(cpecan_k_wv_expect)(
  * is a choice of function pointer */
 static dim3 wv_sweep_grid(const SweepArgs &a) { return dim3((unsigned) ((a.nItems + WV_WPB - 1) / WV_WPB)); }
 static int wv_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+#ifndef WV_FUSED
 static void wv_sweep_back(decltype(&WV_SYM(cpecan_k_wv_backward)) k, hipStream_t stream, const SweepArgs &a, int window) {
     hipLaunchKernelGGL(k, wv_sweep_grid(a), dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track,
                        a.trackBase, a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, a.pairs, a.pairLogp,
                        a.scratch, a.scratchBytes, a.Bring, window);
 }
+#endif
 /* the window's totals and decode -- or, fused, its totals and the sums into expect[] (no pairs) */
 static void wv_post(hipStream_t stream, const SweepArgs &a, int window, bool fused) {
     hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) a.nItems), dim3(256), 0, stream, a.items, a.nItems, a.P,
@@ -2384,11 +2557,18 @@ static void wv_post(hipStream_t stream, const SweepArgs &a, int window, bool fus
                        a.scratchBytes, window, fused ? 1 : 0, fused ? a.expect : nullptr, fused ? a.kidx : nullptr);
 }
 static int wv_launch_forward(hipStream_t stream, const SweepArgs &a, int window) {
-    hipLaunchKernelGGL(a.withSwitch ? WV_SYM(cpecan_k_wv_forward_sw) : WV_SYM(cpecan_k_wv_forward), wv_sweep_grid(a),
+#ifdef WV_FUSED
+    if (a.withSwitch) return -1;
+    const auto forward = WV_SYM(cpecan_k_wv_forward);
+#else
+    const auto forward = a.withSwitch ? WV_SYM(cpecan_k_wv_forward_sw) : WV_SYM(cpecan_k_wv_forward);
+#endif
+    hipLaunchKernelGGL(forward, wv_sweep_grid(a),
                        dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.events,
                        a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, window);
     return wv_status();
 }
+#ifndef WV_FUSED
 /* the totals and the decode of a window swept back with decode candidates, then the kernel that sweeps once more the
  * windows whose candidates could not be trusted (it returns at once for the others).  The same two follow the assembly
  * sweep back of a window (cpecan_asm.h), which leaves the refreshes' terms and the candidates in scratch as the
@@ -2420,10 +2600,12 @@ static int wv_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
                        a.pairLogp);
     return wv_status();
 }
-#if !defined(WV_VANILLA) && !defined(WV_HDP)
-/* the strawMan E-step of a window with fused expectations: the sweep back summing them, the totals and the sums into
- * expect[] (cpecan_k_wv_post), then the re-sweep of the windows the estimate could not carry (it returns at once for
- * the others).  All three index alignments by blockIdx.x. */
+#endif /* WV_FUSED */
+#if (!defined(WV_VANILLA) && !defined(WV_HDP)) || defined(WV_FUSED)
+/* the E-step of a window with fused expectations (the strawMan machine's, and the vanilla machine's on its fused
+ * builds): the sweep back summing them, the totals and the sums into expect[] (cpecan_k_wv_post), then the re-sweep of
+ * the windows the estimate could not carry (it returns at once for the others).  All three index alignments by
+ * blockIdx.x. */
 static void wv_sweep_back_fx(decltype(&WV_SYM(cpecan_k_wv_backward_fx)) k, hipStream_t stream, const SweepArgs &a,
                              int window) {
     hipLaunchKernelGGL(k, wv_sweep_grid(a), dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track,
@@ -2431,11 +2613,22 @@ static void wv_sweep_back_fx(decltype(&WV_SYM(cpecan_k_wv_backward_fx)) k, hipSt
                        a.scratchBytes, a.expect, a.kidx, window);
 }
 static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int window) {
+#ifdef WV_FUSED
+    if (a.withSwitch) return -1;
+    wv_sweep_back_fx(WV_SYM(cpecan_k_wv_backward_fx), stream, a, window);
+    wv_post(stream, a, window, true);
+    wv_sweep_back_fx(WV_SYM(cpecan_k_wv_resweep_fx), stream, a, window);
+    return wv_status();
+}
+#else
     wv_sweep_back_fx(a.withSwitch ? WV_SYM(cpecan_k_wv_backward_fx_sw) : WV_SYM(cpecan_k_wv_backward_fx), stream, a, window);
     wv_post(stream, a, window, true);
     wv_sweep_back_fx(a.withSwitch ? WV_SYM(cpecan_k_wv_resweep_fx_sw) : WV_SYM(cpecan_k_wv_resweep_fx), stream, a, window);
     return wv_status();
 }
+#endif
+#endif
+#if !defined(WV_VANILLA) && !defined(WV_HDP)
 #define WV_STRAWMAN_ONLY(f) f
 #else
 #define WV_STRAWMAN_ONLY(f) nullptr
@@ -2452,10 +2645,20 @@ static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int win
 #endif
 /* scratch: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list], and after it,
  * in batches with fused expectations, the segments' sums (WvFx) */
+#ifdef WV_FUSED
+/* (a name of its own, cpecan_wavefx_build_vf<n>: these builds are not among the Makefile's WV_BUILDS; they have the
+ * fused E-step and nothing else) */
+extern "C" const SweepBuild WV_SYM(cpecan_wavefx_build);
+const SweepBuild WV_SYM(cpecan_wavefx_build) = {
+    WV_L, true, WV_MACHINE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
+    wv_scratch_base_bytes, wv_fx_bytes,
+    wv_launch_forward, nullptr, wv_launch_backward_fx, nullptr, nullptr };
+#else
 extern "C" const SweepBuild WV_SYM(cpecan_wave_build);
 const SweepBuild WV_SYM(cpecan_wave_build) = {
     WV_L, true, WV_MACHINE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
     wv_scratch_base_bytes, WV_STRAWMAN_ONLY(wv_fx_bytes),
     wv_launch_forward, wv_launch_backward, WV_STRAWMAN_ONLY(wv_launch_backward_fx), wv_launch_expect,
     WV_STRAWMAN_ONLY(wv_launch_post) };
+#endif
 #endif

@@ -1069,10 +1069,16 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
         else if (sm4)
             CHECK(cpecan_hip_batch_create_sm4(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
                                               unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0, &batch));
-        else if (van)
+        else if (van) {
+            /* CPECAN_VANILLA_FUSED_ESTEP=1: the E-step summed inside the sweep back on the wave kernels (the flag means
+             * nothing to a batch it does not serve) */
+            const char *fusedEstep = getenv("CPECAN_VANILLA_FUSED_ESTEP");
             CHECK(cpecan_hip_batch_create_vanilla(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
                                                   (unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0) |
-                                                      (mode ? CPECAN_FLAG_EXPECTATIONS : 0), &batch));
+                                                      (mode ? CPECAN_FLAG_EXPECTATIONS : 0) |
+                                                      (mode && fusedEstep && atoi(fusedEstep) == 1
+                                                           ? CPECAN_FLAG_VANILLA_FUSED_ESTEP : 0), &batch));
+        }
         else
             CHECK(cpecan_hip_batch_create(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
                                           mode ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,

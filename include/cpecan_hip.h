@@ -404,6 +404,32 @@ typedef struct {
                                           environment variable CPECAN_ASM_NARROW=1 (read per batch) sets it for every
                                           strawMan posterior batch: the way in for callers of libcpecan_host.so,
                                           vanillaAlign and bench.py --band. */
+#define CPECAN_FLAG_VANILLA_FUSED_ESTEP 16384 /* cpecan_hip_batch_create_vanilla with CPECAN_FLAG_EXPECTATIONS only: a
+                                          batch of the wave-per-alignment kernels (a widest band of at most 184 k-mers
+                                          whose edges step by one k-mer per diagonal, no CPECAN_FLAG_GENERAL_KERNEL) sums
+                                          its two expectations per cell -- match -> gap X into the skip bin of the cell's
+                                          k-mer pair, gap X -> gap X into bin + 30 -- inside the sweep back, against the
+                                          forward sweep's estimate of the window's total, per segment of ten decoded
+                                          diagonals (cpecan_k_wv_backward_fx_vf2 / _vf3, on the build of as many cells
+                                          per lane as the batch would run on without the flag): no ring of backward
+                                          cells, no expectation kernel.  The post kernel scales a segment's sums by
+                                          exp(estimate - total); a window whose estimate is not finite or lies more than
+                                          30 nats from one of its totals is swept once more against the exact totals
+                                          (CPECAN_EXPECT_RESWEEP=1 / 2 forces that for every / every other window:
+                                          tests).  cpecan_hip_batch_expectation_pass reports 1,
+                                          cpecan_hip_plan_expectation_pass answers beforehand; the kernel, family, rows
+                                          and widest band cpecan_hip_plan_dispatch names do not change.  Results agree
+                                          with the ring path to rounding (the sums are added in another order).  These
+                                          builds have no other form of the E-step: CPECAN_EXPECT_FUSED=0 does not undo
+                                          the flag.  Every other batch ignores it: a posterior batch, another machine,
+                                          a vanilla E-step on the general kernel (CPECAN_FLAG_GENERAL_KERNEL, a band
+                                          past 184 k-mers, band edges that step by more than one, a k-mer that is none)
+                                          or on the _ve workgroup builds (CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP, 185..504
+                                          k-mers).  Opt-in: tests pin that a vanilla batch of expectations without the
+                                          flag keeps the ring.  No environment variable of the C-ABI sets it;
+                                          libcpecan_host.so sets it for its vanilla batches of expectations when
+                                          CPECAN_VANILLA_FUSED_ESTEP=1 (the way in for vanillaAlign and
+                                          cpecan_trainModels). */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -426,7 +452,7 @@ int cpecan_hip_batch_create_dna(cpecan_ctx *ctx, const cpecan_item *items, int64
 /* k-mers against events with a vanilla model (getAlignedPairsUsingAnchors with a StateMachine3Vanilla,
  * sequence_getKmer2 / sequence_getEvent): same buffers as cpecan_hip_batch_create, model_id is a
  * cpecan_hip_modelsv_create id.  flags: UNBANDED (general kernel, posterior decode only), EXPECTATIONS, GENERAL_KERNEL,
- * WIDE_BANDS, WIDE_BANDS_VANILLA_ESTEP.  There is no kernel argument: the batch picks its kernels itself (the wave builds
+ * WIDE_BANDS, WIDE_BANDS_VANILLA_ESTEP, VANILLA_FUSED_ESTEP.  There is no kernel argument: the batch picks its kernels itself (the wave builds
  * up to 184 k-mers of band, the general kernel past that), and the two wide-bands flags alone select the workgroup builds
  * for bands of 185..504 k-mers: CPECAN_FLAG_WIDE_BANDS for the posterior decode, CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for
  * the E-step.
@@ -555,7 +581,8 @@ int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
  * wave kernels (CPECAN_EXPECT_FUSED=0 in the environment when the batch is created opts out) and, with
  * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP=1, on the workgroup kernels of one to four waves,
  * with CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WIDE=1 on those of six and eight waves
- * (cpecan_hip_batch_kernel_family tells which): no ring of backward cells, no expectation kernel.  0 for the
+ * (cpecan_hip_batch_kernel_family tells which), and the vanilla machine on the wave kernels (bands up to 184 k-mers)
+ * with CPECAN_FLAG_VANILLA_FUSED_ESTEP: no ring of backward cells, no expectation kernel.  0 for the
  * ring-of-backward-cells path and for posterior batches. */
 int cpecan_hip_batch_expectation_pass(cpecan_batch *batch, int32_t *fused);
 /* The same beforehand, without a batch and without a device, asked as cpecan_hip_plan_dispatch is: returns (and stores
