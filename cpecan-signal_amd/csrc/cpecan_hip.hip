@@ -38,25 +38,17 @@ extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
  * is past every build of the tables above and the batch carries the table's flag: CPECAN_FLAG_WIDE_BANDS for the
  * strawMan machine (_r) and the vanilla machine's posterior decode (_v), CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for the
  * vanilla E-step (_ve; without it that E-step stays on the general kernel), CPECAN_FLAG_WIDE_BANDS_HDP for the HDP
- * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f: the
- * strawMan E-step summed inside the sweep back, and no other form of it) stand in for the build of as many waves that the
- * rules above come to, as the last step of choose_dispatch and for a strawMan batch of expectations alone: _f<r> for
- * the workgroup family's build of r waves (bands up to 248 k-mers) when the batch carries
- * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP is 1, _f6 / _f8 for _r6 / _r8
- * (CPECAN_FLAG_WIDE_BANDS, a widest band of 249..504 k-mers) when it carries CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP or
- * CPECAN_EXPECT_FUSED_WIDE is 1.  Neither flag means anything to the other's range, to another machine or mode, to the
- * wave family or to the general kernel: such a batch runs what it runs without it.
- * The wave family has two fused builds of the same kind for the vanilla machine (_vf2, _vf3: cpecan_wavefx_build_vf<n>, the
- * Makefile's WV_FUSED_BUILDS): a vanilla batch of expectations that the rules above put on _v2 or _v3 and that carries
- * CPECAN_FLAG_VANILLA_FUSED_ESTEP runs on the one of as many cells per lane.  That flag means nothing to a posterior
- * batch, to another machine, to the general kernel or to the _ve builds of the workgroup family. */
+ * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f of the
+ * workgroup family, _vf of the wave family: the E-step summed inside the sweep back, and no other form of it) are in no
+ * table here: each stands in for the build of as many rows that the rules above come to, as the last step of
+ * choose_dispatch and for a batch of expectations alone (FUSED_STAND_INS, which also says what asks for each). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
 SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(cpecan_wave_build_l4)
 SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
-SWEEP_BUILD(cpecan_wavefx_build_vf2) SWEEP_BUILD(cpecan_wavefx_build_vf3)
+SWEEP_BUILD(cpecan_wave_build_vf2) SWEEP_BUILD(cpecan_wave_build_vf3)
 SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
 SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
@@ -65,13 +57,8 @@ SWEEP_BUILD(cpecan_systolic_build_f1) SWEEP_BUILD(cpecan_systolic_build_f2) SWEE
 SWEEP_BUILD(cpecan_systolic_build_f4) SWEEP_BUILD(cpecan_systolic_build_f6) SWEEP_BUILD(cpecan_systolic_build_f8)
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
-/* (the fused E-step of the build of as many waves in SY_BUILDS) */
-static SweepFamily SY_FUSED_BUILDS = { &cpecan_systolic_build_f1, &cpecan_systolic_build_f2, &cpecan_systolic_build_f3,
-                                       &cpecan_systolic_build_f4 };
 /* (a table of wide builds ends with a null entry) */
 static const SweepBuild *const SY_WIDE_BUILDS[3] = { &cpecan_systolic_build_r6, &cpecan_systolic_build_r8, nullptr };
-/* (the fused E-step of the build of as many waves in SY_WIDE_BUILDS) */
-static const SweepBuild *const SY_FUSED_WIDE_BUILDS[3] = { &cpecan_systolic_build_f6, &cpecan_systolic_build_f8, nullptr };
 static const SweepBuild *const SYV_WIDE_BUILDS[4] = { &cpecan_systolic_build_v4, &cpecan_systolic_build_v6,
                                                       &cpecan_systolic_build_v8, nullptr };
 static const SweepBuild *const SYH_WIDE_BUILDS[3] = { &cpecan_systolic_build_h6, &cpecan_systolic_build_h8, nullptr };
@@ -81,9 +68,6 @@ static const SweepBuild *const SYVE_WIDE_BUILDS[4] = { &cpecan_systolic_build_ve
 static SweepFamily WV_BUILDS = { &cpecan_wave_build_l2, &cpecan_wave_build_l2, &cpecan_wave_build_l3, &cpecan_wave_build_l4 };
 static SweepFamily HV_BUILDS = { &cpecan_wave_build_h2, &cpecan_wave_build_h2, &cpecan_wave_build_h3, &cpecan_wave_build_h4 };
 static SweepFamily VV_BUILDS = { &cpecan_wave_build_v2, &cpecan_wave_build_v2, &cpecan_wave_build_v3, &cpecan_wave_build_v3 };
-/* (the fused E-step of the build of as many cells per lane in VV_BUILDS) */
-static SweepFamily VV_FUSED_BUILDS = { &cpecan_wavefx_build_vf2, &cpecan_wavefx_build_vf2, &cpecan_wavefx_build_vf3,
-                                       &cpecan_wavefx_build_vf3 };
 
 namespace {
 
@@ -230,6 +214,25 @@ struct Dispatch {
     int refusal = CPECAN_OK;
     char why[160] = "";
 };
+/* The fused builds: a batch of expectations that the rules of choose_dispatch put on a row's ring build, and that carries
+ * the row's flag or whose environment has the row's switch on, runs on the row's fused build, of as many waves per
+ * workgroup or cells per lane.  The _r builds are the strawMan machine's alone and the _v wave builds the vanilla
+ * machine's, so a flag means nothing to another machine, mode, range of bands or family, or to the general kernel:
+ * such a batch runs what it runs without it (and a vanilla batch on the _ve workgroup builds keeps its build). */
+static const struct FusedStandIn {
+    const SweepBuild *ring, *fused;
+    int flag;
+    bool BatchEnv::*env; /* (null: no variable) */
+} FUSED_STAND_INS[] = {
+    { &cpecan_systolic_build_r1, &cpecan_systolic_build_f1, CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, &BatchEnv::fusedWorkgroup },
+    { &cpecan_systolic_build_r2, &cpecan_systolic_build_f2, CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, &BatchEnv::fusedWorkgroup },
+    { &cpecan_systolic_build_r3, &cpecan_systolic_build_f3, CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, &BatchEnv::fusedWorkgroup },
+    { &cpecan_systolic_build, &cpecan_systolic_build_f4, CPECAN_FLAG_WORKGROUP_FUSED_ESTEP, &BatchEnv::fusedWorkgroup },
+    { &cpecan_systolic_build_r6, &cpecan_systolic_build_f6, CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, &BatchEnv::fusedWide },
+    { &cpecan_systolic_build_r8, &cpecan_systolic_build_f8, CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, &BatchEnv::fusedWide },
+    { &cpecan_wave_build_v2, &cpecan_wave_build_vf2, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_wave_build_v3, &cpecan_wave_build_vf3, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
+};
 #define CP_WAVE5_MAX_WIDTH 192 /* cells: one to three per lane */
 static Dispatch choose_dispatch(const DispatchQuery &q) {
     const MachineRow &m = MACHINES[q.machine];
@@ -301,20 +304,10 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
                               : d.build->rows == ASM2_L && q.maxWidth <= ASM2_MAX_WIDTH && narrow ? ASM2_L : 0;
             d.asmSweeps = d.asmPlan && q.env.asmMode != 0 && d.build->post_asm && cells != 0;
             d.asmCells = d.asmSweeps ? cells : 0;
-            /* the fused builds of the workgroup family, for the build of as many waves (see the tables of builds) */
-            if (q.machine == STRAWMAN && q.mode == CPECAN_MODE_EXPECTATIONS) {
-                if ((d.flags & CPECAN_FLAG_WORKGROUP_FUSED_ESTEP) || q.env.fusedWorkgroup)
-                    for (int i = 0; i < 4; i++)
-                        if (d.build == SY_BUILDS[i]) d.build = SY_FUSED_BUILDS[i];
-                if ((d.flags & CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP) || q.env.fusedWide)
-                    for (int i = 0; SY_WIDE_BUILDS[i]; i++)
-                        if (d.build == SY_WIDE_BUILDS[i]) d.build = SY_FUSED_WIDE_BUILDS[i];
-            }
-            /* ... and the vanilla machine's of the wave family (a wide build of the workgroup family is in no entry of
-             * VV_BUILDS, so a batch on the _ve builds keeps its build) */
-            if (q.machine == VANILLA && q.mode == CPECAN_MODE_EXPECTATIONS && (d.flags & CPECAN_FLAG_VANILLA_FUSED_ESTEP))
-                for (int i = 0; i < 4; i++)
-                    if (d.build == VV_BUILDS[i]) d.build = VV_FUSED_BUILDS[i];
+            /* the fused build in the place of the ring build of as many rows, where the batch asks for it */
+            if (q.mode == CPECAN_MODE_EXPECTATIONS)
+                for (const FusedStandIn &f : FUSED_STAND_INS)
+                    if (d.build == f.ring && ((d.flags & f.flag) || (f.env && q.env.*f.env))) d.build = f.fused;
             /* the strawMan machine's E-step on the wave kernels sums its expectations inside the sweep back (same box,
              * configs[3] on one context: 97.2 against 150.8 ms per iteration); CPECAN_EXPECT_FUSED=0 keeps
              * the ring of backward cells and the expectation kernel.  A fused build of the workgroup family, or of the

@@ -47,7 +47,7 @@
  * Gaussian level term plus an inverse-Gaussian noise term per emission; symbols suffixed _v2, _v3 (four cells per lane spill: not built) */
 /* -DWV_VANILLA -DWV_FUSED: the vanilla machine's E-step with its expectations summed inside the sweep back and no other
  * kernel than that E-step needs (forward sweep, fused sweep back, post kernel, fused re-sweep), in objects of their own:
- * symbols suffixed _vf2, _vf3, the record cpecan_wavefx_build_vf<n>; the _v2 / _v3 objects keep their device code */
+ * symbols suffixed _vf2, _vf3; the _v2 / _v3 objects keep their device code */
 /* Every build holds the sweeps, their launchers and one SweepBuild record; what does not depend on the build (track,
  * counts, the machines' records) is cpecan_kernel_prep.hip's */
 #if defined(WV_FUSED) && !defined(WV_VANILLA)
@@ -2542,6 +2542,23 @@ extern "C" __global__ __launch_bounds__(WV_P) void WV_SYM(cpecan_k_wv_expect)(
  * is a choice of function pointer */
 static dim3 wv_sweep_grid(const SweepArgs &a) { return dim3((unsigned) ((a.nItems + WV_WPB - 1) / WV_WPB)); }
 static int wv_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+/* const auto var = the build's kernel k, or k_sw for a batch with the switch (a.withSwitch); where the build has no k_sw
+ * (the fused builds have none, and the vanilla machine has no gap Y -> gap X transition for an E-step to count), such a
+ * batch ends the launcher with -1 before anything is launched */
+#define WV_KERNEL_SW(var, k) const auto var = a.withSwitch ? WV_SYM(k##_sw) : WV_SYM(k)
+#define WV_KERNEL_NO_SW(var, k)                                                                                   \
+    if (a.withSwitch) return -1;                                                                                  \
+    const auto var = WV_SYM(k)
+#ifdef WV_FUSED
+#define WV_KERNEL WV_KERNEL_NO_SW
+#else
+#define WV_KERNEL WV_KERNEL_SW
+#endif
+#ifdef WV_VANILLA
+#define WV_KERNEL_EM WV_KERNEL_NO_SW
+#else
+#define WV_KERNEL_EM WV_KERNEL_SW
+#endif
 #ifndef WV_FUSED
 static void wv_sweep_back(decltype(&WV_SYM(cpecan_k_wv_backward)) k, hipStream_t stream, const SweepArgs &a, int window) {
     hipLaunchKernelGGL(k, wv_sweep_grid(a), dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track,
@@ -2557,12 +2574,7 @@ static void wv_post(hipStream_t stream, const SweepArgs &a, int window, bool fus
                        a.scratchBytes, window, fused ? 1 : 0, fused ? a.expect : nullptr, fused ? a.kidx : nullptr);
 }
 static int wv_launch_forward(hipStream_t stream, const SweepArgs &a, int window) {
-#ifdef WV_FUSED
-    if (a.withSwitch) return -1;
-    const auto forward = WV_SYM(cpecan_k_wv_forward);
-#else
-    const auto forward = a.withSwitch ? WV_SYM(cpecan_k_wv_forward_sw) : WV_SYM(cpecan_k_wv_forward);
-#endif
+    WV_KERNEL(forward, cpecan_k_wv_forward);
     hipLaunchKernelGGL(forward, wv_sweep_grid(a),
                        dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track, a.trackBase, a.events,
                        a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, window);
@@ -2574,23 +2586,20 @@ static int wv_launch_forward(hipStream_t stream, const SweepArgs &a, int window)
  * sweep back of a window (cpecan_asm.h), which leaves the refreshes' terms and the candidates in scratch as the
  * compiled sweep does */
 static int wv_launch_post(hipStream_t stream, const SweepArgs &a, int window) {
+    WV_KERNEL(resweep, cpecan_k_wv_resweep);
     wv_post(stream, a, window, false);
-    wv_sweep_back(a.withSwitch ? WV_SYM(cpecan_k_wv_resweep_sw) : WV_SYM(cpecan_k_wv_resweep), stream, a, window);
+    wv_sweep_back(resweep, stream, a, window);
     return wv_status();
 }
 static int wv_launch_backward(hipStream_t stream, const SweepArgs &a, int window) {
     if (a.P.mode != 0) {
-#if defined(WV_VANILLA)
-        if (a.withSwitch) return -1;
-        wv_sweep_back(WV_SYM(cpecan_k_wv_backward_em), stream, a, window);
-#else
-        wv_sweep_back(a.withSwitch ? WV_SYM(cpecan_k_wv_backward_em_sw) : WV_SYM(cpecan_k_wv_backward_em), stream, a,
-                      window);
-#endif
+        WV_KERNEL_EM(backward_em, cpecan_k_wv_backward_em);
+        wv_sweep_back(backward_em, stream, a, window);
         wv_post(stream, a, window, false);
         return wv_status();
     }
-    wv_sweep_back(a.withSwitch ? WV_SYM(cpecan_k_wv_backward_sw) : WV_SYM(cpecan_k_wv_backward), stream, a, window);
+    WV_KERNEL(backward, cpecan_k_wv_backward);
+    wv_sweep_back(backward, stream, a, window);
     return wv_launch_post(stream, a, window);
 }
 static int wv_launch_expect(hipStream_t stream, const SweepArgs &a, int window) {
@@ -2613,25 +2622,28 @@ static void wv_sweep_back_fx(decltype(&WV_SYM(cpecan_k_wv_backward_fx)) k, hipSt
                        a.scratchBytes, a.expect, a.kidx, window);
 }
 static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int window) {
-#ifdef WV_FUSED
-    if (a.withSwitch) return -1;
-    wv_sweep_back_fx(WV_SYM(cpecan_k_wv_backward_fx), stream, a, window);
+    WV_KERNEL(backward_fx, cpecan_k_wv_backward_fx);
+    WV_KERNEL(resweep_fx, cpecan_k_wv_resweep_fx);
+    wv_sweep_back_fx(backward_fx, stream, a, window);
     wv_post(stream, a, window, true);
-    wv_sweep_back_fx(WV_SYM(cpecan_k_wv_resweep_fx), stream, a, window);
-    return wv_status();
-}
-#else
-    wv_sweep_back_fx(a.withSwitch ? WV_SYM(cpecan_k_wv_backward_fx_sw) : WV_SYM(cpecan_k_wv_backward_fx), stream, a, window);
-    wv_post(stream, a, window, true);
-    wv_sweep_back_fx(a.withSwitch ? WV_SYM(cpecan_k_wv_resweep_fx_sw) : WV_SYM(cpecan_k_wv_resweep_fx), stream, a, window);
+    wv_sweep_back_fx(resweep_fx, stream, a, window);
     return wv_status();
 }
 #endif
-#endif
+/* what a build lacks is a null entry of its record: both forms of the E-step and the post launch of the assembly sweeps
+ * are the strawMan builds', a fused build has the fused E-step and nothing else */
 #if !defined(WV_VANILLA) && !defined(WV_HDP)
 #define WV_STRAWMAN_ONLY(f) f
+#define WV_FX(f) f
+#define WV_RING(f) f
+#elif defined(WV_FUSED)
+#define WV_STRAWMAN_ONLY(f) nullptr
+#define WV_FX(f) f
+#define WV_RING(f) nullptr
 #else
 #define WV_STRAWMAN_ONLY(f) nullptr
+#define WV_FX(f) nullptr
+#define WV_RING(f) f
 #endif
 
 /* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
@@ -2645,20 +2657,10 @@ static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int win
 #endif
 /* scratch: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list], and after it,
  * in batches with fused expectations, the segments' sums (WvFx) */
-#ifdef WV_FUSED
-/* (a name of its own, cpecan_wavefx_build_vf<n>: these builds are not among the Makefile's WV_BUILDS; they have the
- * fused E-step and nothing else) */
-extern "C" const SweepBuild WV_SYM(cpecan_wavefx_build);
-const SweepBuild WV_SYM(cpecan_wavefx_build) = {
-    WV_L, true, WV_MACHINE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
-    wv_scratch_base_bytes, wv_fx_bytes,
-    wv_launch_forward, nullptr, wv_launch_backward_fx, nullptr, nullptr };
-#else
 extern "C" const SweepBuild WV_SYM(cpecan_wave_build);
 const SweepBuild WV_SYM(cpecan_wave_build) = {
     WV_L, true, WV_MACHINE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
-    wv_scratch_base_bytes, WV_STRAWMAN_ONLY(wv_fx_bytes),
-    wv_launch_forward, wv_launch_backward, WV_STRAWMAN_ONLY(wv_launch_backward_fx), wv_launch_expect,
+    wv_scratch_base_bytes, WV_FX(wv_fx_bytes),
+    wv_launch_forward, WV_RING(wv_launch_backward), WV_FX(wv_launch_backward_fx), WV_RING(wv_launch_expect),
     WV_STRAWMAN_ONLY(wv_launch_post) };
-#endif
 #endif

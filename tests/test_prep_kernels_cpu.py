@@ -11,6 +11,7 @@ import pytest
 
 from cpecan_load import ROOT
 from sweep_builds import builds, defined
+from test_sweep_build_resources import WAVE
 
 AMD = os.path.join(ROOT, "cpecan-signal_amd")
 ONCE = ("cpecan_k_kmer_index", "cpecan_k_hdp_kmer_id", "cpecan_k_track", "cpecan_k_sy_track_hdp", "cpecan_k_wv_track",
@@ -44,7 +45,7 @@ def test_once_kernels_are_in_the_prep_object_alone(objects):
 
 def test_sweep_objects_define_their_own_build_only(objects):
     listed = dict((b.obj, b) for b in builds() if b.name)
-    assert len(listed) >= 27 and set(listed) <= set(objects)
+    assert len(listed) >= 31 and set(listed) <= set(objects)
     seen = 0
     for p, names in objects.items():
         m = re.fullmatch(r"cpecan_kernel_(systolic|wave)(_[a-z]+\d)\.o", os.path.basename(p))
@@ -61,6 +62,8 @@ def test_sweep_objects_define_their_own_build_only(objects):
         if m.group(1) == "systolic":  # forward and backward, and an expectation kernel where the E-step is not elsewhere
             stems = ("forward", "backward") + (() if listed[p].tag in NO_EXPECT else ("expect",))
             assert kernels == set("cpecan_k_sy_%s%s" % (s, m.group(2)) for s in stems), os.path.basename(p)
+        else:  # the kernels of the tag's row
+            assert kernels == set("cpecan_k_wv_%s%s" % (s, m.group(2)) for s in WAVE[listed[p].tag][0]), os.path.basename(p)
     assert seen == len(listed)  # every suffixed build of the Makefile's list, and no other object of that name
 
 

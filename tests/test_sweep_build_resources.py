@@ -2,8 +2,9 @@
 keeps the registers, the scratch and the static LDS its occupancy is designed around, from the compiler's own metadata:
 the register allocator has crossed such a line silently before (an inlined helper with its own constants, a loop the
 optimiser decided to clone), halving the measured throughput.  One table per kernel file, keyed by the build's tag; a
-build added to the Makefile's list is held to its tag's row with no edit here.  The library exports one record per listed
-build and nothing else under those names.  CPU-only: hipcc cross-compiles gfx950."""
+build added to the Makefile's list under a tag that has a row is held to it with no edit here, a new tag needs its row.
+The library exports one record per listed build and nothing else under those names.  CPU-only: hipcc cross-compiles
+gfx950."""
 import os
 import re
 import shutil
@@ -73,16 +74,19 @@ def test_workgroup_build_keeps_its_kernels_and_budget(build):
 SWEEPS = ("forward", "forward_sw", "backward", "backward_sw", "backward_em", "resweep", "resweep_sw", "expect", "post")
 BACK = ("backward", "resweep", "backward_em")  # (every machine's E-step sweeps back with the last)
 FX = ("backward_fx", "backward_fx_sw", "resweep_fx", "resweep_fx_sw")  # the expectations summed inside the sweep back
+FXV = ("backward_fx", "resweep_fx")  # ... of the vanilla machine's fused builds: no switch, and no other sweep back
 # tag: the kernels of a build; per number of cells, the sweeps back that share a SIMD with the forward sweep (one
 # forward and one backward wave per SIMD: the forward sweep of window w+1 beside the backward sweep of window w; a
 # unified register file of 512 per lane, handed out in blocks of 8) and the ones that only must not spill; the VGPRs of
 # the forward sweep where they are capped.  Four cells per lane are the documented exception (the backward sweep takes
 # 306 registers: one wave per SIMD while it runs), and at three the fused sweeps back are one too (364 against 248
-# beside the forward sweep; measured faster than the B-ring path all the same)
+# beside the forward sweep; measured faster than the B-ring path all the same), as are the vanilla machine's
+# (304 beside 264)
 WAVE = {
     "l": (SWEEPS + ("backward_em_sw",) + FX, {2: BACK + FX, 3: BACK}, {3: FX}, None),
     "h": (SWEEPS + ("backward_em_sw",), {3: BACK}, {}, 192),  # three register pairs per slot, not ten: a light forward
     "v": (SWEEPS, {2: BACK}, {}, None),
+    "vf": (("forward", "post") + FXV, {2: FXV, 3: ()}, {3: FXV}, None),  # the fused E-step and nothing else
 }
 
 
@@ -106,6 +110,26 @@ def test_wave_build_keeps_its_kernels_and_budget(build):
                     stem, build.suffix, m["vgpr"], forward["vgpr"])
 
 
+@needs_hipcc
+@pytest.mark.parametrize("name", ("vf2", "vf3"))
+def test_vanilla_fused_build_spills_nowhere_and_keeps_the_ring_builds_forward_sweep(name):
+    """the vanilla machine's fused builds are compiled as the vanilla builds plus -DWV_FUSED; none of their four kernels,
+    the post kernel included, touches scratch; and the forward sweep is the one of the build they stand in for (_v<n>):
+    the same registers and static LDS"""
+    listed = dict((b.name, b) for b in builds())
+    build, ring = listed[name], listed["v" + name[2]]
+    assert build.defines == ("-DWV_L=" + name[2], "-DWV_VANILLA", "-DWV_FUSED")
+    text = device_asm(build)
+    assert "cpecan_k_wv_expect" not in text and "backward_em" not in text
+    for stem in WAVE["vf"][0]:
+        m = kernel_meta(text, "cpecan_k_wv_%s%s" % (stem, build.suffix))
+        assert m["spill"] == 0 and m["scratch"] == 0 and "scratch_" not in m["body"], "%s%s spills" % (stem, build.suffix)
+        assert m["threads"] == (256 if stem == "post" else 64)
+    mine = kernel_meta(text, "cpecan_k_wv_forward" + build.suffix)
+    theirs = kernel_meta(device_asm(ring), "cpecan_k_wv_forward" + ring.suffix)
+    assert (mine["vgpr"], mine["sgpr"], mine["lds"]) == (theirs["vgpr"], theirs["sgpr"], theirs["lds"])
+
+
 def test_library_exports_the_declared_names_and_the_listed_builds():
     """a build adds kernels and one record, no entry point: what libcpecan_hip.so exports under the cpecan_hip_ prefix is
     exactly what include/cpecan_hip.h declares, its build records are exactly the list's, and every object is there"""
@@ -123,5 +147,8 @@ def test_library_exports_the_declared_names_and_the_listed_builds():
     assert re.search(r"#define CPECAN_FLAG_WORKGROUP_FUSED_ESTEP 2048\b", header)
     listed = set("cpecan_%s_build%s" % (b.family, b.suffix) for b in builds())
     assert set(n for n in names if re.match(r"cpecan_(systolic|wave)_build", n)) == listed
+    assert {"cpecan_wave_build_vf2", "cpecan_wave_build_vf3"} <= listed
+    # ... under the family's name, not one of their own as when they were off the list (cpecan_wave<something>_build_vf<n>)
+    assert not any(re.match(r"cpecan_wave[^_]", n) for n in names)
     assert "cpecan_systolic_build_h4" not in names  # the HDP wave builds reach 248: no four-wave build
     assert {"cpecan_systolic_machine", "cpecan_systolic_machine_vanilla", "cpecan_systolic_machine_hdp"} <= names

@@ -19,14 +19,14 @@ from concurrent.futures import ThreadPoolExecutor
 WIDTHS = (0, 1, 56, 57, 120, 121, 158, 159, 184, 185, 192, 193, 248, 249, 376, 377, 504, 505)
 BASES = ("WORKGROUP_KERNELS", "GENERAL_KERNEL", "UNBANDED", "DEBUG_DUMP", "WIDE_BANDS")
 WITH = ("WIDE_BANDS", "WIDE_BANDS_HDP", "WIDE_BANDS_HDP_ESTEP", "WIDE_BANDS_VANILLA_ESTEP", "WORKGROUP_FUSED_ESTEP",
-        "WIDE_BANDS_FUSED_ESTEP", "ASM_NARROW_BANDS")  # the wide, fused and asm flags
+        "WIDE_BANDS_FUSED_ESTEP", "ASM_NARROW_BANDS", "VANILLA_FUSED_ESTEP")  # the wide, fused and asm flags
 
 
 def grid_of(branch):
     """(flags, environment settings) of the grid, from the branch tree's header and source"""
     header = open(os.path.join(branch, "include", "cpecan_hip.h")).read()
     flag = dict((n, int(v)) for n, v in re.findall(r"#define CPECAN_FLAG_(\w+) (\d+)", header))
-    flags = [0] + [1 << k for k in range(14)] + [flag[b] | flag[w] for b in BASES for w in WITH]
+    flags = [0] + list(flag.values()) + [flag[b] | flag[w] for b in BASES for w in WITH]
     source = open(os.path.join(branch, "cpecan-signal_amd", "csrc", "cpecan_hip.hip")).read()
     at = source.index("static BatchEnv read_batch_env()")
     names = re.findall(r'getenv\("(CPECAN_[A-Z0-9_]+)"\)', source[at:source.index("\n}\n", at)])
