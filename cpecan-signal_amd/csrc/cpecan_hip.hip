@@ -39,7 +39,8 @@ extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
  * strawMan machine (_r) and the vanilla machine's posterior decode (_v), CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for the
  * vanilla E-step (_ve; without it that E-step stays on the general kernel), CPECAN_FLAG_WIDE_BANDS_HDP for the HDP
  * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f of the
- * workgroup family, _vf of the wave family: the E-step summed inside the sweep back, and no other form of it) are in no
+ * workgroup family, _vf of the wave family, and the vanilla machine's _vf4 / _vf6 / _vf8 of the workgroup family, the
+ * Makefile's SY_FUSED_BUILDS: the E-step summed inside the sweep back, and no other form of it) are in no
  * table here: each stands in for the build of as many rows that the rules above come to, as the last step of
  * choose_dispatch and for a batch of expectations alone (FUSED_STAND_INS, which also says what asks for each). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
@@ -55,6 +56,7 @@ SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
 SWEEP_BUILD(cpecan_systolic_build_ve4) SWEEP_BUILD(cpecan_systolic_build_ve6) SWEEP_BUILD(cpecan_systolic_build_ve8)
 SWEEP_BUILD(cpecan_systolic_build_f1) SWEEP_BUILD(cpecan_systolic_build_f2) SWEEP_BUILD(cpecan_systolic_build_f3)
 SWEEP_BUILD(cpecan_systolic_build_f4) SWEEP_BUILD(cpecan_systolic_build_f6) SWEEP_BUILD(cpecan_systolic_build_f8)
+SWEEP_BUILD(cpecan_systolicfx_build_vf4) SWEEP_BUILD(cpecan_systolicfx_build_vf6) SWEEP_BUILD(cpecan_systolicfx_build_vf8)
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
 /* (a table of wide builds ends with a null entry) */
@@ -218,7 +220,9 @@ struct Dispatch {
  * the row's flag or whose environment has the row's switch on, runs on the row's fused build, of as many waves per
  * workgroup or cells per lane.  The _r builds are the strawMan machine's alone and the _v wave builds the vanilla
  * machine's, so a flag means nothing to another machine, mode, range of bands or family, or to the general kernel:
- * such a batch runs what it runs without it (and a vanilla batch on the _ve workgroup builds keeps its build). */
+ * such a batch runs what it runs without it.  A vanilla batch on the _ve workgroup builds (reached with
+ * CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP alone) keeps its build under the wave builds' flag and leaves it for _vf4 / _vf6 /
+ * _vf8 under one of its own. */
 static const struct FusedStandIn {
     const SweepBuild *ring, *fused;
     int flag;
@@ -232,6 +236,9 @@ static const struct FusedStandIn {
     { &cpecan_systolic_build_r8, &cpecan_systolic_build_f8, CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, &BatchEnv::fusedWide },
     { &cpecan_wave_build_v2, &cpecan_wave_build_vf2, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
     { &cpecan_wave_build_v3, &cpecan_wave_build_vf3, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_ve4, &cpecan_systolicfx_build_vf4, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_ve6, &cpecan_systolicfx_build_vf6, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_ve8, &cpecan_systolicfx_build_vf8, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
 };
 #define CP_WAVE5_MAX_WIDTH 192 /* cells: one to three per lane */
 static Dispatch choose_dispatch(const DispatchQuery &q) {

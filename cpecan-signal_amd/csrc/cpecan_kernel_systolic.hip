@@ -84,8 +84,17 @@
  * The terms are taken against the window's estimated total and kept per refresh segment (FxRecords); after phase T they
  * are scaled to the exact totals and added to the model's sums (fx_finish), and a window whose estimate cannot be
  * trusted is swept back once more, in the same launch, against the exact totals. */
-#if defined(SY_FUSED) && (defined(SY_HDP) || defined(SY_VANILLA) || defined(SY_ESTEP))
-#error "SY_FUSED: a build of the strawMan machine"
+/* -DSY_VANILLA -DSY_FUSED: the vanilla machine's E-step with its expectations summed inside the sweep back, with four,
+ * six and eight waves per workgroup (the bands of _ve4 / _ve6 / _ve8), in objects of their own that the Makefile keeps
+ * on a list of their own (SY_FUSED_BUILDS: symbols suffixed _vf4, _vf6, _vf8, the record cpecan_systolicfx_build_vf<n>;
+ * the _ve objects keep their device code).  The forward sweep is the _ve builds'.  This machine collects two terms per
+ * cell and no transition, both from the cell's lower neighbour (cpecan_k_sy_expect, vanilla form), so the sweep back
+ * fetches F.gapX beside F.match, takes B.gapX and the column's a_mx / a_xx apart down the lanes (the recurrence's sums
+ * are formed by the receiver: the same doubles) and keeps (column, beta, alpha) per slot and refresh segment, in
+ * registers: no ring of backward cells, no expectation kernel.  The estimate, the segments' scaling, the second sweep
+ * and DevParams::expectResweep are the strawMan fused builds' (above); fx_finish adds through 60 bins in LDS. */
+#if defined(SY_FUSED) && (defined(SY_HDP) || defined(SY_ESTEP))
+#error "SY_FUSED: a build of the strawMan machine or, with SY_VANILLA alone, of the vanilla machine"
 #elif defined(SY_HDP) && defined(SY_VANILLA)
 #error "SY_HDP and SY_VANILLA are builds of their own"
 #elif defined(SY_ESTEP) && !defined(SY_HDP) && !defined(SY_VANILLA)
@@ -100,7 +109,9 @@
 #error "SY_R: 1, 2, 3, 4, 6 or 8 waves per workgroup"
 #endif
 /* a symbol's suffix: the machine's tag and the number of waves; the strawMan's four-wave build alone has none */
-#if defined(SY_FUSED)
+#if defined(SY_FUSED) && defined(SY_VANILLA)
+#define SY_SYM(n) SWEEP_SYM(n, vf, SY_R)
+#elif defined(SY_FUSED)
 #define SY_SYM(n) SWEEP_SYM(n, f, SY_R)
 #elif defined(SY_ESTEP) && defined(SY_VANILLA)
 #define SY_SYM(n) SWEEP_SYM(n, ve, SY_R)
@@ -116,6 +127,10 @@
 #define SY_SYM(n) n
 #endif
 #if defined(SY_VANILLA) /* the vanilla row does not fit 128 VGPRs: whatever occupancy the allocation lands on */
+/* (the _ve sweep back lands on 124..128; the fused one, _vf, on 141..145: the four F.gapX in flight, the two sums, their
+ * column and the record addresses are seventeen registers the 128 do not have -- held to four waves per SIMD it spills
+ * twelve to fourteen, eight with the sums in LDS, six to twelve with three of the row's transitions there too -- so it
+ * runs three waves per SIMD) */
 #define SY_BACKWARD_ATTR
 #elif defined(SY_FUSED) && SY_R == 6 && !defined(SY_FX_REG_SUMS)
 /* the six-wave fused sweep back with its eight sums in LDS (SY_FX_LDS below) fits three waves per SIMD without a spill (165
@@ -150,7 +165,7 @@
 #define SY_MODEL_DOUBLES ((long long) CP_VMODEL_STRIDE)
 #define SY_MACHINE_ID SWEEP_VANILLA /* (the build's record, at the end of the file) */
 #define SY_MACHINE cpecan_systolic_machine_vanilla
-#ifdef SY_ESTEP
+#if defined(SY_ESTEP) || defined(SY_FUSED)
 #define SY_MODE(P) 1 /* E-step only */
 #else
 #define SY_MODE(P) 0 /* posterior decode only */
@@ -198,20 +213,24 @@
 #else
 #define SY_FX false
 #endif
-/* SY_FXQ(...): arguments only the fused builds' fetch and step take (a row's F.gapX and F.gapY) */
-#ifdef SY_FUSED
-#define SY_FXQ(...) , __VA_ARGS__
+/* SY_FXQ(x, y): arguments only the fused builds' fetch and step take (a row's F.gapX and F.gapY; the vanilla machine's
+ * terms start at no gap-Y cell: F.gapX alone) */
+#if defined(SY_FUSED) && defined(SY_VANILLA)
+#define SY_FXQ(x, y) , x
+#elif defined(SY_FUSED)
+#define SY_FXQ(x, y) , x, y
 #else
-#define SY_FXQ(...)
+#define SY_FXQ(x, y)
 #endif
 /* SY_FX_LDS: the fused sweep back keeps a lane's eight transition sums in LDS, [sum][thread], instead of sixteen VGPRs --
  * the six-wave build only: up to four waves no occupancy is in reach of sixteen registers, at eight only 128 registers
  * would bring a second workgroup to the CU.  -DSY_FX_REG_SUMS (a timing-study switch, like SY_ABLATE_*, with the same
  * results) keeps them in registers there too */
-#if defined(SY_FUSED) && SY_R == 6 && !defined(SY_FX_REG_SUMS)
+#if defined(SY_FUSED) && !defined(SY_VANILLA) && SY_R == 6 && !defined(SY_FX_REG_SUMS)
 #define SY_FX_LDS
 #endif
 #define SY_FX_EST_BOUND 30.0 /* nats an exact total may lie from the estimate the fused sums were taken against */
+#define SY_FX_ZERO (-746.0)  /* exp() below this is +0 in double precision (the least denormal is exp(-744.44)) */
 /* per cell in the ring of backward cells: the three states, or the one the vanilla E-step reads (gap X) */
 #if defined(SY_VANILLA)
 #define SY_BRING_VALUES 1
@@ -275,8 +294,13 @@ struct Shared {
     int cnt[2][SY_R][2];     /* aligned-pair counts per wave, double-buffered */
     int item;
     int scan;                /* this window's posteriors must be decoded by the full scan */
-#ifdef SY_FUSED
+#if defined(SY_FUSED) && !defined(SY_VANILLA)
     int fxRedo;              /* this window's sums must be taken again, against the exact totals */
+#define SY_FX_REDO(sh) (sh).fxRedo
+#elif defined(SY_FUSED)
+/* (the vanilla fused builds keep the forward sweep's LDS that of the _ve builds: the flag lives in the decode's first
+ * pair count, which no E-step build reads or writes) */
+#define SY_FX_REDO(sh) (sh).cnt[0][0][0]
 #endif
 };
 
@@ -949,22 +973,86 @@ __device__ __forceinline__ double uni_d(double v) {
  *       need the band to travel SY_P columns within the segment's eleven diagonals
  *   c   their matrix columns (-1: none)
  * The sweep writes every record of every segment it closes, so nothing is left over from an earlier window or run.
+ * The vanilla machine (-DSY_VANILLA) collects two sums per cell and no transition: no tr, and a record of g is the pair
+ * (beta: match -> gap X, alpha: gap X -> gap X) of its column, [segment][A | B][slot][2].
  */
 struct FxRecords {
     double *tr, *g;
     int *c;
 };
+#ifdef SY_VANILLA
+#define SY_FX_TR 0 /* doubles per wave and segment of tr, per record of g */
+#define SY_FX_G 2
+#else
+#define SY_FX_TR 8
+#define SY_FX_G 1
+#endif
 static __host__ __device__ long long sy_fx_bytes(int ringD) {
-    return ((long long) ringD / 10 + 8) * (SY_R * 8 * sizeof(double) + 2 * SY_P * (sizeof(double) + sizeof(int)));
+    return ((long long) ringD / 10 + 8)
+           * (SY_R * SY_FX_TR * sizeof(double) + 2 * SY_P * (SY_FX_G * sizeof(double) + sizeof(int)));
 }
 __device__ __forceinline__ FxRecords fx_records(char *base, int ringD) {
     const long long nW = (long long) ringD / 10 + 8;
     FxRecords f;
     f.tr = (double *) base;
-    f.g = f.tr + nW * SY_R * 8;
-    f.c = (int *) (f.g + nW * 2 * SY_P);
+    f.g = f.tr + nW * SY_R * SY_FX_TR;
+    f.c = (int *) (f.g + nW * 2 * SY_P * SY_FX_G);
     return f;
 }
+#ifdef SY_VANILLA
+/* A window's fused sums into the model's expectations (layout of cpecan_k_sy_expect's, vanilla form: 30 + 30 skip bins and
+ * the likelihood); the whole workgroup.  Segment k's sums were taken against the estimate and scale by
+ * exp(est - total_k), or, on the second sweep (exact), against total_k itself.  Every thread adds the records of its
+ * slot, one pair of LDS atomics per column, to the window's 60 bin sums (bins: SY_P doubles of LDS no E-step uses
+ * otherwise), the bin being entry 21 of the column's track row; then threads 0-59 add those to the model's, thread 60 the
+ * likelihood (the exact total once per decoded diagonal, :849). */
+__device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal *wtot, const int nSeg, const int tPost0,
+                          const int to, const double est, const bool exact, double *expect,
+                          const double *__restrict__ track, double *bins) {
+    double *dst = expect + (long long) it.model * CP_EXPECTV_LEN;
+    const int tid = threadIdx.x;
+    if (tid < 60) bins[tid] = 0.0;
+    __syncthreads();
+    auto add = [&](const int col, const double beta, const double alpha) __attribute__((always_inline)) {
+        const int bin = col > 0 && col <= (int) it.lX ? (int) track[(long long) col * SY_ROW + 21] : -1;
+        if (bin >= 0 && bin < 30) {
+            if (beta != 0.0) atomicAdd(&bins[bin], beta);
+            if (alpha != 0.0) atomicAdd(&bins[bin + 30], alpha);
+        }
+    };
+    int cur = -1;
+    double beta = 0.0, alpha = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < nSeg; k++) {
+        const double f = exact ? 1.0 : exp(est - wtot[k].total);
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            const long long i = (long long) (k * 2 + r) * SY_P + tid;
+            const int col = fx.c[i];
+            const double b = fx.g[i * 2], a = fx.g[i * 2 + 1];
+            if (col > 0 && (b != 0.0 || a != 0.0)) {
+                if (col != cur) {
+                    add(cur, beta, alpha);
+                    cur = col;
+                    beta = alpha = 0.0;
+                }
+                beta += f * b;
+                alpha += f * a;
+            }
+        }
+    }
+    add(cur, beta, alpha);
+    __syncthreads();
+    if (tid < 60) {
+        if (bins[tid] != 0.0) atomicAdd(dst + tid, bins[tid]);
+    } else if (tid == 60) {
+        double lik = 0.0;
+#pragma unroll 1
+        for (int u = tPost0; u > to; u--) lik += wtot[(tPost0 - u) / 10].total;
+        atomicAdd(dst + 60, lik);
+    }
+}
+#else
 /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y into the model's nine transition sums (from * 3 + to) */
 #define SY_EXPECT_SLOTS { 0 * 3 + 1, 1 * 3 + 1, 2 * 3 + 1, 0 * 3 + 0, 1 * 3 + 0, 2 * 3 + 0, 0 * 3 + 2, 2 * 3 + 2 }
 
@@ -1015,6 +1103,7 @@ __device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal
     }
     if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
 }
+#endif /* SY_VANILLA */
 #endif /* SY_FUSED */
 
 /*
@@ -1071,7 +1160,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
      * candidates leave those out: the scan decodes the window, as in the wave kernels */
     if (threadIdx.x == 0) sh.scan = P.logThrSlack > CP_NEG_INF ? 0 : 1;
 #ifdef SY_FUSED
-    if (threadIdx.x == 0) sh.fxRedo = fxForce ? 1 : 0;
+    if (threadIdx.x == 0) SY_FX_REDO(sh) = fxForce ? 1 : 0;
 #endif
     __syncthreads();
     /* Candidates for the posterior decode, collected by the sweep: a cell whose F.match + B.match
@@ -1181,14 +1270,80 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             f = p[0];
             pm = p[3 * 64];
             py = p[4 * 64];
-#ifdef SY_FUSED /* the fused E-step reads the row's two gap states too */
+#ifdef SY_FUSED /* the fused E-step reads the row's two gap states too (the vanilla machine's: gap X) */
             fx = p[1 * 64];
+#ifndef SY_VANILLA
             fy = p[2 * 64];
+#endif
 #endif
         };
         int calcs = 0, nTotWin = 0;
         int xsN = xs; /* this slot's k-mer on diagonal t+1 */
-#ifdef SY_FUSED
+#if defined(SY_FUSED) && defined(SY_VANILLA)
+        /*
+         * The terms of diagonalCalculation_Expectations (:841-863 with cell_signal_updateBetaAndAlphaProb :478-498), those
+         * cpecan_k_sy_expect (vanilla form) takes from the two rings: match -> gap X (beta) and gap X -> gap X (alpha), from
+         * the cell's lower neighbour, into the skip bin of the cell's column.  A slot that holds the forward cell (t, x)
+         * also holds, shifted down from the slot above, B.gapX of the cell (t+1, x+1) and that column's a_mx and a_xx --
+         * what the backward recurrence's lower block gathers from.  Each term is taken against the total of diagonal t+1:
+         * the window's estimate, or on the second sweep the exact total of that diagonal's segment.  Sums per segment:
+         * beta and alpha of the column the slot points at (gCol = x + 1), in registers: five VGPRs, and keeping them in LDS
+         * brings no occupancy step in reach (SY_BACKWARD_ATTR).
+         */
+        double beta = 0.0, alpha = 0.0, refX = exact ? uni_d(ld_agent(&wtot[0].total)) : 0.0;
+        int gCol = -1, segAcc = 0;
+        const int fxSlot = wave * 64 + lane;
+        fxo.c[fxSlot] = -1; /* segment 0 has no A record yet */
+        auto fx_flush = [&]() __attribute__((always_inline)) {
+            fxo.g[((segAcc * 2 + 1) * SY_P + fxSlot) * 2 + 0] = beta;
+            fxo.g[((segAcc * 2 + 1) * SY_P + fxSlot) * 2 + 1] = alpha;
+            fxo.c[(segAcc * 2 + 1) * SY_P + fxSlot] = gCol;
+            fxo.c[(segAcc * 2 + 2) * SY_P + fxSlot] = -1; /* the next segment's A record */
+            beta = alpha = 0.0;
+            segAcc++;
+            if (exact) refX = uni_d(ld_agent(&wtot[segAcc].total));
+        };
+        /* fM, fX: the slot's forward cell on diagonal t (-inf outside the band), x its column, in: it is in the band; lB,
+         * aMX, aXX: B.gapX of (t+1, x+1) and that column's two transitions; nMin..nMax the band of t+1.  Called with
+         * t+1 <= tPost0. */
+        auto fx_terms = [&](const int t, const bool on, const int x, const bool in, const double fM, const double fX,
+                            const double lB, const double aMX, const double aXX, const int nMin, const int nMax)
+                            __attribute__((always_inline)) {
+            if (t + 2 <= tPost0 && (tPost0 - (t + 2)) % 10 == 9) fx_flush(); /* t+2 ended its segment */
+            if (on) {
+                const double ref = exact ? refX : totEst;
+                /* (second sweep only) a total of -inf or NaN: every term is NaN, as in the reference, and the terms must
+                 * then be those the reference forms -- a cell of the band whose lower neighbour is in the band too --
+                 * instead of one per slot */
+                const bool nf = exact && !(ref > CP_NEG_INF);
+                /* exp() of anything below SY_FX_ZERO is +0: a wave none of whose lanes holds a larger exponent (or a NaN)
+                 * -- most waves of a wide band, whose cells far from the alignment lie thousands of nats under the
+                 * total -- adds its zeros without the two exp() calls, a third of the step's instructions */
+                const double a0 = fM + lB + (0 + aMX) - ref, a1 = fX + lB + (0 + aXX) - ref;
+                double p0 = 0.0, p1 = 0.0;
+                if (__ballot(!(a0 < SY_FX_ZERO) || !(a1 < SY_FX_ZERO)) != 0ull) {
+                    p0 = exp(a0);
+                    p1 = exp(a1);
+                }
+                const bool inL = in && x + 1 >= nMin && x + 1 <= nMax; /* the cell (t+1, x+1) exists */
+                if (nf) {
+                    p0 = inL ? p0 : 0.0;
+                    p1 = inL ? p1 : 0.0;
+                }
+                if (inL && x + 1 != gCol) { /* the slot points at another column than before */
+                    if (beta != 0.0 || alpha != 0.0) {
+                        fxo.g[((segAcc * 2) * SY_P + fxSlot) * 2 + 0] = beta;
+                        fxo.g[((segAcc * 2) * SY_P + fxSlot) * 2 + 1] = alpha;
+                        fxo.c[(segAcc * 2) * SY_P + fxSlot] = gCol;
+                    }
+                    beta = alpha = 0.0;
+                    gCol = x + 1;
+                }
+                beta += p0;
+                alpha += p1;
+            }
+        };
+#elif defined(SY_FUSED)
         /*
          * The terms of diagonalCalculation_Expectations (:841-863 with cell_signal_updateTransAndKmerSkipExpectations
          * :426-443), those cpecan_k_sy_expect forms from the two rings.  A slot that holds the forward cell (t, x) also
@@ -1308,7 +1463,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             }
             const bool vt = xs >= bxmin;
             const double fMc = vt ? qF : CP_NEG_INF, pmc = vt ? qPm : 0.0, pyc = vt ? qPy : 0.0;
-#ifdef SY_FUSED
+#if defined(SY_FUSED) && defined(SY_VANILLA)
+            const double fXc = vt ? qFx : CP_NEG_INF;
+#elif defined(SY_FUSED)
             const double fXc = vt ? qFx : CP_NEG_INF, fYc = vt ? qFy : CP_NEG_INF;
 #endif
             /* the slot's k-mer SY_PREFETCH diagonals down is xs or out of band (bands <= SY_P - 2 * depth) */
@@ -1319,7 +1476,14 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
 #ifdef SY_VANILLA
                 /* of slot+1 on t+1: the lower block's sums (used now) and the middle block's (one diagonal further
                  * down); tr[] is still that diagonal's here */
+#ifdef SY_FUSED
+                /* (the fused terms take B.gapX and the two transitions apart, so those travel and the lower block's
+                 * sums are formed here: the same operands, the same doubles) */
+                const double rBx = shl1(xa[5], Bx), rA0 = shl1(xa[6], tr[0]), rA1 = shl1(xa[7], tr[1]);
+                const double rX0 = rBx + rA0, rX1 = rBx + rA1;
+#else
                 const double rX0 = shl1(xa[0], Bx + tr[0]), rX1 = shl1(xa[1], Bx + tr[1]);
+#endif
                 const double rM0 = shl1(xa[2], Bm + S0), rM1 = shl1(xa[3], Bm + S1), rM2 = shl1(xa[4], Bm + S2);
                 const bool bvalid = xs >= bxmin;
                 while (xinB >= bxmin) {
@@ -1346,7 +1510,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     xinB--;
                 }
 #endif
-#ifdef SY_FUSED
+#if defined(SY_FUSED) && defined(SY_VANILLA)
+                if (t + 1 <= tPost0) fx_terms(t, active, xs, bvalid, fMc, fXc, rBx, rA0, rA1, nxmin, nxmax);
+#elif defined(SY_FUSED)
                 if (t + 1 <= tPost0)
                     fx_terms(t, active, xs, bvalid, fMc, fXc, fYc, hB, hP, rBx, rPx, Um, Uy, nxmin, nxmax);
 #endif
@@ -1385,7 +1551,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             const double nS0 = pmc + tr[2], nS1 = pmc + tr[3], nS2 = pmc + lYM;
             if (lane == 0) {
                 double *x = sh.xch[t & 1][wave];
+#ifdef SY_FUSED
+                x[5] = Bx; x[6] = tr[0]; x[7] = tr[1]; x[2] = Bm + nS0; x[3] = Bm + nS1; x[4] = Bm + nS2;
+#else
                 x[0] = Bx + tr[0]; x[1] = Bx + tr[1]; x[2] = Bm + nS0; x[3] = Bm + nS1; x[4] = Bm + nS2;
+#endif
             }
 #else
             Um = By + (pyc + T[T_GAP_OPEN_Y]);
@@ -1505,7 +1675,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             if (t - 2 >= tracedBackTo) band_get(bf, t - 2, pxmin, pxmax);
         };
         double q0F, q0Pm, q0Py, q1F, q1Pm, q1Py, q2F, q2Pm, q2Py, q3F, q3Pm, q3Py;
-#ifdef SY_FUSED
+#if defined(SY_FUSED) && defined(SY_VANILLA)
+        double q0Fx, q1Fx, q2Fx, q3Fx;
+#elif defined(SY_FUSED)
         double q0Fx, q0Fy, q1Fx, q1Fy, q2Fx, q2Fy, q3Fx, q3Fy;
 #endif
         {
@@ -1549,6 +1721,15 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
              * bxmax is that diagonal's, nxmin .. nxmax the lowest decoded one's) */
             if (xs > bxmax) xs -= SY_P;
             const bool vt = xs >= bxmin;
+#ifdef SY_VANILLA
+            double f, pm, py, fx;
+            fetch(tracedBackTo, vt, f, pm, py, fx);
+            lds_barrier();
+            const double *xa = sh.xch[(tracedBackTo + 1) & 1][g.waveAbove];
+            const double rBx = shl1(xa[5], Bx), rA0 = shl1(xa[6], tr[0]), rA1 = shl1(xa[7], tr[1]);
+            fx_terms(tracedBackTo, row_active(wave, bxmin, bxmax), xs, vt, vt ? f : CP_NEG_INF, vt ? fx : CP_NEG_INF,
+                     rBx, rA0, rA1, nxmin, nxmax);
+#else
             double f, pm, py, fx, fy;
             fetch(tracedBackTo, vt, f, pm, py, fx, fy);
             lds_barrier();
@@ -1556,6 +1737,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             const double rBx = shl1(xa[0], Bx), rPx = shl1(xa[1], pxReg);
             fx_terms(tracedBackTo, row_active(wave, bxmin, bxmax), xs, vt, vt ? f : CP_NEG_INF, vt ? fx : CP_NEG_INF,
                      vt ? fy : CP_NEG_INF, hB, hP, rBx, rPx, Um, Uy, nxmin, nxmax);
+#endif
             fx_flush();
         }
 #endif
@@ -1604,7 +1786,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             wtot[k >> 1].total = tot;
             if (!(fabs(tot - totEst) <= SY_CAND_SLACK)) sh.scan = 1; /* also catches NaN and infinities */
 #ifdef SY_FUSED
-            if (!(fabs(tot - totEst) <= SY_FX_EST_BOUND)) sh.fxRedo = 1;
+            if (!(fabs(tot - totEst) <= SY_FX_EST_BOUND)) SY_FX_REDO(sh) = 1;
 #endif
             const long long o = out.nTot + (k >> 1);
             if (o < out.totCap) {
@@ -1619,12 +1801,17 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
     /* the window's sums into the model's: scaled from the estimate, or taken once more against the exact totals where
      * the estimate is not finite or lies more than SY_FX_EST_BOUND from one of them (or the caller forces it) */
     if (nPost > 0) {
-        const bool redo = sh.fxRedo != 0;
+        const bool redo = SY_FX_REDO(sh) != 0;
         if (redo) {
             sweep(true);
             __syncthreads();
         }
+#ifdef SY_VANILLA
+        fx_finish(it, fxo, wtot, nTotWin, tPost0, tracedBackTo, totEst, redo, expect, track, sh.wbuf);
+        (void) kidx;
+#else
         fx_finish(it, fxo, wtot, nTotWin, tPost0, tracedBackTo, totEst, redo, expect, kidx);
+#endif
     }
 #endif
 
@@ -2300,11 +2487,17 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 
 /* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
-extern "C" const SweepBuild SY_SYM(cpecan_systolic_build);
+/* (the vanilla _vf builds, which are not among the Makefile's SY_BUILDS, have a record name of their own) */
+#if defined(SY_FUSED) && defined(SY_VANILLA)
+#define SY_BUILD_SYM SY_SYM(cpecan_systolicfx_build)
+#else
+#define SY_BUILD_SYM SY_SYM(cpecan_systolic_build)
+#endif
+extern "C" const SweepBuild SY_BUILD_SYM;
 /* (the _f builds serve a batch that asks for them only: cpecan_hip.hip puts one in the place of the build of as many
  * waves that the dispatch chose; their segment records lie behind the scratch.  The dispatch sends the other E-step
  * builds of the vanilla and the HDP machine no posterior batch, and their posterior builds no E-step) */
-const SweepBuild SY_SYM(cpecan_systolic_build) = {
+const SweepBuild SY_BUILD_SYM = {
     SY_R, false, SY_MACHINE_ID, &SY_MACHINE, SY_P - 2 * SY_PREFETCH, SY_R * SY_RING_VALUES * 64, SY_BRING_ROW_DOUBLES,
     sy_scratch_bytes, SY_ESTEP_BY(sy_fx_bytes, nullptr), sy_launch_forward, sy_launch_backward,
     SY_ESTEP_BY(sy_launch_backward, nullptr), SY_ESTEP_BY(nullptr, sy_launch_expect), nullptr };

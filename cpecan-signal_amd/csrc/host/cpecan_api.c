@@ -1071,13 +1071,17 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
                                               unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0, &batch));
         else if (van) {
             /* CPECAN_VANILLA_FUSED_ESTEP=1: the E-step summed inside the sweep back on the wave kernels (the flag means
-             * nothing to a batch it does not serve) */
+             * nothing to a batch it does not serve); CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP=1: the same on the workgroup
+             * kernels, for a batch that CPECAN_WIDE_BANDS_VANILLA_ESTEP=1 sends there (bands of 185..504 k-mers) */
             const char *fusedEstep = getenv("CPECAN_VANILLA_FUSED_ESTEP");
+            const char *fusedWide = getenv("CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP");
             CHECK(cpecan_hip_batch_create_vanilla(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
                                                   (unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0) |
                                                       (mode ? CPECAN_FLAG_EXPECTATIONS : 0) |
                                                       (mode && fusedEstep && atoi(fusedEstep) == 1
-                                                           ? CPECAN_FLAG_VANILLA_FUSED_ESTEP : 0), &batch));
+                                                           ? CPECAN_FLAG_VANILLA_FUSED_ESTEP : 0) |
+                                                      (mode && fusedWide && atoi(fusedWide) == 1
+                                                           ? CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP : 0), &batch));
         }
         else
             CHECK(cpecan_hip_batch_create(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,

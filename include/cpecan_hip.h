@@ -430,6 +430,36 @@ typedef struct {
                                           libcpecan_host.so sets it for its vanilla batches of expectations when
                                           CPECAN_VANILLA_FUSED_ESTEP=1 (the way in for vanillaAlign and
                                           cpecan_trainModels). */
+#define CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP 32768 /* cpecan_hip_batch_create_vanilla with
+                                          CPECAN_FLAG_EXPECTATIONS only: a batch that CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP
+                                          (or CPECAN_WIDE_BANDS_VANILLA_ESTEP=1) puts on the _ve workgroup builds -- a
+                                          widest band of 185..504 k-mers whose edges step by one k-mer per diagonal, no
+                                          CPECAN_FLAG_GENERAL_KERNEL, no k-mer that is none -- sums its two expectations
+                                          per cell inside the sweep back instead (cpecan_k_sy_backward_vf4 / _vf6 / _vf8,
+                                          the build of as many waves per workgroup), as CPECAN_FLAG_VANILLA_FUSED_ESTEP
+                                          does on the wave kernels: against the sweep's estimate of the window's total,
+                                          per segment of ten decoded diagonals, scaled by exp(estimate - total) after
+                                          the totals, in the same launch; no ring of backward cells, no expectation
+                                          kernel.  A window whose estimate is not finite or lies more than 30 nats from
+                                          one of its totals is swept back once more in that launch against the exact
+                                          totals (CPECAN_EXPECT_RESWEEP=1 / 2 forces that for every / every other
+                                          window: tests).  cpecan_hip_batch_expectation_pass reports 1,
+                                          cpecan_hip_plan_expectation_pass answers beforehand; the kernel, family, rows
+                                          and widest band cpecan_hip_plan_dispatch names do not change.  Results agree
+                                          with the ring path to rounding (the sums are added in another order).  These
+                                          builds have no other form of the E-step: CPECAN_EXPECT_FUSED=0 does not undo
+                                          the flag.  Every other batch ignores it: a posterior batch, another machine,
+                                          a band of at most 184 k-mers (the wave kernels, where
+                                          CPECAN_FLAG_VANILLA_FUSED_ESTEP rules) or past 504, the general kernel, a
+                                          batch without the wide-bands flag of the E-step.  A number of its own because
+                                          16384 is pinned as meaning nothing to a batch on the _ve builds.  Opt-in, and
+                                          as measured so far slower than the ring path (0.81 / 0.91 / 0.96 x at four /
+                                          six / eight waves: the fused sweep back takes 141..145 registers where the
+                                          ring build's takes 124..128).  No
+                                          environment variable of the C-ABI sets it; libcpecan_host.so sets it for its
+                                          vanilla batches of expectations when CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP=1
+                                          (the way in for vanillaAlign and cpecan_trainModels, beside
+                                          CPECAN_WIDE_BANDS_VANILLA_ESTEP=1). */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -452,7 +482,7 @@ int cpecan_hip_batch_create_dna(cpecan_ctx *ctx, const cpecan_item *items, int64
 /* k-mers against events with a vanilla model (getAlignedPairsUsingAnchors with a StateMachine3Vanilla,
  * sequence_getKmer2 / sequence_getEvent): same buffers as cpecan_hip_batch_create, model_id is a
  * cpecan_hip_modelsv_create id.  flags: UNBANDED (general kernel, posterior decode only), EXPECTATIONS, GENERAL_KERNEL,
- * WIDE_BANDS, WIDE_BANDS_VANILLA_ESTEP, VANILLA_FUSED_ESTEP.  There is no kernel argument: the batch picks its kernels itself (the wave builds
+ * WIDE_BANDS, WIDE_BANDS_VANILLA_ESTEP, VANILLA_FUSED_ESTEP, WIDE_BANDS_VANILLA_FUSED_ESTEP.  There is no kernel argument: the batch picks its kernels itself (the wave builds
  * up to 184 k-mers of band, the general kernel past that), and the two wide-bands flags alone select the workgroup builds
  * for bands of 185..504 k-mers: CPECAN_FLAG_WIDE_BANDS for the posterior decode, CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for
  * the E-step.
@@ -582,7 +612,8 @@ int cpecan_hip_batch_assembly_sweeps(cpecan_batch *batch, int32_t *sweeps);
  * CPECAN_FLAG_WORKGROUP_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WORKGROUP=1, on the workgroup kernels of one to four waves,
  * with CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP or CPECAN_EXPECT_FUSED_WIDE=1 on those of six and eight waves
  * (cpecan_hip_batch_kernel_family tells which), and the vanilla machine on the wave kernels (bands up to 184 k-mers)
- * with CPECAN_FLAG_VANILLA_FUSED_ESTEP: no ring of backward cells, no expectation kernel.  0 for the
+ * with CPECAN_FLAG_VANILLA_FUSED_ESTEP and on the workgroup kernels of four, six and eight waves (185..504) with
+ * CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP: no ring of backward cells, no expectation kernel.  0 for the
  * ring-of-backward-cells path and for posterior batches. */
 int cpecan_hip_batch_expectation_pass(cpecan_batch *batch, int32_t *fused);
 /* The same beforehand, without a batch and without a device, asked as cpecan_hip_plan_dispatch is: returns (and stores
