@@ -2052,22 +2052,34 @@ WV_BACKWARD_FX_KERNEL(cpecan_k_wv_resweep_fx_sw, true, WV_KIND_EXPECT_REDO)
  * sweep's single wave):
  *  T  the totals of the window's totalProbability refreshes (their per-cell terms were formed by the sweep's wave,
  *     phase T0): the reference's order-dependent logAdd fold is inherently serial, so each THREAD folds one
- *     diagonal's terms privately, in the reference's order (dpDiagonal_dotProduct :587-597);
+ *     diagonal's terms privately, in the reference's order (dpDiagonal_dotProduct :587-597), from an LDS tile the
+ *     workgroup loads together;
  *  D  diagonalCalculationPosteriorMatchProbs (:756-795) from the sweep's candidate list: hits are marked per
  *     diagonal, prefix-summed in emission order (diagonals descending, x-y ascending) and written.  A window
  *     whose candidates cannot be trusted (a total strays from the forward kernel's estimate, the list overflowed,
  *     threshold 0) is left to the re-sweep kernel.
  */
+#define WV_POST_C 4 /* terms of a row the LDS tile holds at a time (eight would take 16 KB: §4.0 of DESIGN.md) */
+/* term c of row r in the tile: rows of C doubles, the column XORed with bits of the row so that the 32 threads of a
+ * half wave, each reading column c of its own row, touch 32 different 8-byte banks of the 256-byte bank row */
+template <int C> __device__ __forceinline__ int post_tile_at(int r, int c) {
+    static_assert(C == 4 || C == 8, "the swizzle is written for rows of 4 or 8 doubles");
+    return r * C + (c ^ ((r / (32 / C)) & (C - 1)));
+}
 struct PostShared {
     double coef[64];
     double vbuf[256];
+    double tile[256 * WV_POST_C]; /* phase T: WV_POST_C terms of each of the round's 256 rows */
+    unsigned rowB[256];           /* ... a row's first slot, and its length << 16 (0: no such row) */
     int part[4];
     int scan, carry, fxRedo;
+    int maxLen; /* phase T: the longest row of the round */
 #ifdef WV_FUSED
     double bins[60]; /* the window's sums per skip bin (fx_finish_bins) */
 #endif
 };
-extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
+/* (64 registers: what fits beside a backward wave of the assembly sweeps, §4.0a) */
+extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void WV_SYM(cpecan_k_wv_post)(
     const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTabAll,
     const double *__restrict__ models, const double *Fring, long long ringDoubles, int ringD, WvState *states,
     long long *pairs, double *pairLogp, long long *totXay, double *totVal, char *scratch, long long scratchBytes,
@@ -2080,7 +2092,7 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     WvWindow *wp = &state->win[window & 3];
     if (uni(ld_agent(&wp->valid)) != 3) return;
     const DevItem it = uniform_item(items[idx]);
-    const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6);
+    const int tid = threadIdx.x, wv = uni(tid >> 6);
     if (tid < 64) init_coef(sh.coef);
     const int dTop = uni(ld_agent(&wp->top)), tracedBackFrom = uni(ld_agent(&wp->from)), tracedBackTo = uni(ld_agent(&wp->to));
     const int nTotWin = uni(ld_agent(&wp->nRefresh)), nCand = uni(ld_agent(&wp->nCand));
@@ -2090,6 +2102,7 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
     const int candCap = WV_CAND_PER_DIAG * WV_L * ringD;
     if (tid == 0) sh.scan = (P.scanDecode != 0 || !(P.logThrSlack > CP_NEG_INF) || nCand > candCap) ? 1 : 0;
     /* (tests: 1 every window down the re-sweep, 2 every other one -- the items and windows alternate) */
+    if (tid == 0) sh.maxLen = 0;
     if (tid == 0) sh.fxRedo = P.expectResweep == 1 || (P.expectResweep == 2 && ((idx ^ window) & 1)) ? 1 : 0;
 #ifdef WV_FUSED
     if (tid < 60) sh.bins[tid] = 0.0;
@@ -2112,46 +2125,85 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
 
     /* ------------------------------ phase T: the totals ------------------------------ */
     /* (plain loads throughout: what this kernel reads was written by an earlier kernel, or by this workgroup
-     * before a __syncthreads(); atomic loads would each be waited for on their own) */
+     * before a __syncthreads(); atomic loads would each be waited for on their own)
+     * A round of 256 rows: thread r folds row k0 + r (row k lies at vw + k * WV_P) in ascending x, as before, but takes
+     * the terms from an LDS tile the whole workgroup fills, C = WV_POST_C terms of every row at a time: thread tid loads
+     * term tid % C of rows q * (256 / C) + tid / C, so a load instruction covers 64 / C rows of C * 8 contiguous bytes
+     * (but for a row's wrap) where a thread reading its own row touched 64 lines.  Two chunks are in flight in
+     * registers (A, B: eight loads per thread, as before); a chunk is folded by the rows it reaches into, with -inf
+     * past the row's end up to a multiple of eight terms -- the logAdds, their operands and their order are the ones
+     * of a thread folding its row eight terms at a time. */
 #pragma unroll 1
     for (int k0 = 0; k0 < 2 * nTotWin; k0 += 256) {
-        const int k = k0 + tid;
+        constexpr int C = WV_POST_C, RQ = 256 / C;
+        static_assert(2 * C == 8, "two chunks are the eight terms a row's fold is padded to");
+        /* (the thread's number is taken anew in every round of rows, so that what derives from it lives in registers
+         * through the round alone: kept through the whole kernel it does not fit in 64) */
+        int tl = threadIdx.x;
+        asm volatile("" : "+v"(tl));
+        const int k = k0 + tl;
         double acc = CP_NEG_INF;
-        WinTotal w;
-        w.second = 0; w.t = 0; w.xmin = w.xmax = w.nxmin = w.nxmax = 0;
+        int len = 0, loSlot = 0;
         const int f = k & 1;
         if (k < 2 * nTotWin) {
-            w = wtot[k >> 1];
-            if (f == 0 || w.second) {
+            const WinTotal w = wtot[k >> 1];
+            if (f == 0 || w.second) { /* the row exists */
                 const int lo = f ? w.nxmin : w.xmin, hi = f ? w.nxmax : w.xmax;
-                const double *src = vw + ((long long) (k >> 1) * 2 + f) * WV_P;
-                double v[8], nv[8]; /* the next eight terms are in flight while these eight are folded */
-#pragma unroll
-                for (int q = 0; q < 8; q++) v[q] = lo + q <= hi ? src[(lo + q) % WV_P] : CP_NEG_INF;
-#pragma unroll 1
-                for (int x0 = lo; x0 <= hi; x0 += 8) {
-#pragma unroll
-                    for (int q = 0; q < 8; q++)
-                        nv[q] = x0 + 8 + q <= hi ? src[(x0 + 8 + q) % WV_P] : CP_NEG_INF;
-#pragma unroll
-                    for (int q = 0; q < 8; q++) acc = ladd(acc, v[q], cf);
-#pragma unroll
-                    for (int q = 0; q < 8; q++) v[q] = nv[q];
-                }
+                len = hi - lo + 1;
+                len = len < 0 ? 0 : len > WV_P ? WV_P : len; /* (a row has WV_P slots) */
+                loSlot = lo % WV_P;
             }
         }
-        sh.vbuf[tid] = acc;
+        sh.rowB[tl] = (unsigned) loSlot | (unsigned) len << 16;
+        if (len > 0) atomicMax(&sh.maxLen, len);
         __syncthreads();
-        const double partner = sh.vbuf[(tid + 1) & 255];
+        const int maxLen = uni(sh.maxLen); /* the longest row of the round */
+        const int j = tl % C, r0 = tl / C;
+        const double *src = vw + (long long) k0 * WV_P; /* (uniform: the rows of the round, 256 * WV_P doubles at most) */
+        double bufA[C], bufB[C];
+/* (every thread loads, a term past its row's end from the round's first double, so that the number of loads in flight
+ * is the same in every thread and the older chunk alone is waited for; such a term enters the tile as -inf) */
+#define WV_POST_LOAD(dst, x)                                                                     \
+        _Pragma("unroll") for (int q = 0; q < C; q++) {                                          \
+            const unsigned b = sh.rowB[q * RQ + r0]; /* (from LDS every time: four registers fewer) */ \
+            const int e = (x) + j, s = (int) (b & 0xffffu) + e;                                  \
+            const unsigned at = (unsigned) (q * RQ + r0) * WV_P + (unsigned) (s >= WV_P ? s - WV_P : s); \
+            dst[q] = src[e < (int) (b >> 16) ? at : 0u];                                         \
+        }
+/* a chunk into the tile, its registers to the chunk after the next, and the fold (x0: the eight terms the chunk is of) */
+#define WV_POST_STEP(buf, x, xNext)                                                              \
+        _Pragma("unroll") for (int q = 0; q < C; q++)                                            \
+            sh.tile[post_tile_at<C>(q * RQ + r0, j)] = (x) + j < (int) (sh.rowB[q * RQ + r0] >> 16) ? buf[q] : CP_NEG_INF; \
+        WV_POST_LOAD(buf, xNext)                                                                 \
+        __syncthreads();                                                                         \
+        if (x0 < len) {                                                                          \
+            _Pragma("unroll") for (int c = 0; c < C; c++) acc = ladd(acc, sh.tile[post_tile_at<C>(tl, c)], cf); \
+        }                                                                                        \
+        __syncthreads();
+        WV_POST_LOAD(bufA, 0)
+        __builtin_amdgcn_sched_barrier(0); /* (A's loads first: the loop waits for the older four of eight) */
+        WV_POST_LOAD(bufB, C)
+#pragma unroll 1
+        for (int x0 = 0; x0 < maxLen; x0 += 2 * C) {
+            WV_POST_STEP(bufA, x0, x0 + 2 * C)
+            WV_POST_STEP(bufB, x0 + C, x0 + 3 * C)
+        }
+#undef WV_POST_STEP
+#undef WV_POST_LOAD
+        sh.vbuf[tl] = acc;
+        if (tl == 0) sh.maxLen = 0; /* (every thread has read it, and the next round's rows come after a barrier) */
+        __syncthreads();
+        const double partner = sh.vbuf[(tl + 1) & 255];
         if (k < 2 * nTotWin && f == 0) {
+            const int second = wtot[k >> 1].second, wt = wtot[k >> 1].t;
             double tot = acc;
-            if (w.second) tot = ladd(acc, partner, cf);
+            if (second) tot = ladd(acc, partner, cf);
             wtot[k >> 1].total = tot;
             if (!(fabs(tot - totEst) <= WV_CAND_SLACK)) sh.scan = 1; /* also catches NaN and infinities */
             if (!(fabs(tot - totEst) <= WV_FX_EST_BOUND)) sh.fxRedo = 1;
             const long long o = nTot0 + (k >> 1);
             if (o < it.totCap) {
-                totXay[it.totBase + o] = w.t;
+                totXay[it.totBase + o] = wt;
                 totVal[it.totBase + o] = tot;
             }
         }
@@ -2197,14 +2249,26 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
         return;
     }
 
+#ifdef CPECAN_TIMING_BUILD
+#ifdef CPECAN_TIMING_POST_TOTALS_ONLY /* timing study (what phase D costs: a kernel trace with and without): no pairs */
+    if (tid == 0) {
+        state->nTot = nTot0 + nTotWin;
+        wp->valid = 0;
+    }
+    return;
+#endif
+#endif
     /* ------------------------------ phase D: the aligned pairs ------------------------------ */
+    int td = threadIdx.x; /* (taken anew, as in phase T) */
+    asm volatile("" : "+v"(td));
+    const int lane = td & 63;
     long long *outPairs = pairs + it.pairBase * 3;
     double *outLogp = pairLogp + it.pairBase;
-    for (int i = tid; i < nPost * 4; i += 256) msk[i] = 0ull;
+    for (int i = td; i < nPost * 4; i += 256) msk[i] = 0ull;
     __syncthreads();
     for (int pass = 0; pass < 2; pass++) {
 #pragma unroll 1
-        for (int i = tid; i < nCand; i += 256) {
+        for (int i = td; i < nCand; i += 256) {
             const int2 kx = candKx[i];
             const int k = kx.x, x = kx.y, t = tPost0 - k;
             const double ee = candFb[i] - wtot[k / 10].total;
@@ -2233,7 +2297,7 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
             int carry = 0;
 #pragma unroll 1
             for (int base = 0; base < nPost; base += 8 * 256) {
-                const int b0 = base + tid * 8;
+                const int b0 = base + td * 8;
                 int h[8], sum = 0;
 #pragma unroll
                 for (int q = 0; q < 8; q++) {
@@ -2267,11 +2331,11 @@ extern "C" __global__ __launch_bounds__(256) void WV_SYM(cpecan_k_wv_post)(
                         o += h[q];
                     }
             }
-            if (tid == 0) sh.carry = carry;
+            if (td == 0) sh.carry = carry;
                     __syncthreads();
         }
     }
-    if (tid == 0) {
+    if (td == 0) {
         state->nPairs = nPairs0 + sh.carry;
         state->nTot = nTot0 + nTotWin;
         wp->valid = 0;
