@@ -251,7 +251,21 @@ def edge_mass(batch, i, bp, ragged=(0, 0), transitions=None):
     refreshes it every ten decoded diagonals), gapx[d] the same of gap X, cell[d] the cells' posterior summed over the
     states, xmin[d] the diagonal's least x, seg[d] the diagonal at which the total that covers d was refreshed"""
     from harness import run_oracle_item
-    dump = run_oracle_item(batch, i, bp, ragged, transitions=transitions, dump=True)
+    return _state_mass(run_oracle_item(batch, i, bp, ragged, transitions=transitions, dump=True))
+
+
+def vanilla_edge_mass(batch, i, model, bp, ragged=(0, 0)):
+    """edge_mass of item i under the vanilla machine: the oracle's cell dump with `model` (an o.VanillaModel, whose
+    states are match, gap X, gap Y as the strawMan machine's)"""
+    from harness import orc_params
+    it = batch["items"][i]
+    x = batch["x_chars"][it["x_offset"]: it["x_offset"] + it["lX"] + 5]
+    ev = batch["events"][it["y_offset"]: it["y_offset"] + it["lY"]]
+    an = batch["anchors"][it["anchor_offset"]: it["anchor_offset"] + it["n_anchors"]]
+    return _state_mass(o.banded_dump(model, x, it["lX"], ev, an, orc_params(bp, split=1 << 60), ragged[0], ragged[1]))
+
+
+def _state_mass(dump):
     txay = np.asarray(dump["totals_xay"])
     tval = np.asarray(dump["totals"])
     order = np.argsort(txay)
@@ -286,16 +300,39 @@ def edge_fraction(m, place, thr, reach=1, skip_ends=0, kind="match"):
     return hit / max(n, 1)
 
 
+SLOT_PERIODS = (128, 192, 256, 384, 512)  # WV_P of the two wave builds, SY_P of the three workgroup builds
+
+
+def slot_period(build):
+    """the slot period of a build, given as the wave family's cells per lane (2, 3: 64 slots each) or as the period
+    itself (one of SLOT_PERIODS)"""
+    P = 64 * build if build < 64 else build
+    assert P in SLOT_PERIODS, build
+    return P
+
+
+def column_skip_bin(seq, match, x):
+    """the skip bin of column x (the cells that have consumed x k-mers) on a read's scaled match table, as skip_bin in
+    oracle/cpecan_oracle.c takes it through get_symbols: min(29, int(|level(k) - level(k_prev)| / 0.5)) of the k-mers
+    at max(x - 2, 0) and one past it"""
+    kidx = synth.kmer_indices(seq)
+    p = max(x - 2, 0)
+    level = np.asarray(match)[1:].reshape(synth.NUM_KMERS, 5)[:, 0]
+    return min(29, int(abs(level[kidx[p + 1]] - level[kidx[p]]) / 0.5))
+
+
 def a_record_slots(m, cells_per_lane, floor=1e-3):
     """the fused E-step's A-record condition on an oracle dump (edge_mass): refresh segments (the decoded diagonals
-    that share one total) in which one slot of the wave kernel (column x mod 64 * cells_per_lane) holds two columns
-    of the band, the higher one (the sweep back meets it first, and moves the slot on from it) with gap-X posterior
-    >= floor summed over the segment.  The issue that asked for this condition wants gap-X mass on both columns; the
+    that share one total) in which one slot of the kernel (column x mod P, P = slot_period(cells_per_lane): the wave
+    builds' WV_P, or given directly the workgroup builds' SY_P -- there a slot holds the forward cell of column
+    x mod SY_P and points at column x + 1 (SY_SLOT, gCol), and two columns P apart share a slot under any such fixed
+    shift) holds two columns of the band, the higher one (the sweep back meets it first, and moves the slot on from
+    it) with gap-X posterior >= floor summed over the segment.  The issue that asked for this condition wants gap-X mass on both columns; the
     kernel's store (cpecan_kernel_wave.hip, `x != cA[j]`) fires whenever the slot moves on from a column whose sum is
     non-zero, whatever the new column holds, and a lost A record loses the higher column's sum only, so the lower
     column has only to be in the band here.  Returns a list of (segment's top diagonal, slot, higher column, its gap-X
     mass, lower column)."""
-    P = 64 * cells_per_lane
+    P = slot_period(cells_per_lane)
     segs = {}
     for d in range(1, len(m["gapx"])):
         g = m["gapx"][d]
@@ -475,8 +512,24 @@ WIDE_FAMILIES = {"w%d" % _w: _f(place="upper", lX=300, lY=450, width=_w, md=150,
                  for _w in (64, 65, 256, 257)}
 
 
+# the vanilla machine's workgroup builds (SY_P = 256, 384, 512 slots for bands of up to 248, 376, 504 k-mers), kept
+# apart as WIDE_FAMILIES is.  varec...: the A-record condition at the build's slot period (`arec`): a band within a few
+# k-mers of the period that crosses 30 skipped k-mers in the middle of the read, 700 k-mers long so that the band has
+# that many columns to cross.  vlower...: the path on the band's lower edge at the build's widest band
+# (test_vanilla_workgroup_gpu.exact_width_batch is the same read on the upper edge).
+VANILLA_FAMILIES = {}
+for _w in (248, 376, 504):
+    VANILLA_FAMILIES["varec%d" % _w] = _f(place="upper", lX=700, lY=1050, width=_w, skip=(350, 30, 1), md=150, tb=40,
+                                          ragged=(1, 1), arec=_w + 8)
+    VANILLA_FAMILIES["vlower%d" % _w] = _f(place="lower", lX=700, lY=1050, width=_w, md=150, tb=40,
+                                           ragged=(_w % 2, 1))
+
+
 def signal_family(name):
-    return FAMILIES[name] if name in FAMILIES else WIDE_FAMILIES[name]
+    for families in (FAMILIES, WIDE_FAMILIES, VANILLA_FAMILIES):
+        if name in families:
+            return families[name]
+    raise KeyError(name)
 
 
 def signal_batch(name, n=2, seed=None, centred=False):

@@ -27,13 +27,14 @@ import pytest
 import pyoracle as o
 from cpecan_load import em
 from harness import band_params, batch_results, cp
-from test_fuzz_expectations_gpu import assert_expectations_match
+from test_fuzz_expectations_gpu import assert_expectations_match, env
 from test_fuzz_expectations_machines_gpu import same_doubles, signal_width, vanilla_oracle
+from test_vanilla_fused_cases_cpu import family_case
 from test_vanilla_fused_expectations_gpu import FUDGE
 from test_vanilla_scaled_models_gpu import as_tuple, host_scaled, two_strand_batch
 from test_vanilla_workgroup_estep_cases_cpu import EDGE_WIDTHS, edge_case, oracle_sums, shape_case
-from test_vanilla_workgroup_estep_gpu import (NEW_BINS, check_oracle, ebatch, run_estep, short_items_beside_a_wide_read,
-                                              upload)
+from test_vanilla_workgroup_estep_gpu import (NEW_BINS, WIDE_FAMILIES, check_oracle, ebatch, run_estep,
+                                              short_items_beside_a_wide_read, upload)
 from test_vanilla_workgroup_gpu import (SHAPES, W8, WV, build_of, check_workgroup, shape_batch, shape_id, shape_of,
                                         vanilla_models)
 
@@ -118,6 +119,49 @@ def test_windows_down_the_second_sweep(ctx, rows, resweep, monkeypatch):
     res, info, got = run_estep(ctx, batch, models, bp, ragged, FUSED)
     check_fused(info, rows)
     check_oracle(case, res, got, "rows %d resweep %d" % (rows, resweep))
+
+
+def run_wide_family(ctx, name, rows, resweep=None, centred=False):
+    """an edge_reads.VANILLA_FAMILIES batch on the fused build of `rows` waves, against the oracle at check_oracle's
+    bars (sums, totals, cell counts); CPECAN_EXPECT_RESWEEP as test_windows_down_the_second_sweep sets it"""
+    case = family_case(name, centred)
+    _, batch, models, bp, ragged = case
+    with env(CPECAN_EXPECT_RESWEEP=resweep):
+        res, info, got = run_estep(ctx, batch, models, bp, ragged, FUSED)
+    check_fused(info, rows)
+    assert info["max_band_width"] == signal_width(batch, batch["e"])
+    for k, (g, r) in enumerate(zip(got, oracle_sums(*case))):
+        print("%s resweep %s%s model %d: largest relative error of the bins %.3g" % (
+            name, resweep, " centred" * centred, k,
+            (np.abs(g[:60] - r[:60])[r[:60] != 0] / np.abs(r[:60][r[:60] != 0])).max(initial=0.0)))
+    check_oracle(case, res, got, (name, resweep, centred))
+    return case, res, got
+
+
+@pytest.mark.parametrize("resweep", [None, "1", "2"], ids=["fused", "every-window", "every-other-window"])
+@pytest.mark.parametrize("name,rows", WIDE_FAMILIES, ids=[n for n, _ in WIDE_FAMILIES])
+def test_a_records_and_lower_edges(ctx, name, rows, resweep):
+    """varec...: a slot hands the sums of the column it leaves to the segment's A record (`x + 1 != gCol`): the store,
+    the post kernel's read of it and, on the second sweep, the same against the exact totals -- against the oracle and
+    against the _ve build's path through the ring.  vlower...: the path on the band's lower edge"""
+    case, res_f, fused = run_wide_family(ctx, name, rows, resweep)
+    _, batch, models, bp, ragged = case
+    res_r, info, ring = run_estep(ctx, batch, models, bp, ragged, ESTEP)
+    check_workgroup(info, rows)
+    for k, (f, r) in enumerate(zip(fused, ring)):
+        assert np.allclose(f[:60], r[:60], rtol=1e-11, atol=1e-300), (name, k)
+        assert np.isclose(f[60], r[60], rtol=1e-12, atol=0), (name, k)
+    for a, b in zip(res_f, res_r):
+        assert same_doubles(a["totals"], b["totals"]) and a["cells"] == b["cells"]
+
+
+@pytest.mark.parametrize("width", [248, 376, 504])
+def test_no_stale_a_records(ctx, width):
+    """the A-record batch, then the batch with the same band and its mass down the middle (no A record), then the first
+    again, on one context: a record of the first that the second's sweep did not reset would be added to the second's
+    sums"""
+    for centred in (False, True, False):
+        run_wide_family(ctx, "varec%d" % width, build_of(width), centred=centred)
 
 
 @pytest.mark.parametrize("rows", [4, 6, 8])

@@ -21,6 +21,7 @@ from harness import batch_results, cp, make_items
 from test_fuzz_expectations_gpu import assert_expectations_match
 from test_fuzz_expectations_machines_gpu import (assert_same_totals, same_doubles, signal_width, vanilla_oracle,
                                                  vanilla_short_items)
+from test_vanilla_fused_cases_cpu import family_case
 from test_vanilla_gpu import skip_bins
 from test_vanilla_workgroup_estep_cases_cpu import (EDGE_WIDTHS, edge_case, oracle_posteriors, oracle_sums,
                                                     shape_case)
@@ -107,6 +108,21 @@ def test_bands_at_the_edges_of_the_builds(ctx, width):
     else:
         check_workgroup(info, build_of(width))
     check_oracle(case, res, got, width)
+
+
+# edge_reads.VANILLA_FAMILIES: a band that crosses 30 skipped k-mers within a few k-mers of the build's slot period (on
+# the fused builds the A-record cases; here the same reads through the ring), and the path on the band's lower edge
+WIDE_FAMILIES = [(name % w, build_of(w)) for w in (248, 376, 504) for name in ("varec%d", "vlower%d")]
+
+
+@pytest.mark.parametrize("name,rows", WIDE_FAMILIES, ids=[n for n, _ in WIDE_FAMILIES])
+def test_fast_bands_and_lower_edges(ctx, name, rows):
+    case = family_case(name)
+    _, batch, models, bp, ragged = case
+    res, info, got = run_estep(ctx, batch, models, bp, ragged, ESTEP)
+    check_workgroup(info, rows)
+    assert info["max_band_width"] == signal_width(batch, batch["e"])
+    check_oracle(case, res, got, name)
 
 
 @pytest.mark.parametrize("rows", [4, 6, 8])
