@@ -524,31 +524,14 @@ class Batch:
             _check(lib().cpecan_hip_batch_create_dna(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
                                                      _ptr(yb), yb.size, _ptr(an), an.shape[0],
                                                      C.byref(params), flags, C.byref(h)))
-        elif hdp:
-            ev = np.ascontiguousarray(events, dtype=np.float64).reshape(-1)
-            _check(lib().cpecan_hip_batch_create_hdp(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
-                                                     _ptr(ev), ev.size // 3, _ptr(an), an.shape[0],
-                                                     C.byref(params), flags, C.byref(h)))
-        elif echelon:
-            ev = np.ascontiguousarray(events, dtype=np.float64).reshape(-1)
-            _check(lib().cpecan_hip_batch_create_echelon(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
-                                                         _ptr(ev), ev.size // 3, _ptr(an), an.shape[0],
-                                                         C.byref(params), flags, C.byref(h)))
-        elif sm4:
-            ev = np.ascontiguousarray(events, dtype=np.float64).reshape(-1)
-            _check(lib().cpecan_hip_batch_create_sm4(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
-                                                     _ptr(ev), ev.size // 3, _ptr(an), an.shape[0],
-                                                     C.byref(params), flags, C.byref(h)))
-        elif vanilla:
-            ev = np.ascontiguousarray(events, dtype=np.float64).reshape(-1)
-            _check(lib().cpecan_hip_batch_create_vanilla(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
-                                                         _ptr(ev), ev.size // 3, _ptr(an), an.shape[0],
-                                                         C.byref(params), flags, C.byref(h)))
         else:
+            # the five event machines: the same arguments, but for the strawMan call's own mode and kernel
+            name = "_hdp" if hdp else "_echelon" if echelon else "_sm4" if sm4 else "_vanilla" if vanilla else ""
+            extra = () if name else (mode, kernel)
             ev = np.ascontiguousarray(events, dtype=np.float64).reshape(-1)
-            _check(lib().cpecan_hip_batch_create(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size,
-                                                 _ptr(ev), ev.size // 3, _ptr(an), an.shape[0],
-                                                 C.byref(params), mode, kernel, flags, C.byref(h)))
+            create = getattr(lib(), "cpecan_hip_batch_create" + name)
+            _check(create(ctx.h, _ptr(items), items.shape[0], _ptr(xb), xb.size, _ptr(ev), ev.size // 3,
+                          _ptr(an), an.shape[0], C.byref(params), *extra, flags, C.byref(h)))
         self.h = h
         ctx._batches.add(self)
         self.n = items.shape[0]

@@ -270,6 +270,20 @@ static int read_doubles(FILE *f, double *dst, int64_t n) {
     return 1;
 }
 
+/* emissions_signal_loadPoreModel (impl/stateMachine.c:242-320), 3 lines: match table, 30 skip bins, Y-gap table.  The
+ * skip bins are the vanilla and echelon models' only, where they serve as beta and alpha */
+static void load_pore_model(StateMachine *sM, const char *modelFile, bool skipBins) {
+    const int64_t tableLen = 1 + NUM_OF_KMERS * MODEL_PARAMS;
+    double unused[30], *skip = skipBins ? sM->EMISSION_GAP_X_PROBS : unused;
+    FILE *f = fopen(modelFile, "r");
+    if (!f) die("cpecan: cannot open pore model %s", modelFile);
+    if (!read_doubles(f, sM->EMISSION_MATCH_PROBS, tableLen) || !read_doubles(f, skip, 30) ||
+        !read_doubles(f, sM->EMISSION_GAP_Y_PROBS, tableLen))
+        die("This stateMachine is not correct for signal model (%s)", modelFile);
+    fclose(f);
+    for (int i = 0; skipBins && i < 30; i++) skip[i + 30] = skip[i];
+}
+
 StateMachine *getStrawManStateMachine3(const char *modelFile) {
     StateMachine3 *s = calloc(1, sizeof(StateMachine3));
     s->model.type = threeState;
@@ -287,16 +301,7 @@ StateMachine *getStrawManStateMachine3(const char *modelFile) {
     cpecan_sm3_set_functions(s);
     s->model.cellCalculateUpdateExpectations = cell_signal_updateTransAndKmerSkipExpectations;
     for (int64_t i = 0; i < NUM_OF_KMERS; i++) s->model.EMISSION_GAP_X_PROBS[i] = -2.3025850929940455;
-    if (modelFile) {
-        /* 3 lines: match table, 30 skip bins (used by the vanilla/echelon models only), Y-gap table */
-        FILE *f = fopen(modelFile, "r");
-        double skip[30];
-        if (!f) die("cpecan: cannot open pore model %s", modelFile);
-        if (!read_doubles(f, s->model.EMISSION_MATCH_PROBS, tableLen) || !read_doubles(f, skip, 30) ||
-            !read_doubles(f, s->model.EMISSION_GAP_Y_PROBS, tableLen))
-            die("This stateMachine is not correct for signal model (%s)", modelFile);
-        fclose(f);
-    }
+    if (modelFile) load_pore_model(&s->model, modelFile, false);
     return (StateMachine *) s;
 }
 
@@ -322,16 +327,7 @@ StateMachine *getStateMachine4(const char *modelFile) { /* impl/stateMachine.c:1
                                                emissions_kmer_getGapProb, emissions_signal_strawManGetKmerEventMatchProb,
                                                emissions_signal_strawManGetKmerEventMatchProb,
                                                cell_signal_updateTransAndKmerSkipExpectations);
-    if (modelFile) { /* emissions_signal_loadPoreModel :242-320: match table, 30 skip bins (not this machine's), Y-gap table */
-        const int64_t tableLen = 1 + NUM_OF_KMERS * MODEL_PARAMS;
-        FILE *f = fopen(modelFile, "r");
-        double skip[30];
-        if (!f) die("cpecan: cannot open pore model %s", modelFile);
-        if (!read_doubles(f, sM->EMISSION_MATCH_PROBS, tableLen) || !read_doubles(f, skip, 30) ||
-            !read_doubles(f, sM->EMISSION_GAP_Y_PROBS, tableLen))
-            die("This stateMachine is not correct for signal model (%s)", modelFile);
-        fclose(f);
-    }
+    if (modelFile) load_pore_model(sM, modelFile, false);
     return sM;
 }
 
@@ -571,16 +567,7 @@ StateMachine *getSignalStateMachine3Vanilla(const char *modelFile) {
     s->model.EMISSION_MATCH_PROBS = calloc((size_t) tableLen, sizeof(double));
     s->model.EMISSION_GAP_Y_PROBS = calloc((size_t) tableLen, sizeof(double));
     s->model.EMISSION_GAP_X_PROBS = calloc(60, sizeof(double)); /* skip bins: beta[30] | alpha[30] */
-    if (modelFile) {
-        FILE *f = fopen(modelFile, "r");
-        if (!f) die("cpecan: cannot open pore model %s", modelFile);
-        if (!read_doubles(f, s->model.EMISSION_MATCH_PROBS, tableLen) ||
-            !read_doubles(f, s->model.EMISSION_GAP_X_PROBS, 30) ||
-            !read_doubles(f, s->model.EMISSION_GAP_Y_PROBS, tableLen))
-            die("This stateMachine is not correct for signal model (%s)", modelFile);
-        fclose(f);
-        for (int i = 0; i < 30; i++) s->model.EMISSION_GAP_X_PROBS[i + 30] = s->model.EMISSION_GAP_X_PROBS[i];
-    }
+    if (modelFile) load_pore_model(&s->model, modelFile, true);
     return (StateMachine *) s;
 }
 StateMachine *getStateMachineEchelon(const char *modelFile) { /* impl/stateMachine.c:1773-1784 */
@@ -589,16 +576,7 @@ StateMachine *getStateMachineEchelon(const char *modelFile) { /* impl/stateMachi
                                                      emissions_signal_getBetaOrAlphaSkipProb,
                                                      emissions_signal_multipleKmerMatchProb,
                                                      emissions_signal_getEventMatchProbWithTwoDists, NULL);
-    if (modelFile) { /* emissions_signal_loadPoreModel :242-320: the skip bins serve as beta and alpha, as for vanilla */
-        const int64_t tableLen = 1 + NUM_OF_KMERS * MODEL_PARAMS;
-        FILE *f = fopen(modelFile, "r");
-        if (!f) die("cpecan: cannot open pore model %s", modelFile);
-        if (!read_doubles(f, sM->EMISSION_MATCH_PROBS, tableLen) || !read_doubles(f, sM->EMISSION_GAP_X_PROBS, 30) ||
-            !read_doubles(f, sM->EMISSION_GAP_Y_PROBS, tableLen))
-            die("This stateMachine is not correct for signal model (%s)", modelFile);
-        fclose(f);
-        for (int i = 0; i < 30; i++) sM->EMISSION_GAP_X_PROBS[i + 30] = sM->EMISSION_GAP_X_PROBS[i];
-    }
+    if (modelFile) load_pore_model(sM, modelFile, true);
     return sM;
 }
 void stateMachine3Vanilla_setStrandTransitionsToDefaults(StateMachine *sM, Strand strand) {
@@ -656,17 +634,25 @@ int64_t diagonal_getXCoordinate(int64_t xay, int64_t xmy) { return (xay + xmy) /
 int64_t diagonal_getYCoordinate(int64_t xay, int64_t xmy) { return (xay - xmy) / 2; }
 int64_t diagonal_equals(Diagonal a, Diagonal b) { return a.xay == b.xay && a.xmyL == b.xmyL && a.xmyR == b.xmyR; }
 
+/* the (x, y) pairs of an anchor list (NULL: none) as the flat array the C-ABI takes; *n receives how many */
+static int64_t *flat_anchors(stList *anchorPairs, int64_t *n) {
+    *n = anchorPairs ? stList_length(anchorPairs) : 0;
+    int64_t *a = malloc(sizeof(int64_t) * 2 * (size_t) (*n + 1));
+    for (int64_t k = 0; k < *n; k++) {
+        a[2 * k] = stIntTuple_get(stList_get(anchorPairs, k), 0);
+        a[2 * k + 1] = stIntTuple_get(stList_get(anchorPairs, k), 1);
+    }
+    return a;
+}
+
 struct _band {
     Diagonal *diagonals;
     int64_t lXalY;
 };
 Band *band_construct(stList *anchorPairs, int64_t lX, int64_t lY, int64_t expansion) {
-    const int64_t na = anchorPairs ? stList_length(anchorPairs) : 0, n = lX + lY + 1;
-    int64_t *a = malloc(sizeof(int64_t) * 2 * (size_t) (na + 1));
-    for (int64_t k = 0; k < na; k++) {
-        a[2 * k] = stIntTuple_get(stList_get(anchorPairs, k), 0);
-        a[2 * k + 1] = stIntTuple_get(stList_get(anchorPairs, k), 1);
-    }
+    int64_t na;
+    const int64_t n = lX + lY + 1;
+    int64_t *a = flat_anchors(anchorPairs, &na);
     int32_t *L = malloc(sizeof(int32_t) * (size_t) n), *R = malloc(sizeof(int32_t) * (size_t) n);
     CHECK(cpecan_band_construct(a, na, lX, lY, expansion, L, R));
     Band *b = malloc(sizeof *b);
@@ -756,12 +742,8 @@ stList *filterToRemoveOverlap(stList *pairs) {
 
 stList *getSplitPoints(stList *anchorPairs, int64_t lX, int64_t lY, int64_t maxMatrixSize,
                        bool raggedL, bool raggedR) {
-    int64_t n = stList_length(anchorPairs);
-    int64_t *a = malloc(sizeof(int64_t) * 2 * (size_t) (n + 1));
-    for (int64_t i = 0; i < n; i++) {
-        a[2 * i] = stIntTuple_get(stList_get(anchorPairs, i), 0);
-        a[2 * i + 1] = stIntTuple_get(stList_get(anchorPairs, i), 1);
-    }
+    int64_t n;
+    int64_t *a = flat_anchors(anchorPairs, &n);
     int64_t *out = malloc(sizeof(int64_t) * 4 * (size_t) (n + 2));
     int64_t m = cpecan_split_points(a, n, lX, lY, maxMatrixSize, raggedL, raggedR, out, n + 2);
     stList *l = stList_construct3(0, (void (*)(void *)) stIntTuple_destruct);
@@ -795,421 +777,473 @@ static cpecan_ctx *context(void) {
     return ctx;
 }
 
-/* returns 1 for the DNA-against-DNA combination (5-state machine, sequence_getBase on both sides),
- * 2 for k-mers against events under the vanilla machine (sequence_getKmer2), 3 under the HDP machine
- * (sequence_getKmer3), 4 under the 4-state signal machine and 0 under the 3-state strawMan machine (both
- * sequence_getKmer), 5 under the echelon machine (sequence_getKmer2); anything else is not on the GPU path */
-static int check_known_combination(StateMachine *sM, Sequence *sX, Sequence *sY) {
-    if (!cpecan_sm_functions_known(sM))
-        die("cpecan: this StateMachine carries a cellCalculate or emission function of the caller's own; the GPU path "
-            "implements the reference's models only (symbol, strawMan, vanilla two-distribution and HDP emissions) "
-            "and there is no CPU path to fall back to");
-    if ((sM->type == fiveState || sM->type == fiveStateAsymmetric) && sM->stateNumber == 5) {
-        if (sX->get != sequence_getBase || sY->get != sequence_getBase)
-            die("cpecan: the 5-state machine needs sequence_getBase element getters on both sequences");
-        return 1;
-    }
-    if (sM->type == threeStateHdp && sM->stateNumber == 3) {
-        if (sX->get != sequence_getKmer3 || sY->get != sequence_getEvent)
-            die("cpecan: the HDP machine needs sequence_getKmer3 / sequence_getEvent element getters");
-        if (!((StateMachine3_HDP *) sM)->hdpModel) die("cpecan: the HDP machine has no NanoporeHDP");
-        return 3;
-    }
-    if (sM->type == vanilla && sM->stateNumber == 3) {
-        if (sX->get != sequence_getKmer2 || sY->get != sequence_getEvent)
-            die("cpecan: the vanilla machine needs sequence_getKmer2 / sequence_getEvent element getters");
-        return 2;
-    }
-    if (sM->type == echelon && sM->stateNumber == 7) {
-        if (sX->get != sequence_getKmer2 || sY->get != sequence_getEvent)
-            die("cpecan: the echelon machine needs sequence_getKmer2 / sequence_getEvent element getters");
-        return 5;
-    }
-    if (sM->type == fourState && sM->stateNumber == 4) {
-        if (sX->get != sequence_getKmer || sY->get != sequence_getEvent)
-            die("cpecan: the 4-state machine needs sequence_getKmer / sequence_getEvent element getters");
-        return 4;
-    }
-    if (sM->type != threeState || sM->stateNumber != 3)
-        die("cpecan: only the threeState (strawMan), fourState, vanilla, echelon and HDP signal StateMachines and the fiveState "
-            "symbol StateMachine run on the GPU path (type %d)", sM->type);
-    if (sX->get != sequence_getKmer || sY->get != sequence_getEvent)
-        die("cpecan: the GPU path needs sequence_getKmer / sequence_getEvent element getters");
-    return 0;
-}
+/* ---- the six machines of the GPU path: one table row each, and run_reads in steps over one record ---- */
+typedef enum { /* in the order of CPECAN_MACHINE_* (cpecan_hip.h) */
+    HM_STRAWMAN, HM_DNA5, HM_VANILLA, HM_HDP, HM_SM4, HM_ECHELON, HM_COUNT
+} HostMachine;
 
 typedef struct {
     int64_t read, x1, y1;
 } ItemOrigin;
 
+/* One call of run_reads: its arguments and every buffer its steps allocate (run_release frees them all) */
+typedef struct {
+    const struct MachineRow *row;
+    int64_t n;
+    StateMachine **sMs;
+    Sequence **sXs, **sYs;
+    stList **anchorLists;
+    PairwiseAlignmentParameters *p;
+    bool raggedL, raggedR;
+    int mode, unbanded;
+    void *hmmOut;
+    /* dedupe_models: nModels structs of row->modelSize bytes, the state machine each was filled from */
+    void *models;
+    StateMachine **owner;
+    int32_t *modelOf, *ids, nModels;
+    /* pack_reads; nAnchorsGiven in the callers' lists, nAnchors packed (those past a read's last cell are left out) */
+    char *chars, *ychars;
+    double *events;
+    int64_t *anchors, *firstItem, nX, nY, nAnchorsGiven, nAnchors, nItems;
+    cpecan_item *items;
+    ItemOrigin *origin;
+} Run;
+
+typedef struct MachineRow {
+    /* recognition: StateMachineType(s), stateNumber, element getters of X and Y, what to say of other getters */
+    StateMachineType type, type2;
+    int64_t stateNumber;
+    void *(*getX)(void *, int64_t), *(*getY)(void *, int64_t);
+    const char *gettersText;
+    /* input geometry: chars a k-mer sequence spans beyond its length; Y as characters instead of events */
+    int64_t xPad;
+    bool yChars;
+    /* modes: what to say of an E-step where add_expectations is NULL; the same for unbanded == 2 */
+    const char *refusal;
+    bool noSingleBand;
+    bool echelonRuns; /* a cell emits runs of pairs: the look-ahead of pack_items, append_diagonals_upwards */
+    /* model: size, fill from a state machine, "the same model" (NULL: the same StateMachine), upload */
+    size_t modelSize;
+    void (*fill)(StateMachine *sM, void *slot);
+    bool (*same)(const void *a, const void *b);
+    void (*models_create)(cpecan_ctx *ctx, const void *models, int32_t nModels, int32_t *ids);
+    void (*batch_create)(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch);
+    void (*add_expectations)(const Run *r, cpecan_batch *batch);
+} MachineRow;
+
+/* ---- models ---- */
+static void fill_sm3(StateMachine *sM, void *slot) {
+    const StateMachine3 *s3 = (const StateMachine3 *) sM;
+    cpecan_sm3_model *m = slot;
+    memcpy(m->transitions, &s3->TRANSITION_MATCH_CONTINUE, sizeof m->transitions);
+    m->match_probs = sM->EMISSION_MATCH_PROBS;
+    m->gap_x_probs = sM->EMISSION_GAP_X_PROBS;
+    m->gap_y_probs = sM->EMISSION_GAP_Y_PROBS;
+}
+/* strawMan reads share a model when the three emission tables and the nine transitions agree (vanillaAlign builds a
+ * machine per read over shared tables) */
+static bool same_sm3(const void *a, const void *b) {
+    const cpecan_sm3_model *p = a, *q = b;
+    return p->match_probs == q->match_probs && p->gap_x_probs == q->gap_x_probs && p->gap_y_probs == q->gap_y_probs &&
+           memcmp(p->transitions, q->transitions, sizeof p->transitions) == 0;
+}
+static void fill_sm5(StateMachine *sM, void *slot) {
+    const StateMachine5 *s5 = (const StateMachine5 *) sM;
+    cpecan_sm5_model *m = slot;
+    memcpy(m->transitions, &s5->TRANSITION_MATCH_CONTINUE, sizeof m->transitions);
+    memcpy(m->match_probs, sM->EMISSION_MATCH_PROBS, sizeof m->match_probs);
+    memcpy(m->gap_x_probs, sM->EMISSION_GAP_X_PROBS, sizeof m->gap_x_probs);
+    memcpy(m->gap_y_probs, sM->EMISSION_GAP_Y_PROBS, sizeof m->gap_y_probs);
+}
+static void fill_vanilla(StateMachine *sM, void *slot) {
+    const StateMachine3Vanilla *sv = (const StateMachine3Vanilla *) sM;
+    cpecan_vanilla_model *m = slot;
+    m->m_to_y_not_x = sv->TRANSITION_M_TO_Y_NOT_X;
+    m->e_to_e = sv->TRANSITION_E_TO_E;
+    m->end_match_prob = sv->DEFAULT_END_MATCH_PROB;
+    m->end_from_x_prob = sv->DEFAULT_END_FROM_X_PROB;
+    m->end_from_y_prob = sv->DEFAULT_END_FROM_Y_PROB;
+    m->match_probs = sM->EMISSION_MATCH_PROBS;
+    m->skip_probs = sM->EMISSION_GAP_X_PROBS;
+    m->gap_y_probs = sM->EMISSION_GAP_Y_PROBS;
+}
+static void fill_sm4(StateMachine *sM, void *slot) {
+    const StateMachine4 *s4 = (const StateMachine4 *) sM;
+    cpecan_sm4_model *m = slot;
+    memcpy(m->transitions, &s4->TRANSITION_MATCH_CONTINUE, sizeof m->transitions);
+    m->match_probs = sM->EMISSION_MATCH_PROBS;
+    m->gap_x_probs = sM->EMISSION_GAP_X_PROBS;
+    m->gap_y_probs = sM->EMISSION_GAP_Y_PROBS;
+}
+static void fill_echelon(StateMachine *sM, void *slot) {
+    const StateMachineEchelon *se = (const StateMachineEchelon *) sM;
+    cpecan_echelon_model *m = slot;
+    m->end_match_prob = se->DEFAULT_END_MATCH_PROB;
+    m->end_from_x_prob = se->DEFAULT_END_FROM_X_PROB;
+    m->match_probs = sM->EMISSION_MATCH_PROBS;
+    m->skip_probs = sM->EMISSION_GAP_X_PROBS;
+    m->gap_y_probs = sM->EMISSION_GAP_Y_PROBS;
+}
+/* (the strawMan and vanilla calls derive tables on the host: threads 0, all cores) */
+static void models_sm3(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_models_create(c, m, n, 0, ids)); }
+static void models_sm5(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_models5_create(c, m, n, ids)); }
+static void models_vanilla(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_modelsv_create(c, m, n, 0, ids)); }
+static void models_hdp(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_modelsh_create(c, m, n, ids)); }
+static void models_sm4(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_models4_create(c, m, n, ids)); }
+static void models_echelon(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_modelse_create(c, m, n, ids)); }
+
+/* ---- batches: each machine's create call with its own flags ---- */
+static int32_t unbanded_flag(const Run *r) { return r->unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0; }
+static int32_t estep_flag(const Run *r) { return r->mode ? CPECAN_FLAG_EXPECTATIONS : 0; }
+/* CPECAN_VANILLA_FUSED_ESTEP=1: the E-step summed inside the sweep back on the wave kernels (the flag means
+ * nothing to a batch it does not serve); CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP=1: the same on the workgroup
+ * kernels, for a batch that CPECAN_WIDE_BANDS_VANILLA_ESTEP=1 sends there (bands of 185..504 k-mers) */
+static int32_t vanilla_fused_estep_flags(void) {
+    const char *fusedEstep = getenv("CPECAN_VANILLA_FUSED_ESTEP");
+    const char *fusedWide = getenv("CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP");
+    return (fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_VANILLA_FUSED_ESTEP : 0) |
+           (fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP : 0);
+}
+/* what every create call takes of the record; y: the events, or the characters of a DNA read */
+#define PACKED(r, y) (r)->items, (r)->nItems, (r)->chars, (r)->nX, (y), (r)->nY, (r)->anchors, (r)->nAnchors
+static void batch_sm3(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    /* (one batch per call, nothing chained behind it: the smaller footprint) */
+    CHECK(cpecan_hip_batch_create(ctx, PACKED(r, r->events), bp, r->mode ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
+                                  CPECAN_KERNEL_AUTO, unbanded_flag(r) | CPECAN_FLAG_SMALL_FOOTPRINT, batch));
+}
+static void batch_dna(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    CHECK(cpecan_hip_batch_create_dna(ctx, PACKED(r, r->ychars), bp, unbanded_flag(r) | estep_flag(r), batch));
+}
+static void batch_vanilla(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    const int32_t fused = r->mode ? vanilla_fused_estep_flags() : 0;
+    CHECK(cpecan_hip_batch_create_vanilla(ctx, PACKED(r, r->events), bp, unbanded_flag(r) | estep_flag(r) | fused, batch));
+}
+static void batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    cpecan_band_params own = *bp;
+    if (r->mode) own.threshold = ((HdpHmmExpectations *) r->hmmOut)->threshold; /* the assignment bar */
+    CHECK(cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r), batch));
+}
+static void batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    CHECK(cpecan_hip_batch_create_sm4(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch));
+}
+static void batch_echelon(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    CHECK(cpecan_hip_batch_create_echelon(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch));
+}
+
+/* ---- expectations: the device's per-model sums added into the caller's struct ---- */
+/* every model's sums: the first nA onto a, the next nB onto b, the one after them onto the likelihood */
+static void add_sums(const Run *r, cpecan_batch *batch, double *a, int nA, double *b, int nB, double *likelihood) {
+    double *e = malloc(sizeof(double) * (size_t) (nA + nB + 1));
+    for (int32_t k = 0; k < r->nModels; k++) {
+        CHECK(cpecan_hip_batch_fetch_expectations(batch, r->ids[k], e));
+        for (int q = 0; q < nA; q++) a[q] += e[q];
+        for (int q = 0; q < nB; q++) b[q] += e[nA + q];
+        *likelihood += e[nA + nB];
+    }
+    free(e);
+}
+static void expect_sm3(const Run *r, cpecan_batch *batch) { /* CPECAN_EXPECTATION_LEN */
+    ContinuousPairHmmExpectations *hmm = r->hmmOut;
+    add_sums(r, batch, hmm->transitions, 9, hmm->individualKmerGapProbs, NUM_OF_KMERS, &hmm->likelihood);
+}
+static void expect_vanilla(const Run *r, cpecan_batch *batch) { /* CPECAN_EXPECTATIONV_LEN */
+    VanillaHmmExpectations *hmm = r->hmmOut;
+    add_sums(r, batch, hmm->kmerSkipBins, 60, NULL, 0, &hmm->likelihood);
+}
+/* through the Hmm's own add functions (cell_updateExpectations :407-424 calls them per transition) */
+static void expect_dna(const Run *r, cpecan_batch *batch) {
+    Hmm *hmm = r->hmmOut;
+    double e[CPECAN_EXPECTATION5_LEN];
+    for (int32_t k = 0; k < r->nModels; k++) {
+        CHECK(cpecan_hip_batch_fetch_expectations(batch, r->ids[k], e));
+        for (int64_t f = 0; f < 5; f++)
+            for (int64_t t = 0; t < 5; t++)
+                if (e[f * 5 + t] != 0.0) hmm->addToTransitionExpectationFcn(hmm, f, t, e[f * 5 + t]);
+        for (int64_t st = 0; st < 5; st++)
+            for (int64_t x = 0; x < 4; x++)
+                for (int64_t y = 0; y < 4; y++)
+                    if (e[25 + st * 16 + x * 4 + y] != 0.0)
+                        hmm->addToEmissionExpectationFcn(hmm, st, x, y, e[25 + st * 16 + x * 4 + y]);
+        hmm->likelihood += e[CPECAN_EXPECTATION5_LEN - 1];
+    }
+}
+/* one assignment of the HDP E-step: (k-mer, event mean) at (x, y) of read i */
+static void hdp_add_assignment(HdpHmmExpectations *hmm, const Run *r, int64_t i, int64_t x, int64_t y) {
+    if (hmm->numberOfAssignments == hmm->capacity || !hmm->assignmentXY) {
+        hmm->capacity = hmm->capacity ? 2 * hmm->capacity : 1024;
+        hmm->eventAssignments = realloc(hmm->eventAssignments, sizeof(double) * (size_t) hmm->capacity);
+        hmm->kmerAssignments = realloc(hmm->kmerAssignments, (size_t) hmm->capacity * (KMER_LENGTH + 1));
+        hmm->assignmentXY = realloc(hmm->assignmentXY, sizeof(int64_t) * 3 * (size_t) hmm->capacity);
+    }
+    hmm->assignmentXY[3 * hmm->numberOfAssignments] = x >= 0 ? x : 0;
+    hmm->assignmentXY[3 * hmm->numberOfAssignments + 1] = y;
+    hmm->assignmentXY[3 * hmm->numberOfAssignments + 2] = i;
+    char *dst = hmm->kmerAssignments + hmm->numberOfAssignments * (KMER_LENGTH + 1);
+    memcpy(dst, (const char *) r->sXs[i]->elements + (x >= 0 ? x : 0), KMER_LENGTH);
+    dst[KMER_LENGTH] = 0;
+    hmm->eventAssignments[hmm->numberOfAssignments++] = ((const double *) r->sYs[i]->elements)[3 * y];
+}
+static void expect_hdp(const Run *r, cpecan_batch *batch) {
+    HdpHmmExpectations *hmm = r->hmmOut;
+    add_sums(r, batch, hmm->transitions, 9, NULL, 0, &hmm->likelihood); /* CPECAN_EXPECTATIONH_LEN */
+    /* assignments, sub-alignment after sub-alignment as the reference walks them */
+    int64_t *np = malloc(sizeof(int64_t) * (size_t) r->nItems);
+    CHECK(cpecan_hip_batch_counts(batch, np, NULL, NULL));
+    for (int64_t i = 0; i < r->n; i++)
+        for (int64_t k = r->firstItem[i]; k < r->firstItem[i + 1]; k++) {
+            int64_t *tri = malloc(sizeof(int64_t) * 3 * (size_t) (np[k] + 1));
+            CHECK(cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, np[k] + 1));
+            for (int64_t q = 0; q < np[k]; q++)
+                hdp_add_assignment(hmm, r, i, tri[3 * q + 1] + r->origin[k].x1, tri[3 * q + 2] + r->origin[k].y1);
+            free(tri);
+        }
+    free(np);
+}
+
+#define ECHELON_REFUSAL                                                                                              \
+    "cpecan: the echelon machine has posterior decode only, through getAlignedPairsUsingAnchors, "                   \
+    "getAlignedPairsWithoutBanding or getAlignedPairsUsingAnchorsBatch (the reference has no expectations for it)"
+static const MachineRow MACHINES[HM_COUNT] = {
+    [HM_STRAWMAN] = { threeState, threeState, 3, sequence_getKmer, sequence_getEvent,
+                      "cpecan: the GPU path needs sequence_getKmer / sequence_getEvent element getters",
+                      KMER_LENGTH - 1, false, NULL, false, false,
+                      sizeof(cpecan_sm3_model), fill_sm3, same_sm3, models_sm3, batch_sm3, expect_sm3 },
+    [HM_DNA5] = { fiveState, fiveStateAsymmetric, 5, sequence_getBase, sequence_getBase,
+                  "cpecan: the 5-state machine needs sequence_getBase element getters on both sequences",
+                  0, true, NULL, false, false,
+                  sizeof(cpecan_sm5_model), fill_sm5, NULL, models_sm5, batch_dna, expect_dna },
+    [HM_VANILLA] = { vanilla, vanilla, 3, sequence_getKmer2, sequence_getEvent,
+                     "cpecan: the vanilla machine needs sequence_getKmer2 / sequence_getEvent element getters",
+                     KMER_LENGTH - 1, false, NULL, false, false,
+                     sizeof(cpecan_vanilla_model), fill_vanilla, NULL, models_vanilla, batch_vanilla, expect_vanilla },
+    [HM_HDP] = { threeStateHdp, threeStateHdp, 3, sequence_getKmer3, sequence_getEvent,
+                 "cpecan: the HDP machine needs sequence_getKmer3 / sequence_getEvent element getters",
+                 KMER_LENGTH - 1, false, NULL, false, false,
+                 sizeof(cpecan_hdp_model), cpecan_hdp_machine_as_model, NULL, models_hdp, batch_hdp, expect_hdp },
+    [HM_SM4] = { fourState, fourState, 4, sequence_getKmer, sequence_getEvent,
+                 "cpecan: the 4-state machine needs sequence_getKmer / sequence_getEvent element getters",
+                 KMER_LENGTH - 1, false,
+                 "cpecan: the 4-state machine has no expectations (the reference has no Hmm for it)", false, false,
+                 sizeof(cpecan_sm4_model), fill_sm4, NULL, models_sm4, batch_sm4, NULL },
+    [HM_ECHELON] = { echelon, echelon, 7, sequence_getKmer2, sequence_getEvent,
+                     "cpecan: the echelon machine needs sequence_getKmer2 / sequence_getEvent element getters",
+                     KMER_LENGTH - 1, false, ECHELON_REFUSAL, true, true,
+                     sizeof(cpecan_echelon_model), fill_echelon, NULL, models_echelon, batch_echelon, NULL },
+};
+
+/* the machine of a read, or no return: anything but the six combinations of the table is not on the GPU path */
+static HostMachine check_known_combination(StateMachine *sM, Sequence *sX, Sequence *sY) {
+    if (!cpecan_sm_functions_known(sM))
+        die("cpecan: this StateMachine carries a cellCalculate or emission function of the caller's own; the GPU path "
+            "implements the reference's models only (symbol, strawMan, vanilla two-distribution and HDP emissions) "
+            "and there is no CPU path to fall back to");
+    for (HostMachine m = 0; m < HM_COUNT; m++) {
+        const MachineRow *row = &MACHINES[m];
+        if ((sM->type != row->type && sM->type != row->type2) || sM->stateNumber != row->stateNumber) continue;
+        if (sX->get != row->getX || sY->get != row->getY) die("%s", row->gettersText);
+        if (m == HM_HDP && !((StateMachine3_HDP *) sM)->hdpModel) die("cpecan: the HDP machine has no NanoporeHDP");
+        return m;
+    }
+    die("cpecan: only the threeState (strawMan), fourState, vanilla, echelon and HDP signal StateMachines and the fiveState "
+        "symbol StateMachine run on the GPU path (type %d)", sM->type);
+}
+
+/* ---- the steps of run_reads ---- */
+/* the machine of the call (read 0's; every read must be of it) and the sizes of the packed inputs */
+static void size_inputs(Run *r) {
+    const HostMachine kind = r->n > 0 ? check_known_combination(r->sMs[0], r->sXs[0], r->sYs[0]) : HM_STRAWMAN;
+    r->row = &MACHINES[kind];
+    if ((r->mode != 0 && !r->row->add_expectations) || (r->unbanded == 2 && r->row->noSingleBand))
+        die("%s", r->row->refusal);
+    for (int64_t i = 0; i < r->n; i++) {
+        if (check_known_combination(r->sMs[i], r->sXs[i], r->sYs[i]) != kind)
+            die("cpecan: one call cannot mix state machine kinds");
+        /* a k-mer sequence of lX elements spans lX + 5 chars */
+        r->nX += r->sXs[i]->length + (r->sXs[i]->length > 0 ? r->row->xPad : 0);
+        r->nY += r->sYs[i]->length;
+        r->nAnchorsGiven += r->anchorLists && r->anchorLists[i] ? stList_length(r->anchorLists[i]) : 0;
+    }
+}
+
+/* one device model per distinct model among the reads; modelOf[i] is read i's */
+static void dedupe_models(Run *r, cpecan_ctx *ctx) {
+    const MachineRow *row = r->row;
+    r->models = malloc(row->modelSize * (size_t) (r->n + 1));
+    r->owner = malloc(sizeof(StateMachine *) * (size_t) (r->n + 1));
+    r->modelOf = malloc(sizeof(int32_t) * (size_t) r->n);
+    for (int64_t i = 0; i < r->n; i++) {
+        char *candidate = (char *) r->models + row->modelSize * (size_t) r->nModels;
+        int32_t found = -1;
+        row->fill(r->sMs[i], candidate);
+        for (int32_t k = 0; k < r->nModels && found < 0; k++) {
+            const void *known = (char *) r->models + row->modelSize * (size_t) k;
+            if (row->same ? row->same(known, candidate) : r->owner[k] == r->sMs[i]) found = k;
+        }
+        if (found < 0) { /* the candidate stays */
+            r->owner[r->nModels] = r->sMs[i];
+            found = r->nModels++;
+        }
+        r->modelOf[i] = found;
+    }
+    r->ids = malloc(sizeof(int32_t) * (size_t) r->nModels);
+    CHECK(cpecan_hip_models_clear(ctx));
+    row->models_create(ctx, r->models, r->nModels, r->ids);
+}
+
+/* the items of read i: one, or the reference's split at large anchor-free gaps
+ * (getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps :1356-1422); xo, yo: where the read starts */
+static void pack_items(Run *r, int64_t i, int64_t xo, int64_t yo, int64_t *capItems) {
+    const int64_t lX = r->sXs[i]->length, lY = r->sYs[i]->length;
+    int64_t na;
+    int64_t *ra = flat_anchors(r->anchorLists ? r->anchorLists[i] : NULL, &na);
+    int64_t *sp = malloc(sizeof(int64_t) * 4 * (size_t) (na + 2));
+    int64_t nSp;
+    if (r->unbanded) { /* 1: getAlignedPairsWithoutBanding; 2: one getPosteriorProbsWithBanding call */
+        nSp = 1; sp[0] = 0; sp[1] = 0; sp[2] = lX; sp[3] = lY;
+    } else {
+        nSp = cpecan_split_points(ra, na, lX, lY, r->p->splitMatrixBiggerThanThis, r->raggedL, r->raggedR, sp, na + 2);
+    }
+    int64_t j = 0;
+    for (int64_t s = 0; s < nSp; s++) {
+        const int64_t x1 = sp[4 * s], y1 = sp[4 * s + 1], x2 = sp[4 * s + 2], y2 = sp[4 * s + 3];
+        if (r->nItems == *capItems) {
+            *capItems = *capItems ? *capItems * 2 : 64;
+            r->items = realloc(r->items, sizeof(cpecan_item) * (size_t) *capItems);
+            r->origin = realloc(r->origin, sizeof(ItemOrigin) * (size_t) *capItems);
+        }
+        cpecan_item *it = &r->items[r->nItems];
+        memset(it, 0, sizeof *it);
+        it->x_offset = xo + x1; it->lX = x2 - x1;
+        it->y_offset = yo + y1; it->lY = y2 - y1;
+        it->anchor_offset = r->nAnchors;
+        while (j < na && ra[2 * j] + ra[2 * j + 1] < x2 + y2) { /* relative to the sub-alignment */
+            r->anchors[2 * r->nAnchors] = ra[2 * j] - x1;
+            r->anchors[2 * r->nAnchors + 1] = ra[2 * j + 1] - y1;
+            r->nAnchors++; j++;
+        }
+        it->n_anchors = r->nAnchors - it->anchor_offset;
+        it->model_id = r->ids[r->modelOf[i]];
+        it->ragged_left = r->raggedL || s > 0;
+        it->ragged_right = r->raggedR || s < nSp - 1;
+        /* the echelon look-ahead of a sub-alignment reads on into the rest of the read (the reference slices the
+         * sequence by offsetting its pointer, :1400) */
+        if (r->row->echelonRuns) it->reserved = (int32_t) (lX - x2 < 30 ? lX - x2 : 30);
+        r->origin[r->nItems].read = i; r->origin[r->nItems].x1 = x1; r->origin[r->nItems].y1 = y1;
+        r->nItems++;
+    }
+    free(ra);
+    free(sp);
+}
+
+/* sequences, events and anchors of all reads into one buffer each, and the reads' items (firstItem[i] .. firstItem[i+1]) */
+static void pack_reads(Run *r) {
+    const MachineRow *row = r->row;
+    r->chars = malloc((size_t) r->nX + 8);
+    r->events = malloc(row->yChars ? 8 : sizeof(double) * 3 * (size_t) (r->nY + 1));
+    r->ychars = malloc(row->yChars ? (size_t) r->nY + 8 : 8);
+    r->anchors = malloc(sizeof(int64_t) * 2 * (size_t) (r->nAnchorsGiven + 1));
+    r->firstItem = malloc(sizeof(int64_t) * (size_t) (r->n + 1));
+    int64_t xo = 0, yo = 0, capItems = 0;
+    for (int64_t i = 0; i < r->n; i++) {
+        const int64_t lX = r->sXs[i]->length, lY = r->sYs[i]->length;
+        if (lX > 0) memcpy(r->chars + xo, r->sXs[i]->elements, (size_t) (lX + row->xPad));
+        if (lY > 0 && row->yChars) memcpy(r->ychars + yo, r->sYs[i]->elements, (size_t) lY);
+        if (lY > 0 && !row->yChars) memcpy(r->events + 3 * yo, r->sYs[i]->elements, sizeof(double) * 3 * (size_t) lY);
+        r->firstItem[i] = r->nItems;
+        pack_items(r, i, xo, yo, &capItems);
+        xo += lX + (lX > 0 ? row->xPad : 0);
+        yo += lY;
+    }
+    r->firstItem[r->n] = r->nItems;
+}
+
+static cpecan_batch *create_batch(Run *r, cpecan_ctx *ctx) {
+    const cpecan_band_params bp = { r->p->threshold, r->p->minDiagsBetweenTraceBack, r->p->traceBackDiagonals,
+                                    r->p->diagonalExpansion };
+    cpecan_batch *batch = NULL;
+    r->row->batch_create(ctx, r, &bp, &batch);
+    return batch;
+}
+
+/* ---- the three orders the reference's entry points leave an item's pairs in ---- */
+static void append_triple(stList *list, const int64_t *t, int64_t dx, int64_t dy) {
+    stList_append(list, stIntTuple_construct3(t[0], t[1] + dx, t[2] + dy));
+}
+/* unbanded == 2: the order diagonalCalculationPosteriorMatchProbs appends in */
+static void append_emission_order(stList *list, const int64_t *tri, int64_t np) {
+    for (int64_t q = 0; q < np; q++) append_triple(list, tri + 3 * q, 0, 0);
+}
+/* unbanded == 1: getAlignedPairsWithoutBanding walks the diagonals upwards (:1560): groups of equal x+y in reverse
+ * group order, order inside a group kept.  An echelon cell (x, y) emits runs (x-1, y-1), (x, y-1), ... of one state
+ * each: a run begins where y changes or x does not step on by one, and its first pair names the cell's diagonal. */
+static void append_diagonals_upwards(stList *list, const int64_t *tri, int64_t np, bool echelonRuns) {
+    int64_t *dg = malloc(sizeof(int64_t) * (size_t) (np + 1));
+    for (int64_t q = 0; q < np; q++) {
+        const int64_t x = tri[3 * q + 1], y = tri[3 * q + 2];
+        const bool runGoesOn = echelonRuns && q > 0 && y == tri[3 * (q - 1) + 2] && x == tri[3 * (q - 1) + 1] + 1;
+        dg[q] = runGoesOn ? dg[q - 1] : x + y;
+    }
+    int64_t e = np;
+    while (e > 0) {
+        int64_t s = e - 1;
+        const int64_t d = dg[s];
+        while (s > 0 && dg[s - 1] == d) s--;
+        for (int64_t q = s; q < e; q++) append_triple(list, tri + 3 * q, 0, 0);
+        e = s;
+    }
+    free(dg);
+}
+/* banded: shift back to the read's coordinates, then tail first (stList_pop, :1451-1453) */
+static void append_tail_first(stList *list, const int64_t *tri, int64_t np, const ItemOrigin *o) {
+    for (int64_t q = np - 1; q >= 0; q--) append_triple(list, tri + 3 * q, o->x1, o->y1);
+}
+
+/* lists[i]: the aligned pairs of read i, item after item (batch NULL: there was nothing to run) */
+static void collect_pairs(const Run *r, cpecan_batch *batch, stList **lists) {
+    int64_t *np = malloc(sizeof(int64_t) * (size_t) (r->nItems + 1));
+    if (batch) CHECK(cpecan_hip_batch_counts(batch, np, NULL, NULL));
+    for (int64_t i = 0; i < r->n; i++) {
+        lists[i] = stList_construct3(0, (void (*)(void *)) stIntTuple_destruct);
+        for (int64_t k = r->firstItem[i]; batch && k < r->firstItem[i + 1]; k++) {
+            int64_t *tri = malloc(sizeof(int64_t) * 3 * (size_t) (np[k] + 1));
+            CHECK(cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, np[k] + 1));
+            if (r->unbanded == 2) append_emission_order(lists[i], tri, np[k]);
+            else if (r->unbanded) append_diagonals_upwards(lists[i], tri, np[k], r->row->echelonRuns);
+            else append_tail_first(lists[i], tri, np[k], &r->origin[k]);
+            free(tri);
+        }
+    }
+    free(np);
+}
+
+static void run_release(Run *r) {
+    free(r->models); free(r->owner); free(r->modelOf); free(r->ids);
+    free(r->chars); free(r->ychars); free(r->events); free(r->anchors); free(r->firstItem);
+    free(r->items); free(r->origin);
+}
+
 /* Shared driver: n reads -> one batch.  mode 0: aligned pairs into lists[i]; mode 1: expectations
- * added into hmm (all reads must then share sMs[0]). */
+ * added into hmm (all reads must then share sMs[0]).  unbanded 0: banded, split at large gaps; 1: the full matrix
+ * (getAlignedPairsWithoutBanding); 2: one banded call, unsplit (getPosteriorProbsWithBanding). */
 static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **sYs, stList **anchorLists,
                       PairwiseAlignmentParameters *p, bool raggedL, bool raggedR, int mode, int unbanded,
                       stList **lists, void *hmmOut) {
     cpecan_ctx *ctx = context();
-    int64_t nX = 0, nY = 0, nA = 0, nItems = 0, capItems = 0;
-    const int kind = n > 0 ? check_known_combination(sMs[0], sXs[0], sYs[0]) : 0;
-    const int dna = kind == 1, van = kind == 2, hdp = kind == 3, sm4 = kind == 4, ech = kind == 5;
-    if (sm4 && mode != 0) die("cpecan: the 4-state machine has no expectations (the reference has no Hmm for it)");
-    if (ech && (mode != 0 || unbanded == 2))
-        die("cpecan: the echelon machine has posterior decode only, through getAlignedPairsUsingAnchors, "
-            "getAlignedPairsWithoutBanding or getAlignedPairsUsingAnchorsBatch (the reference has no expectations for it)");
-    const int64_t xPad = dna ? 0 : KMER_LENGTH - 1; /* a k-mer sequence of lX elements spans lX + 5 chars */
-    for (int64_t i = 0; i < n; i++) {
-        if (check_known_combination(sMs[i], sXs[i], sYs[i]) != kind)
-            die("cpecan: one call cannot mix state machine kinds");
-        nX += sXs[i]->length + (sXs[i]->length > 0 ? xPad : 0);
-        nY += sYs[i]->length;
-        nA += anchorLists && anchorLists[i] ? stList_length(anchorLists[i]) : 0;
-    }
-    char *chars = malloc((size_t) nX + 8);
-    double *events = malloc(dna ? 8 : sizeof(double) * 3 * (size_t) (nY + 1));
-    char *ychars = malloc(dna ? (size_t) nY + 8 : 8);
-    int64_t *anchors = malloc(sizeof(int64_t) * 2 * (size_t) (nA + 1));
-    cpecan_item *items = NULL;
-    ItemOrigin *origin = NULL;
-    int64_t *firstItem = malloc(sizeof(int64_t) * (size_t) (n + 1));
-
-    /* models: one per distinct StateMachine pointer */
-    cpecan_sm3_model *models = malloc(sizeof(cpecan_sm3_model) * (size_t) n);
-    int32_t *modelOf = malloc(sizeof(int32_t) * (size_t) n);
-    int32_t nModels = 0;
-    cpecan_sm5_model *models5 = malloc(sizeof(cpecan_sm5_model) * (size_t) (dna ? n : 1));
-    StateMachine **owner5 = malloc(sizeof(StateMachine *) * (size_t) (n + 1));
-    for (int64_t i = 0; dna && i < n; i++) { /* one model per distinct StateMachine5 */
-        int32_t found = -1;
-        for (int32_t k = 0; k < nModels && found < 0; k++)
-            if (owner5[k] == sMs[i]) found = k;
-        if (found < 0) {
-            const StateMachine5 *s5 = (const StateMachine5 *) sMs[i];
-            cpecan_sm5_model *m = &models5[nModels];
-            memcpy(m->transitions, &s5->TRANSITION_MATCH_CONTINUE, sizeof m->transitions);
-            memcpy(m->match_probs, sMs[i]->EMISSION_MATCH_PROBS, sizeof m->match_probs);
-            memcpy(m->gap_x_probs, sMs[i]->EMISSION_GAP_X_PROBS, sizeof m->gap_x_probs);
-            memcpy(m->gap_y_probs, sMs[i]->EMISSION_GAP_Y_PROBS, sizeof m->gap_y_probs);
-            owner5[nModels] = sMs[i];
-            found = nModels++;
-        }
-        modelOf[i] = found;
-    }
-    cpecan_vanilla_model *modelsV = malloc(sizeof(cpecan_vanilla_model) * (size_t) (van ? n : 1));
-    for (int64_t i = 0; van && i < n; i++) { /* one model per distinct StateMachine3Vanilla */
-        int32_t found = -1;
-        for (int32_t k = 0; k < nModels && found < 0; k++)
-            if (owner5[k] == sMs[i]) found = k;
-        if (found < 0) {
-            const StateMachine3Vanilla *sv = (const StateMachine3Vanilla *) sMs[i];
-            cpecan_vanilla_model *m = &modelsV[nModels];
-            m->m_to_y_not_x = sv->TRANSITION_M_TO_Y_NOT_X;
-            m->e_to_e = sv->TRANSITION_E_TO_E;
-            m->end_match_prob = sv->DEFAULT_END_MATCH_PROB;
-            m->end_from_x_prob = sv->DEFAULT_END_FROM_X_PROB;
-            m->end_from_y_prob = sv->DEFAULT_END_FROM_Y_PROB;
-            m->match_probs = sMs[i]->EMISSION_MATCH_PROBS;
-            m->skip_probs = sMs[i]->EMISSION_GAP_X_PROBS;
-            m->gap_y_probs = sMs[i]->EMISSION_GAP_Y_PROBS;
-            owner5[nModels] = sMs[i];
-            found = nModels++;
-        }
-        modelOf[i] = found;
-    }
-    cpecan_hdp_model *modelsH = malloc(sizeof(cpecan_hdp_model) * (size_t) (hdp ? n : 1));
-    for (int64_t i = 0; hdp && i < n; i++) { /* one model per distinct StateMachine3_HDP */
-        int32_t found = -1;
-        for (int32_t k = 0; k < nModels && found < 0; k++)
-            if (owner5[k] == sMs[i]) found = k;
-        if (found < 0) {
-            cpecan_hdp_machine_as_model(sMs[i], &modelsH[nModels]);
-            owner5[nModels] = sMs[i];
-            found = nModels++;
-        }
-        modelOf[i] = found;
-    }
-    for (int64_t i = 0; kind == 0 && i < n; i++) {
-        StateMachine3 *s3 = (StateMachine3 *) sMs[i];
-        const double t[9] = { s3->TRANSITION_MATCH_CONTINUE, s3->TRANSITION_MATCH_FROM_GAP_X,
-                              s3->TRANSITION_MATCH_FROM_GAP_Y, s3->TRANSITION_GAP_OPEN_X,
-                              s3->TRANSITION_GAP_OPEN_Y, s3->TRANSITION_GAP_EXTEND_X,
-                              s3->TRANSITION_GAP_EXTEND_Y, s3->TRANSITION_GAP_SWITCH_TO_X,
-                              s3->TRANSITION_GAP_SWITCH_TO_Y };
-        int32_t found = -1;
-        for (int32_t k = 0; k < nModels && found < 0; k++)
-            if (models[k].match_probs == sMs[i]->EMISSION_MATCH_PROBS &&
-                models[k].gap_x_probs == sMs[i]->EMISSION_GAP_X_PROBS &&
-                models[k].gap_y_probs == sMs[i]->EMISSION_GAP_Y_PROBS &&
-                memcmp(models[k].transitions, t, sizeof t) == 0)
-                found = k;
-        if (found < 0) {
-            cpecan_sm3_model *m = &models[nModels];
-            memcpy(m->transitions, t, sizeof t);
-            m->match_probs = sMs[i]->EMISSION_MATCH_PROBS;
-            m->gap_x_probs = sMs[i]->EMISSION_GAP_X_PROBS;
-            m->gap_y_probs = sMs[i]->EMISSION_GAP_Y_PROBS;
-            found = nModels++;
-        }
-        modelOf[i] = found;
-    }
-    cpecan_sm4_model *models4 = malloc(sizeof(cpecan_sm4_model) * (size_t) (sm4 ? n : 1));
-    for (int64_t i = 0; sm4 && i < n; i++) { /* one model per distinct StateMachine4 */
-        int32_t found = -1;
-        for (int32_t k = 0; k < nModels && found < 0; k++)
-            if (owner5[k] == sMs[i]) found = k;
-        if (found < 0) {
-            const StateMachine4 *s4 = (const StateMachine4 *) sMs[i];
-            cpecan_sm4_model *m = &models4[nModels];
-            memcpy(m->transitions, &s4->TRANSITION_MATCH_CONTINUE, sizeof m->transitions);
-            m->match_probs = sMs[i]->EMISSION_MATCH_PROBS;
-            m->gap_x_probs = sMs[i]->EMISSION_GAP_X_PROBS;
-            m->gap_y_probs = sMs[i]->EMISSION_GAP_Y_PROBS;
-            owner5[nModels] = sMs[i];
-            found = nModels++;
-        }
-        modelOf[i] = found;
-    }
-    cpecan_echelon_model *modelsE = malloc(sizeof(cpecan_echelon_model) * (size_t) (ech ? n : 1));
-    for (int64_t i = 0; ech && i < n; i++) { /* one model per distinct StateMachineEchelon */
-        int32_t found = -1;
-        for (int32_t k = 0; k < nModels && found < 0; k++)
-            if (owner5[k] == sMs[i]) found = k;
-        if (found < 0) {
-            const StateMachineEchelon *se = (const StateMachineEchelon *) sMs[i];
-            cpecan_echelon_model *m = &modelsE[nModels];
-            m->end_match_prob = se->DEFAULT_END_MATCH_PROB;
-            m->end_from_x_prob = se->DEFAULT_END_FROM_X_PROB;
-            m->match_probs = sMs[i]->EMISSION_MATCH_PROBS;
-            m->skip_probs = sMs[i]->EMISSION_GAP_X_PROBS;
-            m->gap_y_probs = sMs[i]->EMISSION_GAP_Y_PROBS;
-            owner5[nModels] = sMs[i];
-            found = nModels++;
-        }
-        modelOf[i] = found;
-    }
-    int32_t *ids = malloc(sizeof(int32_t) * (size_t) nModels);
-    CHECK(cpecan_hip_models_clear(ctx));
-    if (dna) CHECK(cpecan_hip_models5_create(ctx, models5, nModels, ids));
-    else if (van) CHECK(cpecan_hip_modelsv_create(ctx, modelsV, nModels, 0, ids));
-    else if (hdp) CHECK(cpecan_hip_modelsh_create(ctx, modelsH, nModels, ids));
-    else if (sm4) CHECK(cpecan_hip_models4_create(ctx, models4, nModels, ids));
-    else if (ech) CHECK(cpecan_hip_modelse_create(ctx, modelsE, nModels, ids));
-    else CHECK(cpecan_hip_models_create(ctx, models, nModels, 0, ids));
-
-    int64_t xo = 0, yo = 0, ao = 0;
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t lX = sXs[i]->length, lY = sYs[i]->length;
-        const int64_t na = anchorLists && anchorLists[i] ? stList_length(anchorLists[i]) : 0;
-        if (lX > 0) memcpy(chars + xo, sXs[i]->elements, (size_t) (lX + xPad));
-        if (lY > 0 && dna) memcpy(ychars + yo, sYs[i]->elements, (size_t) lY);
-        if (lY > 0 && !dna) memcpy(events + 3 * yo, sYs[i]->elements, sizeof(double) * 3 * (size_t) lY);
-        int64_t *ra = malloc(sizeof(int64_t) * 2 * (size_t) (na + 1));
-        for (int64_t k = 0; k < na; k++) {
-            ra[2 * k] = stIntTuple_get(stList_get(anchorLists[i], k), 0);
-            ra[2 * k + 1] = stIntTuple_get(stList_get(anchorLists[i], k), 1);
-        }
-        /* getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps :1356-1422 */
-        int64_t *sp = malloc(sizeof(int64_t) * 4 * (size_t) (na + 2));
-        int64_t nSp;
-        if (unbanded) { /* 1: getAlignedPairsWithoutBanding; 2: one getPosteriorProbsWithBanding call */
-            nSp = 1; sp[0] = 0; sp[1] = 0; sp[2] = lX; sp[3] = lY;
-        } else {
-            nSp = cpecan_split_points(ra, na, lX, lY, p->splitMatrixBiggerThanThis, raggedL, raggedR, sp, na + 2);
-        }
-        firstItem[i] = nItems;
-        int64_t j = 0;
-        for (int64_t r = 0; r < nSp; r++) {
-            const int64_t x1 = sp[4 * r], y1 = sp[4 * r + 1], x2 = sp[4 * r + 2], y2 = sp[4 * r + 3];
-            if (nItems == capItems) {
-                capItems = capItems ? capItems * 2 : 64;
-                items = realloc(items, sizeof(cpecan_item) * (size_t) capItems);
-                origin = realloc(origin, sizeof(ItemOrigin) * (size_t) capItems);
-            }
-            cpecan_item *it = &items[nItems];
-            memset(it, 0, sizeof *it);
-            it->x_offset = xo + x1; it->lX = x2 - x1;
-            it->y_offset = yo + y1; it->lY = y2 - y1;
-            it->anchor_offset = ao;
-            while (j < na && ra[2 * j] + ra[2 * j + 1] < x2 + y2) {
-                anchors[2 * ao] = ra[2 * j] - x1;
-                anchors[2 * ao + 1] = ra[2 * j + 1] - y1;
-                ao++; j++;
-            }
-            it->n_anchors = ao - it->anchor_offset;
-            it->model_id = ids[modelOf[i]];
-            it->ragged_left = raggedL || r > 0;
-            it->ragged_right = raggedR || r < nSp - 1;
-            /* the echelon look-ahead of a sub-alignment reads on into the rest of the read (the reference slices the
-             * sequence by offsetting its pointer, :1400) */
-            if (ech) it->reserved = (int32_t) (lX - x2 < 30 ? lX - x2 : 30);
-            origin[nItems].read = i; origin[nItems].x1 = x1; origin[nItems].y1 = y1;
-            nItems++;
-        }
-        xo += lX + (lX > 0 ? xPad : 0);
-        yo += lY;
-        free(ra);
-        free(sp);
-    }
-    firstItem[n] = nItems;
-
-    if (nItems > 0) {
-        cpecan_band_params bp = { p->threshold, p->minDiagsBetweenTraceBack, p->traceBackDiagonals,
-                                  p->diagonalExpansion };
-        if (hdp && mode) bp.threshold = ((HdpHmmExpectations *) hmmOut)->threshold; /* the assignment bar */
-        cpecan_batch *batch = NULL;
-        if (dna)
-            CHECK(cpecan_hip_batch_create_dna(ctx, items, nItems, chars, xo, ychars, yo, anchors, ao, &bp,
-                                              (unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0) |
-                                                  (mode ? CPECAN_FLAG_EXPECTATIONS : 0), &batch));
-        else if (hdp)
-            CHECK(cpecan_hip_batch_create_hdp(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
-                                              (unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0) |
-                                                  (mode ? CPECAN_FLAG_EXPECTATIONS : 0), &batch));
-        else if (ech)
-            CHECK(cpecan_hip_batch_create_echelon(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
-                                                  unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0, &batch));
-        else if (sm4)
-            CHECK(cpecan_hip_batch_create_sm4(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
-                                              unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0, &batch));
-        else if (van) {
-            /* CPECAN_VANILLA_FUSED_ESTEP=1: the E-step summed inside the sweep back on the wave kernels (the flag means
-             * nothing to a batch it does not serve); CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP=1: the same on the workgroup
-             * kernels, for a batch that CPECAN_WIDE_BANDS_VANILLA_ESTEP=1 sends there (bands of 185..504 k-mers) */
-            const char *fusedEstep = getenv("CPECAN_VANILLA_FUSED_ESTEP");
-            const char *fusedWide = getenv("CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP");
-            CHECK(cpecan_hip_batch_create_vanilla(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
-                                                  (unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0) |
-                                                      (mode ? CPECAN_FLAG_EXPECTATIONS : 0) |
-                                                      (mode && fusedEstep && atoi(fusedEstep) == 1
-                                                           ? CPECAN_FLAG_VANILLA_FUSED_ESTEP : 0) |
-                                                      (mode && fusedWide && atoi(fusedWide) == 1
-                                                           ? CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP : 0), &batch));
-        }
-        else
-            CHECK(cpecan_hip_batch_create(ctx, items, nItems, chars, xo, events, yo, anchors, ao, &bp,
-                                          mode ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
-                                          CPECAN_KERNEL_AUTO,
-                                          /* (one batch per call, nothing chained behind it: the smaller footprint) */
-                                          (unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0) | CPECAN_FLAG_SMALL_FOOTPRINT, &batch));
+    Run r = { .n = n, .sMs = sMs, .sXs = sXs, .sYs = sYs, .anchorLists = anchorLists, .p = p, .raggedL = raggedL,
+              .raggedR = raggedR, .mode = mode, .unbanded = unbanded, .hmmOut = hmmOut };
+    size_inputs(&r);
+    dedupe_models(&r, ctx);
+    pack_reads(&r);
+    cpecan_batch *batch = NULL;
+    if (r.nItems > 0) {
+        batch = create_batch(&r, ctx);
         CHECK(cpecan_hip_batch_run(batch));
         CHECK(cpecan_hip_batch_sync(batch));
-        if (mode == 0) {
-            int64_t *np = malloc(sizeof(int64_t) * (size_t) nItems);
-            CHECK(cpecan_hip_batch_counts(batch, np, NULL, NULL));
-            for (int64_t i = 0; i < n; i++) {
-                lists[i] = stList_construct3(0, (void (*)(void *)) stIntTuple_destruct);
-                for (int64_t k = firstItem[i]; k < firstItem[i + 1]; k++) {
-                    int64_t *tri = malloc(sizeof(int64_t) * 3 * (size_t) (np[k] + 1));
-                    CHECK(cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, np[k] + 1));
-                    if (unbanded == 2) { /* the order diagonalCalculationPosteriorMatchProbs appends in */
-                        for (int64_t q = 0; q < np[k]; q++)
-                            stList_append(lists[i], stIntTuple_construct3(tri[3 * q], tri[3 * q + 1], tri[3 * q + 2]));
-                    } else if (unbanded) {
-                        /* getAlignedPairsWithoutBanding walks the diagonals upwards (:1560): groups of
-                         * equal x+y in reverse group order, order inside a group kept.  An echelon cell (x, y)
-                         * emits runs (x-1, y-1), (x, y-1), ... of one state each: a run begins where y changes
-                         * or x does not step on by one, and its first pair names the cell's diagonal. */
-                        int64_t *dg = malloc(sizeof(int64_t) * (size_t) (np[k] + 1));
-                        for (int64_t q = 0; q < np[k]; q++) {
-                            const int64_t x = tri[3 * q + 1], y = tri[3 * q + 2];
-                            const bool runGoesOn = ech && q > 0 && y == tri[3 * (q - 1) + 2] && x == tri[3 * (q - 1) + 1] + 1;
-                            dg[q] = runGoesOn ? dg[q - 1] : x + y;
-                        }
-                        int64_t e = np[k];
-                        while (e > 0) {
-                            int64_t s = e - 1;
-                            const int64_t d = dg[s];
-                            while (s > 0 && dg[s - 1] == d) s--;
-                            for (int64_t q = s; q < e; q++)
-                                stList_append(lists[i], stIntTuple_construct3(tri[3 * q], tri[3 * q + 1], tri[3 * q + 2]));
-                            e = s;
-                        }
-                        free(dg);
-                    } else {
-                        /* shift back to the read's coordinates, then tail first (stList_pop, :1451-1453) */
-                        for (int64_t q = np[k] - 1; q >= 0; q--)
-                            stList_append(lists[i], stIntTuple_construct3(tri[3 * q], tri[3 * q + 1] + origin[k].x1,
-                                                                          tri[3 * q + 2] + origin[k].y1));
-                    }
-                    free(tri);
-                }
-            }
-            free(np);
-        } else if (dna) {
-            /* the device's per-model sums go through the Hmm's own add functions (cell_updateExpectations
-             * :407-424 calls them per transition) */
-            Hmm *hmm = hmmOut;
-            double e[CPECAN_EXPECTATION5_LEN];
-            for (int32_t k = 0; k < nModels; k++) {
-                CHECK(cpecan_hip_batch_fetch_expectations(batch, ids[k], e));
-                for (int64_t f = 0; f < 5; f++)
-                    for (int64_t t = 0; t < 5; t++)
-                        if (e[f * 5 + t] != 0.0) hmm->addToTransitionExpectationFcn(hmm, f, t, e[f * 5 + t]);
-                for (int64_t st = 0; st < 5; st++)
-                    for (int64_t x = 0; x < 4; x++)
-                        for (int64_t y = 0; y < 4; y++)
-                            if (e[25 + st * 16 + x * 4 + y] != 0.0)
-                                hmm->addToEmissionExpectationFcn(hmm, st, x, y, e[25 + st * 16 + x * 4 + y]);
-                hmm->likelihood += e[CPECAN_EXPECTATION5_LEN - 1];
-            }
-        } else if (hdp) {
-            HdpHmmExpectations *hmm = hmmOut;
-            double e[CPECAN_EXPECTATIONH_LEN];
-            for (int32_t k = 0; k < nModels; k++) {
-                CHECK(cpecan_hip_batch_fetch_expectations(batch, ids[k], e));
-                for (int q = 0; q < 9; q++) hmm->transitions[q] += e[q];
-                hmm->likelihood += e[9];
-            }
-            /* assignments, sub-alignment after sub-alignment as the reference walks them: (k-mer, event mean) */
-            int64_t *np = malloc(sizeof(int64_t) * (size_t) nItems);
-            CHECK(cpecan_hip_batch_counts(batch, np, NULL, NULL));
-            for (int64_t i = 0; i < n; i++)
-                for (int64_t k = firstItem[i]; k < firstItem[i + 1]; k++) {
-                    int64_t *tri = malloc(sizeof(int64_t) * 3 * (size_t) (np[k] + 1));
-                    CHECK(cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, np[k] + 1));
-                    for (int64_t q = 0; q < np[k]; q++) {
-                        const int64_t x = tri[3 * q + 1] + origin[k].x1, y = tri[3 * q + 2] + origin[k].y1;
-                        if (hmm->numberOfAssignments == hmm->capacity || !hmm->assignmentXY) {
-                            hmm->capacity = hmm->capacity ? 2 * hmm->capacity : 1024;
-                            hmm->eventAssignments = realloc(hmm->eventAssignments, sizeof(double) * (size_t) hmm->capacity);
-                            hmm->kmerAssignments = realloc(hmm->kmerAssignments, (size_t) hmm->capacity * (KMER_LENGTH + 1));
-                            hmm->assignmentXY = realloc(hmm->assignmentXY, sizeof(int64_t) * 3 * (size_t) hmm->capacity);
-                        }
-                        hmm->assignmentXY[3 * hmm->numberOfAssignments] = x >= 0 ? x : 0;
-                        hmm->assignmentXY[3 * hmm->numberOfAssignments + 1] = y;
-                        hmm->assignmentXY[3 * hmm->numberOfAssignments + 2] = i;
-                        char *dst = hmm->kmerAssignments + hmm->numberOfAssignments * (KMER_LENGTH + 1);
-                        memcpy(dst, (const char *) sXs[i]->elements + (x >= 0 ? x : 0), KMER_LENGTH);
-                        dst[KMER_LENGTH] = 0;
-                        hmm->eventAssignments[hmm->numberOfAssignments++] = ((const double *) sYs[i]->elements)[3 * y];
-                    }
-                    free(tri);
-                }
-            free(np);
-        } else if (van) {
-            VanillaHmmExpectations *hmm = hmmOut;
-            double e[CPECAN_EXPECTATIONV_LEN];
-            for (int32_t k = 0; k < nModels; k++) {
-                CHECK(cpecan_hip_batch_fetch_expectations(batch, ids[k], e));
-                for (int q = 0; q < 60; q++) hmm->kmerSkipBins[q] += e[q];
-                hmm->likelihood += e[60];
-            }
-        } else {
-            ContinuousPairHmmExpectations *hmm = hmmOut;
-            double *e = malloc(sizeof(double) * CPECAN_EXPECTATION_LEN);
-            for (int32_t k = 0; k < nModels; k++) {
-                CHECK(cpecan_hip_batch_fetch_expectations(batch, ids[k], e));
-                for (int q = 0; q < 9; q++) hmm->transitions[q] += e[q];
-                for (int q = 0; q < NUM_OF_KMERS; q++) hmm->individualKmerGapProbs[q] += e[9 + q];
-                hmm->likelihood += e[9 + NUM_OF_KMERS];
-            }
-            free(e);
-        }
-        CHECK(cpecan_hip_batch_destroy(batch));
-    } else if (mode == 0) {
-        for (int64_t i = 0; i < n; i++) lists[i] = stList_construct3(0, (void (*)(void *)) stIntTuple_destruct);
     }
-    free(chars); free(events); free(anchors); free(items); free(origin); free(firstItem);
-    free(models); free(modelOf); free(ids); free(models5); free(owner5); free(ychars); free(modelsV); free(modelsH); free(models4);
-    free(modelsE);
+    if (mode == 0) collect_pairs(&r, batch, lists);
+    else if (batch) r.row->add_expectations(&r, batch);
+    if (batch) CHECK(cpecan_hip_batch_destroy(batch));
+    run_release(&r);
 }
 
 /* the decode the GPU path has for the machine: diagonalCalculationMultiPosteriorMatchProbs for the echelon machine (the
