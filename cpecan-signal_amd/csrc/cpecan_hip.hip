@@ -39,8 +39,9 @@ extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
  * strawMan machine (_r) and the vanilla machine's posterior decode (_v), CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for the
  * vanilla E-step (_ve; without it that E-step stays on the general kernel), CPECAN_FLAG_WIDE_BANDS_HDP for the HDP
  * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f of the
- * workgroup family, _vf of the wave family, and the vanilla machine's _vf4 / _vf6 / _vf8 of the workgroup family, the
- * Makefile's SY_FUSED_BUILDS: the E-step summed inside the sweep back, and no other form of it) are in no
+ * workgroup family, _vf of the wave family, the vanilla machine's _vf4 / _vf6 / _vf8 of the workgroup family, the
+ * Makefile's SY_FUSED_BUILDS, and the HDP machine's _hf2 / _hf3 of the wave family, its WV_HDP_FUSED_BUILDS: the E-step
+ * summed inside the sweep back, and no other form of it) are in no
  * table here: each stands in for the build of as many rows that the rules above come to, as the last step of
  * choose_dispatch and for a batch of expectations alone (FUSED_STAND_INS, which also says what asks for each). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
@@ -50,6 +51,7 @@ SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(
 SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
 SWEEP_BUILD(cpecan_wave_build_vf2) SWEEP_BUILD(cpecan_wave_build_vf3)
+SWEEP_BUILD(cpecan_hdpfx_build_hf2) SWEEP_BUILD(cpecan_hdpfx_build_hf3)
 SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
 SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
@@ -220,7 +222,8 @@ struct Dispatch {
  * the row's flag or whose environment has the row's switch on, runs on the row's fused build, of as many waves per
  * workgroup or cells per lane.  The _r builds are the strawMan machine's alone and the _v wave builds the vanilla
  * machine's, so a flag means nothing to another machine, mode, range of bands or family, or to the general kernel:
- * such a batch runs what it runs without it.  A vanilla batch on the _ve workgroup builds (reached with
+ * such a batch runs what it runs without it; the _h2 / _h3 wave builds are the HDP machine's, and its four-cell build
+ * _h4 (bands of 185..248 k-mers) has no fused stand-in: it keeps its ring.  A vanilla batch on the _ve workgroup builds (reached with
  * CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP alone) keeps its build under the wave builds' flag and leaves it for _vf4 / _vf6 /
  * _vf8 under one of its own. */
 static const struct FusedStandIn {
@@ -236,6 +239,8 @@ static const struct FusedStandIn {
     { &cpecan_systolic_build_r8, &cpecan_systolic_build_f8, CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, &BatchEnv::fusedWide },
     { &cpecan_wave_build_v2, &cpecan_wave_build_vf2, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
     { &cpecan_wave_build_v3, &cpecan_wave_build_vf3, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_wave_build_h2, &cpecan_hdpfx_build_hf2, CPECAN_FLAG_HDP_FUSED_ESTEP, nullptr },
+    { &cpecan_wave_build_h3, &cpecan_hdpfx_build_hf3, CPECAN_FLAG_HDP_FUSED_ESTEP, nullptr },
     { &cpecan_systolic_build_ve4, &cpecan_systolicfx_build_vf4, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
     { &cpecan_systolic_build_ve6, &cpecan_systolicfx_build_vf6, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
     { &cpecan_systolic_build_ve8, &cpecan_systolicfx_build_vf8, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
@@ -1212,7 +1217,7 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
 
 int cpecan_hip_batch_expectation_pass(cpecan_batch *b, int32_t *fused) {
     if (!b || !fused) return fail(CPECAN_EINVAL, "bad argument");
-    *fused = b->fused ? 1 : 0; /* (the strawMan wave kernels' E-step, or a fused build's: _f<n>, _vf<n>) */
+    *fused = b->fused ? 1 : 0; /* (the strawMan wave kernels' E-step, or a fused build's: _f<n>, _vf<n>, _hf<n>) */
     return CPECAN_OK;
 }
 

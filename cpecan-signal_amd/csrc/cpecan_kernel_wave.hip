@@ -50,10 +50,19 @@
  * symbols suffixed _vf2, _vf3; the _v2 / _v3 objects keep their device code */
 /* Every build holds the sweeps, their launchers and one SweepBuild record; what does not depend on the build (track,
  * counts, the machines' records) is cpecan_kernel_prep.hip's */
-#if defined(WV_FUSED) && !defined(WV_VANILLA)
-#error "WV_FUSED: a build of the vanilla machine (the strawMan builds hold their fused sweeps themselves)"
+/* -DWV_HDP -DWV_FUSED: the HDP machine's E-step the same way -- the eight transition sums and the likelihood summed
+ * inside the sweep back, the assignments (transitions into match whose own posterior reaches the threshold) selected
+ * from a candidate list the sweep back parks, as the posterior decode's are -- with the forward sweep, the fused sweep
+ * back, the post kernel and the fused re-sweep, each sweep with and without the gap Y -> gap X term: symbols suffixed
+ * _hf2, _hf3, the record cpecan_hdpfx_build_hf<n> (the Makefile's WV_HDP_FUSED_BUILDS); the _h2 / _h3 objects keep
+ * their device code */
+#if defined(WV_FUSED) && !defined(WV_VANILLA) && !defined(WV_HDP)
+#error "WV_FUSED: a build of the vanilla or the HDP machine (the strawMan builds hold their fused sweeps themselves)"
 #endif
-#if defined(WV_FUSED)
+#if defined(WV_FUSED) && defined(WV_HDP)
+#define WV_HDP_FUSED 1
+#define WV_SYM(n) SWEEP_SYM(n, hf, WV_L)
+#elif defined(WV_FUSED)
 #define WV_SYM(n) SWEEP_SYM(n, vf, WV_L)
 #elif defined(WV_VANILLA)
 #define WV_SYM(n) SWEEP_SYM(n, v, WV_L)
@@ -971,7 +980,8 @@ __device__ __forceinline__ void store_b3(unsigned long long laneMask, const doub
  *   c   their matrix columns (-1: none)
  * The vanilla machine (-DWV_FUSED) collects two sums per cell and no transition (cpecan_k_wv_expect): no tr, a record of
  * g is the pair (beta: match -> gap X, alpha: gap X -> gap X) of its column, and c holds the column's skip bin (entry 21
- * of its track row, which the sweep has in the slot's registers and the post kernel has not; -1: none). */
+ * of its track row, which the sweep has in the slot's registers and the post kernel has not; -1: none).
+ * The HDP machine (-DWV_HDP -DWV_FUSED) collects the eight transitions and no k-mer bin: tr alone. */
 struct WvFx {
     double *tr, *g;
     int *c;
@@ -985,12 +995,19 @@ __host__ __device__ inline long long wv_scratch_base_bytes(int ringD) {
 #ifdef WV_VANILLA
 #define WV_FX_TR 0 /* doubles per segment of tr, per record of g */
 #define WV_FX_G 2
+#elif defined(WV_HDP_FUSED)
+#define WV_FX_TR 8 /* (the HDP machine has no k-mer bins: no g, no c) */
+#define WV_FX_G 0
 #else
 #define WV_FX_TR 8
 #define WV_FX_G 1
 #endif
 __host__ __device__ inline long long wv_fx_bytes(int ringD) {
+#ifdef WV_HDP_FUSED
+    return ((long long) ringD / 10 + 8) * (WV_FX_TR * sizeof(double));
+#else
     return ((long long) ringD / 10 + 8) * (WV_FX_TR * sizeof(double) + 2 * WV_P * (WV_FX_G * sizeof(double) + sizeof(int)));
+#endif
 }
 __device__ inline WvFx wv_fx_at(char *sc, int ringD) {
     const long long nW = (long long) ringD / 10 + 8;
@@ -1315,17 +1332,25 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             }
         };
 #else
+#ifdef WV_HDP_FUSED /* (the HDP machine collects no gap-X sums per k-mer: no g, no c) */
+        double ea[8], py1[L];
+#else
         double ea[8], gA[L], py1[L]; /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y */
         int cA[L];
+#endif
         if (FX) {
 #pragma unroll
             for (int i = 0; i < 8; i++) ea[i] = 0.0;
 #pragma unroll
             for (int j = 0; j < L; j++) {
+#ifndef WV_HDP_FUSED
                 gA[j] = 0.0;
                 cA[j] = -1;
+#endif
                 py1[j] = CP_NEG_INF;
+#ifndef WV_HDP_FUSED
                 fxo.c[lane * L + j] = -1; /* segment 0 has no A record yet */
+#endif
             }
             if (KIND == WV_KIND_EXPECT_REDO) refAcc = uni64_d(ld_agent(&wtot[0].total));
         }
@@ -1338,6 +1363,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 if (lane == 0) fxo.tr[segAcc * 8 + i] = v;
                 ea[i] = 0.0;
             }
+#ifndef WV_HDP_FUSED
 #pragma unroll
             for (int j = 0; j < L; j++) {
                 const int sl = lane * L + j;
@@ -1346,9 +1372,56 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 fxo.c[(segAcc * 2 + 2) * WV_P + sl] = -1; /* the next segment's A records */
                 gA[j] = 0.0;
             }
+#endif
             segAcc++;
             if (KIND == WV_KIND_EXPECT_REDO) refAcc = uni64_d(ld_agent(&wtot[segAcc].total));
         };
+#ifdef WV_HDP_FUSED
+        /* The HDP machine's assignments (cell_signal_updateTransAndKmerSkipExpectations2 :445-476): a transition into
+         * match whose own posterior exp(s - total) reaches the threshold leaves as (from-state + 4 * window, x - 1, y - 1)
+         * with its exponent.  s: the three exponents of the middle block of diagonal t before the total is subtracted, of
+         * this lane's cell in layer j.  The sweep parks (t, from-state, x) and s where s lies within WV_CAND_SLACK of the
+         * threshold against the estimate; the post kernel, which holds the exact totals, selects among them (the
+         * subtraction is the last operation of the reference's expression, so its exponents are the ring path's bit for
+         * bit).  The re-sweep has the totals: it emits in the loop, from q, the terms exp(s - total) it has formed, for
+         * the cells of the band whose neighbour is in the band (in).  Order within an alignment is the host's to restore.
+         * nMin: the first column of the band of t - 1 -- an edge moves by at most one column per diagonal, so the band
+         * of t lies within [nMin, nMin + WV_P) and the slot's column on t is the one of its residue there. */
+        const int fxWindow = uni(win.pad);
+        auto fx_assign = [&](const int j, const int t, const int nMin, const bool in, const double (&s)[3],
+                             const double (&q)[3]) __attribute__((always_inline)) {
+            constexpr bool EMIT = KIND == WV_KIND_EXPECT_REDO;
+            bool hit[3];
+#pragma unroll
+            for (int f = 0; f < 3; f++) hit[f] = EMIT ? in && q[f] >= P.threshold : s[f] >= candThr;
+            if (__ballot(hit[0] || hit[1] || hit[2]) == 0ull) return;
+            const int sl = lane * L + j, sMin = nMin % WV_P;
+            const int x = nMin + (sl - sMin + (sl < sMin ? WV_P : 0));
+#pragma unroll
+            for (int f = 0; f < 3; f++) {
+                const unsigned long long hm = __ballot(hit[f]);
+                const int before = __popcll(hm & ((1ull << lane) - 1ull));
+                if (EMIT) {
+                    const long long at = out.nPairs + emitted + before;
+                    if (hit[f] && at < out.pairCap) {
+                        long long *o = out.pairs + at * 3;
+                        o[0] = f + 4ll * fxWindow;
+                        o[1] = x - 1;
+                        o[2] = (t - x) - 1;
+                        out.logp[at] = s[f] - refAcc;
+                    }
+                    emitted += __popcll(hm);
+                } else {
+                    const int ci = nCand + before;
+                    if (hit[f] && ci < candCap) { /* (writes stop at the capacity, the count goes on: the post kernel's sign) */
+                        candKx[ci] = make_int2((tPost0 - t) * 4 + f, x);
+                        candFb[ci] = s[f];
+                    }
+                    nCand += __popcll(hm);
+                }
+            }
+        };
+#endif
         /* rF, rX, rY: this slot's forward cells of row u1 - 1; nMin, nMax: the band of u1 */
         auto fx_terms = [&](const double (&rF)[L], const double (&rX)[L], const double (&rY)[L], const int u1,
                             const int nMin, const int nMax) __attribute__((always_inline)) {
@@ -1364,8 +1437,15 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
              * term included on the build without it (its transition is -inf) -- instead of one per slot */
             if (u1 + 1 <= tPost0) { /* middle block of u1+1: B.match and match emission of u1+1 are hB, hP */
                 const bool nf = KIND == WV_KIND_EXPECT_REDO && !(refAcc > CP_NEG_INF);
+#ifdef WV_HDP_FUSED
+                /* (the re-sweep emits the assignments of the cells the reference visits, whatever the total and the
+                 * threshold: it always knows the bands) */
+                const bool bands = KIND == WV_KIND_EXPECT_REDO;
+#else
+                const bool bands = nf;
+#endif
                 int cMin = 0, cMax = -1, qMin = 0, qMax = -1; /* bands of u1+1 (the cell) and u1-1 (its neighbour) */
-                if (nf) {
+                if (bands) {
                     band_load(bandTab, u1 + 1, cMin, cMax);
                     band_load(bandTab, u1 - 1, qMin, qMax);
                 }
@@ -1375,6 +1455,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     double p3 = exp(sF[j] + hB[j] + (eP + T[T_MATCH_CONTINUE]) - refAcc);
                     double p4 = exp(sX[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_X]) - refAcc);
                     double p5 = exp(sY[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_Y]) - refAcc);
+#ifndef WV_HDP_FUSED
                     if (nf) {
                         const int sl = lane * L + j, s0 = cMin % WV_P;
                         const int x = cMin + (sl - s0 + (sl < s0 ? WV_P : 0));
@@ -1383,6 +1464,25 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                         p4 = in ? p4 : 0.0;
                         p5 = in ? p5 : 0.0;
                     }
+#else
+                    {
+                        bool in = true;
+                        if (bands) {
+                            const int sl = lane * L + j, s0 = cMin % WV_P;
+                            const int x = cMin + (sl - s0 + (sl < s0 ? WV_P : 0));
+                            in = x <= cMax && x - 1 >= qMin && x - 1 <= qMax;
+                        }
+                        if (nf) {
+                            p3 = in ? p3 : 0.0;
+                            p4 = in ? p4 : 0.0;
+                            p5 = in ? p5 : 0.0;
+                        }
+                        const double s[3] = { sF[j] + hB[j] + (eP + T[T_MATCH_CONTINUE]), sX[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_X]),
+                                              sY[j] + hB[j] + (eP + T[T_MATCH_FROM_GAP_Y]) };
+                        const double q[3] = { p3, p4, p5 };
+                        fx_assign(j, u1 + 1, nMin, in, s, q);
+                    }
+#endif
                     ea[3] += p3;
                     ea[4] += p4;
                     ea[5] += p5;
@@ -1415,6 +1515,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     ea[0] += p0;
                     ea[1] += p1;
                     if (SW || nf) ea[2] += p2;
+#ifndef WV_HDP_FUSED
                     if (x <= nMax && x != cA[j]) { /* the slot took another column within the segment */
                         if (gA[j] != 0.0) {
                             fxo.g[(segAcc * 2) * WV_P + sl] = gA[j];
@@ -1426,6 +1527,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                     gA[j] += p0;
                     gA[j] += p1;
                     if (SW || nf) gA[j] += p2;
+#endif
                     ea[6] += p6;
                     ea[7] += p7;
                 }
@@ -1662,6 +1764,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             else fx_terms(q0.f, q0.fx, q0.fy, tracedBackTo + 1, bxmin, bxmax);
             fx_flush();
         }
+#ifdef WV_HDP_FUSED
+        if (KIND == WV_KIND_EXPECT_REDO) out.nPairs += emitted; /* (the assignments of fx_assign) */
+#endif
     }
     nTotOut = nTotWin;
     nCandOut = nCand;
@@ -1824,6 +1929,28 @@ __device__ void fx_finish(const int tid, const int nth, const DevItem &it, const
         if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
     }
 }
+#elif defined(WV_HDP_FUSED)
+/* ... and the HDP machine's (layout of its cpecan_k_wv_expect: nine transitions and the likelihood per model): threads
+ * 0-7 the transitions, scaled as above, thread 8 the likelihood.  The assignments are the caller's. */
+__device__ void fx_finish(const int tid, const DevItem &it, const WvFx &fx, const WinTotal *wtot, const int nSeg,
+                          const int tPost0, const int to, const double est, const bool exact, double *expect) {
+    double *dst = expect + (long long) it.model * (9 + 1);
+    if (tid < 8) {
+        constexpr int slot[8] = WV_EXPECT_SLOTS;
+        int to9 = 0; /* (selects: a table indexed by the thread would live in scratch) */
+#pragma unroll
+        for (int i = 0; i < 8; i++) to9 = tid == i ? slot[i] : to9;
+        double sum = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < nSeg; k++) sum += fx.tr[k * 8 + tid] * (exact ? 1.0 : exp(est - wtot[k].total));
+        atomicAdd(dst + to9, sum);
+    } else if (tid == 8) {
+        double lik = 0.0;
+#pragma unroll 1
+        for (int u = tPost0; u > to; u--) lik += wtot[(tPost0 - u) / 10].total;
+        atomicAdd(dst + 9, lik);
+    }
+}
 #elif defined(WV_FUSED)
 /* ... and the vanilla machine's (layout of its cpecan_k_wv_expect: 60 bins and the likelihood per model), in two steps
  * with the caller's barrier between them.  First every thread adds the records of slots tid, tid + nth, ..., scaled as
@@ -1900,7 +2027,7 @@ extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(cpecan_k_wv_for
     wv_forward_kernel<false>(items, nItems, P, bandTab, track, trackBase, events, models, Fring, ringDoubles, ringD,
                              states, window, sh);
 }
-#ifndef WV_FUSED
+#if !defined(WV_FUSED) || defined(WV_HDP_FUSED) /* (no gap Y -> gap X transition in the vanilla machine) */
 extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(cpecan_k_wv_forward_sw)(
     const DevItem *__restrict__ items, long long nItems, DevParams P,
     const int2 *__restrict__ bandTab, const double *__restrict__ track,
@@ -1934,6 +2061,9 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
         win.to = ld_agent(&w->to); win.atEnd = ld_agent(&w->atEnd); win.nCand = win.nRefresh = win.pad = 0;
         win.est = ld_agent(&w->est);
         if (KIND == WV_KIND_EXPECT_REDO) win.nRefresh = ld_agent(&w->nRefresh);
+#ifdef WV_HDP_FUSED
+        win.pad = window; /* (this copy's alone: an assignment carries its window's number) */
+#endif
     }
     if (uni(win.valid) != (REDO ? 2 : 1)) return;
     const DevItem it = uniform_item(items[idx]);
@@ -1971,6 +2101,14 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
         fx_finish(threadIdx.x & 63, 64, it, fxo, wtot, uni(win.nRefresh), dTop < from ? dTop : from, uni(win.to),
                   uni64_d(win.est), true, expect, kidx);
     }
+#elif defined(WV_HDP_FUSED)
+    if constexpr (KIND == WV_KIND_EXPECT_REDO) { /* ... the same for the HDP machine's; its assignments left in the loop */
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        const int dTop = uni(win.top), from = uni(win.from);
+        fx_finish(threadIdx.x & 63, it, fxo, wtot, uni(win.nRefresh), dTop < from ? dTop : from, uni(win.to),
+                  uni64_d(win.est), true, expect);
+    }
+    (void) kidx;
 #elif defined(WV_FUSED)
     if constexpr (KIND == WV_KIND_EXPECT_REDO) {
         /* ... the same, through the wave's 60 bin sums in LDS (the records of phase T0, which a re-sweep does not run;
@@ -1991,6 +2129,9 @@ template <bool SW, int KIND> __device__ __forceinline__ void wv_backward_kernel(
     if ((threadIdx.x & 63) == 0) {
         WvWindow *w = &state->win[window & 3];
         if (KIND == WV_KIND_EXPECT_REDO) {
+#ifdef WV_HDP_FUSED
+            state->nPairs = out.nPairs;
+#endif
             w->valid = 0;
         } else if (KIND == WV_KIND_REDO) {
             state->nPairs = out.nPairs;
@@ -2023,9 +2164,23 @@ WV_BACKWARD_KERNEL(cpecan_k_wv_backward_em_sw, true, WV_KIND_EXPECT)
 #endif
 #endif /* WV_FUSED */
 #if (!defined(WV_VANILLA) && !defined(WV_HDP)) || defined(WV_FUSED)
-/* the strawMan machine's E-step, and the vanilla machine's on its fused builds: expectations summed inside the sweep
- * back (no B ring, no expectation kernel), and the re-sweep of the windows whose sums the estimate could not carry
+/* the strawMan machine's E-step, and the vanilla and the HDP machine's on their fused builds: expectations summed inside
+ * the sweep back (no B ring, no expectation kernel), and the re-sweep of the windows whose sums the estimate could not carry
  * (cpecan_k_wv_post) */
+#ifdef WV_HDP_FUSED
+/* (the HDP machine's E-step also emits pairs, its assignments: the re-sweep writes them, the sweep takes the same list) */
+#define WV_BACKWARD_FX_KERNEL(name, SW, KIND)                                                                     \
+    extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(name)(                                       \
+        const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTab,       \
+        const double *__restrict__ track, const long long *__restrict__ trackBase,                                \
+        const double *__restrict__ models, double *Fring, long long ringDoubles, int ringD, WvState *states,      \
+        long long *pairs, double *pairLogp, char *scratch, long long scratchBytes, double *expect, int window) {  \
+        __shared__ BwdShared sh[WV_WPB];                                                                          \
+        wv_backward_kernel<SW, KIND>(items, nItems, P, bandTab, track, trackBase, models, Fring, ringDoubles,     \
+                                     ringD, states, pairs, pairLogp, scratch, scratchBytes, nullptr, window, sh,  \
+                                     expect, nullptr);                                                            \
+    }
+#else
 #define WV_BACKWARD_FX_KERNEL(name, SW, KIND)                                                                     \
     extern "C" __global__ __launch_bounds__(64 * WV_WPB) void WV_SYM(name)(                                       \
         const DevItem *__restrict__ items, long long nItems, DevParams P, const int2 *__restrict__ bandTab,       \
@@ -2038,9 +2193,10 @@ WV_BACKWARD_KERNEL(cpecan_k_wv_backward_em_sw, true, WV_KIND_EXPECT)
                                      ringD, states, nullptr, nullptr, scratch, scratchBytes, nullptr, window, sh, \
                                      expect, kidx);                                                               \
     }
+#endif
 WV_BACKWARD_FX_KERNEL(cpecan_k_wv_backward_fx, false, WV_KIND_EXPECT_FUSED)
 WV_BACKWARD_FX_KERNEL(cpecan_k_wv_resweep_fx, false, WV_KIND_EXPECT_REDO)
-#ifndef WV_FUSED /* (no gap Y -> gap X transition in the vanilla machine) */
+#if !defined(WV_FUSED) || defined(WV_HDP_FUSED) /* (no gap Y -> gap X transition in the vanilla machine) */
 WV_BACKWARD_FX_KERNEL(cpecan_k_wv_backward_fx_sw, true, WV_KIND_EXPECT_FUSED)
 WV_BACKWARD_FX_KERNEL(cpecan_k_wv_resweep_fx_sw, true, WV_KIND_EXPECT_REDO)
 #endif
@@ -2074,7 +2230,7 @@ struct PostShared {
     int part[4];
     int scan, carry, fxRedo;
     int maxLen; /* phase T: the longest row of the round */
-#ifdef WV_FUSED
+#if defined(WV_FUSED) && defined(WV_VANILLA)
     double bins[60]; /* the window's sums per skip bin (fx_finish_bins) */
 #endif
 };
@@ -2100,11 +2256,17 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     const int tPost0 = dTop < tracedBackFrom ? dTop : tracedBackFrom; /* first decoded diagonal */
     const int nPost = tPost0 - tracedBackTo;                         /* diagonals decoded      */
     const int candCap = WV_CAND_PER_DIAG * WV_L * ringD;
+#ifdef WV_HDP_FUSED
+    /* (the fused E-step's candidates are assignments: a list that overflowed, or a threshold without a logarithm, sends
+     * the window to the re-sweep, as a total that strays from the estimate does below) */
+    if (tid == 0) sh.scan = (!(P.logThrSlack > CP_NEG_INF) || nCand > candCap) ? 1 : 0;
+#else
     if (tid == 0) sh.scan = (P.scanDecode != 0 || !(P.logThrSlack > CP_NEG_INF) || nCand > candCap) ? 1 : 0;
+#endif
     /* (tests: 1 every window down the re-sweep, 2 every other one -- the items and windows alternate) */
     if (tid == 0) sh.maxLen = 0;
     if (tid == 0) sh.fxRedo = P.expectResweep == 1 || (P.expectResweep == 2 && ((idx ^ window) & 1)) ? 1 : 0;
-#ifdef WV_FUSED
+#if defined(WV_FUSED) && defined(WV_VANILLA)
     if (tid < 60) sh.bins[tid] = 0.0;
 #endif
     __syncthreads();
@@ -2217,6 +2379,39 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
         const bool redo = nPost > 0 && sh.fxRedo != 0;
         if (nPost > 0 && !redo)
             fx_finish(tid, 256, it, wv_fx_at(sc, ringD), wtot, nTotWin, tPost0, tracedBackTo, totEst, false, expect, kidx);
+        if (tid == 0) {
+            state->nTot = nTot0 + nTotWin;
+            wp->valid = redo ? 2 : 0;
+        }
+        return;
+    }
+#elif defined(WV_HDP_FUSED)
+    if (P.mode != 0 && fused) {
+        /* ... the same for the HDP machine's eight sums; and its assignments from the sweep's candidate list, which is
+         * complete only where every total lies within WV_CAND_SLACK of the estimate (sh.scan): one redo rule for both.
+         * A candidate (t, from-state, x) with the exponent s before the total is subtracted: the assignment leaves where
+         * exp(s - total) reaches the threshold, as in cpecan_k_wv_expect, in whatever order the threads get there. */
+        const bool redo = nPost > 0 && (sh.fxRedo != 0 || sh.scan != 0);
+        if (nPost > 0 && !redo) {
+            fx_finish(tid, it, wv_fx_at(sc, ringD), wtot, nTotWin, tPost0, tracedBackTo, totEst, false, expect);
+#pragma unroll 1
+            for (int i0 = 0; i0 < nCand; i0 += 256) {
+                const int i = i0 + tid < nCand ? i0 + tid : nCand - 1; /* (a uniform trip count; the spare threads do not write) */
+                const int2 kx = candKx[i];
+                const int k = kx.x >> 2, f = kx.x & 3, x = kx.y, t = tPost0 - k;
+                const double e = candFb[i] - wtot[k / 10].total;
+                if (i0 + tid < nCand && exp(e) >= P.threshold) {
+                    const long long at = (long long) atomicAdd((unsigned long long *) &state->nPairs, 1ull);
+                    if (at < it.pairCap) {
+                        long long *o = pairs + (it.pairBase + at) * 3;
+                        o[0] = f + 4ll * window;
+                        o[1] = x - 1;
+                        o[2] = (t - x) - 1;
+                        pairLogp[it.pairBase + at] = e;
+                    }
+                }
+            }
+        }
         if (tid == 0) {
             state->nTot = nTot0 + nTotWin;
             wp->valid = redo ? 2 : 0;
@@ -2430,7 +2625,7 @@ extern "C" __global__ __launch_bounds__(WV_P) void WV_SYM(cpecan_k_wv_expect)(
 }
 #endif
 
-#if !defined(WV_VANILLA)
+#if !defined(WV_VANILLA) && !defined(WV_FUSED)
 /*
  * Baum-Welch expectations of the traceback window the backward kernel just swept
  * (diagonalCalculation_Expectations :841-863 with cell_signal_updateTransAndKmerSkipExpectations :426-443).
@@ -2607,13 +2802,13 @@ extern "C" __global__ __launch_bounds__(WV_P) void WV_SYM(cpecan_k_wv_expect)(
 static dim3 wv_sweep_grid(const SweepArgs &a) { return dim3((unsigned) ((a.nItems + WV_WPB - 1) / WV_WPB)); }
 static int wv_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 /* const auto var = the build's kernel k, or k_sw for a batch with the switch (a.withSwitch); where the build has no k_sw
- * (the fused builds have none, and the vanilla machine has no gap Y -> gap X transition for an E-step to count), such a
- * batch ends the launcher with -1 before anything is launched */
+ * (the vanilla machine's fused builds have none, and that machine has no gap Y -> gap X transition for an E-step to
+ * count), such a batch ends the launcher with -1 before anything is launched */
 #define WV_KERNEL_SW(var, k) const auto var = a.withSwitch ? WV_SYM(k##_sw) : WV_SYM(k)
 #define WV_KERNEL_NO_SW(var, k)                                                                                   \
     if (a.withSwitch) return -1;                                                                                  \
     const auto var = WV_SYM(k)
-#ifdef WV_FUSED
+#if defined(WV_FUSED) && !defined(WV_HDP_FUSED)
 #define WV_KERNEL WV_KERNEL_NO_SW
 #else
 #define WV_KERNEL WV_KERNEL_SW
@@ -2630,11 +2825,17 @@ static void wv_sweep_back(decltype(&WV_SYM(cpecan_k_wv_backward)) k, hipStream_t
                        a.scratch, a.scratchBytes, a.Bring, window);
 }
 #endif
-/* the window's totals and decode -- or, fused, its totals and the sums into expect[] (no pairs) */
+/* the window's totals and decode -- or, fused, its totals and the sums into expect[] (no pairs, but for the HDP
+ * machine's fused builds: its assignments) */
+#ifdef WV_HDP_FUSED
+#define WV_POST_PAIRS(p) p
+#else
+#define WV_POST_PAIRS(p) (fused ? nullptr : p)
+#endif
 static void wv_post(hipStream_t stream, const SweepArgs &a, int window, bool fused) {
     hipLaunchKernelGGL(WV_SYM(cpecan_k_wv_post), dim3((unsigned) a.nItems), dim3(256), 0, stream, a.items, a.nItems, a.P,
                        a.bandTab, a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states,
-                       fused ? nullptr : a.pairs, fused ? nullptr : a.pairLogp, a.totXay, a.totVal, a.scratch,
+                       WV_POST_PAIRS(a.pairs), WV_POST_PAIRS(a.pairLogp), a.totXay, a.totVal, a.scratch,
                        a.scratchBytes, window, fused ? 1 : 0, fused ? a.expect : nullptr, fused ? a.kidx : nullptr);
 }
 static int wv_launch_forward(hipStream_t stream, const SweepArgs &a, int window) {
@@ -2681,9 +2882,15 @@ static int wv_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
  * blockIdx.x. */
 static void wv_sweep_back_fx(decltype(&WV_SYM(cpecan_k_wv_backward_fx)) k, hipStream_t stream, const SweepArgs &a,
                              int window) {
+#ifdef WV_HDP_FUSED
+    hipLaunchKernelGGL(k, wv_sweep_grid(a), dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track,
+                       a.trackBase, a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, a.pairs, a.pairLogp,
+                       a.scratch, a.scratchBytes, a.expect, window);
+#else
     hipLaunchKernelGGL(k, wv_sweep_grid(a), dim3(64 * WV_WPB), 0, stream, a.items, a.nItems, a.P, a.bandTab, a.track,
                        a.trackBase, a.models, a.Fring, a.ringDoubles, a.ringD, (WvState *) a.states, a.scratch,
                        a.scratchBytes, a.expect, a.kidx, window);
+#endif
 }
 static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int window) {
     WV_KERNEL(backward_fx, cpecan_k_wv_backward_fx);
@@ -2721,8 +2928,13 @@ static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int win
 #endif
 /* scratch: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list], and after it,
  * in batches with fused expectations, the segments' sums (WvFx) */
-extern "C" const SweepBuild WV_SYM(cpecan_wave_build);
-const SweepBuild WV_SYM(cpecan_wave_build) = {
+#ifdef WV_HDP_FUSED
+#define WV_BUILD_SYM WV_SYM(cpecan_hdpfx_build) /* (a list of its own: the Makefile's WV_HDP_FUSED_BUILDS) */
+#else
+#define WV_BUILD_SYM WV_SYM(cpecan_wave_build)
+#endif
+extern "C" const SweepBuild WV_BUILD_SYM;
+const SweepBuild WV_BUILD_SYM = {
     WV_L, true, WV_MACHINE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
     wv_scratch_base_bytes, WV_FX(wv_fx_bytes),
     wv_launch_forward, WV_RING(wv_launch_backward), WV_FX(wv_launch_backward_fx), WV_RING(wv_launch_expect),

@@ -127,8 +127,8 @@ enum { SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA };
 
 /* One compiled build of the throughput kernels, defined next to them: cpecan_systolic_build<suffix> in
  * cpecan_kernel_systolic.hip, cpecan_wave_build<suffix> in cpecan_kernel_wave.hip, one per build of the Makefile's list
- * (SY_BUILDS, WV_BUILDS, and the unsuffixed four-wave build), and cpecan_systolicfx_build_vf<n> per build of
- * SY_FUSED_BUILDS */
+ * (SY_BUILDS, WV_BUILDS, and the unsuffixed four-wave build), cpecan_systolicfx_build_vf<n> per build of
+ * SY_FUSED_BUILDS and cpecan_hdpfx_build_hf<n> per build of WV_HDP_FUSED_BUILDS */
 struct SweepBuild {
     int rows;    /* waves per workgroup (workgroup family) or cells per lane (wave family) */
     bool wave;   /* one wave per alignment */
@@ -143,8 +143,9 @@ struct SweepBuild {
     SweepLaunch backward;    /* the sweep back of a window and what follows it (totals, decode, re-sweep) */
     SweepLaunch backward_fx; /* the E-step with the expectations summed inside the sweep back (null: none; the wave
                                 builds of the strawMan machine, and the workgroup family's _f and the vanilla machine's
-                                _vf builds, which have no other: their expect is null, and the _vf builds, which only a
-                                batch of expectations reaches, have no backward either) */
+                                _vf builds and the HDP machine's _hf builds, which have no other: their expect is null,
+                                and the _vf and _hf builds, which only a batch of expectations reaches, have no backward
+                                either) */
     SweepLaunch expect;      /* the E-step from the ring of backward cells */
     SweepLaunch post_asm;    /* what follows the assembly sweep back of a window (null: no assembly sweeps) */
 };

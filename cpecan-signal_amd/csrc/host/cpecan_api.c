@@ -921,7 +921,11 @@ static void batch_vanilla(cpecan_ctx *ctx, const Run *r, const cpecan_band_param
 static void batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     cpecan_band_params own = *bp;
     if (r->mode) own.threshold = ((HdpHmmExpectations *) r->hmmOut)->threshold; /* the assignment bar */
-    CHECK(cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r), batch));
+    /* CPECAN_HDP_FUSED_ESTEP=1, read per call: the E-step summed inside the sweep back on the wave kernels at two and three
+     * cells per lane (the flag means nothing to a batch it does not serve) */
+    const char *fusedEstep = getenv("CPECAN_HDP_FUSED_ESTEP");
+    const int32_t fused = r->mode && fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_HDP_FUSED_ESTEP : 0;
+    CHECK(cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | fused, batch));
 }
 static void batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     CHECK(cpecan_hip_batch_create_sm4(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch));

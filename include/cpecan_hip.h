@@ -460,6 +460,36 @@ typedef struct {
                                           vanilla batches of expectations when CPECAN_WIDE_BANDS_VANILLA_FUSED_ESTEP=1
                                           (the way in for vanillaAlign and cpecan_trainModels, beside
                                           CPECAN_WIDE_BANDS_VANILLA_ESTEP=1). */
+#define CPECAN_FLAG_HDP_FUSED_ESTEP 65536 /* cpecan_hip_batch_create_hdp with CPECAN_FLAG_EXPECTATIONS only: a batch of
+                                          the wave-per-alignment kernels at two or three cells per lane (a widest band
+                                          of at most 184 k-mers whose edges step by one k-mer per diagonal, no
+                                          CPECAN_FLAG_GENERAL_KERNEL; a narrow band that CPECAN_SYSTOLIC_ROWS=3 puts on
+                                          three cells included) sums its eight transition expectations and the
+                                          likelihood inside the sweep back, against the forward sweep's estimate of the
+                                          window's total, per segment of ten decoded diagonals
+                                          (cpecan_k_wv_backward_fx_hf2 / _hf3, on the build of as many cells per lane as
+                                          the batch would run on without the flag): no ring of backward cells, no
+                                          expectation kernel.  The sweep parks every transition into match whose
+                                          exponent lies within 0.25 of the threshold against the estimate; the post
+                                          kernel scales a segment's sums by exp(estimate - total) and selects the
+                                          assignments from that list with the exact total, so the triples and their
+                                          exponents are the ring path's bit for bit, and the sums agree with it to
+                                          rounding (they are added in another order).  A window with a total that is not
+                                          finite or lies more than 0.25 from the estimate, whose list overflowed, or of
+                                          a batch whose threshold has no logarithm, is swept once more against the exact
+                                          totals, sums and assignments both (CPECAN_EXPECT_RESWEEP=1 / 2 forces that for
+                                          every / every other window: tests).  cpecan_hip_batch_expectation_pass reports
+                                          1, cpecan_hip_plan_expectation_pass answers beforehand; the kernel, family,
+                                          rows and widest band cpecan_hip_plan_dispatch names do not change.  These
+                                          builds have no other form of the E-step: CPECAN_EXPECT_FUSED=0 does not undo
+                                          the flag.  Every other batch ignores it: a posterior batch, another machine,
+                                          an HDP E-step at four cells per lane (bands of 185..248 k-mers: _h4 keeps its
+                                          ring), on the _he6 / _he8 workgroup builds (CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP,
+                                          249..504 k-mers) or on the general kernel.  Opt-in: an HDP batch of
+                                          expectations without the flag keeps the ring.  No environment variable of the
+                                          C-ABI sets it; libcpecan_host.so sets it for its HDP batches of expectations
+                                          when CPECAN_HDP_FUSED_ESTEP=1 (the way in for
+                                          cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels and vanillaAlign). */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
