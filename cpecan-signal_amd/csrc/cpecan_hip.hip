@@ -40,8 +40,9 @@ extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
  * vanilla E-step (_ve; without it that E-step stays on the general kernel), CPECAN_FLAG_WIDE_BANDS_HDP for the HDP
  * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f of the
  * workgroup family, _vf of the wave family, the vanilla machine's _vf4 / _vf6 / _vf8 of the workgroup family, the
- * Makefile's SY_FUSED_BUILDS, and the HDP machine's _hf2 / _hf3 of the wave family, its WV_HDP_FUSED_BUILDS: the E-step
- * summed inside the sweep back, and no other form of it) are in no
+ * Makefile's SY_FUSED_BUILDS, and the HDP machine's _hf2 / _hf3 of the wave family, its WV_HDP_FUSED_BUILDS, and _hf6 /
+ * _hf8 of the workgroup family, its SY_HDP_FUSED_BUILDS: the E-step summed inside the sweep back, and no other form of
+ * it) are in no
  * table here: each stands in for the build of as many rows that the rules above come to, as the last step of
  * choose_dispatch and for a batch of expectations alone (FUSED_STAND_INS, which also says what asks for each). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
@@ -59,6 +60,7 @@ SWEEP_BUILD(cpecan_systolic_build_ve4) SWEEP_BUILD(cpecan_systolic_build_ve6) SW
 SWEEP_BUILD(cpecan_systolic_build_f1) SWEEP_BUILD(cpecan_systolic_build_f2) SWEEP_BUILD(cpecan_systolic_build_f3)
 SWEEP_BUILD(cpecan_systolic_build_f4) SWEEP_BUILD(cpecan_systolic_build_f6) SWEEP_BUILD(cpecan_systolic_build_f8)
 SWEEP_BUILD(cpecan_systolicfx_build_vf4) SWEEP_BUILD(cpecan_systolicfx_build_vf6) SWEEP_BUILD(cpecan_systolicfx_build_vf8)
+SWEEP_BUILD(cpecan_hdpwfx_build_hf6) SWEEP_BUILD(cpecan_hdpwfx_build_hf8)
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
 /* (a table of wide builds ends with a null entry) */
@@ -225,7 +227,8 @@ struct Dispatch {
  * such a batch runs what it runs without it; the _h2 / _h3 wave builds are the HDP machine's, and its four-cell build
  * _h4 (bands of 185..248 k-mers) has no fused stand-in: it keeps its ring.  A vanilla batch on the _ve workgroup builds (reached with
  * CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP alone) keeps its build under the wave builds' flag and leaves it for _vf4 / _vf6 /
- * _vf8 under one of its own. */
+ * _vf8 under one of its own; an HDP batch on the _he workgroup builds (reached with CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP alone)
+ * likewise keeps its build under the wave builds' flag and leaves it for _hf6 / _hf8 under one of its own. */
 static const struct FusedStandIn {
     const SweepBuild *ring, *fused;
     int flag;
@@ -244,6 +247,8 @@ static const struct FusedStandIn {
     { &cpecan_systolic_build_ve4, &cpecan_systolicfx_build_vf4, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
     { &cpecan_systolic_build_ve6, &cpecan_systolicfx_build_vf6, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
     { &cpecan_systolic_build_ve8, &cpecan_systolicfx_build_vf8, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_he6, &cpecan_hdpwfx_build_hf6, CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_he8, &cpecan_hdpwfx_build_hf8, CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP, nullptr },
 };
 #define CP_WAVE5_MAX_WIDTH 192 /* cells: one to three per lane */
 static Dispatch choose_dispatch(const DispatchQuery &q) {

@@ -93,8 +93,24 @@
  * are formed by the receiver: the same doubles) and keeps (column, beta, alpha) per slot and refresh segment, in
  * registers: no ring of backward cells, no expectation kernel.  The estimate, the segments' scaling, the second sweep
  * and DevParams::expectResweep are the strawMan fused builds' (above); fx_finish adds through 60 bins in LDS. */
-#if defined(SY_FUSED) && (defined(SY_HDP) || defined(SY_ESTEP))
-#error "SY_FUSED: a build of the strawMan machine or, with SY_VANILLA alone, of the vanilla machine"
+/* -DSY_HDP -DSY_FUSED: the HDP machine's E-step with its expectations summed inside the sweep back, with six and eight
+ * waves per workgroup (the bands of _he6 / _he8), in objects of their own that the Makefile keeps on a list of their own
+ * (SY_HDP_FUSED_BUILDS: symbols suffixed _hf6, _hf8, the record cpecan_hdpwfx_build_hf<n>; the _he objects keep their
+ * device code).  The forward sweep is the _he builds'.  The sums are the strawMan fused builds' without the k-mer bins
+ * (no g, no c records: SY_FX_G 0), into the model's nine transitions and its likelihood.  The machine's event-to-k-mer
+ * assignments (cpecan_k_sy_expect, HDP form) come from the same sweep: in the middle block it parks the target cell, the
+ * from-state and the exponent s before the total is subtracted, wherever s lies within SY_CAND_SLACK of the threshold
+ * against the estimate, in the candidate lists the posterior builds keep in the window scratch; after phase T a
+ * selection phase takes e = s - total of the target diagonal's segment and appends where exp(e) reaches the threshold --
+ * the subtraction is the last operation of the ring path's expression, so triples and exponents are its bit for bit.
+ * One redo rule for sums and assignments: a window with a total that is not finite or more than SY_CAND_SLACK from the
+ * estimate, with a list that overflowed, of a batch whose threshold has no logarithm, or that DevParams::expectResweep
+ * names is swept once more against the exact totals, and that sweep emits the assignments in its loop. */
+#if defined(SY_FUSED) && defined(SY_HDP) && !defined(SY_ESTEP) && !defined(SY_VANILLA)
+#define SY_HDP_FUSED
+#endif
+#if defined(SY_FUSED) && defined(SY_ESTEP)
+#error "SY_FUSED: a build of the strawMan machine or, with SY_VANILLA or SY_HDP alone, of that machine"
 #elif defined(SY_HDP) && defined(SY_VANILLA)
 #error "SY_HDP and SY_VANILLA are builds of their own"
 #elif defined(SY_ESTEP) && !defined(SY_HDP) && !defined(SY_VANILLA)
@@ -111,6 +127,8 @@
 /* a symbol's suffix: the machine's tag and the number of waves; the strawMan's four-wave build alone has none */
 #if defined(SY_FUSED) && defined(SY_VANILLA)
 #define SY_SYM(n) SWEEP_SYM(n, vf, SY_R)
+#elif defined(SY_HDP_FUSED)
+#define SY_SYM(n) SWEEP_SYM(n, hf, SY_R)
 #elif defined(SY_FUSED)
 #define SY_SYM(n) SWEEP_SYM(n, f, SY_R)
 #elif defined(SY_ESTEP) && defined(SY_VANILLA)
@@ -134,7 +152,11 @@
 #define SY_BACKWARD_ATTR
 #elif defined(SY_FUSED) && SY_R == 6 && !defined(SY_FX_REG_SUMS)
 /* the six-wave fused sweep back with its eight sums in LDS (SY_FX_LDS below) fits three waves per SIMD without a spill (165
- * VGPRs): two six-wave workgroups share a CU, as on _r6.  Left alone it takes 173, and 179 with the sums in registers */
+ * VGPRs): two six-wave workgroups share a CU, as on _r6.  Left alone it takes 173, and 179 with the sums in registers.
+ * The HDP machine's _hf6 keeps both, the sums in LDS and the three waves: 164 VGPRs, no spill, 33136 bytes of static LDS
+ * (two workgroups: 66 KB of the CU's 160), against 178 with the sums in registers and no occupancy forced -- one
+ * workgroup to a CU where _he6 (119) has two.  _hf8 lands on 178 by itself (below), as _f8 on 179: two waves per SIMD,
+ * one eight-wave workgroup to a CU; its static LDS is _he8's, 10896 bytes. */
 #define SY_BACKWARD_ATTR __attribute__((amdgpu_waves_per_eu(3, 3)))
 #elif defined(SY_FUSED) /* nor do the fused sweep's accumulators and wider fetch buffers: no occupancy is forced */
 #define SY_BACKWARD_ATTR
@@ -177,7 +199,7 @@
 #define SY_MODEL_DOUBLES ((long long) (sizeof(DevHdpModel) / sizeof(double)))
 #define SY_MACHINE_ID SWEEP_HDP
 #define SY_MACHINE cpecan_systolic_machine_hdp
-#ifdef SY_ESTEP
+#if defined(SY_ESTEP) || defined(SY_FUSED)
 #define SY_MODE(P) 1 /* E-step only */
 #else
 #define SY_MODE(P) 0 /* posterior decode only */
@@ -294,12 +316,12 @@ struct Shared {
     int cnt[2][SY_R][2];     /* aligned-pair counts per wave, double-buffered */
     int item;
     int scan;                /* this window's posteriors must be decoded by the full scan */
-#if defined(SY_FUSED) && !defined(SY_VANILLA)
+#if defined(SY_FUSED) && !defined(SY_VANILLA) && !defined(SY_HDP)
     int fxRedo;              /* this window's sums must be taken again, against the exact totals */
 #define SY_FX_REDO(sh) (sh).fxRedo
 #elif defined(SY_FUSED)
-/* (the vanilla fused builds keep the forward sweep's LDS that of the _ve builds: the flag lives in the decode's first
- * pair count, which no E-step build reads or writes) */
+/* (the vanilla and the HDP fused builds keep the forward sweep's LDS that of the _ve / _he builds: the flag lives in the
+ * decode's first pair count, which no E-step build reads or writes) */
 #define SY_FX_REDO(sh) (sh).cnt[0][0][0]
 #endif
 };
@@ -983,13 +1005,16 @@ struct FxRecords {
 #ifdef SY_VANILLA
 #define SY_FX_TR 0 /* doubles per wave and segment of tr, per record of g */
 #define SY_FX_G 2
+#elif defined(SY_HDP)
+#define SY_FX_TR 8
+#define SY_FX_G 0 /* the HDP machine collects no gap-X sums per k-mer: no g and no c */
 #else
 #define SY_FX_TR 8
 #define SY_FX_G 1
 #endif
 static __host__ __device__ long long sy_fx_bytes(int ringD) {
     return ((long long) ringD / 10 + 8)
-           * (SY_R * SY_FX_TR * sizeof(double) + 2 * SY_P * (SY_FX_G * sizeof(double) + sizeof(int)));
+           * (SY_R * SY_FX_TR * sizeof(double) + 2 * SY_P * (SY_FX_G ? SY_FX_G * sizeof(double) + sizeof(int) : 0));
 }
 __device__ __forceinline__ FxRecords fx_records(char *base, int ringD) {
     const long long nW = (long long) ringD / 10 + 8;
@@ -1055,6 +1080,13 @@ __device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal
 #else
 /* M>X X>X Y>X | M>M X>M Y>M | M>Y Y>Y into the model's nine transition sums (from * 3 + to) */
 #define SY_EXPECT_SLOTS { 0 * 3 + 1, 1 * 3 + 1, 2 * 3 + 1, 0 * 3 + 0, 1 * 3 + 0, 2 * 3 + 0, 0 * 3 + 2, 2 * 3 + 2 }
+#ifdef SY_HDP
+#define SY_FX_LIK 9 /* the likelihood follows the nine transitions */
+#define SY_FX_LEN (9 + 1) /* CPECAN_EXPECTATIONH_LEN doubles per model */
+#else
+#define SY_FX_LIK (9 + 4096) /* ... the 4096 k-mer bins */
+#define SY_FX_LEN (9 + 4096 + 1)
+#endif
 
 /* A window's fused sums into the model's expectations (layout of cpecan_k_sy_expect's); the whole workgroup.  Segment
  * k's sums were taken against the estimate and scale by exp(est - total_k), or, on the second sweep (exact), against
@@ -1063,8 +1095,7 @@ __device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal
 __device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal *wtot, const int nSeg, const int tPost0,
                           const int to, const double est, const bool exact, double *expect,
                           const unsigned short *__restrict__ kidx) {
-    double *dst = expect + (long long) it.model * (9 + 4096 + 1);
-    const unsigned short *kx = kidx + it.xOff;
+    double *dst = expect + (long long) it.model * SY_FX_LEN;
     const int slot[8] = SY_EXPECT_SLOTS;
     const int tid = threadIdx.x;
     if (tid < 8) {
@@ -1080,8 +1111,12 @@ __device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal
         double lik = 0.0;
 #pragma unroll 1
         for (int u = tPost0; u > to; u--) lik += wtot[(tPost0 - u) / 10].total;
-        atomicAdd(dst + 9 + 4096, lik);
+        atomicAdd(dst + SY_FX_LIK, lik);
     }
+#ifdef SY_HDP /* (no k-mer bins) */
+    (void) kidx;
+#else
+    const unsigned short *kx = kidx + it.xOff;
     int cur = -1;
     double sum = 0.0;
 #pragma unroll 1
@@ -1102,6 +1137,7 @@ __device__ void fx_finish(const DevItem &it, const FxRecords &fx, const WinTotal
         }
     }
     if (cur > 0 && kx[cur - 1] < 4096) atomicAdd(dst + 9 + kx[cur - 1], sum);
+#endif
 }
 #endif /* SY_VANILLA */
 #endif /* SY_FUSED */
@@ -1132,6 +1168,9 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                                 const bool fxForce
 #ifdef SY_FX_LDS
                                 , double *fxAcc
+#endif
+#ifdef SY_HDP_FUSED
+                                , const int fxWindow
 #endif
 #endif
                                 ) {
@@ -1365,10 +1404,14 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
 #endif
 #pragma unroll
         for (int i = 0; i < 8; i++) SY_EA(i) = 0.0;
-        double gSum = 0.0, refX = exact ? uni_d(ld_agent(&wtot[0].total)) : 0.0;
-        int gCol = -1, segAcc = 0;
+        double refX = exact ? uni_d(ld_agent(&wtot[0].total)) : 0.0;
+        int segAcc = 0;
+#ifndef SY_HDP /* (the HDP machine collects no gap-X sums per k-mer: no g, no c) */
+        double gSum = 0.0;
+        int gCol = -1;
         const int fxSlot = wave * 64 + lane;
         fxo.c[fxSlot] = -1; /* segment 0 has no A record yet */
+#endif
         auto fx_flush = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
@@ -1378,10 +1421,12 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 if (lane == 0) fxo.tr[(segAcc * SY_R + wave) * 8 + i] = v;
                 SY_EA(i) = 0.0;
             }
+#ifndef SY_HDP
             fxo.g[(segAcc * 2 + 1) * SY_P + fxSlot] = gSum;
             fxo.c[(segAcc * 2 + 1) * SY_P + fxSlot] = gCol;
             fxo.c[(segAcc * 2 + 2) * SY_P + fxSlot] = -1; /* the next segment's A record */
             gSum = 0.0;
+#endif
             segAcc++;
             if (exact) refX = uni_d(ld_agent(&wtot[segAcc].total));
         };
@@ -1399,6 +1444,61 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 const double ref = exact ? refX : totEst;
                 const bool nf = exact && !(ref > CP_NEG_INF);
                 if (on) {
+#ifdef SY_HDP_FUSED
+                    /* The HDP machine's assignments (cell_signal_updateTransAndKmerSkipExpectations2 :445-476): a transition
+                     * into match whose own posterior exp(s - total) reaches the threshold leaves as (from-state + 4 *
+                     * window, x - 1, y - 1) of the cell it goes TO, (t+2, x+1), with its exponent.  s: the three exponents
+                     * before the total is subtracted.  The first sweep parks (diagonal, from-state, column) and s where s
+                     * lies within SY_CAND_SLACK of the threshold against the estimate -- a cell or a neighbour outside the
+                     * band has s = -inf -- and the selection after phase T, which has the exact totals, takes s - total: the
+                     * last operation of the ring path's expression, so its exponents bit for bit.  The second sweep has
+                     * the totals and the band of t+2: it emits here, for the cells the reference visits, as
+                     * cpecan_k_sy_expect does. */
+                    const double s3 = fM + mB + (mP + T[T_MATCH_CONTINUE]), s4 = fX + mB + (mP + T[T_MATCH_FROM_GAP_X]),
+                                 s5 = fY + mB + (mP + T[T_MATCH_FROM_GAP_Y]);
+                    const double e3 = s3 - ref, e4 = s4 - ref, e5 = s5 - ref;
+                    /* (skipping the three calls for a wave whose every exponent is below SY_FX_ZERO, as the vanilla fused
+                     * sweep does, was measured and costs more than it saves: this machine's posteriors are flat) */
+                    double p3 = exp(e3), p4 = exp(e4), p5 = exp(e5);
+                    if (exact) {
+                        int cMin, cMax;
+                        band_load(bandTab, t + 2, cMin, cMax);
+                        const bool ok = in && x + 1 >= cMin && x + 1 <= cMax;
+                        const double ee[3] = { e3, e4, e5 }, qq[3] = { p3, p4, p5 };
+#pragma unroll
+                        for (int f = 0; f < 3; f++)
+                            if (ok && qq[f] >= P.threshold) {
+                                const long long at = (long long) atomicAdd((unsigned long long *) &state->nPairs, 1ull);
+                                if (at < out.pairCap) {
+                                    long long *o = out.pairs + at * 3;
+                                    o[0] = f + 4ll * fxWindow;
+                                    o[1] = x;     /* (x + 1) - 1 */
+                                    o[2] = t - x; /* ((t + 2) - (x + 1)) - 1 */
+                                    out.logp[at] = ee[f];
+                                }
+                            }
+                        if (nf) {
+                            p3 = ok ? p3 : 0.0;
+                            p4 = ok ? p4 : 0.0;
+                            p5 = ok ? p5 : 0.0;
+                        }
+                    } else {
+                        const double ss[3] = { s3, s4, s5 };
+#pragma unroll
+                        for (int f = 0; f < 3; f++) {
+                            const bool hit = ss[f] >= candThr;
+                            const unsigned long long hm = __ballot(hit);
+                            if (hm != 0ull) {
+                                const int ci = nCand + __popcll(hm & ((1ull << lane) - 1ull));
+                                if (hit && ci < candCap) { /* (writes stop at the capacity, the count goes on) */
+                                    myKx[ci] = make_int2((tPost0 - (t + 2)) * 4 + f, x + 1);
+                                    myFb[ci] = ss[f];
+                                }
+                                nCand += __popcll(hm);
+                            }
+                        }
+                    }
+#else
                     double p3 = exp(fM + mB + (mP + T[T_MATCH_CONTINUE]) - ref);
                     double p4 = exp(fX + mB + (mP + T[T_MATCH_FROM_GAP_X]) - ref);
                     double p5 = exp(fY + mB + (mP + T[T_MATCH_FROM_GAP_Y]) - ref);
@@ -1410,6 +1510,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                         p4 = ok ? p4 : 0.0;
                         p5 = ok ? p5 : 0.0;
                     }
+#endif
                     SY_EA(3) += p3;
                     SY_EA(4) += p4;
                     SY_EA(5) += p5;
@@ -1436,6 +1537,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 SY_EA(0) += p0;
                 SY_EA(1) += p1;
                 if (hasSwitchX || nf) SY_EA(2) += p2;
+#ifndef SY_HDP
                 if (inL && x + 1 != gCol) { /* the slot points at another column than before */
                     if (gSum != 0.0) {
                         fxo.g[(segAcc * 2) * SY_P + fxSlot] = gSum;
@@ -1447,6 +1549,7 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
                 gSum += p0;
                 gSum += p1;
                 if (hasSwitchX || nf) gSum += p2;
+#endif
                 SY_EA(6) += p6;
                 SY_EA(7) += p7;
             }
@@ -1745,6 +1848,12 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
         if (!exact) sh.item = nTotWin;
     };
     sweep(false);
+#ifdef SY_HDP_FUSED
+    /* a wave's count of parked assignments, for the selection; a list that overflowed sends the window down the
+     * second sweep */
+    if (lane == 0) sh.cnt[1][wave][0] = nCand;
+    if (nCand > candCap) SY_FX_REDO(sh) = 1;
+#endif
 #else
         sh.item = nTotWin;
         if (lane == 0) sh.cnt[1][wave][0] = nCand;
@@ -1785,7 +1894,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
             if (w.second) tot = ladd(acc, sh.vbuf[threadIdx.x + 1], cf);
             wtot[k >> 1].total = tot;
             if (!(fabs(tot - totEst) <= SY_CAND_SLACK)) sh.scan = 1; /* also catches NaN and infinities */
-#ifdef SY_FUSED
+#ifdef SY_HDP_FUSED
+            /* (the parked assignments are complete only where every total lies within SY_CAND_SLACK of the estimate: one
+             * redo rule for sums and assignments) */
+            if (!(fabs(tot - totEst) <= SY_CAND_SLACK)) SY_FX_REDO(sh) = 1;
+#elif defined(SY_FUSED)
             if (!(fabs(tot - totEst) <= SY_FX_EST_BOUND)) SY_FX_REDO(sh) = 1;
 #endif
             const long long o = out.nTot + (k >> 1);
@@ -1801,7 +1914,11 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
     /* the window's sums into the model's: scaled from the estimate, or taken once more against the exact totals where
      * the estimate is not finite or lies more than SY_FX_EST_BOUND from one of them (or the caller forces it) */
     if (nPost > 0) {
+#ifdef SY_HDP_FUSED
+        const bool redo = SY_FX_REDO(sh) != 0 || sh.scan != 0; /* (scan: a threshold without a logarithm, a total astray) */
+#else
         const bool redo = SY_FX_REDO(sh) != 0;
+#endif
         if (redo) {
             sweep(true);
             __syncthreads();
@@ -1811,6 +1928,30 @@ __device__ void backward_window(const DevItem &it, const DevParams &P, const int
         (void) kidx;
 #else
         fx_finish(it, fxo, wtot, nTotWin, tPost0, tracedBackTo, totEst, redo, expect, kidx);
+#endif
+#ifdef SY_HDP_FUSED
+        /* the selection: every wave walks its own list of parked assignments; one leaves where exp(s - total) reaches the
+         * threshold, the test and the record of cpecan_k_sy_expect (HDP form), in whatever order the lanes get there (the
+         * host restores the reference's at fetch).  A window that went down the second sweep has emitted there. */
+        if (!redo) {
+            const int nC = sh.cnt[1][wave][0];
+#pragma unroll 1
+            for (int i = lane; i < nC; i += 64) {
+                const int2 kx = myKx[i];
+                const int k = kx.x >> 2, f = kx.x & 3, x = kx.y, t = tPost0 - k;
+                const double e = myFb[i] - wtot[k / 10].total;
+                if (exp(e) >= P.threshold) {
+                    const long long at = (long long) atomicAdd((unsigned long long *) &state->nPairs, 1ull);
+                    if (at < out.pairCap) {
+                        long long *o = out.pairs + at * 3;
+                        o[0] = f + 4ll * fxWindow;
+                        o[1] = x - 1;
+                        o[2] = (t - x) - 1;
+                        out.logp[at] = e;
+                    }
+                }
+            }
+        }
 #endif
     }
 #endif
@@ -2161,10 +2302,15 @@ extern "C" __global__ __launch_bounds__(SY_P) SY_BACKWARD_ATTR void SY_SYM(cpeca
 #ifdef SY_FX_LDS
                     , fxAcc
 #endif
+#ifdef SY_HDP_FUSED
+                    , window
+#endif
 #endif
                     );
     if (threadIdx.x == 0) {
+#ifndef SY_HDP_FUSED /* (the assignments were counted in place, as cpecan_k_sy_expect counts them) */
         state->nPairs = out.nPairs;
+#endif
         state->nTot = out.nTot;
         state->winValid = 0;
         state->expectPending = SY_MODE(P) != 0 && !SY_FX ? window + 1 : 0; /* which launch's window the B ring holds */
@@ -2490,6 +2636,8 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 /* (the vanilla _vf builds, which are not among the Makefile's SY_BUILDS, have a record name of their own) */
 #if defined(SY_FUSED) && defined(SY_VANILLA)
 #define SY_BUILD_SYM SY_SYM(cpecan_systolicfx_build)
+#elif defined(SY_HDP_FUSED) /* (nor are the HDP _hf builds: the Makefile's SY_HDP_FUSED_BUILDS) */
+#define SY_BUILD_SYM SY_SYM(cpecan_hdpwfx_build)
 #else
 #define SY_BUILD_SYM SY_SYM(cpecan_systolic_build)
 #endif

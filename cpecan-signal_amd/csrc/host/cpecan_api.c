@@ -924,7 +924,11 @@ static void batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *b
     /* CPECAN_HDP_FUSED_ESTEP=1, read per call: the E-step summed inside the sweep back on the wave kernels at two and three
      * cells per lane (the flag means nothing to a batch it does not serve) */
     const char *fusedEstep = getenv("CPECAN_HDP_FUSED_ESTEP");
-    const int32_t fused = r->mode && fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_HDP_FUSED_ESTEP : 0;
+    /* ... and CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP=1 the same on the workgroup kernels at six and eight waves, for a batch
+     * that CPECAN_WIDE_BANDS_HDP_ESTEP=1 puts there (bands of 249..504 k-mers) */
+    const char *fusedWide = getenv("CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP");
+    const int32_t fused = (r->mode && fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_HDP_FUSED_ESTEP : 0) |
+                          (r->mode && fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP : 0);
     CHECK(cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | fused, batch));
 }
 static void batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {

@@ -490,6 +490,42 @@ typedef struct {
                                           C-ABI sets it; libcpecan_host.so sets it for its HDP batches of expectations
                                           when CPECAN_HDP_FUSED_ESTEP=1 (the way in for
                                           cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels and vanillaAlign). */
+#define CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP 131072 /* cpecan_hip_batch_create_hdp with CPECAN_FLAG_EXPECTATIONS only:
+                                          a batch that CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP (or
+                                          CPECAN_WIDE_BANDS_HDP_ESTEP=1) puts on the _he6 / _he8 workgroup builds -- a
+                                          widest band of 249..504 k-mers whose edges step by one k-mer per diagonal, no
+                                          CPECAN_FLAG_GENERAL_KERNEL -- sums its eight transition expectations and the
+                                          likelihood inside the sweep back instead (cpecan_k_sy_backward_hf6 / _hf8, the
+                                          build of as many waves per workgroup), as CPECAN_FLAG_HDP_FUSED_ESTEP does on
+                                          the wave kernels: against the sweep's estimate of the window's total, per
+                                          segment of ten decoded diagonals, scaled by exp(estimate - total) after the
+                                          totals, in the same launch; no ring of backward cells, no expectation kernel.
+                                          The sweep parks every transition into match whose exponent lies within 0.25 of
+                                          the threshold against the estimate, and a selection phase of the same launch
+                                          takes the assignments from that list with the exact total, so the triples and
+                                          their exponents are the ring path's bit for bit, and the sums agree with it to
+                                          rounding (they are added in another order).  A window with a total that is not
+                                          finite or lies more than 0.25 from the estimate, whose list overflowed, or of
+                                          a batch whose threshold has no logarithm, is swept back once more in that
+                                          launch against the exact totals, sums and assignments both
+                                          (CPECAN_EXPECT_RESWEEP=1 / 2 forces that for every / every other window:
+                                          tests).  cpecan_hip_batch_expectation_pass reports 1,
+                                          cpecan_hip_plan_expectation_pass answers beforehand; the kernel, family, rows
+                                          and widest band cpecan_hip_plan_dispatch names do not change.  These builds
+                                          have no other form of the E-step: CPECAN_EXPECT_FUSED=0 does not undo the
+                                          flag.  Every other batch ignores it: a posterior batch, another machine, a
+                                          band of at most 248 k-mers (the wave kernels, where
+                                          CPECAN_FLAG_HDP_FUSED_ESTEP rules up to 184) or past 504, the general kernel,
+                                          a batch without the wide-bands flag of the E-step.  A number of its own
+                                          because 65536 is pinned as meaning nothing to a batch on the _he builds, and
+                                          keeps meaning nothing there.  Opt-in.  As measured (1024 reads of 2 000
+                                          k-mers, threshold 0.05): a gain at both widths, 1.10 x the ring path at six
+                                          waves (widest band 321: 52.9 against 58.0 ms) and 1.10 x at eight (441: 61.8
+                                          against 68.0 ms; 1.13 x in another run).  No environment variable of the C-ABI
+                                          sets it; libcpecan_host.so sets it for its HDP batches of expectations when
+                                          CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP=1 (the way in for
+                                          cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels and vanillaAlign,
+                                          beside CPECAN_WIDE_BANDS_HDP_ESTEP=1). */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
