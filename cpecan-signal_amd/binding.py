@@ -43,6 +43,7 @@ FLAG_VANILLA_FUSED_ESTEP = 16384
 FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP = 32768
 FLAG_HDP_FUSED_ESTEP = 65536
 FLAG_WIDE_BANDS_HDP_FUSED_ESTEP = 131072
+FLAG_HDP_FOUR_CELLS_FUSED_ESTEP = 262144
 MACHINE_STRAWMAN, MACHINE_DNA5, MACHINE_VANILLA, MACHINE_HDP, MACHINE_SM4, MACHINE_ECHELON = range(6)
 NUM_KMERS = 4096
 MODEL_TABLE_LEN = 1 + NUM_KMERS * 5

@@ -927,8 +927,11 @@ static void batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *b
     /* ... and CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP=1 the same on the workgroup kernels at six and eight waves, for a batch
      * that CPECAN_WIDE_BANDS_HDP_ESTEP=1 puts there (bands of 249..504 k-mers) */
     const char *fusedWide = getenv("CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP");
+    /* ... and CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP=1 on the wave kernels at four cells per lane (bands of 185..248 k-mers) */
+    const char *fusedFour = getenv("CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP");
     const int32_t fused = (r->mode && fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_HDP_FUSED_ESTEP : 0) |
-                          (r->mode && fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP : 0);
+                          (r->mode && fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP : 0) |
+                          (r->mode && fusedFour && atoi(fusedFour) == 1 ? CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP : 0);
     CHECK(cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | fused, batch));
 }
 static void batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {

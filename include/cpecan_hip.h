@@ -484,7 +484,7 @@ typedef struct {
                                           builds have no other form of the E-step: CPECAN_EXPECT_FUSED=0 does not undo
                                           the flag.  Every other batch ignores it: a posterior batch, another machine,
                                           an HDP E-step at four cells per lane (bands of 185..248 k-mers: _h4 keeps its
-                                          ring), on the _he6 / _he8 workgroup builds (CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP,
+                                          ring under this flag; CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP serves it), on the _he6 / _he8 workgroup builds (CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP,
                                           249..504 k-mers) or on the general kernel.  Opt-in: an HDP batch of
                                           expectations without the flag keeps the ring.  No environment variable of the
                                           C-ABI sets it; libcpecan_host.so sets it for its HDP batches of expectations
@@ -526,6 +526,43 @@ typedef struct {
                                           CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP=1 (the way in for
                                           cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels and vanillaAlign,
                                           beside CPECAN_WIDE_BANDS_HDP_ESTEP=1). */
+#define CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP 262144 /* cpecan_hip_batch_create_hdp with CPECAN_FLAG_EXPECTATIONS only:
+                                          a batch of the wave-per-alignment kernels at four cells per lane (a widest
+                                          band of 185..248 k-mers whose edges step by one k-mer per diagonal, no
+                                          CPECAN_FLAG_GENERAL_KERNEL; a narrower band that CPECAN_SYSTOLIC_ROWS=4 puts
+                                          on four cells included) sums its eight transition expectations and the
+                                          likelihood inside the sweep back and selects its assignments from the list
+                                          the sweep parks, as CPECAN_FLAG_HDP_FUSED_ESTEP does at two and three cells:
+                                          cpecan_k_wv_backward_fx_hf4 in place of _h4's sweep back and expectation
+                                          kernel, cpecan_k_wv_post_hf4 for the totals, the scaling by
+                                          exp(estimate - total) and the selection with the exact totals, no ring of
+                                          backward cells.  Triples and exponents are the ring path's bit for bit, the
+                                          sums agree with it to rounding.  A window with a total that is not finite or
+                                          lies more than 0.25 from the estimate, whose list overflowed (4 records per
+                                          ring diagonal and layer), or of a batch whose threshold has no logarithm, is
+                                          swept once more against the exact totals, by cpecan_k_wv_resweep_fx_hf4;
+                                          CPECAN_EXPECT_RESWEEP=1 / 2 forces that for every / every other window, for
+                                          tests.  cpecan_hip_batch_expectation_pass reports 1,
+                                          cpecan_hip_plan_expectation_pass answers beforehand; the kernel, family, rows
+                                          (4) and widest band (248) cpecan_hip_plan_dispatch names do not change.  The
+                                          build has no other form of the E-step: CPECAN_EXPECT_FUSED=0 does not undo the
+                                          flag.  Every other batch ignores it: a posterior batch, another machine, an
+                                          HDP E-step at two or three cells per lane (bands up to 184 k-mers, where
+                                          CPECAN_FLAG_HDP_FUSED_ESTEP rules; a batch may carry both and is then fused at
+                                          two, three and four cells), on the _he / _hf workgroup builds, a band past
+                                          248 k-mers or with edges that step by more than one, the general kernel.  A
+                                          number of its own because 65536 is pinned as meaning nothing to a batch on
+                                          _h4, and keeps meaning nothing there.  Opt-in: an HDP batch of expectations
+                                          without the flag keeps the ring.  As measured (1024 reads of 2 000 k-mers,
+                                          threshold 0.05): a gain at both ends of the range, 1.15 x
+                                          the ring path at a widest band of 196 k-mers (37.8 against 43.4 ms) and 1.34 x
+                                          at 236 (39.9 against 53.3 ms), less than at two and three cells: a forward
+                                          wave (232 registers) and a fused backward wave (432) do not share a SIMD, so
+                                          the forward sweep beside it takes 6.7..7.1 ms a window instead of 4.6..5.4.
+                                          No environment variable of the
+                                          C-ABI sets it; libcpecan_host.so sets it for its HDP batches of expectations
+                                          when CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP=1 (the way in for
+                                          cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels and vanillaAlign). */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -589,7 +626,8 @@ int cpecan_hip_batch_create_echelon(cpecan_ctx *ctx, const cpecan_item *items, i
 /* k-mers against events with an HDP model (getAlignedPairsUsingAnchors with a StateMachine3_HDP,
  * sequence_getKmer3 / sequence_getEvent): same buffers as cpecan_hip_batch_create (x characters over the
  * model's alphabet), model_id is a cpecan_hip_modelsh_create id.  flags: UNBANDED (general kernel, posterior decode
- * only), EXPECTATIONS, GENERAL_KERNEL, WIDE_BANDS_HDP, WIDE_BANDS_HDP_ESTEP.  There is no kernel argument: the batch picks
+ * only), EXPECTATIONS, GENERAL_KERNEL, WIDE_BANDS_HDP, WIDE_BANDS_HDP_ESTEP, HDP_FUSED_ESTEP, WIDE_BANDS_HDP_FUSED_ESTEP,
+ * HDP_FOUR_CELLS_FUSED_ESTEP.  There is no kernel argument: the batch picks
  * its kernels itself (the HDP wave builds up to 248 k-mers of band, the general kernel past that), and the two
  * wide-bands flags alone select the workgroup builds for bands of 249..504 k-mers: CPECAN_FLAG_WIDE_BANDS_HDP for the
  * posterior decode, CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for the E-step.  cpecan_hip_batch_info reports the kernel. */

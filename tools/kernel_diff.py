@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Device code of the throughput kernels in two source trees, kernel for kernel: every build the branch tree's Makefile
 makes of cpecan_kernel_systolic.hip and cpecan_kernel_wave.hip (make print-builds, and print-fused-builds and
-print-hdp-fused-builds, print-hdp-wide-fused-builds: the builds the Makefile lists apart, in the same format), and the files around them that are
-compiled once (ONCE below: a unit is a file of csrc, and one that a tree lacks or that defines no kernel there counts for
-nothing, and so does a build that a tree's source refuses with #error: a build from before it existed), is compiled to
-gfx950 assembly in both trees (the branch Makefile's flags, make print-hipflags, plus -S --cuda-device-only) and, per
+print-hdp-fused-builds, print-hdp-four-cells-fused-builds, print-hdp-wide-fused-builds: the builds the Makefile lists
+apart, in the same format), and the files around them that are compiled once (ONCE below: a unit is a file of csrc,
+and one that a tree lacks or that defines no kernel there counts for nothing, and so does a build that a tree's source
+refuses with #error: a build from before it existed), is compiled to gfx950 assembly in both trees (the branch Makefile's flags, make print-hipflags, plus -S --cuda-device-only) and, per
 kernel name, the instructions between the label and the function's end and the resource lines of the metadata block are
 compared.  A kernel that moved to another file is compared with whichever parent build had it: the number of its
 function in the file, which the compiler puts into its local labels (.LBB<n>_), is taken out first.  A refactor of the
@@ -60,6 +60,7 @@ def main():
     flags = make_print(branch, "print-hipflags").split()
     builds = [(os.path.basename(src), defs.split()) for _, _, src, defs in
               (line.split("\t") for target in ("print-builds", "print-fused-builds", "print-hdp-fused-builds",
+                                                  "print-hdp-four-cells-fused-builds",
                                                   "print-hdp-wide-fused-builds")
                for line in make_print(branch, target).splitlines())] + [(u, []) for u in ONCE]
     jobs = [(t, sub, u, d) for u, d in builds for t, sub in ((parent, "P"), (branch, "B"))]
