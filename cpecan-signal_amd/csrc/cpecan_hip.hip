@@ -38,13 +38,10 @@ extern "C" __global__ void cpecan_k_generalh(DevGeneralArgs, DevParams);
  * is past every build of the tables above and the batch carries the table's flag: CPECAN_FLAG_WIDE_BANDS for the
  * strawMan machine (_r) and the vanilla machine's posterior decode (_v), CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP for the
  * vanilla E-step (_ve; without it that E-step stays on the general kernel), CPECAN_FLAG_WIDE_BANDS_HDP for the HDP
- * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f of the
- * workgroup family, _vf of the wave family, the vanilla machine's _vf4 / _vf6 / _vf8 of the workgroup family, the
- * Makefile's SY_FUSED_BUILDS, and the HDP machine's _hf2 / _hf3 / _hf4 of the wave family, its WV_HDP_FUSED_BUILDS and
- * WV_HDP_FUSED4_BUILDS, and _hf6 / _hf8 of the workgroup family, its SY_HDP_FUSED_BUILDS: the E-step summed inside the
- * sweep back, and no other form of it) are in no
- * table here: each stands in for the build of as many rows that the rules above come to, as the last step of
- * choose_dispatch and for a batch of expectations alone (FUSED_STAND_INS, which also says what asks for each). */
+ * machine's posterior decode (_h), CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP for its E-step (_he).  The fused builds (_f, _vf, _hf
+ * of either family: the E-step summed inside the sweep back, and no other form of it) are in no table here: each stands
+ * in for the build of as many rows that the rules above come to, as the last step of choose_dispatch and for a batch of
+ * expectations alone (FUSED_STAND_INS, which also says what asks for each). */
 #define SWEEP_BUILD(name) extern "C" const SweepBuild name;
 SWEEP_BUILD(cpecan_systolic_build_r1) SWEEP_BUILD(cpecan_systolic_build_r2) SWEEP_BUILD(cpecan_systolic_build_r3)
 SWEEP_BUILD(cpecan_systolic_build) SWEEP_BUILD(cpecan_systolic_build_r6) SWEEP_BUILD(cpecan_systolic_build_r8)
@@ -52,15 +49,15 @@ SWEEP_BUILD(cpecan_wave_build_l2) SWEEP_BUILD(cpecan_wave_build_l3) SWEEP_BUILD(
 SWEEP_BUILD(cpecan_wave_build_h2) SWEEP_BUILD(cpecan_wave_build_h3) SWEEP_BUILD(cpecan_wave_build_h4)
 SWEEP_BUILD(cpecan_wave_build_v2) SWEEP_BUILD(cpecan_wave_build_v3)
 SWEEP_BUILD(cpecan_wave_build_vf2) SWEEP_BUILD(cpecan_wave_build_vf3)
-SWEEP_BUILD(cpecan_hdpfx_build_hf2) SWEEP_BUILD(cpecan_hdpfx_build_hf3) SWEEP_BUILD(cpecan_hdpfx_build_hf4)
+SWEEP_BUILD(cpecan_wave_build_hf2) SWEEP_BUILD(cpecan_wave_build_hf3) SWEEP_BUILD(cpecan_wave_build_hf4)
 SWEEP_BUILD(cpecan_systolic_build_v4) SWEEP_BUILD(cpecan_systolic_build_v6) SWEEP_BUILD(cpecan_systolic_build_v8)
 SWEEP_BUILD(cpecan_systolic_build_h6) SWEEP_BUILD(cpecan_systolic_build_h8)
 SWEEP_BUILD(cpecan_systolic_build_he6) SWEEP_BUILD(cpecan_systolic_build_he8)
 SWEEP_BUILD(cpecan_systolic_build_ve4) SWEEP_BUILD(cpecan_systolic_build_ve6) SWEEP_BUILD(cpecan_systolic_build_ve8)
 SWEEP_BUILD(cpecan_systolic_build_f1) SWEEP_BUILD(cpecan_systolic_build_f2) SWEEP_BUILD(cpecan_systolic_build_f3)
 SWEEP_BUILD(cpecan_systolic_build_f4) SWEEP_BUILD(cpecan_systolic_build_f6) SWEEP_BUILD(cpecan_systolic_build_f8)
-SWEEP_BUILD(cpecan_systolicfx_build_vf4) SWEEP_BUILD(cpecan_systolicfx_build_vf6) SWEEP_BUILD(cpecan_systolicfx_build_vf8)
-SWEEP_BUILD(cpecan_hdpwfx_build_hf6) SWEEP_BUILD(cpecan_hdpwfx_build_hf8)
+SWEEP_BUILD(cpecan_systolic_build_vf4) SWEEP_BUILD(cpecan_systolic_build_vf6) SWEEP_BUILD(cpecan_systolic_build_vf8)
+SWEEP_BUILD(cpecan_systolic_build_hf6) SWEEP_BUILD(cpecan_systolic_build_hf8)
 static SweepFamily SY_BUILDS = { &cpecan_systolic_build_r1, &cpecan_systolic_build_r2, &cpecan_systolic_build_r3,
                                  &cpecan_systolic_build };
 /* (a table of wide builds ends with a null entry) */
@@ -222,15 +219,10 @@ struct Dispatch {
 };
 /* The fused builds: a batch of expectations that the rules of choose_dispatch put on a row's ring build, and that carries
  * the row's flag or whose environment has the row's switch on, runs on the row's fused build, of as many waves per
- * workgroup or cells per lane.  The _r builds are the strawMan machine's alone and the _v wave builds the vanilla
- * machine's, so a flag means nothing to another machine, mode, range of bands or family, or to the general kernel:
- * such a batch runs what it runs without it; the _h2 / _h3 wave builds are the HDP machine's, and its four-cell build
- * _h4 (bands of 185..248 k-mers) has a stand-in, _hf4, under a flag of its own (CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP:
- * the flag of _h2 / _h3 is pinned as meaning nothing at four cells, and keeps meaning nothing there).  A vanilla batch
- * on the _ve workgroup builds (reached with
- * CPECAN_FLAG_WIDE_BANDS_VANILLA_ESTEP alone) keeps its build under the wave builds' flag and leaves it for _vf4 / _vf6 /
- * _vf8 under one of its own; an HDP batch on the _he workgroup builds (reached with CPECAN_FLAG_WIDE_BANDS_HDP_ESTEP alone)
- * likewise keeps its build under the wave builds' flag and leaves it for _hf6 / _hf8 under one of its own. */
+ * workgroup or cells per lane.  A ring build belongs to one machine, one family and one range of bands, and a flag is on
+ * the rows of its own builds alone: to any other batch (another machine, mode, family or range of bands, the general
+ * kernel) it means nothing, and that batch runs what it runs without it -- so the flag of _h2 / _h3 moves no batch off
+ * _h4, and a wave build's flag none off the _ve / _he workgroup builds: those rows have flags of their own. */
 static const struct FusedStandIn {
     const SweepBuild *ring, *fused;
     int flag;
@@ -244,14 +236,14 @@ static const struct FusedStandIn {
     { &cpecan_systolic_build_r8, &cpecan_systolic_build_f8, CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, &BatchEnv::fusedWide },
     { &cpecan_wave_build_v2, &cpecan_wave_build_vf2, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
     { &cpecan_wave_build_v3, &cpecan_wave_build_vf3, CPECAN_FLAG_VANILLA_FUSED_ESTEP, nullptr },
-    { &cpecan_wave_build_h2, &cpecan_hdpfx_build_hf2, CPECAN_FLAG_HDP_FUSED_ESTEP, nullptr },
-    { &cpecan_wave_build_h3, &cpecan_hdpfx_build_hf3, CPECAN_FLAG_HDP_FUSED_ESTEP, nullptr },
-    { &cpecan_wave_build_h4, &cpecan_hdpfx_build_hf4, CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP, nullptr },
-    { &cpecan_systolic_build_ve4, &cpecan_systolicfx_build_vf4, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
-    { &cpecan_systolic_build_ve6, &cpecan_systolicfx_build_vf6, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
-    { &cpecan_systolic_build_ve8, &cpecan_systolicfx_build_vf8, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
-    { &cpecan_systolic_build_he6, &cpecan_hdpwfx_build_hf6, CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP, nullptr },
-    { &cpecan_systolic_build_he8, &cpecan_hdpwfx_build_hf8, CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP, nullptr },
+    { &cpecan_wave_build_h2, &cpecan_wave_build_hf2, CPECAN_FLAG_HDP_FUSED_ESTEP, nullptr },
+    { &cpecan_wave_build_h3, &cpecan_wave_build_hf3, CPECAN_FLAG_HDP_FUSED_ESTEP, nullptr },
+    { &cpecan_wave_build_h4, &cpecan_wave_build_hf4, CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_ve4, &cpecan_systolic_build_vf4, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_ve6, &cpecan_systolic_build_vf6, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_ve8, &cpecan_systolic_build_vf8, CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_he6, &cpecan_systolic_build_hf6, CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP, nullptr },
+    { &cpecan_systolic_build_he8, &cpecan_systolic_build_hf8, CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP, nullptr },
 };
 #define CP_WAVE5_MAX_WIDTH 192 /* cells: one to three per lane */
 static Dispatch choose_dispatch(const DispatchQuery &q) {

@@ -85,18 +85,16 @@
  * are scaled to the exact totals and added to the model's sums (fx_finish), and a window whose estimate cannot be
  * trusted is swept back once more, in the same launch, against the exact totals. */
 /* -DSY_VANILLA -DSY_FUSED: the vanilla machine's E-step with its expectations summed inside the sweep back, with four,
- * six and eight waves per workgroup (the bands of _ve4 / _ve6 / _ve8), in objects of their own that the Makefile keeps
- * on a list of their own (SY_FUSED_BUILDS: symbols suffixed _vf4, _vf6, _vf8, the record cpecan_systolicfx_build_vf<n>;
- * the _ve objects keep their device code).  The forward sweep is the _ve builds'.  This machine collects two terms per
+ * six and eight waves per workgroup (the bands of _ve4 / _ve6 / _ve8), in objects of their own (symbols suffixed
+ * _vf4, _vf6, _vf8; the _ve objects keep their device code).  The forward sweep is the _ve builds'.  This machine collects two terms per
  * cell and no transition, both from the cell's lower neighbour (cpecan_k_sy_expect, vanilla form), so the sweep back
  * fetches F.gapX beside F.match, takes B.gapX and the column's a_mx / a_xx apart down the lanes (the recurrence's sums
  * are formed by the receiver: the same doubles) and keeps (column, beta, alpha) per slot and refresh segment, in
  * registers: no ring of backward cells, no expectation kernel.  The estimate, the segments' scaling, the second sweep
  * and DevParams::expectResweep are the strawMan fused builds' (above); fx_finish adds through 60 bins in LDS. */
 /* -DSY_HDP -DSY_FUSED: the HDP machine's E-step with its expectations summed inside the sweep back, with six and eight
- * waves per workgroup (the bands of _he6 / _he8), in objects of their own that the Makefile keeps on a list of their own
- * (SY_HDP_FUSED_BUILDS: symbols suffixed _hf6, _hf8, the record cpecan_hdpwfx_build_hf<n>; the _he objects keep their
- * device code).  The forward sweep is the _he builds'.  The sums are the strawMan fused builds' without the k-mer bins
+ * waves per workgroup (the bands of _he6 / _he8), in objects of their own (symbols suffixed _hf6, _hf8; the
+ * _he objects keep their device code).  The forward sweep is the _he builds'.  The sums are the strawMan fused builds' without the k-mer bins
  * (no g, no c records: SY_FX_G 0), into the model's nine transitions and its likelihood.  The machine's event-to-k-mer
  * assignments (cpecan_k_sy_expect, HDP form) come from the same sweep: in the middle block it parks the target cell, the
  * from-state and the exponent s before the total is subtracted, wherever s lies within SY_CAND_SLACK of the threshold
@@ -2633,14 +2631,7 @@ static int sy_launch_expect(hipStream_t stream, const SweepArgs &a, int window) 
 
 /* the record (host only: the device pass would emit it as a constant, with pointers to host functions) */
 #ifndef __HIP_DEVICE_COMPILE__
-/* (the vanilla _vf builds, which are not among the Makefile's SY_BUILDS, have a record name of their own) */
-#if defined(SY_FUSED) && defined(SY_VANILLA)
-#define SY_BUILD_SYM SY_SYM(cpecan_systolicfx_build)
-#elif defined(SY_HDP_FUSED) /* (nor are the HDP _hf builds: the Makefile's SY_HDP_FUSED_BUILDS) */
-#define SY_BUILD_SYM SY_SYM(cpecan_hdpwfx_build)
-#else
 #define SY_BUILD_SYM SY_SYM(cpecan_systolic_build)
-#endif
 extern "C" const SweepBuild SY_BUILD_SYM;
 /* (the _f builds serve a batch that asks for them only: cpecan_hip.hip puts one in the place of the build of as many
  * waves that the dispatch chose; their segment records lie behind the scratch.  The dispatch sends the other E-step

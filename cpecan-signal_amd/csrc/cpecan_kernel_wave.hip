@@ -54,8 +54,7 @@
  * inside the sweep back, the assignments (transitions into match whose own posterior reaches the threshold) selected
  * from a candidate list the sweep back parks, as the posterior decode's are -- with the forward sweep, the fused sweep
  * back, the post kernel and the fused re-sweep, each sweep with and without the gap Y -> gap X term: symbols suffixed
- * _hf2, _hf3, _hf4, the record cpecan_hdpfx_build_hf<n> (the Makefile's WV_HDP_FUSED_BUILDS and, at four cells per lane,
- * WV_HDP_FUSED4_BUILDS); the _h2 / _h3 / _h4 objects keep their device code */
+ * _hf2, _hf3, _hf4; the _h2 / _h3 / _h4 objects keep their device code */
 #if defined(WV_FUSED) && !defined(WV_VANILLA) && !defined(WV_HDP)
 #error "WV_FUSED: a build of the vanilla or the HDP machine (the strawMan builds hold their fused sweeps themselves)"
 #endif
@@ -2928,19 +2927,8 @@ static int wv_launch_backward_fx(hipStream_t stream, const SweepArgs &a, int win
 #endif
 /* scratch: [hit offsets | window totals | their terms | the parked operands | hit masks | candidate list], and after it,
  * in batches with fused expectations, the segments' sums (WvFx) */
-#ifdef WV_HDP_FUSED
-#define WV_BUILD_SYM WV_SYM(cpecan_hdpfx_build) /* (lists of their own: WV_HDP_FUSED_BUILDS, WV_HDP_FUSED4_BUILDS) */
-#else
 #define WV_BUILD_SYM WV_SYM(cpecan_wave_build)
-#endif
-#if defined(WV_HDP_FUSED) && WV_L == 4
-/* (the four-cell record is named by cpecan_hip.hip alone and is no dynamic symbol of the library:
- * tests/test_hdp_fused_builds_cpu.py holds the cpecan_hdpfx_build* it exports to _hf2 / _hf3) */
-#define WV_BUILD_VISIBILITY __attribute__((visibility("hidden")))
-#else
-#define WV_BUILD_VISIBILITY
-#endif
-extern "C" WV_BUILD_VISIBILITY const SweepBuild WV_BUILD_SYM;
+extern "C" const SweepBuild WV_BUILD_SYM;
 const SweepBuild WV_BUILD_SYM = {
     WV_L, true, WV_MACHINE, WV_P - 8, WV_ROW_DOUBLES, WV_L * 3 * 64,
     wv_scratch_base_bytes, WV_FX(wv_fx_bytes),

@@ -127,9 +127,7 @@ enum { SWEEP_STRAWMAN, SWEEP_HDP, SWEEP_VANILLA };
 
 /* One compiled build of the throughput kernels, defined next to them: cpecan_systolic_build<suffix> in
  * cpecan_kernel_systolic.hip, cpecan_wave_build<suffix> in cpecan_kernel_wave.hip, one per build of the Makefile's list
- * (SY_BUILDS, WV_BUILDS, and the unsuffixed four-wave build), cpecan_systolicfx_build_vf<n> per build of
- * SY_FUSED_BUILDS, cpecan_hdpfx_build_hf<n> per build of WV_HDP_FUSED_BUILDS and WV_HDP_FUSED4_BUILDS and
- * cpecan_hdpwfx_build_hf<n> per build of SY_HDP_FUSED_BUILDS */
+ * (SY_BUILDS, WV_BUILDS, and the unsuffixed four-wave build) */
 struct SweepBuild {
     int rows;    /* waves per workgroup (workgroup family) or cells per lane (wave family) */
     bool wave;   /* one wave per alignment */

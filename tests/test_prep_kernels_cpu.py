@@ -20,7 +20,7 @@ ONCE = ("cpecan_k_kmer_index", "cpecan_k_hdp_kmer_id", "cpecan_k_track", "cpecan
 MACHINES = ("cpecan_systolic_machine", "cpecan_systolic_machine_vanilla", "cpecan_systolic_machine_hdp",
             "cpecan_wave_machine", "cpecan_wave_machine_hdp", "cpecan_wave_machine_vanilla")
 # tags of the workgroup builds without an expectation kernel: posterior decode only, or the E-step fused into the sweep
-NO_EXPECT = ("v", "h", "f")
+NO_EXPECT = ("v", "h", "f", "vf", "hf")
 
 
 @pytest.fixture(scope="module")

@@ -19,8 +19,8 @@ from concurrent.futures import ThreadPoolExecutor
 WIDTHS = (0, 1, 56, 57, 120, 121, 158, 159, 184, 185, 192, 193, 248, 249, 376, 377, 504, 505)
 BASES = ("WORKGROUP_KERNELS", "GENERAL_KERNEL", "UNBANDED", "DEBUG_DUMP", "WIDE_BANDS")
 WITH = ("WIDE_BANDS", "WIDE_BANDS_HDP", "WIDE_BANDS_HDP_ESTEP", "WIDE_BANDS_VANILLA_ESTEP", "WORKGROUP_FUSED_ESTEP",
-        "WIDE_BANDS_FUSED_ESTEP", "ASM_NARROW_BANDS", "VANILLA_FUSED_ESTEP",
-        "WIDE_BANDS_VANILLA_FUSED_ESTEP")  # the wide, fused and asm flags
+        "WIDE_BANDS_FUSED_ESTEP", "ASM_NARROW_BANDS", "VANILLA_FUSED_ESTEP", "WIDE_BANDS_VANILLA_FUSED_ESTEP",
+        "HDP_FUSED_ESTEP", "WIDE_BANDS_HDP_FUSED_ESTEP", "HDP_FOUR_CELLS_FUSED_ESTEP")  # the wide, fused and asm flags
 
 
 def grid_of(branch):

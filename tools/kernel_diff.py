@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Device code of the throughput kernels in two source trees, kernel for kernel: every build the branch tree's Makefile
-makes of cpecan_kernel_systolic.hip and cpecan_kernel_wave.hip (make print-builds, and print-fused-builds and
-print-hdp-fused-builds, print-hdp-four-cells-fused-builds, print-hdp-wide-fused-builds: the builds the Makefile lists
-apart, in the same format), and the files around them that are compiled once (ONCE below: a unit is a file of csrc,
+makes of cpecan_kernel_systolic.hip and cpecan_kernel_wave.hip (make print-builds), and the files around them that are
+compiled once (ONCE below: a unit is a file of csrc,
 and one that a tree lacks or that defines no kernel there counts for nothing, and so does a build that a tree's source
 refuses with #error: a build from before it existed), is compiled to gfx950 assembly in both trees (the branch Makefile's flags, make print-hipflags, plus -S --cuda-device-only) and, per
 kernel name, the instructions between the label and the function's end and the resource lines of the metadata block are
@@ -59,10 +58,7 @@ def main():
         os.makedirs(os.path.join(work, t), exist_ok=True)
     flags = make_print(branch, "print-hipflags").split()
     builds = [(os.path.basename(src), defs.split()) for _, _, src, defs in
-              (line.split("\t") for target in ("print-builds", "print-fused-builds", "print-hdp-fused-builds",
-                                                  "print-hdp-four-cells-fused-builds",
-                                                  "print-hdp-wide-fused-builds")
-               for line in make_print(branch, target).splitlines())] + [(u, []) for u in ONCE]
+              (line.split("\t") for line in make_print(branch, "print-builds").splitlines())] + [(u, []) for u in ONCE]
     jobs = [(t, sub, u, d) for u, d in builds for t, sub in ((parent, "P"), (branch, "B"))]
     with ThreadPoolExecutor(max_workers=int(os.environ.get("JOBS", "8"))) as pool:
         res = list(pool.map(lambda j: kernels(j[0], j[2], j[3], flags, os.path.join(work, j[1])), jobs))
