@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 LIB_PATH = os.environ.get("CPECAN_HIP_LIB") or os.path.join(_HERE, "libcpecan_hip.so")  # (the override serves tools/ablate_asm.sh, tools/ab_bench.sh)
 
-OK, ENODEVICE, EINVAL, EHIP, EOVERFLOW, EBAND = 0, -1, -2, -3, -4, -5
+OK, ENODEVICE, EINVAL, EHIP, EOVERFLOW, EBAND, ELIMIT = 0, -1, -2, -3, -4, -5, -6
 MODE_POSTERIOR, MODE_EXPECTATIONS = 0, 1
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_SYSTOLIC = 0, 1, 2
 FLAG_DEBUG_DUMP = 1
@@ -68,6 +68,7 @@ EXPORTS = [
     "cpecan_hip_modelsv_set_skip_probs", "cpecan_hip_batch_create_vanilla", "cpecan_hip_models4_create", "cpecan_hip_batch_create_sm4",
     "cpecan_hip_modelsh_create", "cpecan_hip_batch_create_hdp",
     "cpecan_hip_modelse_create", "cpecan_hip_batch_create_echelon",
+    "cpecan_hip_ctx_memory", "cpecan_hip_ctx_set_memory_limit", "cpecan_hip_batch_device_bytes", "cpecan_band_extent", "cpecan_hip_cache_capacity",
 ]
 
 
@@ -160,6 +161,12 @@ def lib():
                                           C.c_int, C.c_int, C.c_void_p, C.c_int64]
         L.cpecan_band_construct.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p]
+        L.cpecan_band_extent.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cpecan_hip_ctx_memory.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]
+        L.cpecan_hip_ctx_set_memory_limit.argtypes = [C.c_void_p, C.c_int64]
+        L.cpecan_hip_batch_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.cpecan_hip_cache_capacity.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.cpecan_hip_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.cpecan_hip_ctx_destroy.argtypes = [C.c_void_p]
         L.cpecan_hip_ctx_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -274,6 +281,15 @@ def band_construct(anchors, lX, lY, expansion):
     return L, R
 
 
+def band_extent(anchors, lX, lY, expansion):
+    """(widest diagonal of the band in cells, whether both edges step by at most one k-mer per diagonal): what
+    plan_dispatch takes as max_width and edges_step_by_one, by batch creation's own rule (no device needed)"""
+    a = np.ascontiguousarray(anchors, dtype=np.int64).reshape(-1, 2)
+    w, s = C.c_int32(0), C.c_int32(0)
+    _check(lib().cpecan_band_extent(_ptr(a), a.shape[0], lX, lY, expansion, C.byref(w), C.byref(s)))
+    return w.value, bool(s.value)
+
+
 def split_points(anchors, lX, lY, max_matrix, ragged_left, ragged_right):
     a = np.ascontiguousarray(anchors, dtype=np.int64).reshape(-1, 2)
     out = np.zeros((a.shape[0] + 2, 4), np.int64)
@@ -307,6 +323,23 @@ class Context:
         s = C.c_void_p()
         _check(lib().cpecan_hip_ctx_stream(self.h, C.byref(s)))
         return s.value
+
+    def set_memory_limit(self, nbytes):
+        """device bytes the context's model tables and live batches may hold together (0: no limit); an allocation
+        past it raises CpecanError with code ELIMIT"""
+        _check(lib().cpecan_hip_ctx_set_memory_limit(self.h, int(nbytes)))
+
+    def cache_capacity(self):
+        """bytes of released device blocks the library keeps for reuse at the most (CPECAN_ALLOC_CACHE_GB)"""
+        v = C.c_int64(0)
+        _check(lib().cpecan_hip_cache_capacity(self.h, C.byref(v)))
+        return v.value
+
+    def memory(self, reset_peak=False):
+        """dict(live, peak): device bytes held on behalf of the context now, and the most since the last reset"""
+        live, peak = C.c_int64(0), C.c_int64(0)
+        _check(lib().cpecan_hip_ctx_memory(self.h, C.byref(live), C.byref(peak), int(bool(reset_peak))))
+        return dict(live=live.value, peak=peak.value)
 
     def models_set_transitions(self, transitions, gap_x=None):
         """the M-step's update of every strawMan model of the context, in place on the device"""
@@ -555,6 +588,12 @@ class Batch:
 
     def sync(self):
         _check(lib().cpecan_hip_batch_sync(self.h))
+
+    def device_bytes(self):
+        """device bytes the batch holds now, as the allocator handed its blocks out"""
+        v = C.c_int64(0)
+        _check(lib().cpecan_hip_batch_device_bytes(self.h, C.byref(v)))
+        return v.value
 
     def shader_clock_mhz(self):
         """MHz during the last run's forward sweeps (wave kernels; 0.0 otherwise)"""

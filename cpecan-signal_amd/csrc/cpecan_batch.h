@@ -25,6 +25,7 @@ struct PackedPair {
 
 struct cpecan_batch {
     cpecan_ctx *ctx = nullptr;
+    std::shared_ptr<MemAccount> mem; /* the blocks of its DevBufs; part of its context's account (new_batch) */
     int64_t nItems = 0;
     int mode = 0, kernel = 0, flags = 0;
     DevParams P{};
@@ -47,6 +48,7 @@ struct cpecan_batch {
                            CPECAN_FLAG_WORKGROUP_FUSED_ESTEP / CPECAN_FLAG_WIDE_BANDS_FUSED_ESTEP, on the workgroup kernels'
                            fused builds: expectations summed inside the sweep back, no B ring, no expectation kernel */
     DevBuf<long long> pairs;
+    bool pairsLaidOut = true; /* false: lay_out_pairs was refused, `pairs` / `pairLogp` are not there */
     DevBuf<double> pairLogp;
     DevBuf<long long> nPairs, totXay, nTot, nCells;
     DevBuf<double> totVal;
@@ -178,6 +180,7 @@ extern const MachineRow MACHINES[N_MACHINES]; /* (cpecan_hip.hip, next to the ta
 /* the end of a posterior run, queued on the stream it ends on before its end event: its candidates packed for the host
  * (cpecan_readback.hip) */
 int pack_in_run(cpecan_batch *b, hipStream_t sEnd);
+int lay_out_pairs(cpecan_batch *b); /* (cpecan_readback.hip; the run makes up for one that a memory limit refused) */
 /* the batch's pinned blocks of the readback go back to the cache (cpecan_hip_batch_destroy) */
 void release_readback(cpecan_batch *b);
 

@@ -12,9 +12,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -91,7 +94,8 @@ struct DevCache {
     }
     hipError_t raw_alloc(void **out, size_t bytes) { return pinnedHost ? hipHostMalloc(out, bytes, hipHostMallocDefault) : hipMalloc(out, bytes); }
     void raw_free(void *p) { (void) (pinnedHost ? hipHostFree(p) : hipFree(p)); }
-    hipError_t get(void **out, size_t bytes, size_t *got) {
+    /* most: no cached block larger than this (the room an account with a limit has left) */
+    hipError_t get(void **out, size_t bytes, size_t *got, size_t most = SIZE_MAX) {
         *got = bytes;
         int device = 0;
         (void) hipGetDevice(&device);
@@ -99,7 +103,7 @@ struct DevCache {
             std::lock_guard<std::mutex> g(lock);
             size_t best = blocks.size();
             for (size_t i = 0; i < blocks.size(); i++)
-                if (blocks[i].device == device && blocks[i].bytes >= bytes && blocks[i].bytes <= bytes + bytes / 4 + 4096 &&
+                if (blocks[i].device == device && blocks[i].bytes >= bytes && blocks[i].bytes <= bytes + bytes / 4 + 4096 && blocks[i].bytes <= most &&
                     (best == blocks.size() || blocks[i].bytes < blocks[best].bytes))
                     best = i;
             if (best != blocks.size()) {
@@ -160,17 +164,78 @@ template <typename T> struct PinnedBuf {
     ~PinnedBuf() { release(); }
 };
 
+/* Whose device memory it is: one account per context, shared with its batches (a batch may outlive its context).  live:
+ * the blocks, at the size the cache handed them out, that the context's model tables and its batches hold now; peak: the
+ * most that was since the last reset; limit: 0, none -- otherwise an allocation that would take live past it is refused
+ * (cpecan_hip_ctx_set_memory_limit).  A context and its batches are used by one thread at a time, so the counters are
+ * plain; what the cache itself keeps of released blocks is nobody's (CPECAN_ALLOC_CACHE_GB bounds that, separately). */
+struct MemAccount {
+    long long live = 0, peak = 0, limit = 0;
+    std::shared_ptr<MemAccount> of; /* a batch's account: its context's, which counts the batch's blocks too */
+    /* the account, this one or one it is part of, whose limit `bytes` more would pass (null: none) */
+    const MemAccount *refuses(size_t bytes) const {
+        for (const MemAccount *a = this; a; a = a->of.get())
+            if (a->limit > 0 && a->live + (long long) bytes > a->limit) return a;
+        return nullptr;
+    }
+    size_t room() const { /* the largest block none of them refuses */
+        size_t r = SIZE_MAX;
+        for (const MemAccount *a = this; a; a = a->of.get())
+            if (a->limit > 0) r = std::min(r, (size_t) std::max(a->limit - a->live, 0ll));
+        return r;
+    }
+    void take(size_t bytes) {
+        for (MemAccount *a = this; a; a = a->of.get()) {
+            a->live += (long long) bytes;
+            if (a->live > a->peak) a->peak = a->live;
+        }
+    }
+    void give(size_t bytes) {
+        for (MemAccount *a = this; a; a = a->of.get()) a->live -= (long long) bytes;
+    }
+};
+/* The account that the calling thread's DevBuf allocations go on, for the length of a C-ABI call made on behalf of a
+ * context or one of its batches (none: the allocation is nobody's, as the self-test's). */
+std::shared_ptr<MemAccount> &mem_current();
+struct MemScope {
+    std::shared_ptr<MemAccount> outer;
+    explicit MemScope(const std::shared_ptr<MemAccount> &a);
+    ~MemScope();
+};
+/* a DevBuf allocation was refused by its account's limit: fail() turns the CPECAN_EHIP of the hipErrorOutOfMemory that
+ * alloc() returned into CPECAN_ELIMIT and says what was asked for */
+void mem_refused(size_t asked, const MemAccount &a);
+
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0, blockBytes = 0;
+    std::shared_ptr<MemAccount> account; /* whose the block is (null: nobody's) */
     hipError_t alloc(size_t count) {
         release();
-        n = count;
         if (count == 0) return hipSuccess;
-        return dev_cache().get((void **) &p, count * sizeof(T), &blockBytes);
+        const std::shared_ptr<MemAccount> &a = mem_current();
+        if (a && a->refuses(count * sizeof(T))) {
+            mem_refused(count * sizeof(T), *a->refuses(count * sizeof(T)));
+            return hipErrorOutOfMemory;
+        }
+        /* (a cached block is up to a quarter larger than what was asked for: none that the account has no room for) */
+        const hipError_t e = dev_cache().get((void **) &p, count * sizeof(T), &blockBytes, a ? a->room() : SIZE_MAX);
+        if (e != hipSuccess) { /* a buffer that could not be had is an empty one: `n` never speaks of a block that is not there */
+            p = nullptr;
+            blockBytes = 0;
+            return e;
+        }
+        n = count;
+        if (a) {
+            a->take(blockBytes);
+            account = a;
+        }
+        return e;
     }
     void release() {
         if (p) dev_cache().put(p, blockBytes);
+        if (p && account) account->give(blockBytes);
+        account.reset();
         p = nullptr;
         n = blockBytes = 0;
     }
@@ -178,6 +243,7 @@ template <typename T> struct DevBuf {
         std::swap(p, o.p);
         std::swap(n, o.n);
         std::swap(blockBytes, o.blockBytes);
+        std::swap(account, o.account);
     }
     ~DevBuf() { release(); }
 };
@@ -236,6 +302,7 @@ static_assert(sizeof(DevHdpModel) == CP_HDP_MODEL_DOUBLES * sizeof(double), "the
 
 struct cpecan_ctx {
     int device = 0;
+    std::shared_ptr<MemAccount> mem = std::make_shared<MemAccount>(); /* its model tables and its batches (MemScope) */
     long long modelEpoch = 0; /* counts cpecan_hip_models_clear calls (and tables dropped by a failed upload) */
     LaneSet *lanes = nullptr;
     hipStream_t stream = nullptr; /* lanes->fwd */

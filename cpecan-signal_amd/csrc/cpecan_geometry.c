@@ -12,9 +12,11 @@
  * and an anti-diagonal x+y = d crosses it in x in [max(xLo, d - yHi), min(xHi, d - yLo)].
  */
 #include "cpecan_hip.h"
+#include "cpecan_band_extent.h"
 
 #include <math.h>
 #include <stddef.h>
+#include <stdlib.h>
 
 static int64_t clampi(int64_t z, int64_t hi) { return z < 0 ? 0 : (z > hi ? hi : z); }
 
@@ -56,6 +58,28 @@ int cpecan_band_construct(const int64_t *anchors, int64_t n_anchors, int64_t lX,
         py = ny;
     }
     if (d <= last) return CPECAN_EBAND;
+    return CPECAN_OK;
+}
+
+int cpecan_band_extent(const int64_t *anchors, int64_t n_anchors, int64_t lX, int64_t lY, int64_t expansion,
+                       int32_t *max_width, int32_t *edges_step_by_one) {
+    if (lX < 0 || lY < 0 || lX + lY >= ((int64_t) 1 << 30)) return CPECAN_EINVAL;
+    const int64_t nDiag = lX + lY + 1;
+    int32_t *L = malloc(sizeof(int32_t) * 2 * (size_t) nDiag);
+    if (!L) return CPECAN_EINVAL;
+    int32_t *R = L + nDiag;
+    const int rc = cpecan_band_construct(anchors, n_anchors, lX, lY, expansion, L, R);
+    int widest = 0, stepByOne = 1, prev[2] = { 0, 0 }, col[2];
+    for (int64_t k = 0; rc == CPECAN_OK && k < nDiag; k++) {
+        const int wd = cpecan_diag_extent(k, L[k], R[k], prev, col, &stepByOne);
+        if (wd > widest) widest = wd;
+        prev[0] = col[0];
+        prev[1] = col[1];
+    }
+    free(L);
+    if (rc != CPECAN_OK) return rc;
+    if (max_width) *max_width = widest;
+    if (edges_step_by_one) *edges_step_by_one = stepByOne;
     return CPECAN_OK;
 }
 

@@ -7,6 +7,7 @@
  * Nothing here computes DP cells: when no GPU is usable every compute entry point fails with
  * CPECAN_ENODEVICE (there is deliberately no CPU fallback).
  */
+#include "cpecan_band_extent.h"
 #include "cpecan_batch.h"
 
 #include "cpecan_sweep.h"
@@ -101,6 +102,9 @@ int host_threads() {
     return n < 1 ? 1 : n > 32 ? 32 : n;
 }
 
+/* what the calling thread's last DevBuf allocation was refused for by an account's limit (asked < 0: nothing) */
+static thread_local struct { long long asked = -1, limit = 0, live = 0; } g_memRefused;
+
 int fail(int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
@@ -108,7 +112,32 @@ int fail(int code, const char *fmt, ...) {
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
     g_err = buf;
+    if (code == CPECAN_EHIP && g_memRefused.asked >= 0) { /* the hipErrorOutOfMemory was the account's, not the device's */
+        snprintf(buf, sizeof buf, "device memory limit of the context: %lld bytes asked for, limit %lld bytes (%lld held)",
+                 g_memRefused.asked, g_memRefused.limit, g_memRefused.live);
+        g_err = buf;
+        code = CPECAN_ELIMIT;
+    }
+    g_memRefused.asked = -1;
     return code;
+}
+
+std::shared_ptr<MemAccount> &mem_current() {
+    static thread_local std::shared_ptr<MemAccount> a;
+    return a;
+}
+MemScope::MemScope(const std::shared_ptr<MemAccount> &a) : outer(mem_current()) {
+    mem_current() = a;
+    g_memRefused.asked = -1;
+}
+MemScope::~MemScope() {
+    mem_current() = outer;
+    g_memRefused.asked = -1; /* (a refusal that nobody reported must not colour a later call's failure) */
+}
+void mem_refused(size_t asked, const MemAccount &a) {
+    g_memRefused.asked = (long long) asked;
+    g_memRefused.limit = a.limit;
+    g_memRefused.live = a.live;
 }
 
 DevCache &dev_cache() {
@@ -507,6 +536,35 @@ int cpecan_hip_trim_cache(void) {
     return CPECAN_OK;
 }
 
+int cpecan_hip_cache_capacity(cpecan_ctx *c, int64_t *deviceBytes) {
+    if (!c || !deviceBytes) return fail(CPECAN_EINVAL, "bad argument");
+    HIP_TRY(hipSetDevice(c->device)); /* (the default is worked out from the card's memory) */
+    DevCache &cache = dev_cache();
+    std::lock_guard<std::mutex> g(cache.lock);
+    *deviceBytes = (int64_t) cache.cap();
+    return CPECAN_OK;
+}
+
+int cpecan_hip_ctx_memory(cpecan_ctx *c, int64_t *live, int64_t *peak, int32_t resetPeak) {
+    if (!c) return fail(CPECAN_EINVAL, "ctx is NULL");
+    if (live) *live = c->mem->live;
+    if (peak) *peak = c->mem->peak;
+    if (resetPeak) c->mem->peak = c->mem->live;
+    return CPECAN_OK;
+}
+
+int cpecan_hip_ctx_set_memory_limit(cpecan_ctx *c, int64_t bytes) {
+    if (!c || bytes < 0) return fail(CPECAN_EINVAL, "bad argument");
+    c->mem->limit = bytes;
+    return CPECAN_OK;
+}
+
+int cpecan_hip_batch_device_bytes(cpecan_batch *b, int64_t *bytes) {
+    if (!b || !bytes) return fail(CPECAN_EINVAL, "bad argument");
+    *bytes = b->mem->live;
+    return CPECAN_OK;
+}
+
 int cpecan_hip_ctx_stream(cpecan_ctx *c, void **stream) {
     if (!c || !stream) return fail(CPECAN_EINVAL, "NULL argument");
     *stream = (void *) c->stream;
@@ -649,17 +707,10 @@ static int check_items(const cpecan_ctx *c, Machine machine, const BatchInput &i
     return CPECAN_OK;
 }
 
-/* Whether an item of a vanilla batch meets a k-mer that is none: a character outside ACGT among its lX + 5, or fewer
- * than two k-mers (sequence_getKmer2 looks one k-mer ahead, so an item of no or one k-mer reads the k-mer that runs
- * into its string's terminator). */
+/* Whether an item of a vanilla batch meets a k-mer that is none (cpecan_item_meets_no_kmer, cpecan_band_extent.h) */
 static bool vanilla_meets_no_kmer(const BatchInput &in) {
-    for (int64_t i = 0; i < in.nItems; i++) {
-        const cpecan_item &s = in.items[i];
-        if (s.lX < 2) return true;
-        const char *x = in.xChars + s.x_offset;
-        for (int64_t k = 0; k < s.lX + 5; k++)
-            if (x[k] != 'A' && x[k] != 'C' && x[k] != 'G' && x[k] != 'T') return true;
-    }
+    for (int64_t i = 0; i < in.nItems; i++)
+        if (cpecan_item_meets_no_kmer(in.xChars + in.items[i].x_offset, in.items[i].lX)) return true;
     return false;
 }
 
@@ -705,17 +756,15 @@ static int build_bands(const BatchInput &in, BandPlan &plan, bool general) {
              * diagonals that must be resident at once, and the edge-step property the register-resident
              * kernels rely on */
             long long tracedBackTo = 0;
-            int windows = 0, pmn = 0, pmx = 0;
+            int windows = 0, stepByOne = 1, prev[2] = { 0, 0 }, col[2];
             for (long long k = 0; k < nDiag; k++) {
                 if (pre) pre[k] = cells;
-                const int wd = ((Rp[k] - Lp[k]) >> 1) + 1;
+                const int wd = cpecan_diag_extent(k, Lp[k], Rp[k], prev, col, &stepByOne);
                 cells += wd;
                 maxW = std::max(maxW, wd);
-                const int xmn = (int) ((k + Lp[k]) / 2), xmx = (int) ((k + Rp[k]) / 2);
-                tab[k * 2] = xmn;
-                tab[k * 2 + 1] = xmx;
+                tab[k * 2] = col[0];
+                tab[k * 2 + 1] = col[1];
                 if (k >= 1) {
-                    if (xmn < pmn || xmn > pmn + 1 || xmx < pmx || xmx > pmx + 1) st.edgesStepByOne = false;
                     const bool atEnd = k == nDiag - 1;
                     const bool tb = k >= tracedBackTo + bp.minDiagsBetweenTraceBack && wd <= bp.diagonalExpansion * 2 + 1;
                     if (atEnd || tb) {
@@ -724,9 +773,10 @@ static int build_bands(const BatchInput &in, BandPlan &plan, bool general) {
                         tracedBackTo = k - (bp.traceBackDiagonals + 1);
                     }
                 }
-                pmn = xmn;
-                pmx = xmx;
+                prev[0] = col[0];
+                prev[1] = col[1];
             }
+            if (!stepByOne) st.edgesStepByOne = false;
             d.nCells = cells;
             d.maxWidth = maxW;
             st.windows = std::max(st.windows, windows);
@@ -803,6 +853,8 @@ static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput 
     cpecan_batch *b = new (std::nothrow) cpecan_batch();
     if (!b) return nullptr;
     b->ctx = c;
+    b->mem = std::make_shared<MemAccount>();
+    b->mem->of = c->mem;
     {
         std::lock_guard<std::mutex> g(g_batchesMu);
         c->batches.push_back(b);
@@ -1125,6 +1177,8 @@ static int batch_create_impl(cpecan_ctx *c, Machine machine, const cpecan_item *
 
     cpecan_batch *b = new_batch(c, machine, in, plan, d);
     if (!b) return fail(CPECAN_EINVAL, "out of host memory");
+    /* every block from here on is the batch's (a step that fails destroys it, and its account is empty again) */
+    MemScope mem(b->mem);
     if ((rc = upload_sequences(b, in)) != CPECAN_OK) return rc;
     lap("upload sequences and events");
     if ((rc = alloc_outputs(b, plan)) != CPECAN_OK) return rc;

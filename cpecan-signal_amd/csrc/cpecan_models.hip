@@ -129,6 +129,7 @@ static int download(cpecan_ctx *c, Machine machine, const char *whose, int32_t i
     if (id < 0 || id >= t.n) return fail(CPECAN_EINVAL, "%smodel id %d out of range (%d)", whose, id, t.n);
     if (capacity < (int64_t) t.stride) return fail(CPECAN_EINVAL, "capacity %lld < %d doubles", (long long) capacity, (int) t.stride);
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     HIP_TRY(ctx_fence(c));
     HIP_TRY(hipMemcpy(out, t.block.p + (size_t) id * t.stride, t.stride * sizeof(double), hipMemcpyDeviceToHost));
     return CPECAN_OK;
@@ -141,6 +142,7 @@ int cpecan_hip_models_create(cpecan_ctx *c, const cpecan_sm3_model *models, int3
         if (!models[i].match_probs || !models[i].gap_x_probs || !models[i].gap_y_probs)
             return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     Lap lap("models_create");
     std::vector<double> switchToX((size_t) n);
     for (int i = 0; i < n; i++) switchToX[(size_t) i] = models[i].transitions[T_GAP_SWITCH_TO_X];
@@ -229,6 +231,7 @@ int cpecan_hip_models_create_scaled(cpecan_ctx *c, const cpecan_sm3_model *base,
     if (!c || !base || !scalings || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
     if (!base->match_probs || !base->gap_x_probs || !base->gap_y_probs) return fail(CPECAN_EINVAL, "the base model has a NULL table");
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     Lap lap("models_create_scaled");
     std::vector<double> baseRows(CP_MODEL_STRIDE);
     derive_rows(base, baseRows.data());
@@ -273,6 +276,7 @@ int cpecan_hip_models_set_transitions(cpecan_ctx *c, const double *transitions, 
     ModelTable &t = c->tables[STRAWMAN];
     if (t.n <= 0) return fail(CPECAN_EINVAL, "the context holds no strawMan models");
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     std::vector<double> v(9 + CPECAN_NUM_KMERS, 0.0);
     for (int i = 0; i < 9; i++) v[(size_t) i] = transitions[i];
     if (gapX) std::copy(gapX, gapX + CPECAN_NUM_KMERS, v.begin() + 9);
@@ -354,6 +358,7 @@ int cpecan_hip_modelsv_create(cpecan_ctx *c, const cpecan_vanilla_model *models,
         if (!models[i].match_probs || !models[i].skip_probs || !models[i].gap_y_probs)
             return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     Lap lap("modelsv_create");
     const int nt = pool_threads(threads, n);
     /* a slot holds up to four neighbouring models: the copy engine's cost per copy is that of a block's transfer, so
@@ -403,6 +408,7 @@ int cpecan_hip_modelsv_create_scaled(cpecan_ctx *c, const cpecan_vanilla_model *
     if (!c || !base || !scalings || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
     if (!base->match_probs || !base->skip_probs || !base->gap_y_probs) return fail(CPECAN_EINVAL, "the base model has a NULL table");
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     Lap lap("modelsv_create_scaled");
     static_assert(CP_VHDR % 2 == 0 && CP_VROW % 2 == 0 && CP_V_MU == 0 && CP_V_K == 2 && CP_V_LAMBDA == 4,
                   "cpecan_k_scale_models_v writes a block as pairs of doubles");
@@ -451,6 +457,7 @@ int cpecan_hip_modelsv_set_skip_probs(cpecan_ctx *c, const double *skipProbs) {
     ModelTable &t = c->tables[VANILLA];
     if (t.n <= 0) return fail(CPECAN_EINVAL, "the context holds no vanilla models");
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     /* log a_my and log a_mm depend on the model's m_to_y_not_x: one set of 150 logs per distinct value, taken by the
      * code derive_vanilla runs */
     std::vector<double> v; /* [factors: nSets | bins: nSets x 150] once the sets are known */
@@ -529,6 +536,7 @@ int cpecan_hip_modelse_create(cpecan_ctx *c, const cpecan_echelon_model *models,
         if (!models[i].match_probs || !models[i].skip_probs || !models[i].gap_y_probs)
             return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     std::vector<double> rows((size_t) n * CP_EMODEL_STRIDE);
     for (int i = 0; i < n; i++) derive_echelon(&models[i], rows.data() + (size_t) i * CP_EMODEL_STRIDE);
     return append_rows(c, ECHELON, rows, n, nullptr, ids);
@@ -563,6 +571,7 @@ int cpecan_hip_modelsh_create(cpecan_ctx *c, const cpecan_hdp_model *models, int
                 return fail(CPECAN_EINVAL, "HDP model %d: k-mer %lld points outside the tables", i, k);
     }
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     /* every model's tables are on the device before anything of the call is committed, and go back to the allocator
      * if the call fails: a failed call leaves none of its models behind */
     std::vector<std::unique_ptr<cpecan_ctx::HdpTables>> tables;
@@ -606,6 +615,7 @@ int cpecan_hip_modelsh_create(cpecan_ctx *c, const cpecan_hdp_model *models, int
 int cpecan_hip_models5_create(cpecan_ctx *c, const cpecan_sm5_model *models, int32_t n, int32_t *ids) {
     if (!c || !models || n <= 0 || !ids) return fail(CPECAN_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     std::vector<double> rows((size_t) n * CP_MODEL5_STRIDE, 0.0);
     for (int i = 0; i < n; i++) {
         double *m = rows.data() + (size_t) i * CP_MODEL5_STRIDE;
@@ -624,6 +634,7 @@ int cpecan_hip_models4_create(cpecan_ctx *c, const cpecan_sm4_model *models, int
         if (!models[i].match_probs || !models[i].gap_x_probs || !models[i].gap_y_probs)
             return fail(CPECAN_EINVAL, "model %d has a NULL table", i);
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(c->mem);
     std::vector<double> rows((size_t) n * CP_MODEL_STRIDE);
     for (int i = 0; i < n; i++) {
         cpecan_sm3_model m3;

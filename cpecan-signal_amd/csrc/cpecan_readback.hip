@@ -95,9 +95,10 @@ extern "C" __global__ __launch_bounds__(256) void cpecan_k_pack_base(const DevIt
  * records and verdicts (`capacity` of them where those have to be made or grow). */
 static int pack_buffers(cpecan_batch *b, size_t need, size_t capacity) {
     if (b->packBase.n < (size_t) b->nItems + 1) HIP_TRY(b->packBase.alloc((size_t) b->nItems + 1));
-    if (b->packed.n < need) {
-        HIP_TRY(b->packed.alloc(capacity));
+    if (b->packed.n < need) { /* (`packed`, which is asked, last: a call that fails half-way is made again in full) */
+        b->packed.release();
         HIP_TRY(b->packedPost.alloc(capacity));
+        HIP_TRY(b->packed.alloc(capacity));
     }
     if (b->undecided.n == 0) HIP_TRY(b->undecided.alloc(1 + 2 * CP_UNDECIDED_CAP));
     return CPECAN_OK;
@@ -145,6 +146,20 @@ void release_readback(cpecan_batch *b) {
 /* The run is over and every item's pairs fit its share of the pair buffer.  If an alignment produced more pairs than
  * its share holds (flat posteriors: a tiny threshold, the HDP machine's linear densities), the buffer is re-laid-out to
  * the reported counts and the batch is run once more -- the reference returns the list whatever its length. */
+/* The pair buffer as the items' shares (pairCap, pairBase in hItems) now want it, and the items on the device.  A call
+ * that a memory limit refuses leaves the batch without the buffer and says so in pairsLaidOut: the next run makes it,
+ * and the next readback runs the batch again before it reads anything (ensure_counts). */
+int lay_out_pairs(cpecan_batch *b) {
+    long long total = 0;
+    for (const DevItem &d : b->hItems) total += d.pairCap;
+    b->pairsLaidOut = false;
+    HIP_TRY(b->pairs.alloc((size_t) total * 3));
+    HIP_TRY(b->pairLogp.alloc((size_t) total));
+    HIP_TRY(hipMemcpy(b->items.p, b->hItems.data(), (size_t) b->nItems * sizeof(DevItem), hipMemcpyHostToDevice));
+    b->pairsLaidOut = true;
+    return CPECAN_OK;
+}
+
 static int fit_pair_buffer(cpecan_batch *b) {
     b->hNPairs.resize((size_t) b->nItems);
     b->hNTot.resize((size_t) b->nItems);
@@ -164,10 +179,8 @@ static int fit_pair_buffer(cpecan_batch *b) {
             d.pairBase = total;
             total += d.pairCap;
         }
-        HIP_TRY(b->pairs.alloc((size_t) total * 3));
-        HIP_TRY(b->pairLogp.alloc((size_t) total));
-        HIP_TRY(hipMemcpy(b->items.p, b->hItems.data(), (size_t) b->nItems * sizeof(DevItem), hipMemcpyHostToDevice));
-        int rc = cpecan_hip_batch_run(b);
+        int rc = lay_out_pairs(b);
+        if (rc == CPECAN_OK) rc = cpecan_hip_batch_run(b);
         if (rc != CPECAN_OK) return rc;
     }
 }
@@ -299,9 +312,17 @@ static int settle_close_calls(cpecan_batch *b) {
 
 /* Counts and aligned pairs of a finished run, once per run. */
 static int ensure_counts(cpecan_batch *b) {
+    if (!b->pairsLaidOut) {
+        /* an earlier readback grew the items' shares of the pair buffer and a memory limit refused the buffer: there is
+         * none, and what the last run left is laid out by the old shares.  The run that growth was for, now (it makes
+         * the buffer first); where the limit still refuses it, this call fails as that one did */
+        const int rc = cpecan_hip_batch_run(b);
+        if (rc != CPECAN_OK) return rc;
+    }
     if (!b->ran) return fail(CPECAN_EINVAL, "batch has not run");
     if (b->countsValid) return CPECAN_OK;
     HIP_TRY(hipSetDevice(b->ctx->device));
+    MemScope mem(b->mem);
     Lap lap("ensure_counts");
     const bool estep = b->mode != CPECAN_MODE_POSTERIOR;
     int rc = fit_pair_buffer(b);

@@ -324,6 +324,11 @@ int cpecan_hip_batch_run_after(cpecan_batch *b, cpecan_batch *after) {
                     "its model ids are gone");
     if (after && after->device != b->device) return fail(CPECAN_EINVAL, "the two batches live on different devices");
     HIP_TRY(hipSetDevice(c->device));
+    MemScope mem(b->mem); /* (the pack buffers of the run) */
+    if (!b->pairsLaidOut) { /* a readback's growth of the pair buffer was refused by the memory limit: made now */
+        const int rc = lay_out_pairs(b);
+        if (rc != CPECAN_OK) return rc;
+    }
     if (after == b || (after && !after->ran)) after = nullptr;
     /* behind a wave batch of one stream group, the whole run goes on the lanes that batch ran on: this batch's first
      * forward sweep follows that batch's LAST FORWARD sweep on the forward lane and shares the SIMDs with its last

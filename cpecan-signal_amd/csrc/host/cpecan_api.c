@@ -777,60 +777,8 @@ static cpecan_ctx *context(void) {
     return ctx;
 }
 
-/* ---- the six machines of the GPU path: one table row each, and run_reads in steps over one record ---- */
-typedef enum { /* in the order of CPECAN_MACHINE_* (cpecan_hip.h) */
-    HM_STRAWMAN, HM_DNA5, HM_VANILLA, HM_HDP, HM_SM4, HM_ECHELON, HM_COUNT
-} HostMachine;
-
-typedef struct {
-    int64_t read, x1, y1;
-} ItemOrigin;
-
-/* One call of run_reads: its arguments and every buffer its steps allocate (run_release frees them all) */
-typedef struct {
-    const struct MachineRow *row;
-    int64_t n;
-    StateMachine **sMs;
-    Sequence **sXs, **sYs;
-    stList **anchorLists;
-    PairwiseAlignmentParameters *p;
-    bool raggedL, raggedR;
-    int mode, unbanded;
-    void *hmmOut;
-    /* dedupe_models: nModels structs of row->modelSize bytes, the state machine each was filled from */
-    void *models;
-    StateMachine **owner;
-    int32_t *modelOf, *ids, nModels;
-    /* pack_reads; nAnchorsGiven in the callers' lists, nAnchors packed (those past a read's last cell are left out) */
-    char *chars, *ychars;
-    double *events;
-    int64_t *anchors, *firstItem, nX, nY, nAnchorsGiven, nAnchors, nItems;
-    cpecan_item *items;
-    ItemOrigin *origin;
-} Run;
-
-typedef struct MachineRow {
-    /* recognition: StateMachineType(s), stateNumber, element getters of X and Y, what to say of other getters */
-    StateMachineType type, type2;
-    int64_t stateNumber;
-    void *(*getX)(void *, int64_t), *(*getY)(void *, int64_t);
-    const char *gettersText;
-    /* input geometry: chars a k-mer sequence spans beyond its length; Y as characters instead of events */
-    int64_t xPad;
-    bool yChars;
-    /* modes: what to say of an E-step where add_expectations is NULL; the same for unbanded == 2 */
-    const char *refusal;
-    bool noSingleBand;
-    bool echelonRuns; /* a cell emits runs of pairs: the look-ahead of pack_items, append_diagonals_upwards */
-    /* model: size, fill from a state machine, "the same model" (NULL: the same StateMachine), upload */
-    size_t modelSize;
-    void (*fill)(StateMachine *sM, void *slot);
-    bool (*same)(const void *a, const void *b);
-    void (*models_create)(cpecan_ctx *ctx, const void *models, int32_t nModels, int32_t *ids);
-    void (*batch_create)(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch);
-    void (*add_expectations)(const Run *r, cpecan_batch *batch);
-} MachineRow;
-
+/* ---- the six machines of the GPU path: one table row each, and run_reads in steps over one record (Run, MachineRow:
+ * cpecan_host_private.h, which the stream of cpecan_stream.c shares) ---- */
 /* ---- models ---- */
 static void fill_sm3(StateMachine *sM, void *slot) {
     const StateMachine3 *s3 = (const StateMachine3 *) sM;
@@ -885,12 +833,12 @@ static void fill_echelon(StateMachine *sM, void *slot) {
     m->gap_y_probs = sM->EMISSION_GAP_Y_PROBS;
 }
 /* (the strawMan and vanilla calls derive tables on the host: threads 0, all cores) */
-static void models_sm3(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_models_create(c, m, n, 0, ids)); }
-static void models_sm5(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_models5_create(c, m, n, ids)); }
-static void models_vanilla(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_modelsv_create(c, m, n, 0, ids)); }
-static void models_hdp(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_modelsh_create(c, m, n, ids)); }
-static void models_sm4(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_models4_create(c, m, n, ids)); }
-static void models_echelon(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { CHECK(cpecan_hip_modelse_create(c, m, n, ids)); }
+static int models_sm3(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { return cpecan_hip_models_create(c, m, n, 0, ids); }
+static int models_sm5(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { return cpecan_hip_models5_create(c, m, n, ids); }
+static int models_vanilla(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { return cpecan_hip_modelsv_create(c, m, n, 0, ids); }
+static int models_hdp(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { return cpecan_hip_modelsh_create(c, m, n, ids); }
+static int models_sm4(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { return cpecan_hip_models4_create(c, m, n, ids); }
+static int models_echelon(cpecan_ctx *c, const void *m, int32_t n, int32_t *ids) { return cpecan_hip_modelse_create(c, m, n, ids); }
 
 /* ---- batches: each machine's create call with its own flags ---- */
 static int32_t unbanded_flag(const Run *r) { return r->unbanded == 1 ? CPECAN_FLAG_UNBANDED : 0; }
@@ -906,19 +854,20 @@ static int32_t vanilla_fused_estep_flags(void) {
 }
 /* what every create call takes of the record; y: the events, or the characters of a DNA read */
 #define PACKED(r, y) (r)->items, (r)->nItems, (r)->chars, (r)->nX, (y), (r)->nY, (r)->anchors, (r)->nAnchors
-static void batch_sm3(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
-    /* (one batch per call, nothing chained behind it: the smaller footprint) */
-    CHECK(cpecan_hip_batch_create(ctx, PACKED(r, r->events), bp, r->mode ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
-                                  CPECAN_KERNEL_AUTO, unbanded_flag(r) | CPECAN_FLAG_SMALL_FOOTPRINT, batch));
+/* (one batch per call, or a chunk of a stream that is to fit a budget: the smaller footprint) */
+#define SM3_POSTERIOR_FLAGS CPECAN_FLAG_SMALL_FOOTPRINT
+static int batch_sm3(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    return cpecan_hip_batch_create(ctx, PACKED(r, r->events), bp, r->mode ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
+                                  CPECAN_KERNEL_AUTO, unbanded_flag(r) | SM3_POSTERIOR_FLAGS, batch);
 }
-static void batch_dna(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
-    CHECK(cpecan_hip_batch_create_dna(ctx, PACKED(r, r->ychars), bp, unbanded_flag(r) | estep_flag(r), batch));
+static int batch_dna(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    return cpecan_hip_batch_create_dna(ctx, PACKED(r, r->ychars), bp, unbanded_flag(r) | estep_flag(r), batch);
 }
-static void batch_vanilla(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+static int batch_vanilla(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     const int32_t fused = r->mode ? vanilla_fused_estep_flags() : 0;
-    CHECK(cpecan_hip_batch_create_vanilla(ctx, PACKED(r, r->events), bp, unbanded_flag(r) | estep_flag(r) | fused, batch));
+    return cpecan_hip_batch_create_vanilla(ctx, PACKED(r, r->events), bp, unbanded_flag(r) | estep_flag(r) | fused, batch);
 }
-static void batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+static int batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     cpecan_band_params own = *bp;
     if (r->mode) own.threshold = ((HdpHmmExpectations *) r->hmmOut)->threshold; /* the assignment bar */
     /* CPECAN_HDP_FUSED_ESTEP=1, read per call: the E-step summed inside the sweep back on the wave kernels at two and three
@@ -932,13 +881,13 @@ static void batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *b
     const int32_t fused = (r->mode && fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_HDP_FUSED_ESTEP : 0) |
                           (r->mode && fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP : 0) |
                           (r->mode && fusedFour && atoi(fusedFour) == 1 ? CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP : 0);
-    CHECK(cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | fused, batch));
+    return cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | fused, batch);
 }
-static void batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
-    CHECK(cpecan_hip_batch_create_sm4(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch));
+static int batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    return cpecan_hip_batch_create_sm4(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch);
 }
-static void batch_echelon(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
-    CHECK(cpecan_hip_batch_create_echelon(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch));
+static int batch_echelon(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
+    return cpecan_hip_batch_create_echelon(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch);
 }
 
 /* ---- expectations: the device's per-model sums added into the caller's struct ---- */
@@ -1014,7 +963,7 @@ static void expect_hdp(const Run *r, cpecan_batch *batch) {
 #define ECHELON_REFUSAL                                                                                              \
     "cpecan: the echelon machine has posterior decode only, through getAlignedPairsUsingAnchors, "                   \
     "getAlignedPairsWithoutBanding or getAlignedPairsUsingAnchorsBatch (the reference has no expectations for it)"
-static const MachineRow MACHINES[HM_COUNT] = {
+const MachineRow MACHINES[HM_COUNT] = {
     [HM_STRAWMAN] = { threeState, threeState, 3, sequence_getKmer, sequence_getEvent,
                       "cpecan: the GPU path needs sequence_getKmer / sequence_getEvent element getters",
                       KMER_LENGTH - 1, false, NULL, false, false,
@@ -1043,7 +992,7 @@ static const MachineRow MACHINES[HM_COUNT] = {
 };
 
 /* the machine of a read, or no return: anything but the six combinations of the table is not on the GPU path */
-static HostMachine check_known_combination(StateMachine *sM, Sequence *sX, Sequence *sY) {
+HostMachine check_known_combination(StateMachine *sM, Sequence *sX, Sequence *sY) {
     if (!cpecan_sm_functions_known(sM))
         die("cpecan: this StateMachine carries a cellCalculate or emission function of the caller's own; the GPU path "
             "implements the reference's models only (symbol, strawMan, vanilla two-distribution and HDP emissions) "
@@ -1061,7 +1010,7 @@ static HostMachine check_known_combination(StateMachine *sM, Sequence *sX, Seque
 
 /* ---- the steps of run_reads ---- */
 /* the machine of the call (read 0's; every read must be of it) and the sizes of the packed inputs */
-static void size_inputs(Run *r) {
+void size_inputs(Run *r) {
     const HostMachine kind = r->n > 0 ? check_known_combination(r->sMs[0], r->sXs[0], r->sYs[0]) : HM_STRAWMAN;
     r->row = &MACHINES[kind];
     if ((r->mode != 0 && !r->row->add_expectations) || (r->unbanded == 2 && r->row->noSingleBand))
@@ -1076,8 +1025,10 @@ static void size_inputs(Run *r) {
     }
 }
 
-/* one device model per distinct model among the reads; modelOf[i] is read i's */
-static void dedupe_models(Run *r, cpecan_ctx *ctx) {
+/* one device model per distinct model among the reads; modelOf[i] is read i's.  r->records (the stream): read i's
+ * model record as row->fill left it when the read was submitted, in place of a fill from the machine now.  Returns the
+ * C-ABI's code: a context with a memory limit may refuse the tables (CPECAN_ELIMIT). */
+int dedupe_models(Run *r, cpecan_ctx *ctx) {
     const MachineRow *row = r->row;
     r->models = malloc(row->modelSize * (size_t) (r->n + 1));
     r->owner = malloc(sizeof(StateMachine *) * (size_t) (r->n + 1));
@@ -1085,7 +1036,8 @@ static void dedupe_models(Run *r, cpecan_ctx *ctx) {
     for (int64_t i = 0; i < r->n; i++) {
         char *candidate = (char *) r->models + row->modelSize * (size_t) r->nModels;
         int32_t found = -1;
-        row->fill(r->sMs[i], candidate);
+        if (r->records) memcpy(candidate, (const char *) r->records + row->modelSize * (size_t) i, row->modelSize);
+        else row->fill(r->sMs[i], candidate);
         for (int32_t k = 0; k < r->nModels && found < 0; k++) {
             const void *known = (char *) r->models + row->modelSize * (size_t) k;
             if (row->same ? row->same(known, candidate) : r->owner[k] == r->sMs[i]) found = k;
@@ -1098,7 +1050,7 @@ static void dedupe_models(Run *r, cpecan_ctx *ctx) {
     }
     r->ids = malloc(sizeof(int32_t) * (size_t) r->nModels);
     CHECK(cpecan_hip_models_clear(ctx));
-    row->models_create(ctx, r->models, r->nModels, r->ids);
+    return row->models_create(ctx, r->models, r->nModels, r->ids);
 }
 
 /* the items of read i: one, or the reference's split at large anchor-free gaps
@@ -1147,7 +1099,7 @@ static void pack_items(Run *r, int64_t i, int64_t xo, int64_t yo, int64_t *capIt
 }
 
 /* sequences, events and anchors of all reads into one buffer each, and the reads' items (firstItem[i] .. firstItem[i+1]) */
-static void pack_reads(Run *r) {
+void pack_reads(Run *r) {
     const MachineRow *row = r->row;
     r->chars = malloc((size_t) r->nX + 8);
     r->events = malloc(row->yChars ? 8 : sizeof(double) * 3 * (size_t) (r->nY + 1));
@@ -1168,12 +1120,19 @@ static void pack_reads(Run *r) {
     r->firstItem[r->n] = r->nItems;
 }
 
-static cpecan_batch *create_batch(Run *r, cpecan_ctx *ctx) {
+/* the kernel argument and the flags of a posterior batch of the machine, as its create call above passes them: what
+ * cpecan_hip_plan_dispatch is asked with for a read of the stream */
+void posterior_request(const MachineRow *row, int32_t *kernel, int32_t *flags) {
+    const HostMachine m = (HostMachine) (row - MACHINES);
+    *kernel = m == HM_DNA5 || m == HM_SM4 || m == HM_ECHELON ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
+    *flags = m == HM_STRAWMAN ? SM3_POSTERIOR_FLAGS : 0;
+}
+
+int create_batch(Run *r, cpecan_ctx *ctx, cpecan_batch **batch) {
     const cpecan_band_params bp = { r->p->threshold, r->p->minDiagsBetweenTraceBack, r->p->traceBackDiagonals,
                                     r->p->diagonalExpansion };
-    cpecan_batch *batch = NULL;
-    r->row->batch_create(ctx, r, &bp, &batch);
-    return batch;
+    *batch = NULL;
+    return r->row->batch_create(ctx, r, &bp, batch);
 }
 
 /* ---- the three orders the reference's entry points leave an item's pairs in ---- */
@@ -1209,25 +1168,35 @@ static void append_tail_first(stList *list, const int64_t *tri, int64_t np, cons
     for (int64_t q = np - 1; q >= 0; q--) append_triple(list, tri + 3 * q, o->x1, o->y1);
 }
 
-/* lists[i]: the aligned pairs of read i, item after item (batch NULL: there was nothing to run) */
-static void collect_pairs(const Run *r, cpecan_batch *batch, stList **lists) {
+/* lists[i]: the aligned pairs of read i, item after item (batch NULL: there was nothing to run).  Returns the C-ABI's
+ * code; where it is not CPECAN_OK (a context with a memory limit: the readback's buffers), no list is left behind. */
+int collect_pairs(const Run *r, cpecan_batch *batch, stList **lists) {
     int64_t *np = malloc(sizeof(int64_t) * (size_t) (r->nItems + 1));
-    if (batch) CHECK(cpecan_hip_batch_counts(batch, np, NULL, NULL));
-    for (int64_t i = 0; i < r->n; i++) {
+    int rc = batch ? cpecan_hip_batch_counts(batch, np, NULL, NULL) : CPECAN_OK;
+    for (int64_t i = 0; i < r->n; i++) lists[i] = NULL;
+    for (int64_t i = 0; rc == CPECAN_OK && i < r->n; i++) {
         lists[i] = stList_construct3(0, (void (*)(void *)) stIntTuple_destruct);
-        for (int64_t k = r->firstItem[i]; batch && k < r->firstItem[i + 1]; k++) {
+        for (int64_t k = r->firstItem[i]; rc == CPECAN_OK && batch && k < r->firstItem[i + 1]; k++) {
             int64_t *tri = malloc(sizeof(int64_t) * 3 * (size_t) (np[k] + 1));
-            CHECK(cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, np[k] + 1));
+            if ((rc = cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, np[k] + 1)) != CPECAN_OK) {
+                free(tri);
+                break;
+            }
             if (r->unbanded == 2) append_emission_order(lists[i], tri, np[k]);
             else if (r->unbanded) append_diagonals_upwards(lists[i], tri, np[k], r->row->echelonRuns);
             else append_tail_first(lists[i], tri, np[k], &r->origin[k]);
             free(tri);
         }
     }
+    for (int64_t i = 0; rc != CPECAN_OK && i < r->n; i++) {
+        stList_destruct(lists[i]);
+        lists[i] = NULL;
+    }
     free(np);
+    return rc;
 }
 
-static void run_release(Run *r) {
+void run_release(Run *r) {
     free(r->models); free(r->owner); free(r->modelOf); free(r->ids);
     free(r->chars); free(r->ychars); free(r->events); free(r->anchors); free(r->firstItem);
     free(r->items); free(r->origin);
@@ -1243,15 +1212,15 @@ static void run_reads(int64_t n, StateMachine **sMs, Sequence **sXs, Sequence **
     Run r = { .n = n, .sMs = sMs, .sXs = sXs, .sYs = sYs, .anchorLists = anchorLists, .p = p, .raggedL = raggedL,
               .raggedR = raggedR, .mode = mode, .unbanded = unbanded, .hmmOut = hmmOut };
     size_inputs(&r);
-    dedupe_models(&r, ctx);
+    CHECK(dedupe_models(&r, ctx));
     pack_reads(&r);
     cpecan_batch *batch = NULL;
     if (r.nItems > 0) {
-        batch = create_batch(&r, ctx);
+        CHECK(create_batch(&r, ctx, &batch));
         CHECK(cpecan_hip_batch_run(batch));
         CHECK(cpecan_hip_batch_sync(batch));
     }
-    if (mode == 0) collect_pairs(&r, batch, lists);
+    if (mode == 0) CHECK(collect_pairs(&r, batch, lists));
     else if (batch) r.row->add_expectations(&r, batch);
     if (batch) CHECK(cpecan_hip_batch_destroy(batch));
     run_release(&r);

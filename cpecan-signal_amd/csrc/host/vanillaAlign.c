@@ -294,9 +294,8 @@ typedef struct {
 
 static int name_order(const void *a, const void *b) { return strcmp(*(char *const *) a, *(char *const *) b); }
 
-static int align_directory(const char *dir, const char *outDir, const char *referenceSequence, StateMachineType sMtype,
-                           const char *modelFiles[2], const char *hmmFiles[2], NanoporeHDP *nHdps[2],
-                           PairwiseAlignmentParameters *p, const char *substitute) {
+/* the sorted names of the .npRead files of a directory (without the suffix) */
+static char **read_names(const char *dir, int64_t *count) {
     DIR *d = opendir(dir);
     if (!d) die("vanillaAlign - ERROR: cannot open the directory %s", dir);
     char **names = NULL;
@@ -313,81 +312,119 @@ static int align_directory(const char *dir, const char *outDir, const char *refe
     if (n == 0) die("vanillaAlign - ERROR: no .npRead file in %s", dir);
     qsort(names, (size_t) n, sizeof(char *), name_order);
     fprintf(stderr, "vanillaAlign - %lld reads in %s\n", (long long) n, dir);
+    *count = n;
+    return names;
+}
 
+/* <dir>/<name>.npRead and its guide alignment <dir>/<name>.cigar: the read, the two targets, the event sequences, the anchors */
+static void load_batch_read(BatchRead *r, const char *dir, char *name, const char *referenceSequence, StateMachineType sMtype,
+                            PairwiseAlignmentParameters *p) {
+    r->name = name;
+    const size_t room = strlen(dir) + strlen(name) + 16;
+    char *path = malloc(room);
+    snprintf(path, room, "%s/%s.npRead", dir, name);
+    r->npRead = nanopore_loadNanoporeReadFromFile(path);
+    if (sMtype == threeStateHdp) nanopore_descaleNanoporeRead(r->npRead);
+    snprintf(path, room, "%s/%s.cigar", dir, name);
+    FILE *f = fopen(path, "r");
+    if (!f) die("vanillaAlign - ERROR: no guide alignment %s", path);
+    r->pA = cigar_read(f);
+    fclose(f);
+    free(path);
+    GuideAlignment *pA = r->pA;
+    r->trimmedRefSeq = pA->strand1 ? substring(referenceSequence, pA->start1, pA->end1 - pA->start1)
+                                   : substring(referenceSequence, pA->end1, pA->start1 - pA->end1);
+    if (!pA->strand1) {
+        char *rc = reverse_complement(r->trimmedRefSeq);
+        free(r->trimmedRefSeq);
+        r->trimmedRefSeq = rc;
+    }
+    r->rcTrimmedRefSeq = reverse_complement(r->trimmedRefSeq);
+    r->events[0] = event_sequence_from_guide(r->npRead->templateEvents, pA->start2, pA->end2, r->npRead->templateEventMap);
+    r->events[1] = event_sequence_from_guide(r->npRead->complementEvents, pA->start2, pA->end2, r->npRead->complementEventMap);
+    const int64_t start1 = pA->start1, end1 = pA->end1;
+    const bool forward = pA->strand1;
+    r->anchorPairs = guide_to_anchor_pairs(pA, p); /* (re-bases the target interval in pA) */
+    r->nAnchors = stList_length(r->anchorPairs);
+    pA->start1 = start1; /* the TSV rows need the original offsets */
+    pA->end1 = end1;
+    pA->strand1 = forward;
+}
+
+/* what one strand (0: template, 1: complement) of a loaded read is aligned with */
+static void strand_inputs(BatchRead *r, int st, StateMachineType sMtype, const char *modelFiles[2], const char *hmmFiles[2],
+                          NanoporeHDP *nHdps[2], StateMachine **sM, Sequence **sX, Sequence **sY, stList **anchors) {
+    const NanoporeReadAdjustmentParameters npp = st == 0 ? r->npRead->templateParams : r->npRead->complementParams;
+    *sM = build_state_machine(modelFiles[st], npp, sMtype, st == 0 ? template : complement, nHdps[st]);
+    if (hmmFiles[st]) hmmContinuous_loadSignalHmm(hmmFiles[st], *sM, (*sM)->type);
+    /* (as in the single-read driver, --substitute only applies when expectations are collected) */
+    char *target = st == 0 ? r->trimmedRefSeq : r->rcTrimmedRefSeq;
+    *sX = sequence_construct2(sequence_correctSeqLength((int64_t) strlen(target), event), target, target_getter(sMtype),
+                              sequence_sliceNucleotideSequence2);
+    *sY = r->events[st];
+    *anchors = remapped_anchor_pairs(r->anchorPairs, st == 0 ? r->npRead->templateEventMap : r->npRead->complementEventMap,
+                                     r->pA->start2);
+}
+
+/* the strand's rows appended to `out`; returns its score (scoreByPosteriorProbabilityIgnoringGaps) */
+static double write_strand(const char *out, BatchRead *r, int st, StateMachine *sM, stList *pairs) {
+    GuideAlignment *pA = r->pA;
+    double total = 0.0;
+    for (int64_t q = 0; q < stList_length(pairs); q++) total += (double) stIntTuple_get(stList_get(pairs, q), 0);
+    const double score = 100.0 * total / ((double) stList_length(pairs) * PAIR_ALIGNMENT_PROB_1);
+    stList_sort(pairs, sortByXPlusYCoordinate2);
+    const NanoporeReadAdjustmentParameters npp = st == 0 ? r->npRead->templateParams : r->npRead->complementParams;
+    const int64_t *map = st == 0 ? r->npRead->templateEventMap : r->npRead->complementEventMap;
+    writePosteriorProbs((char *) out, r->name, sM->EMISSION_MATCH_PROBS, npp.scale, npp.shift,
+                        st == 0 ? r->npRead->templateEvents : r->npRead->complementEvents,
+                        st == 0 ? r->trimmedRefSeq : r->rcTrimmedRefSeq, pA->strand1, pA->contig1, map[pA->start2],
+                        st == 0 ? pA->start1 : pA->end1, pairs, st == 0 ? template : complement);
+    return score;
+}
+
+static char *tsv_path(const char *outDir, const char *name) {
+    const size_t room = strlen(outDir) + strlen(name) + 16;
+    char *out = malloc(room);
+    snprintf(out, room, "%s/%s.tsv", outDir, name);
+    return out;
+}
+
+static void free_batch_read(BatchRead *r) {
+    if (r->events[0]) sequence_sequenceDestroy(r->events[0]);
+    if (r->events[1]) sequence_sequenceDestroy(r->events[1]);
+    if (r->anchorPairs) stList_destruct(r->anchorPairs);
+    nanopore_nanoporeReadDestruct(r->npRead);
+    free(r->pA->ops);
+    free(r->pA);
+    free(r->trimmedRefSeq);
+    free(r->rcTrimmedRefSeq);
+    free(r->name);
+}
+
+static int align_directory(const char *dir, const char *outDir, const char *referenceSequence, StateMachineType sMtype,
+                           const char *modelFiles[2], const char *hmmFiles[2], NanoporeHDP *nHdps[2],
+                           PairwiseAlignmentParameters *p, const char *substitute) {
+    int64_t n;
+    char **names = read_names(dir, &n);
     BatchRead *reads = calloc((size_t) n, sizeof(BatchRead));
     StateMachine **sMs = malloc(sizeof(StateMachine *) * 2 * (size_t) n);
     Sequence **sXs = malloc(sizeof(Sequence *) * 2 * (size_t) n), **sYs = malloc(sizeof(Sequence *) * 2 * (size_t) n);
     stList **anchors = malloc(sizeof(stList *) * 2 * (size_t) n);
-    char **targets = malloc(sizeof(char *) * 2 * (size_t) n);
     for (int64_t i = 0; i < n; i++) {
-        BatchRead *r = &reads[i];
-        r->name = names[i];
-        const size_t room = strlen(dir) + strlen(names[i]) + 16;
-        char *path = malloc(room);
-        snprintf(path, room, "%s/%s.npRead", dir, names[i]);
-        r->npRead = nanopore_loadNanoporeReadFromFile(path);
-        if (sMtype == threeStateHdp) nanopore_descaleNanoporeRead(r->npRead);
-        snprintf(path, room, "%s/%s.cigar", dir, names[i]);
-        FILE *f = fopen(path, "r");
-        if (!f) die("vanillaAlign - ERROR: no guide alignment %s", path);
-        r->pA = cigar_read(f);
-        fclose(f);
-        free(path);
-        GuideAlignment *pA = r->pA;
-        r->trimmedRefSeq = pA->strand1 ? substring(referenceSequence, pA->start1, pA->end1 - pA->start1)
-                                       : substring(referenceSequence, pA->end1, pA->start1 - pA->end1);
-        if (!pA->strand1) {
-            char *rc = reverse_complement(r->trimmedRefSeq);
-            free(r->trimmedRefSeq);
-            r->trimmedRefSeq = rc;
-        }
-        r->rcTrimmedRefSeq = reverse_complement(r->trimmedRefSeq);
-        r->events[0] = event_sequence_from_guide(r->npRead->templateEvents, pA->start2, pA->end2, r->npRead->templateEventMap);
-        r->events[1] = event_sequence_from_guide(r->npRead->complementEvents, pA->start2, pA->end2, r->npRead->complementEventMap);
-        const int64_t start1 = pA->start1, end1 = pA->end1;
-        const bool forward = pA->strand1;
-        r->anchorPairs = guide_to_anchor_pairs(pA, p); /* (re-bases the target interval in pA) */
-        r->nAnchors = stList_length(r->anchorPairs);
-        pA->start1 = start1; /* the TSV rows need the original offsets */
-        pA->end1 = end1;
-        pA->strand1 = forward;
+        load_batch_read(&reads[i], dir, names[i], referenceSequence, sMtype, p);
         for (int st = 0; st < 2; st++) {
             const int64_t k = 2 * i + st;
-            const NanoporeReadAdjustmentParameters npp = st == 0 ? r->npRead->templateParams : r->npRead->complementParams;
-            sMs[k] = build_state_machine(modelFiles[st], npp, sMtype, st == 0 ? template : complement, nHdps[st]);
-            if (hmmFiles[st]) hmmContinuous_loadSignalHmm(hmmFiles[st], sMs[k], sMs[k]->type);
-            /* (as in the single-read driver, --substitute only applies when expectations are collected) */
-            targets[k] = st == 0 ? r->trimmedRefSeq : r->rcTrimmedRefSeq;
-            sXs[k] = sequence_construct2(sequence_correctSeqLength((int64_t) strlen(targets[k]), event), targets[k],
-                                         target_getter(sMtype), sequence_sliceNucleotideSequence2);
-            sYs[k] = r->events[st];
-            anchors[k] = remapped_anchor_pairs(r->anchorPairs, st == 0 ? r->npRead->templateEventMap : r->npRead->complementEventMap,
-                                               pA->start2);
+            strand_inputs(&reads[i], st, sMtype, modelFiles, hmmFiles, nHdps, &sMs[k], &sXs[k], &sYs[k], &anchors[k]);
         }
     }
     fprintf(stderr, "vanillaAlign - aligning %lld strands as one batch\n", (long long) (2 * n));
     stList **pairs = getAlignedPairsUsingAnchorsBatch(2 * n, sMs, sXs, sYs, anchors, p, 1, 1);
     for (int64_t i = 0; i < n; i++) {
         BatchRead *r = &reads[i];
-        GuideAlignment *pA = r->pA;
-        const size_t room = strlen(outDir) + strlen(r->name) + 16;
-        char *out = malloc(room);
-        snprintf(out, room, "%s/%s.tsv", outDir, r->name);
+        char *out = tsv_path(outDir, r->name);
         remove(out); /* (writePosteriorProbs appends) */
         double score[2];
-        for (int st = 0; st < 2; st++) {
-            const int64_t k = 2 * i + st;
-            double total = 0.0; /* scoreByPosteriorProbabilityIgnoringGaps */
-            for (int64_t q = 0; q < stList_length(pairs[k]); q++) total += (double) stIntTuple_get(stList_get(pairs[k], q), 0);
-            score[st] = 100.0 * total / ((double) stList_length(pairs[k]) * PAIR_ALIGNMENT_PROB_1);
-            stList_sort(pairs[k], sortByXPlusYCoordinate2);
-            const NanoporeReadAdjustmentParameters npp = st == 0 ? r->npRead->templateParams : r->npRead->complementParams;
-            const int64_t *map = st == 0 ? r->npRead->templateEventMap : r->npRead->complementEventMap;
-            writePosteriorProbs(out, r->name, sMs[k]->EMISSION_MATCH_PROBS, npp.scale, npp.shift,
-                                st == 0 ? r->npRead->templateEvents : r->npRead->complementEvents,
-                                st == 0 ? r->trimmedRefSeq : r->rcTrimmedRefSeq, pA->strand1, pA->contig1, map[pA->start2],
-                                st == 0 ? pA->start1 : pA->end1, pairs[k], st == 0 ? template : complement);
-        }
+        for (int st = 0; st < 2; st++) score[st] = write_strand(out, r, st, sMs[2 * i + st], pairs[2 * i + st]);
         fprintf(stdout, "%s %lld\t%lld(%f)\t%lld(%f)\n", r->name, (long long) r->nAnchors, (long long) stList_length(pairs[2 * i]),
                 score[0], (long long) stList_length(pairs[2 * i + 1]), score[1]);
         free(out);
@@ -399,25 +436,120 @@ static int align_directory(const char *dir, const char *outDir, const char *refe
         stateMachine_destruct(sMs[k]);
     }
     (void) substitute;
-    for (int64_t i = 0; i < n; i++) {
-        sequence_sequenceDestroy(reads[i].events[0]);
-        sequence_sequenceDestroy(reads[i].events[1]);
-        stList_destruct(reads[i].anchorPairs);
-        nanopore_nanoporeReadDestruct(reads[i].npRead);
-        free(reads[i].pA->ops);
-        free(reads[i].pA);
-        free(reads[i].trimmedRefSeq);
-        free(reads[i].rcTrimmedRefSeq);
-        free(reads[i].name);
-    }
-    free(pairs); free(reads); free(sMs); free(sXs); free(sYs); free(anchors); free(targets); free(names);
+    for (int64_t i = 0; i < n; i++) free_batch_read(&reads[i]);
+    free(pairs); free(reads); free(sMs); free(sXs); free(sYs); free(anchors); free(names);
     fprintf(stderr, "vanillaAlign - SUCCESS: finished alignment of %lld reads, exiting\n", (long long) n);
     return 0;
+}
+
+/* ---- the same directory through the stream (--stream): reads are loaded, submitted and let go one at a time, the chunks
+ * run chained within a device-memory budget, and a strand's rows are written when its result arrives.  What a strand's
+ * rows are written from -- the read's events and event map, its two targets, its machine -- stays until both strands of
+ * the read are written; the event sequences and anchor lists go as soon as the strands are submitted. ----------------- */
+typedef struct {
+    BatchRead r;
+    StateMachine *sM[2];
+    Sequence *sX[2];
+    char *out, *summary; /* the TSV's path; the read's summary line, once both strands are written */
+    stList *held;        /* the complement's pairs, where they arrived before the template's */
+    int written, refused;
+    int64_t nPairs[2];
+    double score[2];
+} StreamRead;
+typedef struct {
+    StreamRead *reads;
+    int64_t nRefused;
+} StreamDirectory;
+
+static void stream_strand_done(StreamRead *sr, int st, stList *pairs) {
+    sr->nPairs[st] = stList_length(pairs);
+    sr->score[st] = write_strand(sr->out, &sr->r, st, sr->sM[st], pairs);
+    stList_destruct(pairs);
+    sr->written++;
+}
+
+/* (the stream never runs two of these at once) */
+static void stream_result(void *arg, int64_t tag, stList *pairs) {
+    StreamDirectory *sd = arg;
+    StreamRead *sr = &sd->reads[tag / 2];
+    const int st = (int) (tag % 2);
+    if (!pairs) {
+        fprintf(stderr, "vanillaAlign - ERROR: the %s strand of %s does not fit the device-memory budget, not aligned\n",
+                st == 0 ? "template" : "complement", sr->r.name);
+        sr->refused++;
+        sd->nRefused++;
+    } else if (st == 1 && sr->written == 0 && sr->refused == 0)
+        sr->held = pairs; /* template first, as writePosteriorProbs appends them without --stream */
+    else
+        stream_strand_done(sr, st, pairs);
+    if (sr->held && (sr->written == 1 || sr->refused)) {
+        stList *held = sr->held;
+        sr->held = NULL;
+        stream_strand_done(sr, 1, held);
+    }
+    if (sr->written + sr->refused < 2) return;
+    if (sr->written == 2) {
+        const size_t room = strlen(sr->r.name) + 160;
+        sr->summary = malloc(room);
+        snprintf(sr->summary, room, "%s %lld\t%lld(%f)\t%lld(%f)\n", sr->r.name, (long long) sr->r.nAnchors,
+                 (long long) sr->nPairs[0], sr->score[0], (long long) sr->nPairs[1], sr->score[1]);
+    }
+    for (int k = 0; k < 2; k++) {
+        sequence_sequenceDestroy(sr->sX[k]);
+        stateMachine_destruct(sr->sM[k]);
+    }
+    free(sr->out);
+    free_batch_read(&sr->r);
+}
+
+static int align_directory_stream(const char *dir, const char *outDir, const char *referenceSequence, StateMachineType sMtype,
+                                  const char *modelFiles[2], const char *hmmFiles[2], NanoporeHDP *nHdps[2],
+                                  PairwiseAlignmentParameters *p, const cpecan_stream_options *options) {
+    int64_t n;
+    char **names = read_names(dir, &n);
+    StreamDirectory sd = { calloc((size_t) n, sizeof(StreamRead)), 0 };
+    cpecan_stream *stream = cpecan_stream_open(p, 1, 1, options, stream_result, NULL, &sd);
+    for (int64_t i = 0; i < n; i++) {
+        StreamRead *sr = &sd.reads[i];
+        load_batch_read(&sr->r, dir, names[i], referenceSequence, sMtype, p);
+        sr->out = tsv_path(outDir, names[i]);
+        remove(sr->out); /* (writePosteriorProbs appends) */
+        Sequence *sY[2];
+        stList *anchors[2];
+        for (int st = 0; st < 2; st++)
+            strand_inputs(&sr->r, st, sMtype, modelFiles, hmmFiles, nHdps, &sr->sM[st], &sr->sX[st], &sY[st], &anchors[st]);
+        /* (nothing of the read may be let go between the two: the template's result can arrive at once) */
+        BatchRead *r = &sr->r;
+        Sequence *events[2] = { r->events[0], r->events[1] };
+        stList *anchorPairs = r->anchorPairs;
+        r->events[0] = r->events[1] = NULL;
+        r->anchorPairs = NULL;
+        for (int st = 0; st < 2; st++) cpecan_stream_submit(stream, 2 * i + st, sr->sM[st], sr->sX[st], sY[st], anchors[st]);
+        for (int st = 0; st < 2; st++) {
+            stList_destruct(anchors[st]);
+            sequence_sequenceDestroy(events[st]);
+        }
+        stList_destruct(anchorPairs);
+    }
+    int64_t nChunks = 0, nRefused = 0, peak = 0;
+    cpecan_stream_close(stream, &nChunks, &nRefused, &peak);
+    for (int64_t i = 0; i < n; i++) { /* in name order, as without --stream */
+        if (sd.reads[i].summary) fputs(sd.reads[i].summary, stdout);
+        free(sd.reads[i].summary);
+    }
+    free(sd.reads);
+    free(names);
+    fprintf(stderr, "vanillaAlign - stream: %lld chunks, at most %lld device bytes, %lld strands refused\n", (long long) nChunks,
+            (long long) peak, (long long) nRefused);
+    if (nRefused == 0) fprintf(stderr, "vanillaAlign - SUCCESS: finished alignment of %lld reads, exiting\n", (long long) n);
+    return nRefused == 0 ? 0 : 1;
 }
 
 int main(int argc, char *argv[]) {
     StateMachineType sMtype = vanilla;
     const char *npReadDir = NULL, *outDir = NULL;
+    bool stream = false; /* --stream: the directory through cpecan_stream_*; --streamReads N, --streamGB X: its options */
+    cpecan_stream_options streamOptions = { 0, 0, 0, 0, 0 };
     int64_t diagExpansion = 50, constraintTrim = 14;
     double threshold = 0.01;
     const char *templateModelFile = "../../cPecan/models/template_median68pA.model";
@@ -437,9 +569,11 @@ int main(int argc, char *argv[]) {
         { "complementHdp", required_argument, 0, 'w' }, { "templateExpectations", required_argument, 0, 't' },
         { "complementExpectations", required_argument, 0, 'c' }, { "diagonalExpansion", required_argument, 0, 'x' },
         { "threshold", required_argument, 0, 'D' }, { "constraintTrim", required_argument, 0, 'm' },
-        { "npReadDir", required_argument, 0, 'B' }, { "outDir", required_argument, 0, 'O' }, { 0, 0, 0, 0 } };
+        { "npReadDir", required_argument, 0, 'B' }, { "outDir", required_argument, 0, 'O' },
+        { "stream", no_argument, 0, 'S' }, { "streamReads", required_argument, 0, 'R' },
+        { "streamGB", required_argument, 0, 'G' }, { 0, 0, 0, 0 } };
     int key;
-    while ((key = getopt_long(argc, argv, "hsdfeUp:M:a:T:C:L:q:r:u:y:z:v:w:t:c:x:D:m:B:O:", long_options, NULL)) != -1) {
+    while ((key = getopt_long(argc, argv, "hsdfeUp:M:a:T:C:L:q:r:u:y:z:v:w:t:c:x:D:m:B:O:SR:G:", long_options, NULL)) != -1) {
         switch (key) {
         case 's': sMtype = threeState; break;
         case 'd': sMtype = threeStateHdp; break;
@@ -465,6 +599,9 @@ int main(int argc, char *argv[]) {
         case 'm': constraintTrim = atoll(optarg); break;
         case 'B': npReadDir = optarg; break;
         case 'O': outDir = optarg; break;
+        case 'S': stream = true; break;
+        case 'R': streamOptions.maxReadsPerChunk = atoll(optarg); break;
+        case 'G': streamOptions.deviceBytes = (int64_t) (atof(optarg) * (double) (1ll << 30)); break;
         default:
             fprintf(stderr, "vanillaAlign binary, meant to be used through the signalAlign program.\n");
             return 1;
@@ -474,6 +611,7 @@ int main(int argc, char *argv[]) {
         die("vanillaAlign - the echelon machine has no expectations (the reference has no expectation function for it)");
     if (sMtype == echelon && (templateHmmFile || complementHmmFile))
         die("vanillaAlign - LoadSignalHmm : unupported stateMachineType (no HMM files for the echelon machine)");
+    if (stream && !npReadDir) die("vanillaAlign - ERROR: --stream goes with --npReadDir and --outDir");
     if (npReadDir) { /* additive: a directory of reads as one GPU batch */
         if (!targetFile || !outDir) die("vanillaAlign - ERROR: --npReadDir needs --reference and --outDir");
         if (templateExpectationsFile || complementExpectationsFile)
@@ -486,7 +624,9 @@ int main(int argc, char *argv[]) {
         bp->constraintDiagonalTrim = constraintTrim;
         bp->diagonalExpansion = diagExpansion;
         char *reference = first_line(targetFile);
-        const int rc = align_directory(npReadDir, outDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp, substitute);
+        const int rc = stream ? align_directory_stream(npReadDir, outDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp,
+                                                       &streamOptions)
+                              : align_directory(npReadDir, outDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp, substitute);
         free(reference);
         pairwiseAlignmentBandingParameters_destruct(bp);
         if (nHdps[0]) destroy_nanopore_hdp(nHdps[0]);

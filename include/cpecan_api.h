@@ -559,6 +559,62 @@ stList **getAlignedPairsUsingAnchorsBatch(int64_t n, StateMachine **sMs, Sequenc
                                           bool alignmentHasRaggedLeftEnd,
                                           bool alignmentHasRaggedRightEnd);
 
+/* ---- the stream: reads one at a time, aligned in chained chunks within a device-memory budget -------------------
+ * Posterior decode of any number of reads of one machine kind (any of the six; a second kind ends the process with the
+ * batch call's "cannot mix" message).  Every read's list is what getAlignedPairsUsingAnchors gives for that read alone.
+ *
+ * Grouping.  A read's class is the kernel cpecan_hip_plan_dispatch names for it alone: its machine, the posterior mode, the
+ * flags this library passes for that machine, the widest band over its sub-alignments (cpecan_band_extent), whether the
+ * band's edges step by one, and for the vanilla machine whether it meets a k-mer that is none.  Reads of one class share
+ * chunks, so one read with a wide anchor jump (or an N under the vanilla machine) no longer sends its neighbours to the
+ * general kernel.  oneClass = 1: one class, chunks in submission order, as one batch call per chunk would cut them.
+ *
+ * Chunks.  A class's open group closes into a chunk when the next read would take it past maxReadsPerChunk or past the
+ * bytes predicted to fit deviceBytes / slots: cells (diagonals x widest band, summed over the read's sub-alignments)
+ * times the most bytes per cell a chunk of the class has held so far -- before the class's first chunk, times 64.  The
+ * prediction only sizes chunks; what holds the budget is that every slot's context carries deviceBytes / slots as its
+ * memory limit (cpecan_hip_ctx_set_memory_limit).  A chunk that meets CPECAN_ELIMIT in any of its calls is destroyed, cut
+ * in half and queued again as two (halvings counts the cuts behind a chunk); a chunk of one read that still meets it is
+ * refused: its result is a NULL list, the other reads are not affected and the stream goes on.
+ *
+ * Pipeline.  producerThreads host threads prepare closed chunks in closing order -- model tables, then the batch -- each
+ * on the context of a free slot, and queue each run with cpecan_hip_batch_run_after behind the run queued before it.  One
+ * consumer thread waits for each run in that order, collects its pairs, calls onResult once per read in the order of
+ * submission within the chunk, destroys the batch and frees the slot.  The two callbacks are never called at the same
+ * time, by any two threads.  onResult owns the list it is given.
+ *
+ * Memory.  submit copies the read's characters, events, anchors and model record; the sequences and the anchor list may
+ * be freed when it returns.  What the record points to (the state machine's emission tables, its NanoporeHDP) and the
+ * StateMachine itself must live until the read's result has been delivered.  submit blocks while `slots` chunks are alive
+ * and the read's group cannot take it, so the host holds about slots + open groups chunks of reads.  One thread submits. */
+typedef struct cpecan_stream cpecan_stream;
+typedef struct {
+    int64_t deviceBytes;      /* budget for all live chunks together; 0: the device cache's cap (CPECAN_ALLOC_CACHE_GB) */
+    int32_t slots;            /* chunks alive at once, each on a context of its own, >= 2; 0: 4 */
+    int32_t producerThreads;  /* 0: 2 */
+    int64_t maxReadsPerChunk; /* 0: 1024 */
+    int32_t oneClass;         /* 1: no grouping by kernel, chunks in submission order */
+} cpecan_stream_options;
+typedef struct {              /* one per chunk, as its run is queued */
+    int64_t index, nReads, nItems, deviceBytes; /* deviceBytes: held by the chunk's context, model tables included */
+    int32_t kernel, wave, rows, maxWidth, halvings; /* kernel: CPECAN_KERNEL_GENERAL or _SYSTOLIC; wave, rows: as
+                                                       cpecan_hip_plan_dispatch reports them (0, 0 on the general kernel) */
+} cpecan_stream_chunk;
+typedef void (*cpecan_stream_result_fn)(void *arg, int64_t tag, stList *alignedPairs); /* NULL list: the read was refused */
+typedef void (*cpecan_stream_chunk_fn)(void *arg, const cpecan_stream_chunk *chunk);   /* may be NULL */
+cpecan_stream *cpecan_stream_open(PairwiseAlignmentParameters *p, bool raggedL, bool raggedR, const cpecan_stream_options *o,
+                                  cpecan_stream_result_fn onResult, cpecan_stream_chunk_fn onChunk, void *arg);
+void cpecan_stream_submit(cpecan_stream *s, int64_t tag, StateMachine *sM, Sequence *sX, Sequence *sY, stList *anchors);
+void cpecan_stream_flush(cpecan_stream *s);   /* closes every open group, returns when all results are delivered */
+/* flushes, ends the threads and frees the stream.  *nChunks: chunks that ran; *nRefused: reads refused;
+ * *peakDeviceBytes: the sum of the slots' own high-water marks, an upper bound of what was held at once.  Any may be NULL. */
+void cpecan_stream_close(cpecan_stream *s, int64_t *nChunks, int64_t *nRefused, int64_t *peakDeviceBytes);
+/* Test hook: the chunking rule alone (csrc/host/cpecan_stream_plan.c), over n reads with classes classOf[i] and sizes
+ * cells[i] and one cell budget.  chunkOf[i] receives read i's chunk, chunks numbered as they close, rankOf[i] its place
+ * among that chunk's reads; returns the number of chunks. */
+int64_t cpecan_stream_plan_chunks(int64_t n, const int32_t *classOf, const int64_t *cells, int64_t maxReadsPerChunk,
+                                  int64_t cellBudget, int32_t oneClass, int64_t *chunkOf, int64_t *rankOf);
+
 /* Small exported helpers of the reference that none of its four GPU-backed machines calls (inc/stateMachine.h,
  * inc/emissionMatrix.h, inc/pairwiseAligner.h): plain host functions, same names, signatures and arithmetic. */
 void emissions_kmer_setMatchProbsToDefaults(double *emissionMatchProbs);  /* [625] impl/emissionMatrix.c:11 */

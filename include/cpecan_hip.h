@@ -24,6 +24,7 @@ extern "C" {
 #define CPECAN_EHIP (-3)       /* a HIP call failed (message in last_error)          */
 #define CPECAN_EOVERFLOW (-4)  /* an output capacity was too small                   */
 #define CPECAN_EBAND (-5)      /* anchors describe an invalid band (diagonal_construct throw) */
+#define CPECAN_ELIMIT (-6)     /* the context's device memory limit would be passed   */
 
 #define CPECAN_NUM_KMERS 4096
 #define CPECAN_KMER_LENGTH 6
@@ -40,6 +41,21 @@ int cpecan_hip_ctx_create(int device, cpecan_ctx **ctx);
 int cpecan_hip_ctx_destroy(cpecan_ctx *ctx);
 const char *cpecan_hip_last_error(void);
 const char *cpecan_hip_version(void);
+/* Device memory held on behalf of a context: the blocks of its model tables and of its live batches, each at the size
+ * the library's allocator handed it out (a reused block is up to a quarter larger than what was asked for).  *live: now;
+ * *peak: the most since the context was made or the peak was last reset (reset_peak != 0 sets it to *live after it is
+ * read).  Either may be NULL.  What the allocator keeps of released blocks for reuse belongs to no context: it is bounded
+ * by CPECAN_ALLOC_CACHE_GB and given back by the trim call below. */
+int cpecan_hip_ctx_memory(cpecan_ctx *ctx, int64_t *live, int64_t *peak, int32_t reset_peak);
+/* A limit on that figure, in bytes; 0 (the default): none.  With a limit, an allocation that would take the context's
+ * live bytes past it is not made and the call fails with CPECAN_ELIMIT -- a model create call, a batch create call, the
+ * growth of an output capacity at run or readback -- and last_error names the bytes asked for and the limit.  A create
+ * call that fails so has released all it took: live is what it was, and the context stays usable.  A limit below what
+ * the context already holds refuses every further allocation until enough is released.  A run or a readback that
+ * fails so leaves the batch as it was before the call, but for buffers it will make again: once there is room (memory
+ * released, the limit raised) the same call may simply be made again (a readback whose growth of the pair buffer was
+ * refused runs the batch once more first, as it would have then). */
+int cpecan_hip_ctx_set_memory_limit(cpecan_ctx *ctx, int64_t bytes);
 
 /* ---- model ---------------------------------------------------------------------------------
  * Replaces the StateMachine3 the reference builds with getStrawManStateMachine3()
@@ -197,6 +213,13 @@ int cpecan_band_construct(const int64_t *anchors, int64_t n_anchors, int64_t lX,
 int64_t cpecan_split_points(const int64_t *anchors, int64_t n_anchors, int64_t lX, int64_t lY,
                             int64_t max_matrix_size, int ragged_left, int ragged_right,
                             int64_t *out, int64_t cap);
+/* What the kernel choice asks about an item's band, without a batch and without a device: *max_width receives the cells
+ * of the widest diagonal of the band that cpecan_band_construct builds from these arguments, *edges_step_by_one 1 if
+ * both edges of that band move by at most one k-mer (and never back) from each diagonal to the next, otherwise 0 --
+ * the two band arguments of the plan calls below, by the rule batch creation itself applies (one piece of code).  Either
+ * may be NULL.  Returns what the band's construction returns. */
+int cpecan_band_extent(const int64_t *anchors, int64_t n_anchors, int64_t lX, int64_t lY, int64_t expansion,
+                       int32_t *max_width, int32_t *edges_step_by_one);
 
 /* ---- batch ---------------------------------------------------------------------------------
  * One work item = one getPosteriorProbsWithBanding() call (impl/pairwiseAligner.c:870): a k-mer
@@ -668,6 +691,9 @@ int cpecan_hip_batch_shader_clock_mhz(cpecan_batch *batch, double *mhz);
 /* Which kernel the batch uses (CPECAN_KERNEL_GENERAL / _SYSTOLIC after AUTO is resolved), how many
  * workgroups it launches and the widest band (cells) among its items. */
 int cpecan_hip_batch_info(cpecan_batch *batch, int32_t *kernel, int32_t *workgroups, int32_t *max_width);
+/* The device memory the batch holds now: the sum of its blocks, each at the size the allocator handed it out.  It grows
+ * where a run or a readback grows an output capacity; it is part of its context's figure (the ctx memory call above). */
+int cpecan_hip_batch_device_bytes(cpecan_batch *batch, int64_t *bytes);
 /* The machines of the create calls above, in the order of: cpecan_hip_batch_create, _dna, _vanilla, _hdp, _sm4, _echelon. */
 #define CPECAN_MACHINE_STRAWMAN 0
 #define CPECAN_MACHINE_DNA5 1
@@ -775,6 +801,10 @@ int cpecan_hip_selftest_division(cpecan_ctx *ctx, int64_t n, uint64_t seed, int6
  * CPECAN_PINNED_CACHE_GB).  This gives all of it back to the runtime: call it between phases when something else in the
  * process, or on the card, needs the memory. */
 int cpecan_hip_trim_cache(void);
+/* How many bytes of released device blocks the library keeps at the most (CPECAN_ALLOC_CACHE_GB, or half of the memory
+ * of the card the context is on).  This bounds the blocks nobody holds; a context's memory limit bounds the ones it
+ * holds: the two are separate. */
+int cpecan_hip_cache_capacity(cpecan_ctx *ctx, int64_t *device_bytes);
 
 /* Stream of the context as an opaque pointer (a hipStream_t) for callers' own work (e.g. an RCCL all-reduce of the
  * expectations): the forward stream of the context's lane set (cpecan_hip_batch_run_after).  A run of a wave batch
