@@ -60,7 +60,7 @@ EXPORTS = [
     "cpecan_hip_batch_create", "cpecan_hip_batch_run", "cpecan_hip_batch_run_after", "cpecan_hip_batch_shader_clock_mhz", "cpecan_hip_batch_sync",
     "cpecan_hip_batch_elapsed_ms", "cpecan_hip_batch_counts", "cpecan_hip_batch_fetch_pairs",
     "cpecan_hip_batch_fetch_totals", "cpecan_hip_batch_expectations_device_ptr",
-    "cpecan_hip_batch_fetch_expectations", "cpecan_hip_batch_debug_cells",
+    "cpecan_hip_batch_fetch_expectations", "cpecan_hip_batch_sum_expectations", "cpecan_hip_batch_debug_cells",
     "cpecan_hip_batch_destroy", "cpecan_hip_ctx_stream", "cpecan_hip_selftest_division", "cpecan_hip_batch_info", "cpecan_hip_plan_dispatch", "cpecan_hip_plan_assembly_sweeps", "cpecan_hip_batch_stage_ms",
     "cpecan_hip_batch_systolic_rows", "cpecan_hip_batch_kernel_family", "cpecan_hip_batch_assembly_sweeps", "cpecan_hip_batch_expectation_pass", "cpecan_hip_plan_expectation_pass", "cpecan_hip_trim_cache", "cpecan_hip_models_set_transitions",
     "cpecan_hip_models5_create", "cpecan_hip_batch_create_dna",
@@ -220,6 +220,7 @@ def lib():
         L.cpecan_hip_batch_expectations_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p),
                                                                C.POINTER(C.c_int64)]
         L.cpecan_hip_batch_fetch_expectations.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.cpecan_hip_batch_sum_expectations.argtypes = [C.c_void_p, C.c_void_p]
         L.cpecan_hip_batch_debug_cells.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
         _LIB = L
     return _LIB
@@ -659,10 +660,19 @@ class Batch:
         _check(lib().cpecan_hip_batch_fetch_totals(self.h, item, _ptr(xay), _ptr(tot), xay.size))
         return xay[:n], tot[:n]
 
+    def expectation_len(self):
+        return (EXPECTATION5_LEN if self.dna else EXPECTATIONV_LEN if self.vanilla
+                else EXPECTATIONH_LEN if self.hdp else EXPECTATION_LEN)
+
     def expectations(self, model_id):
-        out = np.zeros(EXPECTATION5_LEN if self.dna else EXPECTATIONV_LEN if self.vanilla
-                       else EXPECTATIONH_LEN if self.hdp else EXPECTATION_LEN)
+        out = np.zeros(self.expectation_len())
         _check(lib().cpecan_hip_batch_fetch_expectations(self.h, int(model_id), _ptr(out)))
+        return out
+
+    def sum_expectations(self):
+        """the per-model blocks added on the device in ascending model id: one kernel, one copy"""
+        out = np.zeros(self.expectation_len())
+        _check(lib().cpecan_hip_batch_sum_expectations(self.h, _ptr(out)))
         return out
 
     def expectations_device_ptr(self):

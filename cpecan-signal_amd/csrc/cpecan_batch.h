@@ -53,6 +53,7 @@ struct cpecan_batch {
     DevBuf<long long> nPairs, totXay, nTot, nCells;
     DevBuf<double> totVal;
     DevBuf<double> expect;
+    DevBuf<double> expectSum; /* cpecan_hip_batch_sum_expectations: the models' blocks added up, made at its first call */
     DevBuf<int> workCounter;
     DevBuf<char> syStates, syScratch;
     DevBuf<int> bandTab; /* systolic kernels: (first, last) matrix column of every diagonal of every item */

@@ -91,6 +91,29 @@ extern "C" __global__ __launch_bounds__(256) void cpecan_k_pack_base(const DevIt
     }
 }
 
+/* out[i] = the models' blocks of an E-step's sums added at element i, in ascending model id from block 0's value on:
+ * ((e[0][i] + e[1][i]) + e[2][i]) + ..., the sum a host forms that fetches the blocks one by one.  The order is the
+ * call's contract (cpecan_hip_batch_sum_expectations), so the adds stay one chain; what runs ahead of it are the loads,
+ * eight blocks at a time, each of them coalesced across i.  One thread per element. */
+#define CP_SUM_LOADS 8
+extern "C" __global__ __launch_bounds__(256) void cpecan_k_sum_expectations(const double *expect, int nModels, int expectLen,
+                                                                            double *out) {
+    const int i = (int) (blockIdx.x * 256 + threadIdx.x);
+    if (i >= expectLen) return; /* (the last block is partly idle: 4106 elements of the strawMan machine) */
+    const double *e = expect + i;
+    double sum = e[0];
+    int k = 1;
+    for (; k + CP_SUM_LOADS <= nModels; k += CP_SUM_LOADS) {
+        double v[CP_SUM_LOADS];
+#pragma unroll
+        for (int u = 0; u < CP_SUM_LOADS; u++) v[u] = e[(size_t) (k + u) * (size_t) expectLen];
+#pragma unroll
+        for (int u = 0; u < CP_SUM_LOADS; u++) sum += v[u];
+    }
+    for (; k < nModels; k++) sum += e[(size_t) k * (size_t) expectLen];
+    out[i] = sum;
+}
+
 /* The pack step's device buffers: the offsets, the list of close calls and, for at least `need` candidates, the packed
  * records and verdicts (`capacity` of them where those have to be made or grow). */
 static int pack_buffers(cpecan_batch *b, size_t need, size_t capacity) {
@@ -418,6 +441,25 @@ int cpecan_hip_batch_fetch_expectations(cpecan_batch *b, int32_t modelId, double
     if (b->ran) HIP_TRY(hipEventSynchronize(b->ev2));
     HIP_TRY(hipMemcpy(out, b->expect.p + (size_t) modelId * b->expectLen, (size_t) b->expectLen * sizeof(double),
                       hipMemcpyDeviceToHost));
+    return CPECAN_OK;
+}
+
+int cpecan_hip_batch_sum_expectations(cpecan_batch *b, double *out) {
+    if (!b || !out) return fail(CPECAN_EINVAL, "bad argument");
+    if (b->mode != CPECAN_MODE_EXPECTATIONS || b->nModels < 1)
+        return fail(CPECAN_EINVAL, "the batch has no expectations (it was not created for an E-step)");
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    MemScope mem(b->mem);
+    Lap lap("sum_expectations");
+    if (b->expectSum.n < (size_t) b->expectLen) HIP_TRY(b->expectSum.alloc((size_t) b->expectLen));
+    /* behind the run's end event, on the context's prep stream like the other readbacks: one kernel, one copy, one wait */
+    hipStream_t rs = b->ctx->prep;
+    if (b->ran) HIP_TRY(hipStreamWaitEvent(rs, b->ev2, 0));
+    hipLaunchKernelGGL(cpecan_k_sum_expectations, dim3((unsigned) ((b->expectLen + 255) / 256)), dim3(256), 0, rs,
+                       (const double *) b->expect.p, b->nModels, b->expectLen, b->expectSum.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b->expectSum.p, (size_t) b->expectLen * sizeof(double), hipMemcpyDeviceToHost, rs));
+    HIP_TRY(hipStreamSynchronize(rs));
     return CPECAN_OK;
 }
 

@@ -852,36 +852,58 @@ static int32_t vanilla_fused_estep_flags(void) {
     return (fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_VANILLA_FUSED_ESTEP : 0) |
            (fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP : 0);
 }
+/* CPECAN_HDP_FUSED_ESTEP=1: the E-step summed inside the sweep back on the wave kernels at two and three cells per lane
+ * (the flag means nothing to a batch it does not serve); CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP=1: the same on the workgroup
+ * kernels at six and eight waves, for a batch that CPECAN_WIDE_BANDS_HDP_ESTEP=1 puts there (bands of 249..504 k-mers);
+ * CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP=1: on the wave kernels at four cells per lane (bands of 185..248 k-mers) */
+static int32_t hdp_fused_estep_flags(void) {
+    const char *fusedEstep = getenv("CPECAN_HDP_FUSED_ESTEP");
+    const char *fusedWide = getenv("CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP");
+    const char *fusedFour = getenv("CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP");
+    return (fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_HDP_FUSED_ESTEP : 0) |
+           (fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP : 0) |
+           (fusedFour && atoi(fusedFour) == 1 ? CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP : 0);
+}
 /* what every create call takes of the record; y: the events, or the characters of a DNA read */
 #define PACKED(r, y) (r)->items, (r)->nItems, (r)->chars, (r)->nX, (y), (r)->nY, (r)->anchors, (r)->nAnchors
 /* (one batch per call, or a chunk of a stream that is to fit a budget: the smaller footprint) */
 #define SM3_POSTERIOR_FLAGS CPECAN_FLAG_SMALL_FOOTPRINT
+
+/* The kernel argument and the flags of a batch of the machine beyond unbanded_flag and estep_flag: what the create calls
+ * below pass, and what cpecan_hip_plan_dispatch is asked with for a read of the stream -- the one place either comes
+ * from.  An E-step's flags are read from the environment per call (run_reads) or once per stream, when it is opened. */
+void posterior_request(const MachineRow *row, int32_t *kernel, int32_t *flags) {
+    const HostMachine m = (HostMachine) (row - MACHINES);
+    *kernel = m == HM_DNA5 || m == HM_SM4 || m == HM_ECHELON ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
+    *flags = m == HM_STRAWMAN ? SM3_POSTERIOR_FLAGS : 0;
+}
+void expectations_request(const MachineRow *row, int32_t *kernel, int32_t *flags) {
+    const HostMachine m = (HostMachine) (row - MACHINES);
+    posterior_request(row, kernel, flags);
+    *flags |= m == HM_VANILLA ? vanilla_fused_estep_flags() : m == HM_HDP ? hdp_fused_estep_flags() : 0;
+}
+static int32_t request_flags(const Run *r) {
+    int32_t kernel, flags;
+    if (r->mode && r->estepFlags) return *r->estepFlags;
+    if (r->mode) expectations_request(r->row, &kernel, &flags);
+    else posterior_request(r->row, &kernel, &flags);
+    return flags;
+}
+
 static int batch_sm3(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     return cpecan_hip_batch_create(ctx, PACKED(r, r->events), bp, r->mode ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR,
-                                  CPECAN_KERNEL_AUTO, unbanded_flag(r) | SM3_POSTERIOR_FLAGS, batch);
+                                  CPECAN_KERNEL_AUTO, unbanded_flag(r) | request_flags(r), batch);
 }
 static int batch_dna(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
-    return cpecan_hip_batch_create_dna(ctx, PACKED(r, r->ychars), bp, unbanded_flag(r) | estep_flag(r), batch);
+    return cpecan_hip_batch_create_dna(ctx, PACKED(r, r->ychars), bp, unbanded_flag(r) | estep_flag(r) | request_flags(r), batch);
 }
 static int batch_vanilla(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
-    const int32_t fused = r->mode ? vanilla_fused_estep_flags() : 0;
-    return cpecan_hip_batch_create_vanilla(ctx, PACKED(r, r->events), bp, unbanded_flag(r) | estep_flag(r) | fused, batch);
+    return cpecan_hip_batch_create_vanilla(ctx, PACKED(r, r->events), bp, unbanded_flag(r) | estep_flag(r) | request_flags(r), batch);
 }
 static int batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     cpecan_band_params own = *bp;
     if (r->mode) own.threshold = ((HdpHmmExpectations *) r->hmmOut)->threshold; /* the assignment bar */
-    /* CPECAN_HDP_FUSED_ESTEP=1, read per call: the E-step summed inside the sweep back on the wave kernels at two and three
-     * cells per lane (the flag means nothing to a batch it does not serve) */
-    const char *fusedEstep = getenv("CPECAN_HDP_FUSED_ESTEP");
-    /* ... and CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP=1 the same on the workgroup kernels at six and eight waves, for a batch
-     * that CPECAN_WIDE_BANDS_HDP_ESTEP=1 puts there (bands of 249..504 k-mers) */
-    const char *fusedWide = getenv("CPECAN_WIDE_BANDS_HDP_FUSED_ESTEP");
-    /* ... and CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP=1 on the wave kernels at four cells per lane (bands of 185..248 k-mers) */
-    const char *fusedFour = getenv("CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP");
-    const int32_t fused = (r->mode && fusedEstep && atoi(fusedEstep) == 1 ? CPECAN_FLAG_HDP_FUSED_ESTEP : 0) |
-                          (r->mode && fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP : 0) |
-                          (r->mode && fusedFour && atoi(fusedFour) == 1 ? CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP : 0);
-    return cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | fused, batch);
+    return cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | request_flags(r), batch);
 }
 static int batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     return cpecan_hip_batch_create_sm4(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch);
@@ -892,43 +914,63 @@ static int batch_echelon(cpecan_ctx *ctx, const Run *r, const cpecan_band_params
 
 /* ---- expectations: the device's per-model sums added into the caller's struct ---- */
 /* every model's sums: the first nA onto a, the next nB onto b, the one after them onto the likelihood */
+static void add_block(const double *e, double *a, int nA, double *b, int nB, double *likelihood) {
+    for (int q = 0; q < nA; q++) a[q] += e[q];
+    for (int q = 0; q < nB; q++) b[q] += e[nA + q];
+    *likelihood += e[nA + nB];
+}
 static void add_sums(const Run *r, cpecan_batch *batch, double *a, int nA, double *b, int nB, double *likelihood) {
     double *e = malloc(sizeof(double) * (size_t) (nA + nB + 1));
     for (int32_t k = 0; k < r->nModels; k++) {
         CHECK(cpecan_hip_batch_fetch_expectations(batch, r->ids[k], e));
-        for (int q = 0; q < nA; q++) a[q] += e[q];
-        for (int q = 0; q < nB; q++) b[q] += e[nA + q];
-        *likelihood += e[nA + nB];
+        add_block(e, a, nA, b, nB, likelihood);
     }
     free(e);
 }
-static void expect_sm3(const Run *r, cpecan_batch *batch) { /* CPECAN_EXPECTATION_LEN */
+/* one block of a machine's sums (a model's, or a batch's models' added on the device) onto the caller's struct */
+static void block_sm3(void *hmmOut, const double *e) { /* CPECAN_EXPECTATION_LEN */
+    ContinuousPairHmmExpectations *hmm = hmmOut;
+    add_block(e, hmm->transitions, 9, hmm->individualKmerGapProbs, NUM_OF_KMERS, &hmm->likelihood);
+}
+static void block_vanilla(void *hmmOut, const double *e) { /* CPECAN_EXPECTATIONV_LEN */
+    VanillaHmmExpectations *hmm = hmmOut;
+    add_block(e, hmm->kmerSkipBins, 60, NULL, 0, &hmm->likelihood);
+}
+static void block_hdp(void *hmmOut, const double *e) { /* CPECAN_EXPECTATIONH_LEN */
+    HdpHmmExpectations *hmm = hmmOut;
+    add_block(e, hmm->transitions, 9, NULL, 0, &hmm->likelihood);
+}
+/* through the Hmm's own add functions (cell_updateExpectations :407-424 calls them per transition) */
+static void block_dna(void *hmmOut, const double *e) { /* CPECAN_EXPECTATION5_LEN */
+    Hmm *hmm = hmmOut;
+    for (int64_t f = 0; f < 5; f++)
+        for (int64_t t = 0; t < 5; t++)
+            if (e[f * 5 + t] != 0.0) hmm->addToTransitionExpectationFcn(hmm, f, t, e[f * 5 + t]);
+    for (int64_t st = 0; st < 5; st++)
+        for (int64_t x = 0; x < 4; x++)
+            for (int64_t y = 0; y < 4; y++)
+                if (e[25 + st * 16 + x * 4 + y] != 0.0)
+                    hmm->addToEmissionExpectationFcn(hmm, st, x, y, e[25 + st * 16 + x * 4 + y]);
+    hmm->likelihood += e[CPECAN_EXPECTATION5_LEN - 1];
+}
+static void expect_sm3(const Run *r, cpecan_batch *batch) {
     ContinuousPairHmmExpectations *hmm = r->hmmOut;
     add_sums(r, batch, hmm->transitions, 9, hmm->individualKmerGapProbs, NUM_OF_KMERS, &hmm->likelihood);
 }
-static void expect_vanilla(const Run *r, cpecan_batch *batch) { /* CPECAN_EXPECTATIONV_LEN */
+static void expect_vanilla(const Run *r, cpecan_batch *batch) {
     VanillaHmmExpectations *hmm = r->hmmOut;
     add_sums(r, batch, hmm->kmerSkipBins, 60, NULL, 0, &hmm->likelihood);
 }
-/* through the Hmm's own add functions (cell_updateExpectations :407-424 calls them per transition) */
 static void expect_dna(const Run *r, cpecan_batch *batch) {
-    Hmm *hmm = r->hmmOut;
     double e[CPECAN_EXPECTATION5_LEN];
     for (int32_t k = 0; k < r->nModels; k++) {
         CHECK(cpecan_hip_batch_fetch_expectations(batch, r->ids[k], e));
-        for (int64_t f = 0; f < 5; f++)
-            for (int64_t t = 0; t < 5; t++)
-                if (e[f * 5 + t] != 0.0) hmm->addToTransitionExpectationFcn(hmm, f, t, e[f * 5 + t]);
-        for (int64_t st = 0; st < 5; st++)
-            for (int64_t x = 0; x < 4; x++)
-                for (int64_t y = 0; y < 4; y++)
-                    if (e[25 + st * 16 + x * 4 + y] != 0.0)
-                        hmm->addToEmissionExpectationFcn(hmm, st, x, y, e[25 + st * 16 + x * 4 + y]);
-        hmm->likelihood += e[CPECAN_EXPECTATION5_LEN - 1];
+        block_dna(r->hmmOut, e);
     }
 }
-/* one assignment of the HDP E-step: (k-mer, event mean) at (x, y) of read i */
-static void hdp_add_assignment(HdpHmmExpectations *hmm, const Run *r, int64_t i, int64_t x, int64_t y) {
+/* one assignment of the HDP E-step: (k-mer, event mean) at (x, y) of read i, which its third field names as `tag` (the
+ * batch calls: i itself) */
+static void hdp_add_assignment(HdpHmmExpectations *hmm, const Run *r, int64_t i, int64_t x, int64_t y, int64_t tag) {
     if (hmm->numberOfAssignments == hmm->capacity || !hmm->assignmentXY) {
         hmm->capacity = hmm->capacity ? 2 * hmm->capacity : 1024;
         hmm->eventAssignments = realloc(hmm->eventAssignments, sizeof(double) * (size_t) hmm->capacity);
@@ -937,7 +979,7 @@ static void hdp_add_assignment(HdpHmmExpectations *hmm, const Run *r, int64_t i,
     }
     hmm->assignmentXY[3 * hmm->numberOfAssignments] = x >= 0 ? x : 0;
     hmm->assignmentXY[3 * hmm->numberOfAssignments + 1] = y;
-    hmm->assignmentXY[3 * hmm->numberOfAssignments + 2] = i;
+    hmm->assignmentXY[3 * hmm->numberOfAssignments + 2] = tag;
     char *dst = hmm->kmerAssignments + hmm->numberOfAssignments * (KMER_LENGTH + 1);
     memcpy(dst, (const char *) r->sXs[i]->elements + (x >= 0 ? x : 0), KMER_LENGTH);
     dst[KMER_LENGTH] = 0;
@@ -954,10 +996,60 @@ static void expect_hdp(const Run *r, cpecan_batch *batch) {
             int64_t *tri = malloc(sizeof(int64_t) * 3 * (size_t) (np[k] + 1));
             CHECK(cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, np[k] + 1));
             for (int64_t q = 0; q < np[k]; q++)
-                hdp_add_assignment(hmm, r, i, tri[3 * q + 1] + r->origin[k].x1, tri[3 * q + 2] + r->origin[k].y1);
+                hdp_add_assignment(hmm, r, i, tri[3 * q + 1] + r->origin[k].x1, tri[3 * q + 2] + r->origin[k].y1, i);
             free(tri);
         }
     free(np);
+}
+
+/* ---- the stream's E-step readback, in two steps: a chunk's sums and assignments into temporaries, which may fail with
+ * the C-ABI's code (a context with a memory limit: the result buffer, the pair buffer's growth) and then leaves
+ * nothing behind; and the temporaries onto the caller's struct, which cannot fail ---- */
+void chunk_expectations_release(ChunkExpectations *t) {
+    free(t->sums);
+    free(t->assignments);
+    memset(t, 0, sizeof *t);
+}
+/* the batch's blocks summed on the device (cpecan_hip_batch_sum_expectations); for the HDP machine also the assignments
+ * as expect_hdp walks them: read after read, sub-alignment after sub-alignment (batch NULL: there was nothing to run) */
+int collect_expectations(const Run *r, cpecan_batch *batch, ChunkExpectations *t) {
+    memset(t, 0, sizeof *t);
+    if (!batch) return CPECAN_OK;
+    t->sums = malloc(sizeof(double) * (size_t) r->row->expectLen);
+    int rc = cpecan_hip_batch_sum_expectations(batch, t->sums);
+    if (rc == CPECAN_OK && r->row == &MACHINES[HM_HDP]) {
+        int64_t *np = malloc(sizeof(int64_t) * (size_t) (r->nItems + 1)), all = 0, most = 0;
+        rc = cpecan_hip_batch_counts(batch, np, NULL, NULL);
+        for (int64_t k = 0; rc == CPECAN_OK && k < r->nItems; k++) {
+            all += np[k];
+            if (np[k] > most) most = np[k];
+        }
+        int64_t *tri = malloc(sizeof(int64_t) * 3 * (size_t) (most + 1));
+        t->assignments = malloc(sizeof(int64_t) * 3 * (size_t) (all + 1));
+        for (int64_t i = 0; rc == CPECAN_OK && i < r->n; i++)
+            for (int64_t k = r->firstItem[i]; rc == CPECAN_OK && k < r->firstItem[i + 1]; k++) {
+                rc = cpecan_hip_batch_fetch_pairs(batch, k, tri, NULL, most + 1);
+                for (int64_t q = 0; rc == CPECAN_OK && q < np[k]; q++) {
+                    int64_t *a = t->assignments + 3 * t->nAssignments++;
+                    a[0] = tri[3 * q + 1] + r->origin[k].x1;
+                    a[1] = tri[3 * q + 2] + r->origin[k].y1;
+                    a[2] = i;
+                }
+            }
+        free(tri);
+        free(np);
+    }
+    if (rc != CPECAN_OK) chunk_expectations_release(t);
+    return rc;
+}
+/* tags[i]: what an assignment of the chunk's read i carries in its third field */
+void apply_expectations(const Run *r, const ChunkExpectations *t, const int64_t *tags) {
+    if (!t->sums) return;
+    r->row->add_block(r->hmmOut, t->sums);
+    for (int64_t q = 0; q < t->nAssignments; q++) {
+        const int64_t *a = t->assignments + 3 * q;
+        hdp_add_assignment(r->hmmOut, r, a[2], a[0], a[1], tags[a[2]]);
+    }
 }
 
 #define ECHELON_REFUSAL                                                                                              \
@@ -967,28 +1059,30 @@ const MachineRow MACHINES[HM_COUNT] = {
     [HM_STRAWMAN] = { threeState, threeState, 3, sequence_getKmer, sequence_getEvent,
                       "cpecan: the GPU path needs sequence_getKmer / sequence_getEvent element getters",
                       KMER_LENGTH - 1, false, NULL, false, false,
-                      sizeof(cpecan_sm3_model), fill_sm3, same_sm3, models_sm3, batch_sm3, expect_sm3 },
+                      sizeof(cpecan_sm3_model), fill_sm3, same_sm3, models_sm3, batch_sm3, expect_sm3, CPECAN_EXPECTATION_LEN, block_sm3 },
     [HM_DNA5] = { fiveState, fiveStateAsymmetric, 5, sequence_getBase, sequence_getBase,
                   "cpecan: the 5-state machine needs sequence_getBase element getters on both sequences",
                   0, true, NULL, false, false,
-                  sizeof(cpecan_sm5_model), fill_sm5, NULL, models_sm5, batch_dna, expect_dna },
+                  sizeof(cpecan_sm5_model), fill_sm5, NULL, models_sm5, batch_dna, expect_dna, CPECAN_EXPECTATION5_LEN, block_dna },
     [HM_VANILLA] = { vanilla, vanilla, 3, sequence_getKmer2, sequence_getEvent,
                      "cpecan: the vanilla machine needs sequence_getKmer2 / sequence_getEvent element getters",
                      KMER_LENGTH - 1, false, NULL, false, false,
-                     sizeof(cpecan_vanilla_model), fill_vanilla, NULL, models_vanilla, batch_vanilla, expect_vanilla },
+                     sizeof(cpecan_vanilla_model), fill_vanilla, NULL, models_vanilla, batch_vanilla, expect_vanilla,
+                     CPECAN_EXPECTATIONV_LEN, block_vanilla },
     [HM_HDP] = { threeStateHdp, threeStateHdp, 3, sequence_getKmer3, sequence_getEvent,
                  "cpecan: the HDP machine needs sequence_getKmer3 / sequence_getEvent element getters",
                  KMER_LENGTH - 1, false, NULL, false, false,
-                 sizeof(cpecan_hdp_model), cpecan_hdp_machine_as_model, NULL, models_hdp, batch_hdp, expect_hdp },
+                 sizeof(cpecan_hdp_model), cpecan_hdp_machine_as_model, NULL, models_hdp, batch_hdp, expect_hdp,
+                 CPECAN_EXPECTATIONH_LEN, block_hdp },
     [HM_SM4] = { fourState, fourState, 4, sequence_getKmer, sequence_getEvent,
                  "cpecan: the 4-state machine needs sequence_getKmer / sequence_getEvent element getters",
                  KMER_LENGTH - 1, false,
                  "cpecan: the 4-state machine has no expectations (the reference has no Hmm for it)", false, false,
-                 sizeof(cpecan_sm4_model), fill_sm4, NULL, models_sm4, batch_sm4, NULL },
+                 sizeof(cpecan_sm4_model), fill_sm4, NULL, models_sm4, batch_sm4, NULL, 0, NULL },
     [HM_ECHELON] = { echelon, echelon, 7, sequence_getKmer2, sequence_getEvent,
                      "cpecan: the echelon machine needs sequence_getKmer2 / sequence_getEvent element getters",
                      KMER_LENGTH - 1, false, ECHELON_REFUSAL, true, true,
-                     sizeof(cpecan_echelon_model), fill_echelon, NULL, models_echelon, batch_echelon, NULL },
+                     sizeof(cpecan_echelon_model), fill_echelon, NULL, models_echelon, batch_echelon, NULL, 0, NULL },
 };
 
 /* the machine of a read, or no return: anything but the six combinations of the table is not on the GPU path */
@@ -1118,14 +1212,6 @@ void pack_reads(Run *r) {
         yo += lY;
     }
     r->firstItem[r->n] = r->nItems;
-}
-
-/* the kernel argument and the flags of a posterior batch of the machine, as its create call above passes them: what
- * cpecan_hip_plan_dispatch is asked with for a read of the stream */
-void posterior_request(const MachineRow *row, int32_t *kernel, int32_t *flags) {
-    const HostMachine m = (HostMachine) (row - MACHINES);
-    *kernel = m == HM_DNA5 || m == HM_SM4 || m == HM_ECHELON ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
-    *flags = m == HM_STRAWMAN ? SM3_POSTERIOR_FLAGS : 0;
 }
 
 int create_batch(Run *r, cpecan_ctx *ctx, cpecan_batch **batch) {

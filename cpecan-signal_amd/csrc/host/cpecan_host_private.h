@@ -48,6 +48,7 @@ typedef struct {
     bool raggedL, raggedR;
     int mode, unbanded;
     void *hmmOut;
+    const int32_t *estepFlags; /* the stream: an E-step's flags as expectations_request gave them at open (NULL: ask now) */
     const void *records; /* the stream: n model records of row->modelSize bytes, filled at submission (NULL: fill now) */
     /* dedupe_models: nModels structs of row->modelSize bytes, the state machine each was filled from */
     void *models;
@@ -82,6 +83,9 @@ typedef struct MachineRow {
     int (*models_create)(cpecan_ctx *ctx, const void *models, int32_t nModels, int32_t *ids);
     int (*batch_create)(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch);
     void (*add_expectations)(const Run *r, cpecan_batch *batch);
+    /* the E-step's sums: doubles per model, and one such block added onto the struct Run.hmmOut points to */
+    int32_t expectLen;
+    void (*add_block)(void *hmmOut, const double *block);
 } MachineRow;
 
 extern const MachineRow MACHINES[HM_COUNT];
@@ -95,8 +99,20 @@ void pack_reads(Run *r);
 int create_batch(Run *r, cpecan_ctx *ctx, cpecan_batch **batch);
 int collect_pairs(const Run *r, cpecan_batch *batch, stList **lists);
 void run_release(Run *r);
-/* kernel argument and flags of a posterior batch of the machine, as its create call passes them */
+/* kernel argument and flags of a posterior batch of the machine and of an E-step batch (the environment's switches for
+ * the fused E-steps among them), as its create call passes them: the create calls take them from these two */
 void posterior_request(const MachineRow *row, int32_t *kernel, int32_t *flags);
+void expectations_request(const MachineRow *row, int32_t *kernel, int32_t *flags);
+/* the E-step readback of a chunk of the stream: into temporaries (returns the C-ABI's code and then leaves none), and
+ * from them onto r->hmmOut; an HDP assignment of read i carries tags[i] */
+typedef struct {
+    double *sums;          /* row->expectLen: the batch's models' blocks added on the device (NULL: nothing ran) */
+    int64_t *assignments;  /* HDP: nAssignments x (x, y, read of the chunk), in the order expect_hdp walks them */
+    int64_t nAssignments;
+} ChunkExpectations;
+int collect_expectations(const Run *r, cpecan_batch *batch, ChunkExpectations *t);
+void apply_expectations(const Run *r, const ChunkExpectations *t, const int64_t *tags);
+void chunk_expectations_release(ChunkExpectations *t);
 
 /* ---- the chunking rule of the stream (cpecan_stream_plan.c, which states it) ---- */
 typedef struct {

@@ -9,7 +9,9 @@
  *                               slot and turn are taken together, so whoever holds a turn can prepare
  *   prepared  (a producer)      size_inputs, dedupe_models, pack_reads, create_batch on the slot's context
  *   queued    (that producer)   when its turn has come: cpecan_hip_batch_run_after behind the run queued before it
- *   finished  (the consumer)    sync, collect_pairs, onResult per read, batch destroyed, slot freed
+ *   finished  (the consumer)    sync, collect_pairs, onResult per read, batch destroyed, slot freed -- a stream opened
+ *                               for expectations: sync, collect_expectations into temporaries, batch destroyed, the
+ *                               temporaries added to the caller's struct, onDone per read
  * CPECAN_ELIMIT from any of these calls cuts the chunk in half; the first half goes on in the chunk's place (a producer
  * keeps slot and turn), the second goes to the head of `pending`.
  */
@@ -77,8 +79,13 @@ struct cpecan_stream {
     bool raggedL, raggedR;
     cpecan_stream_options o;
     cpecan_stream_result_fn onResult;
+    cpecan_stream_done_fn onDone; /* (expectations) */
     cpecan_stream_chunk_fn onChunk;
     void *arg;
+    int mode;                     /* 0: posterior decode, lists to onResult; 1: the E-step, sums into `expectations` */
+    void *expectations;           /* what Run.hmmOut is for the machine of the first read */
+    int32_t reqKernel[HM_COUNT], reqFlags[HM_COUNT]; /* what a batch of each machine is asked for, taken at open
+                                                        (posterior_request / expectations_request) */
     const MachineRow *row; /* the machine of the first read */
     StreamPlanner planner; /* (the submitting thread's) */
     int64_t perSlot;       /* deviceBytes / slots */
@@ -144,10 +151,9 @@ static void classify(cpecan_stream *s, SRead *rd) {
         rd->cls = general;
         return;
     }
-    int32_t kernel, flags;
-    posterior_request(s->row, &kernel, &flags);
-    CHECK(cpecan_hip_plan_dispatch(machine, CPECAN_MODE_POSTERIOR, kernel, flags, widest, stepByOne, &rd->cls.kernel,
-                                   &rd->cls.wave, &rd->cls.rows, NULL));
+    CHECK(cpecan_hip_plan_dispatch(machine, s->mode ? CPECAN_MODE_EXPECTATIONS : CPECAN_MODE_POSTERIOR, s->reqKernel[machine],
+                                   s->reqFlags[machine], widest, stepByOne, &rd->cls.kernel, &rd->cls.wave, &rd->cls.rows,
+                                   NULL));
 }
 
 /* ---- chunks ---- */
@@ -211,7 +217,8 @@ static int chunk_prepare(cpecan_stream *s, Chunk *c) {
         memcpy((char *) c->records + size * i, rd->record, size);
     }
     const Run r = { .n = c->n, .sMs = c->sMs, .sXs = c->sXs, .sYs = c->sYs, .anchorLists = c->anchorLists, .p = &s->p,
-                    .raggedL = s->raggedL, .raggedR = s->raggedR, .records = c->records };
+                    .raggedL = s->raggedL, .raggedR = s->raggedR, .records = c->records, .mode = s->mode,
+                    .hmmOut = s->expectations, .estepFlags = s->mode ? &s->reqFlags[s->row - MACHINES] : NULL };
     c->run = r;
     const double t0 = now_ms();
     size_inputs(&c->run);
@@ -354,9 +361,10 @@ static void *producer_main(void *arg) {
     }
 }
 
-static void deliver(cpecan_stream *s, int64_t tag, stList *list) {
+static void deliver(cpecan_stream *s, int64_t tag, stList *list, bool refused) {
     pthread_mutex_lock(&s->callMu);
-    s->onResult(s->arg, tag, list);
+    if (!s->mode) s->onResult(s->arg, tag, list);
+    else if (s->onDone) s->onDone(s->arg, tag, refused);
     pthread_mutex_unlock(&s->callMu);
 }
 
@@ -376,13 +384,14 @@ static void *consumer_main(void *arg) {
         pthread_mutex_unlock(&s->mu);
 
         stList **lists = calloc((size_t) c->n, sizeof(stList *));
+        ChunkExpectations sums = { NULL, NULL, 0 };
         int rc = CPECAN_OK;
         const double t0 = now_ms();
         double t1 = t0;
         if (!c->refused) {
             if (c->batch) rc = cpecan_hip_batch_sync(c->batch);
             t1 = now_ms();
-            if (rc == CPECAN_OK) rc = collect_pairs(&c->run, c->batch, lists);
+            if (rc == CPECAN_OK) rc = s->mode ? collect_expectations(&c->run, c->batch, &sums) : collect_pairs(&c->run, c->batch, lists);
             if (rc != CPECAN_OK && rc != CPECAN_ELIMIT)
                 die("cpecan: reading a chunk of the stream back failed (%d): %s", rc, cpecan_hip_last_error());
         }
@@ -396,12 +405,23 @@ static void *consumer_main(void *arg) {
             halves[0] = chunk_new(c->reads, c->n, c->halvings);
             c->reads = NULL;
             c->n = 0;
-        } else
-            for (int64_t i = 0; i < c->n; i++) deliver(s, c->reads[i]->tag, c->refused || rc != CPECAN_OK ? NULL : lists[i]);
+        } else {
+            /* the whole readback of the chunk has succeeded: only now does the caller's struct change, chunk after chunk
+             * in turn order (a chunk that was halved above has added nothing) */
+            const bool refused = c->refused || rc != CPECAN_OK;
+            if (s->mode && !refused) {
+                int64_t *tags = malloc(sizeof(int64_t) * (size_t) c->n);
+                for (int64_t i = 0; i < c->n; i++) tags[i] = c->reads[i]->tag;
+                apply_expectations(&c->run, &sums, tags);
+                free(tags);
+            }
+            for (int64_t i = 0; i < c->n; i++) deliver(s, c->reads[i]->tag, refused ? NULL : lists[i], refused);
+        }
+        chunk_expectations_release(&sums);
         free(lists);
         if (s->timing)
-            fprintf(stderr, "[cpecan timing] stream chunk %lld: sync %.1f ms, pairs %.1f ms, batch destroyed in %.1f ms, results delivered in %.1f ms, at %.1f\n",
-                    (long long) c->turn, t1 - t0, t2 - t1, t3 - t2, now_ms() - t3, now_ms());
+            fprintf(stderr, "[cpecan timing] stream chunk %lld: sync %.1f ms, %s %.1f ms, batch destroyed in %.1f ms, results delivered in %.1f ms, at %.1f\n",
+                    (long long) c->turn, t1 - t0, s->mode ? "expectations" : "pairs", t2 - t1, t3 - t2, now_ms() - t3, now_ms());
         pthread_mutex_lock(&s->mu);
         if (c->n > 0 && (c->refused || rc != CPECAN_OK)) s->nRefused += c->n;
         if (halves[0]) {
@@ -432,9 +452,10 @@ static void enqueue(cpecan_stream *s, StreamGroup *g) {
     pthread_mutex_unlock(&s->mu);
 }
 
-cpecan_stream *cpecan_stream_open(PairwiseAlignmentParameters *p, bool raggedL, bool raggedR, const cpecan_stream_options *o,
-                                  cpecan_stream_result_fn onResult, cpecan_stream_chunk_fn onChunk, void *arg) {
-    if (!p || !onResult) die("cpecan_stream_open: parameters and a result callback are needed");
+/* mode 0: onResult; mode 1: expectations, onDone (which may be NULL) */
+static cpecan_stream *stream_open(PairwiseAlignmentParameters *p, bool raggedL, bool raggedR, const cpecan_stream_options *o,
+                                  int mode, cpecan_stream_result_fn onResult, void *expectations, cpecan_stream_done_fn onDone,
+                                  cpecan_stream_chunk_fn onChunk, void *arg) {
     cpecan_stream *s = calloc(1, sizeof *s);
     const double t0 = now_ms();
     s->timing = getenv("CPECAN_TIMING") != NULL;
@@ -448,8 +469,15 @@ cpecan_stream *cpecan_stream_open(PairwiseAlignmentParameters *p, bool raggedL, 
     if (s->o.slots < 2 || s->o.producerThreads < 1 || s->o.maxReadsPerChunk < 1 || s->o.deviceBytes < 0)
         die("cpecan_stream_open: at least 2 slots, 1 producer thread and 1 read per chunk, and no negative budget");
     s->onResult = onResult;
+    s->onDone = onDone;
     s->onChunk = onChunk;
     s->arg = arg;
+    s->mode = mode;
+    s->expectations = expectations;
+    for (int m = 0; m < HM_COUNT; m++) { /* (an E-step's: with the environment's switches as they stand now) */
+        if (mode) expectations_request(&MACHINES[m], &s->reqKernel[m], &s->reqFlags[m]);
+        else posterior_request(&MACHINES[m], &s->reqKernel[m], &s->reqFlags[m]);
+    }
     planner_init(&s->planner, s->o.maxReadsPerChunk);
     pthread_mutex_init(&s->mu, NULL);
     pthread_mutex_init(&s->runMu, NULL);
@@ -471,6 +499,28 @@ cpecan_stream *cpecan_stream_open(PairwiseAlignmentParameters *p, bool raggedL, 
     return s;
 }
 
+cpecan_stream *cpecan_stream_open(PairwiseAlignmentParameters *p, bool raggedL, bool raggedR, const cpecan_stream_options *o,
+                                  cpecan_stream_result_fn onResult, cpecan_stream_chunk_fn onChunk, void *arg) {
+    if (!p || !onResult) die("cpecan_stream_open: parameters and a result callback are needed");
+    return stream_open(p, raggedL, raggedR, o, 0, onResult, NULL, NULL, onChunk, arg);
+}
+
+cpecan_stream *cpecan_stream_open_expectations(PairwiseAlignmentParameters *p, bool raggedL, bool raggedR,
+                                               const cpecan_stream_options *o, void *expectations,
+                                               cpecan_stream_done_fn onDone, cpecan_stream_chunk_fn onChunk, void *arg) {
+    if (!p || !expectations) die("cpecan_stream_open_expectations: parameters and the struct the expectations go to are needed");
+    return stream_open(p, raggedL, raggedR, o, 1, NULL, expectations, onDone, onChunk, arg);
+}
+
+/* Test hook: the class of an E-step read of the machine whose widest band is maxWidth, as classify takes it */
+int32_t cpecan_stream_expectations_class(int32_t machine, int32_t maxWidth, int32_t edgesStepByOne, int32_t *kernel,
+                                         int32_t *wave, int32_t *rows) {
+    if (machine < 0 || machine >= HM_COUNT) return CPECAN_EINVAL;
+    int32_t k, f;
+    expectations_request(&MACHINES[machine], &k, &f);
+    return cpecan_hip_plan_dispatch(machine, CPECAN_MODE_EXPECTATIONS, k, f, maxWidth, edgesStepByOne, kernel, wave, rows, NULL);
+}
+
 void cpecan_stream_submit(cpecan_stream *s, int64_t tag, StateMachine *sM, Sequence *sX, Sequence *sY, stList *anchors) {
     const double t0 = now_ms();
     const HostMachine kind = check_known_combination(sM, sX, sY);
@@ -489,7 +539,8 @@ void cpecan_stream_submit(cpecan_stream *s, int64_t tag, StateMachine *sM, Seque
     /* the read packed alone, by the steps that pack a chunk: its sub-alignments with their anchors, which its class is
      * taken from, and the copy of its characters and events (no device model yet: id 0 stands in) */
     const Run one = { .n = 1, .sMs = &rd->sM, .sXs = &sX, .sYs = &sY, .anchorLists = &rd->anchors, .p = &s->p,
-                      .raggedL = s->raggedL, .raggedR = s->raggedR };
+                      .raggedL = s->raggedL, .raggedR = s->raggedR, .mode = s->mode /* (size_inputs refuses an E-step of a
+                                                                                         machine that has none) */ };
     rd->one = one;
     size_inputs(&rd->one);
     rd->one.modelOf = calloc(1, sizeof(int32_t));

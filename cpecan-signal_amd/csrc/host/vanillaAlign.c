@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include "cpecan_api.h"
+#include "cpecan_hip.h" /* (the device cache's capacity, shared out between the two E-step streams) */
 
 static void die(const char *fmt, ...) __attribute__((noreturn, format(printf, 1, 2)));
 static void die(const char *fmt, ...) {
@@ -545,6 +546,142 @@ static int align_directory_stream(const char *dir, const char *outDir, const cha
     return nRefused == 0 ? 0 : 1;
 }
 
+/* ---- the E-step over the directory (--stream with --templateExpectations / --complementExpectations): what
+ * scripts/trainModels.py gets from one vanillaAlign process per read and a sum over their files, from two expectation
+ * streams here, one per strand, each with half the budget and an accumulator of its own.  Reads are loaded, submitted and
+ * let go one at a time; the targets carry the substitution, as the single-read E-step's do.  Of a read only its two state
+ * machines stay, until its expectations are in. ---------------------------------------------------------------------- */
+#define ESTEP_PSEUDOCOUNT 0.0001 /* the single-read driver's, per strand submitted: what the sum over per-read files holds */
+typedef struct {
+    const char *strand;
+    char **names;
+    StateMachine **sMs; /* per read */
+    bool keepFirst;     /* the vanilla file carries the match tables of the first read in name order */
+    int64_t nRefused;
+} EstepStrands;
+
+/* (a stream never runs two of these at once, and each stream has its own EstepStrands) */
+static void estep_done(void *arg, int64_t tag, bool refused) {
+    EstepStrands *es = arg;
+    if (refused) {
+        fprintf(stderr, "vanillaAlign - ERROR: the %s strand of %s does not fit the device-memory budget, left out of the expectations\n",
+                es->strand, es->names[tag]);
+        es->nRefused++;
+    }
+    if (tag == 0 && es->keepFirst) return;
+    stateMachine_destruct(es->sMs[tag]);
+    es->sMs[tag] = NULL;
+}
+
+static void *empty_expectations(StateMachineType type, double pseudocount, double threshold) {
+    if (type == threeStateHdp) return cpecan_hdpExpectations_construct(pseudocount, threshold);
+    if (type == vanilla) {
+        VanillaHmmExpectations *e = calloc(1, sizeof *e);
+        for (int i = 0; i < 60; i++) e->kmerSkipBins[i] = pseudocount;
+        return e;
+    }
+    ContinuousPairHmmExpectations *e = calloc(1, sizeof *e);
+    for (int i = 0; i < 9; i++) e->transitions[i] = pseudocount;
+    for (int i = 0; i < NUM_OF_KMERS; i++) e->individualKmerGapProbs[i] = pseudocount;
+    return e;
+}
+
+static void write_expectations(const char *path, StateMachineType type, void *e, StateMachine *first) {
+    fprintf(stderr, "vanillaAlign - writing expectations to file: %s\n", path);
+    FILE *fh = fopen(path, "w");
+    if (!fh) die("vanillaAlign - ERROR: cannot write %s", path);
+    if (type == threeStateHdp) {
+        fprintf(stderr, "vanillaAlign - got %lld HDP assignments\n", (long long) ((HdpHmmExpectations *) e)->numberOfAssignments);
+        cpecan_hdpExpectations_write(e, fh);
+    } else if (type == vanilla) cpecan_vanillaExpectations_write(e, first, fh);
+    else cpecan_pairHmmExpectations_write(e, fh);
+    fclose(fh);
+}
+
+static int expectations_directory_stream(const char *dir, const char *referenceSequence, StateMachineType sMtype,
+                                         const char *modelFiles[2], const char *hmmFiles[2], NanoporeHDP *nHdps[2],
+                                         PairwiseAlignmentParameters *p, const cpecan_stream_options *options,
+                                         const char *substitute, const char *expectationsFiles[2]) {
+    int64_t n;
+    char **names = read_names(dir, &n);
+    cpecan_stream_options half = *options;
+    if (half.deviceBytes == 0) { /* (the stream's own default, asked for here so that it can be shared out) */
+        cpecan_ctx *ctx = NULL;
+        const char *dev = getenv("CPECAN_DEVICE");
+        if (cpecan_hip_ctx_create(dev ? atoi(dev) : 0, &ctx) != CPECAN_OK || cpecan_hip_cache_capacity(ctx, &half.deviceBytes) != CPECAN_OK)
+            die("vanillaAlign - ERROR: %s", cpecan_hip_last_error());
+        cpecan_hip_ctx_destroy(ctx);
+    }
+    half.deviceBytes /= 2;
+    EstepStrands es[2];
+    void *sums[2];
+    cpecan_stream *streams[2];
+    for (int st = 0; st < 2; st++) {
+        const EstepStrands empty = { st == 0 ? "template" : "complement", names, calloc((size_t) n, sizeof(StateMachine *)),
+                                     sMtype == vanilla, 0 };
+        es[st] = empty;
+        sums[st] = empty_expectations(sMtype, ESTEP_PSEUDOCOUNT * (double) n, p->threshold);
+        streams[st] = cpecan_stream_open_expectations(p, 1, 1, &half, sums[st], estep_done, NULL, &es[st]);
+    }
+    for (int64_t i = 0; i < n; i++) {
+        BatchRead r;
+        memset(&r, 0, sizeof r);
+        load_batch_read(&r, dir, names[i], referenceSequence, sMtype, p);
+        for (int st = 0; st < 2; st++) {
+            const NanoporeReadAdjustmentParameters npp = st == 0 ? r.npRead->templateParams : r.npRead->complementParams;
+            StateMachine *sM = build_state_machine(modelFiles[st], npp, sMtype, st == 0 ? template : complement, nHdps[st]);
+            if (hmmFiles[st]) hmmContinuous_loadSignalHmm(hmmFiles[st], sM, sM->type);
+            char *seq = st == 0 ? r.trimmedRefSeq : r.rcTrimmedRefSeq;
+            char *target = substitute ? replace_char(seq, 'C', substitute) : seq;
+            Sequence *sX = sequence_construct2(sequence_correctSeqLength((int64_t) strlen(target), event), target,
+                                               target_getter(sMtype), sequence_sliceNucleotideSequence2);
+            stList *anchors = remapped_anchor_pairs(r.anchorPairs, st == 0 ? r.npRead->templateEventMap : r.npRead->complementEventMap,
+                                                    r.pA->start2);
+            es[st].sMs[i] = sM;
+            cpecan_stream_submit(streams[st], i, sM, sX, r.events[st], anchors); /* (copies what it needs of the three) */
+            stList_destruct(anchors);
+            sequence_sequenceDestroy(sX);
+            if (substitute) free(target);
+        }
+        r.name = NULL; /* (names[i] stays for the messages) */
+        free_batch_read(&r);
+    }
+    int64_t nRefused = 0;
+    for (int st = 0; st < 2; st++) {
+        int64_t nChunks = 0, refused = 0, peak = 0;
+        cpecan_stream_close(streams[st], &nChunks, &refused, &peak);
+        fprintf(stderr, "vanillaAlign - %s stream: %lld chunks, at most %lld device bytes, %lld strands refused\n", es[st].strand,
+                (long long) nChunks, (long long) peak, (long long) refused);
+        nRefused += refused;
+        write_expectations(expectationsFiles[st], sMtype, sums[st], es[st].sMs[0]);
+        if (es[st].sMs[0]) stateMachine_destruct(es[st].sMs[0]);
+        free(es[st].sMs);
+        if (sMtype == threeStateHdp) cpecan_hdpExpectations_destruct(sums[st]);
+        else free(sums[st]);
+    }
+    for (int64_t i = 0; i < n; i++) free(names[i]);
+    free(names);
+    if (nRefused == 0) fprintf(stderr, "vanillaAlign - SUCCESS: collected the expectations of %lld reads, exiting\n", (long long) n);
+    return nRefused == 0 ? 0 : 1;
+}
+
+static void usage(void) {
+    fprintf(stderr,
+            "vanillaAlign binary, meant to be used through the signalAlign program.\n"
+            "  one read:     --npRead FILE --reference FILE [--posteriors TSV | --templateExpectations T --complementExpectations C]\n"
+            "                (the guide alignment, an exonerate cigar line, on stdin)\n"
+            "  a directory:  --npReadDir DIR --reference FILE --outDir DIR [--stream [--streamReads N] [--streamGB X]]\n"
+            "                every NAME.npRead with its NAME.cigar aligned, posteriors to outDir/NAME.tsv; --stream: in chained\n"
+            "                chunks of at most N reads within X GB of device memory\n"
+            "  its E-step:   --npReadDir DIR --reference FILE --stream --templateExpectations T --complementExpectations C\n"
+            "                [--streamReads N] [--streamGB X] [--substitute c]\n"
+            "                the expectations of all reads summed, one stream and one file per strand (half of X each); the\n"
+            "                files start from the single-read pseudocount (0.0001) times the number of reads, which is what the\n"
+            "                sum of the per-read files holds.  A vanilla file carries the match tables of the first read in\n"
+            "                name order.\n"
+            "  machines:     --strawMan, --sm3Hdp (with --templateHdp, --complementHdp), --fourState, --echelon; default vanilla\n");
+}
+
 int main(int argc, char *argv[]) {
     StateMachineType sMtype = vanilla;
     const char *npReadDir = NULL, *outDir = NULL;
@@ -603,7 +740,7 @@ int main(int argc, char *argv[]) {
         case 'R': streamOptions.maxReadsPerChunk = atoll(optarg); break;
         case 'G': streamOptions.deviceBytes = (int64_t) (atof(optarg) * (double) (1ll << 30)); break;
         default:
-            fprintf(stderr, "vanillaAlign binary, meant to be used through the signalAlign program.\n");
+            usage();
             return 1;
         }
     }
@@ -612,10 +749,16 @@ int main(int argc, char *argv[]) {
     if (sMtype == echelon && (templateHmmFile || complementHmmFile))
         die("vanillaAlign - LoadSignalHmm : unupported stateMachineType (no HMM files for the echelon machine)");
     if (stream && !npReadDir) die("vanillaAlign - ERROR: --stream goes with --npReadDir and --outDir");
-    if (npReadDir) { /* additive: a directory of reads as one GPU batch */
-        if (!targetFile || !outDir) die("vanillaAlign - ERROR: --npReadDir needs --reference and --outDir");
-        if (templateExpectationsFile || complementExpectationsFile)
-            die("vanillaAlign - ERROR: --npReadDir aligns; expectations are collected read by read (or by cpecan_trainModels)");
+    if (npReadDir) { /* additive: a directory of reads as one GPU batch, or through the stream */
+        const bool expectations = templateExpectationsFile || complementExpectationsFile;
+        if (expectations && !stream)
+            die("vanillaAlign - ERROR: --npReadDir without --stream aligns; the expectations of a directory are collected with "
+                "--stream (or read by read, or by cpecan_trainModels)");
+        if (expectations && !(templateExpectationsFile && complementExpectationsFile))
+            die("vanillaAlign - ERROR: --templateExpectations and --complementExpectations go together");
+        if (expectations && sMtype == fourState)
+            die("vanillaAlign - the fourState machine has no expectations (the reference has no Hmm container for it)");
+        if (!targetFile || (!outDir && !expectations)) die("vanillaAlign - ERROR: --npReadDir needs --reference and --outDir");
         if ((templateHdp != NULL) != (complementHdp != NULL)) die("Need to have template and complement HDPs");
         const char *modelFiles[2] = { templateModelFile, complementModelFile }, *hmmFiles[2] = { templateHmmFile, complementHmmFile };
         NanoporeHDP *nHdps[2] = { templateHdp ? deserialize_nhdp(templateHdp) : NULL, complementHdp ? deserialize_nhdp(complementHdp) : NULL };
@@ -624,9 +767,12 @@ int main(int argc, char *argv[]) {
         bp->constraintDiagonalTrim = constraintTrim;
         bp->diagonalExpansion = diagExpansion;
         char *reference = first_line(targetFile);
-        const int rc = stream ? align_directory_stream(npReadDir, outDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp,
-                                                       &streamOptions)
-                              : align_directory(npReadDir, outDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp, substitute);
+        const char *expectationsFiles[2] = { templateExpectationsFile, complementExpectationsFile };
+        const int rc = expectations ? expectations_directory_stream(npReadDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp,
+                                                                    &streamOptions, substitute, expectationsFiles)
+                       : stream     ? align_directory_stream(npReadDir, outDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp,
+                                                             &streamOptions)
+                                    : align_directory(npReadDir, outDir, reference, sMtype, modelFiles, hmmFiles, nHdps, bp, substitute);
         free(reference);
         pairwiseAlignmentBandingParameters_destruct(bp);
         if (nHdps[0]) destroy_nanopore_hdp(nHdps[0]);

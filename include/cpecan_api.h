@@ -609,6 +609,39 @@ void cpecan_stream_flush(cpecan_stream *s);   /* closes every open group, return
 /* flushes, ends the threads and frees the stream.  *nChunks: chunks that ran; *nRefused: reads refused;
  * *peakDeviceBytes: the sum of the slots' own high-water marks, an upper bound of what was held at once.  Any may be NULL. */
 void cpecan_stream_close(cpecan_stream *s, int64_t *nChunks, int64_t *nRefused, int64_t *peakDeviceBytes);
+
+/* ---- the stream in expectation mode: the Baum-Welch E-step of any number of reads, summed into one struct -----------
+ * submit, flush, close, the options and the chunk report are the stream's above; so are grouping, chunks, budget,
+ * halving and refusal, with a read's class taken from cpecan_hip_plan_dispatch in CPECAN_MODE_EXPECTATIONS under the
+ * flags this library passes for an E-step of the machine (the environment's switches for the fused E-steps among them,
+ * CPECAN_VANILLA_FUSED_ESTEP, CPECAN_HDP_FUSED_ESTEP, ..., read once, when the stream is opened).
+ *
+ * `expectations` is what the single-read calls take for the machine of the first read: a ContinuousPairHmmExpectations *
+ * (strawMan), a VanillaHmmExpectations * (vanilla), an HdpHmmExpectations * (HDP) or an Hmm * (an HmmDiscrete, the
+ * 5-state machine).  These own what they hold, so the caller's sequences may go when submit returns.  The
+ * reference-shaped HdpHmm of getExpectationsUsingAnchors keeps pointers into the caller's sequences and therefore cannot
+ * be a stream's target.  The HDP assignment bar is the struct's `threshold`.  A 4-state or echelon read ends the process
+ * at submit with the batch call's refusal.
+ *
+ * The consumer waits for each chunk in the order the runs were queued, reads it into temporaries -- the chunk's models'
+ * sums added on the device in model order (cpecan_hip_batch_sum_expectations: one kernel, one copy), for the HDP machine
+ * also its assignments -- and adds them to the struct only when the whole readback has succeeded: a chunk that meets
+ * CPECAN_ELIMIT there is halved and run again, and has added nothing.  Given the chunks, the struct's sums are one fixed
+ * sequence of additions.  An HDP assignment's assignmentXY[3 * i + 2] is its read's tag, and a read's assignments stay
+ * in the order the call on that read alone gives.  onDone (which may be NULL) is called once per read after its chunk
+ * has been added or refused, never at the same time as onChunk.
+ *
+ * Between open and flush the struct belongs to the stream; after flush it holds everything delivered so far.  A refused
+ * read has added nothing to it. */
+typedef void (*cpecan_stream_done_fn)(void *arg, int64_t tag, bool refused);
+cpecan_stream *cpecan_stream_open_expectations(PairwiseAlignmentParameters *p, bool raggedL, bool raggedR,
+                                               const cpecan_stream_options *o, void *expectations,
+                                               cpecan_stream_done_fn onDone, cpecan_stream_chunk_fn onChunk, void *arg);
+/* Test hook: the class classify gives an E-step read of the machine (CPECAN_MACHINE_*) whose widest band is maxWidth
+ * k-mers: cpecan_hip_plan_dispatch asked with what expectations_request, the create calls' one source, gives now.
+ * Returns the C-ABI's code. */
+int32_t cpecan_stream_expectations_class(int32_t machine, int32_t maxWidth, int32_t edgesStepByOne, int32_t *kernel,
+                                         int32_t *wave, int32_t *rows);
 /* Test hook: the chunking rule alone (csrc/host/cpecan_stream_plan.c), over n reads with classes classOf[i] and sizes
  * cells[i] and one cell budget.  chunkOf[i] receives read i's chunk, chunks numbered as they close, rankOf[i] its place
  * among that chunk's reads; returns the number of chunks. */

@@ -784,6 +784,14 @@ int cpecan_hip_batch_fetch_totals(cpecan_batch *batch, int64_t item, int64_t *xa
 #define CPECAN_EXPECTATIONH_LEN (9 + 1)
 int cpecan_hip_batch_expectations_device_ptr(cpecan_batch *batch, void **dev_ptr, int64_t *n_doubles);
 int cpecan_hip_batch_fetch_expectations(cpecan_batch *batch, int32_t model_id, double *out);
+/* The batch's per-model blocks added up on the device: out[i], for the expectation length of the batch's machine (the
+ * CPECAN_EXPECTATION*_LEN above), is block 0's value plus block 1's plus ... in ascending model id, in fp64 -- bit for
+ * bit the left-to-right host sum of what cpecan_hip_batch_fetch_expectations returns for ids 0 .. n_models - 1 (no
+ * reassociation, no tree, no atomics: the order is the contract).  One kernel behind the run's end event, one copy, one
+ * wait, however many models the batch has.  The result buffer (that many doubles) is allocated on the batch's account
+ * at the first call: CPECAN_ELIMIT where the context's memory limit refuses it, and the call can be made again once
+ * there is room.  CPECAN_EINVAL for a batch that was not created for an E-step. */
+int cpecan_hip_batch_sum_expectations(cpecan_batch *batch, double *out);
 /* Debug: forward cells and backward cells (as they stand when posteriors are taken) of an item,
  * [cell][state] with cells ordered by diagonal then x-y; needs CPECAN_FLAG_DEBUG_DUMP. */
 int cpecan_hip_batch_debug_cells(cpecan_batch *batch, int64_t item, double *forward,
