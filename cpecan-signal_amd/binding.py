@@ -44,6 +44,7 @@ FLAG_WIDE_BANDS_VANILLA_FUSED_ESTEP = 32768
 FLAG_HDP_FUSED_ESTEP = 65536
 FLAG_WIDE_BANDS_HDP_FUSED_ESTEP = 131072
 FLAG_HDP_FOUR_CELLS_FUSED_ESTEP = 262144
+FLAG_SM4_WAVE = 524288
 MACHINE_STRAWMAN, MACHINE_DNA5, MACHINE_VANILLA, MACHINE_HDP, MACHINE_SM4, MACHINE_ECHELON = range(6)
 NUM_KMERS = 4096
 MODEL_TABLE_LEN = 1 + NUM_KMERS * 5
@@ -576,6 +577,7 @@ class Batch:
         self.vanilla = bool(vanilla) and not self.dna
         self.hdp = bool(hdp) and not self.dna
         self.echelon = bool(echelon) and not self.dna
+        self.sm4 = bool(sm4) and not self.dna and not self.hdp and not self.echelon
 
     def run(self, after=None):
         """after: a Batch that has run (usually of another context): this batch's kernels are ordered behind its last
@@ -612,6 +614,13 @@ class Batch:
         _check(lib().cpecan_hip_batch_stage_ms(self.h, C.byref(f), C.byref(k), C.byref(n)))
         return f.value, k.value, n.value
 
+    def kernel_family(self):
+        """dict(wave=...): 1 on the wave-per-alignment kernels (a DNA or 4-state batch: its machine's one-wave kernel),
+        0 on the workgroup-per-alignment or general ones; the C-ABI refuses a general batch of another machine"""
+        f = C.c_int32()
+        _check(lib().cpecan_hip_batch_kernel_family(self.h, C.byref(f)))
+        return dict(wave=f.value)
+
     def info(self):
         k, w, m = C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().cpecan_hip_batch_info(self.h, C.byref(k), C.byref(w), C.byref(m)))
@@ -624,6 +633,8 @@ class Batch:
             _check(lib().cpecan_hip_batch_kernel_family(self.h, C.byref(f)))
             if f.value:
                 out["family"] = "wave (5-state)"
+        if self.sm4 and self.kernel_family()["wave"]:
+            out["family"] = "wave (4-state)"
         if k.value == KERNEL_SYSTOLIC:
             r = C.c_int32()
             _check(lib().cpecan_hip_batch_systolic_rows(self.h, C.byref(r)))

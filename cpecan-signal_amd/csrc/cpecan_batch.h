@@ -36,6 +36,7 @@ struct cpecan_batch {
     DevBuf<char> chars, charsY; /* charsY: DNA batches (5-state machine) */
     Machine machine = STRAWMAN;
     bool wave5 = false; /* a DNA batch on the 5-state machine's wave kernels (choose_dispatch) */
+    bool wave4 = false; /* a 4-state batch on that machine's wave kernels (CPECAN_FLAG_SM4_WAVE, choose_dispatch) */
     DevBuf<double> logNoise; /* vanilla and echelon batches: log(event noise), host libm */
     DevBuf<double> duration; /* echelon batches: per event the duration terms of 0..5 k-mers, host libm */
     DevBuf<long long> xEnd;  /* echelon batches: per item the X characters that belong to its sequence */

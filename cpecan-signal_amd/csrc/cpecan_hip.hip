@@ -238,6 +238,7 @@ struct Dispatch {
                                expectation kernel (cpecan_hip_batch_expectation_pass) */
     int expectResweep = 0;  /* ... and its DevParams::expectResweep */
     bool wave5 = false;     /* the 5-state machine's wave kernels (cpecan_kernel_wave5.hip) in place of the general one */
+    bool wave4 = false;     /* the 4-state machine's wave kernels (cpecan_kernel_wave4.hip) in place of the general one */
     bool asmPlan = false;   /* the hand-scheduled assembly sweeps may take the batch, as far as the bands do not matter */
     bool asmSweeps = false; /* ... and with its bands; what is left is known at set-up (one stream group, the module) */
     bool asmBackward = false; /* ... both sweeps (CPECAN_ASM=1: the forward sweep only) */
@@ -275,6 +276,7 @@ static const struct FusedStandIn {
     { &cpecan_systolic_build_he8, &cpecan_systolic_build_hf8, CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP, nullptr },
 };
 #define CP_WAVE5_MAX_WIDTH 192 /* cells: one to three per lane */
+#define CP_WAVE4_MAX_WIDTH 128 /* cells: one or two per lane */
 static Dispatch choose_dispatch(const DispatchQuery &q) {
     const MachineRow &m = MACHINES[q.machine];
     const bool unbanded = (q.flags & CPECAN_FLAG_UNBANDED) != 0, debug = (q.flags & CPECAN_FLAG_DEBUG_DUMP) != 0;
@@ -287,7 +289,7 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
     };
     /* the HDP and vanilla machines have wave-per-alignment kernels of their own, for the posterior decode and for the
      * E-step, and CPECAN_FLAG_GENERAL_KERNEL keeps such a batch on the general kernel; the 5-state, 4-state and
-     * echelon machines have no register-resident kernels */
+     * echelon machines have none among the sweep builds (the one-wave kernels of the first two are chosen at the end) */
     /* the reference scores a k-mer that is none as NaN under the vanilla machine, and NaN spreads through its logAdd;
      * cpecan_k_generalv adds as the reference does, the register-resident kernels' branch-free logAdd (v_max / v_min)
      * drops a NaN operand: such a batch runs on the general kernel */
@@ -359,6 +361,10 @@ static Dispatch choose_dispatch(const DispatchQuery &q) {
     }
     d.wave5 = q.machine == DNA5 && !debug && !unbanded && q.maxWidth <= CP_WAVE5_MAX_WIDTH && !q.env.wave5Off &&
               !(q.flags & CPECAN_FLAG_GENERAL_KERNEL);
+    /* the 4-state machine's wave kernels are opt-in, by the flag alone (no environment variable), posterior decode on
+     * banded matrices; a wider band runs on the general kernel, as every 4-state batch without the flag does */
+    d.wave4 = q.machine == SM4 && q.mode == CPECAN_MODE_POSTERIOR && (q.flags & CPECAN_FLAG_SM4_WAVE) && !debug && !unbanded &&
+              q.maxWidth <= CP_WAVE4_MAX_WIDTH && !(q.flags & CPECAN_FLAG_GENERAL_KERNEL);
     return d;
 }
 
@@ -867,6 +873,7 @@ static cpecan_batch *new_batch(cpecan_ctx *c, Machine machine, const BatchInput 
     b->machine = machine;
     b->kernel = d.kernel;
     b->wave5 = d.wave5;
+    b->wave4 = d.wave4;
     b->maxWidth = plan.maxWidth;
     b->compactPairs = plan.maxLXY + m.xReach < 65536;
     b->nModels = c->tables[machine].n;
@@ -1264,6 +1271,10 @@ int cpecan_hip_batch_kernel_family(cpecan_batch *b, int32_t *wave) {
         *wave = b->wave5 ? 1 : 0;
         return CPECAN_OK;
     }
+    if (b->machine == SM4) { /* the 4-state machine likewise (cpecan_kernel_wave4.hip, CPECAN_FLAG_SM4_WAVE) */
+        *wave = b->wave4 ? 1 : 0;
+        return CPECAN_OK;
+    }
     if (b->kernel != CPECAN_KERNEL_SYSTOLIC) return fail(CPECAN_EINVAL, "not a register-resident batch");
     *wave = b->sy->wave ? 1 : 0;
     return CPECAN_OK;
@@ -1315,7 +1326,7 @@ int cpecan_hip_plan_dispatch(int32_t machine, int32_t mode, int32_t kernel, int3
     const int rc = plan_query(machine, mode, kernel, flags, maxWidth, edgesStepByOne, &early, &d);
     if (rc != CPECAN_OK) return rc;
     if (kernelOut) *kernelOut = d.kernel;
-    if (waveOut) *waveOut = d.wave5 || (d.build && d.build->wave) ? 1 : 0;
+    if (waveOut) *waveOut = d.wave5 || d.wave4 || (d.build && d.build->wave) ? 1 : 0;
     if (rowsOut) *rowsOut = d.build ? d.build->rows : 0;
     if (buildMaxWidthOut) *buildMaxWidthOut = d.build ? d.build->maxWidth : 0;
     return CPECAN_OK;

@@ -1,6 +1,6 @@
 /*
  * cpecan_run.hip -- how a run of a batch is queued: the lanes a chain of batches runs on, the launchers of the three
- * kinds of kernels (the 5-state wave kernels, the general kernels, the throughput kernels' sweeps with their event
+ * kinds of kernels (the 5-state and 4-state wave kernels, the general kernels, the throughput kernels' sweeps with their event
  * schedule), cpecan_hip_batch_run / _run_after and what a caller asks of a run afterwards (its end, its times, the
  * sweeps' clock).  Which kernels the batch runs on was settled when it was created (choose_dispatch, cpecan_hip.hip);
  * what a finished run gives back: cpecan_readback.hip.  Host code: it defines no kernel.
@@ -15,6 +15,8 @@
 #include <new>
 
 extern "C" __global__ void cpecan_k_generale(DevGeneralArgs, DevParams, DevEchelonArgs);
+extern "C" __global__ void cpecan_k_wave4_l1(DevGeneralArgs, DevParams);
+extern "C" __global__ void cpecan_k_wave4_l2(DevGeneralArgs, DevParams);
 #define W5_DECLARE(L)                                                                                             \
     extern "C" __global__ void cpecan_k_wave5_l##L(const DevItem *, DevParams, const int *, const int *,          \
                                                    const long long *, const char *, const char *, const double *, \
@@ -97,17 +99,33 @@ static int enqueue_wave5(cpecan_batch *b, hipStream_t st) {
     return CPECAN_OK;
 }
 
-/* The general kernels (cpecan_general.h): one per machine, one parameter list filled from the machine's row */
-static int enqueue_general(cpecan_batch *b, hipStream_t st) {
-    cpecan_ctx *c = b->ctx;
+/* what the general kernels are handed, filled from the machine's row */
+static DevGeneralArgs general_args(const cpecan_batch *b) {
+    const cpecan_ctx *c = b->ctx;
     const MachineRow &m = MACHINES[b->machine];
     const bool em = b->mode == CPECAN_MODE_EXPECTATIONS;
     const void *x = m.x == X_CHARS ? (const void *) b->chars.p : m.x == X_KID ? (const void *) b->kid.p : (const void *) b->kidx.p;
     const void *y = m.x == X_CHARS ? (const void *) b->charsY.p : (const void *) b->events.p; /* (nucleotides on both sides) */
-    DevGeneralArgs a = { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
-                         (const long long *) b->cellPrefix.p, x, y, m.yAux ? (const double *) b->logNoise.p : nullptr,
-                         c->tables[b->machine].block.p, b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p,
-                         b->totVal.p, b->nTot.p, b->dbgB.p, em ? b->expect.p : nullptr };
+    return { (const DevItem *) b->items.p, (const int *) b->bandL.p, (const int *) b->bandR.p,
+             (const long long *) b->cellPrefix.p, x, y, m.yAux ? (const double *) b->logNoise.p : nullptr,
+             c->tables[b->machine].block.p, b->Fstore.p, b->Bstore.p, b->pairs.p, b->pairLogp.p, b->nPairs.p, b->totXay.p,
+             b->totVal.p, b->nTot.p, b->dbgB.p, em ? b->expect.p : nullptr };
+}
+
+/* The 4-state machine for bands a wave covers in one or two cells per lane (CPECAN_FLAG_SM4_WAVE): one wave per
+ * alignment, the recurrence in registers (cpecan_kernel_wave4.hip), on the general kernel's buffers */
+static int enqueue_wave4(cpecan_batch *b, hipStream_t st) {
+    const DevGeneralArgs a = general_args(b);
+    hipLaunchKernelGGL(b->maxWidth <= 64 ? cpecan_k_wave4_l1 : cpecan_k_wave4_l2, dim3((unsigned) b->nItems), dim3(64), 0, st, a,
+                       b->P);
+    HIP_TRY(hipGetLastError());
+    return CPECAN_OK;
+}
+
+/* The general kernels (cpecan_general.h): one per machine, one parameter list */
+static int enqueue_general(cpecan_batch *b, hipStream_t st) {
+    const MachineRow &m = MACHINES[b->machine];
+    DevGeneralArgs a = general_args(b);
     DevParams P = b->P;
     /* the forward sweep's two previous diagonals live in LDS where the widest band fits (three diagonals of the
      * machine's states: 120 bytes per cell of width for the 5-state machine); CPECAN_GENERAL_LDS=0 keeps them in HBM
@@ -299,6 +317,8 @@ static int batch_enqueue(cpecan_batch *b, cpecan_batch *after, LaneSet *L) {
     HIP_TRY(hipEventRecord(b->ev1, L->fwd));
     if (b->wave5)
         rc = enqueue_wave5(b, L->fwd);
+    else if (b->wave4)
+        rc = enqueue_wave4(b, L->fwd);
     else if (b->kernel == CPECAN_KERNEL_GENERAL)
         rc = enqueue_general(b, L->fwd);
     else

@@ -864,6 +864,12 @@ static int32_t hdp_fused_estep_flags(void) {
            (fusedWide && atoi(fusedWide) == 1 ? CPECAN_FLAG_WIDE_BANDS_HDP_FUSED_ESTEP : 0) |
            (fusedFour && atoi(fusedFour) == 1 ? CPECAN_FLAG_HDP_FOUR_CELLS_FUSED_ESTEP : 0);
 }
+/* CPECAN_SM4_WAVE=1: every 4-state posterior batch on the one-wave-per-alignment kernels where its bands fit (at most
+ * 128 cells; a wider or un-banded batch runs on the general kernel with the flag as without it) */
+static int32_t sm4_wave_flag(void) {
+    const char *wave = getenv("CPECAN_SM4_WAVE");
+    return wave && atoi(wave) == 1 ? CPECAN_FLAG_SM4_WAVE : 0;
+}
 /* what every create call takes of the record; y: the events, or the characters of a DNA read */
 #define PACKED(r, y) (r)->items, (r)->nItems, (r)->chars, (r)->nX, (y), (r)->nY, (r)->anchors, (r)->nAnchors
 /* (one batch per call, or a chunk of a stream that is to fit a budget: the smaller footprint) */
@@ -875,7 +881,7 @@ static int32_t hdp_fused_estep_flags(void) {
 void posterior_request(const MachineRow *row, int32_t *kernel, int32_t *flags) {
     const HostMachine m = (HostMachine) (row - MACHINES);
     *kernel = m == HM_DNA5 || m == HM_SM4 || m == HM_ECHELON ? CPECAN_KERNEL_GENERAL : CPECAN_KERNEL_AUTO;
-    *flags = m == HM_STRAWMAN ? SM3_POSTERIOR_FLAGS : 0;
+    *flags = m == HM_STRAWMAN ? SM3_POSTERIOR_FLAGS : m == HM_SM4 ? sm4_wave_flag() : 0;
 }
 void expectations_request(const MachineRow *row, int32_t *kernel, int32_t *flags) {
     const HostMachine m = (HostMachine) (row - MACHINES);
@@ -884,7 +890,7 @@ void expectations_request(const MachineRow *row, int32_t *kernel, int32_t *flags
 }
 static int32_t request_flags(const Run *r) {
     int32_t kernel, flags;
-    if (r->mode && r->estepFlags) return *r->estepFlags;
+    if (r->requestFlags) return *r->requestFlags;
     if (r->mode) expectations_request(r->row, &kernel, &flags);
     else posterior_request(r->row, &kernel, &flags);
     return flags;
@@ -906,7 +912,7 @@ static int batch_hdp(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp
     return cpecan_hip_batch_create_hdp(ctx, PACKED(r, r->events), &own, unbanded_flag(r) | estep_flag(r) | request_flags(r), batch);
 }
 static int batch_sm4(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
-    return cpecan_hip_batch_create_sm4(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch);
+    return cpecan_hip_batch_create_sm4(ctx, PACKED(r, r->events), bp, unbanded_flag(r) | request_flags(r), batch);
 }
 static int batch_echelon(cpecan_ctx *ctx, const Run *r, const cpecan_band_params *bp, cpecan_batch **batch) {
     return cpecan_hip_batch_create_echelon(ctx, PACKED(r, r->events), bp, unbanded_flag(r), batch);

@@ -48,7 +48,8 @@ typedef struct {
     bool raggedL, raggedR;
     int mode, unbanded;
     void *hmmOut;
-    const int32_t *estepFlags; /* the stream: an E-step's flags as expectations_request gave them at open (NULL: ask now) */
+    const int32_t *requestFlags; /* the stream: the flags posterior_request / expectations_request gave at open, the ones its
+                                    reads were classed with (NULL: ask now) */
     const void *records; /* the stream: n model records of row->modelSize bytes, filled at submission (NULL: fill now) */
     /* dedupe_models: nModels structs of row->modelSize bytes, the state machine each was filled from */
     void *models;

@@ -218,7 +218,7 @@ static int chunk_prepare(cpecan_stream *s, Chunk *c) {
     }
     const Run r = { .n = c->n, .sMs = c->sMs, .sXs = c->sXs, .sYs = c->sYs, .anchorLists = c->anchorLists, .p = &s->p,
                     .raggedL = s->raggedL, .raggedR = s->raggedR, .records = c->records, .mode = s->mode,
-                    .hmmOut = s->expectations, .estepFlags = s->mode ? &s->reqFlags[s->row - MACHINES] : NULL };
+                    .hmmOut = s->expectations, .requestFlags = &s->reqFlags[s->row - MACHINES] };
     c->run = r;
     const double t0 = now_ms();
     size_inputs(&c->run);
@@ -249,7 +249,7 @@ static void report_chunk(cpecan_stream *s, Chunk *c) {
         if (info.kernel == CPECAN_KERNEL_SYSTOLIC) {
             CHECK(cpecan_hip_batch_kernel_family(c->batch, &info.wave));
             CHECK(cpecan_hip_batch_systolic_rows(c->batch, &info.rows));
-        } else if (s->row == &MACHINES[HM_DNA5])
+        } else if (s->row == &MACHINES[HM_DNA5] || s->row == &MACHINES[HM_SM4]) /* (their one-wave kernels) */
             CHECK(cpecan_hip_batch_kernel_family(c->batch, &info.wave));
     }
     /* what a cell of this class costs, for the chunks of the class that close from now on */

@@ -586,6 +586,30 @@ typedef struct {
                                           C-ABI sets it; libcpecan_host.so sets it for its HDP batches of expectations
                                           when CPECAN_HDP_FOUR_CELLS_FUSED_ESTEP=1 (the way in for
                                           cpecan_getHdpExpectationsUsingAnchors, cpecan_trainModels and vanillaAlign). */
+#define CPECAN_FLAG_SM4_WAVE 524288 /* cpecan_hip_batch_create_sm4 only: a banded batch whose widest band is at most 128
+                                          cells (no CPECAN_FLAG_UNBANDED, no CPECAN_FLAG_GENERAL_KERNEL) runs on the
+                                          one-wave-per-alignment kernels of the 4-state machine, cpecan_k_wave4_l1
+                                          for bands up to 64 cells at one cell per lane, cpecan_k_wave4_l2 for 65..128
+                                          at two:
+                                          the recurrence in registers, one lane shift per diagonal, the traceback
+                                          windows swept back in the same launch (cpecan_kernel_wave4.hip), in place of
+                                          cpecan_k_general4's workgroup per alignment with its diagonals in HBM behind
+                                          a barrier.  Band edges may step by any number of k-mers.  Totals, exponents
+                                          and pairs are the general kernel's bit for bit; buffers, readback, chaining
+                                          and the threshold-0 re-run are those of any batch.  A wider or un-banded
+                                          batch with the flag runs on cpecan_k_general4 as without it.
+                                          cpecan_hip_plan_dispatch and cpecan_hip_batch_kernel_family report such a
+                                          batch as they report a DNA batch on the 5-state wave kernels: kernel GENERAL,
+                                          wave 1, rows 0; cpecan_hip_batch_info keeps saying general.  Every other
+                                          machine ignores the flag.  Opt-in: without it nothing changes.  No
+                                          environment variable of the C-ABI sets it; libcpecan_host.so sets it for its
+                                          4-state posterior batches when CPECAN_SM4_WAVE=1 (the way in for
+                                          getAlignedPairsUsingAnchors with a fourState machine, vanillaAlign --fourState
+                                          and the stream).  As measured (2 000 k-mers x 4 000 events, the two ways run in
+                                          turn on one box): 1.50 x the general kernel at 1024
+                                          alignments with the driver's diagonalExpansion of 50 (widest band 105: 69.1
+                                          against 103.4 ms) and 2.25 x at a band of 63 (37.1 against 83.3 ms); 2.58 x
+                                          and 3.70 x at 4096 alignments (168.3 against 434.7 ms, 93.4 against 345.5). */
 
 /* Copies the inputs to HBM and builds per-item band tables.  All host pointers may be released
  * after the call returns. */
@@ -730,7 +754,8 @@ int cpecan_hip_batch_systolic_rows(cpecan_batch *batch, int32_t *rows);
 /* Register-resident path only: *wave = 1 if the batch runs on the wave-per-alignment kernels (rows is then the
  * number of cells a lane holds: 2, 3 or 4), 0 on the workgroup-per-alignment ones (rows = waves per workgroup).  For a
  * DNA batch: 1 if its posterior decode runs on the one-wave-per-alignment 5-state kernel (bands up to 192 cells), 0 if
- * on the general one. */
+ * on the general one.  For a 4-state batch: 1 if it runs on the one-wave-per-alignment 4-state kernel
+ * (CPECAN_FLAG_SM4_WAVE, bands up to 128 cells), 0 if on the general one. */
 int cpecan_hip_batch_kernel_family(cpecan_batch *batch, int32_t *wave);
 /* *sweeps = 1 if the batch's sweeps run on the hand-scheduled assembly kernels (strawMan machine, posterior decode,
  * bands of 121..158 k-mers: the BASELINE configs[2] shape; with CPECAN_FLAG_ASM_NARROW_BANDS also bands of at most 120),
